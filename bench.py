@@ -3,7 +3,7 @@
 GPU (BASELINE.json configs[1]) -- one pass of the hot path (forward, backward,
 global-norm clip, Adam) over one synthetic batch per step, inputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU, RCCL all-reduce of the gradient buckets overlapped with
 backward; weak scaling = 512 samples per GPU.  Either the driver launches the ranks
@@ -12,12 +12,19 @@ backward; weak scaling = 512 samples per GPU.  Either the driver launches the ra
 as a CHILD process before it touches the GPU (a process that has initialised the GPU is
 never re-exec'ed) and forwards rank 0's JSON line.
 
-Prints ONE JSON line (rank 0) with the `roofline` of the dominant kernel (the
+Prints ONE JSON line (rank 0): the headline (`metric`, `value` in samples/s, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`) and the `roofline` of the dominant kernel (the
 v_linear_v forward GEMM, timed with HIP events on its own stream inside the timed
-region) plus what the WHOLE step achieves (`roofline.step`: 356 GFLOP over the step time)
-and where its time goes (`roofline.groups`: big GEMMs / recurrence / K = 300 GEMMs / small FCs /
+region) plus what the WHOLE step achieves (`roofline.step`: 356 GFLOP over the step time).
+A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs of the last
+step when --dump-outputs DIR is given (dump_outputs), the line.
+
+--full adds everything that takes passes of its own, after the timed region (each
+--no-* option still drops its part): where the step's time goes
+(`roofline.groups`: big GEMMs / recurrence / K = 300 GEMMs / small FCs /
 HBM-bound kernels, each with its algorithmic work and fraction of its own peak, measured in a
-separate pass after the timed region), a `cpu_baseline` (torch-CPU port of the same step on
+separate pass after the timed region) and the shader clock under it (`roofline.clock`), the
+bf16 x 3 experiment (`experiment_bf16x3`), a `cpu_baseline` (torch-CPU port of the same step on
 the host cores, N = 1 only), the extractor throughput `vfeat`, the end-to-end leg `e2e`
 (BASELINE configs[2]; with N ranks = configs[3]: every rank extracts its own 256 images, no
 collective, and trains on them with the bucketed gradient all-reduce) and the cfg-5 pre-training
@@ -57,6 +64,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-groups", action="store_true")
     ap.add_argument("--no-bf16x3", action="store_true")
     ap.add_argument("--probe", type=str, default="v_linear_v.fwd_gemm")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the group / clock passes, the bf16x3 experiment, the vfeat, e2e "
+                         "and pretrain legs and the CPU baseline (the --no-* options drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -115,6 +127,10 @@ def synth_batches(cfg, g, device, n_batches, B=None, N=None):
     B = B or cfg["B"]
     N = N or cfg["N_img"]
     T, A = cfg["T"], cfg["A"]
+    # Question tokens: uniform over the vocabulary, every id at most once per batch.  The embedding gradient is scatter-
+    # added with float atomics; with one addend per row no summation order exists, so a step -- and the whole run, which
+    # Adam would otherwise carry last-bit differences through -- computes the same bits every time.
+    assert B * T <= cfg["Vq"] - 3, "too few vocabulary ids for distinct tokens"
     batches = []
     scores = torch.tensor([0.3, 0.6, 0.9, 1.0], device=device)
     for _ in range(n_batches):
@@ -126,7 +142,7 @@ def synth_batches(cfg, g, device, n_batches, B=None, N=None):
             tgt[torch.arange(B, device=device)[use], ids[use]] = sc[use]
         batches.append({
             "image_idx": torch.randint(0, N, (B,), generator=g, device=device, dtype=torch.int64),
-            "q_intseq": torch.randint(0, cfg["Vq"] - 3, (B, T), generator=g, device=device, dtype=torch.int32),
+            "q_intseq": torch.randperm(cfg["Vq"] - 3, generator=g, device=device)[:B * T].view(B, T).to(torch.int32),
             "q_intseq_len": torch.full((B,), T, dtype=torch.int32, device=device),
             "answer_target": tgt,
         })
@@ -550,6 +566,43 @@ def groups_pass(eng, lib, batches, cfg, rank, steps=10):
     return groups, step_us
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger variable or gradient
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the last timed train step handed its caller, one DIR/<name>.npy each -- `report` (the 13 report
+    scalars, float64), `logit` [B, A] and `pred` [B] (float32), and for every trainable variable its value after the Adam
+    update (`param.<name>`) and its gradient (`grad.<name>`), float32, '/' of the variable name written as '.'.  A variable
+    of more than DUMP_SAMPLE elements is written as a sample of that many flat positions in ascending order, drawn from a
+    seed derived from its name: the same positions in every run.  About 46 MB at the benchmark's shape.  With the same
+    arguments two runs of one build write the same bits (seeded inputs, distinct tokens per batch: synth_batches)."""
+    import zlib
+    import numpy as np
+    import torch
+    eng.check_recurrence()
+    B, A = eng.dims.B, eng.dims.A
+    arrays = {"report": eng.tensor("report")[:13].cpu().numpy().astype(np.float64),
+              "logit": eng.tensor("logit")[:B * A].view(B, A).cpu().numpy(),
+              "pred": eng.tensor("pred")[:B].cpu().numpy().astype(np.float32)}
+    for name in eng.train_names:
+        key = name.replace("/", ".")
+        p, g = eng.params[name].reshape(-1), eng.grads[name].reshape(-1)
+        if p.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            sel = torch.from_numpy(np.sort(rng.choice(p.numel(), DUMP_SAMPLE, replace=False))).to(p.device)
+            p, g = p[sel], g[sel]
+        arrays["param." + key] = p.cpu().numpy()
+        arrays["grad." + key] = g.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "dump of %d bytes exceeds %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (key, a.dtype)
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+    return total
+
+
 def main():
     argv = sys.argv[1:]
     args = parse_args(argv)
@@ -650,16 +703,18 @@ def main():
     loss = eng.report()["answer_train_loss"]
     assert np.isfinite(loss), "training diverged"
     n_grad_floats = eng.grad_flat.numel()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
     groups, groups_step_us, clock = (None, None, None)
-    if not args.no_groups:
+    if args.full and not args.no_groups:
         groups, groups_step_us = groups_pass(eng, lib, batches, cfg, rank)
         if world == 1:
             clock = clock_pass(eng, lib, batches, rank, dt / args.steps * 1e3)
     # EXPERIMENT leg (never the headline): the same step with the big whole-tile GEMMs on the bf16 matrix pipe through
     # three-way operand splits (csrc/gemm_bf16x3.hip) -- an opt-in numerics mode whose products are f32-equivalent
     bf16x3 = None
-    if not args.no_bf16x3 and world == 1:
+    if args.full and not args.no_bf16x3 and world == 1:
         _lib.check(lib.vqa_gemm_bf16x3_set_mode(1), "vqa_gemm_bf16x3_set_mode")
         try:
             for i in range(3):
@@ -687,13 +742,13 @@ def main():
     legs = {}
     del eng
     torch.cuda.empty_cache()
-    if not args.no_vfeat:
+    if args.full and not args.no_vfeat:
         legs["vfeat"] = vfeat_bench(device, world=world)
         torch.cuda.empty_cache()
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         legs["e2e"] = e2e_bench(device, params, world=world, rank=rank)
         torch.cuda.empty_cache()
-    if not args.no_pretrain:
+    if args.full and not args.no_pretrain:
         legs["pretrain"] = pretrain_bench(device, world=world, rank=rank)
         torch.cuda.empty_cache()
 
@@ -771,7 +826,7 @@ def main():
             out["allreduce_exposed_ms_per_step"] = float(np.mean(ex)) if len(ex) else None
             out["allreduce_bytes_per_step"] = int(n_grad_floats * 4)
         out.update(legs)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, table, nbox, am, batches[0], cfg)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -202,11 +202,14 @@ int vqa_gru_bwd_b(const float* drh, const float* h_prev, const float* r, float* 
 
 /* Whole recurrence with the gate math fused into the GEMM epilogues (2 launches per
  * step).  xp [T,B,3H] holds x_t*W_x + b for (r|u|c) and is read only; hs [T+1,B,H]
- * with hs[0] = initial state (zeros); tape r,u,c,rh [T,B,H]. */
+ * with hs[0] = initial state (zeros); tape r,u,c,rh [T,B,H].  Past a row's length
+ * (t >= len[b]) hs[t+1,b] = hs[t,b] bit for bit and the tape holds what the cell computes
+ * from the carried state: every element is written.  The backward forms other than
+ * vqa_gru_seq_bwd_live read r, u, c of finished rows too (multiplied by zero: they must be finite). */
 int vqa_gru_seq_fwd(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs, float* r,
                     float* u, float* c, float* rh, int T, int B, int H, void* stream);
 /* BPTT.  dh_T [B,H] = gradient wrt hs[T] (used as scratch afterwards); dxp [T,B,3H]
- * receives (dr_pre | du_pre | dc_pre); dh_scratch [B,H]. */
+ * receives (dr_pre | du_pre | dc_pre), exactly 0 for t >= len[b]; dh_scratch [B,H]. */
 int vqa_gru_seq_bwd(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len, const float* hs,
                     const float* r, const float* u, const float* c, float* dxp, float* dh_scratch, int T, int B,
                     int H, void* stream);
@@ -215,7 +218,9 @@ int vqa_gru_seq_bwd(float* dh_T, const float* Wg_h, const float* Wc_h, const int
  * live_rows[t] = #rows with len > t.  Step t runs on rows [0, live_rows[t]); finished rows are filled in
  * afterwards (state carried, r*h and pre-activation gradients zero) exactly as the masked recurrence leaves them
  * (tf.nn.dynamic_rnn(sequence_length=...), vlmap/modules.py:124-140).  Results are identical; the work shrinks
- * with the sequences still running. */
+ * with the sequences still running.  Tape past a row's length: rh = 0, r, u, c NOT written (the weight gradients
+ * read hs, rh and dxp only; vqa_gru_seq_bwd_live reads r, u, c of live rows only -- the other backward forms
+ * read them for every row and need the per-step forms' tape). */
 int vqa_gru_seq_fwd_live(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, const int32_t* live_rows,
                          float* hs, float* r, float* u, float* c, float* rh, int T, int B, int H, void* stream);
 int vqa_gru_seq_bwd_live(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
@@ -267,7 +272,8 @@ int vqa_gru_ws_set_form(int form);      /* tuning: 0 = sub-phase tails inside th
 int vqa_gru_ws_set_stamps(unsigned long long* dev_words);   /* timing study (tools/gru_tune.py); NULL = off */
 
 /* The same restricted to batch rows [row0, row0+rows): samples are independent, so disjoint
- * row windows may run concurrently on different streams. */
+ * row windows may run concurrently on different streams.  Rows outside the window are not touched (in
+ * dh_T and dh_scratch neither). */
 int vqa_gru_seq_fwd_rows(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs, float* r,
                          float* u, float* c, float* rh, int T, int B, int H, int row0, int rows, void* stream);
 int vqa_gru_seq_bwd_rows(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len, const float* hs,

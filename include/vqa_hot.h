@@ -67,7 +67,8 @@ int vqa_gru_unpack_dwx_bias(const float* dwx, float* gwg, float* gwc, float* gbg
 /* backward: dE[q[b,t],:] += dx[t,b,:] (dE must be zeroed by the caller);
  * the IndexedSlices gradient of the gather.  Float atomics by default (order of the adds, hence the last bit,
  * varies run to run -- as in the reference); after vqa_set_deterministic(1) an atomic-free, run-to-run bitwise
- * reproducible form is used for W <= 512 (about 30 us slower at bs 512). */
+ * reproducible form is used (about 30 us slower at bs 512; rows wider than 512 floats are summed in slices of 512
+ * columns, one pass each). */
 int vqa_set_deterministic(int on);   /* process-wide; every other kernel is deterministic already */
 int vqa_embed_bwd(const float* dx_tm, const int32_t* q, float* dE, int B, int T, int W, int Vq, void* stream);
 /* Same, skipping the zero-padded positions t >= len[b]: dynamic_rnn(sequence_length) makes their dx exactly
@@ -816,7 +817,8 @@ int vqa_tile_mul_bwd(const float* dx, const float* pl, float* dll, int B, int M,
 /* :205-211, 281-284 on the pairings' logits tz [B*M, ldz], IN PLACE: softmax over the answers a < cols with
  * train_mask[a] * exist_mask[a] > 0.5, marginal[b,a] = mean over the M pairings [B,cols] (0 for excluded answers),
  * ent_row[b] = sum_a marginal * log(marginal + 1e-8).  want_dz != 0: tz <- d loss / d logit with
- * coef = W_ENTROPY / global batch; otherwise tz <- the pairings' probabilities.  cols <= 4096. */
+ * coef = W_ENTROPY / global batch; otherwise tz <- the pairings' probabilities.  cols <= 4096.  With no selected answer
+ * the result is defined as 0: probabilities, marginal, ent_row and (want_dz) the gradient are all 0. */
 int vqa_marginal_entropy(float* tz, const float* train_mask, const float* exist_mask, float coef, float* marginal,
                          float* ent_row, int B, int M, int cols, int ldz, int want_dz, void* stream);
 /* explicit, reproducible stand-in for tf.random_normal(seed=123) (vqa/model_vlmap_answer_full.py:133): out[i] is a

@@ -104,6 +104,7 @@ __device__ __forceinline__ float block_red(float v, float (*red)[4], int& slot) 
 // The marginal-entropy regulariser on the pairings' logits tz [B * M, ldz] (in place):
 //   prob = softmax over the selected answers (sel[a] = train[a] * exist[a] > 0.5, a < cols) of every pairing
 //   marginal[b, a] = mean_m prob[(b, m), a];  ent_row[b] = sum_a marginal * log(marginal + 1e-8)
+//   no selected answer: prob, marginal, ent_row and dz are all 0 (the entropy of an empty distribution)
 //   want_dz: tz <- d loss / d logit = prob * (dprob - sum_a prob * dprob),
 //            dprob[a] = coef * (log(marginal + 1e-8) + marginal / (marginal + 1e-8)) / M;   otherwise tz <- prob
 // One workgroup per question; thread t owns columns t, t + 256, ... of every row (CPT of them in registers).
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void marginal_entropy_kernel(float* __restrict
             sm += v[i];
         }
         sm = block_red<false>(sm, red, slot);
-        const float inv = 1.f / sm;
+        const float inv = sm > 0.f ? 1.f / sm : 0.f;      // no selected answer: every probability 0 (not 0 * inf)
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const int c = t + 256 * i;

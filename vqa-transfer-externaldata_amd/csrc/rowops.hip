@@ -56,10 +56,10 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const float* __restrict_
 // Positions past a sequence's length (zero padding; their dx is exactly zero) are skipped when `len`
 // is given, so the padding id is not a hot row.
 constexpr int EMB_ROWS = 16;
-template <int NK>   // NK * 64 >= W
+template <int NK>   // NK * 64 >= W: the W columns starting at dx / dE of rows ld floats apart
 __global__ __launch_bounds__(256) void embed_bwd_owner_kernel(const float* __restrict__ dx, const int32_t* __restrict__ q,
                                                               const int32_t* __restrict__ len, float* __restrict__ dE,
-                                                              int B, int T, int W, int Vq, int nw_log2) {
+                                                              int B, int T, int W, int ld, int Vq, int nw_log2) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [4 waves][EMB_ROWS][NK * 64]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // wave w of nw_log2-many owns rows {w, w + NW, w + 2 NW, ...}: frequent words (small ids in a
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void embed_bwd_owner_kernel(const float* __res
                 float r[8][NK];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    const float* s = dx + ((int64_t)t * B + b0 + j[u]) * W;
+                    const float* s = dx + ((int64_t)t * B + b0 + j[u]) * ld;
 #pragma unroll
                     for (int k = 0; k < NK; ++k) r[u][k] = (u < cnt && lane + 64 * k < W) ? s[lane + 64 * k] : 0.f;
                 }
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void embed_bwd_owner_kernel(const float* __res
     }
     for (int rl = 0; rl < EMB_ROWS; ++rl) {
         if (!((touched >> rl) & 1u)) continue;
-        float* d = dE + (int64_t)(w + (rl << nw_log2)) * W;
+        float* d = dE + (int64_t)(w + (rl << nw_log2)) * ld;
         const float* a = acc + rl * NK * 64 + lane;
 #pragma unroll
         for (int k = 0; k < NK; ++k)
@@ -507,7 +507,7 @@ extern "C" int vqa_embed_bwd_len_det(const float* dx_tm, const int32_t* q, const
     if (B * T == 0) return VQA_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool det = deterministic < 0 ? g_deterministic != 0 : deterministic != 0;
-    if (!det || W > 512) {
+    if (!det) {
         // float atomics: the L2 serialises a frequent word's adds per address at ~10 ns each, so skew costs
         // little; the summation order (hence the last bit) varies from run to run, as it does in the reference
         hipLaunchKernelGGL(embed_bwd_kernel, dim3((B * T + 3) / 4), dim3(256), 0, st, dx_tm, q, len, dE, B, T, W, Vq);
@@ -517,30 +517,33 @@ extern "C" int vqa_embed_bwd_len_det(const float* dx_tm, const int32_t* q, const
     int nw_log2 = 0;
     while ((EMB_ROWS << nw_log2) < Vq) ++nw_log2;
     const int grid = ((1 << nw_log2) + 3) / 4;
-    if (W <= 320) {
-        auto kern = embed_bwd_owner_kernel<5>;
-        constexpr int lds = 4 * EMB_ROWS * 5 * 64 * (int)sizeof(float);     // 80 KiB > the 64 KiB default limit
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-                hipSuccess)
-                return VQA_ERR_LAUNCH;
-            attr = true;
+    static bool attr5 = false, attr8 = false;
+    // rows wider than 512 floats: one owner pass per slice of 512 columns (each slice's sums in the same fixed order)
+    for (int c0 = 0; c0 < W; c0 += 512) {
+        const int wc = std::min(512, W - c0);
+        if (wc <= 320) {
+            auto kern = embed_bwd_owner_kernel<5>;
+            constexpr int lds = 4 * EMB_ROWS * 5 * 64 * (int)sizeof(float);     // 80 KiB > the 64 KiB default limit
+            if (!attr5) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        lds) != hipSuccess)
+                    return VQA_ERR_LAUNCH;
+                attr5 = true;
+            }
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dx_tm + c0, q, len, dE + c0, B, T, wc, W, Vq, nw_log2);
+        } else {
+            auto kern = embed_bwd_owner_kernel<8>;
+            constexpr int lds = 4 * EMB_ROWS * 8 * 64 * (int)sizeof(float);     // 128 KiB
+            if (!attr8) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        lds) != hipSuccess)
+                    return VQA_ERR_LAUNCH;
+                attr8 = true;
+            }
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dx_tm + c0, q, len, dE + c0, B, T, wc, W, Vq, nw_log2);
         }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dx_tm, q, len, dE, B, T, W, Vq, nw_log2);
-    } else {
-        auto kern = embed_bwd_owner_kernel<8>;
-        constexpr int lds = 4 * EMB_ROWS * 8 * 64 * (int)sizeof(float);     // 128 KiB
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-                hipSuccess)
-                return VQA_ERR_LAUNCH;
-            attr = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dx_tm, q, len, dE, B, T, W, Vq, nw_log2);
+        VQA_CHECK_LAUNCH();
     }
-    VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
 extern "C" int vqa_embed_bwd(const float* dx_tm, const int32_t* q, float* dE, int B, int T, int W, int Vq,

@@ -617,6 +617,90 @@ int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pret
                                  int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Pre-training with a variable head set (csrc/pretrain_model.hip): the cfg-5 model above plus, per category, the
+ * enwiki-context head of vlmap_memft/model_vlmap_bf_or_wordset_enwiki_withatt_sp.py:519-624 -- enwiki_map embedding of
+ * the context [B,n,Lc] -> encode_L_enwiki (a second GRU W -> H, shared by both categories, lengths enwiki_context_len)
+ * -> the shared pooled_linear_l / q_linear_l / joint_fc (dropout 0.5) / classifier -> masked softmax-CE over the
+ * blank-fill fills.  Head sets:
+ *   VQA_PT_HEAD_BF | VQA_PT_HEAD_WS | VQA_PT_HEAD_EW   vlmap_bf_or_wordset_enwiki_withatt_sp
+ *   VQA_PT_HEAD_BF | VQA_PT_HEAD_EW                    vlmap_bf_enwiki_withatt_sp (wordset_map exists, its gradient is 0;
+ *                                                      no wordset_ft)
+ *   VQA_PT_HEAD_BF | VQA_PT_HEAD_WS                    the cfg-5 model again (same results as vqa_pretrain_*)
+ * Head h = 2 r + k: type of rank r among the enabled types (bf < ws < ew), category k (0 object, 1 attribute).  Without
+ * VQA_FLAG_SHARED_LN head h owns LayerNorm slot h of pooled_linear_l / q_linear_l / joint_fc (TF graph build order:
+ * `LayerNorm` ... `LayerNorm_5` with all three types, ... `LayerNorm_3` for bf | ew); with it every head uses slot 0.
+ * Named intermediates (vqa_pretrain_ext_tensor): those of vqa_pretrain_tensor with head names bf / ws / ew
+ * ("<obj|attr>/<bf|ws|ew>/{z,dz,stats,j,...}", "<obj|attr>/ew_state"), "E/{ctx_s,lens_s,x_tm,xp,hs,...}" for the
+ * context batch, "report" (3 * 2 * #types + 1 floats in the order of vqa_pretrain_ext_report_key(heads, i):
+ * for k in (obj, attr), for each enabled type in bf, ws, ew order: <kind>_<blank_fill|wordset|enwiki>_{loss, acc,
+ * top_5_acc}; then total_loss -- 19 keys with all three types, 13 for bf | ew).
+ * ------------------------------------------------------------------------ */
+#define VQA_PT_HEAD_BF 1
+#define VQA_PT_HEAD_WS 2
+#define VQA_PT_HEAD_EW 4
+typedef struct {
+    vqa_pretrain_dims_t base;                /* as for vqa_pretrain_* (n_ws > 0 even without the word-set head) */
+    int32_t heads;                           /* VQA_PT_HEAD_* mask, VQA_PT_HEAD_BF required */
+    int32_t Lc;                              /* padded context length (max_context_len of the dictionary: 7 for w3) */
+    int32_t n_ctx;                           /* context vocabulary (len(context_word_vocab)) */
+} vqa_pretrain_ext_dims_t;
+
+/* vqa_pt_fc_t with 6 LayerNorm slots (pooled_linear_l / q_linear_l / joint_fc are entered by up to 6 heads) */
+typedef struct { float *w, *b, *beta[6], *gamma[6]; } vqa_pt_fc6_t;
+
+typedef struct {
+    float* wordset_map;                      /* wordset_map/learn [n_ws,W] */
+    float* l_glove;                          /* L_GloVe/embed_map [Vq,W] */
+    float* enwiki_map;                       /* enwiki_map/learn [n_ctx,W] (NULL without VQA_PT_HEAD_EW) */
+    vqa_pt_fc6_t spat_v_linear_v;            /* [6,H]   LN x2 */
+    vqa_pt_fc6_t spat_q_linear_v;            /* [6,H]   LN x2 */
+    vqa_pt_fc6_t spat_att_score;             /* [H,1] */
+    float *gru_wg, *gru_bg, *gru_wc, *gru_bc;      /* encode_L_blank/rnn/gru_cell/{gates,candidate}/{kernel,bias} */
+    float *egru_wg, *egru_bg, *egru_wc, *egru_bc;  /* encode_L_enwiki/rnn/gru_cell/... [W+H,2H], [2H], [W+H,H], [H] */
+    vqa_pt_fc6_t pooled_linear_l;            /* [D,H]   LN x 2 * #types */
+    vqa_pt_fc6_t q_linear_l;                 /* [H,H]   LN x 2 * #types */
+    vqa_pt_fc6_t joint_fc;                   /* [H,2H]  LN x 2 * #types */
+    vqa_pt_fc6_t wordset_ft;                 /* [W,H]   LN x2 (all NULL without VQA_PT_HEAD_WS) */
+    vqa_pt_fc6_t classifier;                 /* [2H,A] */
+} vqa_pretrain_ext_params_t;
+
+typedef struct {                             /* the enwiki fields of one category (dataset_vlmap.py:84-126, 205-234) */
+    const int32_t* context;                  /* {obj,attr}_blank_fill/enwiki_context [B,n,Lc], zero padded */
+    const int32_t* context_len;              /* {obj,attr}_blank_fill/enwiki_context_len [B,n], 1 .. Lc */
+    const uint8_t* keep_ew_joint;            /* [B*n,2H] 0/1 dropout keep-mask of the enwiki head's joint, or NULL */
+} vqa_pretrain_ctx_kind_t;
+
+typedef struct {
+    vqa_pretrain_batch_t base;               /* as for vqa_pretrain_* (wordsets / keep_ws_joint unused without WS) */
+    vqa_pretrain_ctx_kind_t ctx[2];          /* 0 = object, 1 = attribute */
+    /* the contexts of both categories as ONE batch of 2*B*n rows (object rows first), optionally in length order:
+     * device int32 [2*B*n] permutation / inverse and HOST int[Lc] live rows, as base.perm / inv / live_rows */
+    const int32_t *ctx_perm, *ctx_inv, *ctx_live_rows;
+} vqa_pretrain_ext_batch_t;
+
+int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims);
+int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes, int64_t* n_elems);
+/* report key i of head set `heads`; NULL past the last */
+const char* vqa_pretrain_ext_report_key(int heads, int i);
+int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
+                             const vqa_pretrain_ext_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                             void* stream);
+/* grads: same layout as params (every member the model has non-NULL; wordset_map always).  Overwritten; the three
+ * embedding tables are cleared and scatter-added.  Phases as vqa_pretrain_backward_phases, with the enwiki head's parts
+ * in the buckets that keep every data-parallel bucket contiguous:
+ *   1  stacked heads
+ *   2  BPTT of the caption batch, then of the context batch: encode_L_blank and encode_L_enwiki gradients
+ *   4  L_GloVe scatter-add, then enwiki_map scatter-add (both add to the slice sum of squares)
+ *   8  per category: wordset_ft / wordset_map (cleared with or without the word-set head), spatial attention;
+ *      writes slice_sq = the sum of squares of every un-aggregated embedding slice (captions, contexts, word sets) */
+int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
+                              const vqa_pretrain_ext_params_t* grads, const vqa_pretrain_ext_batch_t* batch, void* workspace,
+                              int64_t workspace_bytes, float* slice_sq, void* stream);
+int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
+                                     const vqa_pretrain_ext_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
+                                     void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+
+/* ------------------------------------------------------------------------
  * Region-feature extractor, NHWC fp32.
  * ------------------------------------------------------------------------ */
 /* conv + folded inference BatchNorm (+ residual) (+ ReLU):

@@ -1,4 +1,10 @@
-"""Throughput of the cfg-5 pre-training step (BASELINE configs[4], stage 1) at bs 512 on one MI355X."""
+"""Throughput of the cfg-5 pre-training step (BASELINE configs[4], stage 1) at bs 512 on one MI355X.
+
+`--model_type vlmap_bf_or_wordset_enwiki_withatt_sp | vlmap_bf_enwiki_withatt_sp` times that model instead and also
+prints the analytic MFMA FLOPs per step (flops_per_step) and the rate they give.  `--alternate` builds cfg-5 and the
+chosen model in one process and times their steps alternately (each warmed up first), so that both rates come from the
+same box and clocks.  Without options the output is the cfg-5 line as before."""
+import argparse
 import os
 import sys
 import time
@@ -13,6 +19,31 @@ if os.environ.get("VQA_HOT_LIB"):      # A/B of two builds of the library on one
 from vqa_transfer_externaldata_amd import pretrain as PT  # noqa: E402
 
 B, n, R, D, H, L, W, Vq, n_ws, A = 512, 5, 36, 2048, 1024, 10, 300, 5000, 2000, 4000
+N_CTX, LC = 5000, 7
+_ap = argparse.ArgumentParser()
+_ap.add_argument("steps", nargs="?", type=int, default=10)
+_ap.add_argument("--model_type", default="vlmap_bf_or_wordset_withatt_sp", choices=sorted(PT.MODEL_HEADS))
+_ap.add_argument("--alternate", action="store_true")
+ARGS = _ap.parse_args()
+
+
+def flops_per_step(heads, batch):
+    """Analytic MFMA FLOPs of one training step from the shapes (forward + dX + dW of every GEMM the step runs; the
+    recurrences and their x-projections over the tokens the batch actually holds, i.e. the live rows of the sorted
+    batch): per encoder 3 * 2 * tokens * (W + H) * 3H; pooled_linear_l over 2 B n rows; q_linear_l, joint_fc and the
+    classifier over 2 B n rows per head type; wordset_ft over 2 B n rows."""
+    Bn = B * n
+    tok = lambda key: int(sum(np.asarray(batch["%s_blank_fill/%s" % (k, key)]).sum() for k in PT.KINDS))
+    f = 3 * 2 * tok("blanks_len") * (W + H) * 3 * H
+    if "ew" in heads:
+        f += 3 * 2 * tok("enwiki_context_len") * (W + H) * 3 * H
+    f += 3 * 2 * (2 * Bn) * D * H
+    f += 3 * 2 * (2 * Bn * len(heads)) * (H * H + H * 2 * H + 2 * H * A)
+    if "ws" in heads:
+        f += 3 * 2 * (2 * Bn) * W * H
+    return float(f)
+
+
 rng = np.random.default_rng(0)
 p = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H)
 from vqa_transfer_externaldata_amd import dataset_vlmap as DV  # noqa: E402
@@ -23,7 +54,7 @@ sort_info = {} if os.environ.get("SORT", "1") == "0" else {k: v for k, v in PT.a
 eng = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p)
 db = {k: torch.from_numpy(v).cuda() for k, v in batch.items()}
 db.update(sort_info)
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+steps = ARGS.steps
 if any(os.environ.get(k) for k in ("VQA_LN_FAST", "VQA_GRU_CFG", "VQA_ATTN_FAST", "VQA_SOFTMAX_FAST")):   # A/B switches
     from vqa_transfer_externaldata_amd import _lib
     _l = _lib.load()
@@ -35,14 +66,52 @@ if any(os.environ.get(k) for k in ("VQA_LN_FAST", "VQA_GRU_CFG", "VQA_ATTN_FAST"
         _l.vqa_attn_set_fast(int(os.environ["VQA_ATTN_FAST"]))
     if os.environ.get("VQA_SOFTMAX_FAST"):
         _l.vqa_softmax_set_fast(int(os.environ["VQA_SOFTMAX_FAST"]))
+CFG5_TIMED = ARGS.model_type == "vlmap_bf_or_wordset_withatt_sp" or ARGS.alternate
 for i in range(3):
     eng.train_step(db, eng.make_keep_masks(B, int(os.environ.get("MASK_SEED", "1")), i), 1e-3)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-for i in range(steps):
+for i in range(steps if CFG5_TIMED else 0):
     eng.train_step(db, eng.make_keep_masks(B, int(os.environ.get("MASK_SEED", "1")), 3 + i), 1e-3)
 torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / steps
+dt = (time.perf_counter() - t0) / max(steps, 1)
 rep = eng.fetch_report()
-print("pretrain step %.2f ms  -> %.0f images/s (%.0f blank-fill entries/s); total_loss %.3f"
-      % (dt * 1e3, B / dt, 2 * B * n / dt, rep["total_loss"]))
+if CFG5_TIMED:
+    print("pretrain step %.2f ms  -> %.0f images/s (%.0f blank-fill entries/s); total_loss %.3f"
+          % (dt * 1e3, B / dt, 2 * B * n / dt, rep["total_loss"]))
+
+if ARGS.model_type != "vlmap_bf_or_wordset_withatt_sp" or ARGS.alternate:
+    heads = PT.MODEL_HEADS[ARGS.model_type]
+    f5 = flops_per_step(PT.CFG5_HEADS, batch)
+    runs = {"vlmap_bf_or_wordset_withatt_sp": (eng, db, f5)}
+    if "ew" in heads:
+        data = DV.synthetic_dataset(B, Vq, n_ws, A, R=R, D=D, max_len=L, seed=0, enwiki=dict(n_ctx=N_CTX, Lc=LC))
+        dse = DV.Dataset(split="train", data=data, seed=0, enwiki=True)
+        be = next(DV.create_ops(B, dse, is_train=True, shuffle=False))
+        be = {k: v for k, v in be.items() if v.dtype.kind in "fi" and k != "image_id"}
+        pe = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H, heads=heads, n_ctx=N_CTX)
+        ee = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=pe, heads=heads, n_ctx=N_CTX)
+        dbe = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
+        if os.environ.get("SORT", "1") != "0":
+            dbe.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
+        for i in range(3):
+            ee.train_step(dbe, ee.make_keep_masks(B, 1, i), 1e-3)
+        runs[ARGS.model_type] = (ee, dbe, flops_per_step(heads, be))
+    order = list(runs) if ARGS.alternate else [ARGS.model_type]
+    times = {k: [] for k in order}
+    for i in range(steps):
+        for k in order:
+            e, d, _ = runs[k]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.train_step(d, e.make_keep_masks(B, 1, 3 + steps + i), 1e-3)
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    for k in order:
+        e, d, f = runs[k]
+        ms = 1e3 * float(np.median(times[k]))
+        print("%s: step %.2f ms (median of %d)  flops_per_step %.3f TFLOP  -> %.1f TFLOP/s; total_loss %.3f"
+              % (k, ms, steps, f / 1e12, f / ms / 1e9, e.fetch_report()["total_loss"]))
+    if ARGS.alternate and len(order) == 2:
+        r = [runs[k][2] / np.median(times[k]) for k in order]
+        print("flop-rate ratio %s / cfg-5 = %.3f" % (order[1], r[1] / r[0]))

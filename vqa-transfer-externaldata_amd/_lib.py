@@ -83,6 +83,34 @@ class PtBatch(C.Structure):
                 ("perm", C.c_void_p), ("inv", C.c_void_p), ("live_rows", C.c_void_p)]
 
 
+PT_HEAD_BF, PT_HEAD_WS, PT_HEAD_EW = 1, 2, 4      # VQA_PT_HEAD_*
+
+
+class PtExtDims(C.Structure):
+    _fields_ = [("base", PtDims), ("heads", C.c_int32), ("Lc", C.c_int32), ("n_ctx", C.c_int32)]
+
+
+class PtFc6(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("beta", C.c_void_p * 6), ("gamma", C.c_void_p * 6)]
+
+
+class PtExtParams(C.Structure):
+    _fields_ = [("wordset_map", C.c_void_p), ("l_glove", C.c_void_p), ("enwiki_map", C.c_void_p),
+                ("spat_v_linear_v", PtFc6), ("spat_q_linear_v", PtFc6), ("spat_att_score", PtFc6)] + \
+               [(k, C.c_void_p) for k in ("gru_wg", "gru_bg", "gru_wc", "gru_bc", "egru_wg", "egru_bg", "egru_wc",
+                                          "egru_bc")] + \
+               [(k, PtFc6) for k in ("pooled_linear_l", "q_linear_l", "joint_fc", "wordset_ft", "classifier")]
+
+
+class PtCtxKind(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("context", "context_len", "keep_ew_joint")]
+
+
+class PtExtBatch(C.Structure):
+    _fields_ = [("base", PtBatch), ("ctx", PtCtxKind * 2), ("ctx_perm", C.c_void_p), ("ctx_inv", C.c_void_p),
+                ("ctx_live_rows", C.c_void_p)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol declared in include/vqa_hot.h
@@ -240,6 +268,15 @@ SIGNATURES = {
                                           C.POINTER(PtBatch), _P, _L, _P, _I, _P]),
     "vqa_fusion_backward": (_I, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), C.POINTER(Batch), _P, _L,
                                  _P, _P]),
+    "vqa_pretrain_ext_workspace_bytes": (_L, [C.POINTER(PtExtDims)]),
+    "vqa_pretrain_ext_tensor": (_I, [C.POINTER(PtExtDims), C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vqa_pretrain_ext_report_key": (C.c_char_p, [_I, _I]),
+    "vqa_pretrain_ext_forward": (_I, [C.POINTER(PtExtDims), C.POINTER(PtExtParams), C.POINTER(PtExtBatch), _P, _L, _I,
+                                      _P]),
+    "vqa_pretrain_ext_backward": (_I, [C.POINTER(PtExtDims), C.POINTER(PtExtParams), C.POINTER(PtExtParams),
+                                       C.POINTER(PtExtBatch), _P, _L, _P, _P]),
+    "vqa_pretrain_ext_backward_phases": (_I, [C.POINTER(PtExtDims), C.POINTER(PtExtParams), C.POINTER(PtExtParams),
+                                              C.POINTER(PtExtBatch), _P, _L, _P, _I, _P]),
 }
 
 ABI_VERSION = 5      # VQA_HOT_ABI_VERSION of include/vqa_hot.h

@@ -610,3 +610,518 @@ extern "C" int vqa_pretrain_backward(const vqa_pretrain_dims_t* dims, const vqa_
                                      int64_t workspace_bytes, float* slice_sq, void* stream) {
     return vqa_pretrain_backward_phases(dims, P, G, bt, workspace, workspace_bytes, slice_sq, 15, stream);
 }
+
+// ================================================================ pre-training with a variable head set
+// vlmap_memft/model_vlmap_bf_or_wordset_enwiki_withatt_sp.py (heads bf | ws | ew) and model_vlmap_bf_enwiki_withatt_sp.py
+// (bf | ew): the cfg-5 model above plus, per category, build_*_enwiki (:519-624) -- enwiki_map embedding of the answer's
+// Wikipedia context -> a second GRU (encode_L_enwiki, shared by both categories) -> the same shared fusion MLP and
+// classifier -> masked softmax-CE over the blank-fill fills.  Head h = 2 r + k for the type of rank r among the enabled
+// ones and category k, so its LayerNorm slot (without VQA_FLAG_SHARED_LN) is TF's build order; the stacked blocks hold
+// the 2 * (#types) heads.  The cfg-5 entry points above are untouched; this path reuses their helpers and kernels.
+namespace {
+
+const char* const HEAD_EXT[3] = {"bf", "ws", "ew"};
+const char* const TASK_EXT[3] = {"blank_fill", "wordset", "enwiki"};
+
+struct HeadSet {
+    int type[3] = {0, 0, 0};      // type of rank r (0 blank fill, 1 word set, 2 enwiki)
+    int rank[3] = {-1, -1, -1};   // rank of type t, -1 = not enabled
+    int nt = 0;
+    explicit HeadSet(int mask) {
+        for (int t = 0; t < 3; ++t)
+            if (mask & (1 << t)) { rank[t] = nt; type[nt++] = t; }
+    }
+    int nh() const { return 2 * nt; }
+};
+
+bool ext_dims_ok(const vqa_pretrain_ext_dims_t* d) {
+    if (d == nullptr || !dims_ok(&d->base)) return false;
+    if (!(d->heads & VQA_PT_HEAD_BF) || (d->heads & ~(VQA_PT_HEAD_BF | VQA_PT_HEAD_WS | VQA_PT_HEAD_EW))) return false;
+    return !(d->heads & VQA_PT_HEAD_EW) || (d->Lc > 0 && d->n_ctx > 0);
+}
+
+// report[3 i + j] (i = k * nt + r: the key order of vqa_pretrain_ext_report_key), report[3 nh] = sum of the losses
+struct ReportExtArgs { const float* stats[6]; const float* inv[6]; int rows, nh; };
+__global__ __launch_bounds__(256) void pretrain_ext_report_kernel(ReportExtArgs a, float* __restrict__ report) {
+    __shared__ float red[16];
+    __shared__ float loss[6];
+    for (int h = 0; h < a.nh; ++h) {
+        for (int j = 0; j < 3; ++j) {
+            float s = 0.f;
+            for (int i = threadIdx.x; i < a.rows; i += 256) s += a.stats[h][(int64_t)i * 4 + j];
+            s = block_sum(s, red);
+            if (threadIdx.x == 0) {
+                const float v = s * a.inv[h][0];
+                report[3 * h + j] = v;
+                if (j == 0) loss[h] = v;
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = loss[0];
+        for (int h = 1; h < a.nh; ++h) t += loss[h];
+        report[3 * a.nh] = t;
+    }
+}
+
+Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx) {
+    const vqa_pretrain_dims_t& d = dx.base;
+    const HeadSet hs(dx.heads);
+    Layout L;
+    const int64_t B = d.B, n = d.n, R = d.R, D = d.D, H = d.H, W = d.W, A = d.A, T = d.L, Bn = B * n, NH = hs.nh();
+    const int64_t Tc = hs.rank[2] >= 0 ? dx.Lc : 0;
+    L.add("S/pooled", 2 * Bn * D); L.add("S/vl_pre", 2 * Bn * H); L.add("S/lft", NH * Bn * H);
+    L.add("S/vl", NH * Bn * H); L.add("S/ll_pre", NH * Bn * H); L.add("S/ll", NH * Bn * H); L.add("S/jin", NH * Bn * H);
+    L.add("S/j_pre", NH * Bn * 2 * H); L.add("S/j", NH * Bn * 2 * H);
+    L.add("S/z", NH * Bn * A); L.add("S/dz", NH * Bn * A); L.add("S/stats", NH * Bn * 4);
+    for (int k = 0; k < 2; ++k) {
+        const std::string p = std::string(KIND[k]) + "/";
+        L.add(p + "key6", Bn * 6);
+        L.add(p + "v_pre", B * R * H); L.add(p + "v", B * R * H); L.add(p + "v_mean", B); L.add(p + "v_rstd", B);
+        L.add(p + "qv_pre", Bn * H); L.add(p + "qv", Bn * H); L.add(p + "qv_mean", B); L.add(p + "qv_rstd", B);
+        L.add(p + "att", Bn * R);
+        L.alias(p + "pooled", "S/pooled", k * Bn * D, Bn * D); L.alias(p + "vl_pre", "S/vl_pre", k * Bn * H, Bn * H);
+        L.add(p + "valid", Bn); L.add(p + "inv_valid", 4);
+        L.alias(p + "bf_state", "S/lft", k * Bn * H, Bn * H);
+        if (hs.rank[1] >= 0) {
+            L.add(p + "wse", Bn * W); L.add(p + "ws", Bn * W);
+            L.add(p + "wf_pre", Bn * H); L.alias(p + "wf", "S/lft", (2 * hs.rank[1] + k) * Bn * H, Bn * H);
+            L.add(p + "wf_mean", B); L.add(p + "wf_rstd", B);
+        }
+        if (hs.rank[2] >= 0) L.alias(p + "ew_state", "S/lft", (2 * hs.rank[2] + k) * Bn * H, Bn * H);
+        for (int r = 0; r < hs.nt; ++r) {
+            const std::string q = p + HEAD_EXT[hs.type[r]] + "/";
+            const int64_t h = 2 * r + k;
+            L.alias(q + "vl", "S/vl", h * Bn * H, Bn * H); L.add(q + "vl_mean", B); L.add(q + "vl_rstd", B);
+            L.alias(q + "ll_pre", "S/ll_pre", h * Bn * H, Bn * H); L.alias(q + "ll", "S/ll", h * Bn * H, Bn * H);
+            L.add(q + "ll_mean", B); L.add(q + "ll_rstd", B);
+            L.alias(q + "jin", "S/jin", h * Bn * H, Bn * H);
+            L.alias(q + "j_pre", "S/j_pre", h * Bn * 2 * H, Bn * 2 * H); L.alias(q + "j", "S/j", h * Bn * 2 * H, Bn * 2 * H);
+            L.add(q + "j_mean", B); L.add(q + "j_rstd", B);
+            L.alias(q + "z", "S/z", h * Bn * A, Bn * A); L.alias(q + "dz", "S/dz", h * Bn * A, Bn * A);
+            L.alias(q + "stats", "S/stats", h * Bn * 4, Bn * 4);
+        }
+    }
+    // captions (J/) and enwiki contexts (E/) of both categories, each one batch of 2 Bn rows, time-major
+    L.add("J/blanks_s", 2 * Bn * T); L.add("J/lens_s", 2 * Bn);
+    L.add("J/x_tm", T * 2 * Bn * x_stride(W)); L.add("J/xp", T * 2 * Bn * 3 * H); L.add("J/hs", (T + 1) * 2 * Bn * H);
+    L.add("J/gru_r", T * 2 * Bn * H); L.add("J/gru_u", T * 2 * Bn * H); L.add("J/gru_c", T * 2 * Bn * H);
+    L.add("J/gru_rh", T * 2 * Bn * H);
+    L.add("wx_cat", W * 3 * H); L.add("bx_cat", 3 * H); L.add("dwx_cat", x_stride(W) * 3 * H);
+    if (Tc > 0) {
+        L.add("E/ctx_s", 2 * Bn * Tc); L.add("E/lens_s", 2 * Bn);
+        L.add("E/x_tm", Tc * 2 * Bn * x_stride(W)); L.add("E/xp", Tc * 2 * Bn * 3 * H); L.add("E/hs", (Tc + 1) * 2 * Bn * H);
+        L.add("E/gru_r", Tc * 2 * Bn * H); L.add("E/gru_u", Tc * 2 * Bn * H); L.add("E/gru_c", Tc * 2 * Bn * H);
+        L.add("E/gru_rh", Tc * 2 * Bn * H);
+        L.add("E/wx_cat", W * 3 * H); L.add("E/bx_cat", 3 * H); L.add("E/dwx_cat", x_stride(W) * 3 * H);
+        L.add("E/d_state_s", 2 * Bn * H); L.add("E/dxp", Tc * 2 * Bn * 3 * H); L.add("E/dx", Tc * 2 * Bn * W);
+    }
+    L.add("report", 32);
+    L.add("d_j", NH * Bn * 2 * H); L.add("d_jpre", NH * Bn * 2 * H); L.add("d_jin", NH * Bn * H);
+    L.add("d_vl", NH * Bn * H); L.add("d_ll", NH * Bn * H); L.add("d_vlpre", NH * Bn * H); L.add("d_llpre", NH * Bn * H);
+    L.add("d_lft", NH * Bn * H); L.add("d_pooled", 2 * Bn * D);
+    L.add("d_state_s", 2 * Bn * H); L.add("d_hscratch", 2 * Bn * H);
+    L.add("dxp", T * 2 * Bn * 3 * H); L.add("dx", T * 2 * Bn * W);
+    L.add("d_wfpre", Bn * H); L.add("d_ws", Bn * W); L.add("d_wse", Bn * W);
+    L.add("d_v", B * R * H); L.add("d_vpre", B * R * H); L.add("d_qv", Bn * H); L.add("d_qvpre", Bn * H);
+    L.add("part_a", B * 2 * H); L.add("part_b", B * 2 * H); L.add("part_c", B * 2 * H);
+    L.add("part_dw", Bn * H); L.add("part_db", Bn);
+    L.add("sq", 16);
+    int64_t gw = 4;
+    auto g = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) {
+        gw = max64(gw, vqa_gemm_workspace_floats(tA, tB, (int)M, (int)N, (int)K, 0));
+    };
+    g(0, 0, B * R, H, 6); g(0, 0, Bn, H, 6); g(0, 0, Bn, H, W);
+    g(1, 0, 6, H, B * R); g(1, 0, 6, H, Bn); g(1, 0, W, H, Bn); g(0, 1, Bn, W, H);
+    for (const int64_t S : {T, Tc}) {        // the two recurrences' x-projection, its dW / dx and the h-row dW
+        if (S == 0) continue;
+        g(0, 0, S * 2 * Bn, 3 * H, W); g(1, 0, x_stride(W), 3 * H, S * 2 * Bn); g(0, 1, S * 2 * Bn, W, 3 * H);
+        g(1, 0, H, 2 * H, S * 2 * Bn); g(1, 0, H, H, S * 2 * Bn);
+    }
+    g(0, 0, 2 * Bn, H, D); g(0, 0, NH * Bn, H, H); g(0, 0, NH * Bn, 2 * H, H); g(0, 0, NH * Bn, A, 2 * H);
+    g(1, 0, 2 * H, A, NH * Bn); g(0, 1, NH * Bn, 2 * H, A); g(1, 0, H, 2 * H, NH * Bn); g(0, 1, NH * Bn, H, 2 * H);
+    g(1, 0, D, H, 2 * Bn); g(0, 1, 2 * Bn, D, H); g(1, 0, H, H, NH * Bn); g(0, 1, NH * Bn, H, H);
+    L.add("gemm_ws", gw);
+    int64_t cw = 4;
+    cw = max64(cw, vqa_colsum_workspace_floats((int)B, (int)(2 * H)));
+    cw = max64(cw, vqa_colsum_workspace_floats((int)(NH * Bn), (int)A));
+    cw = max64(cw, vqa_colsum_workspace_floats((int)Bn, (int)H));
+    cw = max64(cw, vqa_colsum_workspace_floats((int)B, (int)H));
+    cw = max64(cw, vqa_colsum_workspace_floats((int)Bn, 1));
+    L.add("colsum_ws", 3 * cw);
+    L.add("sumsq_ws", max64(max64(vqa_sumsq_workspace_floats(2 * T * Bn * W), vqa_sumsq_workspace_floats(2 * Tc * Bn * W)),
+                            max64(vqa_sumsq_workspace_floats(Bn * W), 4)));
+    return L;
+}
+
+// the first four LayerNorm slots of a 6-slot scope (scopes entered by at most 4 call sites)
+vqa_pt_fc_t fc4(const vqa_pt_fc6_t& f) {
+    vqa_pt_fc_t o{};
+    o.w = f.w; o.b = f.b;
+    for (int i = 0; i < 4; ++i) { o.beta[i] = f.beta[i]; o.gamma[i] = f.gamma[i]; }
+    return o;
+}
+
+// LayerNorm slot s of a 6-slot scope as slot 0 of a vqa_pt_fc_t (the stacked heads' per-slice LayerNorm)
+vqa_pt_fc_t fc_slot(const vqa_pt_fc6_t& f, int s) {
+    vqa_pt_fc_t o{};
+    o.w = f.w; o.b = f.b; o.beta[0] = f.beta[s]; o.gamma[0] = f.gamma[s];
+    return o;
+}
+
+std::string ext_report_key(int heads, int i) {
+    const HeadSet hs(heads);
+    if (i == 3 * hs.nh()) return "total_loss";
+    if (i < 0 || i > 3 * hs.nh()) return "";
+    const int h = i / 3, j = i % 3, k = h / hs.nt, r = h % hs.nt;
+    static const char* const SUFFIX[3] = {"_loss", "_acc", "_top_5_acc"};
+    return std::string(KIND[k]) + "_" + TASK_EXT[hs.type[r]] + SUFFIX[j];
+}
+
+}  // namespace
+
+extern "C" const char* vqa_pretrain_ext_report_key(int heads, int i) {
+    static std::vector<std::string> keys[8];        // built once per head set; the pointers stay valid
+    static const int init = [] {
+        for (int m = 0; m < 8; ++m)
+            if (m & VQA_PT_HEAD_BF)
+                for (int i = 0; i <= 3 * HeadSet(m).nh(); ++i) keys[m].push_back(ext_report_key(m, i));
+        return 0;
+    }();
+    (void)init;
+    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[heads].size()) return nullptr;
+    return keys[heads][i].c_str();
+}
+
+extern "C" int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
+    if (!ext_dims_ok(dims)) return VQA_ERR_ARG;
+    return make_layout_ext(*dims).total;
+}
+
+extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
+                                       int64_t* n_elems) {
+    if (!ext_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
+    const Layout L = make_layout_ext(*dims);
+    const Entry* e = L.find(name);
+    if (e == nullptr) return VQA_ERR_ARG;
+    if (offset_bytes) *offset_bytes = e->off;
+    if (n_elems) *n_elems = e->n;
+    return VQA_OK;
+}
+
+extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                        int want_dz, void* stream) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    const vqa_pretrain_dims_t* d = &dims->base;
+    const vqa_pretrain_batch_t* bt = &bx->base;
+    const HeadSet hs(dims->heads);
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, A = d->A, T = d->L, Bn = B * n;
+    const int64_t NH = hs.nh(), B2 = 2 * Bn;
+    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
+    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
+                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
+    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
+    if (hs.rank[2] >= 0)
+        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
+                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
+    ReportExtArgs ra{};
+    ra.rows = (int)Bn;
+    ra.nh = (int)NH;
+    ProbeScope ps_all("pretrain_ext.forward", c.st);
+    const vqa_pt_fc_t spat_v = fc4(P->spat_v_linear_v), spat_q = fc4(P->spat_q_linear_v), wft = fc4(P->wordset_ft);
+    TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
+    for (int k = 0; k < 2; ++k) {
+        const vqa_pretrain_kind_t& kb = bt->kind[k];
+        VQA_REQUIRE(kb.normal_boxes && kb.fills && kb.blanks && kb.blanks_len && kb.num, VQA_ERR_ARG);
+        const std::string p = std::string(KIND[k]) + "/";
+        ProbeScope ps_sp("pt.spatial_wordset.fwd", c.st);
+        hipLaunchKernelGGL(box6_kernel, dim3((unsigned)((Bn + 255) / 256)), dim3(256), 0, c.st, kb.normal_boxes,
+                           c.f(p + "key6"), (int)Bn);
+        VQA_CHECK_LAUNCH();
+        TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, spat_v, li(k), (int)R, 0, p + "v_pre", p + "v", p + "v_mean",
+                      p + "v_rstd", nullptr, 1.f));
+        TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, spat_q, li(k), (int)n, 0, p + "qv_pre", p + "qv", p + "qv_mean",
+                      p + "qv_rstd", nullptr, 1.f));
+        TRY(vqa_attn_pool_fwd_rep(c.f(p + "v"), c.f(p + "qv"), bt->image_ft, bt->num_boxes, P->spat_att_score.w,
+                                  P->spat_att_score.b, kb.keep_att, d->keep_att, c.f(p + "att"), c.f(p + "pooled"),
+                                  (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
+        hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
+                           (int)B, (int)n, d->global_valid[k]);
+        VQA_CHECK_LAUNCH();
+        if (hs.rank[1] >= 0) {
+            VQA_REQUIRE(kb.wordsets, VQA_ERR_ARG);
+            TRY(vqa_embed_fwd(P->wordset_map, kb.wordsets, c.f(p + "wse"), (int)Bn, 1, (int)W, d->n_ws, c.st));
+            TRY(vqa_tanh_fwd(c.f(p + "wse"), c.f(p + "ws"), Bn * W, c.st));
+            TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, wft, li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
+                          p + "wf_rstd", nullptr, 1.f));
+        }
+    }
+    {   // captions of both categories: one batch, final states -> heads 0 / 1 of "S/lft"
+        ProbeScope ps_g("pt.caption_gru.fwd", c.st);
+        TRY(gather_rows2(bt->kind[0].blanks, bt->kind[1].blanks, bt->perm, c.i32("J/blanks_s"), B2, T, Bn, c.st));
+        TRY(gather_rows2(bt->kind[0].blanks_len, bt->kind[1].blanks_len, bt->perm, c.i32("J/lens_s"), B2, 1, Bn, c.st));
+        TRY(vqa_embed_fwd_ld(P->l_glove, c.i32("J/blanks_s"), c.f("J/x_tm"), (int)B2, (int)T, (int)W, d->Vq,
+                             (int)x_stride(W), c.st));
+        float* xp = c.f("J/xp");
+        TRY(c.gemm(0, 0, T * B2, 3 * H, W, c.f("J/x_tm"), (int)x_stride(W), c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H),
+                   c.f("bx_cat")));
+        float* hsb = c.f("J/hs");
+        if (hipMemsetAsync(hsb, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+        if (bt->live_rows != nullptr)
+            TRY(vqa_gru_seq_fwd_live(xp, P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"), bt->live_rows, hsb,
+                                     c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"), c.f("J/gru_rh"), (int)T, (int)B2,
+                                     (int)H, c.st));
+        else
+            TRY(vqa_gru_seq_fwd(xp, P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"), hsb, c.f("J/gru_r"),
+                                c.f("J/gru_u"), c.f("J/gru_c"), c.f("J/gru_rh"), (int)T, (int)B2, (int)H, c.st));
+        TRY(gather_rows(hsb + T * B2 * H, bt->inv, c.f("S/lft"), B2, H, c.st));
+    }
+    if (hs.rank[2] >= 0) {   // enwiki contexts of both categories: one batch through encode_L_enwiki -> heads 2 r_ew + k
+        ProbeScope ps_e("pt.enwiki_gru.fwd", c.st);
+        const int64_t Tc = dims->Lc;
+        TRY(vqa_gru_pack_wx(P->egru_wg, P->egru_wc, P->egru_bg, P->egru_bc, c.f("E/wx_cat"), c.f("E/bx_cat"), (int)W,
+                            (int)H, c.st));
+        TRY(gather_rows2(bx->ctx[0].context, bx->ctx[1].context, bx->ctx_perm, c.i32("E/ctx_s"), B2, Tc, Bn, c.st));
+        TRY(gather_rows2(bx->ctx[0].context_len, bx->ctx[1].context_len, bx->ctx_perm, c.i32("E/lens_s"), B2, 1, Bn, c.st));
+        TRY(vqa_embed_fwd_ld(P->enwiki_map, c.i32("E/ctx_s"), c.f("E/x_tm"), (int)B2, (int)Tc, (int)W, dims->n_ctx,
+                             (int)x_stride(W), c.st));
+        float* xp = c.f("E/xp");
+        TRY(c.gemm(0, 0, Tc * B2, 3 * H, W, c.f("E/x_tm"), (int)x_stride(W), c.f("E/wx_cat"), (int)(3 * H), xp,
+                   (int)(3 * H), c.f("E/bx_cat")));
+        float* hse = c.f("E/hs");
+        if (hipMemsetAsync(hse, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+        if (bx->ctx_live_rows != nullptr)
+            TRY(vqa_gru_seq_fwd_live(xp, P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"), bx->ctx_live_rows,
+                                     hse, c.f("E/gru_r"), c.f("E/gru_u"), c.f("E/gru_c"), c.f("E/gru_rh"), (int)Tc,
+                                     (int)B2, (int)H, c.st));
+        else
+            TRY(vqa_gru_seq_fwd(xp, P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"), hse, c.f("E/gru_r"),
+                                c.f("E/gru_u"), c.f("E/gru_c"), c.f("E/gru_rh"), (int)Tc, (int)B2, (int)H, c.st));
+        TRY(gather_rows(hse + Tc * B2 * H, bx->ctx_inv, c.f("S/lft") + 2 * hs.rank[2] * Bn * H, B2, H, c.st));
+    }
+    {   // the NH heads, stacked
+        const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
+        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+        ProbeScope ps_h("pt.heads.fwd", c.st);
+        TRY(c.gemm(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, P->pooled_linear_l.w, (int)H, c.f("S/vl_pre"), (int)H,
+                   P->pooled_linear_l.b));
+        TRY(c.gemm(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, P->q_linear_l.w, (int)H, c.f("S/ll_pre"), (int)H,
+                   P->q_linear_l.b));
+        for (int h = 0; h < NH; ++h) {
+            const std::string q = hname(h);
+            TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, P->pooled_linear_l.gamma[li(h)], P->pooled_linear_l.beta[li(h)],
+                               nullptr, 1.f, c.f("S/vl") + h * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n,
+                               (int)H, 0, c.st));
+            TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + h * SH, P->q_linear_l.gamma[li(h)], P->q_linear_l.beta[li(h)], nullptr, 1.f,
+                               c.f("S/ll") + h * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
+        }
+        TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
+        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
+                   P->joint_fc.b));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, t = hs.type[h >> 1];
+            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
+                                                                               : bx->ctx[k].keep_ew_joint;
+            const std::string q = hname(h);
+            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[li(h)], P->joint_fc.beta[li(h)], jmask,
+                               d->keep_joint, c.f("S/j") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n,
+                               (int)(2 * H), 0, c.st));
+        }
+        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
+                   P->classifier.b));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, r = h >> 1;
+            const std::string p = std::string(KIND[k]) + "/";
+            TRY(vqa_softmax_ce_fwd(c.f("S/z") + h * SA, bt->kind[k].fills, c.f(p + "valid"), 5, c.f(p + "inv_valid"),
+                                   c.f("S/stats") + h * Bn * 4, want_dz ? c.f("S/dz") + h * SA : nullptr, (int)Bn, (int)A,
+                                   c.st));
+            ra.stats[k * hs.nt + r] = c.f("S/stats") + h * Bn * 4;
+            ra.inv[k * hs.nt + r] = c.f(p + "inv_valid");
+        }
+    }
+    hipLaunchKernelGGL(pretrain_ext_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+// Backward phases of the variable head set; the buckets of vqa_pretrain_backward_phases, with
+//   1  the NH stacked heads
+//   2  BPTT of the caption batch, then of the enwiki context batch (encode_L_blank and encode_L_enwiki gradients)
+//   4  L_GloVe scatter-add, then enwiki_map scatter-add (both slice sums of squares)
+//   8  per category: wordset_ft / wordset_map (cleared even without the word-set head), spatial attention (writes slice_sq)
+extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                void* stream) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    const vqa_pretrain_dims_t* d = &dims->base;
+    const vqa_pretrain_batch_t* bt = &bx->base;
+    const HeadSet hs(dims->heads);
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, A = d->A, T = d->L, Bn = B * n;
+    const int64_t NH = hs.nh(), B2 = 2 * Bn;
+    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    const int det = (d->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    ProbeScope ps_all("pretrain_ext.backward", c.st);
+    Acc acc{c, {}};
+    const float* sq_prev = nullptr;
+    auto add_slice_sq = [&](const float* g, int64_t cnt) -> int {
+        TRY(vqa_sumsq(g, cnt, sq_prev, c.f("sq"), c.f("sumsq_ws"), c.count("sumsq_ws"), c.st));
+        sq_prev = c.f("sq");
+        return VQA_OK;
+    };
+    if (phases & 1) {
+        ProbeScope ps_h("pt.heads.bwd", c.st);
+        const int64_t SH = Bn * H, SJ = Bn * 2 * H;
+        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+        TRY(acc.weight(G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
+        TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G->classifier.b));
+        TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, t = hs.type[h >> 1];
+            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
+                                                                               : bx->ctx[k].keep_ew_joint;
+            const std::string q = hname(h);
+            TRY(ln_bwd_p(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, fc_slot(P->joint_fc, li(h)), fc_slot(G->joint_fc, li(h)), 0,
+                         (int)n, 0, c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), jmask, d->keep_joint,
+                         c.f("d_jpre") + h * SJ));
+        }
+        const vqa_pt_fc_t jP = fc_slot(P->joint_fc, 0), jG = fc_slot(G->joint_fc, 0);
+        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, jP, jG, c.f("d_jin")));
+        TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
+        for (int h = 0; h < NH; ++h) {
+            const std::string q = hname(h);
+            TRY(ln_bwd_p(c, acc, c.f("d_vl") + h * SH, Bn, H, fc_slot(P->pooled_linear_l, li(h)),
+                         fc_slot(G->pooled_linear_l, li(h)), 0, (int)n, 0, c.f("S/vl_pre") + (h & 1) * SH,
+                         c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f, c.f("d_vlpre") + h * SH));
+            TRY(ln_bwd_p(c, acc, c.f("d_ll") + h * SH, Bn, H, fc_slot(P->q_linear_l, li(h)), fc_slot(G->q_linear_l, li(h)), 0,
+                         (int)n, 0, c.f("S/ll_pre") + h * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f,
+                         c.f("d_llpre") + h * SH));
+        }
+        // every head of a category applies pooled_linear_l to the same pooled rows: their d_pre meet before one dW / dx
+        for (int r = 1; r < hs.nt; ++r) TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * r * SH, 2 * SH, c.st));
+        TRY(acc.weight(G->pooled_linear_l.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
+        TRY(c.gemm(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, P->pooled_linear_l.w, (int)H, c.f("d_pooled"), (int)D));
+        TRY(fc_bwd(c, acc, "d_llpre", c.f("S/lft"), NH * Bn, H, H, fc_slot(P->q_linear_l, 0), fc_slot(G->q_linear_l, 0),
+                   c.f("d_lft")));
+    }
+    const int ld3 = (int)(3 * H);
+    const int64_t Wp = x_stride(W);
+    if (phases & 2) {
+        {
+            ProbeScope ps_g("pt.caption_gru.bwd", c.st);
+            float* dxp = c.f("dxp");
+            TRY(gather_rows(c.f("d_lft"), bt->perm, c.f("d_state_s"), B2, H, c.st));
+            const float* hsb = c.f("J/hs");
+            if (bt->live_rows != nullptr)
+                TRY(vqa_gru_seq_bwd_live(c.f("d_state_s"), P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"),
+                                         bt->live_rows, hsb, c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"), dxp,
+                                         c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
+            else
+                TRY(vqa_gru_seq_bwd(c.f("d_state_s"), P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"), hsb,
+                                    c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"), dxp, c.f("d_hscratch"), (int)T, (int)B2,
+                                    (int)H, c.st));
+            TRY(acc.weight(c.f("dwx_cat"), c.f("J/x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
+            TRY(acc.weight(G->gru_wg + W * 2 * H, hsb, (int)H, dxp, ld3, H, 2 * H, T * B2));
+            TRY(acc.weight(G->gru_wc + W * H, c.f("J/gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
+            TRY(vqa_gru_unpack_dwx_bias(c.f("dwx_cat"), G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc, (int)W, (int)H, c.st));
+        }
+        if (hs.rank[2] >= 0) {
+            ProbeScope ps_e("pt.enwiki_gru.bwd", c.st);
+            const int64_t Tc = dims->Lc;
+            float* dxp = c.f("E/dxp");
+            TRY(gather_rows(c.f("d_lft") + 2 * hs.rank[2] * Bn * H, bx->ctx_perm, c.f("E/d_state_s"), B2, H, c.st));
+            const float* hse = c.f("E/hs");
+            if (bx->ctx_live_rows != nullptr)
+                TRY(vqa_gru_seq_bwd_live(c.f("E/d_state_s"), P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"),
+                                         bx->ctx_live_rows, hse, c.f("E/gru_r"), c.f("E/gru_u"), c.f("E/gru_c"), dxp,
+                                         c.f("d_hscratch"), (int)Tc, (int)B2, (int)H, c.st));
+            else
+                TRY(vqa_gru_seq_bwd(c.f("E/d_state_s"), P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"), hse,
+                                    c.f("E/gru_r"), c.f("E/gru_u"), c.f("E/gru_c"), dxp, c.f("d_hscratch"), (int)Tc,
+                                    (int)B2, (int)H, c.st));
+            TRY(acc.weight(c.f("E/dwx_cat"), c.f("E/x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, Tc * B2));
+            TRY(acc.weight(G->egru_wg + W * 2 * H, hse, (int)H, dxp, ld3, H, 2 * H, Tc * B2));
+            TRY(acc.weight(G->egru_wc + W * H, c.f("E/gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, Tc * B2));
+            TRY(vqa_gru_unpack_dwx_bias(c.f("E/dwx_cat"), G->egru_wg, G->egru_wc, G->egru_bg, G->egru_bc, (int)W, (int)H,
+                                        c.st));
+        }
+    }
+    if (phases & 4) {
+        {
+            ProbeScope ps_c("pt.caption_embed.bwd", c.st);
+            if (hipMemsetAsync(G->l_glove, 0, (size_t)d->Vq * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+            float* dx = c.f("dx");
+            TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
+            TRY(c.gemm(0, 1, T * B2, W, 3 * H, c.f("dxp"), ld3, c.f("wx_cat"), (int)(3 * H), dx, (int)W));
+            TRY(vqa_embed_bwd_len_det(dx, c.i32("J/blanks_s"), c.i32("J/lens_s"), G->l_glove, (int)B2, (int)T, (int)W,
+                                      d->Vq, det, c.st));
+            TRY(add_slice_sq(dx, T * B2 * W));
+        }
+        if (hs.rank[2] >= 0) {
+            ProbeScope ps_e("pt.enwiki_embed.bwd", c.st);
+            const int64_t Tc = dims->Lc;
+            if (hipMemsetAsync(G->enwiki_map, 0, (size_t)dims->n_ctx * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+            float* dx = c.f("E/dx");
+            TRY(vqa_gru_pack_wx(P->egru_wg, P->egru_wc, P->egru_bg, P->egru_bc, c.f("E/wx_cat"), c.f("E/bx_cat"), (int)W,
+                                (int)H, c.st));
+            TRY(c.gemm(0, 1, Tc * B2, W, 3 * H, c.f("E/dxp"), ld3, c.f("E/wx_cat"), (int)(3 * H), dx, (int)W));
+            TRY(vqa_embed_bwd_len_det(dx, c.i32("E/ctx_s"), c.i32("E/lens_s"), G->enwiki_map, (int)B2, (int)Tc, (int)W,
+                                      dims->n_ctx, det, c.st));
+            TRY(add_slice_sq(dx, Tc * B2 * W));
+        }
+    }
+    if (phases & 8) {
+        if (hipMemsetAsync(G->wordset_map, 0, (size_t)d->n_ws * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+        if (!(phases & 4)) sq_prev = c.f("sq");
+    }
+    const vqa_pt_fc_t spat_vP = fc4(P->spat_v_linear_v), spat_vG = fc4(G->spat_v_linear_v);
+    const vqa_pt_fc_t spat_qP = fc4(P->spat_q_linear_v), spat_qG = fc4(G->spat_q_linear_v);
+    const vqa_pt_fc_t wftP = fc4(P->wordset_ft), wftG = fc4(G->wordset_ft);
+    for (int k = 0; k < 2 && (phases & 8); ++k) {
+        ProbeScope ps_sp("pt.spatial_wordset.bwd", c.st);
+        const vqa_pretrain_kind_t& kb = bt->kind[k];
+        const std::string p = std::string(KIND[k]) + "/";
+        if (hs.rank[1] >= 0) {
+            TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 * hs.rank[1] + k) * Bn * H, c.f(p + "ws"), Bn, W, H, wftP, wftG, li(k),
+                          (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", nullptr, 1.f, "d_wfpre", c.f("d_ws")));
+            TRY(vqa_tanh_bwd(c.f("d_ws"), c.f(p + "ws"), c.f("d_wse"), Bn * W, c.st));
+            TRY(vqa_embed_bwd_len_det(c.f("d_wse"), kb.wordsets, nullptr, G->wordset_map, (int)Bn, 1, (int)W, d->n_ws, det,
+                                      c.st));
+            TRY(add_slice_sq(c.f("d_wse"), Bn * W));
+        }
+        TRY(vqa_attn_pool_bwd_rep(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), bt->image_ft, c.f(p + "att"),
+                                  P->spat_att_score.w, kb.keep_att, d->keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
+                                  c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
+        TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G->spat_att_score.w));
+        TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G->spat_att_score.b));
+        TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, spat_vP, spat_vG, li(k), (int)R, 0, p + "v_pre",
+                      p + "v_mean", p + "v_rstd", nullptr, 1.f, "d_vpre", nullptr));
+        TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, spat_qP, spat_qG, li(k), (int)n, 0, p + "qv_pre",
+                      p + "qv_mean", p + "qv_rstd", nullptr, 1.f, "d_qvpre", nullptr));
+    }
+    if ((phases & 8) && slice_sq != nullptr && sq_prev != nullptr)
+        if (hipMemcpyAsync(slice_sq, sq_prev, sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
+            return VQA_ERR_LAUNCH;
+    return VQA_OK;
+}
+
+extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                         const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                         void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
+    return vqa_pretrain_ext_backward_phases(dims, P, G, bx, workspace, workspace_bytes, slice_sq, 15, stream);
+}

@@ -4,9 +4,13 @@ vlmap_memft/datasets/dataset_vlmap.py:19-236, 308-353 (model_vlmap_bf_or_wordset
 Per image: up to 5 object and 5 attribute blank-fill entries are drawn at random (shuffle, truncate,
 pad by repeating the last, `num` = number of valid ones), captions padded to the per-image max length
 (batches to the per-batch max), one word set per entry taken round-robin from the answer's shuffled
-word-set list (re-shuffled when exhausted).  The enwiki-context fields are not produced: the cfg-5
-model does not read them.  Files: `<data_dir>/<split>_processed.pkl`, `<split>_image_info.pkl`,
-`answer_dict.pkl`, `wordset_dict5.pkl` as in the reference, features from `<split>_vfeat.hdf5` (or `.npz`).
+word-set list (re-shuffled when exhausted).  With `enwiki` (the enwiki-context pre-training models) every entry
+also draws one Wikipedia context of its answer the same round-robin way and the rows carry
+`{obj,attr}_blank_fill/enwiki_context` [n, max_context_len] and `_len` [n] (dataset_vlmap.py:52-61, 84-126, 158-234 of
+the reference); those draws come from a RandomState stream of their own, so every other field of a batch is the same
+with or without them.  Files: `<data_dir>/<split>_processed.pkl`, `<split>_image_info.pkl`,
+`answer_dict.pkl`, `wordset_dict5.pkl` as in the reference, features from `<split>_vfeat.hdf5` (or `.npz`), and
+`enwiki_context_dict_w3_p<enwiki_preprocessing>_n5.{pkl,hdf5}` for the contexts.
 `synthetic_dataset` builds the same structures in memory.
 """
 from __future__ import annotations
@@ -36,12 +40,44 @@ class DataConfig:
     pass
 
 
+def enwiki_seed(seed):
+    """seed of the context-sampling stream (disjoint from the entry / word-set stream of the same dataset seed)"""
+    return (int(seed) * 2654435761 + 97) % (2 ** 31 - 1)
+
+
+def load_enwiki_dict(data_dir, enwiki_preprocessing=0):
+    """enwiki_context_dict_w3_p{p}_n5.pkl (context_word_vocab, context_word_dict, max_context_len,
+    ans2shuffled_context_idx) + the np_context / np_context_len arrays of the .hdf5 beside it (read without h5py)"""
+    from . import hdf5_io
+    stem = os.path.join(data_dir, "enwiki_context_dict_w3_p{}_n5".format(int(enwiki_preprocessing)))
+    d = _load_pickle(stem + ".pkl")
+    f = hdf5_io.File(stem + ".hdf5")
+    d["np_context"] = np.asarray(f["np_context"].read(), np.int32)
+    d["np_context_len"] = np.asarray(f["np_context_len"].read(), np.int32)
+    return d
+
+
+def wants_enwiki(config):
+    return "enwiki" in str(getattr(config, "model_type", "") or "")
+
+
 class Dataset(object):
-    def __init__(self, config=None, split="train", name="vlmap_memft", data=None, seed=0):
+    def __init__(self, config=None, split="train", name="vlmap_memft", data=None, seed=0, enwiki=None):
         """data: optional dict(ids, image_id2idx, processed, answer_dict, ws_dict, image_features,
-        spatial_features, normal_boxes, num_boxes) replacing the files under config.data_dir."""
+        spatial_features, normal_boxes, num_boxes[, enwiki_dict]) replacing the files under config.data_dir.
+        enwiki: emit the enwiki-context fields (None: when config.model_type is an enwiki model)."""
         self.name, self.split = name, split
         self.rng = np.random.RandomState(seed)
+        if enwiki is None:
+            enwiki = wants_enwiki(config)
+        self.enwiki_dict = None
+        if enwiki:
+            self.ctx_rng = np.random.RandomState(enwiki_seed(seed))
+            if data is not None and "enwiki_dict" in data:
+                self.enwiki_dict = data["enwiki_dict"]
+            else:
+                self.enwiki_dict = load_enwiki_dict(config.data_dir, getattr(config, "enwiki_preprocessing", 0))
+            self.enwiki_choice_idx = defaultdict(lambda: defaultdict(lambda: defaultdict(int)))
         if data is None:
             d = config.data_dir
             info = _load_pickle(os.path.join(d, "{}_image_info.pkl".format(split)))
@@ -91,6 +127,19 @@ class Dataset(object):
             self.wordset_choice_idx[category][task][label] = 0
         return ws
 
+    def sample_context(self, e, category, task):
+        """index of a row of np_context for the entry's answer: round-robin over ans2shuffled_context_idx[label], the
+        list re-shuffled (from the context stream) when exhausted -- the wordset contract"""
+        label = e[task]
+        idxs = self.enwiki_dict["ans2shuffled_context_idx"][label]
+        i = self.enwiki_choice_idx[category][task][label]
+        c = idxs[i]
+        self.enwiki_choice_idx[category][task][label] += 1
+        if self.enwiki_choice_idx[category][task][label] >= len(idxs):
+            self.ctx_rng.shuffle(idxs)
+            self.enwiki_choice_idx[category][task][label] = 0
+        return c
+
     def get_data(self, image_id, with_features=True):
         """with_features=False (not in the reference): the row carries `image_idx` instead of its slices of the
         feature tables -- for trainers that keep the tables in HBM and gather there (create_ops(resident=True))"""
@@ -127,6 +176,10 @@ class Dataset(object):
                         key + "/normal_boxes": np.array(boxes, np.float32), key + "/fills": np.array(fills, np.int32),
                         key + "/blanks": blanks, key + "/blanks_len": np.array(blens, np.int32),
                         key + "/wordsets": np.array(wsets, np.int32)})
+            if self.enwiki_dict is not None:
+                ctx = [self.sample_context(entry[key][i], cat, "fill") for i in idx_list]
+                ret[key + "/enwiki_context"] = np.take(self.enwiki_dict["np_context"], ctx, axis=0).astype(np.int32)
+                ret[key + "/enwiki_context_len"] = np.take(self.enwiki_dict["np_context_len"], ctx, axis=0).astype(np.int32)
         return ret
 
     @property
@@ -169,6 +222,8 @@ def _batches(batch_size, dataset, is_train, shuffle, seed, repeat, resident, par
 
 def _worker_main(q, batch_size, dataset, is_train, shuffle, seed, repeat, resident, part, parts):
     dataset.rng = np.random.RandomState((int(seed) + 1000003 * (part + 1)) % (2 ** 31 - 1))   # own sampling stream
+    if getattr(dataset, "enwiki_dict", None) is not None:
+        dataset.ctx_rng = np.random.RandomState(enwiki_seed((int(seed) + 1000003 * (part + 1)) % (2 ** 31 - 1)))
     try:
         for b in _batches(batch_size, dataset, is_train, shuffle, seed, repeat, resident, part, parts):
             q.put(b)
@@ -277,8 +332,29 @@ def create_ops(batch_size, dataset, is_train=True, scope="vlmap_memft", shuffle=
     return _batches(*args)
 
 
-def synthetic_dataset(num_images, Vq, n_ws, A, R=36, D=2048, max_len=10, seed=0):
-    """In-memory dataset with the reference's structures (5-8 entries per image and category)."""
+def synthetic_enwiki_dict(A, n_ctx=60, Lc=7, per_answer=(1, 4), seed=0):
+    """In-memory enwiki context dictionary with the structures of enwiki_context_dict_w3_p*_n5.{pkl,hdf5}: word 0 is
+    the padding, `<unk>` a real token that counts in the length, row 0 of every answer is the default context `<word>`
+    of length 1, the other rows have lengths 1 .. Lc (data/tools/enwiki/3_make_wordset.py:376-398)."""
+    rng = np.random.default_rng(seed + 7)
+    vocab = ["<s>", "<unk>"] + ["c%d" % i for i in range(n_ctx - 2)]
+    rows, lens, ans2 = [], [], {}
+    for a in range(A):
+        ans2[a] = []
+        for j in range(int(rng.integers(per_answer[0], per_answer[1] + 1))):
+            ln = 1 if j == 0 else int(rng.integers(1, Lc + 1))
+            r = np.zeros(Lc, np.int32)
+            r[:ln] = rng.integers(1, n_ctx, size=ln)        # includes <unk> = 1
+            ans2[a].append(len(rows))
+            rows.append(r)
+            lens.append(ln)
+    return {"context_word_vocab": vocab, "context_word_dict": {w: i for i, w in enumerate(vocab)}, "max_context_len": Lc,
+            "ans2shuffled_context_idx": ans2, "np_context": np.stack(rows), "np_context_len": np.asarray(lens, np.int32)}
+
+
+def synthetic_dataset(num_images, Vq, n_ws, A, R=36, D=2048, max_len=10, seed=0, enwiki=None):
+    """In-memory dataset with the reference's structures (5-8 entries per image and category).  enwiki: optional
+    dict(n_ctx=..., Lc=...) -> also an enwiki context dictionary (synthetic_enwiki_dict) under 'enwiki_dict'."""
     rng = np.random.default_rng(seed)
     ids = list(range(1000, 1000 + num_images))
     ys, xs = np.sort(rng.random((num_images, R, 2)), -1), np.sort(rng.random((num_images, R, 2)), -1)
@@ -301,7 +377,10 @@ def synthetic_dataset(num_images, Vq, n_ws, A, R=36, D=2048, max_len=10, seed=0)
     ws = {"vocab": ["ws%d" % i for i in range(n_ws)],
           "ans2shuffled_wordset": {a: rng.integers(0, n_ws, size=int(rng.integers(1, 4))).tolist() for a in range(A)}}
     adict = {"vocab": ["a%d" % i for i in range(A)], "dict": {"a%d" % i: i for i in range(A)}}
-    return {"ids": ids, "image_id2idx": {i: j for j, i in enumerate(ids)}, "processed": processed,
-            "answer_dict": adict, "ws_dict": ws,
-            "image_features": np.maximum(rng.standard_normal((num_images, R, D)), 0).astype(np.float32),
-            "spatial_features": spat, "normal_boxes": nb, "num_boxes": np.full(num_images, R, np.int32)}
+    out = {"ids": ids, "image_id2idx": {i: j for j, i in enumerate(ids)}, "processed": processed,
+           "answer_dict": adict, "ws_dict": ws,
+           "image_features": np.maximum(rng.standard_normal((num_images, R, D)), 0).astype(np.float32),
+           "spatial_features": spat, "normal_boxes": nb, "num_boxes": np.full(num_images, R, np.int32)}
+    if enwiki is not None:
+        out["enwiki_dict"] = synthetic_enwiki_dict(A, seed=seed, **dict(enwiki))
+    return out

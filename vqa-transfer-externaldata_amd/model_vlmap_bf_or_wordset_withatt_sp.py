@@ -2,7 +2,9 @@
 vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py:13-94: Model(batch, config, is_train) ->
 .loss, .losses, .report (13 scalars), .mid_result, .vocab, .answer_dict, .ws_dict; config carries
 data_cfg (n_obj_bf, n_attr_bf, max_box_num, vfeat_dim), data_dir, expand_depth.  build() runs the
-forward pass of the current batch on libvqahot.so through pretrain.PretrainEngine."""
+forward pass of the current batch on libvqahot.so through pretrain.PretrainEngine.  The enwiki-context models
+(model_vlmap_bf_or_wordset_enwiki_withatt_sp.py, model_vlmap_bf_enwiki_withatt_sp.py) are this class with another
+MODEL_TYPE, hence head set (pretrain.MODEL_HEADS)."""
 from __future__ import annotations
 
 import os
@@ -20,6 +22,9 @@ V_DIM = 1024
 
 
 class Model(object):
+    MODEL_TYPE = "vlmap_bf_or_wordset_withatt_sp"
+    # the word-set dictionary file (the enwiki models read 'wordset_dict5.pkl', :34 of their files)
+    WS_DICT_FILE = "wordset_dict5_depth{depth}.pkl"
 
     def __init__(self, batch, config, is_train=True):
         self.batch = batch
@@ -35,8 +40,18 @@ class Model(object):
             os.path.join(self.data_dir, "answer_dict.pkl"))
         self.num_answer = len(self.answer_dict["vocab"])
         self.ws_dict = getattr(config, "ws_dict", None) or _load_pickle(os.path.join(
-            self.data_dir, "wordset_dict5_depth{}.pkl".format(int(getattr(config, "expand_depth", 0)))))
+            self.data_dir, self.WS_DICT_FILE.format(depth=int(getattr(config, "expand_depth", 0)))))
         self.num_ws = len(self.ws_dict["vocab"])
+        self.heads = PT.MODEL_HEADS[self.MODEL_TYPE]
+        self.num_context_vocab = None
+        if "ew" in self.heads:          # enwiki_context_dict_w3_p{p}_n5.pkl (:38-48 of the enwiki models)
+            ed = getattr(config, "enwiki_dict", None)
+            if ed is None:
+                ed = _load_pickle(os.path.join(self.data_dir, "enwiki_context_dict_w3_p{}_n5.pkl".format(
+                    int(getattr(config, "enwiki_preprocessing", 0)))))
+            self.enwiki_dict = ed
+            self.num_context_vocab = len(ed["context_word_vocab"])
+            self.max_context_len = int(ed["max_context_len"])
         self._step = 0
         self._engine = None
         self.build()
@@ -54,7 +69,7 @@ class Model(object):
                 p[n] = ((torch.rand(s, generator=g) * 2 - 1) * lim).numpy()
             elif n.endswith("gates/bias") or n.endswith("/gamma"):
                 p[n] = np.ones(s, np.float32)
-            elif n == "wordset_map/learn":                 # random_uniform(-0.01, 0.01), modules.py:351-358
+            elif n in ("wordset_map/learn", "enwiki_map/learn"):   # random_uniform(-0.01, 0.01), modules.py:351-358
                 p[n] = (torch.rand(s, generator=g) * 0.02 - 0.01).numpy()
             elif n.endswith("embed_map"):                  # GloVe rows when available, else zeros (OOV)
                 glove = getattr(self.config, "glove", None)
@@ -79,7 +94,8 @@ class Model(object):
         keep = ("image_ft", "spatial_ft", "num_boxes", "image_idx")
         out = {}
         for k, v in self.batch.items():
-            if k in keep or k.split("/")[-1] in ("normal_boxes", "fills", "blanks", "blanks_len", "wordsets", "num"):
+            if k in keep or k.split("/")[-1] in ("normal_boxes", "fills", "blanks", "blanks_len", "wordsets", "num",
+                                                 "enwiki_context", "enwiki_context_len"):
                 if k == "normal_boxes":
                     continue
                 t = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
@@ -88,7 +104,8 @@ class Model(object):
             if k in out:
                 out[k] = out[k].float()
         if getattr(self.config, "sort_by_length", 1):
-            host = PT.add_length_sort({k: v for k, v in self.batch.items() if k.endswith(("/blanks", "/blanks_len"))})
+            host = PT.add_length_sort({k: v for k, v in self.batch.items()
+                                       if k.endswith(("/blanks", "/blanks_len", "/enwiki_context", "/enwiki_context_len"))})
             for k, v in host.items():
                 if k.endswith("/sort"):       # permutation / inverse uploaded here (on the stream of prepare())
                     v["_dev"] = (torch.from_numpy(np.asarray(v["perm"])).to(self.device, torch.int32),
@@ -137,11 +154,13 @@ class Model(object):
             # one LayerNorm per shared fc_layer scope (TF 1.x: pretrain.py) unless the config asks for the
             # per-call-site variable set; a checkpoint's variable names override either (PretrainEngine.load_state_dict)
             shapes = PT.variable_shapes(len(self.vocab["vocab"]), self.num_ws, self.num_answer, W_DIM, cfg.vfeat_dim,
-                                        V_DIM, bool(getattr(self.config, "ln_shared", 1)))
+                                        V_DIM, bool(getattr(self.config, "ln_shared", 1)), self.heads,
+                                        self.num_context_vocab)
             self._engine = PT.PretrainEngine(n=cfg.n_obj_bf, R=cfg.max_box_num, D=cfg.vfeat_dim, H=V_DIM, W=W_DIM,
                                              A=self.num_answer, Vq=len(self.vocab["vocab"]), n_ws=self.num_ws,
                                              params=self._initial_params(shapes), device=self.device,
-                                             deterministic=bool(getattr(self.config, "deterministic", 0)))
+                                             deterministic=bool(getattr(self.config, "deterministic", 0)),
+                                             heads=self.heads, n_ctx=self.num_context_vocab)
         eng = self._engine
         B = int((db["image_ft"] if "image_ft" in db else db["image_idx"]).shape[0])
         tables = getattr(self.config, "feature_tables", None)
@@ -158,14 +177,18 @@ class Model(object):
             kt = eng._tape["kinds"][k]
             name = "object" if k == "obj" else "attribute"
             self.mid_result[name + "_pooled_V_ft"] = kt["pooled"].view(B, eng.n, -1)
-            self.mid_result[k + "_blank_fill/logit"] = kt["wordset"]["z"].view(B, eng.n, -1)
+            if "wordset" in kt:
+                self.mid_result[k + "_blank_fill/logit"] = kt["wordset"]["z"].view(B, eng.n, -1)
+            if "enwiki" in kt:
+                self.mid_result[k + "_enwiki/logit"] = kt["enwiki"]["z"].view(B, eng.n, -1)
         if defer_report and self._reduce_report:
             self._report_event = None             # data parallel: the scalars are reduced over the ranks in finish_report
             return None
         if defer_report:
+            nk = len(eng.report_keys)
             if getattr(self, "_report_host", None) is None:
-                self._report_host = torch.empty(16, dtype=torch.float32).pin_memory()
-            self._report_host.copy_(eng.tensor("report")[:16], non_blocking=True)      # stream-ordered after the forward
+                self._report_host = torch.empty(nk, dtype=torch.float32).pin_memory()
+            self._report_host.copy_(eng.tensor("report")[:nk], non_blocking=True)      # stream-ordered after the forward
             self._report_event = torch.cuda.Event()
             self._report_event.record(torch.cuda.current_stream(self.device))
             return None
@@ -176,7 +199,7 @@ class Model(object):
         if getattr(self, "_report_event", None) is not None:
             self._report_event.synchronize()
             r = self._report_host.numpy()
-            self.report = eng.report = {eng.lib.vqa_pretrain_report_key(i).decode(): float(r[i]) for i in range(13)}
+            self.report = eng.report = {eng.report_key(i): float(r[i]) for i in range(len(eng.report_keys))}
             self._report_event = None
         else:
             self.report = eng.fetch_report(reduce=getattr(self, "_reduce_report", False))

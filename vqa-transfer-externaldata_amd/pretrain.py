@@ -14,6 +14,12 @@ pass is enqueued from C++, the workspace is carved from the dims, no torch op ru
 effective batch is B*n rows and the x n tile of V_ft / spatial_ft that the reference materialises (:324-333)
 never exists: the attention kernels take `rep = n` queries per memory and v_linear_v of the (identical) tiles
 is computed once per image.
+
+The enwiki-context models of the paper's pipeline (vlmap_memft/model_vlmap_bf_or_wordset_enwiki_withatt_sp.py and
+model_vlmap_bf_enwiki_withatt_sp.py) are the same engine with another head set (`heads`, MODEL_HEADS): per category an
+enwiki head (enwiki_map embedding of the answer's context -> encode_L_enwiki GRU -> the shared fusion MLP) beside the
+blank-fill and (optionally) word-set heads.  Those run on vqa_pretrain_ext_forward / _backward_phases; the cfg-5 head
+set keeps the vqa_pretrain_* calls.
 """
 from __future__ import annotations
 
@@ -30,12 +36,22 @@ KINDS = ("obj", "attr")
 KEEP_ATT, KEEP_JOINT = 0.8, 0.5
 ADAM_B1, ADAM_B2, ADAM_EPS, CLIP_NORM = 0.9, 0.999, 1e-8, 20.0
 NO_GRAD_VARS = ("V_GloVe/embed_map", "LearnAnswerGloVe/embed_map")      # created for export only
-SPARSE_VARS = ("wordset_map/learn", "L_GloVe/embed_map")                # IndexedSlices gradients
+SPARSE_VARS = ("wordset_map/learn", "L_GloVe/embed_map", "enwiki_map/learn")   # IndexedSlices gradients (if present)
 # Order of the dense variables in the flat buffers = the order in which the phases of vqa_pretrain_backward_phases
 # complete their gradients, so every data-parallel bucket is one contiguous range:
-#   [wordset_map | L_GloVe | GRU (phase 2) | stacked heads (phase 1) | spatial attention, wordset_ft (phase 8) | tail]
-PHASE_SCOPES = (("encode_L_blank/",), ("classifier/", "joint_fc/", "pooled_linear_l/", "q_linear_l/"),
+#   [wordset_map | L_GloVe, enwiki_map (phase 4) | GRUs (phase 2) | stacked heads (phase 1) |
+#    spatial attention, wordset_ft (phase 8) | tail]
+PHASE_SCOPES = (("encode_L_blank/", "encode_L_enwiki/"), ("classifier/", "joint_fc/", "pooled_linear_l/", "q_linear_l/"),
                 ("spat_att/", "spat_q_linear_v/", "spat_v_linear_v/", "wordset_ft/"))
+# head set per model type: blank fill, word set, enwiki context (in TF build order; head 2 r + k of the type of rank r
+# and category k owns LayerNorm slot 2 r + k of the shared fusion scopes when they are not shared)
+MODEL_HEADS = {"vlmap_bf_or_wordset_withatt_sp": ("bf", "ws"),
+               "vlmap_bf_or_wordset_enwiki_withatt_sp": ("bf", "ws", "ew"),
+               "vlmap_bf_enwiki_withatt_sp": ("bf", "ew")}
+CFG5_HEADS = ("bf", "ws")
+TASK_NAMES = {"bf": "blank_fill", "ws": "wordset", "ew": "enwiki"}
+# the enwiki heads' joint keep-masks are drawn from counters at and above this one: disjoint from the cfg-5 stream
+EW_MASK_COUNTER = 1 << 62
 
 
 def ln_name(scope, idx):
@@ -47,9 +63,24 @@ def ln_shared_in(names):
     return not any("/LayerNorm_" in k for k in names)
 
 
-def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True):
+def head_mask(heads):
+    """VQA_PT_HEAD_* bits of a head set"""
+    return sum({"bf": _lib.PT_HEAD_BF, "ws": _lib.PT_HEAD_WS, "ew": _lib.PT_HEAD_EW}[h] for h in heads)
+
+
+def report_keys(heads=CFG5_HEADS):
+    """the model's report keys: per category, per head type <kind>_<task>_{loss,acc,top_5_acc}; then total_loss"""
+    return ["%s_%s_%s" % (k, TASK_NAMES[h], m) for k in KINDS for h in heads
+            for m in ("loss", "acc", "top_%d_acc" % TOP_K)] + ["total_loss"]
+
+
+def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None):
+    """Variables of the model with head set `heads` (n_ctx: the enwiki context vocabulary, with 'ew')."""
+    heads = tuple(heads)
     s = {"wordset_map/learn": (n_ws, W), "V_GloVe/embed_map": (Vq, W), "L_GloVe/embed_map": (Vq, W),
          "LearnAnswerGloVe/embed_map": (A, W)}
+    if "ew" in heads:
+        s["enwiki_map/learn"] = (int(n_ctx), W)
 
     def fc(scope, fin, fout, n_ln):
         s[scope + "/fc/weights"] = (fin, fout)
@@ -65,19 +96,25 @@ def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True):
     s["encode_L_blank/rnn/gru_cell/gates/bias"] = (2 * H,)
     s["encode_L_blank/rnn/gru_cell/candidate/kernel"] = (W + H, H)
     s["encode_L_blank/rnn/gru_cell/candidate/bias"] = (H,)
-    fc("pooled_linear_l", D, H, 4)
-    fc("q_linear_l", H, H, 4)
-    fc("joint_fc", H, 2 * H, 4)
-    fc("wordset_ft", W, H, 2)
+    if "ew" in heads:
+        s["encode_L_enwiki/rnn/gru_cell/gates/kernel"] = (W + H, 2 * H)
+        s["encode_L_enwiki/rnn/gru_cell/gates/bias"] = (2 * H,)
+        s["encode_L_enwiki/rnn/gru_cell/candidate/kernel"] = (W + H, H)
+        s["encode_L_enwiki/rnn/gru_cell/candidate/bias"] = (H,)
+    fc("pooled_linear_l", D, H, 2 * len(heads))
+    fc("q_linear_l", H, H, 2 * len(heads))
+    fc("joint_fc", H, 2 * H, 2 * len(heads))
+    if "ws" in heads:
+        fc("wordset_ft", W, H, 2)
     fc("classifier", 2 * H, A, 0)
     return s
 
 
-def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True):
+def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None):
     """Random-init weights of the architecture (Xavier-uniform FCs, GRU gate bias 1, LN gamma 1,
     embeddings U(-0.01, 0.01); GloVe vectors are download-only)."""
     p = {}
-    for n, shp in variable_shapes(Vq, n_ws, A, W, D, H, ln_shared).items():
+    for n, shp in variable_shapes(Vq, n_ws, A, W, D, H, ln_shared, heads, n_ctx).items():
         if n.endswith("/weights") or n.endswith("/kernel"):
             lim = np.sqrt(6.0 / (shp[0] + shp[1]))
             p[n] = rng.uniform(-lim, lim, size=shp).astype(np.float32)
@@ -106,6 +143,23 @@ def add_length_sort(batch):
     sl = np.clip(lens[perm], 0, L)
     batch["blank_fill/sort"] = {"perm": perm, "inv": inv,
                                 "live_rows": (sl[None, :] > np.arange(L)[:, None]).sum(1).astype(np.int32)}
+    return add_context_sort(batch)
+
+
+def add_context_sort(batch):
+    """The enwiki contexts of both categories the same way: 'enwiki_context/sort' = permutation (longest first), inverse
+    and live_rows over the 2*B*n context rows, so that encode_L_enwiki also runs on the live prefix only."""
+    keys = [k + "_blank_fill/enwiki_context_len" for k in KINDS]
+    if any(k not in batch or torch.is_tensor(batch[k]) for k in keys):
+        return batch
+    lens = np.concatenate([np.asarray(batch[k]).reshape(-1) for k in keys]).astype(np.int64)
+    Lc = int(np.asarray(batch[KINDS[0] + "_blank_fill/enwiki_context"]).shape[-1])
+    perm = np.argsort(-lens, kind="stable")
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    sl = np.clip(lens[perm], 0, Lc)
+    batch["enwiki_context/sort"] = {"perm": perm, "inv": inv,
+                                    "live_rows": (sl[None, :] > np.arange(Lc)[:, None]).sum(1).astype(np.int32)}
     return batch
 
 
@@ -114,12 +168,21 @@ def _pad4(n):
 
 
 class PretrainEngine:
-    def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None):
+    def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
+                 heads=CFG5_HEADS, n_ctx=None):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
-        variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint."""
+        variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint.
+        heads: the head set (MODEL_HEADS); with 'ew', n_ctx = the enwiki context vocabulary and every batch carries
+        '<kind>_blank_fill/enwiki_context' [B,n,Lc] and '..._len' [B,n]."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("PretrainEngine needs a GPU (no CPU fallback)")
+        self.heads = tuple(heads)
+        if self.heads not in MODEL_HEADS.values():
+            raise ValueError("unsupported head set %r" % (self.heads,))
+        self.ext = self.heads != CFG5_HEADS          # vqa_pretrain_ext_* (the cfg-5 head set keeps vqa_pretrain_*)
+        self.n_ctx = int(n_ctx) if "ew" in self.heads else None
+        self.report_keys = report_keys(self.heads)
         self.device = torch.device(device)
         self.n, self.R, self.D, self.H, self.W, self.A = n, R, D, H, W, A
         self.Vq, self.n_ws, self.deterministic = Vq, n_ws, bool(deterministic)
@@ -133,25 +196,28 @@ class PretrainEngine:
     def _layout(self, ln_shared):
         """Flat parameter / gradient / Adam buffers and the C structs for one of the two LayerNorm variable sets."""
         self.ln_shared = bool(ln_shared)
-        self.shapes = variable_shapes(self.Vq, self.n_ws, self.A, self.W, self.D, self.H, self.ln_shared)
+        self.shapes = variable_shapes(self.Vq, self.n_ws, self.A, self.W, self.D, self.H, self.ln_shared, self.heads,
+                                      self.n_ctx)
+        sparse = [k for k in SPARSE_VARS if k in self.shapes]
         dense = sorted(k for k in self.shapes if k not in NO_GRAD_VARS and k not in SPARSE_VARS)
         groups = [[k for k in dense if k.startswith(sc)] for sc in PHASE_SCOPES]
         assert sorted(sum(groups, [])) == dense, "a variable outside the phase scopes"
-        self.train_names = list(SPARSE_VARS) + sum(groups, [])
+        self.train_names = sparse + sum(groups, [])
         off, self._tab = 0, {}
         for k in self.train_names:
             cnt = int(np.prod(self.shapes[k]))
             self._tab[k] = (off, cnt)
             off += _pad4(cnt)
         self.n_train = off
-        # bucket bounds (floats): wordset_map [0, b0), L_GloVe [b0, b1), GRU [b1, b2), heads [b2, b3), rest [b3, n_train)
+        # bucket bounds (floats): wordset_map [0, b0), L_GloVe (+ enwiki_map) [b0, b1), GRUs [b1, b2), heads [b2, b3),
+        # rest [b3, n_train)
         ends, o = [], 0
-        for names in ([SPARSE_VARS[0]], [SPARSE_VARS[1]], groups[0], groups[1], groups[2]):
+        for names in ([sparse[0]], sparse[1:], groups[0], groups[1], groups[2]):
             o += sum(_pad4(int(np.prod(self.shapes[k]))) for k in names)
             ends.append(o)
         self._bounds = tuple(ends)
         assert ends[-1] == self.n_train
-        self.sparse_floats = sum(_pad4(int(np.prod(self.shapes[k]))) for k in SPARSE_VARS)
+        self.sparse_floats = sum(_pad4(int(np.prod(self.shapes[k]))) for k in sparse)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.train_flat = torch.zeros(self.n_train, **f32)
         self.grad_flat = torch.zeros(self.n_train + 4, **f32)      # tail slot 0: un-aggregated slice sum of squares
@@ -183,9 +249,20 @@ class PretrainEngine:
                                           (k + "/ws_joint", n * 2 * H, KEEP_JOINT)):
                 out[name] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image, keep, self.device)
                 off += Bg * per_image
+        if "ew" in self.heads:
+            # {kind}/ew_joint from their own counter range: the cfg-5 masks above keep their bits for (seed, step, row)
+            per_image = n * 2 * H
+            off = EW_MASK_COUNTER + step * (2 * Bg * per_image)
+            for k in KINDS:
+                out[k + "/ew_joint"] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image, KEEP_JOINT,
+                                                        self.device)
+                off += Bg * per_image
         return out
 
     def _param_struct(self, table):
+        if self.ext:
+            return self._param_struct_ext(table)
+
         def fc(scope, n_ln):
             f = _lib.PtFc(w=table[scope + "/fc/weights"].data_ptr(), b=table[scope + "/fc/biases"].data_ptr())
             for i in range(min(n_ln, 1) if self.ln_shared else n_ln):
@@ -200,6 +277,31 @@ class PretrainEngine:
             gru_bg=table[g + "gates/bias"].data_ptr(), gru_wc=table[g + "candidate/kernel"].data_ptr(),
             gru_bc=table[g + "candidate/bias"].data_ptr(), pooled_linear_l=fc("pooled_linear_l", 4),
             q_linear_l=fc("q_linear_l", 4), joint_fc=fc("joint_fc", 4), wordset_ft=fc("wordset_ft", 2),
+            classifier=fc("classifier", 0))
+
+    def _param_struct_ext(self, table):
+        nh = 2 * len(self.heads)
+
+        def fc(scope, n_ln):
+            f = _lib.PtFc6()
+            if scope + "/fc/weights" not in table:       # wordset_ft of a model without the word-set head
+                return f
+            f.w, f.b = table[scope + "/fc/weights"].data_ptr(), table[scope + "/fc/biases"].data_ptr()
+            for i in range(min(n_ln, 1) if self.ln_shared else n_ln):
+                f.beta[i] = table[ln_name(scope, i) + "/beta"].data_ptr()
+                f.gamma[i] = table[ln_name(scope, i) + "/gamma"].data_ptr()
+            return f
+        g, e = "encode_L_blank/rnn/gru_cell/", "encode_L_enwiki/rnn/gru_cell/"
+        return _lib.PtExtParams(
+            wordset_map=table["wordset_map/learn"].data_ptr(), l_glove=table["L_GloVe/embed_map"].data_ptr(),
+            enwiki_map=table["enwiki_map/learn"].data_ptr(),
+            spat_v_linear_v=fc("spat_v_linear_v", 2), spat_q_linear_v=fc("spat_q_linear_v", 2),
+            spat_att_score=fc("spat_att/compute/score", 0), gru_wg=table[g + "gates/kernel"].data_ptr(),
+            gru_bg=table[g + "gates/bias"].data_ptr(), gru_wc=table[g + "candidate/kernel"].data_ptr(),
+            gru_bc=table[g + "candidate/bias"].data_ptr(), egru_wg=table[e + "gates/kernel"].data_ptr(),
+            egru_bg=table[e + "gates/bias"].data_ptr(), egru_wc=table[e + "candidate/kernel"].data_ptr(),
+            egru_bc=table[e + "candidate/bias"].data_ptr(), pooled_linear_l=fc("pooled_linear_l", nh),
+            q_linear_l=fc("q_linear_l", nh), joint_fc=fc("joint_fc", nh), wordset_ft=fc("wordset_ft", 2),
             classifier=fc("classifier", 0))
 
     def _dev(self, v, dtype):
@@ -274,13 +376,38 @@ class PretrainEngine:
             perm, inv, live = srt["_dev"]
             bs.perm, bs.inv, bs.live_rows = perm.data_ptr(), inv.data_ptr(), live.ctypes.data
             keep.append(srt["_dev"])
-        return bs, B, L, keep
+        if not self.ext:
+            return bs, B, L, keep
+        bx = _lib.PtExtBatch(base=bs)
+        Lc = None
+        for ki, k in enumerate(KINDS):
+            pre = k + "_blank_fill/"
+            ck = bx.ctx[ki]
+            ck.context = get(pre + "enwiki_context", torch.int32).data_ptr()
+            ck.context_len = get(pre + "enwiki_context_len", torch.int32).data_ptr()
+            Lk = int(cache[pre + "enwiki_context"].shape[-1])
+            assert Lc is None or Lc == Lk, "object / attribute contexts must be padded to one length"
+            Lc = Lk
+            if masks is not None:
+                ck.keep_ew_joint = masks[k + "/ew_joint"].data_ptr()
+        srt = batch.get("enwiki_context/sort")
+        if srt is not None:       # contexts in length order (add_context_sort)
+            if "_dev" not in srt:
+                live = np.ascontiguousarray(srt["live_rows"], dtype=np.int32)
+                assert live.shape == (Lc,) and len(srt["perm"]) == 2 * int(cache[KINDS[0] + "_blank_fill/blanks_len"].numel())
+                srt["_dev"] = (self._dev(np.asarray(srt["perm"]), torch.int32),
+                               self._dev(np.asarray(srt["inv"]), torch.int32), live)
+            perm, inv, live = srt["_dev"]
+            bx.ctx_perm, bx.ctx_inv, bx.ctx_live_rows = perm.data_ptr(), inv.data_ptr(), live.ctypes.data
+            keep.append(srt["_dev"])
+        self._Lc = Lc
+        return bx, B, L, keep
 
     def tensor(self, name, dtype=torch.float32):
         """Named intermediate of the last forward as a torch view of the workspace (vqa_pretrain_tensor)."""
         off, n = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.vqa_pretrain_tensor(C.byref(self.dims), name.encode(), C.byref(off), C.byref(n)),
-                   "vqa_pretrain_tensor(%s)" % name)
+        fn = self.lib.vqa_pretrain_ext_tensor if self.ext else self.lib.vqa_pretrain_tensor
+        _lib.check(fn(C.byref(self.dims), name.encode(), C.byref(off), C.byref(n)), "vqa_pretrain_tensor(%s)" % name)
         return self.workspace[off.value:off.value + 4 * n.value].view(dtype)
 
     def _stream(self):
@@ -312,37 +439,48 @@ class PretrainEngine:
                         keep_joint=KEEP_JOINT)
         if global_valid is not None:
             d.global_valid[0], d.global_valid[1] = float(global_valid[0]), float(global_valid[1])
-        need = int(self.lib.vqa_pretrain_workspace_bytes(C.byref(d)))
+        if self.ext:
+            d = _lib.PtExtDims(base=d, heads=head_mask(self.heads), Lc=self._Lc or 0, n_ctx=self.n_ctx or 0)
+        need = int((self.lib.vqa_pretrain_ext_workspace_bytes if self.ext else self.lib.vqa_pretrain_workspace_bytes)(
+            C.byref(d)))
         if need <= 0:
             raise _lib.VqaHotError("vqa_pretrain_workspace_bytes rejected the dims")
         if self.workspace is None or need > self.workspace.numel():
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self.dims, self._bs, self._keepalive = d, bs, keep
-        _lib.check(self.lib.vqa_pretrain_forward(C.byref(d), C.byref(self._p_struct), C.byref(bs),
-                                                 C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
-                                                 1 if want_dz else 0, self._stream()), "vqa_pretrain_forward")
+        fwd = self.lib.vqa_pretrain_ext_forward if self.ext else self.lib.vqa_pretrain_forward
+        _lib.check(fwd(C.byref(d), C.byref(self._p_struct), C.byref(bs), C.c_void_p(self.workspace.data_ptr()),
+                       self.workspace.numel(), 1 if want_dz else 0, self._stream()), "vqa_pretrain_forward")
         Bn = B * self.n
         self._tape = {"B": B, "kinds": {
-            k: {"att": self.tensor(k + "/att").view(Bn, self.R), "pooled": self.tensor(k + "/pooled").view(Bn, self.D),
-                "blank_fill": {"z": self.tensor(k + "/bf/z").view(Bn, self.A)},
-                "wordset": {"z": self.tensor(k + "/ws/z").view(Bn, self.A)}} for k in KINDS}}
+            k: dict({"att": self.tensor(k + "/att").view(Bn, self.R), "pooled": self.tensor(k + "/pooled").view(Bn, self.D)},
+                    **{TASK_NAMES[h]: {"z": self.tensor("%s/%s/z" % (k, h)).view(Bn, self.A)} for h in self.heads})
+            for k in KINDS}}
 
     def fetch_report(self, reduce=False, group=None):
-        """report dict of the reference (13 scalars): <kind>_<task>_{loss,acc,top_5_acc}, total_loss.  reduce: data
-        parallel -- every scalar is a sum over the shard's rows already divided by the GLOBAL valid count
-        (forward(global_valid=...)), so a SUM all-reduce gives what one process on the whole batch reports."""
+        """report dict of the reference (13 scalars, 19 with the enwiki heads): <kind>_<task>_{loss,acc,top_5_acc},
+        total_loss.  reduce: data parallel -- every scalar is a sum over the shard's rows already divided by the GLOBAL
+        valid count (forward(global_valid=...)), so a SUM all-reduce gives what one process on the whole batch reports."""
         import torch.distributed as dist
-        r = self.tensor("report")[:13]
+        nk = len(self.report_keys)
+        r = self.tensor("report")[:nk]
         if reduce and dist.is_initialized() and dist.get_world_size(group) > 1:
             r = r.cpu() if dist.get_backend(group) == "gloo" else r.clone()
             dist.all_reduce(r, op=dist.ReduceOp.SUM, group=group)
         r = r.cpu().numpy()
-        self.report = {self.lib.vqa_pretrain_report_key(i).decode(): float(r[i]) for i in range(13)}
+        self.report = {self.report_key(i): float(r[i]) for i in range(nk)}
         return self.report
+
+    def report_key(self, i):
+        """name of report scalar i (vqa_pretrain_report_key / vqa_pretrain_ext_report_key)"""
+        if self.ext:
+            return self.lib.vqa_pretrain_ext_report_key(head_mask(self.heads), i).decode()
+        return self.lib.vqa_pretrain_report_key(i).decode()
 
     def _backward_phases(self, phases):
         tail = self.grad_flat[self.n_train:]
-        _lib.check(self.lib.vqa_pretrain_backward_phases(
+        fn = self.lib.vqa_pretrain_ext_backward_phases if self.ext else self.lib.vqa_pretrain_backward_phases
+        _lib.check(fn(
             C.byref(self.dims), C.byref(self._p_struct), C.byref(self._g_struct), C.byref(self._bs),
             C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), C.c_void_p(tail.data_ptr()), phases,
             self._stream()), "vqa_pretrain_backward_phases")

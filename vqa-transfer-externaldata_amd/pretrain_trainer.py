@@ -15,9 +15,15 @@ import torch
 from . import dataset_vlmap
 from .log import log
 from .model_vlmap_bf_or_wordset_withatt_sp import Model
+from .model_vlmap_bf_or_wordset_enwiki_withatt_sp import Model as EnwikiModel
+from .model_vlmap_bf_enwiki_withatt_sp import Model as BfEnwikiModel
 from .pretrain import export_word_weights  # noqa: F401  (re-exported: the bridge lives with the engine)
 
-MODEL_TYPES = ["vlmap_bf_or_wordset_withatt_sp"]
+# cfg-5 and the two models the reference's pipeline pre-trains (run.py:104-105, vqa_all_run.py:101-102)
+_MODEL_CLASSES = {"vlmap_bf_or_wordset_withatt_sp": Model,
+                  "vlmap_bf_or_wordset_enwiki_withatt_sp": EnwikiModel,
+                  "vlmap_bf_enwiki_withatt_sp": BfEnwikiModel}
+MODEL_TYPES = list(_MODEL_CLASSES)
 
 
 class Trainer(object):
@@ -27,7 +33,7 @@ class Trainer(object):
         if model_type not in MODEL_TYPES:
             raise ValueError("model_type %r is a pre-training ablation that is out of scope (supported: %s)"
                              % (model_type, ", ".join(MODEL_TYPES)))
-        return Model
+        return _MODEL_CLASSES[model_type]
 
     def __init__(self, config, dataset):
         self.config = config

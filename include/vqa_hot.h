@@ -349,6 +349,26 @@ int vqa_softmax_ce_fwd(const float* z, const int32_t* label, const float* valid,
 /* tuning / A-B switch: 1 (default) = rows of A <= 4096 (A % 4 == 0, 16-byte aligned) are held in registers and read
  * once, 0 = the three-pass kernel for every A */
 int vqa_softmax_set_fast(int on);
+/* The same loss on the two logit blocks of a "no composition" head (vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py:
+ * v_logit from classifier_v, l_logit from classifier_l), one head per entry, every head of a step in ONE launch; each
+ * block is read once and the results are BITWISE those of vqa_softmax_ce_fwd (in both of its paths: rows held in
+ * registers for A <= 4096, A % 4 == 0 and 16-byte aligned blocks, else -- or after vqa_softmax_set_fast(0) -- three
+ * passes):
+ *   split 0 (SUM):   one CE of zv + zl (formed per element in float32, never stored) -> stats_v; its dz goes to BOTH
+ *                    dzv and dzl; stats_l is not written (may be NULL)
+ *   split 1 (SPLIT): one CE of zv -> stats_v / dzv and one of zl -> stats_l / dzl
+ * label / valid / inv_valid_sum as for vqa_softmax_ce_fwd; dzv and dzl both NULL (no gradient) or both set. */
+#define VQA_SOFTMAX_PAIR_MAX 8
+typedef struct {
+    const float *zv, *zl;                   /* [rows,A] each */
+    const int32_t* label;                   /* [rows] */
+    const float* valid;                     /* [rows] */
+    const float* inv_valid_sum;             /* device scalar 1 / sum(valid) (NULL only without dz) */
+    int32_t split;                          /* 0 SUM, 1 SPLIT */
+    float *stats_v, *stats_l;               /* [rows,4] */
+    float *dzv, *dzl;                       /* [rows,A] or NULL */
+} vqa_softmax_pair_t;
+int vqa_softmax_ce_pair_fwd(const vqa_softmax_pair_t* heads, int n_heads, int topk, int rows, int A, void* stream);
 /* report[13] in the order of vqa_report_key(i): means over B + guarded ratios. */
 int vqa_report_reduce(const float* stats, int B, float* report, void* stream);
 #define VQA_REPORT_COUNT 13
@@ -698,6 +718,71 @@ int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pre
                               int64_t workspace_bytes, float* slice_sq, void* stream);
 int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
                                      const vqa_pretrain_ext_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
+                                     void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+
+/* ------------------------------------------------------------------------
+ * "No composition" pre-training (csrc/pretrain_model.hip): vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py (=
+ * model_vlmap_nocarch_bf_or_wordset_withatt_sp.py) with heads VQA_PT_HEAD_BF | VQA_PT_HEAD_WS and
+ * model_vlmap_noc_bf_or_enwiki_withatt_sp.py with VQA_PT_HEAD_BF | VQA_PT_HEAD_EW (any other mask: VQA_ERR_ARG).
+ * Everything up to v_linear_l (pooled_linear_l) and l_linear_l (q_linear_l) is the variable-head-set model above; the
+ * Hadamard product, joint_fc and classifier are replaced per head by two branches
+ *   v_joint = dropout(relu(LN(v_linear_l @ joint_v + b)), 0.5)     l_joint = dropout(relu(LN(l_linear_l @ joint_l + b)), 0.5)
+ *   v_logit = v_joint @ classifier_v + b                           l_logit = l_joint @ classifier_l + b
+ * with the loss of the head's type: blank fill SUM (one masked softmax-CE of v_logit + l_logit), word set / enwiki SPLIT
+ * (one of v_logit and one of l_logit, both in the total).  Head h = 2 r + k as for vqa_pretrain_ext_*; without
+ * VQA_FLAG_SHARED_LN it owns LayerNorm slot h of pooled_linear_l, q_linear_l, joint_v and joint_l.  The v branch's
+ * dropout masks are those of vqa_pretrain_ext_batch_t (keep_bf_joint / keep_ws_joint / keep_ew_joint), the l branch has
+ * its own.  Loss and dz of every head: vqa_softmax_ce_pair_fwd, one launch.
+ * Named intermediates (vqa_pretrain_noc_tensor): those of vqa_pretrain_ext_tensor without jin / j / z / dz, with
+ * "<obj|attr>/<bf|ws|ew>/{jv_pre,jv,jl_pre,jl,zv,zl,dzv,dzl,stats,stats_l}" (stats = the SUM head's or the v branch's,
+ * stats_l = the l branch's), "report" (19 floats in the order of vqa_pretrain_noc_report_key(heads, i): for k in (obj,
+ * attr), for each head type: SUM <kind>_<task>_{loss,acc,top_5_acc}, SPLIT <kind>_<task>_v_{...} then
+ * <kind>_<task>_l_{...}; then total_loss = the sum of the six losses).
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    float* wordset_map;                      /* wordset_map/learn [n_ws,W] */
+    float* l_glove;                          /* L_GloVe/embed_map [Vq,W] */
+    float* enwiki_map;                       /* enwiki_map/learn [n_ctx,W] (NULL without VQA_PT_HEAD_EW) */
+    vqa_pt_fc6_t spat_v_linear_v;            /* [6,H]   LN x2 */
+    vqa_pt_fc6_t spat_q_linear_v;            /* [6,H]   LN x2 */
+    vqa_pt_fc6_t spat_att_score;             /* [H,1] */
+    float *gru_wg, *gru_bg, *gru_wc, *gru_bc;      /* encode_L_blank/rnn/gru_cell/... */
+    float *egru_wg, *egru_bg, *egru_wc, *egru_bc;  /* encode_L_enwiki/rnn/gru_cell/... (NULL without VQA_PT_HEAD_EW) */
+    vqa_pt_fc6_t pooled_linear_l;            /* [D,H]   LN x4 */
+    vqa_pt_fc6_t q_linear_l;                 /* [H,H]   LN x4 */
+    vqa_pt_fc6_t joint_v;                    /* [H,2H]  LN x4 */
+    vqa_pt_fc6_t joint_l;                    /* [H,2H]  LN x4 */
+    vqa_pt_fc6_t wordset_ft;                 /* [W,H]   LN x2 (all NULL without VQA_PT_HEAD_WS) */
+    vqa_pt_fc6_t classifier_v;               /* [2H,A] */
+    vqa_pt_fc6_t classifier_l;               /* [2H,A] */
+} vqa_pretrain_noc_params_t;
+
+typedef struct {                             /* the l branch's dropout keep-masks of one category, [B*n,2H] 0/1 or NULL */
+    const uint8_t *keep_bf_l_joint, *keep_ws_l_joint, *keep_ew_l_joint;
+} vqa_pretrain_noc_kind_t;
+
+typedef struct {
+    vqa_pretrain_ext_batch_t base;           /* as for vqa_pretrain_ext_*; its joint keep-masks serve the v branch */
+    vqa_pretrain_noc_kind_t l[2];            /* 0 = object, 1 = attribute */
+} vqa_pretrain_noc_batch_t;
+
+int64_t vqa_pretrain_noc_workspace_bytes(const vqa_pretrain_ext_dims_t* dims);
+int vqa_pretrain_noc_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes, int64_t* n_elems);
+/* report key i of head set `heads`; NULL past the last or for a head set without a noc model */
+const char* vqa_pretrain_noc_report_key(int heads, int i);
+int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* params,
+                             const vqa_pretrain_noc_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                             void* stream);
+/* grads: same layout as params (every member the model has non-NULL; wordset_map always).  Overwritten; the embedding
+ * tables are cleared and scatter-added.  Phases and buckets as vqa_pretrain_ext_backward_phases, the noc scopes in
+ * phase 1:
+ *   1  stacked heads: classifier_v / classifier_l, joint_v / joint_l, pooled_linear_l, q_linear_l
+ *   2, 4, 8  as for vqa_pretrain_ext_backward_phases (writes slice_sq in phase 8) */
+int vqa_pretrain_noc_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* params,
+                              const vqa_pretrain_noc_params_t* grads, const vqa_pretrain_noc_batch_t* batch, void* workspace,
+                              int64_t workspace_bytes, float* slice_sq, void* stream);
+int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* params,
+                                     const vqa_pretrain_noc_params_t* grads, const vqa_pretrain_noc_batch_t* batch,
                                      void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
 
 /* ------------------------------------------------------------------------

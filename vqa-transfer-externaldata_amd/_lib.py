@@ -111,6 +111,32 @@ class PtExtBatch(C.Structure):
                 ("ctx_live_rows", C.c_void_p)]
 
 
+class PtNocParams(C.Structure):
+    _fields_ = [("wordset_map", C.c_void_p), ("l_glove", C.c_void_p), ("enwiki_map", C.c_void_p),
+                ("spat_v_linear_v", PtFc6), ("spat_q_linear_v", PtFc6), ("spat_att_score", PtFc6)] + \
+               [(k, C.c_void_p) for k in ("gru_wg", "gru_bg", "gru_wc", "gru_bc", "egru_wg", "egru_bg", "egru_wc",
+                                          "egru_bc")] + \
+               [(k, PtFc6) for k in ("pooled_linear_l", "q_linear_l", "joint_v", "joint_l", "wordset_ft", "classifier_v",
+                                     "classifier_l")]
+
+
+class PtNocKind(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("keep_bf_l_joint", "keep_ws_l_joint", "keep_ew_l_joint")]
+
+
+class PtNocBatch(C.Structure):
+    _fields_ = [("base", PtExtBatch), ("l", PtNocKind * 2)]
+
+
+SOFTMAX_PAIR_MAX = 8     # VQA_SOFTMAX_PAIR_MAX
+
+
+class SoftmaxPair(C.Structure):
+    _fields_ = [("zv", C.c_void_p), ("zl", C.c_void_p), ("label", C.c_void_p), ("valid", C.c_void_p),
+                ("inv_valid_sum", C.c_void_p), ("split", C.c_int32), ("stats_v", C.c_void_p), ("stats_l", C.c_void_p),
+                ("dzv", C.c_void_p), ("dzl", C.c_void_p)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol declared in include/vqa_hot.h
@@ -170,6 +196,7 @@ SIGNATURES = {
     "vqa_tanh_bwd": (_I, [_P, _P, _P, _L, _P]),
     "vqa_softmax_ce_fwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
     "vqa_softmax_set_fast": (_I, [_I]),
+    "vqa_softmax_ce_pair_fwd": (_I, [C.POINTER(SoftmaxPair), _I, _I, _I, _I, _P]),
     "vqa_colsum": (_I, [_P, _I, _I, _I, _P, _P, _L, _P]),
     "vqa_colsum_workspace_floats": (_L, [_I, _I]),
     "vqa_colsum3": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
@@ -277,6 +304,15 @@ SIGNATURES = {
                                        C.POINTER(PtExtBatch), _P, _L, _P, _P]),
     "vqa_pretrain_ext_backward_phases": (_I, [C.POINTER(PtExtDims), C.POINTER(PtExtParams), C.POINTER(PtExtParams),
                                               C.POINTER(PtExtBatch), _P, _L, _P, _I, _P]),
+    "vqa_pretrain_noc_workspace_bytes": (_L, [C.POINTER(PtExtDims)]),
+    "vqa_pretrain_noc_tensor": (_I, [C.POINTER(PtExtDims), C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vqa_pretrain_noc_report_key": (C.c_char_p, [_I, _I]),
+    "vqa_pretrain_noc_forward": (_I, [C.POINTER(PtExtDims), C.POINTER(PtNocParams), C.POINTER(PtNocBatch), _P, _L, _I,
+                                      _P]),
+    "vqa_pretrain_noc_backward": (_I, [C.POINTER(PtExtDims), C.POINTER(PtNocParams), C.POINTER(PtNocParams),
+                                       C.POINTER(PtNocBatch), _P, _L, _P, _P]),
+    "vqa_pretrain_noc_backward_phases": (_I, [C.POINTER(PtExtDims), C.POINTER(PtNocParams), C.POINTER(PtNocParams),
+                                              C.POINTER(PtNocBatch), _P, _L, _P, _I, _P]),
 }
 
 ABI_VERSION = 5      # VQA_HOT_ABI_VERSION of include/vqa_hot.h

@@ -176,26 +176,42 @@ __global__ __launch_bounds__(1024) void report_reduce_kernel(const float* __rest
     }
 }
 
+// Row loads of the masked softmax-CE bodies below: one logit row, or the element-wise float32 sum of two (the SUM heads
+// of the "no composition" pre-training models: zv + zl is formed in registers and never stored)
+struct RowOne {
+    const float* __restrict__ z;
+    __device__ __forceinline__ float at(int64_t i) const { return z[i]; }
+    __device__ __forceinline__ float4 at4(int64_t i) const { return reinterpret_cast<const float4*>(z)[i]; }
+};
+struct RowSum {
+    const float* __restrict__ z;
+    const float* __restrict__ z2;
+    __device__ __forceinline__ float at(int64_t i) const { return z[i] + z2[i]; }
+    __device__ __forceinline__ float4 at4(int64_t i) const {
+        const float4 a = reinterpret_cast<const float4*>(z)[i], b = reinterpret_cast<const float4*>(z2)[i];
+        return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+};
+
 // n-way softmax cross-entropy with a validity mask, top-1 and top-k hit (cfg-5 pre-training model:
 // n_way_classification_loss, vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py:675-706).
 // One workgroup per row.  stats[row] = {ce*valid, (argmax == label)*valid, (label in top-k)*valid, valid};
-// dz[row,:] = (softmax - onehot) * valid * inv_valid_sum[0]   (inv_valid_sum = 1 / sum(valid), on device)
-__global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ z, const int32_t* __restrict__ label,
-                                                         const float* __restrict__ valid, int topk,
-                                                         const float* __restrict__ inv_valid_sum,
-                                                         float* __restrict__ stats, float* __restrict__ dz, int A) {
+// dz[row,:] = (softmax - onehot) * valid * inv_valid_sum[0]   (inv_valid_sum = 1 / sum(valid), on device), also
+// written to dz2 when that is set.  zr, s, dz and dz2 point at the row.
+template <class Row>
+__device__ __forceinline__ void softmax_ce_row(const Row zr, int lab, float vm, int topk,
+                                               const float* __restrict__ inv_valid_sum, float* __restrict__ s,
+                                               float* __restrict__ dz, float* __restrict__ dz2, int A) {
     __shared__ float red[16];
     __shared__ float redv[4];
     __shared__ int redi[4];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* zb = z + (int64_t)b * A;
-    const int lab = label[b];
-    const float zl = zb[min(max(lab, 0), A - 1)];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float zl = zr.at(min(max(lab, 0), A - 1));
     float mx = -INFINITY;
     ArgMax am{-INFINITY, 0x7fffffff};
     int rank = 0;   // entries that tf.nn.top_k orders before the label: larger, or equal with a lower index
     for (int a = threadIdx.x; a < A; a += 256) {
-        const float x = zb[a];
+        const float x = zr.at(a);
         mx = fmaxf(mx, x);
         if (x > am.v) { am.v = x; am.i = a; }
         rank += (x > zl || (x == zl && a < lab)) ? 1 : 0;
@@ -212,17 +228,18 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     ArgMax best{redv[0], redi[0]};
     for (int k = 1; k < 4; ++k) best = argmax_combine(best, ArgMax{redv[k], redi[k]});
     float se = 0.f;
-    for (int a = threadIdx.x; a < A; a += 256) se += expf(zb[a] - mx);
+    for (int a = threadIdx.x; a < A; a += 256) se += expf(zr.at(a) - mx);
     se = block_sum(se, red);
     const float lse = mx + logf(se);
-    const float vm = valid[b];
     if (dz != nullptr) {
         const float sc = vm * inv_valid_sum[0];
-        for (int a = threadIdx.x; a < A; a += 256)
-            dz[(int64_t)b * A + a] = (expf(zb[a] - lse) - (a == lab ? 1.f : 0.f)) * sc;
+        for (int a = threadIdx.x; a < A; a += 256) {
+            const float g = (expf(zr.at(a) - lse) - (a == lab ? 1.f : 0.f)) * sc;
+            dz[a] = g;
+            if (dz2 != nullptr) dz2[a] = g;
+        }
     }
     if (threadIdx.x == 0) {
-        float* s = stats + (int64_t)b * 4;
         s[0] = (lse - zl) * vm;
         s[1] = (best.i == lab ? 1.f : 0.f) * vm;
         s[2] = (frank < (float)topk ? 1.f : 0.f) * vm;
@@ -230,30 +247,36 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     }
 }
 
+__global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ z, const int32_t* __restrict__ label,
+                                                         const float* __restrict__ valid, int topk,
+                                                         const float* __restrict__ inv_valid_sum,
+                                                         float* __restrict__ stats, float* __restrict__ dz, int A) {
+    const int b = blockIdx.x;
+    softmax_ce_row(RowOne{z + (int64_t)b * A}, label[b], valid[b], topk, inv_valid_sum, stats + (int64_t)b * 4,
+                   dz != nullptr ? dz + (int64_t)b * A : nullptr, nullptr, A);
+}
+
 // The same with the row held in registers (A <= 4096, A % 4 == 0, 16-byte aligned rows): thread t owns the float4s
 // t, t+256, ... (NV of them), so the logits are read ONCE with 16-byte loads, all of a thread's loads in flight
 // together, instead of three dependent scalar passes over the row, and dz leaves as 16-byte stores.  Same arithmetic per
-// element as softmax_ce_kernel (exp(z - lse) for dz); only the order of the sum of exponentials differs.
-template <int NV>
-__global__ __launch_bounds__(256) void softmax_ce_reg_kernel(const float* __restrict__ z, const int32_t* __restrict__ label,
-                                                             const float* __restrict__ valid, int topk,
-                                                             const float* __restrict__ inv_valid_sum,
-                                                             float* __restrict__ stats, float* __restrict__ dz, int A) {
+// element as softmax_ce_row (exp(z - lse) for dz); only the order of the sum of exponentials differs.
+template <int NV, class Row>
+__device__ __forceinline__ void softmax_ce_row_reg(const Row zr, int lab, float vm, int topk,
+                                                   const float* __restrict__ inv_valid_sum, float* __restrict__ s,
+                                                   float* __restrict__ dz, float* __restrict__ dz2, int A) {
     __shared__ float red[16];
     __shared__ float redv[4];
     __shared__ int redi[4];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int A4 = A >> 2;
-    const float4* zb = reinterpret_cast<const float4*>(z + (int64_t)b * A);
     float x[NV][4];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int i = threadIdx.x + 256 * k;
-        const float4 v = i < A4 ? zb[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        const float4 v = i < A4 ? zr.at4(i) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
         x[k][0] = v.x; x[k][1] = v.y; x[k][2] = v.z; x[k][3] = v.w;
     }
-    const int lab = label[b];
-    const float zl = z[(int64_t)b * A + min(max(lab, 0), A - 1)];
+    const float zl = zr.at(min(max(lab, 0), A - 1));
     float mx = -INFINITY;
     ArgMax am{-INFINITY, 0x7fffffff};
     int rank = 0;
@@ -285,10 +308,8 @@ __global__ __launch_bounds__(256) void softmax_ce_reg_kernel(const float* __rest
         for (int j = 0; j < 4; ++j) se += expf(x[k][j] - mx);     // exp(-inf) = 0 for the padding
     se = block_sum(se, red);
     const float lse = mx + logf(se);
-    const float vm = valid[b];
     if (dz != nullptr) {
         const float sc = vm * inv_valid_sum[0];
-        float4* db = reinterpret_cast<float4*>(dz + (int64_t)b * A);
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
             const int i = threadIdx.x + 256 * k;
@@ -296,16 +317,57 @@ __global__ __launch_bounds__(256) void softmax_ce_reg_kernel(const float* __rest
                 float o[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = (expf(x[k][j] - lse) - (4 * i + j == lab ? 1.f : 0.f)) * sc;
-                db[i] = make_float4(o[0], o[1], o[2], o[3]);
+                reinterpret_cast<float4*>(dz)[i] = make_float4(o[0], o[1], o[2], o[3]);
+                if (dz2 != nullptr) reinterpret_cast<float4*>(dz2)[i] = make_float4(o[0], o[1], o[2], o[3]);
             }
         }
     }
     if (threadIdx.x == 0) {
-        float* s = stats + (int64_t)b * 4;
         s[0] = (lse - zl) * vm;
         s[1] = (best.i == lab ? 1.f : 0.f) * vm;
         s[2] = (frank < (float)topk ? 1.f : 0.f) * vm;
         s[3] = vm;
+    }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void softmax_ce_reg_kernel(const float* __restrict__ z, const int32_t* __restrict__ label,
+                                                             const float* __restrict__ valid, int topk,
+                                                             const float* __restrict__ inv_valid_sum,
+                                                             float* __restrict__ stats, float* __restrict__ dz, int A) {
+    const int b = blockIdx.x;
+    softmax_ce_row_reg<NV>(RowOne{z + (int64_t)b * A}, label[b], valid[b], topk, inv_valid_sum, stats + (int64_t)b * 4,
+                           dz != nullptr ? dz + (int64_t)b * A : nullptr, nullptr, A);
+}
+
+// Paired masked softmax-CE of the "no composition" heads (vqa_softmax_ce_pair_fwd): task blockIdx.y is one CE over
+// `rows` rows -- of z alone (a SPLIT head's branch) or of z + z2 (a SUM head; its dz goes to dz and dz2) -- so one
+// launch covers every head of a step and each logit block is read once.  NV = 0: the three-pass body.
+struct PairTask {
+    const float *z, *z2;
+    const int32_t* label;
+    const float *valid, *inv;
+    float *stats, *dz, *dz2;
+};
+struct PairArgs { PairTask t[2 * VQA_SOFTMAX_PAIR_MAX]; };
+
+template <int NV>
+__global__ __launch_bounds__(256) void softmax_ce_pair_kernel(const PairArgs a, int topk, int A) {
+    const PairTask& t = a.t[blockIdx.y];
+    const int b = blockIdx.x;
+    const int64_t o = (int64_t)b * A;
+    const int lab = t.label[b];
+    const float vm = t.valid[b];
+    float* s = t.stats + (int64_t)b * 4;
+    float* dz = t.dz != nullptr ? t.dz + o : nullptr;
+    float* dz2 = t.dz2 != nullptr ? t.dz2 + o : nullptr;
+    if (NV == 0) {
+        if (t.z2 != nullptr) softmax_ce_row(RowSum{t.z + o, t.z2 + o}, lab, vm, topk, t.inv, s, dz, dz2, A);
+        else softmax_ce_row(RowOne{t.z + o}, lab, vm, topk, t.inv, s, dz, dz2, A);
+    } else {
+        constexpr int NR = NV > 0 ? NV : 1;
+        if (t.z2 != nullptr) softmax_ce_row_reg<NR>(RowSum{t.z + o, t.z2 + o}, lab, vm, topk, t.inv, s, dz, dz2, A);
+        else softmax_ce_row_reg<NR>(RowOne{t.z + o}, lab, vm, topk, t.inv, s, dz, dz2, A);
     }
 }
 int g_softmax_reg = 1;   // A/B switch (vqa_softmax_set_fast)
@@ -501,6 +563,45 @@ extern "C" int vqa_softmax_ce_fwd(const float* z, const int32_t* label, const fl
         }
     } else {
         hipLaunchKernelGGL(softmax_ce_kernel, dim3(rows), dim3(256), 0, st, z, label, valid, topk, inv_valid_sum, stats, dz, A);
+    }
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+extern "C" int vqa_softmax_ce_pair_fwd(const vqa_softmax_pair_t* heads, int n_heads, int topk, int rows, int A,
+                                       void* stream) {
+    VQA_REQUIRE(heads && n_heads > 0 && n_heads <= VQA_SOFTMAX_PAIR_MAX && rows >= 0 && A > 0 && topk > 0, VQA_ERR_ARG);
+    PairArgs args{};
+    int nt = 0;
+    bool aligned = true;
+    for (int h = 0; h < n_heads; ++h) {
+        const vqa_softmax_pair_t& p = heads[h];
+        VQA_REQUIRE(p.zv && p.zl && p.label && p.valid && p.stats_v && (p.split == 0 || p.split == 1), VQA_ERR_ARG);
+        VQA_REQUIRE((p.dzv == nullptr) == (p.dzl == nullptr), VQA_ERR_ARG);
+        VQA_REQUIRE(p.dzv == nullptr || p.inv_valid_sum != nullptr, VQA_ERR_ARG);
+        VQA_REQUIRE(!p.split || p.stats_l != nullptr, VQA_ERR_ARG);
+        aligned = aligned && vqa_aligned16(p.zv) && vqa_aligned16(p.zl) && (p.dzv == nullptr || vqa_aligned16(p.dzv)) &&
+                  (p.dzl == nullptr || vqa_aligned16(p.dzl));
+        if (p.split) {
+            args.t[nt++] = PairTask{p.zv, nullptr, p.label, p.valid, p.inv_valid_sum, p.stats_v, p.dzv, nullptr};
+            args.t[nt++] = PairTask{p.zl, nullptr, p.label, p.valid, p.inv_valid_sum, p.stats_l, p.dzl, nullptr};
+        } else {
+            args.t[nt++] = PairTask{p.zv, p.zl, p.label, p.valid, p.inv_valid_sum, p.stats_v, p.dzv, p.dzl};
+        }
+    }
+    if (rows == 0) return VQA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(rows, nt);
+    // the register-resident row under the condition vqa_softmax_ce_fwd applies, so that both give the same bits
+    if (g_softmax_reg && A % 4 == 0 && A <= 4096 && aligned) {
+        switch ((A / 4 + 255) / 256) {
+        case 1: hipLaunchKernelGGL(softmax_ce_pair_kernel<1>, grid, dim3(256), 0, st, args, topk, A); break;
+        case 2: hipLaunchKernelGGL(softmax_ce_pair_kernel<2>, grid, dim3(256), 0, st, args, topk, A); break;
+        case 3: hipLaunchKernelGGL(softmax_ce_pair_kernel<3>, grid, dim3(256), 0, st, args, topk, A); break;
+        default: hipLaunchKernelGGL(softmax_ce_pair_kernel<4>, grid, dim3(256), 0, st, args, topk, A); break;
+        }
+    } else {
+        hipLaunchKernelGGL(softmax_ce_pair_kernel<0>, grid, dim3(256), 0, st, args, topk, A);
     }
     VQA_CHECK_LAUNCH();
     return VQA_OK;

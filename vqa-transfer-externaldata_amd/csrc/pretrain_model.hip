@@ -665,16 +665,26 @@ __global__ __launch_bounds__(256) void pretrain_ext_report_kernel(ReportExtArgs 
     }
 }
 
-Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx) {
+// noc: the "no composition" heads (vqa_pretrain_noc_*): two joint branches and two logit blocks per head instead of
+// jin / joint_fc / classifier
+Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false) {
     const vqa_pretrain_dims_t& d = dx.base;
     const HeadSet hs(dx.heads);
     Layout L;
     const int64_t B = d.B, n = d.n, R = d.R, D = d.D, H = d.H, W = d.W, A = d.A, T = d.L, Bn = B * n, NH = hs.nh();
     const int64_t Tc = hs.rank[2] >= 0 ? dx.Lc : 0;
     L.add("S/pooled", 2 * Bn * D); L.add("S/vl_pre", 2 * Bn * H); L.add("S/lft", NH * Bn * H);
-    L.add("S/vl", NH * Bn * H); L.add("S/ll_pre", NH * Bn * H); L.add("S/ll", NH * Bn * H); L.add("S/jin", NH * Bn * H);
-    L.add("S/j_pre", NH * Bn * 2 * H); L.add("S/j", NH * Bn * 2 * H);
-    L.add("S/z", NH * Bn * A); L.add("S/dz", NH * Bn * A); L.add("S/stats", NH * Bn * 4);
+    L.add("S/vl", NH * Bn * H); L.add("S/ll_pre", NH * Bn * H); L.add("S/ll", NH * Bn * H);
+    if (noc) {
+        L.add("S/jv_pre", NH * Bn * 2 * H); L.add("S/jv", NH * Bn * 2 * H);
+        L.add("S/jl_pre", NH * Bn * 2 * H); L.add("S/jl", NH * Bn * 2 * H);
+        L.add("S/zv", NH * Bn * A); L.add("S/zl", NH * Bn * A); L.add("S/dzv", NH * Bn * A); L.add("S/dzl", NH * Bn * A);
+        L.add("S/stats", NH * Bn * 4); L.add("S/stats_l", NH * Bn * 4);
+    } else {
+        L.add("S/jin", NH * Bn * H);
+        L.add("S/j_pre", NH * Bn * 2 * H); L.add("S/j", NH * Bn * 2 * H);
+        L.add("S/z", NH * Bn * A); L.add("S/dz", NH * Bn * A); L.add("S/stats", NH * Bn * 4);
+    }
     for (int k = 0; k < 2; ++k) {
         const std::string p = std::string(KIND[k]) + "/";
         L.add(p + "key6", Bn * 6);
@@ -696,6 +706,17 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx) {
             L.alias(q + "vl", "S/vl", h * Bn * H, Bn * H); L.add(q + "vl_mean", B); L.add(q + "vl_rstd", B);
             L.alias(q + "ll_pre", "S/ll_pre", h * Bn * H, Bn * H); L.alias(q + "ll", "S/ll", h * Bn * H, Bn * H);
             L.add(q + "ll_mean", B); L.add(q + "ll_rstd", B);
+            if (noc) {
+                for (const char* br : {"v", "l"}) {
+                    const std::string b = br;
+                    L.alias(q + "j" + b + "_pre", "S/j" + b + "_pre", h * Bn * 2 * H, Bn * 2 * H);
+                    L.alias(q + "j" + b, "S/j" + b, h * Bn * 2 * H, Bn * 2 * H);
+                    L.add(q + "j" + b + "_mean", B); L.add(q + "j" + b + "_rstd", B);
+                    L.alias(q + "z" + b, "S/z" + b, h * Bn * A, Bn * A); L.alias(q + "dz" + b, "S/dz" + b, h * Bn * A, Bn * A);
+                }
+                L.alias(q + "stats", "S/stats", h * Bn * 4, Bn * 4); L.alias(q + "stats_l", "S/stats_l", h * Bn * 4, Bn * 4);
+                continue;
+            }
             L.alias(q + "jin", "S/jin", h * Bn * H, Bn * H);
             L.alias(q + "j_pre", "S/j_pre", h * Bn * 2 * H, Bn * 2 * H); L.alias(q + "j", "S/j", h * Bn * 2 * H, Bn * 2 * H);
             L.add(q + "j_mean", B); L.add(q + "j_rstd", B);
@@ -718,7 +739,12 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx) {
         L.add("E/d_state_s", 2 * Bn * H); L.add("E/dxp", Tc * 2 * Bn * 3 * H); L.add("E/dx", Tc * 2 * Bn * W);
     }
     L.add("report", 32);
-    L.add("d_j", NH * Bn * 2 * H); L.add("d_jpre", NH * Bn * 2 * H); L.add("d_jin", NH * Bn * H);
+    if (noc) {
+        L.add("d_jv", NH * Bn * 2 * H); L.add("d_jvpre", NH * Bn * 2 * H);
+        L.add("d_jl", NH * Bn * 2 * H); L.add("d_jlpre", NH * Bn * 2 * H);
+    } else {
+        L.add("d_j", NH * Bn * 2 * H); L.add("d_jpre", NH * Bn * 2 * H); L.add("d_jin", NH * Bn * H);
+    }
     L.add("d_vl", NH * Bn * H); L.add("d_ll", NH * Bn * H); L.add("d_vlpre", NH * Bn * H); L.add("d_llpre", NH * Bn * H);
     L.add("d_lft", NH * Bn * H); L.add("d_pooled", 2 * Bn * D);
     L.add("d_state_s", 2 * Bn * H); L.add("d_hscratch", 2 * Bn * H);
@@ -779,65 +805,17 @@ std::string ext_report_key(int heads, int i) {
     return std::string(KIND[k]) + "_" + TASK_EXT[hs.type[r]] + SUFFIX[j];
 }
 
-}  // namespace
-
-extern "C" const char* vqa_pretrain_ext_report_key(int heads, int i) {
-    static std::vector<std::string> keys[8];        // built once per head set; the pointers stay valid
-    static const int init = [] {
-        for (int m = 0; m < 8; ++m)
-            if (m & VQA_PT_HEAD_BF)
-                for (int i = 0; i <= 3 * HeadSet(m).nh(); ++i) keys[m].push_back(ext_report_key(m, i));
-        return 0;
-    }();
-    (void)init;
-    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[heads].size()) return nullptr;
-    return keys[heads][i].c_str();
-}
-
-extern "C" int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    if (!ext_dims_ok(dims)) return VQA_ERR_ARG;
-    return make_layout_ext(*dims).total;
-}
-
-extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
-                                       int64_t* n_elems) {
-    if (!ext_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    const Layout L = make_layout_ext(*dims);
-    const Entry* e = L.find(name);
-    if (e == nullptr) return VQA_ERR_ARG;
-    if (offset_bytes) *offset_bytes = e->off;
-    if (n_elems) *n_elems = e->n;
-    return VQA_OK;
-}
-
-extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
-                                        int want_dz, void* stream) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+// The trunk of the variable-head-set models, shared by vqa_pretrain_ext_forward and vqa_pretrain_noc_forward: spatial
+// attention and pooling, word sets, the caption batch and the context batch, up to the stacked "S/pooled" and "S/lft"
+// blocks the heads read
+int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                  const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
-    const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
-    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, A = d->A, T = d->L, Bn = B * n;
-    const int64_t NH = hs.nh(), B2 = 2 * Bn;
+    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
+    const int64_t B2 = 2 * Bn;
     const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
     auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
-    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
-                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
-    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
-    if (hs.rank[2] >= 0)
-        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
-                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
-    ReportExtArgs ra{};
-    ra.rows = (int)Bn;
-    ra.nh = (int)NH;
-    ProbeScope ps_all("pretrain_ext.forward", c.st);
     const vqa_pt_fc_t spat_v = fc4(P->spat_v_linear_v), spat_q = fc4(P->spat_q_linear_v), wft = fc4(P->wordset_ft);
     TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
     for (int k = 0; k < 2; ++k) {
@@ -909,116 +887,27 @@ extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, con
                                 c.f("E/gru_u"), c.f("E/gru_c"), c.f("E/gru_rh"), (int)Tc, (int)B2, (int)H, c.st));
         TRY(gather_rows(hse + Tc * B2 * H, bx->ctx_inv, c.f("S/lft") + 2 * hs.rank[2] * Bn * H, B2, H, c.st));
     }
-    {   // the NH heads, stacked
-        const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
-        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
-        ProbeScope ps_h("pt.heads.fwd", c.st);
-        TRY(c.gemm(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, P->pooled_linear_l.w, (int)H, c.f("S/vl_pre"), (int)H,
-                   P->pooled_linear_l.b));
-        TRY(c.gemm(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, P->q_linear_l.w, (int)H, c.f("S/ll_pre"), (int)H,
-                   P->q_linear_l.b));
-        for (int h = 0; h < NH; ++h) {
-            const std::string q = hname(h);
-            TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, P->pooled_linear_l.gamma[li(h)], P->pooled_linear_l.beta[li(h)],
-                               nullptr, 1.f, c.f("S/vl") + h * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n,
-                               (int)H, 0, c.st));
-            TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + h * SH, P->q_linear_l.gamma[li(h)], P->q_linear_l.beta[li(h)], nullptr, 1.f,
-                               c.f("S/ll") + h * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
-        }
-        TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
-        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
-                   P->joint_fc.b));
-        for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, t = hs.type[h >> 1];
-            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
-                                                                               : bx->ctx[k].keep_ew_joint;
-            const std::string q = hname(h);
-            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[li(h)], P->joint_fc.beta[li(h)], jmask,
-                               d->keep_joint, c.f("S/j") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n,
-                               (int)(2 * H), 0, c.st));
-        }
-        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
-                   P->classifier.b));
-        for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, r = h >> 1;
-            const std::string p = std::string(KIND[k]) + "/";
-            TRY(vqa_softmax_ce_fwd(c.f("S/z") + h * SA, bt->kind[k].fills, c.f(p + "valid"), 5, c.f(p + "inv_valid"),
-                                   c.f("S/stats") + h * Bn * 4, want_dz ? c.f("S/dz") + h * SA : nullptr, (int)Bn, (int)A,
-                                   c.st));
-            ra.stats[k * hs.nt + r] = c.f("S/stats") + h * Bn * 4;
-            ra.inv[k * hs.nt + r] = c.f(p + "inv_valid");
-        }
-    }
-    hipLaunchKernelGGL(pretrain_ext_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
-    VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
 
-// Backward phases of the variable head set; the buckets of vqa_pretrain_backward_phases, with
-//   1  the NH stacked heads
-//   2  BPTT of the caption batch, then of the enwiki context batch (encode_L_blank and encode_L_enwiki gradients)
-//   4  L_GloVe scatter-add, then enwiki_map scatter-add (both slice sums of squares)
-//   8  per category: wordset_ft / wordset_map (cleared even without the word-set head), spatial attention (writes slice_sq)
-extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
-                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                                void* stream) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+// Phases 2, 4 and 8 of the variable-head-set backward (everything below the heads), shared by
+// vqa_pretrain_ext_backward_phases and vqa_pretrain_noc_backward_phases
+int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                  const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs,
+                  float* slice_sq, int phases) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
-    const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
-    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, A = d->A, T = d->L, Bn = B * n;
-    const int64_t NH = hs.nh(), B2 = 2 * Bn;
+    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
+    const int64_t B2 = 2 * Bn;
     const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
     const int det = (d->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0;
     auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    ProbeScope ps_all("pretrain_ext.backward", c.st);
-    Acc acc{c, {}};
     const float* sq_prev = nullptr;
     auto add_slice_sq = [&](const float* g, int64_t cnt) -> int {
         TRY(vqa_sumsq(g, cnt, sq_prev, c.f("sq"), c.f("sumsq_ws"), c.count("sumsq_ws"), c.st));
         sq_prev = c.f("sq");
         return VQA_OK;
     };
-    if (phases & 1) {
-        ProbeScope ps_h("pt.heads.bwd", c.st);
-        const int64_t SH = Bn * H, SJ = Bn * 2 * H;
-        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
-        TRY(acc.weight(G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
-        TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G->classifier.b));
-        TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
-        for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, t = hs.type[h >> 1];
-            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
-                                                                               : bx->ctx[k].keep_ew_joint;
-            const std::string q = hname(h);
-            TRY(ln_bwd_p(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, fc_slot(P->joint_fc, li(h)), fc_slot(G->joint_fc, li(h)), 0,
-                         (int)n, 0, c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), jmask, d->keep_joint,
-                         c.f("d_jpre") + h * SJ));
-        }
-        const vqa_pt_fc_t jP = fc_slot(P->joint_fc, 0), jG = fc_slot(G->joint_fc, 0);
-        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, jP, jG, c.f("d_jin")));
-        TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
-        for (int h = 0; h < NH; ++h) {
-            const std::string q = hname(h);
-            TRY(ln_bwd_p(c, acc, c.f("d_vl") + h * SH, Bn, H, fc_slot(P->pooled_linear_l, li(h)),
-                         fc_slot(G->pooled_linear_l, li(h)), 0, (int)n, 0, c.f("S/vl_pre") + (h & 1) * SH,
-                         c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f, c.f("d_vlpre") + h * SH));
-            TRY(ln_bwd_p(c, acc, c.f("d_ll") + h * SH, Bn, H, fc_slot(P->q_linear_l, li(h)), fc_slot(G->q_linear_l, li(h)), 0,
-                         (int)n, 0, c.f("S/ll_pre") + h * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f,
-                         c.f("d_llpre") + h * SH));
-        }
-        // every head of a category applies pooled_linear_l to the same pooled rows: their d_pre meet before one dW / dx
-        for (int r = 1; r < hs.nt; ++r) TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * r * SH, 2 * SH, c.st));
-        TRY(acc.weight(G->pooled_linear_l.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
-        TRY(c.gemm(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, P->pooled_linear_l.w, (int)H, c.f("d_pooled"), (int)D));
-        TRY(fc_bwd(c, acc, "d_llpre", c.f("S/lft"), NH * Bn, H, H, fc_slot(P->q_linear_l, 0), fc_slot(G->q_linear_l, 0),
-                   c.f("d_lft")));
-    }
     const int ld3 = (int)(3 * H);
     const int64_t Wp = x_stride(W);
     if (phases & 2) {
@@ -1120,8 +1009,417 @@ extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* d
     return VQA_OK;
 }
 
+// pooled_linear_l over the 2 Bn pooled rows and q_linear_l over the NH Bn stacked language rows ("S/lft"), then each
+// head's LayerNorm + ReLU of both into its slices of "S/vl" / "S/ll" (v_linear_l / l_linear_l of the reference)
+int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, n = d.n, D = d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
+    const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+    TRY(c.gemm(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, pooled.w, (int)H, c.f("S/vl_pre"), (int)H, pooled.b));
+    TRY(c.gemm(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, qlin.w, (int)H, c.f("S/ll_pre"), (int)H, qlin.b));
+    for (int h = 0; h < NH; ++h) {
+        const std::string q = hname(h);
+        TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, pooled.gamma[li(h)], pooled.beta[li(h)], nullptr, 1.f,
+                           c.f("S/vl") + h * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n, (int)H, 0, c.st));
+        TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + h * SH, qlin.gamma[li(h)], qlin.beta[li(h)], nullptr, 1.f, c.f("S/ll") + h * SH,
+                           c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
+    }
+    return VQA_OK;
+}
+
+// its backward from "d_vl" / "d_ll": LayerNorms, pooled_linear_l (dW, d_pooled) and q_linear_l (dW, d_lft)
+int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin,
+                 const vqa_pt_fc6_t& g_pooled, const vqa_pt_fc6_t& g_qlin) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, n = d.n, D = d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
+    const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+    for (int h = 0; h < NH; ++h) {
+        const std::string q = hname(h);
+        TRY(ln_bwd_p(c, acc, c.f("d_vl") + h * SH, Bn, H, fc_slot(pooled, li(h)), fc_slot(g_pooled, li(h)), 0, (int)n, 0,
+                     c.f("S/vl_pre") + (h & 1) * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f,
+                     c.f("d_vlpre") + h * SH));
+        TRY(ln_bwd_p(c, acc, c.f("d_ll") + h * SH, Bn, H, fc_slot(qlin, li(h)), fc_slot(g_qlin, li(h)), 0, (int)n, 0,
+                     c.f("S/ll_pre") + h * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f, c.f("d_llpre") + h * SH));
+    }
+    // every head of a category applies pooled_linear_l to the same pooled rows: their d_pre meet before one dW / dx
+    for (int r = 1; r < hs.nt; ++r) TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * r * SH, 2 * SH, c.st));
+    TRY(acc.weight(g_pooled.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
+    TRY(c.gemm(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, pooled.w, (int)H, c.f("d_pooled"), (int)D));
+    return fc_bwd(c, acc, "d_llpre", c.f("S/lft"), NH * Bn, H, H, fc_slot(qlin, 0), fc_slot(g_qlin, 0), c.f("d_lft"));
+}
+
+}  // namespace
+
+extern "C" const char* vqa_pretrain_ext_report_key(int heads, int i) {
+    static std::vector<std::string> keys[8];        // built once per head set; the pointers stay valid
+    static const int init = [] {
+        for (int m = 0; m < 8; ++m)
+            if (m & VQA_PT_HEAD_BF)
+                for (int i = 0; i <= 3 * HeadSet(m).nh(); ++i) keys[m].push_back(ext_report_key(m, i));
+        return 0;
+    }();
+    (void)init;
+    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[heads].size()) return nullptr;
+    return keys[heads][i].c_str();
+}
+
+extern "C" int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
+    if (!ext_dims_ok(dims)) return VQA_ERR_ARG;
+    return make_layout_ext(*dims).total;
+}
+
+extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
+                                       int64_t* n_elems) {
+    if (!ext_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
+    const Layout L = make_layout_ext(*dims);
+    const Entry* e = L.find(name);
+    if (e == nullptr) return VQA_ERR_ARG;
+    if (offset_bytes) *offset_bytes = e->off;
+    if (n_elems) *n_elems = e->n;
+    return VQA_OK;
+}
+
+extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                        int want_dz, void* stream) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    const vqa_pretrain_dims_t* d = &dims->base;
+    const vqa_pretrain_batch_t* bt = &bx->base;
+    const HeadSet hs(dims->heads);
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
+    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
+    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
+                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
+    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
+    if (hs.rank[2] >= 0)
+        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
+                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
+    ReportExtArgs ra{};
+    ra.rows = (int)Bn;
+    ra.nh = (int)NH;
+    ProbeScope ps_all("pretrain_ext.forward", c.st);
+    TRY(ext_trunk_fwd(c, dims, P, bx, hs));
+    {   // the NH heads, stacked
+        const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
+        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+        ProbeScope ps_h("pt.heads.fwd", c.st);
+        TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l));
+        TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
+        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
+                   P->joint_fc.b));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, t = hs.type[h >> 1];
+            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
+                                                                               : bx->ctx[k].keep_ew_joint;
+            const std::string q = hname(h);
+            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[li(h)], P->joint_fc.beta[li(h)], jmask,
+                               d->keep_joint, c.f("S/j") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n,
+                               (int)(2 * H), 0, c.st));
+        }
+        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
+                   P->classifier.b));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, r = h >> 1;
+            const std::string p = std::string(KIND[k]) + "/";
+            TRY(vqa_softmax_ce_fwd(c.f("S/z") + h * SA, bt->kind[k].fills, c.f(p + "valid"), 5, c.f(p + "inv_valid"),
+                                   c.f("S/stats") + h * Bn * 4, want_dz ? c.f("S/dz") + h * SA : nullptr, (int)Bn, (int)A,
+                                   c.st));
+            ra.stats[k * hs.nt + r] = c.f("S/stats") + h * Bn * 4;
+            ra.inv[k * hs.nt + r] = c.f(p + "inv_valid");
+        }
+    }
+    hipLaunchKernelGGL(pretrain_ext_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+// Backward phases of the variable head set; the buckets of vqa_pretrain_backward_phases, with
+//   1  the NH stacked heads
+//   2  BPTT of the caption batch, then of the enwiki context batch (encode_L_blank and encode_L_enwiki gradients)
+//   4  L_GloVe scatter-add, then enwiki_map scatter-add (both slice sums of squares)
+//   8  per category: wordset_ft / wordset_map (cleared even without the word-set head), spatial attention (writes slice_sq)
+extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                void* stream) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    const vqa_pretrain_dims_t* d = &dims->base;
+    const vqa_pretrain_batch_t* bt = &bx->base;
+    const HeadSet hs(dims->heads);
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
+    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    ProbeScope ps_all("pretrain_ext.backward", c.st);
+    Acc acc{c, {}};
+    if (phases & 1) {
+        ProbeScope ps_h("pt.heads.bwd", c.st);
+        const int64_t SH = Bn * H, SJ = Bn * 2 * H;
+        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+        TRY(acc.weight(G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
+        TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G->classifier.b));
+        TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, t = hs.type[h >> 1];
+            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
+                                                                               : bx->ctx[k].keep_ew_joint;
+            const std::string q = hname(h);
+            TRY(ln_bwd_p(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, fc_slot(P->joint_fc, li(h)), fc_slot(G->joint_fc, li(h)), 0,
+                         (int)n, 0, c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), jmask, d->keep_joint,
+                         c.f("d_jpre") + h * SJ));
+        }
+        const vqa_pt_fc_t jP = fc_slot(P->joint_fc, 0), jG = fc_slot(G->joint_fc, 0);
+        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, jP, jG, c.f("d_jin")));
+        TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
+        TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l));
+    }
+    return ext_trunk_bwd(c, acc, dims, P, G, bx, hs, slice_sq, phases);
+}
+
 extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                                          const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
                                          void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
     return vqa_pretrain_ext_backward_phases(dims, P, G, bx, workspace, workspace_bytes, slice_sq, 15, stream);
+}
+
+// ================================================================ "no composition" pre-training
+// vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py (= model_vlmap_nocarch_bf_or_wordset_withatt_sp.py, bf | ws) and
+// model_vlmap_noc_bf_or_enwiki_withatt_sp.py (bf | ew): the trunk and head inputs of the variable-head-set model, then
+// per head two branches instead of joint_fc(v_linear_l * l_linear_l) -> classifier:
+//   v_joint = dropout(relu(LN(v_linear_l joint_v)), 0.5) -> classifier_v,  l_joint = the same on l_linear_l -> classifier_l
+// Blank fill is a SUM head (one CE of v_logit + l_logit), word set and enwiki are SPLIT heads (a CE per branch).  Both
+// branches' joint and classifier GEMMs run over the whole stacked NH Bn block, forward and backward, whatever the
+// head's loss; vqa_softmax_ce_pair_fwd writes every head's stats and dz in one launch.
+namespace {
+
+bool noc_dims_ok(const vqa_pretrain_ext_dims_t* d) {
+    return ext_dims_ok(d) && (d->heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS) || d->heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_EW));
+}
+
+bool noc_split(int type) { return type != 0; }      // blank fill SUM, word set / enwiki SPLIT
+
+// the trunk members of the noc params as an ext params struct (joint_fc / classifier stay NULL: the noc path never
+// reads them)
+vqa_pretrain_ext_params_t noc_trunk(const vqa_pretrain_noc_params_t& p) {
+    vqa_pretrain_ext_params_t e{};
+    e.wordset_map = p.wordset_map; e.l_glove = p.l_glove; e.enwiki_map = p.enwiki_map;
+    e.spat_v_linear_v = p.spat_v_linear_v; e.spat_q_linear_v = p.spat_q_linear_v; e.spat_att_score = p.spat_att_score;
+    e.gru_wg = p.gru_wg; e.gru_bg = p.gru_bg; e.gru_wc = p.gru_wc; e.gru_bc = p.gru_bc;
+    e.egru_wg = p.egru_wg; e.egru_bg = p.egru_bg; e.egru_wc = p.egru_wc; e.egru_bc = p.egru_bc;
+    e.pooled_linear_l = p.pooled_linear_l; e.q_linear_l = p.q_linear_l; e.wordset_ft = p.wordset_ft;
+    return e;
+}
+
+// keep-masks of head h's two joint branches: v = the ext batch's (cfg-5 / enwiki streams), l = the noc batch's
+const uint8_t* noc_vmask(const vqa_pretrain_noc_batch_t* b, int k, int t) {
+    const vqa_pretrain_ext_batch_t& x = b->base;
+    return t == 0 ? x.base.kind[k].keep_bf_joint : t == 1 ? x.base.kind[k].keep_ws_joint : x.ctx[k].keep_ew_joint;
+}
+const uint8_t* noc_lmask(const vqa_pretrain_noc_batch_t* b, int k, int t) {
+    const vqa_pretrain_noc_kind_t& l = b->l[k];
+    return t == 0 ? l.keep_bf_l_joint : t == 1 ? l.keep_ws_l_joint : l.keep_ew_l_joint;
+}
+
+std::string noc_report_key(int heads, int i) {
+    const HeadSet hs(heads);
+    std::vector<std::string> keys;
+    static const char* const SUFFIX[3] = {"_loss", "_acc", "_top_5_acc"};
+    for (int k = 0; k < 2; ++k)
+        for (int r = 0; r < hs.nt; ++r) {
+            const std::string base = std::string(KIND[k]) + "_" + TASK_EXT[hs.type[r]];
+            for (const char* br : noc_split(hs.type[r]) ? std::vector<const char*>{"_v", "_l"} : std::vector<const char*>{""})
+                for (const char* suf : SUFFIX) keys.push_back(base + br + suf);
+        }
+    keys.push_back("total_loss");
+    return (i >= 0 && i < (int)keys.size()) ? keys[i] : "";
+}
+
+int noc_inputs_ok(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P, const vqa_pretrain_noc_batch_t* b) {
+    const HeadSet hs(dims->heads);
+    const vqa_pretrain_ext_batch_t* bx = &b->base;
+    const vqa_pretrain_batch_t* bt = &bx->base;
+    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
+    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
+                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
+    VQA_REQUIRE(P->pooled_linear_l.w && P->q_linear_l.w && P->joint_v.w && P->joint_l.w && P->classifier_v.w &&
+                P->classifier_l.w, VQA_ERR_ARG);
+    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
+    if (hs.rank[2] >= 0)
+        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
+                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
+    return VQA_OK;
+}
+
+}  // namespace
+
+extern "C" const char* vqa_pretrain_noc_report_key(int heads, int i) {
+    static std::vector<std::string> keys[8];        // built once per head set; the pointers stay valid
+    static const int init = [] {
+        for (const int m : {VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, VQA_PT_HEAD_BF | VQA_PT_HEAD_EW})
+            for (int i = 0; !noc_report_key(m, i).empty(); ++i) keys[m].push_back(noc_report_key(m, i));
+        return 0;
+    }();
+    (void)init;
+    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[heads].size()) return nullptr;
+    return keys[heads][i].c_str();
+}
+
+extern "C" int64_t vqa_pretrain_noc_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
+    if (!noc_dims_ok(dims)) return VQA_ERR_ARG;
+    return make_layout_ext(*dims, true).total;
+}
+
+extern "C" int vqa_pretrain_noc_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
+                                       int64_t* n_elems) {
+    if (!noc_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
+    const Layout L = make_layout_ext(*dims, true);
+    const Entry* e = L.find(name);
+    if (e == nullptr) return VQA_ERR_ARG;
+    if (offset_bytes) *offset_bytes = e->off;
+    if (n_elems) *n_elems = e->n;
+    return VQA_OK;
+}
+
+extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                        const vqa_pretrain_noc_batch_t* bn, void* workspace, int64_t workspace_bytes,
+                                        int want_dz, void* stream) {
+    VQA_REQUIRE(noc_dims_ok(dims) && P && bn && workspace, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims, true);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    TRY(noc_inputs_ok(dims, P, bn));
+    const vqa_pretrain_dims_t* d = &dims->base;
+    const vqa_pretrain_batch_t* bt = &bn->base.base;
+    const HeadSet hs(dims->heads);
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
+    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    ProbeScope ps_all("pretrain_noc.forward", c.st);
+    const vqa_pretrain_ext_params_t E = noc_trunk(*P);
+    TRY(ext_trunk_fwd(c, dims, &E, &bn->base, hs));
+    ReportExtArgs ra{};
+    ra.rows = (int)Bn;
+    {   // the NH heads, stacked; every branch GEMM covers all of them
+        const int64_t SJ = Bn * 2 * H, SA = Bn * A;
+        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+        ProbeScope ps_h("pt.heads.fwd", c.st);
+        TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l));
+        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/vl"), (int)H, P->joint_v.w, (int)(2 * H), c.f("S/jv_pre"), (int)(2 * H),
+                   P->joint_v.b));
+        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/ll"), (int)H, P->joint_l.w, (int)(2 * H), c.f("S/jl_pre"), (int)(2 * H),
+                   P->joint_l.b));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, t = hs.type[h >> 1];
+            const std::string q = hname(h);
+            TRY(vqa_ln_act_fwd(c.f("S/jv_pre") + h * SJ, P->joint_v.gamma[li(h)], P->joint_v.beta[li(h)], noc_vmask(bn, k, t),
+                               d->keep_joint, c.f("S/jv") + h * SJ, c.f(q + "jv_mean"), c.f(q + "jv_rstd"), (int)B, (int)n,
+                               (int)(2 * H), 0, c.st));
+            TRY(vqa_ln_act_fwd(c.f("S/jl_pre") + h * SJ, P->joint_l.gamma[li(h)], P->joint_l.beta[li(h)], noc_lmask(bn, k, t),
+                               d->keep_joint, c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"), (int)B, (int)n,
+                               (int)(2 * H), 0, c.st));
+        }
+        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/jv"), (int)(2 * H), P->classifier_v.w, (int)A, c.f("S/zv"), (int)A,
+                   P->classifier_v.b));
+        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/jl"), (int)(2 * H), P->classifier_l.w, (int)A, c.f("S/zl"), (int)A,
+                   P->classifier_l.b));
+        // every head's loss in one launch; the report reads the stats blocks in key order
+        vqa_softmax_pair_t pr[VQA_SOFTMAX_PAIR_MAX] = {};
+        const float* st_by_key[2][3][2] = {};
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, r = h >> 1;
+            const std::string p = std::string(KIND[k]) + "/";
+            vqa_softmax_pair_t& e = pr[h];
+            e.zv = c.f("S/zv") + h * SA; e.zl = c.f("S/zl") + h * SA;
+            e.label = bt->kind[k].fills; e.valid = c.f(p + "valid"); e.inv_valid_sum = c.f(p + "inv_valid");
+            e.split = noc_split(hs.type[r]) ? 1 : 0;
+            e.stats_v = c.f("S/stats") + h * Bn * 4; e.stats_l = c.f("S/stats_l") + h * Bn * 4;
+            e.dzv = want_dz ? c.f("S/dzv") + h * SA : nullptr; e.dzl = want_dz ? c.f("S/dzl") + h * SA : nullptr;
+            st_by_key[k][r][0] = e.stats_v;
+            st_by_key[k][r][1] = e.split ? e.stats_l : nullptr;
+        }
+        TRY(vqa_softmax_ce_pair_fwd(pr, (int)NH, 5, (int)Bn, (int)A, c.st));
+        for (int k = 0; k < 2; ++k)
+            for (int r = 0; r < hs.nt; ++r)
+                for (int br = 0; br < 2; ++br)
+                    if (st_by_key[k][r][br] != nullptr) {
+                        ra.stats[ra.nh] = st_by_key[k][r][br];
+                        ra.inv[ra.nh++] = c.f(std::string(KIND[k]) + "/inv_valid");
+                    }
+    }
+    hipLaunchKernelGGL(pretrain_ext_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+// Backward phases of the noc models: phase 1 the stacked heads (both classifiers, both joint branches, pooled_linear_l,
+// q_linear_l); 2, 4, 8 the trunk as vqa_pretrain_ext_backward_phases
+extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                                const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
+                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                void* stream) {
+    VQA_REQUIRE(noc_dims_ok(dims) && P && G && bn && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims, true);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    const vqa_pretrain_dims_t* d = &dims->base;
+    const HeadSet hs(dims->heads);
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
+    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
+    ProbeScope ps_all("pretrain_noc.backward", c.st);
+    Acc acc{c, {}};
+    if (phases & 1) {
+        ProbeScope ps_h("pt.heads.bwd", c.st);
+        const int64_t SJ = Bn * 2 * H;
+        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
+        // per branch: classifier dW / db / dx, each head's joint LayerNorm, the joint dW / db and dx into d_vl / d_ll
+        struct Branch { const char *j, *dz, *dj, *jpre, *djpre, *in, *din, *tag; const vqa_pt_fc6_t *cP, *cG, *jP, *jG; };
+        const Branch br[2] = {
+            {"S/jv", "S/dzv", "d_jv", "S/jv_pre", "d_jvpre", "S/vl", "d_vl", "jv", &P->classifier_v, &G->classifier_v,
+             &P->joint_v, &G->joint_v},
+            {"S/jl", "S/dzl", "d_jl", "S/jl_pre", "d_jlpre", "S/ll", "d_ll", "jl", &P->classifier_l, &G->classifier_l,
+             &P->joint_l, &G->joint_l}};
+        for (int v = 0; v < 2; ++v) {
+            const Branch& b = br[v];
+            TRY(acc.weight(b.cG->w, c.f(b.j), (int)(2 * H), c.f(b.dz), (int)A, 2 * H, A, NH * Bn));
+            TRY(acc.colsum(c.f(b.dz), NH * Bn, A, (int)A, b.cG->b));
+            TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f(b.dz), (int)A, b.cP->w, (int)A, c.f(b.dj), (int)(2 * H)));
+            for (int h = 0; h < NH; ++h) {
+                const int k = h & 1, t = hs.type[h >> 1];
+                const std::string q = hname(h) + b.tag;
+                TRY(ln_bwd_p(c, acc, c.f(b.dj) + h * SJ, Bn, 2 * H, fc_slot(*b.jP, li(h)), fc_slot(*b.jG, li(h)), 0, (int)n, 0,
+                             c.f(b.jpre) + h * SJ, c.f(q + "_mean"), c.f(q + "_rstd"),
+                             v == 0 ? noc_vmask(bn, k, t) : noc_lmask(bn, k, t), d->keep_joint, c.f(b.djpre) + h * SJ));
+            }
+            TRY(fc_bwd(c, acc, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, fc_slot(*b.jP, 0), fc_slot(*b.jG, 0), c.f(b.din)));
+        }
+        TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l));
+    }
+    const vqa_pretrain_ext_params_t EP = noc_trunk(*P), EG = noc_trunk(*G);
+    return ext_trunk_bwd(c, acc, dims, &EP, &EG, &bn->base, hs, slice_sq, phases);
+}
+
+extern "C" int vqa_pretrain_noc_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                         const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
+                                         void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
+    return vqa_pretrain_noc_backward_phases(dims, P, G, bn, workspace, workspace_bytes, slice_sq, 15, stream);
 }

@@ -8,9 +8,10 @@ three embedding tables from a checkpoint and writes `<checkpoint dir>/word_weigh
 answer_dict.pkl}` with the datasets `v_word`, `l_word`, `l_answer_word`, `v_class_weights`, `v_class_biases`,
 `l_class_weights`, `l_class_biases` (:72-80) -- what `modules.WordWeightAnswer(weight_name='v_class_weights', ...)` of
 vqa/model_vlmap_answer_noc.py:190-202 looks up by answer string.  The checkpoint is a name -> tensor archive with the
-reference's TF variable names (what this package's trainers save); the pre-training variant that TRAINS those two heads
-(vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py) is a reference ablation outside this repo's scope, so such a
-checkpoint comes from the reference side (converted) or from a test."""
+reference's TF variable names (what this package's trainers save); the pre-training models that TRAIN those two heads
+(`pretrain_trainer --model_type vlmap_noc_bf_or_wordset_withatt_sp | vlmap_nocarch_bf_or_wordset_withatt_sp |
+vlmap_noc_bf_or_enwiki_withatt_sp`) write such checkpoints; `pretrain.export_noc_word_weights` is the same bridge on an
+in-memory state dict."""
 from __future__ import annotations
 
 import argparse

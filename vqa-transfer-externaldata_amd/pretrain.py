@@ -20,6 +20,13 @@ model_vlmap_bf_enwiki_withatt_sp.py) are the same engine with another head set (
 enwiki head (enwiki_map embedding of the answer's context -> encode_L_enwiki GRU -> the shared fusion MLP) beside the
 blank-fill and (optionally) word-set heads.  Those run on vqa_pretrain_ext_forward / _backward_phases; the cfg-5 head
 set keeps the vqa_pretrain_* calls.
+
+The "no composition" models (vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py, its copy
+model_vlmap_nocarch_bf_or_wordset_withatt_sp.py and model_vlmap_noc_bf_or_enwiki_withatt_sp.py; NOC_MODEL_HEADS) are
+the engine with `noc=True`: per head, instead of joint_fc(v_linear_l * l_linear_l) -> classifier, two branches
+joint_v -> classifier_v on v_linear_l and joint_l -> classifier_l on l_linear_l; a blank-fill head's loss is the CE of
+v_logit + l_logit (SUM), a word-set / enwiki head has one CE per branch (SPLIT, NOC_LOSS_MODE).  Those run on
+vqa_pretrain_noc_forward / _backward_phases, and their checkpoints feed export_noc_word_weights -> vlmap_answer_noc.
 """
 from __future__ import annotations
 
@@ -41,7 +48,9 @@ SPARSE_VARS = ("wordset_map/learn", "L_GloVe/embed_map", "enwiki_map/learn")   #
 # complete their gradients, so every data-parallel bucket is one contiguous range:
 #   [wordset_map | L_GloVe, enwiki_map (phase 4) | GRUs (phase 2) | stacked heads (phase 1) |
 #    spatial attention, wordset_ft (phase 8) | tail]
-PHASE_SCOPES = (("encode_L_blank/", "encode_L_enwiki/"), ("classifier/", "joint_fc/", "pooled_linear_l/", "q_linear_l/"),
+PHASE_SCOPES = (("encode_L_blank/", "encode_L_enwiki/"),
+                ("classifier/", "joint_fc/", "pooled_linear_l/", "q_linear_l/", "classifier_v/", "classifier_l/", "joint_v/",
+                 "joint_l/"),
                 ("spat_att/", "spat_q_linear_v/", "spat_v_linear_v/", "wordset_ft/"))
 # head set per model type: blank fill, word set, enwiki context (in TF build order; head 2 r + k of the type of rank r
 # and category k owns LayerNorm slot 2 r + k of the shared fusion scopes when they are not shared)
@@ -52,6 +61,15 @@ CFG5_HEADS = ("bf", "ws")
 TASK_NAMES = {"bf": "blank_fill", "ws": "wordset", "ew": "enwiki"}
 # the enwiki heads' joint keep-masks are drawn from counters at and above this one: disjoint from the cfg-5 stream
 EW_MASK_COUNTER = 1 << 62
+# "no composition" models: head set per model type (the nocarch file is a byte-identical copy of the noc one) and the
+# loss of each head type -- 'sum': one CE of v_logit + l_logit, 'split': one CE of each branch
+NOC_MODEL_HEADS = {"vlmap_noc_bf_or_wordset_withatt_sp": ("bf", "ws"),
+                   "vlmap_nocarch_bf_or_wordset_withatt_sp": ("bf", "ws"),
+                   "vlmap_noc_bf_or_enwiki_withatt_sp": ("bf", "ew")}
+NOC_LOSS_MODE = {"bf": "sum", "ws": "split", "ew": "split"}
+# the l branch's joint keep-masks of the noc heads: counters from here up, below EW_MASK_COUNTER (the v branch reuses the
+# bf / ws / ew joint streams, which keep their bits)
+NOC_L_MASK_COUNTER = 1 << 61
 
 
 def ln_name(scope, idx):
@@ -68,14 +86,17 @@ def head_mask(heads):
     return sum({"bf": _lib.PT_HEAD_BF, "ws": _lib.PT_HEAD_WS, "ew": _lib.PT_HEAD_EW}[h] for h in heads)
 
 
-def report_keys(heads=CFG5_HEADS):
-    """the model's report keys: per category, per head type <kind>_<task>_{loss,acc,top_5_acc}; then total_loss"""
-    return ["%s_%s_%s" % (k, TASK_NAMES[h], m) for k in KINDS for h in heads
+def report_keys(heads=CFG5_HEADS, noc=False):
+    """the model's report keys: per category, per head type <kind>_<task>_{loss,acc,top_5_acc} (a SPLIT head of a noc
+    model: <kind>_<task>_v_{...} then <kind>_<task>_l_{...}); then total_loss"""
+    return ["%s_%s%s_%s" % (k, TASK_NAMES[h], b, m) for k in KINDS for h in heads
+            for b in (("_v", "_l") if noc and NOC_LOSS_MODE[h] == "split" else ("",))
             for m in ("loss", "acc", "top_%d_acc" % TOP_K)] + ["total_loss"]
 
 
-def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None):
-    """Variables of the model with head set `heads` (n_ctx: the enwiki context vocabulary, with 'ew')."""
+def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None, noc=False):
+    """Variables of the model with head set `heads` (n_ctx: the enwiki context vocabulary, with 'ew'); noc: joint_v /
+    joint_l and classifier_v / classifier_l instead of joint_fc and classifier."""
     heads = tuple(heads)
     s = {"wordset_map/learn": (n_ws, W), "V_GloVe/embed_map": (Vq, W), "L_GloVe/embed_map": (Vq, W),
          "LearnAnswerGloVe/embed_map": (A, W)}
@@ -103,18 +124,20 @@ def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CF
         s["encode_L_enwiki/rnn/gru_cell/candidate/bias"] = (H,)
     fc("pooled_linear_l", D, H, 2 * len(heads))
     fc("q_linear_l", H, H, 2 * len(heads))
-    fc("joint_fc", H, 2 * H, 2 * len(heads))
+    for scope in (("joint_v", "joint_l") if noc else ("joint_fc",)):
+        fc(scope, H, 2 * H, 2 * len(heads))
     if "ws" in heads:
         fc("wordset_ft", W, H, 2)
-    fc("classifier", 2 * H, A, 0)
+    for scope in (("classifier_v", "classifier_l") if noc else ("classifier",)):
+        fc(scope, 2 * H, A, 0)
     return s
 
 
-def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None):
+def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None, noc=False):
     """Random-init weights of the architecture (Xavier-uniform FCs, GRU gate bias 1, LN gamma 1,
     embeddings U(-0.01, 0.01); GloVe vectors are download-only)."""
     p = {}
-    for n, shp in variable_shapes(Vq, n_ws, A, W, D, H, ln_shared, heads, n_ctx).items():
+    for n, shp in variable_shapes(Vq, n_ws, A, W, D, H, ln_shared, heads, n_ctx, noc).items():
         if n.endswith("/weights") or n.endswith("/kernel"):
             lim = np.sqrt(6.0 / (shp[0] + shp[1]))
             p[n] = rng.uniform(-lim, lim, size=shp).astype(np.float32)
@@ -169,20 +192,24 @@ def _pad4(n):
 
 class PretrainEngine:
     def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
-                 heads=CFG5_HEADS, n_ctx=None):
+                 heads=CFG5_HEADS, n_ctx=None, noc=False):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
         variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint.
         heads: the head set (MODEL_HEADS); with 'ew', n_ctx = the enwiki context vocabulary and every batch carries
-        '<kind>_blank_fill/enwiki_context' [B,n,Lc] and '..._len' [B,n]."""
+        '<kind>_blank_fill/enwiki_context' [B,n,Lc] and '..._len' [B,n].
+        noc: the "no composition" model of that head set (NOC_MODEL_HEADS; vqa_pretrain_noc_*).  Its head set (bf, ws)
+        equals cfg-5's, so the flag and not the head set selects it."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("PretrainEngine needs a GPU (no CPU fallback)")
         self.heads = tuple(heads)
-        if self.heads not in MODEL_HEADS.values():
-            raise ValueError("unsupported head set %r" % (self.heads,))
-        self.ext = self.heads != CFG5_HEADS          # vqa_pretrain_ext_* (the cfg-5 head set keeps vqa_pretrain_*)
+        self.noc = bool(noc)
+        if self.heads not in (NOC_MODEL_HEADS if self.noc else MODEL_HEADS).values():
+            raise ValueError("unsupported head set %r%s" % (self.heads, " for a noc model" if self.noc else ""))
+        # vqa_pretrain_ext_* (the cfg-5 head set keeps vqa_pretrain_*); noc: vqa_pretrain_noc_* on the ext dims / batch
+        self.ext = self.noc or self.heads != CFG5_HEADS
         self.n_ctx = int(n_ctx) if "ew" in self.heads else None
-        self.report_keys = report_keys(self.heads)
+        self.report_keys = report_keys(self.heads, self.noc)
         self.device = torch.device(device)
         self.n, self.R, self.D, self.H, self.W, self.A = n, R, D, H, W, A
         self.Vq, self.n_ws, self.deterministic = Vq, n_ws, bool(deterministic)
@@ -197,7 +224,7 @@ class PretrainEngine:
         """Flat parameter / gradient / Adam buffers and the C structs for one of the two LayerNorm variable sets."""
         self.ln_shared = bool(ln_shared)
         self.shapes = variable_shapes(self.Vq, self.n_ws, self.A, self.W, self.D, self.H, self.ln_shared, self.heads,
-                                      self.n_ctx)
+                                      self.n_ctx, self.noc)
         sparse = [k for k in SPARSE_VARS if k in self.shapes]
         dense = sorted(k for k in self.shapes if k not in NO_GRAD_VARS and k not in SPARSE_VARS)
         groups = [[k for k in dense if k.startswith(sc)] for sc in PHASE_SCOPES]
@@ -257,9 +284,20 @@ class PretrainEngine:
                 out[k + "/ew_joint"] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image, KEEP_JOINT,
                                                         self.device)
                 off += Bg * per_image
+        if self.noc:
+            # the l branch of every noc head ({kind}/{head}_joint_l) from a third range; the v branch uses the masks above
+            per_image = n * 2 * H
+            off = NOC_L_MASK_COUNTER + step * (2 * len(self.heads) * Bg * per_image)
+            for h in self.heads:
+                for k in KINDS:
+                    out["%s/%s_joint_l" % (k, h)] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image,
+                                                                     KEEP_JOINT, self.device)
+                    off += Bg * per_image
         return out
 
     def _param_struct(self, table):
+        if self.noc:
+            return self._param_struct_noc(table)
         if self.ext:
             return self._param_struct_ext(table)
 
@@ -279,30 +317,43 @@ class PretrainEngine:
             q_linear_l=fc("q_linear_l", 4), joint_fc=fc("joint_fc", 4), wordset_ft=fc("wordset_ft", 2),
             classifier=fc("classifier", 0))
 
-    def _param_struct_ext(self, table):
-        nh = 2 * len(self.heads)
-
+    def _fc6(self, table):
         def fc(scope, n_ln):
             f = _lib.PtFc6()
-            if scope + "/fc/weights" not in table:       # wordset_ft of a model without the word-set head
+            if scope + "/fc/weights" not in table:       # e.g. wordset_ft of a model without the word-set head
                 return f
             f.w, f.b = table[scope + "/fc/weights"].data_ptr(), table[scope + "/fc/biases"].data_ptr()
             for i in range(min(n_ln, 1) if self.ln_shared else n_ln):
                 f.beta[i] = table[ln_name(scope, i) + "/beta"].data_ptr()
                 f.gamma[i] = table[ln_name(scope, i) + "/gamma"].data_ptr()
             return f
+        return fc
+
+    def _param_struct_ext(self, table):
+        nh = 2 * len(self.heads)
+        fc = self._fc6(table)
+        ptr = lambda k: table[k].data_ptr() if k in table else None      # the enwiki variables exist with 'ew' only
         g, e = "encode_L_blank/rnn/gru_cell/", "encode_L_enwiki/rnn/gru_cell/"
         return _lib.PtExtParams(
             wordset_map=table["wordset_map/learn"].data_ptr(), l_glove=table["L_GloVe/embed_map"].data_ptr(),
-            enwiki_map=table["enwiki_map/learn"].data_ptr(),
+            enwiki_map=ptr("enwiki_map/learn"),
             spat_v_linear_v=fc("spat_v_linear_v", 2), spat_q_linear_v=fc("spat_q_linear_v", 2),
             spat_att_score=fc("spat_att/compute/score", 0), gru_wg=table[g + "gates/kernel"].data_ptr(),
             gru_bg=table[g + "gates/bias"].data_ptr(), gru_wc=table[g + "candidate/kernel"].data_ptr(),
-            gru_bc=table[g + "candidate/bias"].data_ptr(), egru_wg=table[e + "gates/kernel"].data_ptr(),
-            egru_bg=table[e + "gates/bias"].data_ptr(), egru_wc=table[e + "candidate/kernel"].data_ptr(),
-            egru_bc=table[e + "candidate/bias"].data_ptr(), pooled_linear_l=fc("pooled_linear_l", nh),
+            gru_bc=table[g + "candidate/bias"].data_ptr(), egru_wg=ptr(e + "gates/kernel"),
+            egru_bg=ptr(e + "gates/bias"), egru_wc=ptr(e + "candidate/kernel"),
+            egru_bc=ptr(e + "candidate/bias"), pooled_linear_l=fc("pooled_linear_l", nh),
             q_linear_l=fc("q_linear_l", nh), joint_fc=fc("joint_fc", nh), wordset_ft=fc("wordset_ft", 2),
             classifier=fc("classifier", 0))
+
+    def _param_struct_noc(self, table):
+        """the ext struct's trunk members (joint_fc / classifier dropped) plus the two branches' scopes"""
+        ext = self._param_struct_ext(table)
+        nh = 2 * len(self.heads)
+        f = {name: getattr(ext, name) for name, _ in _lib.PtExtParams._fields_ if name not in ("joint_fc", "classifier")}
+        fc = self._fc6(table)
+        return _lib.PtNocParams(joint_v=fc("joint_v", nh), joint_l=fc("joint_l", nh), classifier_v=fc("classifier_v", 0),
+                                classifier_l=fc("classifier_l", 0), **f)
 
     def _dev(self, v, dtype):
         t = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
@@ -380,7 +431,7 @@ class PretrainEngine:
             return bs, B, L, keep
         bx = _lib.PtExtBatch(base=bs)
         Lc = None
-        for ki, k in enumerate(KINDS):
+        for ki, k in enumerate(KINDS if "ew" in self.heads else ()):
             pre = k + "_blank_fill/"
             ck = bx.ctx[ki]
             ck.context = get(pre + "enwiki_context", torch.int32).data_ptr()
@@ -401,12 +452,20 @@ class PretrainEngine:
             bx.ctx_perm, bx.ctx_inv, bx.ctx_live_rows = perm.data_ptr(), inv.data_ptr(), live.ctypes.data
             keep.append(srt["_dev"])
         self._Lc = Lc
-        return bx, B, L, keep
+        if not self.noc:
+            return bx, B, L, keep
+        bn = _lib.PtNocBatch(base=bx)
+        if masks is not None:         # the l branch's keep-masks (make_keep_masks: '<kind>/<head>_joint_l')
+            for ki, k in enumerate(KINDS):
+                for h in self.heads:
+                    setattr(bn.l[ki], "keep_%s_l_joint" % h, masks["%s/%s_joint_l" % (k, h)].data_ptr())
+        return bn, B, L, keep
 
     def tensor(self, name, dtype=torch.float32):
         """Named intermediate of the last forward as a torch view of the workspace (vqa_pretrain_tensor)."""
         off, n = C.c_int64(), C.c_int64()
-        fn = self.lib.vqa_pretrain_ext_tensor if self.ext else self.lib.vqa_pretrain_tensor
+        fn = self.lib.vqa_pretrain_noc_tensor if self.noc else \
+            self.lib.vqa_pretrain_ext_tensor if self.ext else self.lib.vqa_pretrain_tensor
         _lib.check(fn(C.byref(self.dims), name.encode(), C.byref(off), C.byref(n)), "vqa_pretrain_tensor(%s)" % name)
         return self.workspace[off.value:off.value + 4 * n.value].view(dtype)
 
@@ -441,25 +500,28 @@ class PretrainEngine:
             d.global_valid[0], d.global_valid[1] = float(global_valid[0]), float(global_valid[1])
         if self.ext:
             d = _lib.PtExtDims(base=d, heads=head_mask(self.heads), Lc=self._Lc or 0, n_ctx=self.n_ctx or 0)
-        need = int((self.lib.vqa_pretrain_ext_workspace_bytes if self.ext else self.lib.vqa_pretrain_workspace_bytes)(
-            C.byref(d)))
+        need = int((self.lib.vqa_pretrain_noc_workspace_bytes if self.noc else self.lib.vqa_pretrain_ext_workspace_bytes
+                    if self.ext else self.lib.vqa_pretrain_workspace_bytes)(C.byref(d)))
         if need <= 0:
             raise _lib.VqaHotError("vqa_pretrain_workspace_bytes rejected the dims")
         if self.workspace is None or need > self.workspace.numel():
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self.dims, self._bs, self._keepalive = d, bs, keep
-        fwd = self.lib.vqa_pretrain_ext_forward if self.ext else self.lib.vqa_pretrain_forward
+        fwd = self.lib.vqa_pretrain_noc_forward if self.noc else \
+            self.lib.vqa_pretrain_ext_forward if self.ext else self.lib.vqa_pretrain_forward
         _lib.check(fwd(C.byref(d), C.byref(self._p_struct), C.byref(bs), C.c_void_p(self.workspace.data_ptr()),
                        self.workspace.numel(), 1 if want_dz else 0, self._stream()), "vqa_pretrain_forward")
         Bn = B * self.n
+        zs = ("zv", "zl") if self.noc else ("z",)       # noc: the two branches' logits of every head
         self._tape = {"B": B, "kinds": {
             k: dict({"att": self.tensor(k + "/att").view(Bn, self.R), "pooled": self.tensor(k + "/pooled").view(Bn, self.D)},
-                    **{TASK_NAMES[h]: {"z": self.tensor("%s/%s/z" % (k, h)).view(Bn, self.A)} for h in self.heads})
+                    **{TASK_NAMES[h]: {z: self.tensor("%s/%s/%s" % (k, h, z)).view(Bn, self.A) for z in zs}
+                       for h in self.heads})
             for k in KINDS}}
 
     def fetch_report(self, reduce=False, group=None):
-        """report dict of the reference (13 scalars, 19 with the enwiki heads): <kind>_<task>_{loss,acc,top_5_acc},
-        total_loss.  reduce: data parallel -- every scalar is a sum over the shard's rows already divided by the GLOBAL
+        """report dict of the reference (13 scalars, 19 with the enwiki heads or a noc model): <kind>_<task>_{loss,acc,
+        top_5_acc} (noc SPLIT heads: <kind>_<task>_{v,l}_{...}), total_loss.  reduce: data parallel -- every scalar is a sum over the shard's rows already divided by the GLOBAL
         valid count (forward(global_valid=...)), so a SUM all-reduce gives what one process on the whole batch reports."""
         import torch.distributed as dist
         nk = len(self.report_keys)
@@ -473,13 +535,16 @@ class PretrainEngine:
 
     def report_key(self, i):
         """name of report scalar i (vqa_pretrain_report_key / vqa_pretrain_ext_report_key)"""
+        if self.noc:
+            return self.lib.vqa_pretrain_noc_report_key(head_mask(self.heads), i).decode()
         if self.ext:
             return self.lib.vqa_pretrain_ext_report_key(head_mask(self.heads), i).decode()
         return self.lib.vqa_pretrain_report_key(i).decode()
 
     def _backward_phases(self, phases):
         tail = self.grad_flat[self.n_train:]
-        fn = self.lib.vqa_pretrain_ext_backward_phases if self.ext else self.lib.vqa_pretrain_backward_phases
+        fn = self.lib.vqa_pretrain_noc_backward_phases if self.noc else \
+            self.lib.vqa_pretrain_ext_backward_phases if self.ext else self.lib.vqa_pretrain_backward_phases
         _lib.check(fn(
             C.byref(self.dims), C.byref(self._p_struct), C.byref(self._g_struct), C.byref(self._bs),
             C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), C.c_void_p(tail.data_ptr()), phases,
@@ -589,6 +654,29 @@ def export_word_weights(state_dict, vocab, answer_dict, save_dir):
                   {"v_word": g("V_GloVe/embed_map"), "l_word": g("L_GloVe/embed_map"),
                    "l_answer_word": g("LearnAnswerGloVe/embed_map"), "class_weights": g("classifier/fc/weights"),
                    "class_biases": g("classifier/fc/biases")})
+    with open(os.path.join(save_dir, "vocab.pkl"), "wb") as f:
+        pickle.dump(vocab, f)
+    with open(os.path.join(save_dir, "answer_dict.pkl"), "wb") as f:
+        pickle.dump(answer_dict, f)
+    return save_dir
+
+
+def export_noc_word_weights(state_dict, vocab, answer_dict, save_dir):
+    """vlmap_memft/export_noc_word_weights.py:35-95 for a checkpoint of a noc model (what vlmap_answer_noc reads through
+    --vlmap_word_weight_dir): weights.hdf5 with v_word, l_word, l_answer_word and the two heads' v_class_* / l_class_*
+    (export_noc_word_weights.DATASETS), vocab.pkl and answer_dict.pkl."""
+    import os
+    import pickle
+    from . import hdf5_io
+    from .export_noc_word_weights import DATASETS
+    if os.path.exists(save_dir):
+        raise ValueError("Do not overwrite: {}".format(save_dir))
+    missing = [name for _, name in DATASETS if name not in state_dict]
+    if missing:
+        raise KeyError("not a noc checkpoint: no %s" % ", ".join(missing))
+    os.makedirs(save_dir)
+    g = lambda k: np.asarray(state_dict[k].cpu() if torch.is_tensor(state_dict[k]) else state_dict[k])
+    hdf5_io.write(os.path.join(save_dir, "weights.hdf5"), {ds: g(name) for ds, name in DATASETS})
     with open(os.path.join(save_dir, "vocab.pkl"), "wb") as f:
         pickle.dump(vocab, f)
     with open(os.path.join(save_dir, "answer_dict.pkl"), "wb") as f:

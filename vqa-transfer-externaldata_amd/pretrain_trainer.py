@@ -1,7 +1,9 @@
 """Counterpart of vlmap_memft/trainer.py (pre-training stage of BASELINE config 5): same flags and
 defaults (:323-351), two splits (train / val), loop cadence (:202-263), log line, checkpoints
 `model-<step>` every checkpoint_step; `export_word_weights` turns a checkpoint into the
-`word_weights_model-N/` directory the VQA trainer's --vlmap_word_weight_dir expects (run.py:252-286)."""
+`word_weights_model-N/` directory the VQA trainer's --vlmap_word_weight_dir expects (run.py:252-286), and
+`export_noc_word_weights` does the same for a checkpoint of a "no composition" model (the directory vlmap_answer_noc
+reads; run_blank_fill_enwiki.py:214-239)."""
 from __future__ import annotations
 
 import argparse
@@ -17,12 +19,20 @@ from .log import log
 from .model_vlmap_bf_or_wordset_withatt_sp import Model
 from .model_vlmap_bf_or_wordset_enwiki_withatt_sp import Model as EnwikiModel
 from .model_vlmap_bf_enwiki_withatt_sp import Model as BfEnwikiModel
-from .pretrain import export_word_weights  # noqa: F401  (re-exported: the bridge lives with the engine)
+from .model_vlmap_noc_bf_or_wordset_withatt_sp import Model as NocModel
+from .model_vlmap_nocarch_bf_or_wordset_withatt_sp import Model as NocArchModel
+from .model_vlmap_noc_bf_or_enwiki_withatt_sp import Model as NocEnwikiModel
+# re-exported: the bridges live with the engine
+from .pretrain import export_noc_word_weights, export_word_weights  # noqa: F401
 
-# cfg-5 and the two models the reference's pipeline pre-trains (run.py:104-105, vqa_all_run.py:101-102)
+# cfg-5, the two models the reference's pipeline pre-trains (run.py:104-105, vqa_all_run.py:101-102) and the three
+# "no composition" models (vlmap_memft/trainer.py:50-55; run_blank_fill_enwiki.py:104-110)
 _MODEL_CLASSES = {"vlmap_bf_or_wordset_withatt_sp": Model,
                   "vlmap_bf_or_wordset_enwiki_withatt_sp": EnwikiModel,
-                  "vlmap_bf_enwiki_withatt_sp": BfEnwikiModel}
+                  "vlmap_bf_enwiki_withatt_sp": BfEnwikiModel,
+                  "vlmap_noc_bf_or_wordset_withatt_sp": NocModel,
+                  "vlmap_nocarch_bf_or_wordset_withatt_sp": NocArchModel,
+                  "vlmap_noc_bf_or_enwiki_withatt_sp": NocEnwikiModel}
 MODEL_TYPES = list(_MODEL_CLASSES)
 
 

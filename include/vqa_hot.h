@@ -301,7 +301,10 @@ int vqa_attn_pool_bwd(const float* dpooled, const float* v, const float* qv, con
  * [B*rep,R], pooled [B*rep,D] per query; dv [B,R,H] is summed over the queries of a memory. */
 /* tuning / A-B switch: 0 = generic kernel; 1 (default) = the loads-in-flight forward kernel for the models' shapes when
  * rep == 1 and the one-workgroup-per-memory kernel when rep == 5; 2 = also the per-query fast kernel for other reps;
- * 3 = the per-query fast kernel for every rep */
+ * 3 = the per-query fast kernel for every rep.  A 1024-wide memory (D == H == 1024, the adapted memory of
+ * vqa_pretrain_adapt_*) takes loads-in-flight kernels at rep == 5 only (the forward under settings 1 and 2, the
+ * backward under any non-zero setting, like the 2048-wide one); at any other rep, and under 0, it runs on the generic
+ * kernels */
 int vqa_attn_set_fast(int on);
 int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const float* V, const int32_t* nb, const float* w,
                           const float* bias, const uint8_t* keepmask, float keep_prob, float* att, float* pooled,
@@ -786,6 +789,44 @@ int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* dims, const 
                                      void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Pre-training with an adapted memory (csrc/pretrain_model.hip): vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py,
+ * heads VQA_PT_HEAD_BF | VQA_PT_HEAD_WS (any other mask: VQA_ERR_ARG).  The variable-head-set model above with one more
+ * layer (:346-350, :442-446): v_adapt = relu(LN(image_ft @ W + b)) [B,R,H], LayerNorm over the whole [R,H] block of an
+ * image, and the spatial attention pools v_adapt instead of image_ft (:365-367, :461-463), so the pooled vector is
+ * [B*n,H] and pooled_linear_l is [H,H] -- the checkpoint vlmap_answer_adapt transfers.  The FC runs once per image on
+ * the un-tiled features and once for both categories (same weight, bias and input); with VQA_FLAG_SHARED_LN object and
+ * attribute share LayerNorm slot 0 and therefore the whole v_adapt, without it each category normalises the one
+ * pre-activation with its own slot k.  Backward: d v_adapt = vqa_outer_rows_rep over the n queries (and, shared, over both
+ * categories in one launch) -> LayerNorm backward -> ONE dW = image_ft^T (d_pre of both categories) and the bias column
+ * sum; no gradient into the features.
+ * Named intermediates (vqa_pretrain_adapt_tensor): those of vqa_pretrain_ext_tensor with "<obj|attr>/pooled" [B*n,H], plus
+ * "va_pre" [B*R*H], "<obj|attr>/va" (one buffer under both names with VQA_FLAG_SHARED_LN), "d_va".  Report: the 13 scalars
+ * of vqa_pretrain_report_key.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    vqa_pretrain_ext_params_t ext;           /* as for vqa_pretrain_ext_*, pooled_linear_l [H,H] */
+    vqa_pt_fc6_t v_adapt;                    /* [D,H]   LN x2 (object, attribute) */
+} vqa_pretrain_adapt_params_t;
+
+int64_t vqa_pretrain_adapt_workspace_bytes(const vqa_pretrain_ext_dims_t* dims);
+int vqa_pretrain_adapt_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes, int64_t* n_elems);
+/* report key i; NULL past the last or for another head set */
+const char* vqa_pretrain_adapt_report_key(int heads, int i);
+int vqa_pretrain_adapt_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* params,
+                               const vqa_pretrain_ext_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                               void* stream);
+/* grads: same layout as params.  Phases and buckets as vqa_pretrain_ext_backward_phases:
+ *   1, 2, 4  as there (pooled_linear_l's dW and dx with K = H)
+ *   8  as there, the attention backward over v_adapt; then the v_adapt gradients (weights, biases, LayerNorms), which
+ *      need the attention weights and d pooled of both categories and are complete only here */
+int vqa_pretrain_adapt_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* params,
+                                const vqa_pretrain_adapt_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
+                                void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream);
+int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* params,
+                                       const vqa_pretrain_adapt_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
+                                       void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+
+/* ------------------------------------------------------------------------
  * Region-feature extractor, NHWC fp32.
  * ------------------------------------------------------------------------ */
 /* conv + folded inference BatchNorm (+ residual) (+ ReLU):
@@ -978,6 +1019,14 @@ int vqa_reparam_bwd(const float* dx, const float* mean, const float* log_sigma_s
 /* out[b,r,:] = att[b,r] * dp[b,:]: gradient of attention_pooling (vlmap/modules.py:23-39) wrt the pooled memory, needed
  * when the memory is the trainable v_adapt (vqa/model_vlmap_answer_adapt.py:142) instead of the input V_ft. */
 int vqa_outer_rows(const float* att, const float* dp, float* out, int B, int R, int H, void* stream);
+/* the same gradient when `rep` queries pool one memory and when two attentions pool it (the pre-training model
+ * vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py:365-367, 461-463: 5 key boxes per image, object and attribute
+ * attention over one v_adapt):
+ *   out[b,r,:] = sum_{q<rep} att0[b*rep+q, r] * dp0[b*rep+q, :]  (+ the same sum over att1 / dp1 when both are non-NULL)
+ * att* [B*rep,R], dp* [B*rep,H], out [B,R,H] written once; 1 <= rep <= 8.  No atomics and a fixed order (pair 0 before
+ * pair 1, q ascending), so two runs agree bit for bit, and rep = 1 with one pair equals vqa_outer_rows bit for bit. */
+int vqa_outer_rows_rep(const float* att0, const float* dp0, const float* att1, const float* dp1, float* out, int B, int rep,
+                       int R, int H, void* stream);
 /* vqa/model_vlmap_answer_ent.py:196-199: x[(b,m),:] = pl[(b*M+m) % B,:] * ll[b,:] -- the tf.tile([M,1]) + reshape pairing
  * times the broadcast l_linear_l, without materialising the tile; and the gradient wrt ll (pl is behind
  * tf.stop_gradient): dll[b,:] (+)= sum_m dx[(b,m),:] * pl[(b*M+m) % B,:]. */

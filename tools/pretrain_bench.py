@@ -1,7 +1,8 @@
 """Throughput of the cfg-5 pre-training step (BASELINE configs[4], stage 1) at bs 512 on one MI355X.
 
 `--model_type vlmap_bf_or_wordset_enwiki_withatt_sp | vlmap_bf_enwiki_withatt_sp` or one of the "no composition" models
-(vlmap_noc_bf_or_wordset_withatt_sp, vlmap_nocarch_..., vlmap_noc_bf_or_enwiki_withatt_sp) times that model instead and
+(vlmap_noc_bf_or_wordset_withatt_sp, vlmap_nocarch_..., vlmap_noc_bf_or_enwiki_withatt_sp) or the adapted-memory model
+(vlmap_bf_or_wordset_withatt_sp_adapt) times that model instead and
 also prints the analytic MFMA FLOPs per step (flops_per_step) and the rate they give.  `--alternate` builds cfg-5 and the
 chosen model in one process and times their steps alternately (each warmed up first), so that both rates come from the
 same box and clocks.  Without options the output is the cfg-5 line as before."""
@@ -24,23 +25,26 @@ N_CTX, LC = 5000, 7
 _ap = argparse.ArgumentParser()
 _ap.add_argument("steps", nargs="?", type=int, default=10)
 _ap.add_argument("--model_type", default="vlmap_bf_or_wordset_withatt_sp",
-                 choices=sorted(PT.MODEL_HEADS) + sorted(PT.NOC_MODEL_HEADS))
+                 choices=sorted(PT.MODEL_HEADS) + sorted(PT.NOC_MODEL_HEADS) + sorted(PT.ADAPT_MODEL_HEADS))
 _ap.add_argument("--alternate", action="store_true")
 ARGS = _ap.parse_args()
 
 
-def flops_per_step(heads, batch, noc=False):
+def flops_per_step(heads, batch, noc=False, adapt=False):
     """Analytic MFMA FLOPs of one training step from the shapes (forward + dX + dW of every GEMM the step runs; the
     recurrences and their x-projections over the tokens the batch actually holds, i.e. the live rows of the sorted
     batch): per encoder 3 * 2 * tokens * (W + H) * 3H; pooled_linear_l over 2 B n rows; q_linear_l, joint_fc and the
     classifier over 2 B n rows per head type; wordset_ft over 2 B n rows.  noc: joint_v and joint_l (H x 2H each) and
-    classifier_v and classifier_l (2H x A each) in place of joint_fc and the classifier."""
+    classifier_v and classifier_l (2H x A each) in place of joint_fc and the classifier.  adapt: v_adapt over the B R
+    region rows, forward and dW only (the features are an input: no dX), and pooled_linear_l with K = H."""
     Bn = B * n
     tok = lambda key: int(sum(np.asarray(batch["%s_blank_fill/%s" % (k, key)]).sum() for k in PT.KINDS))
     f = 3 * 2 * tok("blanks_len") * (W + H) * 3 * H
     if "ew" in heads:
         f += 3 * 2 * tok("enwiki_context_len") * (W + H) * 3 * H
-    f += 3 * 2 * (2 * Bn) * D * H
+    f += 3 * 2 * (2 * Bn) * (H if adapt else D) * H
+    if adapt:
+        f += 2 * 2 * (B * R) * D * H
     branches = 2 if noc else 1
     f += 3 * 2 * (2 * Bn * len(heads)) * (H * H + branches * (H * 2 * H + 2 * H * A))
     if "ws" in heads:
@@ -85,28 +89,28 @@ if CFG5_TIMED:
           % (dt * 1e3, B / dt, 2 * B * n / dt, rep["total_loss"]))
 
 if ARGS.model_type != "vlmap_bf_or_wordset_withatt_sp" or ARGS.alternate:
-    NOC = ARGS.model_type in PT.NOC_MODEL_HEADS
-    heads = (PT.NOC_MODEL_HEADS if NOC else PT.MODEL_HEADS)[ARGS.model_type]
+    NOC, ADAPT = ARGS.model_type in PT.NOC_MODEL_HEADS, ARGS.model_type in PT.ADAPT_MODEL_HEADS
+    heads = (PT.NOC_MODEL_HEADS if NOC else PT.ADAPT_MODEL_HEADS if ADAPT else PT.MODEL_HEADS)[ARGS.model_type]
     f5 = flops_per_step(PT.CFG5_HEADS, batch)
     runs = {"vlmap_bf_or_wordset_withatt_sp": (eng, db, f5)}
-    if "ew" in heads or NOC:
+    if "ew" in heads or NOC or ADAPT:
         if "ew" in heads:
             data = DV.synthetic_dataset(B, Vq, n_ws, A, R=R, D=D, max_len=L, seed=0, enwiki=dict(n_ctx=N_CTX, Lc=LC))
             dse = DV.Dataset(split="train", data=data, seed=0, enwiki=True)
             be = next(DV.create_ops(B, dse, is_train=True, shuffle=False))
             be = {k: v for k, v in be.items() if v.dtype.kind in "fi" and k != "image_id"}
         else:
-            be = batch                 # the noc word-set model reads cfg-5's batch
+            be = batch                 # the noc word-set model and the adapt model read cfg-5's batch
         n_ctx = N_CTX if "ew" in heads else None
-        pe = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H, heads=heads, n_ctx=n_ctx, noc=NOC)
+        pe = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H, heads=heads, n_ctx=n_ctx, noc=NOC, adapt=ADAPT)
         ee = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=pe, heads=heads, n_ctx=n_ctx,
-                               noc=NOC)
+                               noc=NOC, adapt=ADAPT)
         dbe = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
         if os.environ.get("SORT", "1") != "0":
             dbe.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
         for i in range(3):
             ee.train_step(dbe, ee.make_keep_masks(B, 1, i), 1e-3)
-        runs[ARGS.model_type] = (ee, dbe, flops_per_step(heads, be, NOC))
+        runs[ARGS.model_type] = (ee, dbe, flops_per_step(heads, be, NOC, ADAPT))
     order = list(runs) if ARGS.alternate else [ARGS.model_type]
     times = {k: [] for k in order}
     for i in range(steps):

@@ -128,6 +128,10 @@ class PtNocBatch(C.Structure):
     _fields_ = [("base", PtExtBatch), ("l", PtNocKind * 2)]
 
 
+class PtAdaptParams(C.Structure):
+    _fields_ = [("ext", PtExtParams), ("v_adapt", PtFc6)]
+
+
 SOFTMAX_PAIR_MAX = 8     # VQA_SOFTMAX_PAIR_MAX
 
 
@@ -261,6 +265,7 @@ SIGNATURES = {
     "vqa_reparam_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "vqa_reparam_bwd": (_I, [_P, _P, _P, _P, _F, _P, _P, _L, _P]),
     "vqa_outer_rows": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "vqa_outer_rows_rep": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_tile_mul_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "vqa_tile_mul_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_marginal_entropy": (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -313,6 +318,15 @@ SIGNATURES = {
                                        C.POINTER(PtNocBatch), _P, _L, _P, _P]),
     "vqa_pretrain_noc_backward_phases": (_I, [C.POINTER(PtExtDims), C.POINTER(PtNocParams), C.POINTER(PtNocParams),
                                               C.POINTER(PtNocBatch), _P, _L, _P, _I, _P]),
+    "vqa_pretrain_adapt_workspace_bytes": (_L, [C.POINTER(PtExtDims)]),
+    "vqa_pretrain_adapt_tensor": (_I, [C.POINTER(PtExtDims), C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vqa_pretrain_adapt_report_key": (C.c_char_p, [_I, _I]),
+    "vqa_pretrain_adapt_forward": (_I, [C.POINTER(PtExtDims), C.POINTER(PtAdaptParams), C.POINTER(PtExtBatch), _P, _L, _I,
+                                        _P]),
+    "vqa_pretrain_adapt_backward": (_I, [C.POINTER(PtExtDims), C.POINTER(PtAdaptParams), C.POINTER(PtAdaptParams),
+                                         C.POINTER(PtExtBatch), _P, _L, _P, _P]),
+    "vqa_pretrain_adapt_backward_phases": (_I, [C.POINTER(PtExtDims), C.POINTER(PtAdaptParams), C.POINTER(PtAdaptParams),
+                                                C.POINTER(PtExtBatch), _P, _L, _P, _I, _P]),
 }
 
 ABI_VERSION = 5      # VQA_HOT_ABI_VERSION of include/vqa_hot.h

@@ -59,6 +59,61 @@ __global__ __launch_bounds__(256) void outer_rows_kernel(const float* __restrict
     }
 }
 
+// out[b, r, :] = sum_p sum_{q < rep} att_p[b * rep + q, r] * dp_p[b * rep + q, :]   (p < pairs <= 2): the same gradient when
+// `rep` queries pool one memory (the pre-training model's 5 key boxes per image) and, with two pairs, when two attentions
+// (object, attribute) pool it.  HBM-bound on the store of out (the operands are rep / R and 1 / R of its size): a
+// workgroup owns ROWS rows of one memory, a thread keeps its float4 column of all pairs * rep gradients in registers and
+// the attention weights sit in LDS, so out is written once with 16-byte stores and nothing is read twice from HBM.
+// Fixed summation order (pair 0 before pair 1, q ascending), starting from the first product: with rep = 1 and one pair
+// the result is outer_rows_kernel's bit for bit.
+constexpr int OUTER_REP_MAX = 8, OUTER_REP_ROWS = 12;
+__global__ __launch_bounds__(256) void outer_rows_rep_kernel(const float* __restrict__ att0, const float* __restrict__ dp0,
+                                                             const float* __restrict__ att1, const float* __restrict__ dp1,
+                                                             float* __restrict__ out, int rep, int R, int H) {
+    __shared__ float a_s[2 * OUTER_REP_MAX * OUTER_REP_ROWS];      // [pair][q][row of the chunk]
+    const int b = blockIdx.x, r0 = blockIdx.y * OUTER_REP_ROWS;
+    const int rows = min(OUTER_REP_ROWS, R - r0);
+    const int pairs = att1 != nullptr ? 2 : 1;
+    const int64_t q0 = (int64_t)b * rep;
+    for (int i = threadIdx.x; i < pairs * rep * rows; i += 256) {
+        const int p = i / (rep * rows), j = (i / rows) % rep, r = i % rows;
+        a_s[(p * OUTER_REP_MAX + j) * OUTER_REP_ROWS + r] = (p == 0 ? att0 : att1)[(q0 + j) * R + r0 + r];
+    }
+    __syncthreads();
+    float* o = out + ((int64_t)b * R + r0) * H;
+    if ((H & 3) == 0) {
+        const int H4 = H >> 2;
+        for (int h4 = threadIdx.x; h4 < H4; h4 += 256) {
+            f4 g[2][OUTER_REP_MAX];
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int j = 0; j < OUTER_REP_MAX; ++j)
+                    g[p][j] = (p < pairs && j < rep) ? reinterpret_cast<const f4*>((p == 0 ? dp0 : dp1) + (q0 + j) * H)[h4]
+                                                     : (f4)(0.f);
+            for (int r = 0; r < rows; ++r) {
+                f4 acc = g[0][0] * a_s[r];
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+#pragma unroll
+                    for (int j = 0; j < OUTER_REP_MAX; ++j)
+                        if ((p > 0 || j > 0) && p < pairs && j < rep)
+                            acc += g[p][j] * a_s[(p * OUTER_REP_MAX + j) * OUTER_REP_ROWS + r];
+                reinterpret_cast<f4*>(o + (int64_t)r * H)[h4] = acc;
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < rows * H; i += 256) {
+            const int r = i / H, h = i - r * H;
+            float acc = a_s[r] * dp0[q0 * H + h];
+            for (int p = 0; p < pairs; ++p)
+                for (int j = (p == 0 ? 1 : 0); j < rep; ++j)
+                    acc += a_s[(p * OUTER_REP_MAX + j) * OUTER_REP_ROWS + r] * (p == 0 ? dp0 : dp1)[(q0 + j) * H + h];
+            o[i] = acc;
+        }
+    }
+}
+
 // x[(b, m), :] = pl[(b * M + m) % B, :] * ll[b, :]     (tf.tile([M, 1]) + reshape of vqa/model_vlmap_answer_ent.py:196-199)
 __global__ __launch_bounds__(256) void tile_mul_fwd_kernel(const float* __restrict__ pl, const float* __restrict__ ll,
                                                            float* __restrict__ x, int B, int M, int H) {
@@ -250,6 +305,20 @@ extern "C" int vqa_outer_rows(const float* att, const float* dp, float* out, int
     VQA_REQUIRE((H & 3) != 0 || (vqa_aligned16(dp) && vqa_aligned16(out)), VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
     hipLaunchKernelGGL(outer_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, att, dp, out, R, H);
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+extern "C" int vqa_outer_rows_rep(const float* att0, const float* dp0, const float* att1, const float* dp1, float* out, int B,
+                                  int rep, int R, int H, void* stream) {
+    VQA_REQUIRE(att0 && dp0 && out && B >= 0 && R > 0 && H > 0, VQA_ERR_ARG);
+    VQA_REQUIRE(rep >= 1 && rep <= OUTER_REP_MAX && (att1 == nullptr) == (dp1 == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE((H & 3) != 0 || (vqa_aligned16(dp0) && vqa_aligned16(dp1) && vqa_aligned16(out)), VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    const int chunks = (R + OUTER_REP_ROWS - 1) / OUTER_REP_ROWS;
+    VQA_REQUIRE(chunks <= 65535, VQA_ERR_UNSUPPORTED);
+    hipLaunchKernelGGL(outer_rows_rep_kernel, dim3(B, chunks), dim3(256), 0, (hipStream_t)stream, att0, dp0, att1, dp1, out,
+                       rep, R, H);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }

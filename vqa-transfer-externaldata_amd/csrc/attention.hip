@@ -370,6 +370,79 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
             reinterpret_cast<f32x4v*>(pooled + (q0 + j) * D)[threadIdx.x + c * FWD_THREADS] = acc[j][c];
 }
 
+// The per-memory kernel for a 1024-wide memory (the pre-training model with the adapted memory pools v_adapt [R,1024], not
+// the 2048-wide features): a row is 512 float2 columns, one per thread, so every thread streams V with 8-byte loads (a
+// wave still covers 512 contiguous bytes per row) and sums its rows in order -- the generic kernel's summation order,
+// no thread idle and no partial sums to combine.  Scores and softmax as above.
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+constexpr int REP_N_PF = 6, REP_N_POOL_BATCH = 6;
+template <int H4L, bool MASK, int REP>
+__global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel(
+    const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
+    const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
+    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R) {
+    static_assert(REP <= FWD_THREADS / 64, "one softmax wave per query");
+    constexpr int H = H4L * 256, D = 1024, D2 = D / 2;
+    static_assert(D2 == FWD_THREADS, "one float2 column per thread");
+    extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[REP][H] | s[REP][40]
+    float* qw = lds;
+    float* s = lds + REP * H;
+    const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t q0 = (int64_t)mem * REP;
+    const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
+    const unsigned* mb4 = MASK ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
+    const f32x2v* Vb2 = reinterpret_cast<const f32x2v*>(V + (int64_t)mem * R * D);
+
+    f32x2v xv[REP_N_PF];
+#pragma unroll
+    for (int j = 0; j < REP_N_PF; ++j) xv[j] = Vb2[(int64_t)min(j, R - 1) * D2 + threadIdx.x];
+
+    for (int i = threadIdx.x; i < REP * H; i += FWD_THREADS) qw[i] = qv[q0 * H + i] * w[i % H];
+    const float bias0 = bias[0];
+
+    const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
+    attn_score_rows_rep<H4L, 2, MASK, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
+    attn_score_rows_rep<H4L, 2, MASK, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
+    attn_score_rows_rep<H4L, 1, MASK, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
+    __syncthreads();
+
+    if (wave < REP) {
+        float* sj = s + wave * 40;
+        const int n_valid = nb[mem];
+        const float x = (lane < R && lane < n_valid) ? sj[min(lane, R - 1)] : -INFINITY;      // R <= 40 < 64: one lane per row
+        const float mx = wave_max(x);
+        const float e = (lane < R) ? expf(x - mx) : 0.f;  // all -inf (nb == 0) -> NaN, like TF
+        const float sum = wave_sum(e);
+        if (lane < R) {
+            const float a = e / sum;
+            sj[lane] = a;
+            att_out[(q0 + wave) * R + lane] = a;
+        }
+    }
+    __syncthreads();
+
+    f32x2v acc[REP];
+#pragma unroll
+    for (int j = 0; j < REP; ++j) acc[j] = (f32x2v)(0.f);
+#pragma unroll
+    for (int r = 0; r < REP_N_PF; ++r) {
+#pragma unroll
+        for (int j = 0; j < REP; ++j) acc[j] += ((r < R) ? s[j * 40 + min(r, R - 1)] : 0.f) * xv[r];
+    }
+    for (int r0 = REP_N_PF; r0 < R; r0 += REP_N_POOL_BATCH) {
+        f32x2v y[REP_N_POOL_BATCH];
+#pragma unroll
+        for (int i = 0; i < REP_N_POOL_BATCH; ++i) y[i] = Vb2[(int64_t)min(r0 + i, R - 1) * D2 + threadIdx.x];
+#pragma unroll
+        for (int i = 0; i < REP_N_POOL_BATCH; ++i) {
+#pragma unroll
+            for (int j = 0; j < REP; ++j) acc[j] += ((r0 + i < R) ? s[j * 40 + min(r0 + i, R - 1)] : 0.f) * y[i];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < REP; ++j) reinterpret_cast<f32x2v*>(pooled + (q0 + j) * D)[threadIdx.x] = acc[j];
+}
+
 // Backward.  One workgroup per MEMORY walks its `rep` queries, so dv (the gradient of the shared
 // v block) is accumulated over the queries in registers and written once.  512 threads: the last
 // phase gives every float4 column of v to TWO threads that take alternate rows (dv rows are
@@ -494,25 +567,28 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
 // rows per thread in flight.  Here dpooled of ALL queries of the memory sits in LDS, a wave reads each of its V rows
 // ONCE (two rows in flight) and scores it against the REP queries, the REP softmax backwards run in REP waves, and
 // the dv phase keeps four rows (+ their REP mask words) per thread in flight.  Same per-lane summation order.
-template <int REP, bool MASK>
+// DD = 1024 (REP 5 only is dispatched): the adapted memory of the pre-training model; D4 is then half a workgroup, so
+// half of the threads stage dpooled and a wave's V row is 4 float4 per lane instead of 8.
+template <int REP, bool MASK, int DD = 2048>
 __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
     const float* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
     float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H) {
-    constexpr int D = 2048, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64, RB = 4;
+    constexpr int D = DD, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64, RB = 4;
     static_assert(REP <= NW, "one softmax wave per query");
+    static_assert(D4 <= BWD_THREADS && D4 % 64 == 0, "dpooled is staged with one float4 per thread");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[REP][D] | ds[REP][40] | comb[REP][H]
     float* ds = lds + REP * D;
     float* comb = ds + REP * 40;
     const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t q0 = (int64_t)mem * REP;
     f32x4v* dp4 = reinterpret_cast<f32x4v*>(lds);
-    {
+    if (D4 == BWD_THREADS || threadIdx.x < D4) {      // D == 2048: D4 == BWD_THREADS, every thread
         const f32x4v* g4 = reinterpret_cast<const f32x4v*>(dpooled + q0 * D);
         f32x4v t[REP];
 #pragma unroll
-        for (int j = 0; j < REP; ++j) t[j] = g4[j * D4 + threadIdx.x];       // D4 == BWD_THREADS
+        for (int j = 0; j < REP; ++j) t[j] = g4[j * D4 + threadIdx.x];
 #pragma unroll
         for (int j = 0; j < REP; ++j) dp4[j * D4 + threadIdx.x] = t[j];
     }
@@ -658,7 +734,19 @@ extern "C" int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const floa
     hipStream_t st = (hipStream_t)stream;
     const bool fast = g_attn_fast && (rep == 1 || rep == 5 || g_attn_fast > 1) && R <= 40 && H % 256 == 0 && H <= 1024 && D % 2048 == 0 && D <= 4096 &&
                       vqa_aligned16(qv) && vqa_aligned16(w);
-    if (fast && rep == 5 && g_attn_fast != 3) {
+    // the 1024-wide memory (v_adapt of the pre-training model): per-memory kernel for rep 5 only; one query per memory at
+    // D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
+    const bool fast1024 = g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
+                          vqa_aligned16(qv) && vqa_aligned16(w);
+    if (fast1024) {
+        const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
+        if (keepmask != nullptr)
+            hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, true, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
+                               nb, w, bias, keepmask, ik, att, pooled, R);
+        else
+            hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, false, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
+                               nb, w, bias, keepmask, ik, att, pooled, R);
+    } else if (fast && rep == 5 && g_attn_fast != 3) {
         // one workgroup per memory for the pre-training model's 5 queries per image
         const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
 #define VQA_ATTN_REP5(h4l, d4t)                                                                                        \
@@ -739,6 +827,18 @@ extern "C" int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const
         if (rep == 1) { if (keepmask) VQA_ATTN_BWD_FAST(1, true); else VQA_ATTN_BWD_FAST(1, false); }
         else { if (keepmask) VQA_ATTN_BWD_FAST(5, true); else VQA_ATTN_BWD_FAST(5, false); }
 #undef VQA_ATTN_BWD_FAST
+        VQA_CHECK_LAUNCH();
+        return VQA_OK;
+    }
+    if (g_attn_fast && rep == 5 && D == 1024 && H == 1024 && R <= 40 && vqa_aligned16(dpooled)) {
+        // the 1024-wide memory at 5 queries per memory; rep 1 at D 1024 stays on the generic kernel below
+        const size_t l = (size_t)(5 * D + 5 * 40 + 5 * H) * sizeof(float);
+        if (keepmask)
+            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, true, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
+                               V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
+        else
+            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, false, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
+                               V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
         VQA_CHECK_LAUNCH();
         return VQA_OK;
     }

@@ -667,11 +667,13 @@ __global__ __launch_bounds__(256) void pretrain_ext_report_kernel(ReportExtArgs 
 
 // noc: the "no composition" heads (vqa_pretrain_noc_*): two joint branches and two logit blocks per head instead of
 // jin / joint_fc / classifier
-Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false) {
+// adapt: the attention pools the adapted memory v_adapt [B,R,H] (vqa_pretrain_adapt_*), so the pooled width is H, not D
+Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool adapt = false) {
     const vqa_pretrain_dims_t& d = dx.base;
     const HeadSet hs(dx.heads);
     Layout L;
-    const int64_t B = d.B, n = d.n, R = d.R, D = d.D, H = d.H, W = d.W, A = d.A, T = d.L, Bn = B * n, NH = hs.nh();
+    const int64_t B = d.B, n = d.n, R = d.R, H = d.H, W = d.W, A = d.A, T = d.L, Bn = B * n, NH = hs.nh();
+    const int64_t D = adapt ? d.H : d.D;      // width of the pooled memory
     const int64_t Tc = hs.rank[2] >= 0 ? dx.Lc : 0;
     L.add("S/pooled", 2 * Bn * D); L.add("S/vl_pre", 2 * Bn * H); L.add("S/lft", NH * Bn * H);
     L.add("S/vl", NH * Bn * H); L.add("S/ll_pre", NH * Bn * H); L.add("S/ll", NH * Bn * H);
@@ -758,6 +760,27 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false) {
     auto g = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) {
         gw = max64(gw, vqa_gemm_workspace_floats(tA, tB, (int)M, (int)N, (int)K, 0));
     };
+    if (adapt) {
+        // v_adapt: ONE pre-activation per image (the x n tile and the second category repeat it), one output per
+        // LayerNorm: shared -> "obj/va" and "attr/va" name the same buffer
+        const int64_t S = B * R * H;
+        const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
+        L.add("va_pre", S);
+        if (ln_shared) {
+            L.add("va", S); L.add("va_mean", B); L.add("va_rstd", B);
+        }
+        for (int k = 0; k < 2; ++k) {
+            const std::string p = std::string(KIND[k]) + "/";
+            if (ln_shared) {
+                L.alias(p + "va", "va", 0, S); L.alias(p + "va_mean", "va_mean", 0, B); L.alias(p + "va_rstd", "va_rstd", 0, B);
+            } else {
+                L.add(p + "va", S); L.add(p + "va_mean", B); L.add(p + "va_rstd", B);
+            }
+        }
+        L.add("d_va", S); L.add("d_vapre", S);
+        if (!ln_shared) L.add("d_vapre1", S);      // the attribute call site's d_pre before the two meet
+        g(0, 0, B * R, H, d.D); g(1, 0, d.D, H, B * R);
+    }
     g(0, 0, B * R, H, 6); g(0, 0, Bn, H, 6); g(0, 0, Bn, H, W);
     g(1, 0, 6, H, B * R); g(1, 0, 6, H, Bn); g(1, 0, W, H, Bn); g(0, 1, Bn, W, H);
     for (const int64_t S : {T, Tc}) {        // the two recurrences' x-projection, its dW / dx and the h-row dW
@@ -805,14 +828,17 @@ std::string ext_report_key(int heads, int i) {
     return std::string(KIND[k]) + "_" + TASK_EXT[hs.type[r]] + SUFFIX[j];
 }
 
+// the memory the spatial attention pools when it is not the batch's image_ft [B,R,D]: one [B,R,width] block per category
+struct PoolMem { const float* mem[2]; int64_t width; };
+
 // The trunk of the variable-head-set models, shared by vqa_pretrain_ext_forward and vqa_pretrain_noc_forward: spatial
 // attention and pooling, word sets, the caption batch and the context batch, up to the stacked "S/pooled" and "S/lft"
 // blocks the heads read
 int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                  const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs) {
+                  const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs, const PoolMem* pm = nullptr) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
-    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
+    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
     const int64_t B2 = 2 * Bn;
     const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
     auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
@@ -830,9 +856,9 @@ int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_p
                       p + "v_rstd", nullptr, 1.f));
         TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, spat_q, li(k), (int)n, 0, p + "qv_pre", p + "qv", p + "qv_mean",
                       p + "qv_rstd", nullptr, 1.f));
-        TRY(vqa_attn_pool_fwd_rep(c.f(p + "v"), c.f(p + "qv"), bt->image_ft, bt->num_boxes, P->spat_att_score.w,
-                                  P->spat_att_score.b, kb.keep_att, d->keep_att, c.f(p + "att"), c.f(p + "pooled"),
-                                  (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
+        TRY(vqa_attn_pool_fwd_rep(c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, bt->num_boxes,
+                                  P->spat_att_score.w, P->spat_att_score.b, kb.keep_att, d->keep_att, c.f(p + "att"),
+                                  c.f(p + "pooled"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
                            (int)B, (int)n, d->global_valid[k]);
         VQA_CHECK_LAUNCH();
@@ -894,10 +920,10 @@ int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_p
 // vqa_pretrain_ext_backward_phases and vqa_pretrain_noc_backward_phases
 int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                   const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs,
-                  float* slice_sq, int phases) {
+                  float* slice_sq, int phases, const PoolMem* pm = nullptr) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
-    const int64_t B = d->B, n = d->n, R = d->R, D = d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
+    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
     const int64_t B2 = 2 * Bn;
     const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
     const int det = (d->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0;
@@ -993,9 +1019,9 @@ int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, c
                                       c.st));
             TRY(add_slice_sq(c.f("d_wse"), Bn * W));
         }
-        TRY(vqa_attn_pool_bwd_rep(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), bt->image_ft, c.f(p + "att"),
-                                  P->spat_att_score.w, kb.keep_att, d->keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
-                                  c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
+        TRY(vqa_attn_pool_bwd_rep(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft,
+                                  c.f(p + "att"), P->spat_att_score.w, kb.keep_att, d->keep_att, c.f("d_v"), c.f("d_qv"),
+                                  c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G->spat_att_score.w));
         TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G->spat_att_score.b));
         TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, spat_vP, spat_vG, li(k), (int)R, 0, p + "v_pre",
@@ -1011,9 +1037,11 @@ int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, c
 
 // pooled_linear_l over the 2 Bn pooled rows and q_linear_l over the NH Bn stacked language rows ("S/lft"), then each
 // head's LayerNorm + ReLU of both into its slices of "S/vl" / "S/ll" (v_linear_l / l_linear_l of the reference)
-int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin) {
+// (pooled_width: K of pooled_linear_l when the attention pooled another memory than image_ft; 0 = D)
+int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin,
+                 int64_t pooled_width = 0) {
     const vqa_pretrain_dims_t& d = c.d;
-    const int64_t B = d.B, n = d.n, D = d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
+    const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
     const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
     auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
     auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
@@ -1031,9 +1059,9 @@ int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, co
 
 // its backward from "d_vl" / "d_ll": LayerNorms, pooled_linear_l (dW, d_pooled) and q_linear_l (dW, d_lft)
 int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin,
-                 const vqa_pt_fc6_t& g_pooled, const vqa_pt_fc6_t& g_qlin) {
+                 const vqa_pt_fc6_t& g_pooled, const vqa_pt_fc6_t& g_qlin, int64_t pooled_width = 0) {
     const vqa_pretrain_dims_t& d = c.d;
-    const int64_t B = d.B, n = d.n, D = d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
+    const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
     const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
     auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
     auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
@@ -1083,13 +1111,54 @@ extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, cons
     return VQA_OK;
 }
 
-extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
-                                        int want_dz, void* stream) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+namespace {
+
+// the v_adapt layer of vqa_pretrain_adapt_*: image_ft [B R, D] -> FC -> LayerNorm over each image's [R,H] block + ReLU,
+// one pre-activation, one output per LayerNorm slot in use (pm.mem[1] == pm.mem[0] when the slot is shared)
+int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t& va, PoolMem* pm) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, R = d.R, D = d.D, H = d.H;
+    const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
+    ProbeScope ps("pt.v_adapt.fwd", c.st);
+    TRY(c.gemm(0, 0, B * R, H, D, bt->image_ft, (int)D, va.w, (int)H, c.f("va_pre"), (int)H, va.b));
+    for (int k = 0; k < (ln_shared ? 1 : 2); ++k) {
+        const std::string p = std::string(KIND[k]) + "/";
+        TRY(vqa_ln_act_fwd(c.f("va_pre"), va.gamma[k], va.beta[k], nullptr, 1.f, c.f(p + "va"), c.f(p + "va_mean"),
+                           c.f(p + "va_rstd"), (int)B, (int)R, (int)H, 0, c.st));
+    }
+    pm->mem[0] = c.f("obj/va"); pm->mem[1] = c.f("attr/va"); pm->width = H;
+    return VQA_OK;
+}
+
+// its backward (phase 8, after the attention backward of both categories): d v_adapt from the attention weights and
+// d pooled of the n queries -- shared LayerNorm: both categories pooled the same memory, one launch writes the sum --
+// then the LayerNorm backward per slot, ONE dW over the sum of the call sites' d_pre, no dx (the features are an input)
+int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t& va, const vqa_pt_fc6_t& g_va) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, n = d.n, R = d.R, D = d.D, H = d.H, Bn = B * n;
+    const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
+    ProbeScope ps("pt.v_adapt.bwd", c.st);
+    const float* dp[2] = {c.f("d_pooled"), c.f("d_pooled") + Bn * H};
+    if (ln_shared) {
+        TRY(vqa_outer_rows_rep(c.f("obj/att"), dp[0], c.f("attr/att"), dp[1], c.f("d_va"), (int)B, (int)n, (int)R, (int)H, c.st));
+        TRY(ln_bwd_p(c, acc, c.f("d_va"), B * R, H, fc_slot(va, 0), fc_slot(g_va, 0), 0, (int)R, 0, c.f("va_pre"),
+                     c.f("va_mean"), c.f("va_rstd"), nullptr, 1.f, c.f("d_vapre")));
+    } else {
+        for (int k = 0; k < 2; ++k) {
+            const std::string p = std::string(KIND[k]) + "/";
+            TRY(vqa_outer_rows_rep(c.f(p + "att"), dp[k], nullptr, nullptr, c.f("d_va"), (int)B, (int)n, (int)R, (int)H, c.st));
+            TRY(ln_bwd_p(c, acc, c.f("d_va"), B * R, H, fc_slot(va, k), fc_slot(g_va, k), 0, (int)R, 0, c.f("va_pre"),
+                         c.f(p + "va_mean"), c.f(p + "va_rstd"), nullptr, 1.f, c.f(k == 0 ? "d_vapre" : "d_vapre1")));
+        }
+        TRY(vqa_add_inplace(c.f("d_vapre"), c.f("d_vapre1"), B * R * H, c.st));
+    }
+    return acc.weight(g_va.w, bt->image_ft, (int)D, c.f("d_vapre"), (int)H, D, H, B * R);
+}
+
+// forward of the variable-head-set model on the layout L; va != NULL: with the v_adapt layer (vqa_pretrain_adapt_*)
+int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                     const vqa_pretrain_ext_batch_t* bx, void* workspace, int want_dz, void* stream,
+                     const vqa_pt_fc6_t* va) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
     const HeadSet hs(dims->heads);
@@ -1110,12 +1179,14 @@ extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, con
     ra.rows = (int)Bn;
     ra.nh = (int)NH;
     ProbeScope ps_all("pretrain_ext.forward", c.st);
-    TRY(ext_trunk_fwd(c, dims, P, bx, hs));
+    PoolMem pm{};
+    if (va != nullptr) TRY(v_adapt_fwd(c, bt, *va, &pm));
+    TRY(ext_trunk_fwd(c, dims, P, bx, hs, va ? &pm : nullptr));
     {   // the NH heads, stacked
         const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
         auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
         ProbeScope ps_h("pt.heads.fwd", c.st);
-        TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l));
+        TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l, pm.width));
         TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
         TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
                    P->joint_fc.b));
@@ -1145,19 +1216,29 @@ extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, con
     return VQA_OK;
 }
 
+}  // namespace
+
+extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                        int want_dz, void* stream) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    return ext_forward_impl(L, dims, P, bx, workspace, want_dz, stream, nullptr);
+}
+
 // Backward phases of the variable head set; the buckets of vqa_pretrain_backward_phases, with
 //   1  the NH stacked heads
 //   2  BPTT of the caption batch, then of the enwiki context batch (encode_L_blank and encode_L_enwiki gradients)
 //   4  L_GloVe scatter-add, then enwiki_map scatter-add (both slice sums of squares)
 //   8  per category: wordset_ft / wordset_map (cleared even without the word-set head), spatial attention (writes slice_sq)
-extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
-                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                                void* stream) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+namespace {
+
+// va / g_va != NULL: with the v_adapt layer, whose gradients complete phase 8
+int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                      const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, void* workspace,
+                      float* slice_sq, int phases, void* stream, const vqa_pt_fc6_t* va, const vqa_pt_fc6_t* g_va) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
     const HeadSet hs(dims->heads);
@@ -1186,9 +1267,25 @@ extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* d
         const vqa_pt_fc_t jP = fc_slot(P->joint_fc, 0), jG = fc_slot(G->joint_fc, 0);
         TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, jP, jG, c.f("d_jin")));
         TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
-        TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l));
+        TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l, va ? d->H : 0));
     }
-    return ext_trunk_bwd(c, acc, dims, P, G, bx, hs, slice_sq, phases);
+    if (va == nullptr) return ext_trunk_bwd(c, acc, dims, P, G, bx, hs, slice_sq, phases);
+    const PoolMem pm{{c.f("obj/va"), c.f("attr/va")}, d->H};
+    TRY(ext_trunk_bwd(c, acc, dims, P, G, bx, hs, slice_sq, phases, &pm));
+    return (phases & 8) ? v_adapt_bwd(c, acc, bt, *va, *g_va) : VQA_OK;
+}
+
+}  // namespace
+
+extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                void* stream) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    return ext_backward_impl(L, dims, P, G, bx, workspace, slice_sq, phases, stream, nullptr, nullptr);
 }
 
 extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
@@ -1422,4 +1519,68 @@ extern "C" int vqa_pretrain_noc_backward(const vqa_pretrain_ext_dims_t* dims, co
                                          const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
                                          void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
     return vqa_pretrain_noc_backward_phases(dims, P, G, bn, workspace, workspace_bytes, slice_sq, 15, stream);
+}
+
+// ================================================================ pre-training with the adapted memory
+// vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py (bf | ws): the variable-head-set model with the v_adapt layer
+// (:346-350, :442-446) between the features and the attention pooling (:365-367, :461-463); see v_adapt_fwd / v_adapt_bwd.
+namespace {
+
+bool adapt_dims_ok(const vqa_pretrain_ext_dims_t* d) {
+    return ext_dims_ok(d) && d->heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS);
+}
+
+}  // namespace
+
+extern "C" const char* vqa_pretrain_adapt_report_key(int heads, int i) {
+    return heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS) ? vqa_pretrain_ext_report_key(heads, i) : nullptr;
+}
+
+extern "C" int64_t vqa_pretrain_adapt_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
+    if (!adapt_dims_ok(dims)) return VQA_ERR_ARG;
+    return make_layout_ext(*dims, false, true).total;
+}
+
+extern "C" int vqa_pretrain_adapt_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
+                                         int64_t* n_elems) {
+    if (!adapt_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
+    const Layout L = make_layout_ext(*dims, false, true);
+    const Entry* e = L.find(name);
+    if (e == nullptr) return VQA_ERR_ARG;
+    if (offset_bytes) *offset_bytes = e->off;
+    if (n_elems) *n_elems = e->n;
+    return VQA_OK;
+}
+
+extern "C" int vqa_pretrain_adapt_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                          const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                          int want_dz, void* stream) {
+    VQA_REQUIRE(adapt_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
+    const bool ln_shared = (dims->base.flags & VQA_FLAG_SHARED_LN) != 0;
+    VQA_REQUIRE(P->v_adapt.w && P->v_adapt.b && P->v_adapt.gamma[0] && P->v_adapt.beta[0] &&
+                (ln_shared || (P->v_adapt.gamma[1] && P->v_adapt.beta[1])), VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims, false, true);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    return ext_forward_impl(L, dims, &P->ext, bx, workspace, want_dz, stream, &P->v_adapt);
+}
+
+extern "C" int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                                  const vqa_pretrain_adapt_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                  void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                  void* stream) {
+    VQA_REQUIRE(adapt_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    const bool ln_shared = (dims->base.flags & VQA_FLAG_SHARED_LN) != 0;
+    VQA_REQUIRE(G->v_adapt.w && G->v_adapt.b && G->v_adapt.gamma[0] && G->v_adapt.beta[0] &&
+                (ln_shared || (G->v_adapt.gamma[1] && G->v_adapt.beta[1])), VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims, false, true);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    return ext_backward_impl(L, dims, &P->ext, &G->ext, bx, workspace, slice_sq, phases, stream, &P->v_adapt, &G->v_adapt);
+}
+
+extern "C" int vqa_pretrain_adapt_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                           const vqa_pretrain_adapt_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                           void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
+    return vqa_pretrain_adapt_backward_phases(dims, P, G, bx, workspace, workspace_bytes, slice_sq, 15, stream);
 }

@@ -5,7 +5,8 @@ data_cfg (n_obj_bf, n_attr_bf, max_box_num, vfeat_dim), data_dir, expand_depth. 
 forward pass of the current batch on libvqahot.so through pretrain.PretrainEngine.  The enwiki-context models
 (model_vlmap_bf_or_wordset_enwiki_withatt_sp.py, model_vlmap_bf_enwiki_withatt_sp.py) are this class with another
 MODEL_TYPE, hence head set (pretrain.MODEL_HEADS); the "no composition" models (model_vlmap_noc_*) set NOC
-(pretrain.NOC_MODEL_HEADS, PretrainEngine(noc=True))."""
+(pretrain.NOC_MODEL_HEADS, PretrainEngine(noc=True)), the adapted-memory model (model_vlmap_bf_or_wordset_withatt_sp_adapt.py)
+sets ADAPT (pretrain.ADAPT_MODEL_HEADS, PretrainEngine(adapt=True))."""
 from __future__ import annotations
 
 import os
@@ -27,6 +28,7 @@ class Model(object):
     # the word-set dictionary file (the enwiki models read 'wordset_dict5.pkl', :34 of their files)
     WS_DICT_FILE = "wordset_dict5_depth{depth}.pkl"
     NOC = False       # the "no composition" fusion (joint_v / joint_l, classifier_v / classifier_l)
+    ADAPT = False     # the attention pools v_adapt = fc_layer(V_ft) instead of V_ft
 
     def __init__(self, batch, config, is_train=True):
         self.batch = batch
@@ -44,7 +46,8 @@ class Model(object):
         self.ws_dict = getattr(config, "ws_dict", None) or _load_pickle(os.path.join(
             self.data_dir, self.WS_DICT_FILE.format(depth=int(getattr(config, "expand_depth", 0)))))
         self.num_ws = len(self.ws_dict["vocab"])
-        self.heads = (PT.NOC_MODEL_HEADS if self.NOC else PT.MODEL_HEADS)[self.MODEL_TYPE]
+        self.heads = (PT.NOC_MODEL_HEADS if self.NOC else PT.ADAPT_MODEL_HEADS if self.ADAPT else
+                      PT.MODEL_HEADS)[self.MODEL_TYPE]
         self.num_context_vocab = None
         if "ew" in self.heads:          # enwiki_context_dict_w3_p{p}_n5.pkl (:38-48 of the enwiki models)
             ed = getattr(config, "enwiki_dict", None)
@@ -157,12 +160,13 @@ class Model(object):
             # per-call-site variable set; a checkpoint's variable names override either (PretrainEngine.load_state_dict)
             shapes = PT.variable_shapes(len(self.vocab["vocab"]), self.num_ws, self.num_answer, W_DIM, cfg.vfeat_dim,
                                         V_DIM, bool(getattr(self.config, "ln_shared", 1)), self.heads,
-                                        self.num_context_vocab, self.NOC)
+                                        self.num_context_vocab, self.NOC, self.ADAPT)
             self._engine = PT.PretrainEngine(n=cfg.n_obj_bf, R=cfg.max_box_num, D=cfg.vfeat_dim, H=V_DIM, W=W_DIM,
                                              A=self.num_answer, Vq=len(self.vocab["vocab"]), n_ws=self.num_ws,
                                              params=self._initial_params(shapes), device=self.device,
                                              deterministic=bool(getattr(self.config, "deterministic", 0)),
-                                             heads=self.heads, n_ctx=self.num_context_vocab, noc=self.NOC)
+                                             heads=self.heads, n_ctx=self.num_context_vocab, noc=self.NOC,
+                                             adapt=self.ADAPT)
         eng = self._engine
         B = int((db["image_ft"] if "image_ft" in db else db["image_idx"]).shape[0])
         tables = getattr(self.config, "feature_tables", None)

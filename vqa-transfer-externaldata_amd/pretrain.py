@@ -27,6 +27,12 @@ the engine with `noc=True`: per head, instead of joint_fc(v_linear_l * l_linear_
 joint_v -> classifier_v on v_linear_l and joint_l -> classifier_l on l_linear_l; a blank-fill head's loss is the CE of
 v_logit + l_logit (SUM), a word-set / enwiki head has one CE per branch (SPLIT, NOC_LOSS_MODE).  Those run on
 vqa_pretrain_noc_forward / _backward_phases, and their checkpoints feed export_noc_word_weights -> vlmap_answer_noc.
+
+The adapted-memory model (vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py; ADAPT_MODEL_HEADS) is the engine
+with `adapt=True`: v_adapt = fc_layer(V_ft, 1024, LayerNorm over the [36, 1024] block, ReLU) (:346-350, :442-446) is what
+the attention pools (:365-367, :461-463), so pooled_linear_l is [H, H] -- the only pre-training checkpoint
+vlmap_answer_adapt can transfer its heads from.  It runs on vqa_pretrain_adapt_forward / _backward_phases; the FC is
+computed once per image and once for both categories, and its gradients complete in backward phase 8.
 """
 from __future__ import annotations
 
@@ -47,11 +53,12 @@ SPARSE_VARS = ("wordset_map/learn", "L_GloVe/embed_map", "enwiki_map/learn")   #
 # Order of the dense variables in the flat buffers = the order in which the phases of vqa_pretrain_backward_phases
 # complete their gradients, so every data-parallel bucket is one contiguous range:
 #   [wordset_map | L_GloVe, enwiki_map (phase 4) | GRUs (phase 2) | stacked heads (phase 1) |
-#    spatial attention, wordset_ft (phase 8) | tail]
+#    spatial attention, wordset_ft, v_adapt (phase 8: v_adapt's gradients need the attention backward of both categories) |
+#    tail]
 PHASE_SCOPES = (("encode_L_blank/", "encode_L_enwiki/"),
                 ("classifier/", "joint_fc/", "pooled_linear_l/", "q_linear_l/", "classifier_v/", "classifier_l/", "joint_v/",
                  "joint_l/"),
-                ("spat_att/", "spat_q_linear_v/", "spat_v_linear_v/", "wordset_ft/"))
+                ("spat_att/", "spat_q_linear_v/", "spat_v_linear_v/", "wordset_ft/", "v_adapt/"))
 # head set per model type: blank fill, word set, enwiki context (in TF build order; head 2 r + k of the type of rank r
 # and category k owns LayerNorm slot 2 r + k of the shared fusion scopes when they are not shared)
 MODEL_HEADS = {"vlmap_bf_or_wordset_withatt_sp": ("bf", "ws"),
@@ -67,6 +74,8 @@ NOC_MODEL_HEADS = {"vlmap_noc_bf_or_wordset_withatt_sp": ("bf", "ws"),
                    "vlmap_nocarch_bf_or_wordset_withatt_sp": ("bf", "ws"),
                    "vlmap_noc_bf_or_enwiki_withatt_sp": ("bf", "ew")}
 NOC_LOSS_MODE = {"bf": "sum", "ws": "split", "ew": "split"}
+# the adapted-memory model (the attention pools v_adapt [R, H] instead of the features [R, D])
+ADAPT_MODEL_HEADS = {"vlmap_bf_or_wordset_withatt_sp_adapt": ("bf", "ws")}
 # the l branch's joint keep-masks of the noc heads: counters from here up, below EW_MASK_COUNTER (the v branch reuses the
 # bf / ws / ew joint streams, which keep their bits)
 NOC_L_MASK_COUNTER = 1 << 61
@@ -94,9 +103,11 @@ def report_keys(heads=CFG5_HEADS, noc=False):
             for m in ("loss", "acc", "top_%d_acc" % TOP_K)] + ["total_loss"]
 
 
-def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None, noc=False):
+def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None, noc=False,
+                    adapt=False):
     """Variables of the model with head set `heads` (n_ctx: the enwiki context vocabulary, with 'ew'); noc: joint_v /
-    joint_l and classifier_v / classifier_l instead of joint_fc and classifier."""
+    joint_l and classifier_v / classifier_l instead of joint_fc and classifier; adapt: the v_adapt scope (two call
+    sites: object, attribute) and a pooled_linear_l that reads the H-wide pooled v_adapt."""
     heads = tuple(heads)
     s = {"wordset_map/learn": (n_ws, W), "V_GloVe/embed_map": (Vq, W), "L_GloVe/embed_map": (Vq, W),
          "LearnAnswerGloVe/embed_map": (A, W)}
@@ -122,7 +133,9 @@ def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CF
         s["encode_L_enwiki/rnn/gru_cell/gates/bias"] = (2 * H,)
         s["encode_L_enwiki/rnn/gru_cell/candidate/kernel"] = (W + H, H)
         s["encode_L_enwiki/rnn/gru_cell/candidate/bias"] = (H,)
-    fc("pooled_linear_l", D, H, 2 * len(heads))
+    if adapt:
+        fc("v_adapt", D, H, 2)
+    fc("pooled_linear_l", H if adapt else D, H, 2 * len(heads))
     fc("q_linear_l", H, H, 2 * len(heads))
     for scope in (("joint_v", "joint_l") if noc else ("joint_fc",)):
         fc(scope, H, 2 * H, 2 * len(heads))
@@ -133,11 +146,12 @@ def variable_shapes(Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CF
     return s
 
 
-def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None, noc=False):
+def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, heads=CFG5_HEADS, n_ctx=None, noc=False,
+                       adapt=False):
     """Random-init weights of the architecture (Xavier-uniform FCs, GRU gate bias 1, LN gamma 1,
     embeddings U(-0.01, 0.01); GloVe vectors are download-only)."""
     p = {}
-    for n, shp in variable_shapes(Vq, n_ws, A, W, D, H, ln_shared, heads, n_ctx, noc).items():
+    for n, shp in variable_shapes(Vq, n_ws, A, W, D, H, ln_shared, heads, n_ctx, noc, adapt).items():
         if n.endswith("/weights") or n.endswith("/kernel"):
             lim = np.sqrt(6.0 / (shp[0] + shp[1]))
             p[n] = rng.uniform(-lim, lim, size=shp).astype(np.float32)
@@ -192,22 +206,29 @@ def _pad4(n):
 
 class PretrainEngine:
     def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
-                 heads=CFG5_HEADS, n_ctx=None, noc=False):
+                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
         variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint.
         heads: the head set (MODEL_HEADS); with 'ew', n_ctx = the enwiki context vocabulary and every batch carries
         '<kind>_blank_fill/enwiki_context' [B,n,Lc] and '..._len' [B,n].
         noc: the "no composition" model of that head set (NOC_MODEL_HEADS; vqa_pretrain_noc_*).  Its head set (bf, ws)
-        equals cfg-5's, so the flag and not the head set selects it."""
+        equals cfg-5's, so the flag and not the head set selects it.
+        adapt: the adapted-memory model (ADAPT_MODEL_HEADS; vqa_pretrain_adapt_*), likewise selected by the flag."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("PretrainEngine needs a GPU (no CPU fallback)")
         self.heads = tuple(heads)
-        self.noc = bool(noc)
-        if self.heads not in (NOC_MODEL_HEADS if self.noc else MODEL_HEADS).values():
-            raise ValueError("unsupported head set %r%s" % (self.heads, " for a noc model" if self.noc else ""))
-        # vqa_pretrain_ext_* (the cfg-5 head set keeps vqa_pretrain_*); noc: vqa_pretrain_noc_* on the ext dims / batch
-        self.ext = self.noc or self.heads != CFG5_HEADS
+        self.noc, self.adapt = bool(noc), bool(adapt)
+        if self.noc and self.adapt:
+            raise ValueError("the reference has no model that is both noc and adapt")
+        if self.heads not in (NOC_MODEL_HEADS if self.noc else ADAPT_MODEL_HEADS if self.adapt else MODEL_HEADS).values():
+            raise ValueError("unsupported head set %r%s" % (self.heads, " for a noc model" if self.noc else
+                                                            " for the adapt model" if self.adapt else ""))
+        # vqa_pretrain_ext_* (the cfg-5 head set keeps vqa_pretrain_*); noc / adapt: vqa_pretrain_noc_* / _adapt_* on the
+        # ext dims / batch
+        self.ext = self.noc or self.adapt or self.heads != CFG5_HEADS
+        self._abi = "vqa_pretrain_noc_" if self.noc else "vqa_pretrain_adapt_" if self.adapt else \
+            "vqa_pretrain_ext_" if self.ext else "vqa_pretrain_"
         self.n_ctx = int(n_ctx) if "ew" in self.heads else None
         self.report_keys = report_keys(self.heads, self.noc)
         self.device = torch.device(device)
@@ -224,7 +245,7 @@ class PretrainEngine:
         """Flat parameter / gradient / Adam buffers and the C structs for one of the two LayerNorm variable sets."""
         self.ln_shared = bool(ln_shared)
         self.shapes = variable_shapes(self.Vq, self.n_ws, self.A, self.W, self.D, self.H, self.ln_shared, self.heads,
-                                      self.n_ctx, self.noc)
+                                      self.n_ctx, self.noc, self.adapt)
         sparse = [k for k in SPARSE_VARS if k in self.shapes]
         dense = sorted(k for k in self.shapes if k not in NO_GRAD_VARS and k not in SPARSE_VARS)
         groups = [[k for k in dense if k.startswith(sc)] for sc in PHASE_SCOPES]
@@ -298,6 +319,8 @@ class PretrainEngine:
     def _param_struct(self, table):
         if self.noc:
             return self._param_struct_noc(table)
+        if self.adapt:
+            return _lib.PtAdaptParams(ext=self._param_struct_ext(table), v_adapt=self._fc6(table)("v_adapt", 2))
         if self.ext:
             return self._param_struct_ext(table)
 
@@ -464,8 +487,7 @@ class PretrainEngine:
     def tensor(self, name, dtype=torch.float32):
         """Named intermediate of the last forward as a torch view of the workspace (vqa_pretrain_tensor)."""
         off, n = C.c_int64(), C.c_int64()
-        fn = self.lib.vqa_pretrain_noc_tensor if self.noc else \
-            self.lib.vqa_pretrain_ext_tensor if self.ext else self.lib.vqa_pretrain_tensor
+        fn = getattr(self.lib, self._abi + "tensor")
         _lib.check(fn(C.byref(self.dims), name.encode(), C.byref(off), C.byref(n)), "vqa_pretrain_tensor(%s)" % name)
         return self.workspace[off.value:off.value + 4 * n.value].view(dtype)
 
@@ -500,21 +522,20 @@ class PretrainEngine:
             d.global_valid[0], d.global_valid[1] = float(global_valid[0]), float(global_valid[1])
         if self.ext:
             d = _lib.PtExtDims(base=d, heads=head_mask(self.heads), Lc=self._Lc or 0, n_ctx=self.n_ctx or 0)
-        need = int((self.lib.vqa_pretrain_noc_workspace_bytes if self.noc else self.lib.vqa_pretrain_ext_workspace_bytes
-                    if self.ext else self.lib.vqa_pretrain_workspace_bytes)(C.byref(d)))
+        need = int(getattr(self.lib, self._abi + "workspace_bytes")(C.byref(d)))
         if need <= 0:
             raise _lib.VqaHotError("vqa_pretrain_workspace_bytes rejected the dims")
         if self.workspace is None or need > self.workspace.numel():
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self.dims, self._bs, self._keepalive = d, bs, keep
-        fwd = self.lib.vqa_pretrain_noc_forward if self.noc else \
-            self.lib.vqa_pretrain_ext_forward if self.ext else self.lib.vqa_pretrain_forward
+        fwd = getattr(self.lib, self._abi + "forward")
         _lib.check(fwd(C.byref(d), C.byref(self._p_struct), C.byref(bs), C.c_void_p(self.workspace.data_ptr()),
                        self.workspace.numel(), 1 if want_dz else 0, self._stream()), "vqa_pretrain_forward")
         Bn = B * self.n
         zs = ("zv", "zl") if self.noc else ("z",)       # noc: the two branches' logits of every head
         self._tape = {"B": B, "kinds": {
-            k: dict({"att": self.tensor(k + "/att").view(Bn, self.R), "pooled": self.tensor(k + "/pooled").view(Bn, self.D)},
+            k: dict({"att": self.tensor(k + "/att").view(Bn, self.R),
+                     "pooled": self.tensor(k + "/pooled").view(Bn, self.H if self.adapt else self.D)},
                     **{TASK_NAMES[h]: {z: self.tensor("%s/%s/%s" % (k, h, z)).view(Bn, self.A) for z in zs}
                        for h in self.heads})
             for k in KINDS}}
@@ -537,14 +558,15 @@ class PretrainEngine:
         """name of report scalar i (vqa_pretrain_report_key / vqa_pretrain_ext_report_key)"""
         if self.noc:
             return self.lib.vqa_pretrain_noc_report_key(head_mask(self.heads), i).decode()
+        if self.adapt:
+            return self.lib.vqa_pretrain_adapt_report_key(head_mask(self.heads), i).decode()
         if self.ext:
             return self.lib.vqa_pretrain_ext_report_key(head_mask(self.heads), i).decode()
         return self.lib.vqa_pretrain_report_key(i).decode()
 
     def _backward_phases(self, phases):
         tail = self.grad_flat[self.n_train:]
-        fn = self.lib.vqa_pretrain_noc_backward_phases if self.noc else \
-            self.lib.vqa_pretrain_ext_backward_phases if self.ext else self.lib.vqa_pretrain_backward_phases
+        fn = getattr(self.lib, self._abi + "backward_phases")
         _lib.check(fn(
             C.byref(self.dims), C.byref(self._p_struct), C.byref(self._g_struct), C.byref(self._bs),
             C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), C.c_void_p(tail.data_ptr()), phases,

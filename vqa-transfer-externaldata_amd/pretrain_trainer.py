@@ -22,17 +22,20 @@ from .model_vlmap_bf_enwiki_withatt_sp import Model as BfEnwikiModel
 from .model_vlmap_noc_bf_or_wordset_withatt_sp import Model as NocModel
 from .model_vlmap_nocarch_bf_or_wordset_withatt_sp import Model as NocArchModel
 from .model_vlmap_noc_bf_or_enwiki_withatt_sp import Model as NocEnwikiModel
+from .model_vlmap_bf_or_wordset_withatt_sp_adapt import Model as AdaptModel
 # re-exported: the bridges live with the engine
 from .pretrain import export_noc_word_weights, export_word_weights  # noqa: F401
 
 # cfg-5, the two models the reference's pipeline pre-trains (run.py:104-105, vqa_all_run.py:101-102) and the three
-# "no composition" models (vlmap_memft/trainer.py:50-55; run_blank_fill_enwiki.py:104-110)
+# "no composition" models (vlmap_memft/trainer.py:50-55; run_blank_fill_enwiki.py:104-110), and the adapted-memory model
+# that vlmap_answer_adapt starts from (vlmap_memft/trainer.py:58-59)
 _MODEL_CLASSES = {"vlmap_bf_or_wordset_withatt_sp": Model,
                   "vlmap_bf_or_wordset_enwiki_withatt_sp": EnwikiModel,
                   "vlmap_bf_enwiki_withatt_sp": BfEnwikiModel,
                   "vlmap_noc_bf_or_wordset_withatt_sp": NocModel,
                   "vlmap_nocarch_bf_or_wordset_withatt_sp": NocArchModel,
-                  "vlmap_noc_bf_or_enwiki_withatt_sp": NocEnwikiModel}
+                  "vlmap_noc_bf_or_enwiki_withatt_sp": NocEnwikiModel,
+                  "vlmap_bf_or_wordset_withatt_sp_adapt": AdaptModel}
 MODEL_TYPES = list(_MODEL_CLASSES)
 
 

@@ -474,6 +474,19 @@ typedef struct {
                                      * (vqa_gemm_f32_gather) and leaves V_ft behind as a by-product; default: a gather
                                      * pass in front of the GEMM (same step time, see csrc/fusion_model.hip) */
 #define VQA_FLAG_SHARED_LN 4        /* cfg-5 model only: one LayerNorm per shared fc_layer scope (see vqa_pt_fc_t) */
+#define VQA_FLAG_BF16_GEMM 8        /* opt-in mixed precision of the fusion model's train / eval step: f32 master weights, f32
+                                     * activations and gradients in HBM, f32 accumulation, bf16 operands in the matrix unit
+                                     * (vqa_gemm_bf16: both operands of a routed product rounded to bf16, nearest even).
+                                     * ROUTED (forward y = x W, dW = x^T d_pre and dx = d_pre W^T alike): v_linear_v,
+                                     * q_linear_v, pooled_linear_l, q_linear_l, joint_fc and the answer head.
+                                     * NOT ROUTED, f32 MFMA as without the flag: the question encoder -- the K = W
+                                     * x-projection of the GRU, its weight-stationary / per-step recurrence, its dx product
+                                     * and its weight gradients (dwx, dwh) -- because rounding would compound over the T
+                                     * steps.  Everything that is not a GEMM (LayerNorm, attention, loss, clip, Adam) is f32.
+                                     * Accepted model types: 0 (vlmap_answer) and 1 (standard); every other type, and the
+                                     * flag together with VQA_FLAG_FUSED_GATHER (the gather-fused GEMM has no bf16 form),
+                                     * makes vqa_fusion_workspace_bytes / _tensor / _forward / _backward* return
+                                     * VQA_ERR_ARG.  Per call like VQA_FLAG_DETERMINISTIC: no process-wide state. */
 
 /* One FC(+LN) layer: weights [in,out], biases [out], LayerNorm beta/gamma [out] (NULL if no LN). */
 typedef struct { float *w, *b, *beta, *gamma; } vqa_fc_t;
@@ -908,6 +921,21 @@ int64_t vqa_gemm_bf16x3_workspace_floats(int M, int N, int K, int split_k);
 int vqa_gemm_bf16x3(int transA, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     const float* bias, int split_k, float* workspace, int64_t workspace_floats, void* stream);
 int vqa_gemm_bf16x3_set_mode(int on);
+/* Mixed-precision GEMM of VQA_FLAG_BF16_GEMM (csrc/gemm_bf16.hip):
+ *   C[M,N] = op(A) op(B) (+ bias[N]) (+ D[M,N])      all f32 row-major; transA: A stored [K,M]; transB: B stored [N,K]
+ * NN, TN and NT (both transposed: VQA_ERR_UNSUPPORTED).  Every element of A and B is rounded to bf16 (nearest even) on its way
+ * into LDS -- no bf16 copy reaches HBM --, products run on v_mfma_f32_32x32x16_bf16, accumulation, bias and D are f32 and C
+ * is stored unrounded.  Any M, N, K >= 1 (ragged edges: zero fill, predicated stores); leading dimensions or bases that are
+ * not 16-byte aligned take an element-wise load path.  D may be C itself (accumulate in place).
+ * split_k > 1: that many k ranges (multiples of 32) whose partial products meet in `workspace`
+ * (vqa_gemm_bf16_workspace_floats) and are summed in range order; <= 0: chosen from the shape alone (deep K, few tiles);
+ * 1: one range.  Same inputs give the same bits in every mode.  VQA_ERR_WORKSPACE if the split needs more workspace than
+ * given.  max_blocks > 0: persistent launch with at most that many workgroups (side-stream products), 0: one per unit.
+ * VQA_ERR_ARG: null operand, size < 1, leading dimension smaller than the row.  Nothing is launched on an error. */
+int64_t vqa_gemm_bf16_workspace_floats(int M, int N, int K, int split_k);
+int vqa_gemm_bf16(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
+                  int ldc, const float* bias, const float* D, int ldd, int split_k, float* workspace,
+                  int64_t workspace_floats, int max_blocks, void* stream);
 /* Short-K GEMM with the left operand stationary in registers (csrc/gemm_shortk.hip):
  *   C[M,N] = [relu]( (A[M,K] * B[K,N]) * scale[n] + bias[n] + D[M,N] )     row-major, bias / scale / D optional (NULL)
  * for K <= 512 -- the packed x-projection of the GRU (K = 300; replaces the x half of GRUCell's two matmuls,

@@ -29,6 +29,7 @@ class Dims(C.Structure):
 FLAG_DETERMINISTIC = 1
 FLAG_FUSED_GATHER = 2
 FLAG_SHARED_LN = 4
+FLAG_BF16_GEMM = 8
 
 
 class Fc(C.Structure):
@@ -284,6 +285,8 @@ SIGNATURES = {
     "vqa_gemm_bf16x3_workspace_floats": (_L, [_I, _I, _I, _I]),
     "vqa_gemm_bf16x3": (_I, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _L, _P]),
     "vqa_gemm_bf16x3_set_mode": (_I, [_I]),
+    "vqa_gemm_bf16_workspace_floats": (_L, [_I, _I, _I, _I]),
+    "vqa_gemm_bf16": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _L, _I, _P]),
     "vqa_probe_disable": (_I, []),
     "vqa_fusion_workspace_bytes": (_L, [C.POINTER(Dims)]),
     "vqa_fusion_tensor": (_I, [C.POINTER(Dims), C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -144,6 +144,7 @@ Layout make_layout(const vqa_dims_t& d) {
     int64_t gw = 0;
     auto g = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) {
         gw = max64(gw, vqa_gemm_workspace_floats(tA, tB, (int)M, (int)N, (int)K, 0));
+        if (d.flags & VQA_FLAG_BF16_GEMM) gw = max64(gw, vqa_gemm_bf16_workspace_floats((int)M, (int)N, (int)K, 0));
     };
     g(0, 0, B * R, H, D); g(0, 0, T * B, 2 * H, W); g(0, 0, T * B, H, W); g(0, 0, B, H, H); g(0, 0, B, H, D);
     g(0, 0, B, 2 * H, H); g(0, 0, B, A, 2 * H);                                   // forward
@@ -344,12 +345,23 @@ bool join_side(const Ctx& c, Side& sd) {
 }
 
 
-int gemm(const Ctx& c, int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B,
-         int ldb, float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) {
+// The f32 MFMA product, whatever the flags say: the question encoder's sites (x-projection, dx, dwx, dwh) call this one
+// (include/vqa_hot.h, VQA_FLAG_BF16_GEMM: the unrouted list).
+int gemm_f32(const Ctx& c, int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B,
+             int ldb, float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) {
     // side-stream GEMMs: one workgroup per CU (persistent), so the recurrence on the caller's
     // stream keeps finding free LDS / wave slots on every CU
     return vqa_gemm_f32_ex(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, c.gemm_ws(),
                            c.gemm_ws_floats(), c.lane ? side_max_blocks() : 0, c.st);
+}
+// The dense layers' products (forward, dW, dx): bf16 operands in the matrix unit under VQA_FLAG_BF16_GEMM, else f32.  A
+// shape the bf16 kernel refused would be an error, never a silent f32 product.
+int gemm(const Ctx& c, int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B,
+         int ldb, float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) {
+    if (c.d.flags & VQA_FLAG_BF16_GEMM)
+        return vqa_gemm_bf16(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, c.gemm_ws(),
+                             c.gemm_ws_floats(), c.lane ? side_max_blocks() : 0, c.st);
+    return gemm_f32(c, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd);
 }
 int colsum(const Ctx& c, const float* X, int64_t M, int64_t N, int ldx, float* out) {
     return vqa_colsum(X, (int)M, (int)N, ldx, out, c.colsum_ws(), c.colsum_ws_floats(), c.st);
@@ -359,6 +371,8 @@ bool dims_ok(const vqa_dims_t* d) {
     if (!(d && d->B > 0 && d->R > 0 && d->D > 0 && d->H > 0 && d->T > 0 && d->W > 0 && d->A > 0 && d->Vq > 0 &&
           d->N_img > 0 && d->model_type >= 0 && d->model_type <= VQA_MODEL_LEGACY_VQA))
         return false;
+    // bf16 mode: the two model types whose every dense product is on the routed list, and no gather-fused GEMM
+    if ((d->flags & VQA_FLAG_BF16_GEMM) && (d->model_type > 1 || (d->flags & VQA_FLAG_FUSED_GATHER))) return false;
     if (d->model_type == VQA_MODEL_LEGACY_VQA)      // 16-byte rows everywhere; the scoring kernel keeps one H-row in LDS
         return d->map_dim > 0 && d->La > 0 && d->H % 4 == 0 && d->D % 4 == 0 && d->map_dim % 4 == 0 && d->W % 4 == 0 && d->H <= 1024 && d->Vq > 3;
     if (d->model_type == VQA_MODEL_BI) return d->H % 8 == 0;      // two cells of H / 2 units, 16-byte rows each
@@ -462,7 +476,7 @@ int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt) 
         {
             ProbeScope ps("gru.xp_gemm", c.st);
             TRY(vqa_gru_pack_wx(cell[k].wg, cell[k].wc, cell[k].bg, cell[k].bc, c.f(nm[k][2]), c.f(nm[k][3]), (int)W, (int)h, c.st));
-            TRY(gemm(c, 0, 0, T * B, 3 * h, W, c.f(nm[k][0]), (int)Wp, c.f(nm[k][2]), (int)(3 * h), c.f(nm[k][1]), (int)(3 * h),
+            TRY(gemm_f32(c, 0, 0, T * B, 3 * h, W, c.f(nm[k][0]), (int)Wp, c.f(nm[k][2]), (int)(3 * h), c.f(nm[k][1]), (int)(3 * h),
                      c.f(nm[k][3])));
         }
         float* hs = c.f(nm[k][4]);
@@ -535,10 +549,10 @@ int bi_question_bwd_bptt(const Ctx& c, const vqa_params_t* P, const vqa_params_t
     {
         ProbeScope ps("gru.dx_gemm", c.st);
         TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)h, c.st));
-        TRY(gemm(c, 0, 1, T * B, W, 3 * h, c.f("dxp"), (int)(3 * h), c.f("wx_cat"), (int)(3 * h), c.f("dx_fw"), (int)W));
+        TRY(gemm_f32(c, 0, 1, T * B, W, 3 * h, c.f("dxp"), (int)(3 * h), c.f("wx_cat"), (int)(3 * h), c.f("dx_fw"), (int)W));
         TRY(vqa_gru_pack_wx(P->gru_bw_wg, P->gru_bw_wc, P->gru_bw_bg, P->gru_bw_bc, c.f("wx_cat_bw"), c.f("bx_cat_bw"), (int)W,
                             (int)h, c.st));
-        TRY(gemm(c, 0, 1, T * B, W, 3 * h, c.f("dxp_bw"), (int)(3 * h), c.f("wx_cat_bw"), (int)(3 * h), c.f("dx_bw"), (int)W));
+        TRY(gemm_f32(c, 0, 1, T * B, W, 3 * h, c.f("dxp_bw"), (int)(3 * h), c.f("wx_cat_bw"), (int)(3 * h), c.f("dx_bw"), (int)W));
         TRY(vqa_bi_dx_combine(c.f("dx_fw"), c.f("dx_bw"), bt->q_intseq_len, c.f("dx_embed"), (int)B, (int)T, (int)W, c.st));
     }
     ProbeScope ps("embed.bwd", c.st);
@@ -564,15 +578,15 @@ int bi_question_bwd_weights(const Ctx& c, const vqa_params_t* G, int phases) {
         if (phases & 4) {
             {
                 ProbeScope ps("gru.dwx_gemm", c.st);
-                TRY(gemm(c, 1, 0, Wp, 3 * h, T * B, c.f(nm[k][0]), (int)Wp, dxp, (int)(3 * h), c.f(nm[k][2]), (int)(3 * h)));
+                TRY(gemm_f32(c, 1, 0, Wp, 3 * h, T * B, c.f(nm[k][0]), (int)Wp, dxp, (int)(3 * h), c.f(nm[k][2]), (int)(3 * h)));
                 TRY(vqa_gru_unpack_dwx_bias(c.f(nm[k][2]), gw[k][0], gw[k][1], gw[k][2], gw[k][3], (int)W, (int)h, c.st));
             }
             ProbeScope ps("gru.dwh_gemm", c.st);
-            TRY(gemm(c, 1, 0, h, 2 * h, T * B, c.f(nm[k][3]), (int)h, dxp, (int)(3 * h), gw[k][0] + W * 2 * h, (int)(2 * h)));
+            TRY(gemm_f32(c, 1, 0, h, 2 * h, T * B, c.f(nm[k][3]), (int)h, dxp, (int)(3 * h), gw[k][0] + W * 2 * h, (int)(2 * h)));
         }
         if (phases & 8) {
             ProbeScope ps("gru.dwh_gemm", c.st);
-            TRY(gemm(c, 1, 0, h, h, T * B, c.f(nm[k][4]), (int)h, dxp + 2 * h, (int)(3 * h), gw[k][1] + W * h, (int)h));
+            TRY(gemm_f32(c, 1, 0, h, h, T * B, c.f(nm[k][4]), (int)h, dxp + 2 * h, (int)(3 * h), gw[k][1] + W * h, (int)h));
         }
     }
     return VQA_OK;
@@ -646,7 +660,8 @@ extern "C" int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* P,
     Side& sd = side_stream();
     const bool forked = fork_side(c, sd);
     Ctx cv{*dims, L, c.ws, forked ? sd.s : c.st, forked ? 1 : 0};
-    const bool fuse_gather = gather_mode(dims) == 1 && (D % 32 == 0) && (H % 4 == 0) && vqa_aligned16(bt->table);
+    // (dims_ok refuses the FLAG pair; VQA_HOT_GATHER=fused in the environment must not bring the f32 gather GEMM into a bf16 step either)
+    const bool fuse_gather = !(dims->flags & VQA_FLAG_BF16_GEMM) && gather_mode(dims) == 1 && (D % 32 == 0) && (H % 4 == 0) && vqa_aligned16(bt->table);
     const int mt = dims->model_type;
     // The visual branch (a1 + a2).  With the side stream it is launched first and overlaps the recurrence; on one
     // stream it runs AFTER the question branch, right before the attention that consumes it: V_ft (151 MB) and
@@ -705,10 +720,10 @@ extern "C" int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* P,
     ProbeScope ps("gru.xp_gemm", c.st);
     if (xcat_enabled()) {
         TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-        TRY(gemm(c, 0, 0, T * B, 3 * H, W, c.f("x_tm"), (int)Wp, c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H), c.f("bx_cat")));
+        TRY(gemm_f32(c, 0, 0, T * B, 3 * H, W, c.f("x_tm"), (int)Wp, c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H), c.f("bx_cat")));
     } else {
-        TRY(gemm(c, 0, 0, T * B, 2 * H, W, c.f("x_tm"), (int)Wp, P->gru_wg, (int)(2 * H), xp, (int)(3 * H), P->gru_bg));
-        TRY(gemm(c, 0, 0, T * B, H, W, c.f("x_tm"), (int)Wp, P->gru_wc, (int)H, xp + 2 * H, (int)(3 * H), P->gru_bc));
+        TRY(gemm_f32(c, 0, 0, T * B, 2 * H, W, c.f("x_tm"), (int)Wp, P->gru_wg, (int)(2 * H), xp, (int)(3 * H), P->gru_bg));
+        TRY(gemm_f32(c, 0, 0, T * B, H, W, c.f("x_tm"), (int)Wp, P->gru_wc, (int)H, xp + 2 * H, (int)(3 * H), P->gru_bc));
     }
     }
     float* hs = c.f("hs");
@@ -1105,10 +1120,10 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         static const bool repack = [] { const char* e = getenv("VQA_HOT_REPACK"); return e != nullptr && atoi(e) != 0; }();
         if (repack)
             TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-        TRY(gemm(c, 0, 1, T * B, W, 3 * H, dxp, (int)(3 * H), c.f("wx_cat"), (int)(3 * H), dx, (int)W));
+        TRY(gemm_f32(c, 0, 1, T * B, W, 3 * H, dxp, (int)(3 * H), c.f("wx_cat"), (int)(3 * H), dx, (int)W));
     } else {
-        TRY(gemm(c, 0, 1, T * B, W, 2 * H, dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
-        TRY(gemm(c, 0, 1, T * B, W, H, dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
+        TRY(gemm_f32(c, 0, 1, T * B, W, 2 * H, dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
+        TRY(gemm_f32(c, 0, 1, T * B, W, H, dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
     }
     }
     ProbeScope ps_embed("embed.bwd", c.st);
@@ -1124,24 +1139,24 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         ProbeScope ps("gru.dwx_gemm", c.st);
         if (xcat_enabled()) {   // x rows of BOTH kernels' gradients (the candidate's bucket is reduced after phase 4)
             // rows 0..W-1: x rows of both kernels' gradients; row W (the constant input): both bias gradients
-            TRY(gemm(c, 1, 0, Wp, 3 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), c.f("dwx_cat"), (int)(3 * H)));
+            TRY(gemm_f32(c, 1, 0, Wp, 3 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), c.f("dwx_cat"), (int)(3 * H)));
             TRY(vqa_gru_unpack_dwx_bias(c.f("dwx_cat"), G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc, (int)W, (int)H, c.st));
         } else {
-            TRY(gemm(c, 1, 0, W, 2 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), G->gru_wg, (int)(2 * H)));
+            TRY(gemm_f32(c, 1, 0, W, 2 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), G->gru_wg, (int)(2 * H)));
             TRY(colsum(c, dxp, T * B, 2 * H, (int)(3 * H), G->gru_bg));
         }
         }
         ProbeScope ps("gru.dwh_gemm", c.st);
-        TRY(gemm(c, 1, 0, H, 2 * H, T * B, hs, (int)H, dxp, (int)(3 * H), G->gru_wg + W * 2 * H, (int)(2 * H)));
+        TRY(gemm_f32(c, 1, 0, H, 2 * H, T * B, hs, (int)H, dxp, (int)(3 * H), G->gru_wg + W * 2 * H, (int)(2 * H)));
     }   // phase 3: gates
     if ((phases & 8) && G->gru_wg != nullptr) {
         if (!xcat_enabled()) {
             ProbeScope ps("gru.dwx_gemm", c.st);
-            TRY(gemm(c, 1, 0, W, H, T * B, c.f("x_tm"), (int)Wp, dxp + 2 * H, (int)(3 * H), G->gru_wc, (int)H));
+            TRY(gemm_f32(c, 1, 0, W, H, T * B, c.f("x_tm"), (int)Wp, dxp + 2 * H, (int)(3 * H), G->gru_wc, (int)H));
             TRY(colsum(c, dxp + 2 * H, T * B, H, (int)(3 * H), G->gru_bc));
         }
         ProbeScope ps("gru.dwh_gemm", c.st);
-        TRY(gemm(c, 1, 0, H, H, T * B, c.f("gru_rh"), (int)H, dxp + 2 * H, (int)(3 * H), G->gru_wc + W * H, (int)H));
+        TRY(gemm_f32(c, 1, 0, H, H, T * B, c.f("gru_rh"), (int)H, dxp + 2 * H, (int)(3 * H), G->gru_wc + W * H, (int)H));
     }   // phase 4: candidate
     return VQA_OK;
 }

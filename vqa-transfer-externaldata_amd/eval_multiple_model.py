@@ -30,6 +30,8 @@ def build_parser():
     parser.add_argument("--train_dirs", nargs="+", type=str, default=[], help=" ")
     parser.add_argument("--batch_size", type=int, default=512, help=" ")
     parser.add_argument("--dump_heavy_output", action="store_true", default=False, help=" ")
+    parser.add_argument("--precision", type=str, default="f32", choices=["f32", "bf16"],
+                        help="bf16: the dense layers' products with bf16 operands in the matrix unit (not in the reference)")
     parser.add_argument("--debug", type=int, default=0, help="0: normal, 1: debug")
     return parser
 

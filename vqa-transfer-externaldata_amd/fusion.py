@@ -64,6 +64,10 @@ W_ENTROPY = 0.1               # vqa/model_vlmap_answer_ent.py:14
 LATENT_LOSS_WEIGHT = 0.1      # vqa/model_vlmap_answer_full.py:33
 
 
+PRECISIONS = ("f32", "bf16")
+BF16_MODEL_TYPES = ("vlmap_answer", "standard")       # include/vqa_hot.h, VQA_FLAG_BF16_GEMM
+
+
 def scope_names(model_type):
     """logical layer -> TF variable scope (vqa/model_vlmap_answer.py:126-185,
     vqa/model_standard.py:223-275)."""
@@ -253,8 +257,14 @@ class FusionEngine:
     def __init__(self, *, model_type, B, R, D, H, T, W, A, Vq, N_img, params, device="cuda:0",
                  keep_att=0.8, keep_joint=0.5, global_batch=None, deterministic=None, answer_glove=None,
                  fused_gather=False, num_marginal=NUM_MARGINAL, ent_cols=None, map_dim=None, ft_vlmap=False,
-                 glove_fixed=None, answers=None):
-        """deterministic=True: run-to-run bitwise reproducible steps (the embedding-gradient scatter-add switches
+                 glove_fixed=None, answers=None, precision="f32"):
+        """precision="bf16": opt-in mixed precision -- the dense layers' products (forward, dW, dx of v_linear_v,
+        q_linear_v, pooled_linear_l, q_linear_l, joint_fc and the answer head) round both operands to bf16 on their way
+        into the matrix unit (vqa_gemm_bf16); parameters, Adam slots, activations, gradients and accumulation stay f32,
+        the question encoder and everything that is not a GEMM stay f32, so checkpoints and data parallelism are those
+        of "f32" (the default).  Per engine (VQA_FLAG_BF16_GEMM in vqa_dims_t.flags); model types vlmap_answer and
+        standard, not together with fused_gather.
+        deterministic=True: run-to-run bitwise reproducible steps (the embedding-gradient scatter-add switches
         from float atomics to an atomic-free kernel, ~30 us slower at bs 512).  Per engine: the choice travels in
         vqa_dims_t.flags with every call, no process-wide library state is touched.
         fused_gather=True: no feature-gather pass; v_linear_v's GEMM reads the table rows through image_idx
@@ -267,6 +277,13 @@ class FusionEngine:
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("FusionEngine needs a GPU (no CPU fallback)")
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
+        if precision == "bf16" and model_type not in BF16_MODEL_TYPES:
+            raise ValueError("precision='bf16' covers the model types %s, not %r" % (BF16_MODEL_TYPES, model_type))
+        if precision == "bf16" and fused_gather:
+            raise ValueError("precision='bf16' cannot be combined with fused_gather (the gather-fused GEMM has no bf16 form)")
+        self.precision = precision
         self.device = torch.device(device)
         self.model_type = model_type
         self.sc = scope_names(model_type)
@@ -275,7 +292,8 @@ class FusionEngine:
                               keep_att=keep_att, keep_joint=keep_joint,
                               inv_global_batch=1.0 / float(global_batch or B),
                               flags=(_lib.FLAG_DETERMINISTIC if deterministic else 0) |
-                                    (_lib.FLAG_FUSED_GATHER if fused_gather else 0),
+                                    (_lib.FLAG_FUSED_GATHER if fused_gather else 0) |
+                                    (_lib.FLAG_BF16_GEMM if precision == "bf16" else 0),
                               num_marginal=int(num_marginal) if model_type == "vlmap_answer_ent" else 0,
                               ent_cols=int(ent_cols or A) if model_type == "vlmap_answer_ent" else 0,
                               extra_weight={"vlmap_answer_ent": W_ENTROPY, "vlmap_answer_full": LATENT_LOSS_WEIGHT}.get(model_type, 0.0))

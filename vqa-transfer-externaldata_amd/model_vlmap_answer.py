@@ -274,7 +274,8 @@ class Model(object):
         eng = F.FusionEngine(model_type=self.MODEL_TYPE, B=B, R=self.max_box_num, D=self.vfeat_dim, H=V_DIM, T=T,
                              W=W_DIM, A=self.num_answer, Vq=Vq, N_img=len(self.features),
                              params=self._initial_params(shapes), device=self.device,
-                             global_batch=getattr(self.config, "global_batch", None), **self._engine_kwargs())
+                             global_batch=getattr(self.config, "global_batch", None),
+                             precision=getattr(self.config, "precision", "f32"), **self._engine_kwargs())
         eng.bind_inputs(
             table=self._to_dev(self.features, torch.float32),        # the whole table lives in HBM (a1)
             nbox_table=self._to_dev(self.num_boxes, torch.int32),

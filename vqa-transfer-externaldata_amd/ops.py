@@ -187,6 +187,25 @@ def gemm_bf16x3_ex(A, B, transA=False, bias=None, split_k=1, out=None):
     return Cm
 
 
+def gemm_bf16(A, B, transA=False, transB=False, bias=None, add=None, split_k=0, out=None):
+    """C = op(A) @ op(B) (+bias) (+add) with both operands rounded to bf16 (nearest even) on their way into the matrix
+    unit, f32 accumulation, f32 result (csrc/gemm_bf16.hip; the product of FusionEngine(precision="bf16")).  NN, TN and NT,
+    any shape.  split_k: 0 = chosen from the shape, 1 = one k range, n > 1 = n ranges summed in range order."""
+    lib = _lib.load()
+    assert A.dtype == torch.float32 and B.dtype == torch.float32 and A.stride(-1) == 1 and B.stride(-1) == 1
+    M, K = (A.shape[1], A.shape[0]) if transA else (A.shape[0], A.shape[1])
+    N = B.shape[0] if transB else B.shape[1]
+    assert (B.shape[1] if transB else B.shape[0]) == K
+    Cm = out if out is not None else _f32(M, N, like=A)
+    assert Cm.dtype == torch.float32 and tuple(Cm.shape) == (M, N) and Cm.stride(1) == 1
+    nws = int(lib.vqa_gemm_bf16_workspace_floats(M, N, K, split_k))
+    ws = _f32(max(nws, 4), like=A)
+    _lib.check(lib.vqa_gemm_bf16(int(transA), int(transB), M, N, K, _p(A), A.stride(0), _p(B), B.stride(0), _p(Cm),
+                                 Cm.stride(0), _p(bias), _p(add), add.stride(0) if add is not None else 0, split_k, _p(ws),
+                                 ws.numel(), 0, _st(A)), "vqa_gemm_bf16")
+    return Cm
+
+
 def gemm_bf16x3(A, B, bias=None, out=None):
     """EXPERIMENT: C = A @ B (+ bias) through three-way bf16 splits and six bf16 MFMA products per a*b (f32-equivalent
     products; csrc/gemm_bf16x3.hip).  Whole 128 x 128 x 32 tiles only; the product path uses gemm() (exact f32 MFMA)."""

@@ -324,6 +324,9 @@ def build_parser():
                              "reference; results are unchanged)")
     parser.add_argument("--device_batch_cache_gb", type=int, default=32,
                         help="keep the cached padded batches on the device up to this many GiB (not in the reference)")
+    parser.add_argument("--precision", type=str, default="f32", choices=["f32", "bf16"],
+                        help="bf16: the dense layers' products with bf16 operands in the matrix unit, f32 master weights and "
+                             "accumulation (vlmap_answer and standard; not in the reference; checkpoints are those of f32)")
     parser.add_argument("--debug", type=int, default=0, help="0: normal, 1: debug")
     return parser
 

@@ -572,6 +572,8 @@ int vqa_fusion_backward(const vqa_dims_t* dims, const vqa_params_t* params, cons
 /* ------------------------------------------------------------------------
  * Whole cfg-5 pre-training model (vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py:54-94,
  * 323-609, 675-706) and its backward, one host call each -- the same shape as vqa_fusion_forward / _backward.
+ * These entry points are the VQA_PT_HEAD_BF | VQA_PT_HEAD_WS case of the variable-head-set path below (vqa_pretrain_ext_*):
+ * they widen their arguments to its structs and run it, so layout, kernels and results are those of that head set.
  * ------------------------------------------------------------------------ */
 typedef struct {
     int32_t B, n, R, D, H, W, A, Vq, n_ws;  /* images, entries per category (5), regions, feature / hidden / word dims,
@@ -661,7 +663,7 @@ int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pret
  *   VQA_PT_HEAD_BF | VQA_PT_HEAD_WS | VQA_PT_HEAD_EW   vlmap_bf_or_wordset_enwiki_withatt_sp
  *   VQA_PT_HEAD_BF | VQA_PT_HEAD_EW                    vlmap_bf_enwiki_withatt_sp (wordset_map exists, its gradient is 0;
  *                                                      no wordset_ft)
- *   VQA_PT_HEAD_BF | VQA_PT_HEAD_WS                    the cfg-5 model again (same results as vqa_pretrain_*)
+ *   VQA_PT_HEAD_BF | VQA_PT_HEAD_WS                    the cfg-5 model (what vqa_pretrain_* runs)
  * Head h = 2 r + k: type of rank r among the enabled types (bf < ws < ew), category k (0 object, 1 attribute).  Without
  * VQA_FLAG_SHARED_LN head h owns LayerNorm slot h of pooled_linear_l / q_linear_l / joint_fc (TF graph build order:
  * `LayerNorm` ... `LayerNorm_5` with all three types, ... `LayerNorm_3` for bf | ew); with it every head uses slot 0.
@@ -892,7 +894,8 @@ int vqa_crop_and_resize_nhwc(const float* fmap, int B, int H, int W, int C, cons
  *   backward  "backward" = { "head.bwd_gemm", "fc.ln_bwd", "fc.dw_gemm", "fc.dx_gemm", "eltwise", "attn_pool.bwd",
  *             "v_linear_v.ln_bwd", "v_linear_v.dw_gemm", "gru.bwd", "gru.dx_gemm", "embed.bwd", "gru.dwx_gemm",
  *             "gru.dwh_gemm" }
- *   cfg-5     "pretrain.forward", "pretrain.backward" and "pt.*" groups (csrc/pretrain_model.hip)
+ *   pre-training  "pretrain_ext.forward", "pretrain_ext.backward" (cfg 5 too: it runs the ext path), "pretrain_noc.*" and
+ *             the "pt.*" groups (csrc/pretrain_model.hip)
  * vqa_probe_enable(labels, max_samples): `labels` is a comma-separated list ("*" = every scope met); HIP events are
  * recorded around every enabled group, at most max_samples per label.  vqa_probe_read_label synchronises the events of
  * one label and returns its per-sample durations in milliseconds (vqa_probe_read: the first label of the list).

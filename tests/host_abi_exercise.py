@@ -29,6 +29,10 @@ ok(lib.vqa_hot_version() == _lib.ABI_VERSION, "version")
 ok(lib.vqa_hot_error_string(0) == b"ok" and lib.vqa_hot_error_string(-99) is not None, "error strings")
 ok([lib.vqa_report_key(i) is not None for i in range(-2, 16)] == [False] * 2 + [True] * 13 + [False] * 3, "report keys")
 ok([lib.vqa_pretrain_report_key(i) is not None for i in range(-1, 15)] == [False] + [True] * 13 + [False] * 2, "pretrain keys")
+PRETRAIN_KEYS = [b"obj_blank_fill_loss", b"obj_blank_fill_acc", b"obj_blank_fill_top_5_acc", b"obj_wordset_loss", b"obj_wordset_acc",
+                 b"obj_wordset_top_5_acc", b"attr_blank_fill_loss", b"attr_blank_fill_acc", b"attr_blank_fill_top_5_acc",
+                 b"attr_wordset_loss", b"attr_wordset_acc", b"attr_wordset_top_5_acc", b"total_loss"]
+ok([lib.vqa_pretrain_report_key(i) for i in range(14)] == PRETRAIN_KEYS + [None], "pretrain key names")
 
 # fusion model: workspace + every named tensor, for all five model types and a sweep of sizes (ragged, tiny, full)
 off, n = C.c_int64(), C.c_int64()
@@ -109,6 +113,14 @@ for flags in (0, 4, 5):
             ok(lib.vqa_pretrain_tensor(C.byref(pd), nm, C.byref(off), C.byref(n)) == 0, "pretrain tensor %s" % nm)
             ok(off.value + 4 * n.value <= total and off.value >= 0, "pretrain tensor %s inside" % nm)
         ok(lib.vqa_pretrain_tensor(C.byref(pd), b"nope", C.byref(off), C.byref(n)) == -1, "pretrain unknown")
+        # the cfg-5 entry points are the bf | ws case of the variable-head-set path: same layout, name by name
+        xd = _lib.PtExtDims(base=pd, heads=3, Lc=0, n_ctx=0)
+        ok(total == lib.vqa_pretrain_ext_workspace_bytes(C.byref(xd)), "pretrain workspace == ext workspace, heads 3")
+        xoff, xn = C.c_int64(), C.c_int64()
+        for nm in pnames + [b"d_lft", b"d_pooled", b"obj/ws/stats", b"attr/bf/j_mean"]:
+            ok(lib.vqa_pretrain_tensor(C.byref(pd), nm, C.byref(off), C.byref(n)) == 0 and
+               lib.vqa_pretrain_ext_tensor(C.byref(xd), nm, C.byref(xoff), C.byref(xn)) == 0, "pretrain / ext tensor %s" % nm)
+            ok((off.value, n.value) == (xoff.value, xn.value), "pretrain tensor %s == ext tensor" % nm)
 ok(lib.vqa_pretrain_workspace_bytes(C.byref(_lib.PtDims(B=1, n=9, R=1, D=4, H=4, W=1, A=1, Vq=1, n_ws=1, L=1))) < 0, "n > 8")
 ok(lib.vqa_pretrain_forward(None, None, None, None, 0, 1, None) == -1, "pretrain forward null")
 pd = _lib.PtDims(B=2, n=5, R=6, D=16, H=8, W=12, A=12, Vq=20, n_ws=7, L=4, keep_att=0.8, keep_joint=0.5)

@@ -1,20 +1,32 @@
-// Host-side composition of the cfg-5 pre-training model: one call enqueues the whole forward
-// (or backward) pass of vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py on the caller's stream -- the
-// counterpart of vqa_fusion_forward / vqa_fusion_backward for the fusion model.
+// Host-side composition of the pre-training models: one call enqueues the whole forward (or backward)
+// pass on the caller's stream -- the counterpart of vqa_fusion_forward / vqa_fusion_backward for the fusion model.
+// ONE code path serves every model; a model is a head set plus, for two of them, another head block or pooled memory:
+//   vqa_pretrain_*        cfg 5, vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py: heads bf | ws.  Thin adapters onto
+//   vqa_pretrain_ext_*    model_vlmap_bf_or_wordset_enwiki_withatt_sp.py (bf | ws | ew), model_vlmap_bf_enwiki_withatt_sp.py
+//                         (bf | ew)
+//   vqa_pretrain_noc_*    the "no composition" heads on the same trunk (see that section)
+//   vqa_pretrain_adapt_*  the v_adapt layer between the features and the attention pooling (see that section)
 //
-// Per category k in {object, attribute} (reference lines relative to that file):
+// Per category k in {object, attribute} (reference lines relative to the cfg-5 file):
 //   build_*_V_ft      :323-364, :414-455   6-d box -> FC 1024 + LN + ReLU for the 36 regions (once per image) and the
 //                                          n = 5 key boxes, Hadamard attention + pooling over the raw features with the
 //                                          x5 tile of V_ft never materialised (attn_pool_*_rep)
 //   build_*_blank_fill:505-609             L_GloVe embedding -> GRU over the caption with a blank (length-sorted live
 //                                          prefix) -> fusion MLP -> classifier -> masked softmax-CE, top-1 / top-5
 //   build_*_wordset   :366-412, :457-503   tanh(word-set embedding) -> FC + LN + tanh -> the same fusion MLP
+//   build_*_enwiki    (enwiki file :519-624) enwiki_map embedding of the answer's Wikipedia context -> a second GRU
+//                                          (encode_L_enwiki, shared by both categories) -> the same fusion MLP and
+//                                          classifier -> masked softmax-CE over the blank-fill fills
 //   n_way_classification_loss :675-706
+// Head h = 2 r + k for the type of rank r among the enabled ones (bf < ws < ew) and category k; the heads share
+// pooled_linear_l, q_linear_l, joint_fc and the classifier, so their rows are stacked and every shared FC is ONE GEMM
+// over NH Bn rows (2 Bn for pooled_linear_l): for cfg 5, M = 2560 leaves the last round of tiles half empty (1260 tiles of
+// 128x64 on 512 workgroup slots = 2.46 rounds), M = 10240 does not (9.84).  LayerNorm and the loss run per slice.
 // LayerNorm variables of an fc_layer scope entered by several call sites: with VQA_FLAG_SHARED_LN (what TF 1.x builds:
 // leaving the string-named scope zeroes its sub-scope counts, so the un-scoped layers.layer_norm gets the un-suffixed
 // name again and AUTO_REUSE shares it -- oracle/pretrain_oracle.py) every call site uses slot 0 and the
-// call sites' d_gamma / d_beta are accumulated; without the flag each call site owns slot [ki] (V_ft / blank-fill /
-// wordset_ft) or [2 t + ki] (the four heads of the shared fusion MLP) in TF graph build order.
+// call sites' d_gamma / d_beta are accumulated; without the flag each call site owns slot [k] (V_ft / blank-fill /
+// wordset_ft) or [h] (the heads of the shared fusion MLP) in TF graph build order.
 //
 // The workspace layout is a function of the dims alone, so the host views named intermediates without copies.
 #include <string.h>
@@ -76,27 +88,6 @@ __global__ __launch_bounds__(256) void gather_rows2_kernel(const uint32_t* __res
     }
 }
 
-// report[3 h + j] = sum_rows stats_h[:, j] * inv_valid_h (j = loss, top-1, top-k), report[12] = sum of the 4 losses
-struct ReportArgs { const float* stats[4]; const float* inv[4]; int rows; };
-__global__ __launch_bounds__(256) void pretrain_report_kernel(ReportArgs a, float* __restrict__ report) {
-    __shared__ float red[16];
-    __shared__ float loss[4];
-    for (int h = 0; h < 4; ++h) {
-        for (int j = 0; j < 3; ++j) {
-            float s = 0.f;
-            for (int i = threadIdx.x; i < a.rows; i += 256) s += a.stats[h][(int64_t)i * 4 + j];
-            s = block_sum(s, red);
-            if (threadIdx.x == 0) {
-                const float v = s * a.inv[h][0];
-                report[3 * h + j] = v;
-                if (j == 0) loss[h] = v;
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) report[12] = ((loss[0] + loss[1]) + loss[2]) + loss[3];
-}
-
 // row stride of the time-major GRU inputs: W word-vector columns, the constant 1 (its row of the x-part weight gradient
 // is the bias gradient), zero padding to 16 bytes
 inline int64_t x_stride(int64_t W) { return ((W + 1 + 3) / 4) * 4; }
@@ -123,93 +114,10 @@ struct Layout {
 };
 
 const char* const KIND[2] = {"obj", "attr"};
-const char* const HEAD[2] = {"bf", "ws"};      // blank fill, word set
+const char* const HEAD[3] = {"bf", "ws", "ew"};      // blank fill, word set, enwiki context
+const char* const TASK[3] = {"blank_fill", "wordset", "enwiki"};
 
 int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
-
-Layout make_layout(const vqa_pretrain_dims_t& d) {
-    Layout L;
-    const int64_t B = d.B, n = d.n, R = d.R, D = d.D, H = d.H, W = d.W, A = d.A, T = d.L, Bn = B * n;
-    // The four heads (ln = 2 t + k: obj/bf, attr/bf, obj/ws, attr/ws) share pooled_linear_l, q_linear_l, joint_fc and the
-    // classifier, so their rows are stacked and every shared FC is ONE GEMM over 4 Bn (2 Bn for pooled_linear_l) rows:
-    // M = 2560 leaves the last round of tiles half empty (1260 tiles of 128x64 on 512 workgroup slots = 2.46 rounds),
-    // M = 10240 does not (9.84).  The per-head names below are views into the stacked blocks.
-    L.add("S/pooled", 2 * Bn * D); L.add("S/vl_pre", 2 * Bn * H); L.add("S/lft", 4 * Bn * H);
-    L.add("S/vl", 4 * Bn * H); L.add("S/ll_pre", 4 * Bn * H); L.add("S/ll", 4 * Bn * H); L.add("S/jin", 4 * Bn * H);
-    L.add("S/j_pre", 4 * Bn * 2 * H); L.add("S/j", 4 * Bn * 2 * H);
-    L.add("S/z", 4 * Bn * A); L.add("S/dz", 4 * Bn * A); L.add("S/stats", 4 * Bn * 4);
-    for (int k = 0; k < 2; ++k) {
-        const std::string p = std::string(KIND[k]) + "/";
-        L.add(p + "key6", Bn * 6);
-        L.add(p + "v_pre", B * R * H); L.add(p + "v", B * R * H); L.add(p + "v_mean", B); L.add(p + "v_rstd", B);
-        L.add(p + "qv_pre", Bn * H); L.add(p + "qv", Bn * H); L.add(p + "qv_mean", B); L.add(p + "qv_rstd", B);
-        L.add(p + "att", Bn * R);
-        L.alias(p + "pooled", "S/pooled", k * Bn * D, Bn * D); L.alias(p + "vl_pre", "S/vl_pre", k * Bn * H, Bn * H);
-        L.add(p + "valid", Bn); L.add(p + "inv_valid", 4);
-        L.alias(p + "bf_state", "S/lft", k * Bn * H, Bn * H);
-        L.add(p + "wse", Bn * W); L.add(p + "ws", Bn * W);
-        L.add(p + "wf_pre", Bn * H); L.alias(p + "wf", "S/lft", (2 + k) * Bn * H, Bn * H);
-        L.add(p + "wf_mean", B); L.add(p + "wf_rstd", B);
-        for (int t = 0; t < 2; ++t) {
-            const std::string q = p + HEAD[t] + "/";
-            const int64_t ln = 2 * t + k;
-            L.alias(q + "vl", "S/vl", ln * Bn * H, Bn * H); L.add(q + "vl_mean", B); L.add(q + "vl_rstd", B);
-            L.alias(q + "ll_pre", "S/ll_pre", ln * Bn * H, Bn * H); L.alias(q + "ll", "S/ll", ln * Bn * H, Bn * H);
-            L.add(q + "ll_mean", B); L.add(q + "ll_rstd", B);
-            L.alias(q + "jin", "S/jin", ln * Bn * H, Bn * H);
-            L.alias(q + "j_pre", "S/j_pre", ln * Bn * 2 * H, Bn * 2 * H); L.alias(q + "j", "S/j", ln * Bn * 2 * H, Bn * 2 * H);
-            L.add(q + "j_mean", B); L.add(q + "j_rstd", B);
-            L.alias(q + "z", "S/z", ln * Bn * A, Bn * A); L.alias(q + "dz", "S/dz", ln * Bn * A, Bn * A);
-            L.alias(q + "stats", "S/stats", ln * Bn * 4, Bn * 4);
-        }
-    }
-    // blank-fill captions of BOTH categories as one batch of 2 Bn rows (object rows first), time-major: the GRU weights are
-    // shared, so one recurrence over 5120 rows replaces two over 2560 (half the step launches, tiles that fill the chip)
-    L.add("J/blanks_s", 2 * Bn * T); L.add("J/lens_s", 2 * Bn);
-    L.add("J/x_tm", T * 2 * Bn * x_stride(W)); L.add("J/xp", T * 2 * Bn * 3 * H); L.add("J/hs", (T + 1) * 2 * Bn * H);
-    L.add("J/gru_r", T * 2 * Bn * H); L.add("J/gru_u", T * 2 * Bn * H); L.add("J/gru_c", T * 2 * Bn * H);
-    L.add("J/gru_rh", T * 2 * Bn * H);
-    L.add("wx_cat", W * 3 * H); L.add("bx_cat", 3 * H); L.add("dwx_cat", x_stride(W) * 3 * H);      // packed x rows of the GRU kernels
-    L.add("report", 16);
-    // backward scratch, shared by the two categories
-    L.add("d_j", 4 * Bn * 2 * H); L.add("d_jpre", 4 * Bn * 2 * H); L.add("d_jin", 4 * Bn * H);
-    L.add("d_vl", 4 * Bn * H); L.add("d_ll", 4 * Bn * H); L.add("d_vlpre", 4 * Bn * H); L.add("d_llpre", 4 * Bn * H);
-    L.add("d_lft", 4 * Bn * H); L.add("d_pooled", 2 * Bn * D);
-    L.add("d_state_s", 2 * Bn * H); L.add("d_hscratch", 2 * Bn * H);
-    L.add("dxp", T * 2 * Bn * 3 * H); L.add("dx", T * 2 * Bn * W);
-    L.add("d_wfpre", Bn * H); L.add("d_ws", Bn * W); L.add("d_wse", Bn * W);
-    L.add("d_v", B * R * H); L.add("d_vpre", B * R * H); L.add("d_qv", Bn * H); L.add("d_qvpre", Bn * H);
-    L.add("part_a", B * 2 * H); L.add("part_b", B * 2 * H); L.add("part_c", B * 2 * H);
-    L.add("part_dw", Bn * H); L.add("part_db", Bn);
-    L.add("vec_a", max64(max64(A, 3 * H), 16)); L.add("vec_b", max64(max64(A, 3 * H), 16));
-    L.add("vec_c", max64(max64(A, 3 * H), 16));
-    L.add("sq", 16);
-    int64_t gw = 4;
-    auto g = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) {
-        gw = max64(gw, vqa_gemm_workspace_floats(tA, tB, (int)M, (int)N, (int)K, 0));
-    };
-    g(0, 0, B * R, H, 6); g(0, 0, Bn, H, 6); g(0, 0, Bn, H, D); g(0, 0, Bn, H, H); g(0, 0, Bn, 2 * H, H);
-    g(0, 0, Bn, A, 2 * H);
-    g(0, 0, 2 * T * Bn, 3 * H, W); g(0, 1, 2 * T * Bn, W, 3 * H); g(1, 0, x_stride(W), 3 * H, 2 * T * Bn);      // packed x-projection
-    g(1, 0, H, 2 * H, 2 * T * Bn); g(1, 0, H, H, 2 * T * Bn);
-    g(0, 0, 2 * Bn, H, D); g(0, 0, 4 * Bn, H, H); g(0, 0, 4 * Bn, 2 * H, H); g(0, 0, 4 * Bn, A, 2 * H);      // stacked heads
-    g(1, 0, 2 * H, A, 4 * Bn); g(0, 1, 4 * Bn, 2 * H, A); g(1, 0, H, 2 * H, 4 * Bn); g(0, 1, 4 * Bn, H, 2 * H);
-    g(1, 0, D, H, 2 * Bn); g(0, 1, 2 * Bn, D, H); g(1, 0, H, H, 4 * Bn); g(0, 1, 4 * Bn, H, H); g(0, 0, T * Bn, 2 * H, W); g(0, 0, T * Bn, H, W); g(0, 0, Bn, H, W);
-    g(1, 0, 2 * H, A, Bn); g(0, 1, Bn, 2 * H, A); g(1, 0, H, 2 * H, Bn); g(0, 1, Bn, H, 2 * H); g(1, 0, D, H, Bn);
-    g(0, 1, Bn, D, H); g(1, 0, H, H, Bn); g(0, 1, Bn, H, H); g(1, 0, W, H, Bn); g(0, 1, Bn, W, H);
-    g(1, 0, W, 2 * H, T * Bn); g(1, 0, H, 2 * H, T * Bn); g(1, 0, W, H, T * Bn); g(1, 0, H, H, T * Bn);
-    g(0, 1, T * Bn, W, 2 * H); g(0, 1, T * Bn, W, H); g(1, 0, 6, H, B * R); g(1, 0, 6, H, Bn);
-    L.add("gemm_ws", gw);
-    int64_t cw = 4;
-    cw = max64(cw, vqa_colsum_workspace_floats((int)B, (int)(2 * H)));
-    cw = max64(cw, vqa_colsum_workspace_floats((int)Bn, (int)A));
-    cw = max64(cw, vqa_colsum_workspace_floats((int)(4 * Bn), (int)A));
-    cw = max64(cw, vqa_colsum_workspace_floats((int)(T * Bn), (int)(3 * H)));
-    cw = max64(cw, vqa_colsum_workspace_floats((int)Bn, (int)H));
-    L.add("colsum_ws", 3 * cw);
-    L.add("sumsq_ws", max64(vqa_sumsq_workspace_floats(2 * T * Bn * W), 4));
-    return L;
-}
 
 bool dims_ok(const vqa_pretrain_dims_t* d) {
     return d && d->B > 0 && d->n > 0 && d->n <= 8 && d->R > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->A > 0 &&
@@ -230,6 +138,8 @@ struct Ctx {
     float* f(const std::string& name) const { return reinterpret_cast<float*>(ws + L.find(name)->off); }
     int32_t* i32(const std::string& name) const { return reinterpret_cast<int32_t*>(ws + L.find(name)->off); }
     int64_t count(const std::string& name) const { return L.find(name)->n; }
+    // LayerNorm slot of call site `site` of an fc_layer scope: slot 0 for every site under VQA_FLAG_SHARED_LN
+    int li(int site) const { return (d.flags & VQA_FLAG_SHARED_LN) ? 0 : site; }
     int gemm(int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B, int ldb, float* C,
              int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) const {
         return vqa_gemm_f32(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, f("gemm_ws"),
@@ -238,7 +148,7 @@ struct Ctx {
 };
 
 // modules.fc_layer forward: FC on the last axis, layer_norm over groups of `rows` rows, activation (0 relu, 1 tanh)
-int fc_ln_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc_t& p, int ln, int rows,
+int fc_ln_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc6_t& p, int ln, int rows,
               int act, const std::string& pre, const std::string& y, const std::string& mean, const std::string& rstd,
               const uint8_t* keep, float keep_prob) {
     TRY(c.gemm(0, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
@@ -276,20 +186,11 @@ struct Acc {
     }
 };
 
-// backward of the LayerNorm / activation half of fc_ln_fwd: dy -> d_pre (named); gamma, beta and bias gradients accumulated
-int ln_bwd(const Ctx& c, Acc& acc, const float* dy, int64_t M, int64_t N, const vqa_pt_fc_t& p, const vqa_pt_fc_t& g, int ln,
-           int rows, int act, const std::string& pre, const std::string& mean, const std::string& rstd, const uint8_t* keep,
-           float keep_prob, const std::string& d_pre) {
-    const int64_t G = M / rows;
-    TRY(vqa_ln_act_bwd(dy, c.f(pre), c.f(mean), c.f(rstd), p.gamma[ln], p.beta[ln], keep, keep_prob, c.f(d_pre),
-                       c.f("part_a"), c.f("part_b"), c.f("part_c"), (int)G, rows, (int)N, act, c.st));
-    return acc.colsum3(c.f("part_a"), c.f("part_b"), c.f("part_c"), G, N, g.gamma[ln], g.beta[ln], g.b);
-}
-
-// the same on pointers (slices of the stacked head blocks)
-int ln_bwd_p(const Ctx& c, Acc& acc, const float* dy, int64_t M, int64_t N, const vqa_pt_fc_t& p, const vqa_pt_fc_t& g, int ln,
-             int rows, int act, const float* pre, const float* mean, const float* rstd, const uint8_t* keep, float keep_prob,
-             float* d_pre) {
+// backward of the LayerNorm / activation half of fc_ln_fwd on pointers (the stacked heads hand in their slices):
+// dy -> d_pre; gamma, beta and bias gradients accumulated
+int ln_bwd(const Ctx& c, Acc& acc, const float* dy, int64_t M, int64_t N, const vqa_pt_fc6_t& p, const vqa_pt_fc6_t& g, int ln,
+           int rows, int act, const float* pre, const float* mean, const float* rstd, const uint8_t* keep, float keep_prob,
+           float* d_pre) {
     const int64_t G = M / rows;
     TRY(vqa_ln_act_bwd(dy, pre, mean, rstd, p.gamma[ln], p.beta[ln], keep, keep_prob, d_pre, c.f("part_a"), c.f("part_b"),
                        c.f("part_c"), (int)G, rows, (int)N, act, c.st));
@@ -298,17 +199,17 @@ int ln_bwd_p(const Ctx& c, Acc& acc, const float* dy, int64_t M, int64_t N, cons
 
 // backward of the FC half: dW (+)= x^T d_pre, optional dx = d_pre * W^T
 int fc_bwd(const Ctx& c, Acc& acc, const std::string& d_pre, const float* x, int64_t M, int64_t K, int64_t N,
-           const vqa_pt_fc_t& p, const vqa_pt_fc_t& g, float* dx) {
+           const vqa_pt_fc6_t& p, const vqa_pt_fc6_t& g, float* dx) {
     TRY(acc.weight(g.w, x, (int)K, c.f(d_pre), (int)N, K, N, M));
     if (dx != nullptr) TRY(c.gemm(0, 1, M, K, N, c.f(d_pre), (int)N, p.w, (int)N, dx, (int)K));
     return VQA_OK;
 }
 
 // backward of fc_ln_fwd
-int fc_ln_bwd(const Ctx& c, Acc& acc, const float* dy, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc_t& p,
-              const vqa_pt_fc_t& g, int ln, int rows, int act, const std::string& pre, const std::string& mean,
+int fc_ln_bwd(const Ctx& c, Acc& acc, const float* dy, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc6_t& p,
+              const vqa_pt_fc6_t& g, int ln, int rows, int act, const std::string& pre, const std::string& mean,
               const std::string& rstd, const uint8_t* keep, float keep_prob, const std::string& d_pre, float* dx) {
-    TRY(ln_bwd(c, acc, dy, M, N, p, g, ln, rows, act, pre, mean, rstd, keep, keep_prob, d_pre));
+    TRY(ln_bwd(c, acc, dy, M, N, p, g, ln, rows, act, c.f(pre), c.f(mean), c.f(rstd), keep, keep_prob, c.f(d_pre)));
     return fc_bwd(c, acc, d_pre, x, M, K, N, p, g, dx);
 }
 
@@ -331,298 +232,6 @@ int gather_rows2(const void* in0, const void* in1, const int32_t* index, void* o
     return VQA_OK;
 }
 
-const char* const REPORT_KEYS[13] = {
-    "obj_blank_fill_loss", "obj_blank_fill_acc", "obj_blank_fill_top_5_acc", "obj_wordset_loss", "obj_wordset_acc",
-    "obj_wordset_top_5_acc", "attr_blank_fill_loss", "attr_blank_fill_acc", "attr_blank_fill_top_5_acc",
-    "attr_wordset_loss", "attr_wordset_acc", "attr_wordset_top_5_acc", "total_loss"};
-
-}  // namespace
-
-extern "C" const char* vqa_pretrain_report_key(int i) { return (i >= 0 && i < 13) ? REPORT_KEYS[i] : nullptr; }
-
-extern "C" int64_t vqa_pretrain_workspace_bytes(const vqa_pretrain_dims_t* dims) {
-    if (!dims_ok(dims)) return VQA_ERR_ARG;
-    return make_layout(*dims).total;
-}
-
-extern "C" int vqa_pretrain_tensor(const vqa_pretrain_dims_t* dims, const char* name, int64_t* offset_bytes,
-                                   int64_t* n_elems) {
-    if (!dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    const Layout L = make_layout(*dims);
-    const Entry* e = L.find(name);
-    if (e == nullptr) return VQA_ERR_ARG;
-    if (offset_bytes) *offset_bytes = e->off;
-    if (n_elems) *n_elems = e->n;
-    return VQA_OK;
-}
-
-extern "C" int vqa_pretrain_forward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
-                                    const vqa_pretrain_batch_t* bt, void* workspace, int64_t workspace_bytes,
-                                    int want_dz, void* stream) {
-    VQA_REQUIRE(dims_ok(dims) && P && bt && workspace, VQA_ERR_ARG);
-    const Layout L = make_layout(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    const Ctx c{*dims, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
-    const int64_t B = dims->B, n = dims->n, R = dims->R, D = dims->D, H = dims->H, W = dims->W, A = dims->A, T = dims->L;
-    const int64_t Bn = B * n;
-    const bool ln_shared = (dims->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
-    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
-    ReportArgs ra{};
-    ra.rows = (int)Bn;
-    ProbeScope ps_all("pretrain.forward", c.st);
-    // the x rows of the two GRU kernels side by side (vqa_gru_pack_wx): one projection GEMM per category
-    TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-    for (int k = 0; k < 2; ++k) {
-        const vqa_pretrain_kind_t& kb = bt->kind[k];
-        VQA_REQUIRE(kb.normal_boxes && kb.fills && kb.blanks && kb.blanks_len && kb.wordsets && kb.num, VQA_ERR_ARG);
-        const std::string p = std::string(KIND[k]) + "/";
-        // ---- build_*_V_ft: spatial attention over the regions
-        ProbeScope ps_sp("pt.spatial_wordset.fwd", c.st);
-        hipLaunchKernelGGL(box6_kernel, dim3((unsigned)((Bn + 255) / 256)), dim3(256), 0, c.st, kb.normal_boxes,
-                           c.f(p + "key6"), (int)Bn);
-        VQA_CHECK_LAUNCH();
-        TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, li(k), (int)R, 0, p + "v_pre", p + "v", p + "v_mean",
-                      p + "v_rstd", nullptr, 1.f));
-        TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, li(k), (int)n, 0, p + "qv_pre", p + "qv", p + "qv_mean",
-                      p + "qv_rstd", nullptr, 1.f));
-        TRY(vqa_attn_pool_fwd_rep(c.f(p + "v"), c.f(p + "qv"), bt->image_ft, bt->num_boxes, P->spat_att_score.w,
-                                  P->spat_att_score.b, kb.keep_att, dims->keep_att, c.f(p + "att"), c.f(p + "pooled"),
-                                  (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
-        hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
-                           (int)B, (int)n, dims->global_valid[k]);
-        VQA_CHECK_LAUNCH();
-
-        // ---- build_*_wordset
-        TRY(vqa_embed_fwd(P->wordset_map, kb.wordsets, c.f(p + "wse"), (int)Bn, 1, (int)W, dims->n_ws, c.st));
-        TRY(vqa_tanh_fwd(c.f(p + "wse"), c.f(p + "ws"), Bn * W, c.st));
-        TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, P->wordset_ft, li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
-                      p + "wf_rstd", nullptr, 1.f));
-    }
-    // ---- build_*_blank_fill of BOTH categories as one batch (shared L_GloVe / GRU weights): captions in length order
-    // when the host sorted them (live prefix recurrence); the final states go back to caption order as rows
-    // [0, Bn) = obj/bf_state and [Bn, 2 Bn) = attr/bf_state of the stacked "S/lft" block
-    {
-        const int64_t B2 = 2 * Bn;
-        ProbeScope ps_g("pt.caption_gru.fwd", c.st);
-        TRY(gather_rows2(bt->kind[0].blanks, bt->kind[1].blanks, bt->perm, c.i32("J/blanks_s"), B2, T, Bn, c.st));
-        TRY(gather_rows2(bt->kind[0].blanks_len, bt->kind[1].blanks_len, bt->perm, c.i32("J/lens_s"), B2, 1, Bn, c.st));
-        TRY(vqa_embed_fwd_ld(P->l_glove, c.i32("J/blanks_s"), c.f("J/x_tm"), (int)B2, (int)T, (int)W, dims->Vq,
-                             (int)x_stride(W), c.st));
-        float* xp = c.f("J/xp");
-        TRY(c.gemm(0, 0, T * B2, 3 * H, W, c.f("J/x_tm"), (int)x_stride(W), c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H),
-                   c.f("bx_cat")));
-        float* hs = c.f("J/hs");
-        if (hipMemsetAsync(hs, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-        const float* Wg_h = P->gru_wg + W * 2 * H;
-        const float* Wc_h = P->gru_wc + W * H;
-        if (bt->live_rows != nullptr)
-            TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, c.i32("J/lens_s"), bt->live_rows, hs, c.f("J/gru_r"), c.f("J/gru_u"),
-                                     c.f("J/gru_c"), c.f("J/gru_rh"), (int)T, (int)B2, (int)H, c.st));
-        else
-            TRY(vqa_gru_seq_fwd(xp, Wg_h, Wc_h, c.i32("J/lens_s"), hs, c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"),
-                                c.f("J/gru_rh"), (int)T, (int)B2, (int)H, c.st));
-        TRY(gather_rows(hs + T * B2 * H, bt->inv, c.f("S/lft"), B2, H, c.st));      // back to caption order
-    }
-    // ---- the four heads, stacked (ln = 2 t + k; see make_layout): every shared FC is one GEMM, LayerNorm (its own
-    // gamma / beta per head) and the loss run per slice
-    {
-        const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
-        auto hname = [&](int ln) { return std::string(KIND[ln & 1]) + "/" + HEAD[ln >> 1] + "/"; };
-        ProbeScope ps_h("pt.heads.fwd", c.st);
-        // pooled_linear_l: both heads of a category apply the SAME FC to the same pooled features, so the product is
-        // computed once per category (2 Bn rows)
-        TRY(c.gemm(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, P->pooled_linear_l.w, (int)H, c.f("S/vl_pre"), (int)H,
-                   P->pooled_linear_l.b));
-        TRY(c.gemm(0, 0, 4 * Bn, H, H, c.f("S/lft"), (int)H, P->q_linear_l.w, (int)H, c.f("S/ll_pre"), (int)H, P->q_linear_l.b));
-        for (int ln = 0; ln < 4; ++ln) {
-            const std::string q = hname(ln);
-            TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (ln & 1) * SH, P->pooled_linear_l.gamma[li(ln)], P->pooled_linear_l.beta[li(ln)],
-                               nullptr, 1.f, c.f("S/vl") + ln * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n,
-                               (int)H, 0, c.st));
-            TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + ln * SH, P->q_linear_l.gamma[li(ln)], P->q_linear_l.beta[li(ln)], nullptr, 1.f,
-                               c.f("S/ll") + ln * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
-        }
-        TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), 4 * SH, c.st));
-        TRY(c.gemm(0, 0, 4 * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
-                   P->joint_fc.b));
-        for (int ln = 0; ln < 4; ++ln) {
-            const std::string q = hname(ln);
-            const vqa_pretrain_kind_t& kb = bt->kind[ln & 1];
-            const uint8_t* jmask = (ln >> 1) == 0 ? kb.keep_bf_joint : kb.keep_ws_joint;
-            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + ln * SJ, P->joint_fc.gamma[li(ln)], P->joint_fc.beta[li(ln)], jmask, dims->keep_joint,
-                               c.f("S/j") + ln * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0,
-                               c.st));
-        }
-        TRY(c.gemm(0, 0, 4 * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
-                   P->classifier.b));
-        for (int ln = 0; ln < 4; ++ln) {
-            const int k = ln & 1, t = ln >> 1;
-            const std::string p = std::string(KIND[k]) + "/";
-            TRY(vqa_softmax_ce_fwd(c.f("S/z") + ln * SA, bt->kind[k].fills, c.f(p + "valid"), 5, c.f(p + "inv_valid"),
-                                   c.f("S/stats") + ln * Bn * 4, want_dz ? c.f("S/dz") + ln * SA : nullptr, (int)Bn, (int)A,
-                                   c.st));
-            ra.stats[2 * k + t] = c.f("S/stats") + ln * Bn * 4;
-            ra.inv[2 * k + t] = c.f(p + "inv_valid");
-        }
-    }
-    hipLaunchKernelGGL(pretrain_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
-    VQA_CHECK_LAUNCH();
-    return VQA_OK;
-}
-
-// Backward in dependency-ordered phases, so that a data-parallel caller can start reducing the gradients a phase
-// completed while the next phase runs (the cfg-5 counterpart of vqa_fusion_backward_phases):
-//   1  the four stacked heads: classifier, joint_fc, pooled_linear_l, q_linear_l (weights, biases, LayerNorms)
-//   2  back-propagation through time of the joint caption batch + the GRU kernels' and biases' gradients
-//   4  dx of the packed x-projection -> L_GloVe scatter-add (starts the running slice sum of squares)
-//   8  per category: wordset_ft / wordset_map, spatial attention, spat_v_linear_v / spat_q_linear_v (finishes slice_sq)
-// Each phase reads what the lower-numbered ones left in the workspace; a step runs them in this order.
-extern "C" int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
-                                            const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt,
-                                            void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                            void* stream) {
-    VQA_REQUIRE(dims_ok(dims) && P && G && bt && workspace, VQA_ERR_ARG);
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const Layout L = make_layout(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    const Ctx c{*dims, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
-    const int64_t B = dims->B, n = dims->n, R = dims->R, D = dims->D, H = dims->H, W = dims->W, A = dims->A, T = dims->L;
-    const int64_t Bn = B * n;
-    const bool ln_shared = (dims->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    ProbeScope ps_all("pretrain.backward", c.st);
-    Acc acc{c, {}};      // no gradient is touched by two different phases, so the first-touch record may be per call
-    // the two embedding tables are scatter-added: cleared in their phase; every other gradient is overwritten on first touch
-    const float* sq_prev = nullptr;
-    auto add_slice_sq = [&](const float* g, int64_t cnt) -> int {     // running sum of the un-aggregated slice norms
-        TRY(vqa_sumsq(g, cnt, sq_prev, c.f("sq"), c.f("sumsq_ws"), c.count("sumsq_ws"), c.st));
-        sq_prev = c.f("sq");
-        return VQA_OK;
-    };
-    // ---- the four heads, stacked (ln = 2 t + k): every shared FC's dW and dx is one GEMM over the 4 Bn rows
-    if (phases & 1) {
-        ProbeScope ps_h("pt.heads.bwd", c.st);
-        const int64_t SH = Bn * H, SJ = Bn * 2 * H;
-        auto hname = [&](int ln) { return std::string(KIND[ln & 1]) + "/" + HEAD[ln >> 1] + "/"; };
-        TRY(acc.weight(G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, 4 * Bn));
-        TRY(acc.colsum(c.f("S/dz"), 4 * Bn, A, (int)A, G->classifier.b));
-        TRY(c.gemm(0, 1, 4 * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
-        for (int ln = 0; ln < 4; ++ln) {
-            const std::string q = hname(ln);
-            const vqa_pretrain_kind_t& kb = bt->kind[ln & 1];
-            const uint8_t* jmask = (ln >> 1) == 0 ? kb.keep_bf_joint : kb.keep_ws_joint;
-            TRY(ln_bwd_p(c, acc, c.f("d_j") + ln * SJ, Bn, 2 * H, P->joint_fc, G->joint_fc, li(ln), (int)n, 0,
-                         c.f("S/j_pre") + ln * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), jmask, dims->keep_joint,
-                         c.f("d_jpre") + ln * SJ));
-        }
-        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), 4 * Bn, H, 2 * H, P->joint_fc, G->joint_fc, c.f("d_jin")));
-        TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), 4 * SH, c.st));
-        for (int ln = 0; ln < 4; ++ln) {
-            const std::string q = hname(ln);
-            TRY(ln_bwd_p(c, acc, c.f("d_vl") + ln * SH, Bn, H, P->pooled_linear_l, G->pooled_linear_l, li(ln), (int)n, 0,
-                         c.f("S/vl_pre") + (ln & 1) * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f,
-                         c.f("d_vlpre") + ln * SH));
-            TRY(ln_bwd_p(c, acc, c.f("d_ll") + ln * SH, Bn, H, P->q_linear_l, G->q_linear_l, li(ln), (int)n, 0,
-                         c.f("S/ll_pre") + ln * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f,
-                         c.f("d_llpre") + ln * SH));
-        }
-        // pooled_linear_l's product is shared by the two heads of a category: their d_pre (slices k and 2 + k) meet
-        // before ONE dW and ONE dx GEMM over the 2 Bn pooled rows
-        TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * SH, 2 * SH, c.st));
-        TRY(acc.weight(G->pooled_linear_l.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
-        TRY(c.gemm(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, P->pooled_linear_l.w, (int)H, c.f("d_pooled"), (int)D));
-        TRY(fc_bwd(c, acc, "d_llpre", c.f("S/lft"), 4 * Bn, H, H, P->q_linear_l, G->q_linear_l, c.f("d_lft")));
-    }
-    // ---- blank fill -> GRU -> L_GloVe, both categories as the one batch of the forward
-    const int64_t B2 = 2 * Bn;
-    float* dxp = c.f("dxp");
-    const int ld3 = (int)(3 * H);
-    if (phases & 2) {
-        ProbeScope ps_g("pt.caption_gru.bwd", c.st);
-        TRY(gather_rows(c.f("d_lft"), bt->perm, c.f("d_state_s"), B2, H, c.st));   // rows [0, 2 Bn) of d_lft, into the sorted order
-        const float* Wg_h = P->gru_wg + W * 2 * H;
-        const float* Wc_h = P->gru_wc + W * H;
-        const float* hs = c.f("J/hs");
-        if (bt->live_rows != nullptr)
-            TRY(vqa_gru_seq_bwd_live(c.f("d_state_s"), Wg_h, Wc_h, c.i32("J/lens_s"), bt->live_rows, hs, c.f("J/gru_r"),
-                                     c.f("J/gru_u"), c.f("J/gru_c"), dxp, c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
-        else
-            TRY(vqa_gru_seq_bwd(c.f("d_state_s"), Wg_h, Wc_h, c.i32("J/lens_s"), hs, c.f("J/gru_r"), c.f("J/gru_u"),
-                                c.f("J/gru_c"), dxp, c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
-        // x rows of both kernels' gradients as one GEMM into the packed [Wp, 3H] block; x_tm carries the constant 1 in
-        // column W, so row W of the block is the two bias gradients and dxp is not read again for them.  The h rows
-        // as before
-        const int64_t Wp = x_stride(W);
-        TRY(acc.weight(c.f("dwx_cat"), c.f("J/x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
-        TRY(acc.weight(G->gru_wg + W * 2 * H, hs, (int)H, dxp, ld3, H, 2 * H, T * B2));
-        TRY(acc.weight(G->gru_wc + W * H, c.f("J/gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
-        TRY(vqa_gru_unpack_dwx_bias(c.f("dwx_cat"), G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc, (int)W, (int)H, c.st));
-    }
-    if (phases & 4) {
-        ProbeScope ps_e("pt.caption_embed.bwd", c.st);
-        if (hipMemsetAsync(G->l_glove, 0, (size_t)dims->Vq * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-        float* dx = c.f("dx");
-        // packed again here (one small kernel): no hidden dependence on the forward's copy of the weights
-        TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-        TRY(c.gemm(0, 1, T * B2, W, 3 * H, dxp, ld3, c.f("wx_cat"), (int)(3 * H), dx, (int)W));
-        TRY(vqa_embed_bwd_len_det(dx, c.i32("J/blanks_s"), c.i32("J/lens_s"), G->l_glove, (int)B2, (int)T, (int)W,
-                                  dims->Vq, (dims->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
-        TRY(add_slice_sq(dx, T * B2 * W));
-    }
-    if (phases & 8) {
-        if (hipMemsetAsync(G->wordset_map, 0, (size_t)dims->n_ws * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-        if (!(phases & 4)) sq_prev = c.f("sq");      // phase 4 of this step left the captions' slice sum of squares there
-    }
-    for (int k = 0; k < 2 && (phases & 8); ++k) {
-        ProbeScope ps_sp("pt.spatial_wordset.bwd", c.st);
-        const vqa_pretrain_kind_t& kb = bt->kind[k];
-        const std::string p = std::string(KIND[k]) + "/";
-        const float* d_pooled = c.f("d_pooled") + k * Bn * D;
-        // ---- word set -> wordset_ft -> tanh -> wordset_map
-        TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 + k) * Bn * H, c.f(p + "ws"), Bn, W, H, P->wordset_ft, G->wordset_ft, li(k), (int)n, 1, p + "wf_pre",
-                      p + "wf_mean", p + "wf_rstd", nullptr, 1.f, "d_wfpre", c.f("d_ws")));
-        TRY(vqa_tanh_bwd(c.f("d_ws"), c.f(p + "ws"), c.f("d_wse"), Bn * W, c.st));
-        TRY(vqa_embed_bwd_len_det(c.f("d_wse"), kb.wordsets, nullptr, G->wordset_map, (int)Bn, 1, (int)W, dims->n_ws,
-                                  (dims->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
-        TRY(add_slice_sq(c.f("d_wse"), Bn * W));
-        // ---- spatial attention
-        TRY(vqa_attn_pool_bwd_rep(d_pooled, c.f(p + "v"), c.f(p + "qv"), bt->image_ft, c.f(p + "att"),
-                                  P->spat_att_score.w, kb.keep_att, dims->keep_att, c.f("d_v"), c.f("d_qv"),
-                                  c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
-        TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G->spat_att_score.w));
-        TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G->spat_att_score.b));
-        TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, G->spat_v_linear_v, li(k), (int)R, 0,
-                      p + "v_pre", p + "v_mean", p + "v_rstd", nullptr, 1.f, "d_vpre", nullptr));
-        TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, G->spat_q_linear_v, li(k), (int)n, 0,
-                      p + "qv_pre", p + "qv_mean", p + "qv_rstd", nullptr, 1.f, "d_qvpre", nullptr));
-    }
-    if ((phases & 8) && slice_sq != nullptr && sq_prev != nullptr)
-        if (hipMemcpyAsync(slice_sq, sq_prev, sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
-            return VQA_ERR_LAUNCH;
-    return VQA_OK;
-}
-
-extern "C" int vqa_pretrain_backward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
-                                     const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt, void* workspace,
-                                     int64_t workspace_bytes, float* slice_sq, void* stream) {
-    return vqa_pretrain_backward_phases(dims, P, G, bt, workspace, workspace_bytes, slice_sq, 15, stream);
-}
-
-// ================================================================ pre-training with a variable head set
-// vlmap_memft/model_vlmap_bf_or_wordset_enwiki_withatt_sp.py (heads bf | ws | ew) and model_vlmap_bf_enwiki_withatt_sp.py
-// (bf | ew): the cfg-5 model above plus, per category, build_*_enwiki (:519-624) -- enwiki_map embedding of the answer's
-// Wikipedia context -> a second GRU (encode_L_enwiki, shared by both categories) -> the same shared fusion MLP and
-// classifier -> masked softmax-CE over the blank-fill fills.  Head h = 2 r + k for the type of rank r among the enabled
-// ones and category k, so its LayerNorm slot (without VQA_FLAG_SHARED_LN) is TF's build order; the stacked blocks hold
-// the 2 * (#types) heads.  The cfg-5 entry points above are untouched; this path reuses their helpers and kernels.
-namespace {
-
-const char* const HEAD_EXT[3] = {"bf", "ws", "ew"};
-const char* const TASK_EXT[3] = {"blank_fill", "wordset", "enwiki"};
-
 struct HeadSet {
     int type[3] = {0, 0, 0};      // type of rank r (0 blank fill, 1 word set, 2 enwiki)
     int rank[3] = {-1, -1, -1};   // rank of type t, -1 = not enabled
@@ -632,6 +241,8 @@ struct HeadSet {
             if (mask & (1 << t)) { rank[t] = nt; type[nt++] = t; }
     }
     int nh() const { return 2 * nt; }
+    // workspace prefix of head h = 2 r + k: "<obj|attr>/<bf|ws|ew>/"
+    std::string name(int h) const { return std::string(KIND[h & 1]) + "/" + HEAD[type[h >> 1]] + "/"; }
 };
 
 bool ext_dims_ok(const vqa_pretrain_ext_dims_t* d) {
@@ -703,7 +314,7 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool
         }
         if (hs.rank[2] >= 0) L.alias(p + "ew_state", "S/lft", (2 * hs.rank[2] + k) * Bn * H, Bn * H);
         for (int r = 0; r < hs.nt; ++r) {
-            const std::string q = p + HEAD_EXT[hs.type[r]] + "/";
+            const std::string q = p + HEAD[hs.type[r]] + "/";
             const int64_t h = 2 * r + k;
             L.alias(q + "vl", "S/vl", h * Bn * H, Bn * H); L.add(q + "vl_mean", B); L.add(q + "vl_rstd", B);
             L.alias(q + "ll_pre", "S/ll_pre", h * Bn * H, Bn * H); L.alias(q + "ll", "S/ll", h * Bn * H, Bn * H);
@@ -804,19 +415,13 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool
     return L;
 }
 
-// the first four LayerNorm slots of a 6-slot scope (scopes entered by at most 4 call sites)
-vqa_pt_fc_t fc4(const vqa_pt_fc6_t& f) {
-    vqa_pt_fc_t o{};
-    o.w = f.w; o.b = f.b;
-    for (int i = 0; i < 4; ++i) { o.beta[i] = f.beta[i]; o.gamma[i] = f.gamma[i]; }
-    return o;
-}
-
-// LayerNorm slot s of a 6-slot scope as slot 0 of a vqa_pt_fc_t (the stacked heads' per-slice LayerNorm)
-vqa_pt_fc_t fc_slot(const vqa_pt_fc6_t& f, int s) {
-    vqa_pt_fc_t o{};
-    o.w = f.w; o.b = f.b; o.beta[0] = f.beta[s]; o.gamma[0] = f.gamma[s];
-    return o;
+// vqa_pretrain_*_tensor of every model: a name of the layout -> byte offset and element count
+int layout_tensor(const Layout& L, const char* name, int64_t* offset_bytes, int64_t* n_elems) {
+    const Entry* e = L.find(name);
+    if (e == nullptr) return VQA_ERR_ARG;
+    if (offset_bytes) *offset_bytes = e->off;
+    if (n_elems) *n_elems = e->n;
+    return VQA_OK;
 }
 
 std::string ext_report_key(int heads, int i) {
@@ -825,212 +430,243 @@ std::string ext_report_key(int heads, int i) {
     if (i < 0 || i > 3 * hs.nh()) return "";
     const int h = i / 3, j = i % 3, k = h / hs.nt, r = h % hs.nt;
     static const char* const SUFFIX[3] = {"_loss", "_acc", "_top_5_acc"};
-    return std::string(KIND[k]) + "_" + TASK_EXT[hs.type[r]] + SUFFIX[j];
+    return std::string(KIND[k]) + "_" + TASK[hs.type[r]] + SUFFIX[j];
 }
 
 // the memory the spatial attention pools when it is not the batch's image_ft [B,R,D]: one [B,R,width] block per category
 struct PoolMem { const float* mem[2]; int64_t width; };
 
-// The trunk of the variable-head-set models, shared by vqa_pretrain_ext_forward and vqa_pretrain_noc_forward: spatial
-// attention and pooling, word sets, the caption batch and the context batch, up to the stacked "S/pooled" and "S/lft"
-// blocks the heads read
+// joint_fc dropout mask of the head of type t, category k
+const uint8_t* joint_keep(const vqa_pretrain_ext_batch_t& x, int k, int t) {
+    return t == 0 ? x.base.kind[k].keep_bf_joint : t == 1 ? x.base.kind[k].keep_ws_joint : x.ctx[k].keep_ew_joint;
+}
+
+// what the trunk dereferences, checked before the first launch
+int trunk_inputs_ok(const HeadSet& hs, const vqa_pretrain_ext_params_t* P, const vqa_pretrain_ext_batch_t* bx) {
+    const vqa_pretrain_batch_t* bt = &bx->base;
+    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
+    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
+                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
+    for (const vqa_pretrain_kind_t& kb : bt->kind)
+        VQA_REQUIRE(kb.normal_boxes && kb.fills && kb.blanks && kb.blanks_len && kb.num && (hs.rank[1] < 0 || kb.wordsets),
+                    VQA_ERR_ARG);
+    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
+    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
+    if (hs.rank[2] >= 0)
+        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
+                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------- the sequence encoder
+// A token batch of BOTH categories as one batch of 2 Bn rows (object rows first), time-major: embedding -> GRU -> final
+// states into two Bn-row head slices of "S/lft".  The embedding and the GRU are shared by the categories, so one
+// recurrence over 5120 rows replaces two over 2560 (half the step launches, tiles that fill the chip).  Rows in length
+// order when the host sorted them (perm / inv / live_rows: the recurrence runs on the live prefix).  Two users: the
+// blank-fill captions (L_GloVe, encode_L_blank, "J/...") and the enwiki contexts (enwiki_map, encode_L_enwiki, "E/...").
+struct GruVars { float *wg, *bg, *wc, *bc; };      // gates / candidate kernel [W + H, 2H] / [W + H, H] and bias
+struct Seq {
+    // workspace names: in + {tok, "lens_s", "x_tm", "xp", "hs", "gru_r", "gru_u", "gru_c", "gru_rh"} hold the sorted
+    // batch and the forward tape, scr + {"wx_cat", "bx_cat", "dwx_cat", "d_state_s", "dxp", "dx"} the packed x rows
+    // and the backward scratch
+    std::string in, tok, scr;
+    const char *fwd_label, *bptt_label, *embed_label;      // probe scopes
+    const int32_t *tokens[2], *len[2];                     // per category: tokens [Bn,T] zero padded, lengths [Bn]
+    const int32_t *perm, *inv, *live_rows;
+    float *table, *g_table;                                // embedding table [vocab,W] and its gradient
+    int vocab;
+    GruVars P, G;                                          // the recurrence's variables and their gradients
+    int64_t T, head;                                       // padded length; "S/lft" / "d_lft" slices head, head + 1
+};
+struct SeqSet { Seq s[2]; int n; };
+
+// the token batches of the head set: the captions, then the contexts when the enwiki head is on (G NULL in the forward:
+// the gradient members stay NULL)
+SeqSet make_seqs(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P, const vqa_pretrain_ext_params_t* G,
+                 const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs) {
+    const vqa_pretrain_batch_t& bt = bx->base;
+    SeqSet q{};
+    Seq& j = q.s[0];
+    j.in = "J/"; j.tok = "blanks_s"; j.scr = "";
+    j.fwd_label = "pt.caption_gru.fwd"; j.bptt_label = "pt.caption_gru.bwd"; j.embed_label = "pt.caption_embed.bwd";
+    for (int k = 0; k < 2; ++k) { j.tokens[k] = bt.kind[k].blanks; j.len[k] = bt.kind[k].blanks_len; }
+    j.perm = bt.perm; j.inv = bt.inv; j.live_rows = bt.live_rows;
+    j.table = P->l_glove; j.vocab = dims->base.Vq; j.T = dims->base.L; j.head = 0;
+    j.P = {P->gru_wg, P->gru_bg, P->gru_wc, P->gru_bc};
+    if (G != nullptr) { j.g_table = G->l_glove; j.G = {G->gru_wg, G->gru_bg, G->gru_wc, G->gru_bc}; }
+    q.n = 1;
+    if (hs.rank[2] < 0) return q;
+    Seq& e = q.s[1];
+    e.in = "E/"; e.tok = "ctx_s"; e.scr = "E/";
+    e.fwd_label = "pt.enwiki_gru.fwd"; e.bptt_label = "pt.enwiki_gru.bwd"; e.embed_label = "pt.enwiki_embed.bwd";
+    for (int k = 0; k < 2; ++k) { e.tokens[k] = bx->ctx[k].context; e.len[k] = bx->ctx[k].context_len; }
+    e.perm = bx->ctx_perm; e.inv = bx->ctx_inv; e.live_rows = bx->ctx_live_rows;
+    e.table = P->enwiki_map; e.vocab = dims->n_ctx; e.T = dims->Lc; e.head = 2 * hs.rank[2];
+    e.P = {P->egru_wg, P->egru_bg, P->egru_wc, P->egru_bc};
+    if (G != nullptr) { e.g_table = G->enwiki_map; e.G = {G->egru_wg, G->egru_bg, G->egru_wc, G->egru_bc}; }
+    q.n = 2;
+    return q;
+}
+
+// the x rows of the two GRU kernels side by side: one projection GEMM for all steps
+int seq_pack_wx(const Ctx& c, const Seq& s) {
+    return vqa_gru_pack_wx(s.P.wg, s.P.wc, s.P.bg, s.P.bc, c.f(s.scr + "wx_cat"), c.f(s.scr + "bx_cat"), (int)c.d.W, (int)c.d.H,
+                           c.st);
+}
+
+// pack_wx false: the caller has packed the x rows already (the caption batch: the step's first launch)
+int seq_fwd(const Ctx& c, const Seq& s, bool pack_wx) {
+    const int64_t H = c.d.H, W = c.d.W, Bn = (int64_t)c.d.B * c.d.n, B2 = 2 * Bn, T = s.T;
+    ProbeScope ps(s.fwd_label, c.st);
+    if (pack_wx) TRY(seq_pack_wx(c, s));
+    int32_t *tok = c.i32(s.in + s.tok), *lens = c.i32(s.in + "lens_s");
+    float *x_tm = c.f(s.in + "x_tm"), *xp = c.f(s.in + "xp"), *hs = c.f(s.in + "hs");
+    float *r = c.f(s.in + "gru_r"), *u = c.f(s.in + "gru_u"), *cc = c.f(s.in + "gru_c"), *rh = c.f(s.in + "gru_rh");
+    TRY(gather_rows2(s.tokens[0], s.tokens[1], s.perm, tok, B2, T, Bn, c.st));
+    TRY(gather_rows2(s.len[0], s.len[1], s.perm, lens, B2, 1, Bn, c.st));
+    TRY(vqa_embed_fwd_ld(s.table, tok, x_tm, (int)B2, (int)T, (int)W, s.vocab, (int)x_stride(W), c.st));
+    TRY(c.gemm(0, 0, T * B2, 3 * H, W, x_tm, (int)x_stride(W), c.f(s.scr + "wx_cat"), (int)(3 * H), xp, (int)(3 * H),
+               c.f(s.scr + "bx_cat")));
+    if (hipMemsetAsync(hs, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+    const float *Wg_h = s.P.wg + W * 2 * H, *Wc_h = s.P.wc + W * H;
+    if (s.live_rows != nullptr)
+        TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, lens, s.live_rows, hs, r, u, cc, rh, (int)T, (int)B2, (int)H, c.st));
+    else
+        TRY(vqa_gru_seq_fwd(xp, Wg_h, Wc_h, lens, hs, r, u, cc, rh, (int)T, (int)B2, (int)H, c.st));
+    return gather_rows(hs + T * B2 * H, s.inv, c.f("S/lft") + s.head * Bn * H, B2, H, c.st);      // back to the given order
+}
+
+// phase 2: back-propagation through time from the two "d_lft" slices, the GRU kernels' and biases' gradients
+int seq_bptt(const Ctx& c, Acc& acc, const Seq& s) {
+    const int64_t H = c.d.H, W = c.d.W, Bn = (int64_t)c.d.B * c.d.n, B2 = 2 * Bn, T = s.T, Wp = x_stride(W);
+    const int ld3 = (int)(3 * H);
+    ProbeScope ps(s.bptt_label, c.st);
+    const int32_t* lens = c.i32(s.in + "lens_s");
+    const float *hs = c.f(s.in + "hs"), *r = c.f(s.in + "gru_r"), *u = c.f(s.in + "gru_u"), *cc = c.f(s.in + "gru_c");
+    float *d_state = c.f(s.scr + "d_state_s"), *dxp = c.f(s.scr + "dxp"), *dwx = c.f(s.scr + "dwx_cat");
+    TRY(gather_rows(c.f("d_lft") + s.head * Bn * H, s.perm, d_state, B2, H, c.st));      // into the sorted order
+    const float *Wg_h = s.P.wg + W * 2 * H, *Wc_h = s.P.wc + W * H;
+    if (s.live_rows != nullptr)
+        TRY(vqa_gru_seq_bwd_live(d_state, Wg_h, Wc_h, lens, s.live_rows, hs, r, u, cc, dxp, c.f("d_hscratch"), (int)T,
+                                 (int)B2, (int)H, c.st));
+    else
+        TRY(vqa_gru_seq_bwd(d_state, Wg_h, Wc_h, lens, hs, r, u, cc, dxp, c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
+    // x rows of both kernels' gradients as one GEMM into the packed [Wp, 3H] block; x_tm carries the constant 1 in
+    // column W, so row W of the block is the two bias gradients and dxp is not read again for them
+    TRY(acc.weight(dwx, c.f(s.in + "x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
+    TRY(acc.weight(s.G.wg + W * 2 * H, hs, (int)H, dxp, ld3, H, 2 * H, T * B2));
+    TRY(acc.weight(s.G.wc + W * H, c.f(s.in + "gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
+    return vqa_gru_unpack_dwx_bias(dwx, s.G.wg, s.G.wc, s.G.bg, s.G.bc, (int)W, (int)H, c.st);
+}
+
+// running sum of squares of the un-aggregated embedding slices
+struct SliceSq {
+    const Ctx& c;
+    const float* prev;
+    int add(const float* g, int64_t cnt) {
+        TRY(vqa_sumsq(g, cnt, prev, c.f("sq"), c.f("sumsq_ws"), c.count("sumsq_ws"), c.st));
+        prev = c.f("sq");
+        return VQA_OK;
+    }
+};
+
+// phase 4: dx of the packed x-projection -> scatter-add into the (cleared) embedding gradient, slice sum of squares
+int seq_embed_bwd(const Ctx& c, const Seq& s, SliceSq& sq) {
+    const int64_t H = c.d.H, W = c.d.W, B2 = 2 * (int64_t)c.d.B * c.d.n, T = s.T;
+    ProbeScope ps(s.embed_label, c.st);
+    if (hipMemsetAsync(s.g_table, 0, (size_t)s.vocab * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+    float* dx = c.f(s.scr + "dx");
+    // packed again here (one small kernel): no hidden dependence on the forward's copy of the weights
+    TRY(seq_pack_wx(c, s));
+    TRY(c.gemm(0, 1, T * B2, W, 3 * H, c.f(s.scr + "dxp"), (int)(3 * H), c.f(s.scr + "wx_cat"), (int)(3 * H), dx, (int)W));
+    TRY(vqa_embed_bwd_len_det(dx, c.i32(s.in + s.tok), c.i32(s.in + "lens_s"), s.g_table, (int)B2, (int)T, (int)W, s.vocab,
+                              (c.d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
+    return sq.add(dx, T * B2 * W);
+}
+
+// The trunk of every model of this file: spatial attention and pooling, word sets, the caption batch and the context
+// batch, up to the stacked "S/pooled" and "S/lft" blocks the heads read
 int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                   const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs, const PoolMem* pm = nullptr) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
-    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
-    const int64_t B2 = 2 * Bn;
-    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    const vqa_pt_fc_t spat_v = fc4(P->spat_v_linear_v), spat_q = fc4(P->spat_q_linear_v), wft = fc4(P->wordset_ft);
-    TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
+    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, Bn = B * n;
+    const SeqSet q = make_seqs(dims, P, nullptr, bx, hs);
+    TRY(seq_pack_wx(c, q.s[0]));
     for (int k = 0; k < 2; ++k) {
         const vqa_pretrain_kind_t& kb = bt->kind[k];
-        VQA_REQUIRE(kb.normal_boxes && kb.fills && kb.blanks && kb.blanks_len && kb.num, VQA_ERR_ARG);
         const std::string p = std::string(KIND[k]) + "/";
+        // ---- build_*_V_ft: spatial attention over the regions
         ProbeScope ps_sp("pt.spatial_wordset.fwd", c.st);
         hipLaunchKernelGGL(box6_kernel, dim3((unsigned)((Bn + 255) / 256)), dim3(256), 0, c.st, kb.normal_boxes,
                            c.f(p + "key6"), (int)Bn);
         VQA_CHECK_LAUNCH();
-        TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, spat_v, li(k), (int)R, 0, p + "v_pre", p + "v", p + "v_mean",
-                      p + "v_rstd", nullptr, 1.f));
-        TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, spat_q, li(k), (int)n, 0, p + "qv_pre", p + "qv", p + "qv_mean",
-                      p + "qv_rstd", nullptr, 1.f));
+        TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, c.li(k), (int)R, 0, p + "v_pre", p + "v",
+                      p + "v_mean", p + "v_rstd", nullptr, 1.f));
+        TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, c.li(k), (int)n, 0, p + "qv_pre", p + "qv",
+                      p + "qv_mean", p + "qv_rstd", nullptr, 1.f));
         TRY(vqa_attn_pool_fwd_rep(c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, bt->num_boxes,
                                   P->spat_att_score.w, P->spat_att_score.b, kb.keep_att, d->keep_att, c.f(p + "att"),
                                   c.f(p + "pooled"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
                            (int)B, (int)n, d->global_valid[k]);
         VQA_CHECK_LAUNCH();
-        if (hs.rank[1] >= 0) {
-            VQA_REQUIRE(kb.wordsets, VQA_ERR_ARG);
+        if (hs.rank[1] >= 0) {      // ---- build_*_wordset
             TRY(vqa_embed_fwd(P->wordset_map, kb.wordsets, c.f(p + "wse"), (int)Bn, 1, (int)W, d->n_ws, c.st));
             TRY(vqa_tanh_fwd(c.f(p + "wse"), c.f(p + "ws"), Bn * W, c.st));
-            TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, wft, li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
+            TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, P->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
                           p + "wf_rstd", nullptr, 1.f));
         }
     }
-    {   // captions of both categories: one batch, final states -> heads 0 / 1 of "S/lft"
-        ProbeScope ps_g("pt.caption_gru.fwd", c.st);
-        TRY(gather_rows2(bt->kind[0].blanks, bt->kind[1].blanks, bt->perm, c.i32("J/blanks_s"), B2, T, Bn, c.st));
-        TRY(gather_rows2(bt->kind[0].blanks_len, bt->kind[1].blanks_len, bt->perm, c.i32("J/lens_s"), B2, 1, Bn, c.st));
-        TRY(vqa_embed_fwd_ld(P->l_glove, c.i32("J/blanks_s"), c.f("J/x_tm"), (int)B2, (int)T, (int)W, d->Vq,
-                             (int)x_stride(W), c.st));
-        float* xp = c.f("J/xp");
-        TRY(c.gemm(0, 0, T * B2, 3 * H, W, c.f("J/x_tm"), (int)x_stride(W), c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H),
-                   c.f("bx_cat")));
-        float* hsb = c.f("J/hs");
-        if (hipMemsetAsync(hsb, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-        if (bt->live_rows != nullptr)
-            TRY(vqa_gru_seq_fwd_live(xp, P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"), bt->live_rows, hsb,
-                                     c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"), c.f("J/gru_rh"), (int)T, (int)B2,
-                                     (int)H, c.st));
-        else
-            TRY(vqa_gru_seq_fwd(xp, P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"), hsb, c.f("J/gru_r"),
-                                c.f("J/gru_u"), c.f("J/gru_c"), c.f("J/gru_rh"), (int)T, (int)B2, (int)H, c.st));
-        TRY(gather_rows(hsb + T * B2 * H, bt->inv, c.f("S/lft"), B2, H, c.st));
-    }
-    if (hs.rank[2] >= 0) {   // enwiki contexts of both categories: one batch through encode_L_enwiki -> heads 2 r_ew + k
-        ProbeScope ps_e("pt.enwiki_gru.fwd", c.st);
-        const int64_t Tc = dims->Lc;
-        TRY(vqa_gru_pack_wx(P->egru_wg, P->egru_wc, P->egru_bg, P->egru_bc, c.f("E/wx_cat"), c.f("E/bx_cat"), (int)W,
-                            (int)H, c.st));
-        TRY(gather_rows2(bx->ctx[0].context, bx->ctx[1].context, bx->ctx_perm, c.i32("E/ctx_s"), B2, Tc, Bn, c.st));
-        TRY(gather_rows2(bx->ctx[0].context_len, bx->ctx[1].context_len, bx->ctx_perm, c.i32("E/lens_s"), B2, 1, Bn, c.st));
-        TRY(vqa_embed_fwd_ld(P->enwiki_map, c.i32("E/ctx_s"), c.f("E/x_tm"), (int)B2, (int)Tc, (int)W, dims->n_ctx,
-                             (int)x_stride(W), c.st));
-        float* xp = c.f("E/xp");
-        TRY(c.gemm(0, 0, Tc * B2, 3 * H, W, c.f("E/x_tm"), (int)x_stride(W), c.f("E/wx_cat"), (int)(3 * H), xp,
-                   (int)(3 * H), c.f("E/bx_cat")));
-        float* hse = c.f("E/hs");
-        if (hipMemsetAsync(hse, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-        if (bx->ctx_live_rows != nullptr)
-            TRY(vqa_gru_seq_fwd_live(xp, P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"), bx->ctx_live_rows,
-                                     hse, c.f("E/gru_r"), c.f("E/gru_u"), c.f("E/gru_c"), c.f("E/gru_rh"), (int)Tc,
-                                     (int)B2, (int)H, c.st));
-        else
-            TRY(vqa_gru_seq_fwd(xp, P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"), hse, c.f("E/gru_r"),
-                                c.f("E/gru_u"), c.f("E/gru_c"), c.f("E/gru_rh"), (int)Tc, (int)B2, (int)H, c.st));
-        TRY(gather_rows(hse + Tc * B2 * H, bx->ctx_inv, c.f("S/lft") + 2 * hs.rank[2] * Bn * H, B2, H, c.st));
-    }
+    // ---- build_*_blank_fill -> heads 0 / 1 of "S/lft", build_*_enwiki -> heads 2 r_ew + k
+    for (int i = 0; i < q.n; ++i) TRY(seq_fwd(c, q.s[i], i > 0));
     return VQA_OK;
 }
 
-// Phases 2, 4 and 8 of the variable-head-set backward (everything below the heads), shared by
-// vqa_pretrain_ext_backward_phases and vqa_pretrain_noc_backward_phases
+// Phases 2, 4 and 8 of the backward (everything below the heads)
 int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                   const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs,
                   float* slice_sq, int phases, const PoolMem* pm = nullptr) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
-    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, T = d->L, Bn = B * n;
-    const int64_t B2 = 2 * Bn;
-    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
+    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, Bn = B * n;
     const int det = (d->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    const float* sq_prev = nullptr;
-    auto add_slice_sq = [&](const float* g, int64_t cnt) -> int {
-        TRY(vqa_sumsq(g, cnt, sq_prev, c.f("sq"), c.f("sumsq_ws"), c.count("sumsq_ws"), c.st));
-        sq_prev = c.f("sq");
-        return VQA_OK;
-    };
-    const int ld3 = (int)(3 * H);
-    const int64_t Wp = x_stride(W);
-    if (phases & 2) {
-        {
-            ProbeScope ps_g("pt.caption_gru.bwd", c.st);
-            float* dxp = c.f("dxp");
-            TRY(gather_rows(c.f("d_lft"), bt->perm, c.f("d_state_s"), B2, H, c.st));
-            const float* hsb = c.f("J/hs");
-            if (bt->live_rows != nullptr)
-                TRY(vqa_gru_seq_bwd_live(c.f("d_state_s"), P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"),
-                                         bt->live_rows, hsb, c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"), dxp,
-                                         c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
-            else
-                TRY(vqa_gru_seq_bwd(c.f("d_state_s"), P->gru_wg + W * 2 * H, P->gru_wc + W * H, c.i32("J/lens_s"), hsb,
-                                    c.f("J/gru_r"), c.f("J/gru_u"), c.f("J/gru_c"), dxp, c.f("d_hscratch"), (int)T, (int)B2,
-                                    (int)H, c.st));
-            TRY(acc.weight(c.f("dwx_cat"), c.f("J/x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
-            TRY(acc.weight(G->gru_wg + W * 2 * H, hsb, (int)H, dxp, ld3, H, 2 * H, T * B2));
-            TRY(acc.weight(G->gru_wc + W * H, c.f("J/gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
-            TRY(vqa_gru_unpack_dwx_bias(c.f("dwx_cat"), G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc, (int)W, (int)H, c.st));
-        }
-        if (hs.rank[2] >= 0) {
-            ProbeScope ps_e("pt.enwiki_gru.bwd", c.st);
-            const int64_t Tc = dims->Lc;
-            float* dxp = c.f("E/dxp");
-            TRY(gather_rows(c.f("d_lft") + 2 * hs.rank[2] * Bn * H, bx->ctx_perm, c.f("E/d_state_s"), B2, H, c.st));
-            const float* hse = c.f("E/hs");
-            if (bx->ctx_live_rows != nullptr)
-                TRY(vqa_gru_seq_bwd_live(c.f("E/d_state_s"), P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"),
-                                         bx->ctx_live_rows, hse, c.f("E/gru_r"), c.f("E/gru_u"), c.f("E/gru_c"), dxp,
-                                         c.f("d_hscratch"), (int)Tc, (int)B2, (int)H, c.st));
-            else
-                TRY(vqa_gru_seq_bwd(c.f("E/d_state_s"), P->egru_wg + W * 2 * H, P->egru_wc + W * H, c.i32("E/lens_s"), hse,
-                                    c.f("E/gru_r"), c.f("E/gru_u"), c.f("E/gru_c"), dxp, c.f("d_hscratch"), (int)Tc,
-                                    (int)B2, (int)H, c.st));
-            TRY(acc.weight(c.f("E/dwx_cat"), c.f("E/x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, Tc * B2));
-            TRY(acc.weight(G->egru_wg + W * 2 * H, hse, (int)H, dxp, ld3, H, 2 * H, Tc * B2));
-            TRY(acc.weight(G->egru_wc + W * H, c.f("E/gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, Tc * B2));
-            TRY(vqa_gru_unpack_dwx_bias(c.f("E/dwx_cat"), G->egru_wg, G->egru_wc, G->egru_bg, G->egru_bc, (int)W, (int)H,
-                                        c.st));
-        }
-    }
-    if (phases & 4) {
-        {
-            ProbeScope ps_c("pt.caption_embed.bwd", c.st);
-            if (hipMemsetAsync(G->l_glove, 0, (size_t)d->Vq * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-            float* dx = c.f("dx");
-            TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-            TRY(c.gemm(0, 1, T * B2, W, 3 * H, c.f("dxp"), ld3, c.f("wx_cat"), (int)(3 * H), dx, (int)W));
-            TRY(vqa_embed_bwd_len_det(dx, c.i32("J/blanks_s"), c.i32("J/lens_s"), G->l_glove, (int)B2, (int)T, (int)W,
-                                      d->Vq, det, c.st));
-            TRY(add_slice_sq(dx, T * B2 * W));
-        }
-        if (hs.rank[2] >= 0) {
-            ProbeScope ps_e("pt.enwiki_embed.bwd", c.st);
-            const int64_t Tc = dims->Lc;
-            if (hipMemsetAsync(G->enwiki_map, 0, (size_t)dims->n_ctx * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-            float* dx = c.f("E/dx");
-            TRY(vqa_gru_pack_wx(P->egru_wg, P->egru_wc, P->egru_bg, P->egru_bc, c.f("E/wx_cat"), c.f("E/bx_cat"), (int)W,
-                                (int)H, c.st));
-            TRY(c.gemm(0, 1, Tc * B2, W, 3 * H, c.f("E/dxp"), ld3, c.f("E/wx_cat"), (int)(3 * H), dx, (int)W));
-            TRY(vqa_embed_bwd_len_det(dx, c.i32("E/ctx_s"), c.i32("E/lens_s"), G->enwiki_map, (int)B2, (int)Tc, (int)W,
-                                      dims->n_ctx, det, c.st));
-            TRY(add_slice_sq(dx, Tc * B2 * W));
-        }
-    }
+    // the embedding tables are scatter-added: cleared in their phase; every other gradient is overwritten on first touch
+    SliceSq sq{c, nullptr};
+    const SeqSet q = make_seqs(dims, P, G, bx, hs);
+    for (int i = 0; i < q.n && (phases & 2); ++i) TRY(seq_bptt(c, acc, q.s[i]));
+    for (int i = 0; i < q.n && (phases & 4); ++i) TRY(seq_embed_bwd(c, q.s[i], sq));
     if (phases & 8) {
         if (hipMemsetAsync(G->wordset_map, 0, (size_t)d->n_ws * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-        if (!(phases & 4)) sq_prev = c.f("sq");
+        if (!(phases & 4)) sq.prev = c.f("sq");      // phase 4 of this step left the sequences' slice sum of squares there
     }
-    const vqa_pt_fc_t spat_vP = fc4(P->spat_v_linear_v), spat_vG = fc4(G->spat_v_linear_v);
-    const vqa_pt_fc_t spat_qP = fc4(P->spat_q_linear_v), spat_qG = fc4(G->spat_q_linear_v);
-    const vqa_pt_fc_t wftP = fc4(P->wordset_ft), wftG = fc4(G->wordset_ft);
     for (int k = 0; k < 2 && (phases & 8); ++k) {
         ProbeScope ps_sp("pt.spatial_wordset.bwd", c.st);
         const vqa_pretrain_kind_t& kb = bt->kind[k];
         const std::string p = std::string(KIND[k]) + "/";
-        if (hs.rank[1] >= 0) {
-            TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 * hs.rank[1] + k) * Bn * H, c.f(p + "ws"), Bn, W, H, wftP, wftG, li(k),
-                          (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", nullptr, 1.f, "d_wfpre", c.f("d_ws")));
+        if (hs.rank[1] >= 0) {      // ---- word set -> wordset_ft -> tanh -> wordset_map
+            TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 * hs.rank[1] + k) * Bn * H, c.f(p + "ws"), Bn, W, H, P->wordset_ft,
+                          G->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", nullptr, 1.f, "d_wfpre",
+                          c.f("d_ws")));
             TRY(vqa_tanh_bwd(c.f("d_ws"), c.f(p + "ws"), c.f("d_wse"), Bn * W, c.st));
             TRY(vqa_embed_bwd_len_det(c.f("d_wse"), kb.wordsets, nullptr, G->wordset_map, (int)Bn, 1, (int)W, d->n_ws, det,
                                       c.st));
-            TRY(add_slice_sq(c.f("d_wse"), Bn * W));
+            TRY(sq.add(c.f("d_wse"), Bn * W));
         }
+        // ---- spatial attention
         TRY(vqa_attn_pool_bwd_rep(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft,
                                   c.f(p + "att"), P->spat_att_score.w, kb.keep_att, d->keep_att, c.f("d_v"), c.f("d_qv"),
                                   c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G->spat_att_score.w));
         TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G->spat_att_score.b));
-        TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, spat_vP, spat_vG, li(k), (int)R, 0, p + "v_pre",
-                      p + "v_mean", p + "v_rstd", nullptr, 1.f, "d_vpre", nullptr));
-        TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, spat_qP, spat_qG, li(k), (int)n, 0, p + "qv_pre",
-                      p + "qv_mean", p + "qv_rstd", nullptr, 1.f, "d_qvpre", nullptr));
+        TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, G->spat_v_linear_v, c.li(k), (int)R,
+                      0, p + "v_pre", p + "v_mean", p + "v_rstd", nullptr, 1.f, "d_vpre", nullptr));
+        TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, G->spat_q_linear_v, c.li(k), (int)n,
+                      0, p + "qv_pre", p + "qv_mean", p + "qv_rstd", nullptr, 1.f, "d_qvpre", nullptr));
     }
-    if ((phases & 8) && slice_sq != nullptr && sq_prev != nullptr)
-        if (hipMemcpyAsync(slice_sq, sq_prev, sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
+    if ((phases & 8) && slice_sq != nullptr && sq.prev != nullptr)
+        if (hipMemcpyAsync(slice_sq, sq.prev, sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
             return VQA_ERR_LAUNCH;
     return VQA_OK;
 }
@@ -1042,16 +678,13 @@ int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, co
                  int64_t pooled_width = 0) {
     const vqa_pretrain_dims_t& d = c.d;
     const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
-    const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
     TRY(c.gemm(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, pooled.w, (int)H, c.f("S/vl_pre"), (int)H, pooled.b));
     TRY(c.gemm(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, qlin.w, (int)H, c.f("S/ll_pre"), (int)H, qlin.b));
     for (int h = 0; h < NH; ++h) {
-        const std::string q = hname(h);
-        TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, pooled.gamma[li(h)], pooled.beta[li(h)], nullptr, 1.f,
+        const std::string q = hs.name(h);
+        TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, pooled.gamma[c.li(h)], pooled.beta[c.li(h)], nullptr, 1.f,
                            c.f("S/vl") + h * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n, (int)H, 0, c.st));
-        TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + h * SH, qlin.gamma[li(h)], qlin.beta[li(h)], nullptr, 1.f, c.f("S/ll") + h * SH,
+        TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + h * SH, qlin.gamma[c.li(h)], qlin.beta[c.li(h)], nullptr, 1.f, c.f("S/ll") + h * SH,
                            c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
     }
     return VQA_OK;
@@ -1062,22 +695,18 @@ int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& 
                  const vqa_pt_fc6_t& g_pooled, const vqa_pt_fc6_t& g_qlin, int64_t pooled_width = 0) {
     const vqa_pretrain_dims_t& d = c.d;
     const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
-    const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
     for (int h = 0; h < NH; ++h) {
-        const std::string q = hname(h);
-        TRY(ln_bwd_p(c, acc, c.f("d_vl") + h * SH, Bn, H, fc_slot(pooled, li(h)), fc_slot(g_pooled, li(h)), 0, (int)n, 0,
-                     c.f("S/vl_pre") + (h & 1) * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f,
-                     c.f("d_vlpre") + h * SH));
-        TRY(ln_bwd_p(c, acc, c.f("d_ll") + h * SH, Bn, H, fc_slot(qlin, li(h)), fc_slot(g_qlin, li(h)), 0, (int)n, 0,
-                     c.f("S/ll_pre") + h * SH, c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f, c.f("d_llpre") + h * SH));
+        const std::string q = hs.name(h);
+        TRY(ln_bwd(c, acc, c.f("d_vl") + h * SH, Bn, H, pooled, g_pooled, c.li(h), (int)n, 0, c.f("S/vl_pre") + (h & 1) * SH,
+                   c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f, c.f("d_vlpre") + h * SH));
+        TRY(ln_bwd(c, acc, c.f("d_ll") + h * SH, Bn, H, qlin, g_qlin, c.li(h), (int)n, 0, c.f("S/ll_pre") + h * SH,
+                   c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f, c.f("d_llpre") + h * SH));
     }
     // every head of a category applies pooled_linear_l to the same pooled rows: their d_pre meet before one dW / dx
     for (int r = 1; r < hs.nt; ++r) TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * r * SH, 2 * SH, c.st));
     TRY(acc.weight(g_pooled.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
     TRY(c.gemm(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, pooled.w, (int)H, c.f("d_pooled"), (int)D));
-    return fc_bwd(c, acc, "d_llpre", c.f("S/lft"), NH * Bn, H, H, fc_slot(qlin, 0), fc_slot(g_qlin, 0), c.f("d_lft"));
+    return fc_bwd(c, acc, "d_llpre", c.f("S/lft"), NH * Bn, H, H, qlin, g_qlin, c.f("d_lft"));
 }
 
 }  // namespace
@@ -1096,19 +725,13 @@ extern "C" const char* vqa_pretrain_ext_report_key(int heads, int i) {
 }
 
 extern "C" int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    if (!ext_dims_ok(dims)) return VQA_ERR_ARG;
-    return make_layout_ext(*dims).total;
+    return ext_dims_ok(dims) ? make_layout_ext(*dims).total : VQA_ERR_ARG;
 }
 
 extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
                                        int64_t* n_elems) {
     if (!ext_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    const Layout L = make_layout_ext(*dims);
-    const Entry* e = L.find(name);
-    if (e == nullptr) return VQA_ERR_ARG;
-    if (offset_bytes) *offset_bytes = e->off;
-    if (n_elems) *n_elems = e->n;
-    return VQA_OK;
+    return layout_tensor(make_layout_ext(*dims), name, offset_bytes, n_elems);
 }
 
 namespace {
@@ -1141,14 +764,14 @@ int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vq
     const float* dp[2] = {c.f("d_pooled"), c.f("d_pooled") + Bn * H};
     if (ln_shared) {
         TRY(vqa_outer_rows_rep(c.f("obj/att"), dp[0], c.f("attr/att"), dp[1], c.f("d_va"), (int)B, (int)n, (int)R, (int)H, c.st));
-        TRY(ln_bwd_p(c, acc, c.f("d_va"), B * R, H, fc_slot(va, 0), fc_slot(g_va, 0), 0, (int)R, 0, c.f("va_pre"),
-                     c.f("va_mean"), c.f("va_rstd"), nullptr, 1.f, c.f("d_vapre")));
+        TRY(ln_bwd(c, acc, c.f("d_va"), B * R, H, va, g_va, 0, (int)R, 0, c.f("va_pre"), c.f("va_mean"), c.f("va_rstd"),
+                   nullptr, 1.f, c.f("d_vapre")));
     } else {
         for (int k = 0; k < 2; ++k) {
             const std::string p = std::string(KIND[k]) + "/";
             TRY(vqa_outer_rows_rep(c.f(p + "att"), dp[k], nullptr, nullptr, c.f("d_va"), (int)B, (int)n, (int)R, (int)H, c.st));
-            TRY(ln_bwd_p(c, acc, c.f("d_va"), B * R, H, fc_slot(va, k), fc_slot(g_va, k), 0, (int)R, 0, c.f("va_pre"),
-                         c.f(p + "va_mean"), c.f(p + "va_rstd"), nullptr, 1.f, c.f(k == 0 ? "d_vapre" : "d_vapre1")));
+            TRY(ln_bwd(c, acc, c.f("d_va"), B * R, H, va, g_va, k, (int)R, 0, c.f("va_pre"), c.f(p + "va_mean"),
+                       c.f(p + "va_rstd"), nullptr, 1.f, c.f(k == 0 ? "d_vapre" : "d_vapre1")));
         }
         TRY(vqa_add_inplace(c.f("d_vapre"), c.f("d_vapre1"), B * R * H, c.st));
     }
@@ -1164,17 +787,7 @@ int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const
     const HeadSet hs(dims->heads);
     const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
-    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
-    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
-                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
-    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
-    if (hs.rank[2] >= 0)
-        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
-                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
+    TRY(trunk_inputs_ok(hs, P, bx));
     ReportExtArgs ra{};
     ra.rows = (int)Bn;
     ra.nh = (int)NH;
@@ -1184,20 +797,16 @@ int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const
     TRY(ext_trunk_fwd(c, dims, P, bx, hs, va ? &pm : nullptr));
     {   // the NH heads, stacked
         const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
-        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
         ProbeScope ps_h("pt.heads.fwd", c.st);
         TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l, pm.width));
         TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
         TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
                    P->joint_fc.b));
         for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, t = hs.type[h >> 1];
-            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
-                                                                               : bx->ctx[k].keep_ew_joint;
-            const std::string q = hname(h);
-            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[li(h)], P->joint_fc.beta[li(h)], jmask,
-                               d->keep_joint, c.f("S/j") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n,
-                               (int)(2 * H), 0, c.st));
+            const std::string q = hs.name(h);
+            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[c.li(h)], P->joint_fc.beta[c.li(h)],
+                               joint_keep(*bx, h & 1, hs.type[h >> 1]), d->keep_joint, c.f("S/j") + h * SJ,
+                               c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0, c.st));
         }
         TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
                    P->classifier.b));
@@ -1244,28 +853,21 @@ int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, cons
     const HeadSet hs(dims->heads);
     const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
     ProbeScope ps_all("pretrain_ext.backward", c.st);
     Acc acc{c, {}};
     if (phases & 1) {
         ProbeScope ps_h("pt.heads.bwd", c.st);
         const int64_t SH = Bn * H, SJ = Bn * 2 * H;
-        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
         TRY(acc.weight(G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
         TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G->classifier.b));
         TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
         for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, t = hs.type[h >> 1];
-            const uint8_t* jmask = t == 0 ? bt->kind[k].keep_bf_joint : t == 1 ? bt->kind[k].keep_ws_joint
-                                                                               : bx->ctx[k].keep_ew_joint;
-            const std::string q = hname(h);
-            TRY(ln_bwd_p(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, fc_slot(P->joint_fc, li(h)), fc_slot(G->joint_fc, li(h)), 0,
-                         (int)n, 0, c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), jmask, d->keep_joint,
-                         c.f("d_jpre") + h * SJ));
+            const std::string q = hs.name(h);
+            TRY(ln_bwd(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, P->joint_fc, G->joint_fc, c.li(h), (int)n, 0,
+                       c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), joint_keep(*bx, h & 1, hs.type[h >> 1]),
+                       d->keep_joint, c.f("d_jpre") + h * SJ));
         }
-        const vqa_pt_fc_t jP = fc_slot(P->joint_fc, 0), jG = fc_slot(G->joint_fc, 0);
-        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, jP, jG, c.f("d_jin")));
+        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, P->joint_fc, G->joint_fc, c.f("d_jin")));
         TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
         TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l, va ? d->H : 0));
     }
@@ -1292,6 +894,86 @@ extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, co
                                          const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
                                          void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
     return vqa_pretrain_ext_backward_phases(dims, P, G, bx, workspace, workspace_bytes, slice_sq, 15, stream);
+}
+
+// ================================================================ the cfg-5 entry points
+// vqa_pretrain_* = vqa_pretrain_ext_* with heads bf | ws, no context batch, and every fc_layer scope widened from 4 to 6
+// LayerNorm slots (4 and 5 NULL: four heads never index them)
+namespace {
+
+bool cfg5_dims(const vqa_pretrain_dims_t* d, vqa_pretrain_ext_dims_t* x) {
+    if (!dims_ok(d)) return false;
+    *x = vqa_pretrain_ext_dims_t{*d, VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, 0, 0};
+    return true;
+}
+
+vqa_pt_fc6_t fc6(const vqa_pt_fc_t& f) {
+    vqa_pt_fc6_t o{};
+    o.w = f.w; o.b = f.b;
+    for (int i = 0; i < 4; ++i) { o.beta[i] = f.beta[i]; o.gamma[i] = f.gamma[i]; }
+    return o;
+}
+
+vqa_pretrain_ext_params_t cfg5_params(const vqa_pretrain_params_t& p) {
+    vqa_pretrain_ext_params_t e{};      // the enwiki members stay NULL
+    e.wordset_map = p.wordset_map; e.l_glove = p.l_glove;
+    e.spat_v_linear_v = fc6(p.spat_v_linear_v); e.spat_q_linear_v = fc6(p.spat_q_linear_v);
+    e.spat_att_score = fc6(p.spat_att_score);
+    e.gru_wg = p.gru_wg; e.gru_bg = p.gru_bg; e.gru_wc = p.gru_wc; e.gru_bc = p.gru_bc;
+    e.pooled_linear_l = fc6(p.pooled_linear_l); e.q_linear_l = fc6(p.q_linear_l); e.joint_fc = fc6(p.joint_fc);
+    e.wordset_ft = fc6(p.wordset_ft); e.classifier = fc6(p.classifier);
+    return e;
+}
+
+vqa_pretrain_ext_batch_t cfg5_batch(const vqa_pretrain_batch_t& b) {
+    vqa_pretrain_ext_batch_t e{};
+    e.base = b;
+    return e;
+}
+
+}  // namespace
+
+extern "C" const char* vqa_pretrain_report_key(int i) {
+    return vqa_pretrain_ext_report_key(VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, i);
+}
+
+extern "C" int64_t vqa_pretrain_workspace_bytes(const vqa_pretrain_dims_t* dims) {
+    vqa_pretrain_ext_dims_t x;
+    return cfg5_dims(dims, &x) ? make_layout_ext(x).total : VQA_ERR_ARG;
+}
+
+extern "C" int vqa_pretrain_tensor(const vqa_pretrain_dims_t* dims, const char* name, int64_t* offset_bytes,
+                                   int64_t* n_elems) {
+    vqa_pretrain_ext_dims_t x;
+    if (!cfg5_dims(dims, &x) || name == nullptr) return VQA_ERR_ARG;
+    return layout_tensor(make_layout_ext(x), name, offset_bytes, n_elems);
+}
+
+extern "C" int vqa_pretrain_forward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
+                                    const vqa_pretrain_batch_t* bt, void* workspace, int64_t workspace_bytes,
+                                    int want_dz, void* stream) {
+    vqa_pretrain_ext_dims_t x;
+    VQA_REQUIRE(cfg5_dims(dims, &x) && P && bt && workspace, VQA_ERR_ARG);
+    const vqa_pretrain_ext_params_t EP = cfg5_params(*P);
+    const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
+    return vqa_pretrain_ext_forward(&x, &EP, &bx, workspace, workspace_bytes, want_dz, stream);
+}
+
+extern "C" int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
+                                            const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt,
+                                            void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                            void* stream) {
+    vqa_pretrain_ext_dims_t x;
+    VQA_REQUIRE(cfg5_dims(dims, &x) && P && G && bt && workspace, VQA_ERR_ARG);
+    const vqa_pretrain_ext_params_t EP = cfg5_params(*P), EG = cfg5_params(*G);
+    const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
+    return vqa_pretrain_ext_backward_phases(&x, &EP, &EG, &bx, workspace, workspace_bytes, slice_sq, phases, stream);
+}
+
+extern "C" int vqa_pretrain_backward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
+                                     const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt, void* workspace,
+                                     int64_t workspace_bytes, float* slice_sq, void* stream) {
+    return vqa_pretrain_backward_phases(dims, P, G, bt, workspace, workspace_bytes, slice_sq, 15, stream);
 }
 
 // ================================================================ "no composition" pre-training
@@ -1322,11 +1004,7 @@ vqa_pretrain_ext_params_t noc_trunk(const vqa_pretrain_noc_params_t& p) {
     return e;
 }
 
-// keep-masks of head h's two joint branches: v = the ext batch's (cfg-5 / enwiki streams), l = the noc batch's
-const uint8_t* noc_vmask(const vqa_pretrain_noc_batch_t* b, int k, int t) {
-    const vqa_pretrain_ext_batch_t& x = b->base;
-    return t == 0 ? x.base.kind[k].keep_bf_joint : t == 1 ? x.base.kind[k].keep_ws_joint : x.ctx[k].keep_ew_joint;
-}
+// keep-mask of the l joint branch of the head of type t, category k (the v branch has joint_keep of the ext batch)
 const uint8_t* noc_lmask(const vqa_pretrain_noc_batch_t* b, int k, int t) {
     const vqa_pretrain_noc_kind_t& l = b->l[k];
     return t == 0 ? l.keep_bf_l_joint : t == 1 ? l.keep_ws_l_joint : l.keep_ew_l_joint;
@@ -1338,7 +1016,7 @@ std::string noc_report_key(int heads, int i) {
     static const char* const SUFFIX[3] = {"_loss", "_acc", "_top_5_acc"};
     for (int k = 0; k < 2; ++k)
         for (int r = 0; r < hs.nt; ++r) {
-            const std::string base = std::string(KIND[k]) + "_" + TASK_EXT[hs.type[r]];
+            const std::string base = std::string(KIND[k]) + "_" + TASK[hs.type[r]];
             for (const char* br : noc_split(hs.type[r]) ? std::vector<const char*>{"_v", "_l"} : std::vector<const char*>{""})
                 for (const char* suf : SUFFIX) keys.push_back(base + br + suf);
         }
@@ -1347,20 +1025,10 @@ std::string noc_report_key(int heads, int i) {
 }
 
 int noc_inputs_ok(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P, const vqa_pretrain_noc_batch_t* b) {
-    const HeadSet hs(dims->heads);
-    const vqa_pretrain_ext_batch_t* bx = &b->base;
-    const vqa_pretrain_batch_t* bt = &bx->base;
-    VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
-    VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
-                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
+    const vqa_pretrain_ext_params_t E = noc_trunk(*P);
+    TRY(trunk_inputs_ok(HeadSet(dims->heads), &E, &b->base));
     VQA_REQUIRE(P->pooled_linear_l.w && P->q_linear_l.w && P->joint_v.w && P->joint_l.w && P->classifier_v.w &&
                 P->classifier_l.w, VQA_ERR_ARG);
-    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
-    if (hs.rank[2] >= 0)
-        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
-                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
     return VQA_OK;
 }
 
@@ -1379,19 +1047,13 @@ extern "C" const char* vqa_pretrain_noc_report_key(int heads, int i) {
 }
 
 extern "C" int64_t vqa_pretrain_noc_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    if (!noc_dims_ok(dims)) return VQA_ERR_ARG;
-    return make_layout_ext(*dims, true).total;
+    return noc_dims_ok(dims) ? make_layout_ext(*dims, true).total : VQA_ERR_ARG;
 }
 
 extern "C" int vqa_pretrain_noc_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
                                        int64_t* n_elems) {
     if (!noc_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    const Layout L = make_layout_ext(*dims, true);
-    const Entry* e = L.find(name);
-    if (e == nullptr) return VQA_ERR_ARG;
-    if (offset_bytes) *offset_bytes = e->off;
-    if (n_elems) *n_elems = e->n;
-    return VQA_OK;
+    return layout_tensor(make_layout_ext(*dims, true), name, offset_bytes, n_elems);
 }
 
 extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
@@ -1407,8 +1069,6 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
     const HeadSet hs(dims->heads);
     const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
     ProbeScope ps_all("pretrain_noc.forward", c.st);
     const vqa_pretrain_ext_params_t E = noc_trunk(*P);
     TRY(ext_trunk_fwd(c, dims, &E, &bn->base, hs));
@@ -1416,7 +1076,6 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
     ra.rows = (int)Bn;
     {   // the NH heads, stacked; every branch GEMM covers all of them
         const int64_t SJ = Bn * 2 * H, SA = Bn * A;
-        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
         ProbeScope ps_h("pt.heads.fwd", c.st);
         TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l));
         TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/vl"), (int)H, P->joint_v.w, (int)(2 * H), c.f("S/jv_pre"), (int)(2 * H),
@@ -1425,11 +1084,11 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
                    P->joint_l.b));
         for (int h = 0; h < NH; ++h) {
             const int k = h & 1, t = hs.type[h >> 1];
-            const std::string q = hname(h);
-            TRY(vqa_ln_act_fwd(c.f("S/jv_pre") + h * SJ, P->joint_v.gamma[li(h)], P->joint_v.beta[li(h)], noc_vmask(bn, k, t),
+            const std::string q = hs.name(h);
+            TRY(vqa_ln_act_fwd(c.f("S/jv_pre") + h * SJ, P->joint_v.gamma[c.li(h)], P->joint_v.beta[c.li(h)], joint_keep(bn->base, k, t),
                                d->keep_joint, c.f("S/jv") + h * SJ, c.f(q + "jv_mean"), c.f(q + "jv_rstd"), (int)B, (int)n,
                                (int)(2 * H), 0, c.st));
-            TRY(vqa_ln_act_fwd(c.f("S/jl_pre") + h * SJ, P->joint_l.gamma[li(h)], P->joint_l.beta[li(h)], noc_lmask(bn, k, t),
+            TRY(vqa_ln_act_fwd(c.f("S/jl_pre") + h * SJ, P->joint_l.gamma[c.li(h)], P->joint_l.beta[c.li(h)], noc_lmask(bn, k, t),
                                d->keep_joint, c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"), (int)B, (int)n,
                                (int)(2 * H), 0, c.st));
         }
@@ -1480,14 +1139,11 @@ extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* d
     const HeadSet hs(dims->heads);
     const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    const bool ln_shared = (d->flags & VQA_FLAG_SHARED_LN) != 0;
-    auto li = [ln_shared](int site) { return ln_shared ? 0 : site; };
     ProbeScope ps_all("pretrain_noc.backward", c.st);
     Acc acc{c, {}};
     if (phases & 1) {
         ProbeScope ps_h("pt.heads.bwd", c.st);
         const int64_t SJ = Bn * 2 * H;
-        auto hname = [&](int h) { return std::string(KIND[h & 1]) + "/" + HEAD_EXT[hs.type[h >> 1]] + "/"; };
         // per branch: classifier dW / db / dx, each head's joint LayerNorm, the joint dW / db and dx into d_vl / d_ll
         struct Branch { const char *j, *dz, *dj, *jpre, *djpre, *in, *din, *tag; const vqa_pt_fc6_t *cP, *cG, *jP, *jG; };
         const Branch br[2] = {
@@ -1502,12 +1158,12 @@ extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* d
             TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f(b.dz), (int)A, b.cP->w, (int)A, c.f(b.dj), (int)(2 * H)));
             for (int h = 0; h < NH; ++h) {
                 const int k = h & 1, t = hs.type[h >> 1];
-                const std::string q = hname(h) + b.tag;
-                TRY(ln_bwd_p(c, acc, c.f(b.dj) + h * SJ, Bn, 2 * H, fc_slot(*b.jP, li(h)), fc_slot(*b.jG, li(h)), 0, (int)n, 0,
+                const std::string q = hs.name(h) + b.tag;
+                TRY(ln_bwd(c, acc, c.f(b.dj) + h * SJ, Bn, 2 * H, *b.jP, *b.jG, c.li(h), (int)n, 0,
                              c.f(b.jpre) + h * SJ, c.f(q + "_mean"), c.f(q + "_rstd"),
-                             v == 0 ? noc_vmask(bn, k, t) : noc_lmask(bn, k, t), d->keep_joint, c.f(b.djpre) + h * SJ));
+                             v == 0 ? joint_keep(bn->base, k, t) : noc_lmask(bn, k, t), d->keep_joint, c.f(b.djpre) + h * SJ));
             }
-            TRY(fc_bwd(c, acc, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, fc_slot(*b.jP, 0), fc_slot(*b.jG, 0), c.f(b.din)));
+            TRY(fc_bwd(c, acc, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, *b.jP, *b.jG, c.f(b.din)));
         }
         TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l));
     }
@@ -1537,19 +1193,13 @@ extern "C" const char* vqa_pretrain_adapt_report_key(int heads, int i) {
 }
 
 extern "C" int64_t vqa_pretrain_adapt_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    if (!adapt_dims_ok(dims)) return VQA_ERR_ARG;
-    return make_layout_ext(*dims, false, true).total;
+    return adapt_dims_ok(dims) ? make_layout_ext(*dims, false, true).total : VQA_ERR_ARG;
 }
 
 extern "C" int vqa_pretrain_adapt_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
                                          int64_t* n_elems) {
     if (!adapt_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    const Layout L = make_layout_ext(*dims, false, true);
-    const Entry* e = L.find(name);
-    if (e == nullptr) return VQA_ERR_ARG;
-    if (offset_bytes) *offset_bytes = e->off;
-    if (n_elems) *n_elems = e->n;
-    return VQA_OK;
+    return layout_tensor(make_layout_ext(*dims, false, true), name, offset_bytes, n_elems);
 }
 
 extern "C" int vqa_pretrain_adapt_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,

@@ -1,7 +1,8 @@
 """Every form of the GRU recurrence (include/vqa_hot.h, a4 / K4) against the float64 reference of the op contract
 (tests/gru_ref.py): weight-stationary one-launch forward and BPTT (csrc/gru_ws.hip), per-step fused GEMM epilogues
 with and without per-step output gradients, row windows, the live prefix of length-sorted rows, the register-streamed
-step kernels (gru config 30) and the grid-barrier persistent forward (csrc/gru_persistent.hip).
+step kernels (gru config 30) and the grid-barrier persistent forward (csrc/gru_persistent.hip).  The per-step drivers
+(csrc/gru_step.hip) are also held to each other bit for bit where they are the same computation.
 
 Outputs start NaN-poisoned; the comparator requires them fully written, hs of a finished row carried bit for bit,
 dxp exactly 0 past a row's length, forward values within FWD_ATOL (1e-5) elementwise and dxp within BWD_RTOL (1e-4) of
@@ -302,6 +303,53 @@ def test_step_forms_match_f64(H, T, B, form):
     if form in ("step", "stream"):
         bwd = max(bwd, G.check_backward(run_backward(form, c, True), _ref_dxp(c, True), c["lens"]))
     _print(form, (H, T, B), fwd, bwd)
+
+
+@pytest.mark.parametrize("B", [70, 300])
+def test_step_drivers_agree_bit_for_bit(B):
+    """Where the per-step drivers are the same computation they launch the same kernels on the same rows: the whole
+    batch as one row window, and as a live prefix that never shrinks (lens all T), must leave the same bits as the plain
+    form, and BPTT with all-zero output gradients the same values (x + 0.0 may turn -0 into +0).  H = 300 (a multiple
+    of 4, not of 32), B = 70 (no tile height divides it) and 300 (above the 256-row config switch), T = 3 (the state
+    gradient's two buffers swap both ways and end on the odd one); outputs NaN-poisoned.  Every identity also holds on
+    the build that preceded csrc/gru_step.hip (profiles/r10_gru_step_refactor.txt)."""
+    L, lib = _lib()
+    T, H = 3, 300
+    c = G.make_inputs(T, B, H, seed=977 + B, lens="full", device="cuda")
+    live_rows = np.full(T, B, dtype=np.int32)       # host array read by the _live drivers: alive for the whole test
+    bits = lambda t: t.view(torch.int32)
+
+    def fwd(name, live=(), window=()):
+        hs = torch.full((T + 1, B, H), NAN, device="cuda")
+        hs[0] = c["h0"]
+        o = {k: torch.full((T, B, H), NAN, device="cuda") for k in ("r", "u", "c", "rh")}
+        L.check(getattr(lib, name)(P(c["xp"]), P(c["Wg"]), P(c["Wc"]), P(c["lens"]), *live, P(hs), P(o["r"]), P(o["u"]),
+                                   P(o["c"]), P(o["rh"]), T, B, H, *window, None), name)
+        torch.cuda.synchronize()
+        return dict(o, hs=hs)
+
+    tape = fwd("vqa_gru_seq_fwd")
+    assert not any(bool(torch.isnan(v).any()) for v in tape.values())
+    for name, kw in (("vqa_gru_seq_fwd_rows", dict(window=(0, B))),
+                     ("vqa_gru_seq_fwd_live", dict(live=(live_rows.ctypes.data,)))):
+        got = fwd(name, **kw)
+        for k, v in tape.items():
+            assert torch.equal(bits(got[k]), bits(v)), "%s differs from vqa_gru_seq_fwd in %s" % (name, k)
+
+    def bwd(name, live=(), d_outs=(), window=()):
+        dxp = torch.full((T, B, 3 * H), NAN, device="cuda")
+        dh, scratch = c["dh_T"].clone(), torch.full((B, H), NAN, device="cuda")
+        L.check(getattr(lib, name)(P(dh), P(c["Wg"]), P(c["Wc"]), P(c["lens"]), *live, P(tape["hs"]), P(tape["r"]),
+                                   P(tape["u"]), P(tape["c"]), *d_outs, P(dxp), P(scratch), T, B, H, *window, None), name)
+        torch.cuda.synchronize()
+        return dxp
+
+    dxp = bwd("vqa_gru_seq_bwd")
+    assert not bool(torch.isnan(dxp).any())
+    assert torch.equal(bits(bwd("vqa_gru_seq_bwd_rows", window=(0, B))), bits(dxp)), "vqa_gru_seq_bwd_rows"
+    assert torch.equal(bits(bwd("vqa_gru_seq_bwd_live", live=(live_rows.ctypes.data,))), bits(dxp)), "vqa_gru_seq_bwd_live"
+    zeros = torch.zeros(T, B, H, device="cuda")
+    assert torch.equal(bwd("vqa_gru_seq_bwd_outs", d_outs=(P(zeros),)), dxp), "vqa_gru_seq_bwd_outs with zero d_outs"
 
 
 # --------------------------------------------------------------------------- persistent

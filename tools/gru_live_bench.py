@@ -3,6 +3,8 @@ import ctypes as C, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vqa_transfer_externaldata_amd import _lib
+if os.environ.get("VQA_HOT_LIB"):      # another build of the library (same-box A/B of compile-time choices)
+    _lib._LIB_PATH = os.path.abspath(os.environ["VQA_HOT_LIB"])
 lib = _lib.load()
 T, H = 14, 1024
 P = lambda t: C.c_void_p(t.data_ptr())

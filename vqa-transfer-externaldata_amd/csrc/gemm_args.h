@@ -1,6 +1,8 @@
 // Argument blocks shared by the GEMM kernels of libvqahot.so (gemm_f32.hip and the register-streamed GRU step kernels of
-// gru_stream.hip).  Internal: nothing here is part of the C ABI.
+// gru_stream.hip) and the host driver of the per-step GRU recurrence (gru_step.hip), and the launch functions those
+// translation units call across.  Internal: nothing here is part of the C ABI.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 struct GemmArgs {
@@ -46,3 +48,11 @@ struct EpiArgs {
     float* o2;             // GATES: rh                                      BWD_DH: dh_acc
 };
 
+// gemm_f32.hip: the argument block of C = A B (+ bias) (+ D); operand extents and tile grid are filled by the launch
+GemmArgs vqa_gemm_make_args(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                            const float* bias, const float* D, int ldd);
+// gemm_f32.hip: one fused GRU-step GEMM, epilogue `epi` (EPI_GATES .. EPI_BWD_DH), tile config `cfg` (4, 7..13, 16..18,
+// 20, 21; 30 = vqa_gru_rs_launch, falling back to 16 for the shapes it does not take)
+int vqa_gru_step_launch(int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);
+// gru_stream.hip: the register-streamed form of the same step; VQA_ERR_UNSUPPORTED for shapes it does not take
+int vqa_gru_rs_launch(int epi, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);

@@ -1076,9 +1076,6 @@ int launch_by_id(int cfg, int tA, int tB, const GemmArgs& a_in, int split, hipSt
 }
 
 // fused GRU-step GEMMs: layout fixed by the epilogue (forward NN, backward NT)
-}  // namespace
-int vqa_gru_rs_launch(int epi, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);   // gru_stream.hip
-namespace {
 template <int EPI>
 int launch_gru(int cfg, const GemmArgs& a_in, const EpiArgs& ep, hipStream_t st) {
     constexpr bool BKC = (EPI == EPI_BWD_RH || EPI == EPI_BWD_DH);
@@ -1119,41 +1116,6 @@ int g_tall_cfg = 20;
 int g_max_blocks = 0;   // tuning override for vqa_gemm_f32 (vqa_gemm_set_max_blocks)
 int g_conv_cfg = -1;    // tile config of the implicit-GEMM convolutions (vqa_conv_set_config); -1 = by shape
 int g_conv_cfg_plain = -1;
-// Tile config of the fused GRU-step GEMMs: many waves with small per-wave tiles (32x32), in-block split-k and two
-// tiles of register prefetch hide the per-tile barrier and load latency better than 4 waves of 64x32 per CU, and
-// every k group finishes its share of the rows in the epilogue (recurrence at B 512, H 1024, T 14: 622 -> 523 us
-// forward, 607 -> 487 us backward).  Default: one 16-wave workgroup per CU (cfg 18), 32x32 tiles / 4 waves
-// (cfg 16) once the live prefix is down to 256 rows, plain 4-wave tiles for tall batches.
-// vqa_gemm_set_gru_config(cfg) forces one config on both directions (tests, tuning); -1 = defaults.
-int g_gru_cfg = -1;
-// Tall batches (the pre-training model runs 2560 rows per step) fill the chip with plain 4-wave tiles.
-// (2560 rows, T 10: forward 1637 us with 64x64 BK 64, 1550 with BK 32 -- profiles/r2_gru_tune_b2560.txt)
-// Between 512 and 2048 rows (the live prefix of the pre-training model's 2560-row recurrence passes through all of
-// them) one 16-wave workgroup per CU is no longer the best form: 32x64 / 4-wave tiles forward (768 rows: 693 -> 565 us,
-// 1536 rows: 1072 -> 961 us per 10 steps) and 64x32 tiles of 8 waves backward (632 -> 559, 995 -> 869);
-// profiles/r2_gru_tune_rows.txt.
-inline int env_cfg(const char* name, int dflt) {      // tuning overrides, read once
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-inline int gru_cfg_fwd(int rows) {
-    static const int mid = env_cfg("VQA_HOT_GRU_MID_FWD", 9), tall = env_cfg("VQA_HOT_GRU_TALL_FWD", 12);
-    return g_gru_cfg >= 0 ? g_gru_cfg : (rows >= 2048 ? tall : rows > 512 ? mid : rows > 256 ? 18 : 16);
-}
-// The H-wide candidate kernel of a tall batch takes 32x64 tiles: at 2560 rows x 1024 columns the 64x64 tile gives 640
-// tiles (2.5 per CU, a half-empty last round), 32x64 gives 1280 (5 per CU): forward recurrence 1548 -> 1489 us at
-// 2560 rows, T 10.  VQA_HOT_GRU_NARROW_CFG overrides (tuning; -1 = the same config as the gate kernel).
-inline int gru_narrow_override() {
-    static const int v = [] { const char* e = getenv("VQA_HOT_GRU_NARROW_CFG"); return e ? atoi(e) : 9; }();
-    return v;
-}
-inline int gru_cfg_fwd_cand(int rows) {
-    return (g_gru_cfg < 0 && rows >= 2048 && gru_narrow_override() >= 0) ? gru_narrow_override() : gru_cfg_fwd(rows);
-}
-inline int gru_cfg_bwd(int rows) {
-    static const int mid = env_cfg("VQA_HOT_GRU_MID_BWD", 17), tall = env_cfg("VQA_HOT_GRU_TALL_BWD", 13);
-    return g_gru_cfg >= 0 ? g_gru_cfg : (rows >= 2048 ? tall : rows > 512 ? mid : rows > 256 ? 18 : 16);
-}
 
 // Tile / split-k choice from the gemm_tune sweep on MI355X (tools/gemm_tune.py, profiles/):
 //  * dW-type (reduction over the batch rows, K huge, M x N small): 128x128 tiles, BK 16, EIGHT waves
@@ -1165,7 +1127,7 @@ inline int gru_cfg_bwd(int rows) {
 //    (one workgroup per CU cannot hide a global load behind a single tile's MFMAs) -- 8 waves / 4 k groups
 //    (512x1024x1024: 14.4 us against 16.0 with 4 waves / 2 k groups), 4 waves for the wide answer head.
 inline int tall_small_cfg() {      // VQA_HOT_TALL_SMALL_CFG: tuning override (-1 = keep the 128x64 tile)
-    static const int v = [] { const char* e = getenv("VQA_HOT_TALL_SMALL_CFG"); return e ? atoi(e) : 12; }();
+    static const int v = vqa_env_int("VQA_HOT_TALL_SMALL_CFG", 12);
     return v < NUM_CFG ? v : 12;
 }
 
@@ -1183,8 +1145,8 @@ void choose(int tA, int tB, int M, int N, int K, int& cfg, int& split) {
     if (tA) {
         // weight gradients: 128x128 tiles of 16-deep k tiles for the long ones; up to k = 4096 the 128x64 tile of 32-deep k
         // tiles is 5 % (1024 x 2048 x 2560) to 23 % (the answer head's 2048 x 3000 x 512) faster (profiles/r3_tn_tune.txt)
-        static const int tn_short = env_cfg("VQA_HOT_TN_SHORT_CFG", 20);
-        static const int tn_mid = env_cfg("VQA_HOT_TN_MID_CFG", 20);   // (k < 20000, at most 128 tiles of 128x128: v_linear_v and recurrent dW, -5 and -9 us)
+        static const int tn_short = vqa_env_int("VQA_HOT_TN_SHORT_CFG", 20);
+        static const int tn_mid = vqa_env_int("VQA_HOT_TN_MID_CFG", 20);   // (k < 20000, at most 128 tiles of 128x128: v_linear_v and recurrent dW, -5 and -9 us)
         const bool mid = K < 20000 && cdiv(M, 128) * cdiv(N, 128) <= 128;
         cfg = ((int64_t)M * N >= (1 << 20)) ? (K <= 4096 ? tn_short : (mid ? tn_mid : 19)) : 3;
         target = 512;
@@ -1221,8 +1183,10 @@ void choose(int tA, int tB, int M, int N, int K, int& cfg, int& split) {
     }
 }
 
-GemmArgs make_args(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                   const float* bias, const float* D, int ldd) {
+}  // namespace
+
+GemmArgs vqa_gemm_make_args(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                            const float* bias, const float* D, int ldd) {
     GemmArgs a;
     a.M = M; a.N = N; a.K = K;
     a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
@@ -1238,7 +1202,16 @@ GemmArgs make_args(int M, int N, int K, const float* A, int lda, const float* B,
     return a;
 }
 
-}  // namespace
+// the per-step GRU recurrence (gru_step.hip) launches its fused step GEMMs through this
+int vqa_gru_step_launch(int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, hipStream_t st) {
+    switch (epi) {
+        case EPI_GATES: return launch_gru<EPI_GATES>(cfg, a, ep, st);
+        case EPI_CAND: return launch_gru<EPI_CAND>(cfg, a, ep, st);
+        case EPI_BWD_RH: return launch_gru<EPI_BWD_RH>(cfg, a, ep, st);
+        case EPI_BWD_DH: return launch_gru<EPI_BWD_DH>(cfg, a, ep, st);
+        default: return VQA_ERR_ARG;
+    }
+}
 
 extern "C" int64_t vqa_gemm_workspace_floats(int transA, int transB, int M, int N, int K, int split_k) {
     int cfg, split = split_k;
@@ -1249,13 +1222,6 @@ extern "C" int64_t vqa_gemm_workspace_floats(int transA, int transB, int M, int 
 extern "C" int vqa_gemm_set_config(int cfg) {
     VQA_REQUIRE(cfg >= -1 && cfg < NUM_CFG, VQA_ERR_ARG);
     g_force_cfg = cfg;
-    return VQA_OK;
-}
-
-extern "C" int vqa_gemm_set_gru_config(int cfg) {
-    VQA_REQUIRE(cfg == -1 || cfg == 4 || (cfg >= 7 && cfg <= 13) || (cfg >= 16 && cfg <= 18) || cfg == 20 || cfg == 21 || cfg == 30,
-                VQA_ERR_ARG);
-    g_gru_cfg = cfg;   // -1 restores the defaults
     return VQA_OK;
 }
 
@@ -1342,7 +1308,7 @@ extern "C" int vqa_gemm_f32_ex(int transA, int transB, int M, int N, int K, cons
     choose(transA, transB, M, N, K, cfg, split);
     if (split > 1 && ((N % 4) != 0 || workspace == nullptr)) split = 1;
 
-    GemmArgs a = make_args(M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd);
+    GemmArgs a = vqa_gemm_make_args(M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd);
     if (split > 1) {
         VQA_REQUIRE(workspace_floats >= (int64_t)split * M * N, VQA_ERR_WORKSPACE);
         int kps = (int)cdiv(cdiv(K, split), 64) * 64;
@@ -1376,7 +1342,7 @@ extern "C" int vqa_gemm_f32_gather(int M, int N, int K, const float* table, int 
     VQA_REQUIRE(lda % 4 == 0 && vqa_aligned16(table) && ldb % 4 == 0 && vqa_aligned16(B) &&
                     (gathered_out == nullptr || (ldg % 4 == 0 && vqa_aligned16(gathered_out))),
                 VQA_ERR_ALIGN);
-    GemmArgs a = make_args(M, N, K, table, lda, B, ldb, C, ldc, bias, nullptr, 0);
+    GemmArgs a = vqa_gemm_make_args(M, N, K, table, lda, B, ldb, C, ldc, bias, nullptr, 0);
     const int64_t bb = ((int64_t)(K - 1) * ldb + N) * 4;
     VQA_REQUIRE(bb < 0xFFFFFF00ll, VQA_ERR_UNSUPPORTED);
     a.a_bytes = 0;                     // A is addressed through per-lane 64-bit pointers (the table may exceed 4 GiB)
@@ -1397,234 +1363,6 @@ extern "C" int vqa_gemm_set_tall_config(int cfg) {
     return VQA_OK;
 }
 
-// ---------------------------------------------------------------------------- fused GRU recurrence
-// tf.contrib.rnn.GRUCell + tf.nn.dynamic_rnn(sequence_length) (vlmap/modules.py:124-140): two
-// GEMM launches per time step with the gate math in their epilogues.
-extern "C" int vqa_gru_seq_fwd(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
-                               float* r, float* u, float* c, float* rh, int T, int B, int H, void* stream) {
-    return vqa_gru_seq_fwd_rows(xp, Wg_h, Wc_h, len, hs, r, u, c, rh, T, B, H, 0, B, stream);
-}
-
-// rows [row0, row0 + rows) of the batch only (independent chains: one per stream)
-extern "C" int vqa_gru_seq_fwd_rows(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
-                                    float* r, float* u, float* c, float* rh, int T, int B, int H, int row0, int rows,
-                                    void* stream) {
-    VQA_REQUIRE(xp && Wg_h && Wc_h && len && hs && r && u && c && rh && T >= 0 && B > 0 && H > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(row0 >= 0 && rows >= 0 && row0 + rows <= B, VQA_ERR_ARG);
-    VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    if (rows == 0) return VQA_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t BH = (int64_t)B * H, o = (int64_t)row0 * H;
-    for (int t = 0; t < T; ++t) {
-        float* xpt = xp + ((int64_t)t * B + row0) * 3 * H;
-        const float* hp = hs + t * BH + o;
-        EpiArgs eg{};
-        eg.H = H; eg.h_prev = hp; eg.o0 = r + t * BH + o; eg.o1 = u + t * BH + o; eg.o2 = rh + t * BH + o;
-        GemmArgs ag = make_args(rows, 2 * H, H, hp, H, Wg_h, 2 * H, nullptr, 0, nullptr, xpt, 3 * H);
-        int rc = launch_gru<EPI_GATES>(gru_cfg_fwd(rows), ag, eg, st);
-        if (rc != VQA_OK) return rc;
-        EpiArgs ec{};
-        ec.H = H; ec.t = t; ec.len = len + row0; ec.h_prev = hp; ec.i0 = u + t * BH + o; ec.o0 = c + t * BH + o;
-        ec.o1 = hs + (t + 1) * BH + o;
-        GemmArgs ac = make_args(rows, H, H, rh + t * BH + o, H, Wc_h, H, nullptr, 0, nullptr, xpt + 2 * H, 3 * H);
-        rc = launch_gru<EPI_CAND>(gru_cfg_fwd_cand(rows), ac, ec, st);
-        if (rc != VQA_OK) return rc;
-    }
-    return VQA_OK;
-}
-
-// Back-propagation through time.  dh_T [B,H] is the gradient wrt the final state (consumed:
-// used as scratch); dxp [T,B,3H] receives (dr_pre | du_pre | dc_pre) per step; dh0 [B,H]
-// scratch/returns the gradient wrt the initial state.
-// Recurrence over the LIVE prefix only.  Contract: the batch rows are sorted by length, longest first, and
-// live_rows[t] (HOST array of T ints) = number of rows with len > t.  Step t then runs on rows [0, live_rows[t])
-// -- the gate / candidate GEMMs shrink with the sequences that are still running (real questions average ~6 of
-// 14 tokens) -- and finished rows are filled in afterwards exactly as the masked recurrence leaves them.
-extern "C" int vqa_gru_seq_fwd_live(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len,
-                                    const int32_t* live_rows, float* hs, float* r, float* u, float* c, float* rh,
-                                    int T, int B, int H, void* stream) {
-    VQA_REQUIRE(xp && Wg_h && Wc_h && len && live_rows && hs && r && u && c && rh && T >= 0 && B > 0 && H > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t BH = (int64_t)B * H;
-    int prev = B;
-    for (int t = 0; t < T; ++t) {
-        const int rows = live_rows[t];
-        VQA_REQUIRE(rows >= 0 && rows <= prev, VQA_ERR_ARG);      // non-increasing
-        prev = rows;
-        if (rows == 0) break;
-        float* xpt = xp + (int64_t)t * B * 3 * H;
-        const float* hp = hs + t * BH;
-        EpiArgs eg{};
-        eg.H = H; eg.h_prev = hp; eg.o0 = r + t * BH; eg.o1 = u + t * BH; eg.o2 = rh + t * BH;
-        GemmArgs ag = make_args(rows, 2 * H, H, hp, H, Wg_h, 2 * H, nullptr, 0, nullptr, xpt, 3 * H);
-        int rc = launch_gru<EPI_GATES>(gru_cfg_fwd(rows), ag, eg, st);
-        if (rc != VQA_OK) return rc;
-        EpiArgs ec{};
-        ec.H = H; ec.t = t; ec.len = len; ec.h_prev = hp; ec.i0 = u + t * BH; ec.o0 = c + t * BH;
-        ec.o1 = hs + (t + 1) * BH;
-        GemmArgs ac = make_args(rows, H, H, rh + t * BH, H, Wc_h, H, nullptr, 0, nullptr, xpt + 2 * H, 3 * H);
-        rc = launch_gru<EPI_CAND>(gru_cfg_fwd_cand(rows), ac, ec, st);
-        if (rc != VQA_OK) return rc;
-    }
-    return vqa_gru_fill_finished(hs, rh, len, T, B, H, stream);
-}
-
-extern "C" int vqa_gru_seq_bwd_live(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
-                                    const int32_t* live_rows, const float* hs, const float* r, const float* u,
-                                    const float* c, float* dxp, float* dh_scratch, int T, int B, int H, void* stream) {
-    VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && live_rows && hs && r && u && c && dxp && dh_scratch && T >= 0 && B > 0 &&
-                    H > 0,
-                VQA_ERR_ARG);
-    VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    if (T == 0) return VQA_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t BH = (int64_t)B * H;
-    const int ld = 3 * H;
-    // both state-gradient buffers start as dL/dh_final: a row is first touched at its own last step
-    if (hipMemcpyAsync(dh_scratch, dh_T, (size_t)BH * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return VQA_ERR_LAUNCH;
-    int rc = vqa_gru_zero_finished(dxp, len, T, B, H, stream);
-    if (rc != VQA_OK) return rc;
-    float* cur = dh_T;
-    float* other = dh_scratch;
-    int entered = 0;   // rows [0, entered) already carry a running dh_acc in `cur`
-    for (int t = T - 1; t >= 0; --t) {
-        const int rows = live_rows[t];
-        VQA_REQUIRE(rows >= entered && rows <= B, VQA_ERR_ARG);
-        float* dxpt = dxp + (int64_t)t * B * ld;
-        if (rows > entered) {   // rows whose LAST step is t: first half of the step from dL/dh_final, in place
-            const int64_t o = (int64_t)entered * H;
-            rc = vqa_gru_bwd_a(cur + o, hs + t * BH + o, u + t * BH + o, c + t * BH + o, len + entered, t,
-                               dxpt + (int64_t)entered * ld + 2 * H, ld, dxpt + (int64_t)entered * ld + H, ld, cur + o,
-                               rows - entered, H, stream);
-            if (rc != VQA_OK) return rc;
-            entered = rows;
-        }
-        if (rows == 0) continue;
-        EpiArgs e1{};
-        e1.H = H; e1.ldo = ld; e1.h_prev = hs + t * BH; e1.i0 = r + t * BH; e1.o0 = dxpt; e1.o1 = cur;
-        GemmArgs a1 = make_args(rows, H, H, dxpt + 2 * H, ld, Wc_h, H, nullptr, 0, nullptr, nullptr, 0);
-        rc = launch_gru<EPI_BWD_RH>(gru_cfg_bwd(rows), a1, e1, st);
-        if (rc != VQA_OK) return rc;
-        if (t > 0) {
-            float* dxpp = dxp + (int64_t)(t - 1) * B * ld;
-            EpiArgs e2{};
-            e2.H = H; e2.t = t - 1; e2.ldo = ld; e2.len = len; e2.h_prev = hs + (t - 1) * BH;
-            e2.i0 = u + (t - 1) * BH; e2.i1 = c + (t - 1) * BH; e2.o0 = dxpp + 2 * H; e2.o1 = dxpp + H;
-            e2.o2 = other;
-            GemmArgs a2 = make_args(rows, H, 2 * H, dxpt, ld, Wg_h, 2 * H, nullptr, 0, nullptr, cur, H);
-            rc = launch_gru<EPI_BWD_DH>(gru_cfg_bwd(rows), a2, e2, st);
-            if (rc != VQA_OK) return rc;
-            float* x = cur; cur = other; other = x;
-        }
-    }
-    return VQA_OK;
-}
-
-extern "C" int vqa_gru_seq_bwd(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
-                               const float* hs, const float* r, const float* u, const float* c, float* dxp,
-                               float* dh_scratch, int T, int B, int H, void* stream) {
-    return vqa_gru_seq_bwd_rows(dh_T, Wg_h, Wc_h, len, hs, r, u, c, dxp, dh_scratch, T, B, H, 0, B, stream);
-}
-
-extern "C" int vqa_gru_seq_bwd_rows(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
-                                    const float* hs, const float* r, const float* u, const float* c, float* dxp,
-                                    float* dh_scratch, int T, int B, int H, int row0, int rows, void* stream) {
-    VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && hs && r && u && c && dxp && dh_scratch && T >= 0 && B > 0 && H > 0,
-                VQA_ERR_ARG);
-    VQA_REQUIRE(row0 >= 0 && rows >= 0 && row0 + rows <= B, VQA_ERR_ARG);
-    VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    if (T == 0 || rows == 0) return VQA_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t BH = (int64_t)B * H, o = (int64_t)row0 * H;
-    const int ld = 3 * H;
-    len += row0;
-    float* dhT = dh_T + o;
-    float* dhS = dh_scratch + o;
-    float* dh_acc = dhS;   // running dL/dh_{t-1} (partial)
-    // first half of step T-1 from dh_T
-    {
-        const int t = T - 1;
-        float* dxpt = dxp + ((int64_t)t * B + row0) * ld;
-        int rc = vqa_gru_bwd_a(dhT, hs + t * BH + o, u + t * BH + o, c + t * BH + o, len, t, dxpt + 2 * H, ld,
-                               dxpt + H, ld, dh_acc, rows, H, stream);
-        if (rc != VQA_OK) return rc;
-    }
-    for (int t = T - 1; t >= 0; --t) {
-        float* dxpt = dxp + ((int64_t)t * B + row0) * ld;
-        // drh = dc_pre * Wc_h^T ; epilogue: dr_pre, dh_acc += drh*r
-        EpiArgs e1{};
-        e1.H = H; e1.ldo = ld; e1.h_prev = hs + t * BH + o; e1.i0 = r + t * BH + o; e1.o0 = dxpt; e1.o1 = dh_acc;
-        GemmArgs a1 = make_args(rows, H, H, dxpt + 2 * H, ld, Wc_h, H, nullptr, 0, nullptr, nullptr, 0);
-        int rc = launch_gru<EPI_BWD_RH>(gru_cfg_bwd(rows), a1, e1, st);
-        if (rc != VQA_OK) return rc;
-        // dh_{t-1} = (dr_pre|du_pre) * Wg_h^T + dh_acc ; epilogue: first half of step t-1
-        if (t > 0) {
-            float* dxpp = dxp + ((int64_t)(t - 1) * B + row0) * ld;
-            float* dh_next = (dh_acc == dhS) ? dhT : dhS;
-            EpiArgs e2{};
-            e2.H = H; e2.t = t - 1; e2.ldo = ld; e2.len = len; e2.h_prev = hs + (t - 1) * BH + o;
-            e2.i0 = u + (t - 1) * BH + o; e2.i1 = c + (t - 1) * BH + o; e2.o0 = dxpp + 2 * H; e2.o1 = dxpp + H;
-            e2.o2 = dh_next;
-            GemmArgs a2 = make_args(rows, H, 2 * H, dxpt, ld, Wg_h, 2 * H, nullptr, 0, nullptr, dh_acc, H);
-            rc = launch_gru<EPI_BWD_DH>(gru_cfg_bwd(rows), a2, e2, st);
-            if (rc != VQA_OK) return rc;
-            dh_acc = dh_next;
-        }
-    }
-    return VQA_OK;
-}
-
-// BPTT of a recurrence whose per-step OUTPUTS are consumed too (the bi-directional encoder of vqa/model_vlmap_finetune.py:
-// q_L_map = every step's state): d_outs [T,B,H], the gradient wrt the output of step t (zero where t >= len, as
-// dynamic_rnn zeroes those outputs), joins the running state gradient before step t is differentiated -- one small add
-// per step in front of the same two fused launches as vqa_gru_seq_bwd.
-extern "C" int vqa_gru_seq_bwd_outs(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len, const float* hs,
-                                    const float* r, const float* u, const float* c, const float* d_outs, float* dxp,
-                                    float* dh_scratch, int T, int B, int H, void* stream) {
-    VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && hs && r && u && c && d_outs && dxp && dh_scratch && T >= 0 && B > 0 && H > 0,
-                VQA_ERR_ARG);
-    VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    if (T == 0) return VQA_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t BH = (int64_t)B * H;
-    const int ld = 3 * H;
-    float* dh_acc = dh_scratch;
-    {
-        const int t = T - 1;
-        float* dxpt = dxp + (int64_t)t * B * ld;
-        int rc = vqa_add_inplace(dh_T, d_outs + t * BH, BH, stream);
-        if (rc != VQA_OK) return rc;
-        rc = vqa_gru_bwd_a(dh_T, hs + t * BH, u + t * BH, c + t * BH, len, t, dxpt + 2 * H, ld, dxpt + H, ld, dh_acc, B, H,
-                           stream);
-        if (rc != VQA_OK) return rc;
-    }
-    for (int t = T - 1; t >= 0; --t) {
-        float* dxpt = dxp + (int64_t)t * B * ld;
-        EpiArgs e1{};
-        e1.H = H; e1.ldo = ld; e1.h_prev = hs + t * BH; e1.i0 = r + t * BH; e1.o0 = dxpt; e1.o1 = dh_acc;
-        GemmArgs a1 = make_args(B, H, H, dxpt + 2 * H, ld, Wc_h, H, nullptr, 0, nullptr, nullptr, 0);
-        int rc = launch_gru<EPI_BWD_RH>(gru_cfg_bwd(B), a1, e1, st);
-        if (rc != VQA_OK) return rc;
-        if (t > 0) {
-            rc = vqa_add_inplace(dh_acc, d_outs + (t - 1) * BH, BH, stream);     // + dL/d(output of step t-1)
-            if (rc != VQA_OK) return rc;
-            float* dxpp = dxp + (int64_t)(t - 1) * B * ld;
-            float* dh_next = (dh_acc == dh_scratch) ? dh_T : dh_scratch;
-            EpiArgs e2{};
-            e2.H = H; e2.t = t - 1; e2.ldo = ld; e2.len = len; e2.h_prev = hs + (t - 1) * BH;
-            e2.i0 = u + (t - 1) * BH; e2.i1 = c + (t - 1) * BH; e2.o0 = dxpp + 2 * H; e2.o1 = dxpp + H;
-            e2.o2 = dh_next;
-            GemmArgs a2 = make_args(B, H, 2 * H, dxpt, ld, Wg_h, 2 * H, nullptr, 0, nullptr, dh_acc, H);
-            rc = launch_gru<EPI_BWD_DH>(gru_cfg_bwd(B), a2, e2, st);
-            if (rc != VQA_OK) return rc;
-            dh_acc = dh_next;
-        }
-    }
-    return VQA_OK;
-}
-
 // ---------------------------------------------------------------------------- convolution (NHWC)
 // slim resnet_v1 inference conv + folded BatchNorm (+ residual) (+ ReLU): vlmap/modules.py:143-191,
 // 219-239, 552-572.  1x1/stride-1 convs are plain GEMMs over [B*H*W, Ci]; every other filter is an
@@ -1639,7 +1377,7 @@ extern "C" int vqa_conv2d_nhwc(const float* x, int B, int Hi, int Wi, int Ci, co
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int M = B * Ho * Wo, K = kh * kw * Ci;
     const bool plain = (kh == 1 && kw == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && Ho == Hi && Wo == Wi);
-    GemmArgs a = make_args(M, Co, K, x, Ci, w, Co, y, Co, shift, residual, Co);
+    GemmArgs a = vqa_gemm_make_args(M, Co, K, x, Ci, w, Co, y, Co, shift, residual, Co);
     a.scale = scale;
     a.relu = relu;
     if (plain && (shortk_mode() & 2) && Ci >= 128 && Ci <= 256 && Co >= 2 * Ci && g_conv_cfg_plain < 0 && g_force_cfg < 0 &&

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/vqa_hot.h"
 
@@ -36,6 +37,12 @@ struct ProbeScope {
 };
 
 static inline bool vqa_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// integer tuning override from the environment; callers keep the value in a function-local static (read once)
+static inline int vqa_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -65,6 +65,9 @@ ROWOPS = [
     "gru_gates_fwd", "gru_cand_fwd", "gru_bwd_a", "gru_bwd_b", "im2col_nhwc",
 ]
 
+# the attention entry points tests/test_gpu_attn_f64.py pins to the float64 reference of tests/attn_ref.py, form by form
+ATTN = ["attn_pool_fwd", "attn_pool_bwd", "attn_pool_fwd_rep", "attn_pool_bwd_rep"]
+
 
 def _declared(repo_root):
     src = open(os.path.join(repo_root, "include", "vqa_hot.h")).read()
@@ -93,3 +96,14 @@ def test_the_row_kernels_stay_pinned_by_their_float64_test(repo_root):
     assert not set("vqa_" + k for k in ROWOPS) & set(ALLOWED)
     declared = set(_declared(repo_root))
     assert all("vqa_" + k in declared for k in ROWOPS)
+
+
+def test_the_attention_kernels_stay_pinned_by_their_float64_test(repo_root):
+    text = open(os.path.join(repo_root, "tests", "test_gpu_attn_f64.py")).read()
+    calls = set(re.findall(r"\bvqa_[a-z0-9_]+\b", text))
+    missing = ["vqa_" + k for k in ATTN if "vqa_" + k not in calls]
+    assert not missing, "tests/test_gpu_attn_f64.py no longer calls %s" % missing
+    assert "vqa_attn_set_fast" in calls and "attn_ref" in text
+    assert not set("vqa_" + k for k in ATTN) & set(ALLOWED)
+    declared = set(_declared(repo_root))
+    assert all("vqa_" + k in declared for k in ATTN)

@@ -16,12 +16,9 @@ ALLOWED = {
     "vqa_fusion_tensor": "host-only layout query, tests/test_abi.py",
     "vqa_pretrain_workspace_bytes": "host-only layout query, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
     "vqa_pretrain_tensor": "host-only layout query, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
-    "vqa_gemm_workspace_floats": "host-only size query behind ops.gemm's split-K (test_gpu_ops.py::test_gemm_split_k_deterministic)",
     "vqa_gemm_bf16x3_workspace_floats": "host-only size query behind ops.gemm_bf16x3_ex (test_gpu_ops.py)",
     "vqa_conv2d_bwd_workspace_floats": "host-only size query of the extractor's backward, tests/host_abi_exercise.py",
     # knobs, debug and profiling hooks
-    "vqa_gemm_set_max_blocks": "tuning knob",
-    "vqa_gemm_set_order": "tuning knob",
     "vqa_gemm_bf16x3_set_mode": "tuning knob of the experimental bf16x3 GEMM",
     "vqa_gemm_shortk_set_mode": "tuning knob of the short-K GEMM",
     "vqa_gru_set_persistent": "A/B switch of the recurrence forms",
@@ -40,8 +37,6 @@ ALLOWED = {
     # whole-model entry points (test_gpu_pretrain.py / test_gpu_fusion.py call them through the model classes)
     "vqa_pretrain_forward": "whole-model entry point, test_gpu_pretrain.py",
     # kernels pinned under another name
-    "vqa_gemm_f32": "ops.gemm, test_gpu_ops.py::test_gemm_matches_f64",
-    "vqa_gemm_f32_ex": "the form vqa_gemm_f32 delegates to, test_gpu_ops.py::test_gemm_matches_f64",
     "vqa_gemm_bf16x3_nn": "ops.gemm_bf16x3, test_gpu_ops.py::test_experimental_bf16x3_gemm_is_f32_equivalent",
     "vqa_gemm_shortk_nn": "ops.gemm_shortk, test_gpu_ops.py::test_shortk_gemm_matches_float64",
     "vqa_gru_fill_finished": "vqa_gru_seq_fwd_live's finished rows, test_gpu_gru_f64.py (form live)",
@@ -67,6 +62,10 @@ ROWOPS = [
 
 # the attention entry points tests/test_gpu_attn_f64.py pins to the float64 reference of tests/attn_ref.py, form by form
 ATTN = ["attn_pool_fwd", "attn_pool_bwd", "attn_pool_fwd_rep", "attn_pool_bwd_rep"]
+
+# the f32 GEMM entry points and knobs tests/test_gpu_gemm_f64.py pins to the float64 reference of tests/gemm_ref.py, route by route
+GEMM = ["gemm_f32", "gemm_f32_ex", "gemm_f32_gather", "gemm_set_config", "gemm_set_order", "gemm_set_max_blocks",
+        "gemm_set_tall_config", "gemm_workspace_floats"]
 
 
 def _declared(repo_root):
@@ -107,3 +106,14 @@ def test_the_attention_kernels_stay_pinned_by_their_float64_test(repo_root):
     assert not set("vqa_" + k for k in ATTN) & set(ALLOWED)
     declared = set(_declared(repo_root))
     assert all("vqa_" + k in declared for k in ATTN)
+
+
+def test_the_f32_gemm_stays_pinned_by_its_float64_test(repo_root):
+    text = open(os.path.join(repo_root, "tests", "test_gpu_gemm_f64.py")).read()
+    calls = set(re.findall(r"\blib\.(vqa_[a-z0-9_]+)\(", text))
+    missing = ["vqa_" + k for k in GEMM if "vqa_" + k not in calls]
+    assert not missing, "tests/test_gpu_gemm_f64.py no longer calls %s" % missing
+    assert "vqa_gemm_shortk_set_mode" in calls and "gemm_ref" in text
+    assert not set("vqa_" + k for k in GEMM) & set(ALLOWED)
+    declared = set(_declared(repo_root))
+    assert all("vqa_" + k in declared for k in GEMM)

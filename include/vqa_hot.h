@@ -487,7 +487,20 @@ typedef struct {
                                      * Accepted model types: 0 (vlmap_answer) and 1 (standard); every other type, and the
                                      * flag together with VQA_FLAG_FUSED_GATHER (the gather-fused GEMM has no bf16 form),
                                      * makes vqa_fusion_workspace_bytes / _tensor / _forward / _backward* return
-                                     * VQA_ERR_ARG.  Per call like VQA_FLAG_DETERMINISTIC: no process-wide state. */
+                                     * VQA_ERR_ARG.  Per call like VQA_FLAG_DETERMINISTIC: no process-wide state.
+                                     * The pre-training steps (vqa_pretrain_dims_t.flags; vqa_pretrain_*, _ext_*, _noc_* and
+                                     * _adapt_*: workspace / tensor queries, forward with want_dz 0 or 1, backward and
+                                     * backward_phases) honour the bit the same way.  ROUTED (forward, dW and dx):
+                                     * pooled_linear_l, q_linear_l, joint_fc and classifier; in the "no composition" models
+                                     * joint_v, joint_l, classifier_v and classifier_l; in the adapt model v_adapt (forward
+                                     * and dW: it has no dx).  NOT ROUTED: everything of both encoders (encode_L_blank,
+                                     * encode_L_enwiki) -- the packed K = W x-projection, the recurrence, the dx product of
+                                     * the embedding backward and the three weight products of the BPTT (dwx, both dwh) --
+                                     * for the same reason; wordset_ft (K = W) and spat_v_linear_v / spat_q_linear_v (K = 6),
+                                     * which hold no matrix time.  A shape vqa_gemm_bf16 refuses is its error return, never
+                                     * an f32 product.  With the flag set "gemm_ws" also covers
+                                     * vqa_gemm_bf16_workspace_floats of the routed shapes; with it clear every layout is
+                                     * what it was. */
 
 /* One FC(+LN) layer: weights [in,out], biases [out], LayerNorm beta/gamma [out] (NULL if no LN). */
 typedef struct { float *w, *b, *beta, *gamma; } vqa_fc_t;
@@ -580,7 +593,8 @@ typedef struct {
     int32_t B, n, R, D, H, W, A, Vq, n_ws;  /* images, entries per category (5), regions, feature / hidden / word dims,
                                              * answers, caption vocabulary, word-set vocabulary */
     int32_t L;                               /* padded caption length of THIS batch (blanks [B,n,L]) */
-    int32_t flags;                           /* VQA_FLAG_* */
+    int32_t flags;                           /* VQA_FLAG_DETERMINISTIC, VQA_FLAG_SHARED_LN, VQA_FLAG_BF16_GEMM (honoured:
+                                              * the routed layers listed at the flag) */
     float keep_att, keep_joint;              /* 0.8 / 0.5 */
     float global_valid[2];                   /* data parallel: number of valid entries of the GLOBAL batch per category
                                               * (object, attribute) = the denominator of the masked mean losses

@@ -5,7 +5,9 @@
 (vlmap_bf_or_wordset_withatt_sp_adapt) times that model instead and
 also prints the analytic MFMA FLOPs per step (flops_per_step) and the rate they give.  `--alternate` builds cfg-5 and the
 chosen model in one process and times their steps alternately (each warmed up first), so that both rates come from the
-same box and clocks.  Without options the output is the cfg-5 line as before."""
+same box and clocks.  `--precision bf16` builds the timed engine(s) with PretrainEngine(precision="bf16");
+`--ab_precision` builds the chosen model twice, f32 and bf16 (same parameters, same batch), and alternates their steps
+the same way: both medians and their ratio.  Without options the output is the cfg-5 line as before."""
 import argparse
 import os
 import sys
@@ -27,6 +29,8 @@ _ap.add_argument("steps", nargs="?", type=int, default=10)
 _ap.add_argument("--model_type", default="vlmap_bf_or_wordset_withatt_sp",
                  choices=sorted(PT.MODEL_HEADS) + sorted(PT.NOC_MODEL_HEADS) + sorted(PT.ADAPT_MODEL_HEADS))
 _ap.add_argument("--alternate", action="store_true")
+_ap.add_argument("--precision", default="f32", choices=list(PT.PRECISIONS))
+_ap.add_argument("--ab_precision", action="store_true")
 ARGS = _ap.parse_args()
 
 
@@ -59,10 +63,63 @@ ds = DV.Dataset(split="train", data=DV.synthetic_dataset(B, Vq, n_ws, A, R=R, D=
 batch = next(DV.create_ops(B, ds, is_train=True, shuffle=False))
 batch = {k: v for k, v in batch.items() if v.dtype.kind in "fi" and k != "image_id"}
 sort_info = {} if os.environ.get("SORT", "1") == "0" else {k: v for k, v in PT.add_length_sort(dict(batch)).items() if k.endswith("/sort")}
-eng = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p)
+steps = ARGS.steps
+
+
+def other_model(model_type, precisions):
+    """the engines (one per precision, same parameters), device batch and FLOPs per step of a model other than cfg-5"""
+    noc, adapt = model_type in PT.NOC_MODEL_HEADS, model_type in PT.ADAPT_MODEL_HEADS
+    heads = (PT.NOC_MODEL_HEADS if noc else PT.ADAPT_MODEL_HEADS if adapt else PT.MODEL_HEADS)[model_type]
+    if "ew" in heads:
+        data = DV.synthetic_dataset(B, Vq, n_ws, A, R=R, D=D, max_len=L, seed=0, enwiki=dict(n_ctx=N_CTX, Lc=LC))
+        dse = DV.Dataset(split="train", data=data, seed=0, enwiki=True)
+        be = next(DV.create_ops(B, dse, is_train=True, shuffle=False))
+        be = {k: v for k, v in be.items() if v.dtype.kind in "fi" and k != "image_id"}
+    else:
+        be = batch                 # the noc word-set model and the adapt model read cfg-5's batch
+    n_ctx = N_CTX if "ew" in heads else None
+    pe = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H, heads=heads, n_ctx=n_ctx, noc=noc, adapt=adapt)
+    engines = [PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=pe, heads=heads, n_ctx=n_ctx,
+                                 noc=noc, adapt=adapt, precision=pr) for pr in precisions]
+    dbe = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
+    if os.environ.get("SORT", "1") != "0":
+        dbe.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
+    for ee in engines:
+        for i in range(3):
+            ee.train_step(dbe, ee.make_keep_masks(B, 1, i), 1e-3)
+    return engines, dbe, flops_per_step(heads, be, noc, adapt)
+
+
+if ARGS.ab_precision:
+    if ARGS.model_type == "vlmap_bf_or_wordset_withatt_sp":
+        engines = [PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p, precision=pr) for pr in PT.PRECISIONS]
+        dba = {k: torch.from_numpy(v).cuda() for k, v in batch.items()}
+        dba.update(sort_info)
+        for e in engines:
+            for i in range(3):
+                e.train_step(dba, e.make_keep_masks(B, 1, i), 1e-3)
+        fl = flops_per_step(PT.CFG5_HEADS, batch)
+    else:
+        engines, dba, fl = other_model(ARGS.model_type, PT.PRECISIONS)
+    times = {e.precision: [] for e in engines}
+    for i in range(steps):
+        for e in engines:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.train_step(dba, e.make_keep_masks(B, 1, 3 + i), 1e-3)
+            torch.cuda.synchronize()
+            times[e.precision].append(time.perf_counter() - t0)
+    med = {k: 1e3 * float(np.median(v)) for k, v in times.items()}
+    for e in engines:
+        print("%s %s: step %.2f ms (median of %d alternated)  flops_per_step %.3f TFLOP  -> %.1f TFLOP/s; total_loss %.3f"
+              % (ARGS.model_type, e.precision, med[e.precision], steps, fl / 1e12, fl / med[e.precision] / 1e9,
+                 e.fetch_report()["total_loss"]))
+    print("step time ratio f32 / bf16 = %.3f" % (med["f32"] / med["bf16"]))
+    sys.exit(0)
+
+eng = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p, precision=ARGS.precision)
 db = {k: torch.from_numpy(v).cuda() for k, v in batch.items()}
 db.update(sort_info)
-steps = ARGS.steps
 if any(os.environ.get(k) for k in ("VQA_LN_FAST", "VQA_GRU_CFG", "VQA_ATTN_FAST", "VQA_SOFTMAX_FAST")):   # A/B switches
     from vqa_transfer_externaldata_amd import _lib
     _l = _lib.load()
@@ -94,23 +151,8 @@ if ARGS.model_type != "vlmap_bf_or_wordset_withatt_sp" or ARGS.alternate:
     f5 = flops_per_step(PT.CFG5_HEADS, batch)
     runs = {"vlmap_bf_or_wordset_withatt_sp": (eng, db, f5)}
     if "ew" in heads or NOC or ADAPT:
-        if "ew" in heads:
-            data = DV.synthetic_dataset(B, Vq, n_ws, A, R=R, D=D, max_len=L, seed=0, enwiki=dict(n_ctx=N_CTX, Lc=LC))
-            dse = DV.Dataset(split="train", data=data, seed=0, enwiki=True)
-            be = next(DV.create_ops(B, dse, is_train=True, shuffle=False))
-            be = {k: v for k, v in be.items() if v.dtype.kind in "fi" and k != "image_id"}
-        else:
-            be = batch                 # the noc word-set model and the adapt model read cfg-5's batch
-        n_ctx = N_CTX if "ew" in heads else None
-        pe = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H, heads=heads, n_ctx=n_ctx, noc=NOC, adapt=ADAPT)
-        ee = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=pe, heads=heads, n_ctx=n_ctx,
-                               noc=NOC, adapt=ADAPT)
-        dbe = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
-        if os.environ.get("SORT", "1") != "0":
-            dbe.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
-        for i in range(3):
-            ee.train_step(dbe, ee.make_keep_masks(B, 1, i), 1e-3)
-        runs[ARGS.model_type] = (ee, dbe, flops_per_step(heads, be, NOC, ADAPT))
+        (ee,), dbe, fe = other_model(ARGS.model_type, (ARGS.precision,))
+        runs[ARGS.model_type] = (ee, dbe, fe)
     order = list(runs) if ARGS.alternate else [ARGS.model_type]
     times = {k: [] for k in order}
     for i in range(steps):

@@ -140,18 +140,32 @@ struct Ctx {
     int64_t count(const std::string& name) const { return L.find(name)->n; }
     // LayerNorm slot of call site `site` of an fc_layer scope: slot 0 for every site under VQA_FLAG_SHARED_LN
     int li(int site) const { return (d.flags & VQA_FLAG_SHARED_LN) ? 0 : site; }
-    int gemm(int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B, int ldb, float* C,
-             int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) const {
+    // The f32 MFMA product, whatever the flags say: both encoders (x-projection, dx, dwx, dwh), wordset_ft and the K = 6
+    // box layers call this one (include/vqa_hot.h, VQA_FLAG_BF16_GEMM: the unrouted list).
+    int gemm_f32(int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B, int ldb, float* C,
+                 int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) const {
         return vqa_gemm_f32(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, f("gemm_ws"),
                             count("gemm_ws"), st);
     }
+    // The routed layers' products (forward, dW, dx): bf16 operands in the matrix unit under VQA_FLAG_BF16_GEMM, else f32.
+    // A shape the bf16 kernel refuses is its error return, never a silent f32 product.  Every call site names one of the
+    // two wrappers: there is no default a new site could pick up by accident.
+    int gemm_routed(int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B, int ldb,
+                    float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) const {
+        if (d.flags & VQA_FLAG_BF16_GEMM)
+            return vqa_gemm_bf16(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, f("gemm_ws"),
+                                 count("gemm_ws"), 0, st);
+        return gemm_f32(tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd);
+    }
 };
+enum Prec { PREC_F32, PREC_ROUTED };      // which of the two a helper shared by routed and unrouted layers uses
 
-// modules.fc_layer forward: FC on the last axis, layer_norm over groups of `rows` rows, activation (0 relu, 1 tanh)
+// modules.fc_layer forward: FC on the last axis, layer_norm over groups of `rows` rows, activation (0 relu, 1 tanh).
+// Its users are the unrouted layers (K = 6 box layers, wordset_ft): the product is f32 in every mode.
 int fc_ln_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc6_t& p, int ln, int rows,
               int act, const std::string& pre, const std::string& y, const std::string& mean, const std::string& rstd,
               const uint8_t* keep, float keep_prob) {
-    TRY(c.gemm(0, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
+    TRY(c.gemm_f32(0, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
     return vqa_ln_act_fwd(c.f(pre), p.gamma[ln], p.beta[ln], keep, keep_prob, c.f(y), c.f(mean), c.f(rstd),
                           (int)(M / rows), rows, (int)N, act, c.st);
 }
@@ -166,10 +180,15 @@ struct Acc {
             return hipMemcpyAsync(grad, value, (size_t)n * 4, hipMemcpyDeviceToDevice, c.st) == hipSuccess ? VQA_OK : VQA_ERR_LAUNCH;
         return vqa_add_inplace(grad, value, n, c.st);
     }
-    // dW (+)= x^T * dpre
-    int weight(float* gw, const float* x, int ldx, const float* dpre, int ldp, int64_t K, int64_t N, int64_t M) {
+    // dW (+)= x^T * dpre, through the wrapper the call site names; the in-place addend of a second touch goes through
+    // the same kernel's D == C form.  No model touches a ROUTED weight twice today (every routed layer is one stacked
+    // product; the second touches are wordset_ft and the box layers, f32), so no step-level test runs the bf16 kernel's
+    // D == C form: it is covered by the op tests of vqa_gemm_bf16 only (tests/test_gpu_bf16.py, in-place addend).
+    int weight(Prec prec, float* gw, const float* x, int ldx, const float* dpre, int ldp, int64_t K, int64_t N, int64_t M) {
         const bool first = touched.insert(gw).second;
-        return c.gemm(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, first ? nullptr : gw, (int)N);
+        const float* add = first ? nullptr : gw;
+        if (prec == PREC_ROUTED) return c.gemm_routed(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
+        return c.gemm_f32(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
     }
     // three column sums (d_gamma, d_beta, d_bias partials [G, N]) into their gradients: first touch overwrites, later
     // ones add inside the reduction's last pass (no temporaries, no add kernels)
@@ -198,19 +217,20 @@ int ln_bwd(const Ctx& c, Acc& acc, const float* dy, int64_t M, int64_t N, const 
 }
 
 // backward of the FC half: dW (+)= x^T d_pre, optional dx = d_pre * W^T
-int fc_bwd(const Ctx& c, Acc& acc, const std::string& d_pre, const float* x, int64_t M, int64_t K, int64_t N,
+int fc_bwd(const Ctx& c, Acc& acc, Prec prec, const std::string& d_pre, const float* x, int64_t M, int64_t K, int64_t N,
            const vqa_pt_fc6_t& p, const vqa_pt_fc6_t& g, float* dx) {
-    TRY(acc.weight(g.w, x, (int)K, c.f(d_pre), (int)N, K, N, M));
-    if (dx != nullptr) TRY(c.gemm(0, 1, M, K, N, c.f(d_pre), (int)N, p.w, (int)N, dx, (int)K));
-    return VQA_OK;
+    TRY(acc.weight(prec, g.w, x, (int)K, c.f(d_pre), (int)N, K, N, M));
+    if (dx == nullptr) return VQA_OK;
+    if (prec == PREC_ROUTED) return c.gemm_routed(0, 1, M, K, N, c.f(d_pre), (int)N, p.w, (int)N, dx, (int)K);
+    return c.gemm_f32(0, 1, M, K, N, c.f(d_pre), (int)N, p.w, (int)N, dx, (int)K);
 }
 
-// backward of fc_ln_fwd
+// backward of fc_ln_fwd (the unrouted layers: f32 products)
 int fc_ln_bwd(const Ctx& c, Acc& acc, const float* dy, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc6_t& p,
               const vqa_pt_fc6_t& g, int ln, int rows, int act, const std::string& pre, const std::string& mean,
               const std::string& rstd, const uint8_t* keep, float keep_prob, const std::string& d_pre, float* dx) {
     TRY(ln_bwd(c, acc, dy, M, N, p, g, ln, rows, act, c.f(pre), c.f(mean), c.f(rstd), keep, keep_prob, c.f(d_pre)));
-    return fc_bwd(c, acc, d_pre, x, M, K, N, p, g, dx);
+    return fc_bwd(c, acc, PREC_F32, d_pre, x, M, K, N, p, g, dx);
 }
 
 int gather_rows(const void* in, const int32_t* index, void* out, int64_t rows, int64_t cols, hipStream_t st) {
@@ -371,6 +391,11 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool
     auto g = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) {
         gw = max64(gw, vqa_gemm_workspace_floats(tA, tB, (int)M, (int)N, (int)K, 0));
     };
+    // a routed product: under VQA_FLAG_BF16_GEMM also what the bf16 kernel's shape-chosen split k needs
+    auto gr = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) {
+        g(tA, tB, M, N, K);
+        if (d.flags & VQA_FLAG_BF16_GEMM) gw = max64(gw, vqa_gemm_bf16_workspace_floats((int)M, (int)N, (int)K, 0));
+    };
     if (adapt) {
         // v_adapt: ONE pre-activation per image (the x n tile and the second category repeat it), one output per
         // LayerNorm: shared -> "obj/va" and "attr/va" name the same buffer
@@ -390,7 +415,7 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool
         }
         L.add("d_va", S); L.add("d_vapre", S);
         if (!ln_shared) L.add("d_vapre1", S);      // the attribute call site's d_pre before the two meet
-        g(0, 0, B * R, H, d.D); g(1, 0, d.D, H, B * R);
+        gr(0, 0, B * R, H, d.D); gr(1, 0, d.D, H, B * R);
     }
     g(0, 0, B * R, H, 6); g(0, 0, Bn, H, 6); g(0, 0, Bn, H, W);
     g(1, 0, 6, H, B * R); g(1, 0, 6, H, Bn); g(1, 0, W, H, Bn); g(0, 1, Bn, W, H);
@@ -399,9 +424,10 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool
         g(0, 0, S * 2 * Bn, 3 * H, W); g(1, 0, x_stride(W), 3 * H, S * 2 * Bn); g(0, 1, S * 2 * Bn, W, 3 * H);
         g(1, 0, H, 2 * H, S * 2 * Bn); g(1, 0, H, H, S * 2 * Bn);
     }
-    g(0, 0, 2 * Bn, H, D); g(0, 0, NH * Bn, H, H); g(0, 0, NH * Bn, 2 * H, H); g(0, 0, NH * Bn, A, 2 * H);
-    g(1, 0, 2 * H, A, NH * Bn); g(0, 1, NH * Bn, 2 * H, A); g(1, 0, H, 2 * H, NH * Bn); g(0, 1, NH * Bn, H, 2 * H);
-    g(1, 0, D, H, 2 * Bn); g(0, 1, 2 * Bn, D, H); g(1, 0, H, H, NH * Bn); g(0, 1, NH * Bn, H, H);
+    // the routed layers: pooled_linear_l, q_linear_l, the joint layer(s) and the classifier(s), forward / dW / dx
+    gr(0, 0, 2 * Bn, H, D); gr(0, 0, NH * Bn, H, H); gr(0, 0, NH * Bn, 2 * H, H); gr(0, 0, NH * Bn, A, 2 * H);
+    gr(1, 0, 2 * H, A, NH * Bn); gr(0, 1, NH * Bn, 2 * H, A); gr(1, 0, H, 2 * H, NH * Bn); gr(0, 1, NH * Bn, H, 2 * H);
+    gr(1, 0, D, H, 2 * Bn); gr(0, 1, 2 * Bn, D, H); gr(1, 0, H, H, NH * Bn); gr(0, 1, NH * Bn, H, H);
     L.add("gemm_ws", gw);
     int64_t cw = 4;
     cw = max64(cw, vqa_colsum_workspace_floats((int)B, (int)(2 * H)));
@@ -526,8 +552,8 @@ int seq_fwd(const Ctx& c, const Seq& s, bool pack_wx) {
     TRY(gather_rows2(s.tokens[0], s.tokens[1], s.perm, tok, B2, T, Bn, c.st));
     TRY(gather_rows2(s.len[0], s.len[1], s.perm, lens, B2, 1, Bn, c.st));
     TRY(vqa_embed_fwd_ld(s.table, tok, x_tm, (int)B2, (int)T, (int)W, s.vocab, (int)x_stride(W), c.st));
-    TRY(c.gemm(0, 0, T * B2, 3 * H, W, x_tm, (int)x_stride(W), c.f(s.scr + "wx_cat"), (int)(3 * H), xp, (int)(3 * H),
-               c.f(s.scr + "bx_cat")));
+    TRY(c.gemm_f32(0, 0, T * B2, 3 * H, W, x_tm, (int)x_stride(W), c.f(s.scr + "wx_cat"), (int)(3 * H), xp, (int)(3 * H),
+                   c.f(s.scr + "bx_cat")));
     if (hipMemsetAsync(hs, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
     const float *Wg_h = s.P.wg + W * 2 * H, *Wc_h = s.P.wc + W * H;
     if (s.live_rows != nullptr)
@@ -554,9 +580,9 @@ int seq_bptt(const Ctx& c, Acc& acc, const Seq& s) {
         TRY(vqa_gru_seq_bwd(d_state, Wg_h, Wc_h, lens, hs, r, u, cc, dxp, c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
     // x rows of both kernels' gradients as one GEMM into the packed [Wp, 3H] block; x_tm carries the constant 1 in
     // column W, so row W of the block is the two bias gradients and dxp is not read again for them
-    TRY(acc.weight(dwx, c.f(s.in + "x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
-    TRY(acc.weight(s.G.wg + W * 2 * H, hs, (int)H, dxp, ld3, H, 2 * H, T * B2));
-    TRY(acc.weight(s.G.wc + W * H, c.f(s.in + "gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
+    TRY(acc.weight(PREC_F32, dwx, c.f(s.in + "x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
+    TRY(acc.weight(PREC_F32, s.G.wg + W * 2 * H, hs, (int)H, dxp, ld3, H, 2 * H, T * B2));
+    TRY(acc.weight(PREC_F32, s.G.wc + W * H, c.f(s.in + "gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
     return vqa_gru_unpack_dwx_bias(dwx, s.G.wg, s.G.wc, s.G.bg, s.G.bc, (int)W, (int)H, c.st);
 }
 
@@ -579,7 +605,7 @@ int seq_embed_bwd(const Ctx& c, const Seq& s, SliceSq& sq) {
     float* dx = c.f(s.scr + "dx");
     // packed again here (one small kernel): no hidden dependence on the forward's copy of the weights
     TRY(seq_pack_wx(c, s));
-    TRY(c.gemm(0, 1, T * B2, W, 3 * H, c.f(s.scr + "dxp"), (int)(3 * H), c.f(s.scr + "wx_cat"), (int)(3 * H), dx, (int)W));
+    TRY(c.gemm_f32(0, 1, T * B2, W, 3 * H, c.f(s.scr + "dxp"), (int)(3 * H), c.f(s.scr + "wx_cat"), (int)(3 * H), dx, (int)W));
     TRY(vqa_embed_bwd_len_det(dx, c.i32(s.in + s.tok), c.i32(s.in + "lens_s"), s.g_table, (int)B2, (int)T, (int)W, s.vocab,
                               (c.d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
     return sq.add(dx, T * B2 * W);
@@ -678,8 +704,8 @@ int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, co
                  int64_t pooled_width = 0) {
     const vqa_pretrain_dims_t& d = c.d;
     const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
-    TRY(c.gemm(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, pooled.w, (int)H, c.f("S/vl_pre"), (int)H, pooled.b));
-    TRY(c.gemm(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, qlin.w, (int)H, c.f("S/ll_pre"), (int)H, qlin.b));
+    TRY(c.gemm_routed(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, pooled.w, (int)H, c.f("S/vl_pre"), (int)H, pooled.b));
+    TRY(c.gemm_routed(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, qlin.w, (int)H, c.f("S/ll_pre"), (int)H, qlin.b));
     for (int h = 0; h < NH; ++h) {
         const std::string q = hs.name(h);
         TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, pooled.gamma[c.li(h)], pooled.beta[c.li(h)], nullptr, 1.f,
@@ -704,9 +730,9 @@ int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& 
     }
     // every head of a category applies pooled_linear_l to the same pooled rows: their d_pre meet before one dW / dx
     for (int r = 1; r < hs.nt; ++r) TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * r * SH, 2 * SH, c.st));
-    TRY(acc.weight(g_pooled.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
-    TRY(c.gemm(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, pooled.w, (int)H, c.f("d_pooled"), (int)D));
-    return fc_bwd(c, acc, "d_llpre", c.f("S/lft"), NH * Bn, H, H, qlin, g_qlin, c.f("d_lft"));
+    TRY(acc.weight(PREC_ROUTED, g_pooled.w, c.f("S/pooled"), (int)D, c.f("d_vlpre"), (int)H, D, H, 2 * Bn));
+    TRY(c.gemm_routed(0, 1, 2 * Bn, D, H, c.f("d_vlpre"), (int)H, pooled.w, (int)H, c.f("d_pooled"), (int)D));
+    return fc_bwd(c, acc, PREC_ROUTED, "d_llpre", c.f("S/lft"), NH * Bn, H, H, qlin, g_qlin, c.f("d_lft"));
 }
 
 }  // namespace
@@ -743,7 +769,7 @@ int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t
     const int64_t B = d.B, R = d.R, D = d.D, H = d.H;
     const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
     ProbeScope ps("pt.v_adapt.fwd", c.st);
-    TRY(c.gemm(0, 0, B * R, H, D, bt->image_ft, (int)D, va.w, (int)H, c.f("va_pre"), (int)H, va.b));
+    TRY(c.gemm_routed(0, 0, B * R, H, D, bt->image_ft, (int)D, va.w, (int)H, c.f("va_pre"), (int)H, va.b));
     for (int k = 0; k < (ln_shared ? 1 : 2); ++k) {
         const std::string p = std::string(KIND[k]) + "/";
         TRY(vqa_ln_act_fwd(c.f("va_pre"), va.gamma[k], va.beta[k], nullptr, 1.f, c.f(p + "va"), c.f(p + "va_mean"),
@@ -775,7 +801,7 @@ int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vq
         }
         TRY(vqa_add_inplace(c.f("d_vapre"), c.f("d_vapre1"), B * R * H, c.st));
     }
-    return acc.weight(g_va.w, bt->image_ft, (int)D, c.f("d_vapre"), (int)H, D, H, B * R);
+    return acc.weight(PREC_ROUTED, g_va.w, bt->image_ft, (int)D, c.f("d_vapre"), (int)H, D, H, B * R);
 }
 
 // forward of the variable-head-set model on the layout L; va != NULL: with the v_adapt layer (vqa_pretrain_adapt_*)
@@ -800,16 +826,16 @@ int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const
         ProbeScope ps_h("pt.heads.fwd", c.st);
         TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l, pm.width));
         TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
-        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
-                   P->joint_fc.b));
+        TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"),
+                          (int)(2 * H), P->joint_fc.b));
         for (int h = 0; h < NH; ++h) {
             const std::string q = hs.name(h);
             TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[c.li(h)], P->joint_fc.beta[c.li(h)],
                                joint_keep(*bx, h & 1, hs.type[h >> 1]), d->keep_joint, c.f("S/j") + h * SJ,
                                c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0, c.st));
         }
-        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
-                   P->classifier.b));
+        TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
+                          P->classifier.b));
         for (int h = 0; h < NH; ++h) {
             const int k = h & 1, r = h >> 1;
             const std::string p = std::string(KIND[k]) + "/";
@@ -858,16 +884,16 @@ int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, cons
     if (phases & 1) {
         ProbeScope ps_h("pt.heads.bwd", c.st);
         const int64_t SH = Bn * H, SJ = Bn * 2 * H;
-        TRY(acc.weight(G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
+        TRY(acc.weight(PREC_ROUTED, G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
         TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G->classifier.b));
-        TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
+        TRY(c.gemm_routed(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
         for (int h = 0; h < NH; ++h) {
             const std::string q = hs.name(h);
             TRY(ln_bwd(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, P->joint_fc, G->joint_fc, c.li(h), (int)n, 0,
                        c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), joint_keep(*bx, h & 1, hs.type[h >> 1]),
                        d->keep_joint, c.f("d_jpre") + h * SJ));
         }
-        TRY(fc_bwd(c, acc, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, P->joint_fc, G->joint_fc, c.f("d_jin")));
+        TRY(fc_bwd(c, acc, PREC_ROUTED, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, P->joint_fc, G->joint_fc, c.f("d_jin")));
         TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
         TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l, va ? d->H : 0));
     }
@@ -1078,10 +1104,10 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
         const int64_t SJ = Bn * 2 * H, SA = Bn * A;
         ProbeScope ps_h("pt.heads.fwd", c.st);
         TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l));
-        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/vl"), (int)H, P->joint_v.w, (int)(2 * H), c.f("S/jv_pre"), (int)(2 * H),
-                   P->joint_v.b));
-        TRY(c.gemm(0, 0, NH * Bn, 2 * H, H, c.f("S/ll"), (int)H, P->joint_l.w, (int)(2 * H), c.f("S/jl_pre"), (int)(2 * H),
-                   P->joint_l.b));
+        TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/vl"), (int)H, P->joint_v.w, (int)(2 * H), c.f("S/jv_pre"),
+                          (int)(2 * H), P->joint_v.b));
+        TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/ll"), (int)H, P->joint_l.w, (int)(2 * H), c.f("S/jl_pre"),
+                          (int)(2 * H), P->joint_l.b));
         for (int h = 0; h < NH; ++h) {
             const int k = h & 1, t = hs.type[h >> 1];
             const std::string q = hs.name(h);
@@ -1092,10 +1118,10 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
                                d->keep_joint, c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"), (int)B, (int)n,
                                (int)(2 * H), 0, c.st));
         }
-        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/jv"), (int)(2 * H), P->classifier_v.w, (int)A, c.f("S/zv"), (int)A,
-                   P->classifier_v.b));
-        TRY(c.gemm(0, 0, NH * Bn, A, 2 * H, c.f("S/jl"), (int)(2 * H), P->classifier_l.w, (int)A, c.f("S/zl"), (int)A,
-                   P->classifier_l.b));
+        TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jv"), (int)(2 * H), P->classifier_v.w, (int)A, c.f("S/zv"),
+                          (int)A, P->classifier_v.b));
+        TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jl"), (int)(2 * H), P->classifier_l.w, (int)A, c.f("S/zl"),
+                          (int)A, P->classifier_l.b));
         // every head's loss in one launch; the report reads the stats blocks in key order
         vqa_softmax_pair_t pr[VQA_SOFTMAX_PAIR_MAX] = {};
         const float* st_by_key[2][3][2] = {};
@@ -1153,9 +1179,9 @@ extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* d
              &P->joint_l, &G->joint_l}};
         for (int v = 0; v < 2; ++v) {
             const Branch& b = br[v];
-            TRY(acc.weight(b.cG->w, c.f(b.j), (int)(2 * H), c.f(b.dz), (int)A, 2 * H, A, NH * Bn));
+            TRY(acc.weight(PREC_ROUTED, b.cG->w, c.f(b.j), (int)(2 * H), c.f(b.dz), (int)A, 2 * H, A, NH * Bn));
             TRY(acc.colsum(c.f(b.dz), NH * Bn, A, (int)A, b.cG->b));
-            TRY(c.gemm(0, 1, NH * Bn, 2 * H, A, c.f(b.dz), (int)A, b.cP->w, (int)A, c.f(b.dj), (int)(2 * H)));
+            TRY(c.gemm_routed(0, 1, NH * Bn, 2 * H, A, c.f(b.dz), (int)A, b.cP->w, (int)A, c.f(b.dj), (int)(2 * H)));
             for (int h = 0; h < NH; ++h) {
                 const int k = h & 1, t = hs.type[h >> 1];
                 const std::string q = hs.name(h) + b.tag;
@@ -1163,7 +1189,7 @@ extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* d
                              c.f(b.jpre) + h * SJ, c.f(q + "_mean"), c.f(q + "_rstd"),
                              v == 0 ? joint_keep(bn->base, k, t) : noc_lmask(bn, k, t), d->keep_joint, c.f(b.djpre) + h * SJ));
             }
-            TRY(fc_bwd(c, acc, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, *b.jP, *b.jG, c.f(b.din)));
+            TRY(fc_bwd(c, acc, PREC_ROUTED, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, *b.jP, *b.jG, c.f(b.din)));
         }
         TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l));
     }

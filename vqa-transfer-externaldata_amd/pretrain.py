@@ -200,20 +200,31 @@ def add_context_sort(batch):
     return batch
 
 
+PRECISIONS = ("f32", "bf16")      # PretrainEngine(precision=...): "bf16" sets VQA_FLAG_BF16_GEMM
+
+
 def _pad4(n):
     return (n + 3) // 4 * 4
 
 
 class PretrainEngine:
     def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
-                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False):
+                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False, precision="f32"):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
         variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint.
         heads: the head set (MODEL_HEADS); with 'ew', n_ctx = the enwiki context vocabulary and every batch carries
         '<kind>_blank_fill/enwiki_context' [B,n,Lc] and '..._len' [B,n].
         noc: the "no composition" model of that head set (NOC_MODEL_HEADS; vqa_pretrain_noc_*).  Its head set (bf, ws)
         equals cfg-5's, so the flag and not the head set selects it.
-        adapt: the adapted-memory model (ADAPT_MODEL_HEADS; vqa_pretrain_adapt_*), likewise selected by the flag."""
+        adapt: the adapted-memory model (ADAPT_MODEL_HEADS; vqa_pretrain_adapt_*), likewise selected by the flag.
+        precision="bf16": opt-in mixed precision -- forward, dW and dx of pooled_linear_l, q_linear_l, joint_fc and the
+        classifier (noc: joint_v / joint_l / classifier_v / classifier_l; adapt: also v_adapt) multiply bf16-rounded
+        operands with f32 accumulation (ops.gemm_bf16); both encoders, wordset_ft, the box layers and everything that is
+        not a GEMM stay f32 (include/vqa_hot.h, VQA_FLAG_BF16_GEMM).  Every head set, noc and adapt.  Parameters,
+        gradients, Adam slots, state_dict() and the DP buckets are those of "f32": checkpoints are interchangeable."""
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
+        self.precision = precision
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("PretrainEngine needs a GPU (no CPU fallback)")
@@ -282,7 +293,8 @@ class PretrainEngine:
         self._g_struct = self._param_struct(self.grads)
 
     def _flags(self):
-        return (_lib.FLAG_DETERMINISTIC if self.deterministic else 0) | (_lib.FLAG_SHARED_LN if self.ln_shared else 0)
+        return (_lib.FLAG_DETERMINISTIC if self.deterministic else 0) | (_lib.FLAG_SHARED_LN if self.ln_shared else 0) | \
+            (_lib.FLAG_BF16_GEMM if self.precision == "bf16" else 0)
 
     # ------------------------------------------------------------------ C-ABI plumbing
     def make_keep_masks(self, B, seed, step, row_offset=0, global_rows=None):

@@ -65,6 +65,8 @@ class Trainer(object):
         if self.rank == 0:
             os.makedirs(self.train_dir, exist_ok=True)
             log.infov("Train Dir: %s", self.train_dir)
+            log.infov("Model: %s, batch size %d, precision %s", config.model_type, config.batch_size,
+                      getattr(config, "precision", "f32"))
         self.batch_size = config.batch_size
         # Input side (not in the reference, whose sequential py_func pipeline fed a 2018 GPU): the feature tables of
         # both splits stay in HBM and batches carry image indices (features_on_device), batches are assembled by
@@ -247,6 +249,10 @@ def build_parser():
     parser.add_argument("--ln_shared", type=int, default=1,
                         help="1: one LayerNorm per shared fc_layer scope (what TF 1.x builds); 0: one per call site; "
                              "a --checkpoint's variable names override this")
+    parser.add_argument("--precision", type=str, default="f32", choices=["f32", "bf16"],
+                        help="bf16: the shared head layers' products (pooled_linear_l, q_linear_l, joint, classifier, "
+                             "v_adapt) with bf16 operands in the matrix unit, f32 master weights and accumulation; the "
+                             "encoders stay f32 (not in the reference; checkpoints are those of f32)")
     parser.add_argument("--input_workers", type=int, default=4, help="forked batch producers (0: in-process)")
     parser.add_argument("--input_prefetch", type=int, default=2, help="batches assembled ahead of the step")
     return parser

@@ -314,6 +314,35 @@ int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const float* qv,
                           const float* w, const uint8_t* keepmask, float keep_prob, float* dv, float* dqv,
                           float* part_dw, float* part_db, int B, int rep, int R, int H, int D, void* stream);
 
+/* The backward of v_linear_v's LayerNorm and of the attention score as ONE chain, for one query per memory at R == 36,
+ * H == 1024, D == 2048 (vqa_vtail_supported; every entry point below returns VQA_ERR_UNSUPPORTED for another shape and
+ * writes nothing).  With one query the gradient of the score with respect to v_linear_v is rank one per region,
+ * dv[b,r,h] = ds[b,r] * keep[b,r,h]/keep_prob * qv[b,h] * w[h], so it is never materialised:
+ *  vqa_attn_pool_bwd_ds: dpooled [B,D], V [B,R,D], att [B,R] -> ds [B,R] (gradient of the raw scores) and part_db [B],
+ *    bit for bit what vqa_attn_pool_bwd computes on its way; reads neither v nor the keep mask.
+ *  vqa_ln_relu_att_bwd: vqa_ln_relu_bwd of the [R,H] group with dy = dv formed in registers from ds, qv [B,H], w [H] and
+ *    keep_att (u8 [B,R,H], the keep mask of the SCORE, or NULL; the LayerNorm itself has no mask): dpre [B*R,H] and the
+ *    three [B,H] partials hold the bits of vqa_attn_pool_bwd -> vqa_ln_relu_bwd; it also writes the attention backward's
+ *    dqv [B,H] and part_dw [B,H], in that kernel's summation order: the same bits.  All partials are required.
+ *  vqa_colsum_vtail: the chain's five parameter-gradient reductions (four [M,N] partial arrays and the [M] vector
+ *    part_db) in one pair of launches; every output keeps the bits of vqa_colsum3 / vqa_colsum.  N % 4 == 0, 16-byte
+ *    aligned X_i / out_i / workspace; workspace >= vqa_colsum_vtail_workspace_floats(M, N).
+ *  vqa_vtail_set_mode: which path vqa_fusion_backward takes where the chain applies (single stream, not
+ *    VQA_MODEL_ADAPT, v_linear_v and the score trainable): 0 = the separate calls, 1 = the chain above (default);
+ *    -1 = back to the default (the environment variable VQA_HOT_VTAIL, else 1).  Returns the mode now in force. */
+int vqa_vtail_supported(int rep, int R, int H, int D);
+int vqa_vtail_set_mode(int mode);
+int vqa_attn_pool_bwd_ds(const float* dpooled, const float* V, const float* att, float* ds, float* part_db, int B, int rep,
+                         int R, int H, int D, void* stream);
+int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
+                        const float* pre, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, float* dqv, float* part_dw,
+                        int B, int rep, int R, int H, int D, void* stream);
+int64_t vqa_colsum_vtail_workspace_floats(int M, int N);
+int vqa_colsum_vtail(const float* X0, const float* X1, const float* X2, const float* X3, const float* Xb, int M, int N,
+                     float* out0, float* out1, float* out2, float* out3, float* outb, float* workspace,
+                     int64_t workspace_floats, void* stream);
+
 /* --------------------------------------------------------------- a11 / K11
  * sigmoid-CE loss, argmax, VQA scores (vqa/model_vlmap_answer.py:192-288).
  * Per sample stats[b, VQA_STAT_*]; dz = (sigmoid(z)-t)*(loss_mask?)/B_norm when

@@ -219,6 +219,12 @@ SIGNATURES = {
     "vqa_attn_pool_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_fwd_rep": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_bwd_rep": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_vtail_supported": (_I, [_I, _I, _I, _I]),
+    "vqa_vtail_set_mode": (_I, [_I]),
+    "vqa_attn_pool_bwd_ds": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_ln_relu_att_bwd": (_I, [_P, _P, _P, _P, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
+    "vqa_colsum_vtail_workspace_floats": (_L, [_I, _I]),
+    "vqa_colsum_vtail": (_I, [_P] * 5 + [_I, _I] + [_P] * 6 + [_L, _P]),
     "vqa_loss_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _I, _I, _P]),
     "vqa_loss2_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vqa_rowmin_mask_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),

@@ -701,6 +701,66 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     }
 }
 
+// Phases 1-3 of attn_pool_bwd_fast_kernel<1, ., 2048> on their own (vqa_attn_pool_bwd_ds): dpooled staged in LDS, datt
+// with two V rows per wave in flight, the softmax backward in one wave -- the same expressions in the same order, so ds
+// and part_db hold the bits of that kernel.  The score gradient ds [B,R] leaves the CU instead of dv [B,R,H]: dv is
+// ds[b,r] x (keep/keep_prob * qv * w), which the LayerNorm backward of v_linear_v forms in registers
+// (layernorm.hip: ln_att_bwd_reg_kernel), so neither v nor the keep mask is read here.
+__global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_ds_kernel(const float* __restrict__ dpooled,
+                                                                       const float* __restrict__ V,
+                                                                       const float* __restrict__ att,
+                                                                       float* __restrict__ ds_out,
+                                                                       float* __restrict__ part_db, int R) {
+    constexpr int D = 2048, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64;
+    static_assert(D4 == BWD_THREADS, "dpooled is staged with one float4 per thread");
+    __shared__ __attribute__((aligned(16))) float lds[D + 40];  // dp[D] | ds[40]
+    float* ds = lds + D;
+    const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t q0 = (int64_t)mem;
+    f32x4v* dp4 = reinterpret_cast<f32x4v*>(lds);
+    {
+        const f32x4v* g4 = reinterpret_cast<const f32x4v*>(dpooled + q0 * D);
+        const f32x4v t = g4[threadIdx.x];
+        dp4[threadIdx.x] = t;
+    }
+    __syncthreads();
+    const f32x4v* Vb4 = reinterpret_cast<const f32x4v*>(V + (int64_t)mem * R * D);
+    for (int r0 = wave; r0 < R; r0 += 2 * NW) {
+        const int rb = min(r0 + NW, R - 1);
+        const bool okb = r0 + NW < R;
+        f32x4v xa[DL], xb[DL];
+#pragma unroll
+        for (int k = 0; k < DL; ++k) {
+            xa[k] = Vb4[(int64_t)r0 * D4 + lane + 64 * k];
+            xb[k] = Vb4[(int64_t)rb * D4 + lane + 64 * k];
+        }
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int k = 0; k < DL; ++k) {
+            const f32x4v g = dp4[lane + 64 * k];
+            a += xa[k].x * g.x + xa[k].y * g.y + xa[k].z * g.z + xa[k].w * g.w;
+            b += xb[k].x * g.x + xb[k].y * g.y + xb[k].z * g.z + xb[k].w * g.w;
+        }
+        a = wave_sum(a);
+        b = wave_sum(b);
+        if (lane == 0) {
+            ds[r0] = a;
+            if (okb) ds[rb] = b;
+        }
+    }
+    __syncthreads();
+    // softmax backward: ds = att * (datt - sum(att*datt)); R <= 40 < 64: one lane per region
+    if (wave == 0) {
+        const float a = lane < R ? att[q0 * R + lane] : 0.f;
+        const float d = lane < R ? ds[lane] : 0.f;
+        const float dot = wave_sum(a * d);
+        const float g = a * (d - dot);
+        if (lane < R) ds_out[q0 * R + lane] = g;
+        const float tot = wave_sum(g);
+        if (lane == 0) part_db[q0] = tot;
+    }
+}
+
 int g_attn_fast = 1;   // tuning / A-B switch (vqa_attn_set_fast)
 
 }  // namespace
@@ -851,6 +911,24 @@ extern "C" int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const
     else
         hipLaunchKernelGGL(attn_pool_bwd_kernel<8>, dim3(B), dim3(BWD_THREADS), lds_for(8), st, dpooled, v, qv, V, att, w,
                            keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+// The chain v_linear_v's LayerNorm -> attention score and its gradient at the one shape of the register-resident
+// LayerNorm kernels and the fast attention kernels: one query per memory, 36 regions, 1024 hidden units, 2048 features.
+extern "C" int vqa_vtail_supported(int rep, int R, int H, int D) {
+    return (rep == 1 && R == 36 && H == 1024 && D == 2048) ? 1 : 0;
+}
+
+extern "C" int vqa_attn_pool_bwd_ds(const float* dpooled, const float* V, const float* att, float* ds, float* part_db,
+                                    int B, int rep, int R, int H, int D, void* stream) {
+    VQA_REQUIRE(dpooled && V && att && ds && part_db && B >= 0, VQA_ERR_ARG);
+    VQA_REQUIRE(vqa_vtail_supported(rep, R, H, D), VQA_ERR_UNSUPPORTED);
+    VQA_REQUIRE(vqa_aligned16(dpooled) && vqa_aligned16(V), VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    hipLaunchKernelGGL(attn_pool_bwd_ds_kernel, dim3(B), dim3(BWD_THREADS), 0, (hipStream_t)stream, dpooled, V, att, ds,
+                       part_db, R);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }

@@ -137,6 +137,7 @@ Layout make_layout(const vqa_dims_t& d) {
     L.add("d_qv", B * H); L.add("d_pre_qv", B * H);
     L.add("part_a", B * 2 * H); L.add("part_b", B * 2 * H); L.add("part_c", B * 2 * H);
     L.add("part_dw", B * H); L.add("part_db", B);
+    L.add("ds", B * R);          // gradient of the raw attention scores (the fused v_linear_v chain, vtail_mode)
     L.add("dxp", T * B * 3 * H);
     L.add("d_rh", B * H);
     L.add("dx_embed", T * B * W);
@@ -174,6 +175,7 @@ Layout make_layout(const vqa_dims_t& d) {
     cw = max64(cw, vqa_colsum_workspace_floats((int)B, (int)A));
     cw = max64(cw, vqa_colsum_workspace_floats((int)B, (int)W));
     cw = max64(cw, vqa_colsum_workspace_floats((int)(B * T), (int)H));
+    cw = max64(cw, (vqa_colsum_vtail_workspace_floats((int)B, (int)H) + 2) / 3);
     if (d.model_type == VQA_MODEL_LEGACY_VQA)
         cw = max64(cw, max64(max64(vqa_colsum_workspace_floats((int)(T * B), (int)(4 * H)), vqa_colsum_workspace_floats((int)(d.La * A), (int)(4 * H))),
                              vqa_colsum_workspace_floats((int)A, 1)));
@@ -628,6 +630,24 @@ extern "C" int vqa_fusion_tensor(const vqa_dims_t* dims, const char* name, int64
 }
 
 namespace {
+// The backward of v_linear_v's LayerNorm and of the attention score as one chain (vqa_attn_pool_bwd_ds ->
+// vqa_ln_relu_att_bwd -> vqa_colsum_vtail) where it applies; 0 = the separate calls.  VQA_HOT_VTAIL / vqa_vtail_set_mode.
+int g_vtail_mode = -1;
+inline int vtail_mode() {
+    if (g_vtail_mode < 0) {
+        const char* e = getenv("VQA_HOT_VTAIL");
+        g_vtail_mode = (e != nullptr && atoi(e) == 0) ? 0 : 1;
+    }
+    return g_vtail_mode;
+}
+}  // namespace
+
+extern "C" int vqa_vtail_set_mode(int mode) {
+    g_vtail_mode = mode < 0 ? -1 : (mode ? 1 : 0);
+    return vtail_mode();
+}
+
+namespace {
 inline bool visual_late_enabled() {       // VQA_HOT_VISUAL_LATE=0: the round-1 order (A/B)
     static const bool v = [] { const char* e = getenv("VQA_HOT_VISUAL_LATE"); return e == nullptr || atoi(e) != 0; }();
     return v;
@@ -1041,7 +1061,38 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
     } else {
     TRY(ll_bwd(mt == VQA_MODEL_BI ? c.f("q_L_ft") : h, dh));
     }
-    // attention + pooling
+    // attention + pooling, and v_linear_v behind it.  With one query per memory d_v is rank one per region, so on one
+    // stream the chain runs fused ("The fused v_linear_v chain"): the attention backward stops at the score
+    // gradient ds, v_linear_v's LayerNorm backward forms d_v in registers and delivers d_qv and the score's weight partials,
+    // and one pair of launches reduces the five parameter gradients.  d_v is not written on this path.  The separate calls
+    // stay for the side stream (VQA_HOT_OVERLAP=1), for vlmap_answer_adapt (a second consumer of att_score and a 1024-wide
+    // memory), for frozen layers and for every other shape.
+    Side& sd = side_stream();
+    const bool vtail = vtail_mode() != 0 && !sd.ok && mt != VQA_MODEL_ADAPT && vqa_vtail_supported(1, (int)R, (int)H, (int)Dp) == 1 &&
+                       G->v_linear_v.w != nullptr && G->v_linear_v.gamma != nullptr && G->v_linear_v.beta != nullptr &&
+                       G->v_linear_v.b != nullptr && G->score.w != nullptr && G->score.b != nullptr && vqa_aligned16(c.f("d_pooled")) &&
+                       vqa_aligned16(P->score.w) && vqa_aligned16(P->v_linear_v.gamma) && vqa_aligned16(P->v_linear_v.beta) &&
+                       (bt->keep_att == nullptr || (reinterpret_cast<uintptr_t>(bt->keep_att) & 3u) == 0) &&
+                       vqa_aligned16(G->v_linear_v.gamma) && vqa_aligned16(G->v_linear_v.beta) && vqa_aligned16(G->v_linear_v.b) &&
+                       vqa_aligned16(G->score.w);
+    if (vtail) {
+        {
+            ProbeScope ps("attn_pool.bwd", c.st);
+            TRY(vqa_attn_pool_bwd_ds(c.f("d_pooled"), c.f("V_ft"), c.f("att_score"), c.f("ds"), c.f("part_db"), (int)B, 1, (int)R,
+                                     (int)H, (int)D, c.st));
+        }
+        {
+            ProbeScope ps("v_linear_v.ln_bwd", c.st);
+            TRY(vqa_ln_relu_att_bwd(c.f("ds"), c.f("q_linear_v"), P->score.w, bt->keep_att, dims->keep_att, c.f("pre_v"),
+                                    c.f("mean_v"), c.f("rstd_v"), P->v_linear_v.gamma, P->v_linear_v.beta, c.f("d_pre_v"), c.part(0),
+                                    c.part(1), c.part(2), c.f("d_qv"), c.f("part_dw"), (int)B, 1, (int)R, (int)H, (int)D, c.st));
+            TRY(vqa_colsum_vtail(c.part(0), c.part(1), c.part(2), c.f("part_dw"), c.f("part_db"), (int)B, (int)H,
+                                 G->v_linear_v.gamma, G->v_linear_v.beta, G->v_linear_v.b, G->score.w, G->score.b, c.colsum_ws(),
+                                 c.colsum_ws_floats(), c.st));
+        }
+        ProbeScope ps("v_linear_v.dw_gemm", c.st);
+        TRY(gemm(c, 1, 0, D, H, B * R, c.f("V_ft"), (int)D, c.f("d_pre_v"), (int)H, G->v_linear_v.w, (int)H));  // dW = x^T * d_pre
+    } else {
     {
     ProbeScope ps("attn_pool.bwd", c.st);
     TRY(vqa_attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.f(mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
@@ -1060,11 +1111,11 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         TRY(colsum(c, c.f("part_dw"), B, H, (int)H, G->score.w));
         TRY(colsum(c, c.f("part_db"), B, 1, 1, G->score.b));
     }
+    }
     // v_linear_v: parameters only (V_ft is an input).  77 GFLOP of dW on the side stream, beside
     // the latency-bound back-propagation through time below.
-    Side& sd = side_stream();
-    const bool forked = fork_side(c, sd);
-    {
+    const bool forked = !vtail && fork_side(c, sd);
+    if (!vtail) {
         Ctx cv{*dims, L, c.ws, forked ? sd.s : c.st, forked ? 1 : 0};
         TRY(fc_ln_relu_bwd(cv, cv.f("d_v"), cv.f("V_ft"), B * R, D, H, P->v_linear_v, &G->v_linear_v, (int)R, "pre_v",
                            "mean_v", "rstd_v", nullptr, 1.f, "d_pre_v", nullptr, false));

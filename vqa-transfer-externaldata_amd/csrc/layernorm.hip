@@ -368,6 +368,139 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_bwd_reg_kernel(
     }
 }
 
+// ln_bwd_reg_kernel<9, 1, false, true> for v_linear_v behind the attention score, with dy GENERATED instead of loaded
+// (vqa_ln_relu_att_bwd).  With one query per memory the gradient of the score with respect to v_linear_v is rank one per
+// region: dy[r,h] = ds[r] * keep[r,h]/keep_prob * qv[h] * w[h] (attention.hip: attn_pool_bwd_fast_kernel, whose grouping
+// of the products is kept, so dy has the bits of the dv that kernel writes), so the [R,H] gradient block is neither
+// written by the attention backward nor read here -- ds [R], qv [H], w [H] and the keep mask of the score replace it.
+// The first pass holds ln = xhat * gamma + beta anyway, so it also forms S[h] = sum_r g[r,h] * relu(ln[r,h]) with
+// g = ds * keep/keep_prob and from it the attention backward's dqv = S * w and part_dw = S * qv.  S is summed in the
+// attention kernel's order, even rows 0, 2, ... in one chain, odd rows in another, then even + odd, so dqv and part_dw
+// hold that kernel's bits too: row lanes 2 and 3 hand g and relu(ln) of each row to lanes 0 and 1 through LDS.
+// Everything downstream of dy (dpre, the gamma / beta / bias partials) keeps the thread mapping and order of
+// ln_bwd_reg_kernel.
+// `rpt` is RPT, as a kernel argument: `if (i < rpt)` puts every row's chain of pass 1 into a basic block of its own.
+// In one block the instruction selector is free to order the 36 elements' chains breadth first -- every mask factor,
+// ln and dln at once beside x and dxh -- and the kernel spills 30 to 70 registers; row by row a row's mask word and ds
+// die as its four dxh appear.
+__device__ __forceinline__ float mul_rounded(float a, float b) {      // a product that no later add absorbs into an fma
+#pragma clang fp contract(off)
+    return a * b;
+}
+template <bool MASK>
+__global__ __launch_bounds__(REG_CUT * REG_RY) void ln_att_bwd_reg_kernel(
+    const float* __restrict__ ds, const float* __restrict__ qv, const float* __restrict__ w,
+    const uint8_t* __restrict__ keep_att, float inv_keep, const float* __restrict__ pre, const float* __restrict__ mean_in,
+    const float* __restrict__ rstd_in, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ dpre, float* __restrict__ part_dgamma, float* __restrict__ part_dbeta,
+    float* __restrict__ part_dbias, float* __restrict__ dqv, float* __restrict__ part_dw, int rpt) {
+    constexpr int RPT = 9, N4 = REG_CUT, N = N4 * 4, ROWS = REG_RY * RPT;
+    extern __shared__ __attribute__((aligned(16))) float dyn[];  // [2][RY*CUt*4]
+    __shared__ float red[16];
+    // (ry is one value per wave: said so, a row's ds and the row-lane branches below stay in scalar registers)
+    const int g = blockIdx.x, cx = threadIdx.x % REG_CUT, ry = __builtin_amdgcn_readfirstlane(threadIdx.x / REG_CUT);
+    const int64_t base4 = (int64_t)g * ROWS * N4;
+    const f32x4v* p4 = reinterpret_cast<const f32x4v*>(pre) + base4;
+    const unsigned* m4 = MASK ? reinterpret_cast<const unsigned*>(keep_att) + base4 : nullptr;
+    const float invL = 1.f / ((float)ROWS * (float)N);
+    const float mean = mean_in[g], rstd = rstd_in[g];
+    float* buf0 = dyn;
+    float* buf1 = dyn + (size_t)REG_RY * REG_CUT * 4;
+    f32x4v x[RPT], d[RPT];
+    unsigned km[RPT];
+    float dsr[RPT];
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+        const int o = (ry + REG_RY * i) * N4 + cx;
+        x[i] = p4[o];
+        if (MASK) km[i] = m4[o];
+        dsr[i] = ds[(int64_t)g * ROWS + ry + REG_RY * i];
+        d[i] = (f32x4v)(0.f);
+    }
+    const f32x4v ga = reinterpret_cast<const f32x4v*>(gamma)[cx];
+    const f32x4v be = reinterpret_cast<const f32x4v*>(beta)[cx];
+    // v_linear_v as ln_fwd_reg_kernel<9, 1, false, true> stored it.  hipcc contracts that kernel's mean = sum * invL into
+    // the subtraction, x - mean = fma(-sum, invL, x), so its y is not a function of the rounded mean it publishes: the
+    // group's sum is formed again (same thread mapping, same order) and the forward's operations are spelled out below.
+    float xs = 0.f;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) { xs += x[i].x; xs += x[i].y; xs += x[i].z; xs += x[i].w; }
+    const float xsum = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, block_sum(xs, red))));
+    float s1 = 0.f, s2 = 0.f;
+    {
+        const f32x4v qj = reinterpret_cast<const f32x4v*>(qv + (int64_t)g * N)[cx];
+        const f32x4v ww = reinterpret_cast<const f32x4v*>(w)[cx];
+        float cb[4] = {0.f, 0.f, 0.f, 0.f}, cg[4] = {0.f, 0.f, 0.f, 0.f}, S[4] = {0.f, 0.f, 0.f, 0.f};
+        // pass 1 (registers only): d receives dxh = dln * gamma, x is overwritten by xhat
+#pragma unroll
+        for (int i = 0; i < RPT; ++i) {
+            if (i < rpt) {
+                f32x4v gv, rv;      // g and relu(ln) = v_linear_v of row ry + 4i
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float xh = (x[i][j] - mean) * rstd;
+                    const float ln = xh * ga[j] + be[j];
+                    // dy, as the attention backward forms dv: g = ds * (keep * inv_keep), dv = 0 + g * qv * w
+                    float gj = dsr[i];
+                    if (MASK) gj *= (float)((km[i] >> (8 * j)) & 0xFFu) * inv_keep;
+                    gv[j] = gj;
+                    rv[j] = fmaxf(__builtin_fmaf(__builtin_fmaf(-xsum, invL, x[i][j]) * rstd, ga[j], be[j]), 0.f);
+                    float gg = 0.f;
+                    gg += gj * qj[j] * ww[j];
+                    const float dln = ln > 0.f ? gg : 0.f;
+                    const float dxh = dln * ga[j];
+                    s1 += dxh; s2 += dxh * xh; cb[j] += dln; cg[j] += dln * xh;
+                    x[i][j] = xh;
+                    d[i][j] = dxh;
+                }
+                // S in the attention kernel's order: rows 4i + ry (own), then 4i + ry + 2 (the partner's, through LDS);
+                // the two buffers alternate, so one barrier per row separates a buffer's readers from its next writers
+                f32x4v* xch = reinterpret_cast<f32x4v*>((i & 1) ? buf1 : buf0);
+                if (ry >= 2) {
+                    xch[(ry - 2) * REG_CUT + cx] = gv;
+                    xch[ry * REG_CUT + cx] = rv;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) S[j] += gv[j] * rv[j];
+                }
+                __syncthreads();
+                if (ry < 2) {
+                    const f32x4v pg = xch[ry * REG_CUT + cx], pr = xch[(ry + 2) * REG_CUT + cx];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) S[j] += pg[j] * pr[j];
+                }
+            }
+        }
+        col_reduce_store<4>(buf0, cb, part_dbeta + (int64_t)g * N, cx, N4, cx, ry, REG_CUT, REG_RY);
+        col_reduce_store<4>(buf1, cg, part_dgamma + (int64_t)g * N, cx, N4, cx, ry, REG_CUT, REG_RY);
+        // (buf0 was read before the barriers of the second reduction)
+        if (ry == 1) reinterpret_cast<f32x4v*>(buf0)[cx] = (f32x4v){S[0], S[1], S[2], S[3]};
+        __syncthreads();
+        if (ry == 0) {
+            const f32x4v t = (f32x4v){S[0], S[1], S[2], S[3]} + reinterpret_cast<const f32x4v*>(buf0)[cx];   // even + odd rows
+            reinterpret_cast<f32x4v*>(dqv + (int64_t)g * N)[cx] = t * ww;
+            reinterpret_cast<f32x4v*>(part_dw + (int64_t)g * N)[cx] = t * qj;
+        }
+    }
+    const float m1 = block_sum(s1, red) * invL;
+    const float m2 = block_sum(s2, red) * invL;
+    f32x4v* o4 = reinterpret_cast<f32x4v*>(dpre) + base4;
+    float cbias[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+        f32x4v o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            // (ln_bwd_reg_kernel's bias partial is a sum of the rounded dp: hipcc leaves its adds alone there)
+            const float dp = mul_rounded(rstd, d[i][j] - m1 - x[i][j] * m2);
+            o[j] = dp;
+            cbias[j] += dp;
+        }
+        o4[(ry + REG_RY * i) * N4 + cx] = o;
+    }
+    col_reduce_store<4>(buf0, cbias, part_dbias + (int64_t)g * N, cx, N4, cx, ry, REG_CUT, REG_RY);
+}
+
 int g_ln_reg = 1;   // A/B switch (vqa_ln_set_fast)
 
 // register-resident kernels apply (16-byte path, ReLU): 1 = N 1024, rows == 36 (v_linear_v's block per sample);
@@ -699,6 +832,34 @@ extern "C" int vqa_ln_act_bwd(const float* dy, const float* pre, const float* me
     else
         hipLaunchKernelGGL(ln_relu_bwd_kernel<1>, dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd, gamma, beta,
                            keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act);
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+extern "C" int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
+                                   const float* pre, const float* mean, const float* rstd, const float* gamma,
+                                   const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
+                                   float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream) {
+    VQA_REQUIRE(ds && qv && w && pre && mean && rstd && gamma && beta && dpre && part_dgamma && part_dbeta && part_dbias && dqv &&
+                    part_dw && B >= 0,
+                VQA_ERR_ARG);
+    VQA_REQUIRE(keep_att == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
+    VQA_REQUIRE(vqa_vtail_supported(rep, R, H, D), VQA_ERR_UNSUPPORTED);
+    VQA_REQUIRE(vqa_aligned16(qv) && vqa_aligned16(w) && vqa_aligned16(pre) && vqa_aligned16(gamma) && vqa_aligned16(beta) &&
+                    vqa_aligned16(dpre) && vqa_aligned16(part_dgamma) && vqa_aligned16(part_dbeta) && vqa_aligned16(part_dbias) &&
+                    vqa_aligned16(dqv) && vqa_aligned16(part_dw) &&
+                    (keep_att == nullptr || (reinterpret_cast<uintptr_t>(keep_att) & 3u) == 0),
+                VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    const float inv_keep = keep_att ? 1.f / keep_prob : 1.f;
+    const size_t dyn_reg = (size_t)2 * REG_RY * REG_CUT * 4 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    if (keep_att != nullptr)
+        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<true>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
+                           inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw, 9);
+    else
+        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<false>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
+                           inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw, 9);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }

@@ -333,6 +333,32 @@ __global__ __launch_bounds__(256) void colsum3x4_kernel(Colsum3 a, int M, int N,
                  a.acc[blockIdx.z], red);
 }
 
+// the five parameter-gradient reductions behind v_linear_v's LayerNorm and the attention score in one launch
+// (vqa_colsum_vtail): z < 4 one of four [M,N] partial arrays through the 16-byte body, z == 4 the [M] vector part_db
+// through the scalar kernel's sum (its block x == 0, column 0: rows ry, ry + 4, ..., then the four row lanes in order)
+struct Colsum5 { const float* X[5]; float* out[5]; };
+__global__ __launch_bounds__(256) void colsum4x4p1_kernel(Colsum5 a, int M, int N, int ldx, int ldb,
+                                                          int64_t out_stride_rows, int rows_per_chunk) {
+    __shared__ cs4 red[4][64];
+    if (blockIdx.z < 4) {
+        colsum4_body(a.X[blockIdx.z], a.out[blockIdx.z], M, N, ldx, (int64_t)blockIdx.y * out_stride_rows, rows_per_chunk,
+                     0, red);
+        return;
+    }
+    if (blockIdx.x != 0) return;
+    const float* __restrict__ X = a.X[4];
+    float* sred = reinterpret_cast<float*>(red);      // [4]
+    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int m0 = blockIdx.y * rows_per_chunk, m1 = min(M, m0 + rows_per_chunk);
+    float s = 0.f;
+    if (cx == 0) {
+        for (int m = m0 + ry; m < m1; m += 4) s += X[(int64_t)m * ldb];
+        sred[ry] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.out[4][blockIdx.y] = sred[0] + sred[1] + sred[2] + sred[3];
+}
+
 // ------------------------------------------------------------------ dropout keep-mask
 // Counter-based generator (splitmix64 finaliser on seed ^ counter): the mask of
 // element i depends only on (seed, offset + i), so forward, backward and the test
@@ -721,6 +747,43 @@ extern "C" int vqa_colsum3_acc(const float* X0, const float* X1, const float* X2
     Colsum3 p2{{workspace, workspace + zs, workspace + 2 * zs}, {out0, out1, out2}, {a0, a1, a2}};
     VQA_COLSUM3_LAUNCH(1, p2, ch2, N, ch2);
 #undef VQA_COLSUM3_LAUNCH
+    return VQA_OK;
+}
+
+// workspace of vqa_colsum_vtail: four [chunks, N] slabs and one [chunks] vector (padded to a 16-byte multiple)
+extern "C" int64_t vqa_colsum_vtail_workspace_floats(int M, int N) {
+    const int ch = colsum_chunks(std::max(M, 1));
+    return ch > 1 ? (int64_t)ch * (4 * (int64_t)N + 4) : 0;
+}
+
+extern "C" int vqa_colsum_vtail(const float* X0, const float* X1, const float* X2, const float* X3, const float* Xb, int M,
+                                int N, float* out0, float* out1, float* out2, float* out3, float* outb, float* workspace,
+                                int64_t workspace_floats, void* stream) {
+    VQA_REQUIRE(X0 && X1 && X2 && X3 && Xb && out0 && out1 && out2 && out3 && outb && M >= 0 && N > 0, VQA_ERR_ARG);
+    VQA_REQUIRE(N % 4 == 0 && vqa_aligned16(X0) && vqa_aligned16(X1) && vqa_aligned16(X2) && vqa_aligned16(X3) &&
+                    vqa_aligned16(out0) && vqa_aligned16(out1) && vqa_aligned16(out2) && vqa_aligned16(out3) &&
+                    (workspace == nullptr || vqa_aligned16(workspace)),
+                VQA_ERR_ALIGN);
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = colsum_chunks(std::max(M, 1));
+    const int gx = (N / 4 + 63) / 64;
+    Colsum5 a{{X0, X1, X2, X3, Xb}, {out0, out1, out2, out3, outb}};
+    if (ch == 1) {
+        hipLaunchKernelGGL(colsum4x4p1_kernel, dim3(gx, 1, 5), dim3(256), 0, st, a, M, N, N, 1, (int64_t)N, std::max(M, 1));
+        VQA_CHECK_LAUNCH();
+        return VQA_OK;
+    }
+    VQA_REQUIRE(workspace && workspace_floats >= (int64_t)ch * (4 * (int64_t)N + 4), VQA_ERR_WORKSPACE);
+    const int rpc = (int)cdiv(M, ch);
+    const int ch2 = (int)cdiv(M, rpc);
+    const int64_t zs = (int64_t)ch * N;
+    Colsum5 p1{{X0, X1, X2, X3, Xb}, {workspace, workspace + zs, workspace + 2 * zs, workspace + 3 * zs, workspace + 4 * zs}};
+    hipLaunchKernelGGL(colsum4x4p1_kernel, dim3(gx, ch2, 5), dim3(256), 0, st, p1, M, N, N, 1, (int64_t)N, rpc);
+    VQA_CHECK_LAUNCH();
+    Colsum5 p2{{workspace, workspace + zs, workspace + 2 * zs, workspace + 3 * zs, workspace + 4 * zs},
+               {out0, out1, out2, out3, outb}};
+    hipLaunchKernelGGL(colsum4x4p1_kernel, dim3(gx, 1, 5), dim3(256), 0, st, p2, ch2, N, N, 1, (int64_t)N, ch2);
+    VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
 

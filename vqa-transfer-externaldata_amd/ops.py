@@ -141,6 +141,42 @@ def attn_pool_bwd(dpooled, v, qv, V, att, w, keepmask=None, keep_prob=1.0):
     return dv, dqv, colsum(pdw), colsum(pdb)
 
 
+def attn_pool_bwd_ds(dpooled, V, att):
+    """The attention backward up to the gradient of the raw scores: ds [B,R] and the per-sample score-bias partial [B]
+    (one query per memory, R 36, H 1024, D 2048: vqa_vtail_supported)."""
+    lib = _lib.load()
+    B, R, D = V.shape
+    ds, pdb = _f32(B, R, like=V), _f32(B, like=V)
+    _lib.check(lib.vqa_attn_pool_bwd_ds(_p(dpooled), _p(V), _p(att), _p(ds), _p(pdb), B, 1, R, 1024, D, _st(V)),
+               "vqa_attn_pool_bwd_ds")
+    return ds, pdb
+
+
+def ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keepmask=None, keep_prob=1.0):
+    """v_linear_v's LayerNorm + ReLU backward with dy = ds x (keep / keep_prob * qv * w) formed in registers; also the
+    attention backward's dqv and score-weight partial.  pre [B,R,H] -> dpre, (part_dgamma, part_dbeta, part_dbias) [B,H],
+    dqv [B,H], part_dw [B,H]."""
+    lib = _lib.load()
+    B, R, H = pre.shape
+    dpre = torch.empty_like(pre)
+    pg, pb, pbias, dqv, pdw = (_f32(B, H, like=pre) for _ in range(5))
+    _lib.check(lib.vqa_ln_relu_att_bwd(_p(ds), _p(qv), _p(w), _p(keepmask), keep_prob, _p(pre), _p(mean), _p(rstd),
+                                       _p(gamma), _p(beta), _p(dpre), _p(pg), _p(pb), _p(pbias), _p(dqv), _p(pdw), B, 1, R,
+                                       H, 2048, _st(pre)), "vqa_ln_relu_att_bwd")
+    return dpre, (pg, pb, pbias), dqv, pdw
+
+
+def colsum_vtail(X0, X1, X2, X3, Xb):
+    """Column sums of four equally shaped [M,N] matrices and the sum of one [M] vector in one pair of launches."""
+    lib = _lib.load()
+    M, N = X0.shape
+    outs = [_f32(N, like=X0) for _ in range(4)] + [_f32(1, like=X0)]
+    ws = _f32(max(int(lib.vqa_colsum_vtail_workspace_floats(M, N)), 4), like=X0)
+    _lib.check(lib.vqa_colsum_vtail(_p(X0), _p(X1), _p(X2), _p(X3), _p(Xb), M, N, *[_p(o) for o in outs], _p(ws),
+                                    ws.numel(), _st(X0)), "vqa_colsum_vtail")
+    return outs
+
+
 def loss_fwd(z, target, masks, use_train_mask=True, inv_batch=None, want_dz=True):
     lib = _lib.load()
     B, A = z.shape

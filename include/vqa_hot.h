@@ -925,6 +925,26 @@ int vqa_im2col_nhwc(const float* x, int B, int Hi, int Wi, int Ci, int kh, int k
 int vqa_maxpool3x3s2_same_nhwc(const float* x, int B, int Hi, int Wi, int C, float* y, void* stream);
 /* resnet_utils.subsample (1x1 max-pool with stride = strided slicing) */
 int vqa_subsample_nhwc(const float* x, int B, int Hi, int Wi, int C, int factor, float* y, void* stream);
+/* The extractor's opt-in bf16 mode (vfeat.ResNetV1(precision="bf16")): the trunk after the stem keeps
+ * its activations as bf16 NHWC in HBM.
+ *   y = [relu]( conv(x, w) * scale[co] + shift[co] + residual )
+ * x bf16 [B,Hi,Wi,Ci]; w bf16 [Co][kh*kw*Ci] (k contiguous: the HWIO filter rounded to nearest even and packed once on the
+ * host); scale / shift f32 [Co] (may be NULL); residual bf16 [B,Ho,Wo,Co] or NULL; y bf16 [B,Ho,Wo,Co], or f32 when
+ * y_is_f32 != 0.  Products on v_mfma_f32_32x32x16_bf16, f32 accumulation; scale, shift, residual and ReLU in f32; a bf16
+ * result is rounded once, to nearest even, on store, an f32 result is stored unrounded.  Taps outside the image read as
+ * zero.  One implicit-GEMM kernel for every filter size (1x1 = one tap).
+ * VQA_ERR_ALIGN: Ci % 32 != 0 or a pointer that is not 16-byte aligned; VQA_ERR_UNSUPPORTED: Co % 8 != 0 or an operand of
+ * 4 GiB or more; VQA_ERR_ARG: NULL x / w / y or a non-positive size. */
+int vqa_conv2d_nhwc_bf16(const void* x, int B, int Hi, int Wi, int Ci, const void* w, int kh, int kw, int Co, int stride,
+                         int pad_t, int pad_l, int Ho, int Wo, const float* scale, const float* shift, const void* residual,
+                         int relu, void* y, int y_is_f32, void* stream);
+/* tuning: tile of vqa_conv2d_nhwc_bf16 (-1 = chosen by shape, the default; 0 = 128x128, 1 = 128x64, 2 = 64x64, all 4
+ * waves); process-wide, like vqa_conv_set_config. */
+int vqa_conv_bf16_set_config(int cfg);
+/* vqa_maxpool3x3s2_same_nhwc with x f32 and y bf16 (= the f32 max-pool rounded to nearest even, bit for bit); C % 8 == 0 */
+int vqa_maxpool3x3s2_same_nhwc_bf16(const float* x, int B, int Hi, int Wi, int C, void* y, void* stream);
+/* vqa_subsample_nhwc on bf16 x and y; C % 8 == 0 */
+int vqa_subsample_nhwc_bf16(const void* x, int B, int Hi, int Wi, int C, int factor, void* y, void* stream);
 /* tf.image.crop_and_resize (bilinear, extrapolation 0): boxes [n,4] = normalised [y1,x1,y2,x2],
  * box_ind i32[n] -> out [n,crop_h,crop_w,C]   (modules.roi_pool, vlmap/modules.py:204-216) */
 int vqa_crop_and_resize_nhwc(const float* fmap, int B, int H, int W, int C, const float* boxes,

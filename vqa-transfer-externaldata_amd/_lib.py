@@ -258,6 +258,10 @@ SIGNATURES = {
     "vqa_graph_destroy": (_I, [_P]),
     "vqa_stream_is_capturing": (_I, [_P]),
     "vqa_conv2d_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "vqa_conv2d_nhwc_bf16": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
+    "vqa_conv_bf16_set_config": (_I, [_I]),
+    "vqa_maxpool3x3s2_same_nhwc_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "vqa_subsample_nhwc_bf16": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "vqa_im2col_nhwc": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _I, _P]),
     "vqa_pad_c3c4_nhwc": (_I, [_P, _I, _I, _I, C.POINTER(C.c_float), _P, _P]),
     "vqa_maxpool3x3s2_same_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _P]),

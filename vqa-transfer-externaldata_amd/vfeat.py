@@ -7,6 +7,10 @@ only, as in the reference extraction path (is_training=False -> BatchNorm uses m
 statistics, folded here to per-channel scale/shift).  Variable names are slim's
 (`resnet_v1_50/block1/unit_1/bottleneck_v1/conv1/weights`, `.../BatchNorm/gamma` ...), the
 contract of data/nets/resnet_v1_50.ckpt.  Layout NHWC, fp32, convolutions on the f32 MFMA.
+
+precision="bf16" (opt-in): the trunk after the stem keeps bf16 activations in HBM and runs its
+convolutions on the bf16 MFMA with f32 accumulation (vqa_conv2d_nhwc_bf16); the stem, the last layer's output and
+everything downstream stay f32.
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ LAYERS_BN_EPS = 1e-3                        # tf.contrib.layers.batch_norm defau
 BLOCKS_R50_B3 = [("block1", 64, 3, 2), ("block2", 128, 4, 2), ("block3", 256, 6, 2)]
 BLOCKS_R50_FULL = BLOCKS_R50_B3 + [("block4", 512, 3, 1)]
 BLOCKS_R101_FULL = [("block1", 64, 3, 2), ("block2", 128, 4, 2), ("block3", 256, 23, 2), ("block4", 512, 3, 1)]
+PRECISIONS = ("f32", "bf16")
 
 
 def block_units(base_depth, num_units, stride):
@@ -98,7 +103,8 @@ def _st(t):
 class ConvBN:
     """conv weights (HWIO) + BatchNorm folded to scale/shift, resident on the device."""
 
-    def __init__(self, params, prefix, eps, device, wname="/weights", bn="/BatchNorm/", pad_k_to=None, pad_taps_to=None):
+    def __init__(self, params, prefix, eps, device, wname="/weights", bn="/BatchNorm/", pad_k_to=None, pad_taps_to=None,
+                 bf16=False):
         w = np.asarray(params[prefix + wname], np.float32)
         if pad_taps_to is not None:       # zero taps / channels: [kh,kw,ci,co] -> [KH,KW,CI,co]
             wp = np.zeros(tuple(pad_taps_to) + (w.shape[3],), np.float32)
@@ -115,6 +121,15 @@ class ConvBN:
         self.w = torch.from_numpy(np.ascontiguousarray(w2)).to(device)
         self.scale = torch.from_numpy(scale.astype(np.float32)).to(device)
         self.shift = torch.from_numpy(shift.astype(np.float32)).to(device)
+        # the bf16 mode's filter, built only when asked for: rounded once (nearest even) and packed [Co][kh*kw*Ci]
+        self.w_bf16 = pack_weight_bf16(w).to(device) if bf16 else None
+
+
+def pack_weight_bf16(w_hwio):
+    """HWIO f32 filter [kh,kw,Ci,Co] -> bf16 [Co, kh*kw*Ci] (k contiguous, k = (ky, kx, ci)), rounded to nearest even"""
+    w = torch.from_numpy(np.ascontiguousarray(w_hwio, dtype=np.float32))
+    kh, kw, ci, co = w.shape
+    return w.reshape(kh * kw * ci, co).t().contiguous().to(torch.bfloat16)
 
 
 def conv2d(x, cb, stride=1, pad=(0, 0), out_hw=None, residual=None, relu=True):
@@ -127,6 +142,23 @@ def conv2d(x, cb, stride=1, pad=(0, 0), out_hw=None, residual=None, relu=True):
     _lib.check(lib.vqa_conv2d_nhwc(_p(x), B, Hi, Wi, Ci, _p(cb.w), cb.kh, cb.kw, cb.co, stride, pad[0], pad[1], Ho, Wo,
                                    _p(cb.scale), _p(cb.shift), _p(residual), int(relu), _p(y), _st(x)),
                "vqa_conv2d_nhwc")
+    return y
+
+
+def conv2d_bf16(x, cb, stride=1, pad=(0, 0), out_hw=None, residual=None, relu=True, out_f32=False):
+    """y = [relu](conv(x)*scale + shift [+ residual]) through vqa_conv2d_nhwc_bf16: x and residual bf16, f32 accumulation,
+    y bf16 (rounded once on store) or, with out_f32, f32 unrounded."""
+    lib = _lib.load()
+    B, Hi, Wi, Ci = x.shape
+    if cb.w_bf16 is None:
+        raise _lib.VqaHotError("conv2d_bf16 needs a ConvBN built with bf16=True")
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and Ci == cb.ci
+    assert residual is None or (residual.dtype == torch.bfloat16 and residual.is_contiguous())
+    Ho, Wo = out_hw if out_hw is not None else (Hi, Wi)
+    y = torch.empty(B, Ho, Wo, cb.co, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    _lib.check(lib.vqa_conv2d_nhwc_bf16(_p(x), B, Hi, Wi, Ci, _p(cb.w_bf16), cb.kh, cb.kw, cb.co, stride, pad[0], pad[1], Ho,
+                                        Wo, _p(cb.scale), _p(cb.shift), _p(residual), int(relu), _p(y), int(out_f32), _st(x)),
+               "vqa_conv2d_nhwc_bf16")
     return y
 
 
@@ -155,9 +187,13 @@ def conv2d_backward(x, cb, y, dy, stride=1, pad=(0, 0), relu=True, need_dx=True,
     return dx, dw, dshift, dres
 
 
-def max_pool_3x3_s2_same(x):
+def max_pool_3x3_s2_same(x, out_bf16=False):
     lib = _lib.load()
     B, H, W, Cc = x.shape
+    if out_bf16:        # f32 in, bf16 out: the f32 max-pool rounded to nearest even
+        y = torch.empty(B, (H + 1) // 2, (W + 1) // 2, Cc, dtype=torch.bfloat16, device=x.device)
+        _lib.check(lib.vqa_maxpool3x3s2_same_nhwc_bf16(_p(x), B, H, W, Cc, _p(y), _st(x)), "vqa_maxpool3x3s2_same_nhwc_bf16")
+        return y
     y = torch.empty(B, (H + 1) // 2, (W + 1) // 2, Cc, dtype=torch.float32, device=x.device)
     _lib.check(lib.vqa_maxpool3x3s2_same_nhwc(_p(x), B, H, W, Cc, _p(y), _st(x)), "vqa_maxpool3x3s2_same_nhwc")
     return y
@@ -168,6 +204,10 @@ def subsample(x, factor):
         return x
     lib = _lib.load()
     B, H, W, Cc = x.shape
+    if x.dtype == torch.bfloat16:
+        y = torch.empty(B, (H - 1) // factor + 1, (W - 1) // factor + 1, Cc, dtype=torch.bfloat16, device=x.device)
+        _lib.check(lib.vqa_subsample_nhwc_bf16(_p(x), B, H, W, Cc, factor, _p(y), _st(x)), "vqa_subsample_nhwc_bf16")
+        return y
     y = torch.empty(B, (H - 1) // factor + 1, (W - 1) // factor + 1, Cc, dtype=torch.float32, device=x.device)
     _lib.check(lib.vqa_subsample_nhwc(_p(x), B, H, W, Cc, factor, _p(y), _st(x)), "vqa_subsample_nhwc")
     return y
@@ -189,10 +229,14 @@ def roi_pool(ftmap, box, height, width):
 class ResNetV1:
     """modules.encode_I_block3 / encode_I_full: mean subtraction + conv1 + pool1 + bottleneck blocks."""
 
-    def __init__(self, params, blocks=BLOCKS_R50_B3, scope="resnet_v1_50", device="cuda:0"):
+    def __init__(self, params, blocks=BLOCKS_R50_B3, scope="resnet_v1_50", device="cuda:0", precision="f32"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("ResNetV1 needs a GPU (no CPU fallback)")
         self.device = torch.device(device)
+        self.precision = precision
+        bf16 = precision == "bf16"
         self.blocks = blocks
         self.conv1 = ConvBN(params, scope + "/conv1", SLIM_BN_EPS, self.device, pad_taps_to=(7, 8, 4))   # [7,7,3,Co] -> [7,8,4,Co]
         self.units = []
@@ -200,17 +244,17 @@ class ResNetV1:
         for name, base, n, stride in blocks:
             for i, (depth, db, s) in enumerate(block_units(base, n, stride)):
                 pre = "%s/%s/unit_%d/bottleneck_v1" % (scope, name, i + 1)
-                u = {"depth": depth, "stride": s,
-                     "shortcut": ConvBN(params, pre + "/shortcut", SLIM_BN_EPS, self.device) if depth != cin else None,
-                     "conv1": ConvBN(params, pre + "/conv1", SLIM_BN_EPS, self.device),
-                     "conv2": ConvBN(params, pre + "/conv2", SLIM_BN_EPS, self.device),
-                     "conv3": ConvBN(params, pre + "/conv3", SLIM_BN_EPS, self.device)}
+                u = {"depth": depth, "stride": s, "name": "%s/unit_%d" % (name, i + 1),
+                     "shortcut": ConvBN(params, pre + "/shortcut", SLIM_BN_EPS, self.device, bf16=bf16) if depth != cin else None,
+                     "conv1": ConvBN(params, pre + "/conv1", SLIM_BN_EPS, self.device, bf16=bf16),
+                     "conv2": ConvBN(params, pre + "/conv2", SLIM_BN_EPS, self.device, bf16=bf16),
+                     "conv3": ConvBN(params, pre + "/conv3", SLIM_BN_EPS, self.device, bf16=bf16)}
                 self.units.append(u)
                 cin = depth
         self.out_channels = cin
         self._mean = (C.c_float * 3)(*ENC_I_MEAN)
 
-    def stem(self, images):
+    def stem(self, images, out_bf16=False):
         lib = _lib.load()
         B, H, W, Cc = images.shape
         assert Cc == 3 and images.dtype == torch.float32 and images.is_contiguous()
@@ -221,7 +265,9 @@ class ResNetV1:
         x4 = torch.empty(B, H, W, 4, dtype=torch.float32, device=images.device)
         _lib.check(lib.vqa_pad_c3c4_nhwc(_p(images), B, H, W, self._mean, _p(x4), _st(images)), "vqa_pad_c3c4_nhwc")
         y = conv2d(x4, self.conv1, stride=2, pad=(3, 3), out_hw=(Ho, Wo), relu=True)
-        return max_pool_3x3_s2_same(y)
+        if out_bf16:
+            self.stem_conv1 = y                   # the f32 stem output the bf16 max-pool read (tests compare against it)
+        return max_pool_3x3_s2_same(y, out_bf16=out_bf16)
 
     def bottleneck(self, x, u):
         s = u["stride"]
@@ -235,7 +281,35 @@ class ResNetV1:
         r = conv2d(r, u["conv2"], stride=s, pad=(1, 1), out_hw=(Ho, Wo), relu=True)    # conv2d_same(3, s)
         return conv2d(r, u["conv3"], residual=shortcut, relu=True)
 
-    def __call__(self, images):
+    def bottleneck_bf16(self, x, u, last, trace):
+        """bottleneck() on bf16 activations; `last`: the trunk's final unit, whose conv3 writes f32 unrounded"""
+        def conv(name, inp, **kw):
+            y = conv2d_bf16(inp, u[name], **kw)
+            if trace is not None:
+                trace.append({"name": u["name"] + "/" + name, "x": inp, "residual": kw.get("residual"),
+                              "stride": kw.get("stride", 1), "pad": kw.get("pad", (0, 0)), "relu": kw["relu"],
+                              "out_f32": kw.get("out_f32", False), "cb": u[name], "y": y})
+            return y
+
+        s = u["stride"]
+        B, H, W, _ = x.shape
+        Ho, Wo = ((H - 1) // s + 1, (W - 1) // s + 1) if s > 1 else (H, W)
+        if u["shortcut"] is None:
+            shortcut = subsample(x, s)
+        else:       # 1x1 / stride s == subsample, then 1x1
+            shortcut = conv("shortcut", subsample(x, s), relu=False)
+        r = conv("conv1", x, relu=True)
+        r = conv("conv2", r, stride=s, pad=(1, 1), out_hw=(Ho, Wo), relu=True)
+        return conv("conv3", r, residual=shortcut, relu=True, out_f32=last)
+
+    def __call__(self, images, trace=None):
+        """trace (a list, bf16 mode): every bf16 convolution appends {name, x, residual, stride, pad, relu, out_f32, cb, y},
+        the tensors as they are (no copies)"""
+        if self.precision == "bf16":
+            x = self.stem(images, out_bf16=True)
+            for i, u in enumerate(self.units):
+                x = self.bottleneck_bf16(x, u, i == len(self.units) - 1, trace)
+            return x
         x = self.stem(images)
         for u in self.units:
             x = self.bottleneck(x, u)
@@ -245,8 +319,8 @@ class ResNetV1:
 class VfeatResnetModel:
     """vqa/model_vfeat_resnet.py:28-40: conv map -> 1x1 crop_and_resize -> outputs['V_ft'] [B,n_box,C]."""
 
-    def __init__(self, params, blocks=BLOCKS_R50_B3, device="cuda:0"):
-        self.net = ResNetV1(params, blocks, device=device)
+    def __init__(self, params, blocks=BLOCKS_R50_B3, device="cuda:0", precision="f32"):
+        self.net = ResNetV1(params, blocks, device=device, precision=precision)
         self.outputs = {}
 
     def build(self, batch):
@@ -263,8 +337,8 @@ class VfeatModel:
 
     ROI_SZ = 5
 
-    def __init__(self, params, blocks=BLOCKS_R50_B3, device="cuda:0"):
-        self.net = ResNetV1(params, blocks, device=device)
+    def __init__(self, params, blocks=BLOCKS_R50_B3, device="cuda:0", precision="f32"):
+        self.net = ResNetV1(params, blocks, device=device, precision=precision)
         dev = self.net.device
         self.reduce = ConvBN(params, "I_reduce_dim/conv2d", LAYERS_BN_EPS, dev, wname="/conv2d/weights")
         self.i2v = ConvBN(params, "I2V/conv2d_1", LAYERS_BN_EPS, dev, wname="/conv2d/weights")

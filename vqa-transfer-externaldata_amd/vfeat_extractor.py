@@ -68,6 +68,9 @@ def build_parser():
     parser.add_argument("--model_type", type=str, default="vfeat", help=" ", choices=["vfeat", "resnet"])
     # not in the reference: JPEG decoding on forked worker processes instead of the thread pool (0 = threads)
     parser.add_argument("--loader_processes", type=int, default=0, help="image decoding worker processes (0: thread pool)")
+    # not in the reference: bf16 activations and bf16 MFMA in the ResNet trunk after the stem
+    parser.add_argument("--precision", type=str, default="f32", choices=list(vfeat.PRECISIONS),
+                        help="arithmetic of the ResNet trunk; the stored features are float32 either way")
     return parser
 
 
@@ -111,7 +114,9 @@ def run(config, dataset=None, blocks=vfeat.BLOCKS_R50_B3, device=None, rank=None
     if device is None:
         device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     params = load_params(config.pretrained_param_path, config.model_type, blocks)
-    model = get_model_class(config.model_type)(params, blocks, device=device)
+    precision = getattr(config, "precision", "f32") or "f32"
+    log.infov("trunk precision: {}".format(precision))
+    model = get_model_class(config.model_type)(params, blocks, device=device, precision=precision)
     if batches is None:
         batches = make_batches()
     ex = vfeat.Extractor(model, image_info["image_id2idx"], dataset.get_config().max_roi_num,

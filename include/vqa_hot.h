@@ -438,14 +438,7 @@ int vqa_dropout_mask(uint8_t* out, int64_t n, uint64_t seed, uint64_t offset, fl
 typedef struct {
     int32_t B, R, D, H, T, W, A, Vq;
     int64_t N_img;
-    int32_t model_type;      /* 7..11: see VQA_MODEL_* below.  0 = vlmap_answer, 1 = standard, 2 = standard_word2vec, 3 = standard_testmask (= 1 with
-                              * the training loss masked by the train-answer mask, vqa/model_standard_testmask.py:266-268),
-                              * 4 = vlmap_answer_vqa_all2 (= 0 + the trainable TunedWordWeightAnswer head, summed logits,
-                              * two-term loss, mixed-mask argmax: vqa/model_vlmap_answer_vqa_all2.py:196-244),
-                              * 6 = vlmap_answer_vqa_all (= 4 with unknown answers' fixed logits at the row minimum, the
-                              * tuned loss on the summed logits, both terms train-masked, argmax of the sum),
-                              * 5 = vlmap_answer_noc / _nocarch (two un-composed branches joint_v(pooled_linear_l) and
-                              * joint_l(l_linear_l) with their own heads, logits summed: vqa/model_vlmap_answer_noc.py:177-204) */
+    int32_t model_type;      /* VQA_MODEL_* below: which registry model the step runs */
     float keep_att;          /* 0.8  vlmap/modules.py:82 */
     float keep_joint;        /* 0.5  vqa/model_vlmap_answer.py:180 */
     float inv_global_batch;  /* 1/B for one GPU, 1/(sum of shard sizes) under data parallel */
@@ -475,6 +468,17 @@ typedef struct {
  * Types 10 and 11 report three more scalars behind the 13 of vqa_report_key: report[13] = latent_loss | entropy,
  * report[14] = extra_weight * report[13], report[15] = the model's total loss (report[0] + report[14]); stats[b,15]
  * carries the per-sample term for data-parallel reporting. */
+#define VQA_MODEL_VLMAP_ANSWER 0   /* vlmap_answer (vqa/model_vlmap_answer.py) */
+#define VQA_MODEL_STANDARD 1       /* standard (vqa/model_standard.py): the training loss is not masked by the train-answer mask */
+#define VQA_MODEL_WORD2VEC 2       /* standard_word2vec: classifier FC into the word space x the constant answer-GloVe matrix */
+#define VQA_MODEL_TESTMASK 3       /* standard_testmask (= 1 with the training loss masked by the train-answer mask,
+                                    * vqa/model_standard_testmask.py:266-268) */
+#define VQA_MODEL_VQA_ALL2 4       /* vlmap_answer_vqa_all2 (= 0 + the trainable TunedWordWeightAnswer head, summed logits,
+                                    * two-term loss, mixed-mask argmax: vqa/model_vlmap_answer_vqa_all2.py:196-244) */
+#define VQA_MODEL_NOC 5            /* vlmap_answer_noc / _nocarch (two un-composed branches joint_v(pooled_linear_l) and
+                                    * joint_l(l_linear_l) with their own heads, logits summed: vqa/model_vlmap_answer_noc.py:177-204) */
+#define VQA_MODEL_VQA_ALL 6        /* vlmap_answer_vqa_all (= 4 with unknown answers' fixed logits at the row minimum, the
+                                    * tuned loss on the summed logits, both terms train-masked, argmax of the sum) */
 #define VQA_MODEL_ANSWER2 7
 #define VQA_MODEL_NO_NOISE 8
 #define VQA_MODEL_ADAPT 9

@@ -79,12 +79,6 @@ __global__ __launch_bounds__(256) void col2im_gather_kernel(const float* __restr
     }
 }
 
-#define TRY(x)                           \
-    do {                                 \
-        int rc__ = (x);                  \
-        if (rc__ != VQA_OK) return rc__; \
-    } while (0)
-
 }  // namespace
 
 // floats of scratch vqa_conv2d_nhwc_bwd needs to process `chunk_images` images at a time (>= 1; B = everything at once)

@@ -39,7 +39,10 @@ struct Layout {
     }
 };
 
-int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
+// properties that several model types share (include/vqa_hot.h: VQA_MODEL_*)
+inline bool has_tuned_head(int mt) { return mt == VQA_MODEL_VQA_ALL2 || mt == VQA_MODEL_VQA_ALL; }      // a second, trainable head on `joint`
+inline bool train_loss_masked(int mt) { return mt != VQA_MODEL_STANDARD; }      // train loss masked by the train-answer mask
+inline bool bf16_routed(int mt) { return mt == VQA_MODEL_VLMAP_ANSWER || mt == VQA_MODEL_STANDARD; }      // every dense product on VQA_FLAG_BF16_GEMM's routed list
 
 void legacy_vqa_layout(Layout& L, const vqa_dims_t& d, int64_t& gw);      // csrc/legacy_vqa.inc (model_type 13)
 
@@ -51,7 +54,7 @@ Layout make_layout(const vqa_dims_t& d) {
     L.add("pre_v", B * R * H);
     L.add("v_linear_v", B * R * H);
     L.add("mean_v", B); L.add("rstd_v", B);
-    const int64_t Wp = ((W + 1 + 3) / 4) * 4;      // row stride of x_tm: W inputs + the constant 1 (+ zero padding to 16 B)
+    const int64_t Wp = x_stride(W);
     L.add("x_tm", T * B * Wp);
     L.add("xp", T * B * 3 * H);
     L.add("wx_cat", W * 3 * H); L.add("bx_cat", 3 * H); L.add("dwx_cat", Wp * 3 * H);
@@ -69,14 +72,14 @@ Layout make_layout(const vqa_dims_t& d) {
     L.add("pre_j", B * 2 * H); L.add("joint", B * 2 * H); L.add("mean_j", B); L.add("rstd_j", B);
     L.add("joint2", B * W);      // standard_word2vec: classifier output in the 300-d word space
     L.add("logit", B * A);
-    if (d.model_type == 5) {     // vlmap_answer_noc: the l_joint branch ("joint" is v_joint)
+    if (d.model_type == VQA_MODEL_NOC) {     // vlmap_answer_noc: the l_joint branch ("joint" is v_joint)
         L.add("pre_jl", B * 2 * H); L.add("l_joint", B * 2 * H); L.add("mean_jl", B); L.add("rstd_jl", B);
         L.add("d_ljoint", B * 2 * H); L.add("d_pre_jl", B * 2 * H);
     }
-    if (d.model_type == 4 || d.model_type == 6) {     // vlmap_answer_vqa_all2 / _vqa_all: the two heads' logits ("logit" = their sum), the tuned head's dz
+    if (has_tuned_head(d.model_type)) {     // vlmap_answer_vqa_all2 / _vqa_all: the two heads' logits ("logit" = their sum), the tuned head's dz
         L.add("logit_fixed", B * A); L.add("logit_tuned", B * A); L.add("dlogit_tuned", B * A);
     }
-    if (d.model_type == 6) { L.add("logit_raw", B * A); L.add("rowmin", B); }      // before the row-minimum substitution
+    if (d.model_type == VQA_MODEL_VQA_ALL) { L.add("logit_raw", B * A); L.add("rowmin", B); }      // before the row-minimum substitution
     // the five older ablations (vqa_hot.h: VQA_MODEL_*)
     if (d.model_type == VQA_MODEL_ANSWER2) {
         L.add("pre_ft2", B * H); L.add("q_L_ft2", B * H); L.add("mean_ft2", B); L.add("rstd_ft2", B);
@@ -94,7 +97,7 @@ Layout make_layout(const vqa_dims_t& d) {
     if (d.model_type == VQA_MODEL_BI) {
         // bi-directional question encoder + question self-attention (the forward cell reuses x_tm / xp / hs / gru_* / dxp /
         // wx_cat / bx_cat / dwx_cat above with h = H / 2 columns; the backward cell gets its own)
-        const int64_t h = H / 2, Wq = ((W + 1 + 3) / 4) * 4;
+        const int64_t h = H / 2, Wq = x_stride(W);
         L.add("q_rev", B * T);
         L.add("x_tm_bw", T * B * Wq); L.add("xp_bw", T * B * 3 * h);
         L.add("wx_cat_bw", W * 3 * h); L.add("bx_cat_bw", 3 * h); L.add("dwx_cat_bw", Wq * 3 * h);
@@ -187,12 +190,6 @@ Layout make_layout(const vqa_dims_t& d) {
     return L;
 }
 
-#define TRY(x)                      \
-    do {                            \
-        int rc__ = (x);             \
-        if (rc__ != VQA_OK) return rc__; \
-    } while (0)
-
 struct Ctx {
     const vqa_dims_t& d;
     const Layout& L;
@@ -211,6 +208,62 @@ struct Ctx {
     int64_t gemm_ws_floats() const { return L.find("gemm_ws")->n; }
     int64_t colsum_ws_floats() const { return L.find("colsum_ws")->n; }
 };
+
+// ---- The VQA_HOT_* switches of this file.  Each is read from the environment once per process, at its first use (never
+// at load time), and exists for same-box A/B runs: the default is the measured best.
+//   VQA_HOT_XCAT=0          question encoder's x-projection, dx and dW as two GEMMs per direction instead of the packed one
+//   VQA_HOT_REPACK=1        the backward packs wx_cat again instead of reusing the forward's copy
+//   VQA_HOT_GRU_WS=0        never the weight-stationary recurrence: the per-step kernels (gru_form)
+//   VQA_HOT_GRU_CHAINS=n    row chains of the per-step recurrence (default 2; 1 = one chain on the caller's stream), and
+//   VQA_HOT_GRU_CHAIN_DELAY_US  their anti-phase delay (default 3)                                    -- gru_chains()
+//   VQA_HOT_VISUAL_LATE=0   the visual branch in front of the question branch (the round-1 order)
+//   VQA_HOT_OVERLAP=1       the visual branch / v_linear_v's backward on a side stream                -- side_stream()
+//   VQA_HOT_SIDE_BLOCKS=n   workgroup cap of the side stream's GEMMs (default 0 = none)
+//   VQA_HOT_GATHER=fused    the feature gather inside v_linear_v's GEMM (anything else: a pass of its own; unset: the flag)
+//   VQA_HOT_LN_PAIR=0       pooled_linear_l and q_linear_l as two LayerNorm launches plus the element-wise product
+//   VQA_HOT_VTAIL=0         v_linear_v's LayerNorm backward and the score gradient as separate calls (vqa_vtail_set_mode)
+inline bool env_on(const char* name, bool dflt) {
+    const char* e = getenv(name);
+    return e == nullptr ? dflt : atoi(e) != 0;
+}
+inline bool xcat_enabled() { static const bool v = env_on("VQA_HOT_XCAT", true); return v; }
+inline bool repack_enabled() { static const bool v = env_on("VQA_HOT_REPACK", false); return v; }
+inline bool gru_ws_on() { static const bool v = env_on("VQA_HOT_GRU_WS", true); return v; }
+inline bool visual_late_enabled() { static const bool v = env_on("VQA_HOT_VISUAL_LATE", true); return v; }
+// pooled_linear_l and q_linear_l finish in one launch that also forms their product (vqa_ln_pair_mul_*): two LayerNorm
+// launches and the element-wise one less per direction
+inline bool ln_pair_enabled() { static const bool v = env_on("VQA_HOT_LN_PAIR", true); return v; }
+// The backward of v_linear_v's LayerNorm and of the attention score as one chain (vqa_attn_pool_bwd_ds ->
+// vqa_ln_relu_att_bwd -> vqa_colsum_vtail) where it applies (vtail_ok); 0 = the separate calls.  vqa_vtail_set_mode
+// overrides the environment, and a negative mode has it read again.
+int g_vtail_mode = -1;
+inline int vtail_mode() {
+    if (g_vtail_mode < 0) g_vtail_mode = env_on("VQA_HOT_VTAIL", true) ? 1 : 0;
+    return g_vtail_mode;
+}
+int side_max_blocks() {
+    static int v = -1;
+    if (v < 0) {
+        const char* e = getenv("VQA_HOT_SIDE_BLOCKS");
+        v = e ? atoi(e) : 0;
+    }
+    return v;
+}
+// how V_ft = features[image_idx] is produced: 0 = a gather pass in front of v_linear_v's GEMM (default), 1 = fused
+// into that GEMM's operand load (VQA_FLAG_FUSED_GATHER or VQA_HOT_GATHER=fused).  Measured at bs 512
+// (profiles/r2_gather_mode_ab.txt, r2_gather_gemm_bench.txt): 3.73 ms per step either way -- the 46 us gather pass
+// doubles as a prefetch of V_ft into the Infinity Cache, from where the GEMM streams its left operand 37 us faster than
+// the fused form streams it from HBM.  A third form, the gather on a helper stream beside the question branch's
+// projection GEMMs, lost 0.13 ms to the cross-stream fork / join.
+int gather_mode(const vqa_dims_t* dims) {
+    static int env = -2;
+    if (env == -2) {
+        const char* e = getenv("VQA_HOT_GATHER");
+        env = e == nullptr ? -1 : (strcmp(e, "fused") == 0 ? 1 : 0);
+    }
+    if (env >= 0) return env;
+    return (dims->flags & VQA_FLAG_FUSED_GATHER) ? 1 : 0;
+}
 
 // ---- side stream: the v_linear_v branch (one big GEMM) runs beside the latency-bound GRU
 // recurrence so its workgroups fill the CUs the small per-step GEMMs leave idle.  Fork/join
@@ -237,14 +290,6 @@ Side& side_stream() {
         }
     }
     return x;
-}
-int side_max_blocks() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VQA_HOT_SIDE_BLOCKS");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
 }
 // The recurrence is latency-bound (M = batch rows only): every one of its 2 T dependent step kernels pays ~7 us that
 // is not matrix work (drain, launch gap, kernel arguments, first tile, fused epilogue) against 7-14 us that is
@@ -322,29 +367,11 @@ int run_chains(const Ctx& c, int64_t B, Fn fn) {
             rc = rc == VQA_OK ? VQA_ERR_LAUNCH : rc;
     return rc;
 }
-// how V_ft = features[image_idx] is produced: 0 = a gather pass in front of v_linear_v's GEMM (default), 1 = fused
-// into that GEMM's operand load (VQA_FLAG_FUSED_GATHER or VQA_HOT_GATHER=fused).  Measured at bs 512
-// (profiles/r2_gather_mode_ab.txt, r2_gather_gemm_bench.txt): 3.73 ms per step either way -- the 46 us gather pass
-// doubles as a prefetch of V_ft into the Infinity Cache, from where the GEMM streams its left operand 37 us faster than
-// the fused form streams it from HBM.  A third form, the gather on a helper stream beside the question branch's
-// projection GEMMs, lost 0.13 ms to the cross-stream fork / join.
-int gather_mode(const vqa_dims_t* dims) {
-    static int env = -2;
-    if (env == -2) {
-        const char* e = getenv("VQA_HOT_GATHER");
-        env = e == nullptr ? -1 : (strcmp(e, "fused") == 0 ? 1 : 0);
-    }
-    if (env >= 0) return env;
-    return (dims->flags & VQA_FLAG_FUSED_GATHER) ? 1 : 0;
-}
 bool fork_side(const Ctx& c, Side& sd) {
     if (!sd.ok) return false;
     return hipEventRecord(sd.fork, c.st) == hipSuccess && hipStreamWaitEvent(sd.s, sd.fork, 0) == hipSuccess;
 }
 bool join_side_record(Side& sd) { return hipEventRecord(sd.join, sd.s) == hipSuccess; }
-bool join_side(const Ctx& c, Side& sd) {
-    return join_side_record(sd) && hipStreamWaitEvent(c.st, sd.join, 0) == hipSuccess;
-}
 
 
 // The f32 MFMA product, whatever the flags say: the question encoder's sites (x-projection, dx, dwx, dwh) call this one
@@ -371,10 +398,10 @@ int colsum(const Ctx& c, const float* X, int64_t M, int64_t N, int ldx, float* o
 
 bool dims_ok(const vqa_dims_t* d) {
     if (!(d && d->B > 0 && d->R > 0 && d->D > 0 && d->H > 0 && d->T > 0 && d->W > 0 && d->A > 0 && d->Vq > 0 &&
-          d->N_img > 0 && d->model_type >= 0 && d->model_type <= VQA_MODEL_LEGACY_VQA))
+          d->N_img > 0 && d->model_type >= VQA_MODEL_VLMAP_ANSWER && d->model_type <= VQA_MODEL_LEGACY_VQA))
         return false;
     // bf16 mode: the two model types whose every dense product is on the routed list, and no gather-fused GEMM
-    if ((d->flags & VQA_FLAG_BF16_GEMM) && (d->model_type > 1 || (d->flags & VQA_FLAG_FUSED_GATHER))) return false;
+    if ((d->flags & VQA_FLAG_BF16_GEMM) && (!bf16_routed(d->model_type) || (d->flags & VQA_FLAG_FUSED_GATHER))) return false;
     if (d->model_type == VQA_MODEL_LEGACY_VQA)      // 16-byte rows everywhere; the scoring kernel keeps one H-row in LDS
         return d->map_dim > 0 && d->La > 0 && d->H % 4 == 0 && d->D % 4 == 0 && d->map_dim % 4 == 0 && d->W % 4 == 0 && d->H <= 1024 && d->Vq > 3;
     if (d->model_type == VQA_MODEL_BI) return d->H % 8 == 0;      // two cells of H / 2 units, 16-byte rows each
@@ -436,14 +463,9 @@ int fc_ln_relu_bwd(const Ctx& c, const float* dy, const float* x, int64_t M, int
     return fc_bwd_tail(c, x, M, K, N, p, g, rows, c.f(d_pre), c.part(0), c.part(1), c.part(2), dx, dx_accumulate);
 }
 
-// pooled_linear_l and q_linear_l finish in one launch that also forms their product (vqa_ln_pair_mul_*): two LayerNorm
-// launches and the element-wise one less per direction.  VQA_HOT_LN_PAIR=0 restores the three-launch form (A/B).
-inline bool ln_pair_enabled() {
-    static const bool v = [] { const char* e = getenv("VQA_HOT_LN_PAIR"); return e == nullptr || atoi(e) != 0; }();
-    return v;
-}
+// whether the paired launch runs: not for vlmap_answer_noc, and only on 16-byte rows
 bool ln_pair_ok(const vqa_dims_t& d, const vqa_params_t* P) {
-    if (!ln_pair_enabled() || d.model_type == 5) return false;       // vlmap_answer_noc has no product
+    if (!ln_pair_enabled() || d.model_type == VQA_MODEL_NOC) return false;       // vlmap_answer_noc has no product
     const void* ptrs[4] = {P->pooled_linear_l.gamma, P->pooled_linear_l.beta, P->q_linear_l.gamma, P->q_linear_l.beta};
     return vqa_ln_pair_mul_supported(d.H, ptrs, 4) != 0;
 }
@@ -456,7 +478,7 @@ struct BiGru { const float *wg, *bg, *wc, *bc; };
 int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt) {
     const vqa_dims_t& d = c.d;
     const int64_t B = d.B, H = d.H, T = d.T, W = d.W, h = H / 2;
-    const int64_t Wp = ((W + 1 + 3) / 4) * 4;
+    const int64_t Wp = x_stride(W);
     VQA_REQUIRE(P->embed2 && P->gru_bw_wg && P->gru_bw_bg && P->gru_bw_wc && P->gru_bw_bc && P->q_att_key.w &&
                     P->q_att_key.gamma && P->q_att_query.w && P->q_att_query.gamma && P->word_score.w && P->word_score.b &&
                     P->v_word_fc.w && P->v_word_fc.gamma,
@@ -571,7 +593,7 @@ int bi_question_bwd_bptt(const Ctx& c, const vqa_params_t* P, const vqa_params_t
 int bi_question_bwd_weights(const Ctx& c, const vqa_params_t* G, int phases) {
     const vqa_dims_t& d = c.d;
     const int64_t B = d.B, H = d.H, T = d.T, W = d.W, h = H / 2;
-    const int64_t Wp = ((W + 1 + 3) / 4) * 4;
+    const int64_t Wp = x_stride(W);
     float* const gw[2][4] = {{G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc}, {G->gru_bw_wg, G->gru_bw_wc, G->gru_bw_bg, G->gru_bw_bc}};
     static const char* const nm[2][5] = {{"x_tm", "dxp", "dwx_cat", "hs", "gru_rh"}, {"x_tm_bw", "dxp_bw", "dwx_cat_bw", "hs_bw", "gru_rh_bw"}};
     for (int k = 0; k < 2; ++k) {
@@ -629,279 +651,389 @@ extern "C" int vqa_fusion_tensor(const vqa_dims_t* dims, const char* name, int64
     return VQA_OK;
 }
 
-namespace {
-// The backward of v_linear_v's LayerNorm and of the attention score as one chain (vqa_attn_pool_bwd_ds ->
-// vqa_ln_relu_att_bwd -> vqa_colsum_vtail) where it applies; 0 = the separate calls.  VQA_HOT_VTAIL / vqa_vtail_set_mode.
-int g_vtail_mode = -1;
-inline int vtail_mode() {
-    if (g_vtail_mode < 0) {
-        const char* e = getenv("VQA_HOT_VTAIL");
-        g_vtail_mode = (e != nullptr && atoi(e) == 0) ? 0 : 1;
-    }
-    return g_vtail_mode;
-}
-}  // namespace
-
 extern "C" int vqa_vtail_set_mode(int mode) {
     g_vtail_mode = mode < 0 ? -1 : (mode ? 1 : 0);
     return vtail_mode();
 }
 
 namespace {
-inline bool visual_late_enabled() {       // VQA_HOT_VISUAL_LATE=0: the round-1 order (A/B)
-    static const bool v = [] { const char* e = getenv("VQA_HOT_VISUAL_LATE"); return e == nullptr || atoi(e) != 0; }();
-    return v;
-}
-}  // namespace
 
-namespace {
-inline bool gru_ws_on() {          // VQA_HOT_GRU_WS=0: the per-step recurrence kernels (A/B)
-    static const bool v = [] { const char* e = getenv("VQA_HOT_GRU_WS"); return e == nullptr || atoi(e) != 0; }();
-    return v;
-}
-inline bool xcat_enabled() {       // VQA_HOT_XCAT=0: the two-GEMM form (A/B)
-    static const bool v = [] { const char* e = getenv("VQA_HOT_XCAT"); return e == nullptr || atoi(e) != 0; }();
-    return v;
-}
-}  // namespace
+// Everything one forward or backward call derives from its arguments, computed once and handed to every stage.  The
+// second half holds what a stage decides for the stages behind it.  Of the VQA_HOT_* switches it holds the ones a later
+// stage depends on (pair, visual_late, fuse_gather, forked); xcat, repack, gru_ws, vtail_mode and the gather mode stay
+// calls of their once-per-process readers at the place of use, so that none is read from the environment before the
+// first step that needs it (vqa_vtail_set_mode(-1) must still take effect between a forward and its backward).
+struct Step {
+    const vqa_dims_t& d;
+    const vqa_params_t* const P;
+    const vqa_params_t* const G;       // where the gradients go (backward); NULL in a forward call
+    const vqa_batch_t* const bt;
+    const Layout L;
+    const Ctx c;                       // the caller's stream
+    const int mt;
+    const int64_t B, R, D, H, T, W, A;
+    const int64_t Wp;                  // row stride of x_tm
+    const int64_t Dp;                  // width of what the attention pools
+    // side stream (VQA_HOT_OVERLAP=1): set where the visual branch (forward) or v_linear_v's backward forks
+    Side* sd = nullptr;
+    bool forked = false;
+    // forward: the visual branch's plan, and what the question branch hands on
+    bool fuse_gather = false, visual_late = false;
+    const float* q_ft = nullptr;       // the question code q_L_ft [B,H]
+    const float* qv_in = nullptr;      // what q_linear_v reads
+    const float* lin_in = nullptr;     // what q_linear_l reads: the question code, or one of the ablations' layers on top of it
+    // both directions: pooled_linear_l and q_linear_l finish in the paired LayerNorm launch (ln_pair_ok)
+    bool pair = false;
 
-extern "C" int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_batch_t* bt,
-                                  void* workspace, int64_t workspace_bytes, int want_dz, void* stream) {
-    VQA_REQUIRE(dims_ok(dims) && P && bt && workspace, VQA_ERR_ARG);
-    const Layout L = make_layout(*dims);
-    Ctx c{*dims, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), 0};
-    VQA_REQUIRE(workspace_bytes >= c.L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    ProbeScope ps_all("forward", c.st);
-    if (dims->model_type == VQA_MODEL_LEGACY_VQA) return legacy_vqa_forward(c, P, bt, want_dz);
-    const int64_t B = dims->B, R = dims->R, D = dims->D, H = dims->H, T = dims->T, W = dims->W, A = dims->A;
+    Step(const vqa_dims_t* dims, const vqa_params_t* P_, const vqa_params_t* G_, const vqa_batch_t* bt_, void* workspace,
+         void* stream)
+        : d(*dims), P(P_), G(G_), bt(bt_), L(make_layout(*dims)),
+          c{*dims, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), 0}, mt(dims->model_type),
+          B(dims->B), R(dims->R), D(dims->D), H(dims->H), T(dims->T), W(dims->W), A(dims->A), Wp(x_stride(dims->W)),
+          Dp(pooled_dim(*dims)) {}
+    Step(const Step&) = delete;
+    Step& operator=(const Step&) = delete;
 
-    // visual branch (a1 + a2) on the side stream (VQA_HOT_OVERLAP=1 only), question branch (a3-a5) on the caller's
-    Side& sd = side_stream();
-    const bool forked = fork_side(c, sd);
-    Ctx cv{*dims, L, c.ws, forked ? sd.s : c.st, forked ? 1 : 0};
+    // the context of what may run beside the caller's stream (the visual branch; v_linear_v's backward): the side stream
+    // and its own scratch when forked, else the caller's
+    Ctx side_ctx() const { return Ctx{d, L, c.ws, forked ? sd->s : c.st, forked ? 1 : 0}; }
+    // backward: resolved once per call (bind_bwd), behind the workspace checks
+    const float* hs = nullptr;         // the GRU's state tape
+    const float* h = nullptr;          // the final GRU state hs[T]
+    float* dh = nullptr;               // gradient wrt the question code
+    float* dxp = nullptr;
+    void bind_bwd() {
+        hs = c.f("hs");
+        h = hs + T * B * H;
+        dh = c.f("d_h0");
+        dxp = c.f("dxp");
+    }
+    const float* Wg_h() const { return P->gru_wg + W * 2 * H; }      // the recurrent rows of the two GRU kernels
+    const float* Wc_h() const { return P->gru_wc + W * H; }
+};
+
+// the two halves of the side stream's join: its work is recorded, the caller's stream waits for the record
+int side_record(const Step& s) { return !s.forked || join_side_record(*s.sd) ? VQA_OK : VQA_ERR_LAUNCH; }
+int side_wait(const Step& s) {
+    return !s.forked || hipStreamWaitEvent(s.c.st, s.sd->join, 0) == hipSuccess ? VQA_OK : VQA_ERR_LAUNCH;
+}
+
+// Which form of the recurrence runs: one decision for the forward and the backward of a step.
+//   GRU_WS      one launch, recurrent weights resident in registers and LDS, eight XCD-local chains (csrc/gru_ws.hip)
+//   GRU_LIVE    rows sorted by length: per-step kernels that skip finished sequences
+//   GRU_CHAINS  per-step kernels on independent row chains in anti-phase (gru_chains)
+// (A length-sorted batch whose longest row runs to T: the weight-stationary launch computes every row of every step under
+// its length mask -- same results -- and is faster than the shrinking per-step kernels at these sizes.)
+enum GruForm { GRU_WS, GRU_LIVE, GRU_CHAINS };
+enum GruDir { GRU_FWD, GRU_BWD };
+GruForm gru_form(GruDir dir, int64_t T, int64_t B, int64_t H, const int32_t* live_rows) {
+    const bool ws_ok = gru_ws_on() && (live_rows == nullptr || (T > 0 && live_rows[T - 1] > 0));
+    if (ws_ok && (dir == GRU_FWD ? vqa_gru_ws_supported((int)T, (int)B, (int)H) : vqa_gru_ws_bwd_supported((int)T, (int)B, (int)H)) == 1)
+        return GRU_WS;
+    return live_rows != nullptr ? GRU_LIVE : GRU_CHAINS;
+}
+
+// ---------------------------------------------------------------- forward stages, in launch order
+
+// Where the visual branch runs.  With the side stream it is launched first and overlaps the recurrence; on one stream it
+// runs AFTER the question branch, right before the attention that consumes it: V_ft (151 MB) and v_linear_v (75 MB) are
+// then still in the 256 MB Infinity Cache when the attention kernel reads them, instead of having been pushed out by the
+// recurrence's traffic.
+void fwd_visual_plan(Step& s) {
+    s.sd = &side_stream();
+    s.forked = fork_side(s.c, *s.sd);
     // (dims_ok refuses the FLAG pair; VQA_HOT_GATHER=fused in the environment must not bring the f32 gather GEMM into a bf16 step either)
-    const bool fuse_gather = !(dims->flags & VQA_FLAG_BF16_GEMM) && gather_mode(dims) == 1 && (D % 32 == 0) && (H % 4 == 0) && vqa_aligned16(bt->table);
-    const int mt = dims->model_type;
-    // The visual branch (a1 + a2).  With the side stream it is launched first and overlaps the recurrence; on one
-    // stream it runs AFTER the question branch, right before the attention that consumes it: V_ft (151 MB) and
-    // v_linear_v (75 MB) are then still in the 256 MB Infinity Cache when the attention kernel reads them, instead
-    // of having been pushed out by the recurrence's traffic.
-    auto visual_branch = [&]() -> int {
-        // a1: V_ft = features[image_idx] (a pass of its own, or inside the GEMM below), num_V_ft = num_boxes[image_idx]
+    s.fuse_gather = !(s.d.flags & VQA_FLAG_BF16_GEMM) && gather_mode(&s.d) == 1 && (s.D % 32 == 0) && (s.H % 4 == 0) &&
+                    vqa_aligned16(s.bt->table);
+    s.visual_late = !s.forked && visual_late_enabled();
+}
+
+// a1 + a2: feature gather, v_linear_v and (vlmap_answer_adapt) v_adapt
+int fwd_visual(const Step& s) {
+    const Ctx cv = s.side_ctx();
+    const vqa_params_t* P = s.P;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, R = s.R, D = s.D, H = s.H;
+    // a1: V_ft = features[image_idx] (a pass of its own, or inside the GEMM below), num_V_ft = num_boxes[image_idx]
+    {
+        ProbeScope ps("gather", cv.st);
+        TRY(vqa_gather_features(bt->table, bt->nbox_table, bt->image_idx, s.fuse_gather ? nullptr : cv.f("V_ft"),
+                                cv.i32("num_V_ft"), (int)B, (int)R, (int)D, s.d.N_img, cv.st));
+    }
+    // a2: v_linear_v, LN statistics over the whole [R,H] block of a sample
+    if (s.fuse_gather) {
         {
-            ProbeScope ps("gather", cv.st);
-            TRY(vqa_gather_features(bt->table, bt->nbox_table, bt->image_idx, fuse_gather ? nullptr : cv.f("V_ft"),
-                                    cv.i32("num_V_ft"), (int)B, (int)R, (int)D, dims->N_img, cv.st));
+            ProbeScope ps("v_linear_v.fwd_gemm", cv.st);
+            TRY(vqa_gemm_f32_gather((int)(B * R), (int)H, (int)D, bt->table, (int)D, bt->image_idx, (int)R, s.d.N_img,
+                                    P->v_linear_v.w, (int)H, cv.f("pre_v"), (int)H, P->v_linear_v.b, cv.f("V_ft"), (int)D,
+                                    cv.st));
         }
-        // a2: v_linear_v, LN statistics over the whole [R,H] block of a sample
-        if (fuse_gather) {
-            {
-                ProbeScope ps("v_linear_v.fwd_gemm", cv.st);
-                TRY(vqa_gemm_f32_gather((int)(B * R), (int)H, (int)D, bt->table, (int)D, bt->image_idx, (int)R, dims->N_img,
-                                        P->v_linear_v.w, (int)H, cv.f("pre_v"), (int)H, P->v_linear_v.b, cv.f("V_ft"), (int)D,
-                                        cv.st));
-            }
-            ProbeScope ps("v_linear_v.ln_fwd", cv.st);
-            TRY(vqa_ln_relu_fwd(cv.f("pre_v"), P->v_linear_v.gamma, P->v_linear_v.beta, nullptr, 1.f, cv.f("v_linear_v"),
-                                cv.f("mean_v"), cv.f("rstd_v"), (int)B, (int)R, (int)H, cv.st));
-        } else {
-            TRY(fc_ln_relu_fwd(cv, cv.f("V_ft"), B * R, D, H, P->v_linear_v, (int)R, "pre_v", "v_linear_v", "mean_v", "rstd_v",
-                               nullptr, 1.f));
-        }
-        if (mt == VQA_MODEL_ADAPT) {     // v_adapt: a second FC + LN[R,H] + ReLU on the same V_ft (:132-135)
-            VQA_REQUIRE(P->v_adapt.w != nullptr && P->v_adapt.gamma != nullptr, VQA_ERR_ARG);
-            TRY(fc_ln_relu_fwd(cv, cv.f("V_ft"), B * R, D, H, P->v_adapt, (int)R, "pre_va", "v_adapt", "mean_va", "rstd_va",
-                               nullptr, 1.f));
-        }
-        return VQA_OK;
-    };
-    const bool visual_late = !forked && visual_late_enabled();
-    if (!visual_late) TRY(visual_branch());
-    if (forked && !join_side_record(sd)) return VQA_ERR_LAUNCH;
-    const float* h = nullptr;            // the question code q_L_ft [B,H]
-    const float* qv_in = nullptr;        // what q_linear_v reads
-    if (mt == VQA_MODEL_BI) {
-        TRY(bi_question_fwd(c, P, bt));
-        h = c.f("q_L_ft");
-        qv_in = c.f("pooled_q_v");
+        ProbeScope ps("v_linear_v.ln_fwd", cv.st);
+        TRY(vqa_ln_relu_fwd(cv.f("pre_v"), P->v_linear_v.gamma, P->v_linear_v.beta, nullptr, 1.f, cv.f("v_linear_v"),
+                            cv.f("mean_v"), cv.f("rstd_v"), (int)B, (int)R, (int)H, cv.st));
     } else {
+        TRY(fc_ln_relu_fwd(cv, cv.f("V_ft"), B * R, D, H, P->v_linear_v, (int)R, "pre_v", "v_linear_v", "mean_v", "rstd_v",
+                           nullptr, 1.f));
+    }
+    if (s.mt == VQA_MODEL_ADAPT) {     // v_adapt: a second FC + LN[R,H] + ReLU on the same V_ft (:132-135)
+        VQA_REQUIRE(P->v_adapt.w != nullptr && P->v_adapt.gamma != nullptr, VQA_ERR_ARG);
+        TRY(fc_ln_relu_fwd(cv, cv.f("V_ft"), B * R, D, H, P->v_adapt, (int)R, "pre_va", "v_adapt", "mean_va", "rstd_va",
+                           nullptr, 1.f));
+    }
+    return VQA_OK;
+}
+
+// a3 + a4: embedding lookup, x-projection of all steps, recurrence.  Leaves the question code in s.q_ft / s.qv_in.
+int fwd_question(Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, H = s.H, T = s.T, W = s.W, Wp = s.Wp;
+    if (s.mt == VQA_MODEL_BI) {
+        TRY(bi_question_fwd(c, P, bt));
+        s.q_ft = c.f("q_L_ft");
+        s.qv_in = c.f("pooled_q_v");
+        return VQA_OK;
+    }
     // a3: embedding lookup, time-major
     // x_tm rows carry the constant 1 after the W inputs (vqa_embed_fwd_ld): the x-part weight-gradient GEMM then also
     // delivers the bias gradients, and the two passes over dxp that summed its columns are gone
-    const int64_t Wp = ((W + 1 + 3) / 4) * 4;
     {
         ProbeScope ps("embed.fwd", c.st);
-        TRY(vqa_embed_fwd_ld(P->embed, bt->q_intseq, c.f("x_tm"), (int)B, (int)T, (int)W, dims->Vq, (int)Wp, c.st));
+        TRY(vqa_embed_fwd_ld(P->embed, bt->q_intseq, c.f("x_tm"), (int)B, (int)T, (int)W, s.d.Vq, (int)Wp, c.st));
     }
-    // a4: GRU.  Input projections of all steps as two big GEMMs ...
+    // a4: GRU.  Input projections of all steps as one packed GEMM (or the two-GEMM form) ...
     float* xp = c.f("xp");
     {
-    ProbeScope ps("gru.xp_gemm", c.st);
-    if (xcat_enabled()) {
-        TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-        TRY(gemm_f32(c, 0, 0, T * B, 3 * H, W, c.f("x_tm"), (int)Wp, c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H), c.f("bx_cat")));
-    } else {
-        TRY(gemm_f32(c, 0, 0, T * B, 2 * H, W, c.f("x_tm"), (int)Wp, P->gru_wg, (int)(2 * H), xp, (int)(3 * H), P->gru_bg));
-        TRY(gemm_f32(c, 0, 0, T * B, H, W, c.f("x_tm"), (int)Wp, P->gru_wc, (int)H, xp + 2 * H, (int)(3 * H), P->gru_bc));
-    }
-    }
-    float* hs = c.f("hs");
-    if (hipMemsetAsync(hs, 0, (size_t)B * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-    const float* Wg_h = P->gru_wg + W * 2 * H;
-    const float* Wc_h = P->gru_wc + W * H;
-    {
-        ProbeScope ps("gru.fwd", c.st);
-        // (a length-sorted batch whose longest row runs to T: the weight-stationary launch computes every row of every step
-        // under its length mask -- same results -- and is faster than the shrinking per-step kernels at these sizes)
-        const bool ws_ok = gru_ws_on() && (bt->live_rows == nullptr || (T > 0 && bt->live_rows[T - 1] > 0));
-        if (ws_ok && vqa_gru_ws_supported((int)T, (int)B, (int)H) == 1) {
-            // one launch, recurrent weights resident in registers and LDS, eight XCD-local chains (csrc/gru_ws.hip)
-            TRY(vqa_gru_seq_fwd_ws(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), c.f("gru_rh"),
-                                   (int)T, (int)B, (int)H, c.f("gru_ws"), c.st));
-        } else if (bt->live_rows != nullptr) {          // rows sorted by length: skip finished sequences
-            TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
-                                     c.f("gru_c"), c.f("gru_rh"), (int)T, (int)B, (int)H, c.st));
-        } else {                                  // independent row chains in anti-phase (gru_chains)
-            float* gr = c.f("gru_r"); float* gu = c.f("gru_u"); float* gc = c.f("gru_c"); float* grh = c.f("gru_rh");
-            TRY(run_chains(c, B, [&](int, int64_t row0, int64_t rows, hipStream_t st) {
-                return vqa_gru_seq_fwd_rows(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, gr, gu, gc, grh, (int)T, (int)B, (int)H,
-                                            (int)row0, (int)rows, st);
-            }));
+        ProbeScope ps("gru.xp_gemm", c.st);
+        if (xcat_enabled()) {
+            TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
+            TRY(gemm_f32(c, 0, 0, T * B, 3 * H, W, c.f("x_tm"), (int)Wp, c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H), c.f("bx_cat")));
+        } else {
+            TRY(gemm_f32(c, 0, 0, T * B, 2 * H, W, c.f("x_tm"), (int)Wp, P->gru_wg, (int)(2 * H), xp, (int)(3 * H), P->gru_bg));
+            TRY(gemm_f32(c, 0, 0, T * B, H, W, c.f("x_tm"), (int)Wp, P->gru_wc, (int)H, xp + 2 * H, (int)(3 * H), P->gru_bc));
         }
     }
-    h = hs + T * B * H;
-    qv_in = h;
+    // ... then the recurrence
+    float* hs = c.f("hs");
+    if (hipMemsetAsync(hs, 0, (size_t)B * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+    const float* Wg_h = s.Wg_h();
+    const float* Wc_h = s.Wc_h();
+    {
+        ProbeScope ps("gru.fwd", c.st);
+        switch (gru_form(GRU_FWD, T, B, H, bt->live_rows)) {
+            case GRU_WS:
+                TRY(vqa_gru_seq_fwd_ws(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), c.f("gru_rh"),
+                                       (int)T, (int)B, (int)H, c.f("gru_ws"), c.st));
+                break;
+            case GRU_LIVE:
+                TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
+                                         c.f("gru_c"), c.f("gru_rh"), (int)T, (int)B, (int)H, c.st));
+                break;
+            case GRU_CHAINS: {
+                float* gr = c.f("gru_r"); float* gu = c.f("gru_u"); float* gc = c.f("gru_c"); float* grh = c.f("gru_rh");
+                TRY(run_chains(c, B, [&](int, int64_t row0, int64_t rows, hipStream_t st) {
+                    return vqa_gru_seq_fwd_rows(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, gr, gu, gc, grh, (int)T, (int)B, (int)H,
+                                                (int)row0, (int)rows, st);
+                }));
+                break;
+            }
+        }
     }
-    // what q_linear_l reads: the GRU state, or one of the ablations' layers on top of it
-    const float* lin_in = h;
-    if (mt == VQA_MODEL_ANSWER2) {           // q_L_ft2 = tanh(LN(fc(q_L_ft)))   (vqa/model_vlmap_answer2.py:127-130)
+    s.q_ft = hs + T * B * H;
+    s.qv_in = s.q_ft;
+    return VQA_OK;
+}
+
+// the ablations' layer between the question code and q_linear_l; leaves what q_linear_l reads in s.lin_in
+int fwd_question_code(Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const int64_t B = s.B, H = s.H;
+    const float* h = s.q_ft;
+    s.lin_in = h;
+    if (s.mt == VQA_MODEL_ANSWER2) {           // q_L_ft2 = tanh(LN(fc(q_L_ft)))   (vqa/model_vlmap_answer2.py:127-130)
         VQA_REQUIRE(P->q_L_ft2.w != nullptr && P->q_L_ft2.gamma != nullptr, VQA_ERR_ARG);
         ProbeScope ps("fc.fwd_gemm", c.st);
         TRY(gemm(c, 0, 0, B, H, H, h, (int)H, P->q_L_ft2.w, (int)H, c.f("pre_ft2"), (int)H, P->q_L_ft2.b));
         TRY(vqa_ln_act_fwd(c.f("pre_ft2"), P->q_L_ft2.gamma, P->q_L_ft2.beta, nullptr, 1.f, c.f("q_L_ft2"), c.f("mean_ft2"),
                            c.f("rstd_ft2"), (int)B, 1, (int)H, 1, c.st));
-        lin_in = c.f("q_L_ft2");
-    } else if (mt == VQA_MODEL_NO_NOISE || mt == VQA_MODEL_FULL) {     // q_L_mean: a plain linear layer (:122-125)
+        s.lin_in = c.f("q_L_ft2");
+    } else if (s.mt == VQA_MODEL_NO_NOISE || s.mt == VQA_MODEL_FULL) {     // q_L_mean: a plain linear layer (:122-125)
         VQA_REQUIRE(P->q_L_mean.w != nullptr, VQA_ERR_ARG);
         ProbeScope ps("fc.fwd_gemm", c.st);
         TRY(gemm(c, 0, 0, B, H, H, h, (int)H, P->q_L_mean.w, (int)H, c.f("q_L_mean"), (int)H, P->q_L_mean.b));
-        lin_in = c.f("q_L_mean");
-        if (mt == VQA_MODEL_FULL) {          // reparameterisation (vqa/model_vlmap_answer_full.py:128-134)
-            VQA_REQUIRE(P->q_L_log_sigma_sq.w != nullptr && bt->noise != nullptr, VQA_ERR_ARG);
+        s.lin_in = c.f("q_L_mean");
+        if (s.mt == VQA_MODEL_FULL) {          // reparameterisation (vqa/model_vlmap_answer_full.py:128-134)
+            VQA_REQUIRE(P->q_L_log_sigma_sq.w != nullptr && s.bt->noise != nullptr, VQA_ERR_ARG);
             TRY(gemm(c, 0, 0, B, H, H, h, (int)H, P->q_L_log_sigma_sq.w, (int)H, c.f("q_L_log_sigma_sq"), (int)H,
                      P->q_L_log_sigma_sq.b));
-            TRY(vqa_reparam_fwd(c.f("q_L_mean"), c.f("q_L_log_sigma_sq"), bt->noise, c.f("q_L_mean_noise"), c.f("extra_row"),
+            TRY(vqa_reparam_fwd(c.f("q_L_mean"), c.f("q_L_log_sigma_sq"), s.bt->noise, c.f("q_L_mean_noise"), c.f("extra_row"),
                                 (int)B, (int)H, c.st));
-            lin_in = c.f("q_L_mean_noise");
+            s.lin_in = c.f("q_L_mean_noise");
         }
     }
-    // a5
-    TRY(fc_ln_relu_fwd(c, qv_in, B, H, H, P->q_linear_v, 1, "pre_qv", "q_linear_v", "mean_qv", "rstd_qv", nullptr, 1.f));
-    if (forked && hipStreamWaitEvent(c.st, sd.join, 0) != hipSuccess) return VQA_ERR_LAUNCH;
-    if (visual_late) TRY(visual_branch());
-    // a6 + a7 (vlmap_answer_adapt pools v_adapt [R,H] instead of V_ft [R,D])
-    const int64_t Dp = pooled_dim(*dims);
-    {
+    return VQA_OK;
+}
+
+// a5
+int fwd_q_linear_v(const Step& s) {
+    return fc_ln_relu_fwd(s.c, s.qv_in, s.B, s.H, s.H, s.P->q_linear_v, 1, "pre_qv", "q_linear_v", "mean_qv", "rstd_qv", nullptr, 1.f);
+}
+
+// a6 + a7: Hadamard attention and pooling (vlmap_answer_adapt pools v_adapt [R,H] instead of V_ft [R,D])
+int fwd_attention(const Step& s) {
+    const Ctx& c = s.c;
     ProbeScope ps("attn_pool.fwd", c.st);
-    TRY(vqa_attn_pool_fwd(c.f("v_linear_v"), c.f("q_linear_v"), c.f(mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
-                          c.i32("num_V_ft"), P->score.w, P->score.b, bt->keep_att, dims->keep_att, c.f("att_score"),
-                          c.f("pooled_V_ft"), (int)B, (int)R, (int)H, (int)Dp, c.st));
+    return vqa_attn_pool_fwd(c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
+                             c.i32("num_V_ft"), s.P->score.w, s.P->score.b, s.bt->keep_att, s.d.keep_att, c.f("att_score"),
+                             c.f("pooled_V_ft"), (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
+}
+
+// a8: pooled_linear_l and q_linear_l; the paired form also leaves their product in joint_in
+int fwd_linear_l(Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const int64_t B = s.B, H = s.H, Dp = s.Dp;
+    s.pair = ln_pair_ok(s.d, P);
+    if (!s.pair) {
+        TRY(fc_ln_relu_fwd(c, c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, 1, "pre_pl", "pooled_linear_l", "mean_pl",
+                           "rstd_pl", nullptr, 1.f));
+        return fc_ln_relu_fwd(c, s.lin_in, B, H, H, P->q_linear_l, 1, "pre_ll", "l_linear_l", "mean_ll", "rstd_ll", nullptr, 1.f);
     }
-    // a8
-    const bool pair = ln_pair_ok(*dims, P);
-    if (pair) {
-        {
-            ProbeScope ps("fc.fwd_gemm", c.st);
-            TRY(gemm(c, 0, 0, B, H, Dp, c.f("pooled_V_ft"), (int)Dp, P->pooled_linear_l.w, (int)H, c.f("pre_pl"), (int)H,
-                     P->pooled_linear_l.b));
-            TRY(gemm(c, 0, 0, B, H, H, lin_in, (int)H, P->q_linear_l.w, (int)H, c.f("pre_ll"), (int)H, P->q_linear_l.b));
-        }
-        ProbeScope ps("fc.ln_fwd", c.st);
-        TRY(vqa_ln_pair_mul_fwd(c.f("pre_pl"), c.f("pre_ll"), P->pooled_linear_l.gamma, P->pooled_linear_l.beta, P->q_linear_l.gamma,
-                                P->q_linear_l.beta, c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("joint_in"), c.f("mean_pl"),
-                                c.f("rstd_pl"), c.f("mean_ll"), c.f("rstd_ll"), (int)B, (int)H, c.st));
-    } else {
-    TRY(fc_ln_relu_fwd(c, c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, 1, "pre_pl", "pooled_linear_l", "mean_pl",
-                       "rstd_pl", nullptr, 1.f));
-    TRY(fc_ln_relu_fwd(c, lin_in, B, H, H, P->q_linear_l, 1, "pre_ll", "l_linear_l", "mean_ll", "rstd_ll", nullptr, 1.f));
+    {
+        ProbeScope ps("fc.fwd_gemm", c.st);
+        TRY(gemm(c, 0, 0, B, H, Dp, c.f("pooled_V_ft"), (int)Dp, P->pooled_linear_l.w, (int)H, c.f("pre_pl"), (int)H,
+                 P->pooled_linear_l.b));
+        TRY(gemm(c, 0, 0, B, H, H, s.lin_in, (int)H, P->q_linear_l.w, (int)H, c.f("pre_ll"), (int)H, P->q_linear_l.b));
     }
-    // a9
-    if (dims->model_type == 5) {
+    ProbeScope ps("fc.ln_fwd", c.st);
+    return vqa_ln_pair_mul_fwd(c.f("pre_pl"), c.f("pre_ll"), P->pooled_linear_l.gamma, P->pooled_linear_l.beta, P->q_linear_l.gamma,
+                               P->q_linear_l.beta, c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("joint_in"), c.f("mean_pl"),
+                               c.f("rstd_pl"), c.f("mean_ll"), c.f("rstd_ll"), (int)B, (int)H, c.st);
+}
+
+// a9: the joint layer on the product of the two branches (dropout .5); vlmap_answer_noc keeps the branches apart
+int fwd_joint(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, H = s.H;
+    if (s.mt == VQA_MODEL_NOC) {
         // vlmap_answer_noc (vqa/model_vlmap_answer_noc.py:177-188): no composition -- joint_v on pooled_linear_l and joint_l
         // on l_linear_l, each FC + LN + ReLU + dropout .5 ("joint" holds v_joint)
         VQA_REQUIRE(P->joint2.w != nullptr && P->head2.w != nullptr, VQA_ERR_ARG);
         TRY(fc_ln_relu_fwd(c, c.f("pooled_linear_l"), B, H, 2 * H, P->joint_fc, 1, "pre_j", "joint", "mean_j", "rstd_j",
-                           bt->keep_joint, dims->keep_joint));
-        TRY(fc_ln_relu_fwd(c, c.f("l_linear_l"), B, H, 2 * H, P->joint2, 1, "pre_jl", "l_joint", "mean_jl", "rstd_jl",
-                           bt->keep_joint2, dims->keep_joint));
-    } else {
-    if (!pair) {
+                           bt->keep_joint, s.d.keep_joint));
+        return fc_ln_relu_fwd(c, c.f("l_linear_l"), B, H, 2 * H, P->joint2, 1, "pre_jl", "l_joint", "mean_jl", "rstd_jl",
+                              bt->keep_joint2, s.d.keep_joint);
+    }
+    if (!s.pair) {
         ProbeScope ps("eltwise", c.st);
         TRY(vqa_mul(c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("joint_in"), B * H, c.st));
     }
-    TRY(fc_ln_relu_fwd(c, c.f("joint_in"), B, H, 2 * H, P->joint_fc, 1, "pre_j", "joint", "mean_j", "rstd_j",
-                       bt->keep_joint, dims->keep_joint));
-    }
-    // a10
-    if (dims->model_type == 2) {
+    return fc_ln_relu_fwd(c, c.f("joint_in"), B, H, 2 * H, P->joint_fc, 1, "pre_j", "joint", "mean_j", "rstd_j", bt->keep_joint,
+                          s.d.keep_joint);
+}
+
+// a10: the answer head
+int fwd_head(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const int64_t B = s.B, H = s.H, W = s.W, A = s.A;
+    if (s.mt == VQA_MODEL_WORD2VEC) {
         // standard_word2vec (vqa/model_standard_word2vec.py:180-188): classifier FC into the 300-d word space, then
         // logits = joint2 x the constant [W, A] GloVe matrix of the answers
         VQA_REQUIRE(P->answer_glove != nullptr, VQA_ERR_ARG);
         ProbeScope ps("head.fwd_gemm", c.st);
         TRY(gemm(c, 0, 0, B, W, 2 * H, c.f("joint"), (int)(2 * H), P->head.w, (int)W, c.f("joint2"), (int)W, P->head.b));
         TRY(gemm(c, 0, 0, B, A, W, c.f("joint2"), (int)W, P->answer_glove, (int)A, c.f("logit"), (int)A));
-    } else if (dims->model_type == 5) {
+    } else if (s.mt == VQA_MODEL_NOC) {
         // logit = WordWeightAnswerV(v_joint) + WordWeightAnswerL(l_joint)   (:190-204): the second GEMM adds onto the first
         ProbeScope ps("head.fwd_gemm", c.st);
         TRY(gemm(c, 0, 0, B, A, 2 * H, c.f("joint"), (int)(2 * H), P->head.w, (int)A, c.f("logit"), (int)A, P->head.b));
         TRY(gemm(c, 0, 0, B, A, 2 * H, c.f("l_joint"), (int)(2 * H), P->head2.w, (int)A, c.f("logit"), (int)A, P->head2.b,
                  c.f("logit"), (int)A));
-    } else if (dims->model_type == 4 || dims->model_type == 6) {
+    } else if (has_tuned_head(s.mt)) {
         // vlmap_answer_vqa_all2 (vqa/model_vlmap_answer_vqa_all2.py:196-227): the fixed WordWeightAnswer head and the
         // trainable TunedWordWeightAnswer head, BOTH on `joint` (the reference's tuned head reads `joint`, :216-217);
         // _vqa_all: the same with the fixed logits of unknown answers moved to the row minimum (:192-194)
         VQA_REQUIRE(P->head2.w != nullptr && P->head2.b != nullptr, VQA_ERR_ARG);
         ProbeScope ps("head.fwd_gemm", c.st);
         TRY(gemm(c, 0, 0, B, A, 2 * H, c.f("joint"), (int)(2 * H), P->head.w, (int)A,
-                 c.f(dims->model_type == 6 ? "logit_raw" : "logit_fixed"), (int)A, P->head.b));
-        if (dims->model_type == 6)
-            TRY(vqa_rowmin_mask_fwd(c.f("logit_raw"), bt->exist_mask, c.f("logit_fixed"), c.f("rowmin"), (int)B, (int)A, c.st));
+                 c.f(s.mt == VQA_MODEL_VQA_ALL ? "logit_raw" : "logit_fixed"), (int)A, P->head.b));
+        if (s.mt == VQA_MODEL_VQA_ALL)
+            TRY(vqa_rowmin_mask_fwd(c.f("logit_raw"), s.bt->exist_mask, c.f("logit_fixed"), c.f("rowmin"), (int)B, (int)A, c.st));
         TRY(gemm(c, 0, 0, B, A, 2 * H, c.f("joint"), (int)(2 * H), P->head2.w, (int)A, c.f("logit_tuned"), (int)A, P->head2.b));
     } else {
         ProbeScope ps("head.fwd_gemm", c.st);
         TRY(gemm(c, 0, 0, B, A, 2 * H, c.f("joint"), (int)(2 * H), P->head.w, (int)A, c.f("logit"), (int)A, P->head.b));
     }
-    // a11 (the train loss is masked by the train-answer mask in vlmap_answer and standard_word2vec, not in standard)
+    return VQA_OK;
+}
+
+// a11: loss, argmax and report; the entropy regulariser's forward and the extra report ride in the same scope
+int fwd_loss(const Step& s, int want_dz) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, H = s.H, A = s.A;
     ProbeScope ps("loss.fwd", c.st);
-    if (dims->model_type == 4 || dims->model_type == 6)
+    if (has_tuned_head(s.mt))
         TRY(vqa_loss2_fwd(c.f("logit_fixed"), c.f("logit_tuned"), bt->answer_target, bt->train_mask, bt->obj_mask,
-                          bt->attr_mask, bt->exist_mask, dims->inv_global_batch, c.f("stats"), c.i32("pred"),
+                          bt->attr_mask, bt->exist_mask, s.d.inv_global_batch, c.f("stats"), c.i32("pred"),
                           want_dz ? c.f("dlogit") : nullptr, want_dz ? c.f("dlogit_tuned") : nullptr, c.f("logit"),
-                          dims->model_type == 6 ? 1 : 0, (int)B, (int)A, c.st));
+                          s.mt == VQA_MODEL_VQA_ALL ? 1 : 0, (int)B, (int)A, c.st));
     else
         TRY(vqa_loss_fwd(c.f("logit"), bt->answer_target, bt->train_mask, bt->obj_mask, bt->attr_mask, bt->exist_mask,
-                         dims->model_type != 1 ? 1 : 0, dims->inv_global_batch, c.f("stats"), c.i32("pred"),
+                         train_loss_masked(s.mt) ? 1 : 0, s.d.inv_global_batch, c.f("stats"), c.i32("pred"),
                          want_dz ? c.f("dlogit") : nullptr, (int)B, (int)A, c.st));
     TRY(vqa_report_reduce(c.f("stats"), (int)B, c.f("report"), c.st));
-    if (mt == VQA_MODEL_ENT) {
+    if (s.mt == VQA_MODEL_ENT) {
         // Maximum entropy regularisation (vqa/model_vlmap_answer_ent.py:191-211, 281-292): joint_fc (+ its own dropout)
         // and the head's first ent_cols columns on num_marginal pairings of every question; tile_z ends up holding
         // d loss / d logit of the pairings (want_dz) or their probabilities
-        ProbeScope ps("ent.fwd", c.st);
-        const int64_t M = dims->num_marginal, C = dims->ent_cols;
+        ProbeScope ps_ent("ent.fwd", c.st);
+        const int64_t M = s.d.num_marginal, C = s.d.ent_cols;
         TRY(vqa_tile_mul_fwd(c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("tile_in"), (int)B, (int)M, (int)H, c.st));
         TRY(gemm(c, 0, 0, B * M, 2 * H, H, c.f("tile_in"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("pre_tj"), (int)(2 * H),
                  P->joint_fc.b));
-        TRY(vqa_ln_relu_fwd(c.f("pre_tj"), P->joint_fc.gamma, P->joint_fc.beta, bt->keep_tile, dims->keep_joint,
+        TRY(vqa_ln_relu_fwd(c.f("pre_tj"), P->joint_fc.gamma, P->joint_fc.beta, bt->keep_tile, s.d.keep_joint,
                             c.f("tile_joint"), c.f("mean_tj"), c.f("rstd_tj"), (int)B, (int)M, (int)(2 * H), c.st));
         TRY(gemm(c, 0, 0, B * M, C, 2 * H, c.f("tile_joint"), (int)(2 * H), P->head.w, (int)A, c.f("tile_z"), (int)C, P->head.b));
-        TRY(vqa_marginal_entropy(c.f("tile_z"), bt->train_mask, bt->exist_mask, dims->extra_weight * dims->inv_global_batch,
+        TRY(vqa_marginal_entropy(c.f("tile_z"), bt->train_mask, bt->exist_mask, s.d.extra_weight * s.d.inv_global_batch,
                                  c.f("marginal_prob"), c.f("extra_row"), (int)B, (int)M, (int)C, (int)C, want_dz, c.st));
     }
-    if (mt == VQA_MODEL_FULL || mt == VQA_MODEL_ENT)      // latent_loss | entropy, its weighted form and the total loss
-        TRY(vqa_extra_report(c.f("extra_row"), c.f("stats"), (int)B, dims->extra_weight, c.f("report"), c.st));
+    if (s.mt == VQA_MODEL_FULL || s.mt == VQA_MODEL_ENT)      // latent_loss | entropy, its weighted form and the total loss
+        TRY(vqa_extra_report(c.f("extra_row"), c.f("stats"), (int)B, s.d.extra_weight, c.f("report"), c.st));
     return VQA_OK;
+}
+
+}  // namespace
+
+extern "C" int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_batch_t* bt,
+                                  void* workspace, int64_t workspace_bytes, int want_dz, void* stream) {
+    VQA_REQUIRE(dims_ok(dims) && P && bt && workspace, VQA_ERR_ARG);
+    Step s(dims, P, nullptr, bt, workspace, stream);
+    VQA_REQUIRE(workspace_bytes >= s.L.total, VQA_ERR_WORKSPACE);
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    ProbeScope ps_all("forward", s.c.st);
+    if (s.mt == VQA_MODEL_LEGACY_VQA) return legacy_vqa_forward(s.c, P, bt, want_dz);
+
+    // visual branch (a1 + a2) on the side stream (VQA_HOT_OVERLAP=1 only), question branch (a3-a5) on the caller's
+    fwd_visual_plan(s);
+    if (!s.visual_late) TRY(fwd_visual(s));
+    TRY(side_record(s));
+    TRY(fwd_question(s));
+    TRY(fwd_question_code(s));
+    TRY(fwd_q_linear_v(s));
+    TRY(side_wait(s));
+    if (s.visual_late) TRY(fwd_visual(s));
+    TRY(fwd_attention(s));
+    TRY(fwd_linear_l(s));
+    TRY(fwd_joint(s));
+    TRY(fwd_head(s));
+    return fwd_loss(s, want_dz);
 }
 
 extern "C" int vqa_fusion_backward(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_params_t* G,
@@ -910,35 +1042,18 @@ extern "C" int vqa_fusion_backward(const vqa_dims_t* dims, const vqa_params_t* P
     return vqa_fusion_backward_phases(dims, P, G, bt, workspace, workspace_bytes, embed_slice_sq, 15, stream);
 }
 
-// phases (bit mask), in dependency order:
-//   1  head .. attention .. v_linear_v / q_linear_v / score gradients      (complete after this phase)
-//   2  GRU back-propagation through time, dx, embedding scatter-add, slice sum of squares
-//   4  GRU gate weight / bias gradients (the larger half, 10.8 MB at H 1024)
-//   8  GRU candidate weight / bias gradients (5.4 MB) -- the only all-reduce nothing is left to overlap with
-// so a data-parallel caller can start all-reducing each gradient bucket while the next phase runs.
-extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_params_t* G,
-                                          const vqa_batch_t* bt, void* workspace, int64_t workspace_bytes,
-                                          float* embed_slice_sq, int phases, void* stream) {
-    VQA_REQUIRE(dims_ok(dims) && P && G && bt && workspace, VQA_ERR_ARG);
-    const Layout L = make_layout(*dims);
-    Ctx c{*dims, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), 0};
-    VQA_REQUIRE(workspace_bytes >= c.L.total, VQA_ERR_WORKSPACE);
-    ProbeScope ps_all("backward", c.st);
-    if (dims->model_type == VQA_MODEL_LEGACY_VQA) return (phases & 1) ? legacy_vqa_backward(c, P, G, bt, embed_slice_sq) : VQA_OK;
-    const int64_t B = dims->B, R = dims->R, D = dims->D, H = dims->H, T = dims->T, W = dims->W, A = dims->A;
-    const int64_t Wp = ((W + 1 + 3) / 4) * 4;      // row stride of x_tm (make_layout)
-    const float* hs = c.f("hs");
-    const float* h = hs + T * B * H;
-    float* dh = c.f("d_h0");
-    float* dxp = c.f("dxp");
-    const int mt = dims->model_type;
-    const int64_t Dp = pooled_dim(*dims);
-    const bool pair = ln_pair_ok(*dims, P);
+namespace {
 
-    if (phases & 1) {
-    {
+// ---------------------------------------------------------------- backward stages: phase 1 in launch order, then 2, 4, 8
+
+// the answer head: dlogit -> the head's gradients and d_joint
+int bwd_head(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_params_t* G = s.G;
+    const int64_t B = s.B, H = s.H, W = s.W, A = s.A;
     ProbeScope ps_head("head.bwd_gemm", c.st);
-    if (dims->model_type == 2) {
+    if (s.mt == VQA_MODEL_WORD2VEC) {
         // word2vec head: d_joint2 = dlogit * G^T (the GloVe matrix is a constant), then the classifier FC
         VQA_REQUIRE(P->answer_glove != nullptr, VQA_ERR_ARG);
         TRY(gemm(c, 0, 1, B, W, A, c.f("dlogit"), (int)A, P->answer_glove, (int)A, c.f("d_joint2"), (int)W));
@@ -946,17 +1061,17 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
             TRY(gemm(c, 1, 0, 2 * H, W, B, c.f("joint"), (int)(2 * H), c.f("d_joint2"), (int)W, G->head.w, (int)W));
             TRY(colsum(c, c.f("d_joint2"), B, W, (int)W, G->head.b));
         }
-        TRY(gemm(c, 0, 1, B, 2 * H, W, c.f("d_joint2"), (int)W, P->head.w, (int)W, c.f("d_joint"), (int)(2 * H)));
-    } else {
-    if (dims->model_type == 6)       // back through the row-minimum substitution, in place (dlogit was taken wrt the masked logits)
-        TRY(vqa_rowmin_mask_bwd(c.f("dlogit"), c.f("logit_raw"), c.f("rowmin"), bt->exist_mask, (int)B, (int)A, c.st));
+        return gemm(c, 0, 1, B, 2 * H, W, c.f("d_joint2"), (int)W, P->head.w, (int)W, c.f("d_joint"), (int)(2 * H));
+    }
+    if (s.mt == VQA_MODEL_VQA_ALL)       // back through the row-minimum substitution, in place (dlogit was taken wrt the masked logits)
+        TRY(vqa_rowmin_mask_bwd(c.f("dlogit"), c.f("logit_raw"), c.f("rowmin"), s.bt->exist_mask, (int)B, (int)A, c.st));
     // head: logit = joint*W + b
     if (G->head.w != nullptr) {
         TRY(gemm(c, 1, 0, 2 * H, A, B, c.f("joint"), (int)(2 * H), c.f("dlogit"), (int)A, G->head.w, (int)A));
         TRY(colsum(c, c.f("dlogit"), B, A, (int)A, G->head.b));
     }
     TRY(gemm(c, 0, 1, B, 2 * H, A, c.f("dlogit"), (int)A, P->head.w, (int)A, c.f("d_joint"), (int)(2 * H)));
-    if (dims->model_type == 4 || dims->model_type == 6) {     // the tuned head: its own weights train, and its dz joins d_joint (unmasked term of the loss)
+    if (has_tuned_head(s.mt)) {     // the tuned head: its own weights train, and its dz joins d_joint (unmasked term of the loss)
         VQA_REQUIRE(P->head2.w != nullptr, VQA_ERR_ARG);
         if (G->head2.w != nullptr) {
             TRY(gemm(c, 1, 0, 2 * H, A, B, c.f("joint"), (int)(2 * H), c.f("dlogit_tuned"), (int)A, G->head2.w, (int)A));
@@ -965,69 +1080,101 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         TRY(gemm(c, 0, 1, B, 2 * H, A, c.f("dlogit_tuned"), (int)A, P->head2.w, (int)A, c.f("d_joint"), (int)(2 * H), nullptr,
                  c.f("d_joint"), (int)(2 * H)));
     }
-    }
-    }
-    if (dims->model_type == 5) {
-        // vlmap_answer_noc: the two branches separately, straight into d_pl / d_ll (no product to differentiate)
+    return VQA_OK;
+}
+
+// the joint layer: d_joint -> d_pl / d_ll (d_joint_in under the paired LayerNorm, whose backward differentiates the product)
+int bwd_joint(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_params_t* G = s.G;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, H = s.H, A = s.A;
+    if (s.mt == VQA_MODEL_NOC) {
+        // vlmap_answer_noc: the two branches separately, straight into d_pl / d_ll (no product to differentiate); the
+        // l_joint branch's head first
         if (G->head2.w != nullptr) {
             TRY(gemm(c, 1, 0, 2 * H, A, B, c.f("l_joint"), (int)(2 * H), c.f("dlogit"), (int)A, G->head2.w, (int)A));
             TRY(colsum(c, c.f("dlogit"), B, A, (int)A, G->head2.b));
         }
         TRY(gemm(c, 0, 1, B, 2 * H, A, c.f("dlogit"), (int)A, P->head2.w, (int)A, c.f("d_ljoint"), (int)(2 * H)));
         TRY(fc_ln_relu_bwd(c, c.f("d_joint"), c.f("pooled_linear_l"), B, H, 2 * H, P->joint_fc, &G->joint_fc, 1, "pre_j",
-                           "mean_j", "rstd_j", bt->keep_joint, dims->keep_joint, "d_pre_j", c.f("d_pl"), false));
-        TRY(fc_ln_relu_bwd(c, c.f("d_ljoint"), c.f("l_linear_l"), B, H, 2 * H, P->joint2, &G->joint2, 1, "pre_jl", "mean_jl",
-                           "rstd_jl", bt->keep_joint2, dims->keep_joint, "d_pre_jl", c.f("d_ll"), false));
-    } else {
+                           "mean_j", "rstd_j", bt->keep_joint, s.d.keep_joint, "d_pre_j", c.f("d_pl"), false));
+        return fc_ln_relu_bwd(c, c.f("d_ljoint"), c.f("l_linear_l"), B, H, 2 * H, P->joint2, &G->joint2, 1, "pre_jl", "mean_jl",
+                              "rstd_jl", bt->keep_joint2, s.d.keep_joint, "d_pre_jl", c.f("d_ll"), false);
+    }
     // joint_fc (dropout mask folded into the LN/ReLU backward)
     TRY(fc_ln_relu_bwd(c, c.f("d_joint"), c.f("joint_in"), B, H, 2 * H, P->joint_fc, &G->joint_fc, 1, "pre_j", "mean_j",
-                       "rstd_j", bt->keep_joint, dims->keep_joint, "d_pre_j", c.f("d_joint_in"), false));
-    if (!pair) {
+                       "rstd_j", bt->keep_joint, s.d.keep_joint, "d_pre_j", c.f("d_joint_in"), false));
+    if (!s.pair) {
         ProbeScope ps("eltwise", c.st);
         TRY(vqa_mul_bwd(c.f("d_joint_in"), c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("d_pl"), c.f("d_ll"), B * H,
                         c.st));
     }
-    }
-    if (mt == VQA_MODEL_ENT) {
-        // the regulariser's path back to l_linear_l (pooled_linear_l is behind tf.stop_gradient, :197): tile_z holds
-        // d loss / d logit; head and joint_fc are frozen (filter_train_vars :86-94), so only dX products run
-        ProbeScope ps("ent.bwd", c.st);
-        const int64_t M = dims->num_marginal, C = dims->ent_cols;
-        TRY(gemm(c, 0, 1, B * M, 2 * H, C, c.f("tile_z"), (int)C, P->head.w, (int)A, c.f("d_tile_joint"), (int)(2 * H)));
-        TRY(vqa_ln_relu_bwd(c.f("d_tile_joint"), c.f("pre_tj"), c.f("mean_tj"), c.f("rstd_tj"), P->joint_fc.gamma,
-                            P->joint_fc.beta, bt->keep_tile, dims->keep_joint, c.f("d_pre_tj"), nullptr, nullptr, nullptr,
-                            (int)B, (int)M, (int)(2 * H), c.st));
-        TRY(gemm(c, 0, 1, B * M, H, 2 * H, c.f("d_pre_tj"), (int)(2 * H), P->joint_fc.w, (int)(2 * H), c.f("d_tile_in"), (int)H));
-        // (paired LayerNorm backward: d_ll holds only this extra gradient and is added inside that kernel)
-        TRY(vqa_tile_mul_bwd(c.f("d_tile_in"), c.f("pooled_linear_l"), c.f("d_ll"), (int)B, (int)M, (int)H, pair ? 0 : 1, c.st));
-    }
-    // pooled_linear_l and q_linear_l: LayerNorm backward (paired with the product's, or each on its own), then the FC halves
+    return VQA_OK;
+}
+
+// vlmap_answer_ent: the regulariser's path back to l_linear_l (pooled_linear_l is behind tf.stop_gradient, :197): tile_z
+// holds d loss / d logit; head and joint_fc are frozen (filter_train_vars :86-94), so only dX products run
+int bwd_entropy(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const int64_t B = s.B, H = s.H, A = s.A;
+    ProbeScope ps("ent.bwd", c.st);
+    const int64_t M = s.d.num_marginal, C = s.d.ent_cols;
+    TRY(gemm(c, 0, 1, B * M, 2 * H, C, c.f("tile_z"), (int)C, P->head.w, (int)A, c.f("d_tile_joint"), (int)(2 * H)));
+    TRY(vqa_ln_relu_bwd(c.f("d_tile_joint"), c.f("pre_tj"), c.f("mean_tj"), c.f("rstd_tj"), P->joint_fc.gamma,
+                        P->joint_fc.beta, s.bt->keep_tile, s.d.keep_joint, c.f("d_pre_tj"), nullptr, nullptr, nullptr,
+                        (int)B, (int)M, (int)(2 * H), c.st));
+    TRY(gemm(c, 0, 1, B * M, H, 2 * H, c.f("d_pre_tj"), (int)(2 * H), P->joint_fc.w, (int)(2 * H), c.f("d_tile_in"), (int)H));
+    // (paired LayerNorm backward: d_ll holds only this extra gradient and is added inside that kernel)
+    return vqa_tile_mul_bwd(c.f("d_tile_in"), c.f("pooled_linear_l"), c.f("d_ll"), (int)B, (int)M, (int)H, s.pair ? 0 : 1, c.st);
+}
+
+// pooled_linear_l, and q_linear_l's LayerNorm where the two are paired: LayerNorm backward (paired with the product's, or
+// on its own), then pooled_linear_l's FC half
+int bwd_linear_l(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_params_t* G = s.G;
+    const int64_t B = s.B, H = s.H, Dp = s.Dp;
+    if (!s.pair)
+        return fc_ln_relu_bwd(c, c.f("d_pl"), c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, &G->pooled_linear_l, 1, "pre_pl",
+                              "mean_pl", "rstd_pl", nullptr, 1.f, "d_pre_pl", c.f("d_pooled"), false);
     const bool tr_pl = G->pooled_linear_l.w != nullptr, tr_ll = G->q_linear_l.w != nullptr;
-    if (pair) {
-        ProbeScope ps("fc.ln_bwd", c.st);
-        TRY(vqa_ln_pair_mul_bwd(c.f("d_joint_in"), mt == VQA_MODEL_ENT ? c.f("d_ll") : nullptr, c.f("pre_pl"), c.f("pre_ll"),
-                                c.f("mean_pl"), c.f("rstd_pl"), c.f("mean_ll"), c.f("rstd_ll"), P->pooled_linear_l.gamma,
-                                P->pooled_linear_l.beta, P->q_linear_l.gamma, P->q_linear_l.beta, c.f("d_pre_pl"), c.f("d_pre_ll"),
-                                tr_pl ? c.part(0) : nullptr, tr_pl ? c.part(1) : nullptr, tr_pl ? c.part(2) : nullptr,
-                                tr_ll ? c.f("part_a1") : nullptr, tr_ll ? c.f("part_b1") : nullptr, tr_ll ? c.f("part_c1") : nullptr,
-                                (int)B, (int)H, c.st));
-        TRY(fc_bwd_tail(c, c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, &G->pooled_linear_l, 1, c.f("d_pre_pl"), c.part(0),
-                        c.part(1), c.part(2), c.f("d_pooled"), false));
-    } else {
-    TRY(fc_ln_relu_bwd(c, c.f("d_pl"), c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, &G->pooled_linear_l, 1, "pre_pl",
-                       "mean_pl", "rstd_pl", nullptr, 1.f, "d_pre_pl", c.f("d_pooled"), false));
-    }
-    // q_linear_l's FC half (after its LayerNorm backward, unless the paired kernel did it): x = what the layer read
-    auto ll_bwd = [&](const float* x, float* dx) -> int {
-        if (pair)
-            return fc_bwd_tail(c, x, B, H, H, P->q_linear_l, &G->q_linear_l, 1, c.f("d_pre_ll"), c.f("part_a1"), c.f("part_b1"),
-                               c.f("part_c1"), dx, false);
-        return fc_ln_relu_bwd(c, c.f("d_ll"), x, B, H, H, P->q_linear_l, &G->q_linear_l, 1, "pre_ll", "mean_ll", "rstd_ll", nullptr,
-                              1.f, "d_pre_ll", dx, false);
-    };
-    if (mt == VQA_MODEL_ANSWER2) {
+    ProbeScope ps("fc.ln_bwd", c.st);
+    TRY(vqa_ln_pair_mul_bwd(c.f("d_joint_in"), s.mt == VQA_MODEL_ENT ? c.f("d_ll") : nullptr, c.f("pre_pl"), c.f("pre_ll"),
+                            c.f("mean_pl"), c.f("rstd_pl"), c.f("mean_ll"), c.f("rstd_ll"), P->pooled_linear_l.gamma,
+                            P->pooled_linear_l.beta, P->q_linear_l.gamma, P->q_linear_l.beta, c.f("d_pre_pl"), c.f("d_pre_ll"),
+                            tr_pl ? c.part(0) : nullptr, tr_pl ? c.part(1) : nullptr, tr_pl ? c.part(2) : nullptr,
+                            tr_ll ? c.f("part_a1") : nullptr, tr_ll ? c.f("part_b1") : nullptr, tr_ll ? c.f("part_c1") : nullptr,
+                            (int)B, (int)H, c.st));
+    return fc_bwd_tail(c, c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, &G->pooled_linear_l, 1, c.f("d_pre_pl"), c.part(0),
+                       c.part(1), c.part(2), c.f("d_pooled"), false);
+}
+
+// q_linear_l's FC half (after its LayerNorm backward, unless the paired kernel did it): x = what the layer read
+int q_linear_l_bwd(const Step& s, const float* x, float* dx) {
+    const Ctx& c = s.c;
+    const int64_t B = s.B, H = s.H;
+    if (s.pair)
+        return fc_bwd_tail(c, x, B, H, H, s.P->q_linear_l, &s.G->q_linear_l, 1, c.f("d_pre_ll"), c.f("part_a1"), c.f("part_b1"),
+                           c.f("part_c1"), dx, false);
+    return fc_ln_relu_bwd(c, c.f("d_ll"), x, B, H, H, s.P->q_linear_l, &s.G->q_linear_l, 1, "pre_ll", "mean_ll", "rstd_ll", nullptr,
+                          1.f, "d_pre_ll", dx, false);
+}
+
+// q_linear_l and the ablations' layer under it: d_ll -> dh, the gradient wrt the question code
+int bwd_question_code(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_params_t* G = s.G;
+    const int64_t B = s.B, H = s.H;
+    const float* h = s.h;
+    float* dh = s.dh;
+    if (s.mt == VQA_MODEL_ANSWER2) {
         // q_linear_l read q_L_ft2: back through it, then through tanh + LN + FC (trainable) into dh
-        TRY(ll_bwd(c.f("q_L_ft2"), c.f("d_ft2")));
+        TRY(q_linear_l_bwd(s, c.f("q_L_ft2"), c.f("d_ft2")));
         const bool train = G->q_L_ft2.w != nullptr;
         TRY(vqa_ln_act_bwd(c.f("d_ft2"), c.f("pre_ft2"), c.f("mean_ft2"), c.f("rstd_ft2"), P->q_L_ft2.gamma, P->q_L_ft2.beta,
                            nullptr, 1.f, c.f("d_pre_ft2"), train ? c.part(0) : nullptr, train ? c.part(1) : nullptr,
@@ -1037,15 +1184,16 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
                             G->q_L_ft2.b, c.colsum_ws(), c.colsum_ws_floats(), c.st));
             TRY(gemm(c, 1, 0, H, H, B, h, (int)H, c.f("d_pre_ft2"), (int)H, G->q_L_ft2.w, (int)H));
         }
-        TRY(gemm(c, 0, 1, B, H, H, c.f("d_pre_ft2"), (int)H, P->q_L_ft2.w, (int)H, dh, (int)H));
-    } else if (mt == VQA_MODEL_NO_NOISE || mt == VQA_MODEL_FULL) {
+        return gemm(c, 0, 1, B, H, H, c.f("d_pre_ft2"), (int)H, P->q_L_ft2.w, (int)H, dh, (int)H);
+    }
+    if (s.mt == VQA_MODEL_NO_NOISE || s.mt == VQA_MODEL_FULL) {
         // q_linear_l read q_L_mean (+ noise * sigma): linear layers on the GRU state
-        const bool full = mt == VQA_MODEL_FULL;
+        const bool full = s.mt == VQA_MODEL_FULL;
         float* d_in = c.f(full ? "d_lin" : "d_qm");
-        TRY(ll_bwd(c.f(full ? "q_L_mean_noise" : "q_L_mean"), d_in));
+        TRY(q_linear_l_bwd(s, c.f(full ? "q_L_mean_noise" : "q_L_mean"), d_in));
         if (full)      // through x = mean + noise * sigma, plus the KL term's own gradient (weight / global batch)
-            TRY(vqa_reparam_bwd(d_in, c.f("q_L_mean"), c.f("q_L_log_sigma_sq"), bt->noise,
-                                dims->extra_weight * dims->inv_global_batch, c.f("d_qm"), c.f("d_qs"), B * H, c.st));
+            TRY(vqa_reparam_bwd(d_in, c.f("q_L_mean"), c.f("q_L_log_sigma_sq"), s.bt->noise,
+                                s.d.extra_weight * s.d.inv_global_batch, c.f("d_qm"), c.f("d_qs"), B * H, c.st));
         if (G->q_L_mean.w != nullptr) {
             TRY(gemm(c, 1, 0, H, H, B, h, (int)H, c.f("d_qm"), (int)H, G->q_L_mean.w, (int)H));
             TRY(colsum(c, c.f("d_qm"), B, H, (int)H, G->q_L_mean.b));
@@ -1058,24 +1206,42 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
             }
             TRY(gemm(c, 0, 1, B, H, H, c.f("d_qs"), (int)H, P->q_L_log_sigma_sq.w, (int)H, dh, (int)H, nullptr, dh, (int)H));
         }
-    } else {
-    TRY(ll_bwd(mt == VQA_MODEL_BI ? c.f("q_L_ft") : h, dh));
+        return VQA_OK;
     }
-    // attention + pooling, and v_linear_v behind it.  With one query per memory d_v is rank one per region, so on one
-    // stream the chain runs fused ("The fused v_linear_v chain"): the attention backward stops at the score
-    // gradient ds, v_linear_v's LayerNorm backward forms d_v in registers and delivers d_qv and the score's weight partials,
-    // and one pair of launches reduces the five parameter gradients.  d_v is not written on this path.  The separate calls
-    // stay for the side stream (VQA_HOT_OVERLAP=1), for vlmap_answer_adapt (a second consumer of att_score and a 1024-wide
-    // memory), for frozen layers and for every other shape.
-    Side& sd = side_stream();
-    const bool vtail = vtail_mode() != 0 && !sd.ok && mt != VQA_MODEL_ADAPT && vqa_vtail_supported(1, (int)R, (int)H, (int)Dp) == 1 &&
-                       G->v_linear_v.w != nullptr && G->v_linear_v.gamma != nullptr && G->v_linear_v.beta != nullptr &&
-                       G->v_linear_v.b != nullptr && G->score.w != nullptr && G->score.b != nullptr && vqa_aligned16(c.f("d_pooled")) &&
-                       vqa_aligned16(P->score.w) && vqa_aligned16(P->v_linear_v.gamma) && vqa_aligned16(P->v_linear_v.beta) &&
-                       (bt->keep_att == nullptr || (reinterpret_cast<uintptr_t>(bt->keep_att) & 3u) == 0) &&
-                       vqa_aligned16(G->v_linear_v.gamma) && vqa_aligned16(G->v_linear_v.beta) && vqa_aligned16(G->v_linear_v.b) &&
-                       vqa_aligned16(G->score.w);
-    if (vtail) {
+    return q_linear_l_bwd(s, s.mt == VQA_MODEL_BI ? c.f("q_L_ft") : h, dh);
+}
+
+// Whether the backward of v_linear_v's LayerNorm and of the attention score runs as one chain ("The fused
+// v_linear_v chain"): on one stream, one query per memory, v_linear_v and the score trainable, 16-byte rows.  The separate
+// calls stay for the side stream (VQA_HOT_OVERLAP=1), for vlmap_answer_adapt (a second consumer of att_score and a
+// 1024-wide memory), for frozen layers and for every other shape.
+bool vtail_ok(const Step& s, const Side& sd) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_params_t* G = s.G;
+    const vqa_batch_t* bt = s.bt;
+    return vtail_mode() != 0 && !sd.ok && s.mt != VQA_MODEL_ADAPT && vqa_vtail_supported(1, (int)s.R, (int)s.H, (int)s.Dp) == 1 &&
+           G->v_linear_v.w != nullptr && G->v_linear_v.gamma != nullptr && G->v_linear_v.beta != nullptr &&
+           G->v_linear_v.b != nullptr && G->score.w != nullptr && G->score.b != nullptr && vqa_aligned16(c.f("d_pooled")) &&
+           vqa_aligned16(P->score.w) && vqa_aligned16(P->v_linear_v.gamma) && vqa_aligned16(P->v_linear_v.beta) &&
+           (bt->keep_att == nullptr || (reinterpret_cast<uintptr_t>(bt->keep_att) & 3u) == 0) &&
+           vqa_aligned16(G->v_linear_v.gamma) && vqa_aligned16(G->v_linear_v.beta) && vqa_aligned16(G->v_linear_v.b) &&
+           vqa_aligned16(G->score.w);
+}
+
+// attention + pooling, and v_linear_v behind it.  With one query per memory d_v is rank one per region, so the fused chain
+// stops the attention backward at the score gradient ds, v_linear_v's LayerNorm backward forms d_v in registers and delivers
+// d_qv and the score's weight partials, and one pair of launches reduces the five parameter gradients; d_v is not written on
+// that path.  Otherwise: the attention backward, v_adapt, the score's gradients, then v_linear_v's backward -- on the side
+// stream where there is one (its join is recorded here; side_wait follows q_linear_v).
+int bwd_attention(Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_params_t* G = s.G;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, R = s.R, D = s.D, H = s.H, Dp = s.Dp;
+    s.sd = &side_stream();
+    if (vtail_ok(s, *s.sd)) {
         {
             ProbeScope ps("attn_pool.bwd", c.st);
             TRY(vqa_attn_pool_bwd_ds(c.f("d_pooled"), c.f("V_ft"), c.f("att_score"), c.f("ds"), c.f("part_db"), (int)B, 1, (int)R,
@@ -1083,7 +1249,7 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         }
         {
             ProbeScope ps("v_linear_v.ln_bwd", c.st);
-            TRY(vqa_ln_relu_att_bwd(c.f("ds"), c.f("q_linear_v"), P->score.w, bt->keep_att, dims->keep_att, c.f("pre_v"),
+            TRY(vqa_ln_relu_att_bwd(c.f("ds"), c.f("q_linear_v"), P->score.w, bt->keep_att, s.d.keep_att, c.f("pre_v"),
                                     c.f("mean_v"), c.f("rstd_v"), P->v_linear_v.gamma, P->v_linear_v.beta, c.f("d_pre_v"), c.part(0),
                                     c.part(1), c.part(2), c.f("d_qv"), c.f("part_dw"), (int)B, 1, (int)R, (int)H, (int)D, c.st));
             TRY(vqa_colsum_vtail(c.part(0), c.part(1), c.part(2), c.f("part_dw"), c.f("part_db"), (int)B, (int)H,
@@ -1091,15 +1257,15 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
                                  c.colsum_ws_floats(), c.st));
         }
         ProbeScope ps("v_linear_v.dw_gemm", c.st);
-        TRY(gemm(c, 1, 0, D, H, B * R, c.f("V_ft"), (int)D, c.f("d_pre_v"), (int)H, G->v_linear_v.w, (int)H));  // dW = x^T * d_pre
-    } else {
-    {
-    ProbeScope ps("attn_pool.bwd", c.st);
-    TRY(vqa_attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.f(mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
-                          c.f("att_score"), P->score.w, bt->keep_att, dims->keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
-                          c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
+        return gemm(c, 1, 0, D, H, B * R, c.f("V_ft"), (int)D, c.f("d_pre_v"), (int)H, G->v_linear_v.w, (int)H);  // dW = x^T * d_pre
     }
-    if (mt == VQA_MODEL_ADAPT) {
+    {
+        ProbeScope ps("attn_pool.bwd", c.st);
+        TRY(vqa_attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
+                              c.f("att_score"), P->score.w, bt->keep_att, s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
+                              c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
+    }
+    if (s.mt == VQA_MODEL_ADAPT) {
         // the pooled memory is trainable here: d v_adapt = att (x) d pooled, then LN[R,H] + ReLU + FC backward (V_ft is an
         // input: parameters only), like v_linear_v's
         TRY(vqa_outer_rows(c.f("att_score"), c.f("d_pooled"), c.f("d_va"), (int)B, (int)R, (int)H, c.st));
@@ -1111,84 +1277,98 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         TRY(colsum(c, c.f("part_dw"), B, H, (int)H, G->score.w));
         TRY(colsum(c, c.f("part_db"), B, 1, 1, G->score.b));
     }
-    }
     // v_linear_v: parameters only (V_ft is an input).  77 GFLOP of dW on the side stream, beside
     // the latency-bound back-propagation through time below.
-    const bool forked = !vtail && fork_side(c, sd);
-    if (!vtail) {
-        Ctx cv{*dims, L, c.ws, forked ? sd.s : c.st, forked ? 1 : 0};
-        TRY(fc_ln_relu_bwd(cv, cv.f("d_v"), cv.f("V_ft"), B * R, D, H, P->v_linear_v, &G->v_linear_v, (int)R, "pre_v",
-                           "mean_v", "rstd_v", nullptr, 1.f, "d_pre_v", nullptr, false));
-        if (forked && !join_side_record(sd)) return VQA_ERR_LAUNCH;
-    }
-    if (mt == VQA_MODEL_BI) {
-        // q_linear_v read pooled_q_v; from there back through the question self-attention into d q_L_ft (dh) / d q_L_map
-        TRY(fc_ln_relu_bwd(c, c.f("d_qv"), c.f("pooled_q_v"), B, H, H, P->q_linear_v, &G->q_linear_v, 1, "pre_qv", "mean_qv",
-                           "rstd_qv", nullptr, 1.f, "d_pre_qv", c.f("d_pooled_qv"), false));
-        TRY(bi_question_bwd_head(c, P, G, bt, dh));
-    } else {
-    // q_linear_v: dh += ...
-    TRY(fc_ln_relu_bwd(c, c.f("d_qv"), h, B, H, H, P->q_linear_v, &G->q_linear_v, 1, "pre_qv", "mean_qv", "rstd_qv",
-                       nullptr, 1.f, "d_pre_qv", dh, true));
-    }
-    if (forked && hipStreamWaitEvent(c.st, sd.join, 0) != hipSuccess) return VQA_ERR_LAUNCH;
-    }   // phase 1
+    s.forked = fork_side(c, *s.sd);
+    const Ctx cv = s.side_ctx();
+    TRY(fc_ln_relu_bwd(cv, cv.f("d_v"), cv.f("V_ft"), B * R, D, H, P->v_linear_v, &G->v_linear_v, (int)R, "pre_v",
+                       "mean_v", "rstd_v", nullptr, 1.f, "d_pre_v", nullptr, false));
+    return side_record(s);
+}
 
-    if (mt == VQA_MODEL_BI) {
-        if (phases & 2) TRY(bi_question_bwd_bptt(c, P, G, bt, dh, embed_slice_sq));
-        if (phases & 12) TRY(bi_question_bwd_weights(c, G, phases));
-        return VQA_OK;
+// q_linear_v: d_qv -> dh (accumulated); the bi-directional models go on through the question self-attention
+int bwd_q_linear_v(const Step& s) {
+    const Ctx& c = s.c;
+    const int64_t B = s.B, H = s.H;
+    if (s.mt == VQA_MODEL_BI) {
+        // q_linear_v read pooled_q_v; from there back through the question self-attention into d q_L_ft (dh) / d q_L_map
+        TRY(fc_ln_relu_bwd(c, c.f("d_qv"), c.f("pooled_q_v"), B, H, H, s.P->q_linear_v, &s.G->q_linear_v, 1, "pre_qv", "mean_qv",
+                           "rstd_qv", nullptr, 1.f, "d_pre_qv", c.f("d_pooled_qv"), false));
+        return bi_question_bwd_head(c, s.P, s.G, s.bt, s.dh);
     }
-    if (phases & 2) {
-    // GRU back-propagation through time (gate math fused into the GEMM epilogues)
-    const float* Wg_h = P->gru_wg + W * 2 * H;
-    const float* Wc_h = P->gru_wc + W * H;
+    // q_linear_v: dh += ...
+    return fc_ln_relu_bwd(c, c.f("d_qv"), s.h, B, H, H, s.P->q_linear_v, &s.G->q_linear_v, 1, "pre_qv", "mean_qv", "rstd_qv",
+                          nullptr, 1.f, "d_pre_qv", s.dh, true);
+}
+
+// phase 2: GRU back-propagation through time (gate math fused into the GEMM epilogues), dx, embedding scatter-add, slice
+// sum of squares
+int bwd_bptt(const Step& s, float* embed_slice_sq) {
+    const Ctx& c = s.c;
+    const vqa_params_t* P = s.P;
+    const vqa_batch_t* bt = s.bt;
+    const int64_t B = s.B, H = s.H, T = s.T, W = s.W;
+    const float* hs = s.hs;
+    float* dh = s.dh;
+    float* dxp = s.dxp;
+    const float* Wg_h = s.Wg_h();
+    const float* Wc_h = s.Wc_h();
     {
         ProbeScope ps("gru.bwd", c.st);
-        const bool ws_ok = gru_ws_on() && (bt->live_rows == nullptr || (T > 0 && bt->live_rows[T - 1] > 0));
-        if (ws_ok && vqa_gru_ws_bwd_supported((int)T, (int)B, (int)H) == 1) {
-            TRY(vqa_gru_seq_bwd_ws(dh, nullptr, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), dxp,
-                                   (int)T, (int)B, (int)H, c.f("gru_ws"), c.st));
-        } else if (bt->live_rows != nullptr) {
-            TRY(vqa_gru_seq_bwd_live(dh, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
-                                     c.f("gru_c"), dxp, c.f("d_h1"), (int)T, (int)B, (int)H, c.st));
-        } else {
-            const float* gr = c.f("gru_r"); const float* gu = c.f("gru_u"); const float* gc = c.f("gru_c");
-            float* dh1 = c.f("d_h1");
-            TRY(run_chains(c, B, [&](int, int64_t row0, int64_t rows, hipStream_t st) {
-                return vqa_gru_seq_bwd_rows(dh, Wg_h, Wc_h, bt->q_intseq_len, hs, gr, gu, gc, dxp, dh1, (int)T, (int)B, (int)H,
-                                            (int)row0, (int)rows, st);
-            }));
+        switch (gru_form(GRU_BWD, T, B, H, bt->live_rows)) {
+            case GRU_WS:
+                TRY(vqa_gru_seq_bwd_ws(dh, nullptr, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), dxp,
+                                       (int)T, (int)B, (int)H, c.f("gru_ws"), c.st));
+                break;
+            case GRU_LIVE:
+                TRY(vqa_gru_seq_bwd_live(dh, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
+                                         c.f("gru_c"), dxp, c.f("d_h1"), (int)T, (int)B, (int)H, c.st));
+                break;
+            case GRU_CHAINS: {
+                const float* gr = c.f("gru_r"); const float* gu = c.f("gru_u"); const float* gc = c.f("gru_c");
+                float* dh1 = c.f("d_h1");
+                TRY(run_chains(c, B, [&](int, int64_t row0, int64_t rows, hipStream_t st) {
+                    return vqa_gru_seq_bwd_rows(dh, Wg_h, Wc_h, bt->q_intseq_len, hs, gr, gu, gc, dxp, dh1, (int)T, (int)B, (int)H,
+                                                (int)row0, (int)rows, st);
+                }));
+                break;
+            }
         }
     }
     // embedding: un-aggregated slices dx [T,B,W], then scatter-add
     float* dx = c.f("dx_embed");
     {
-    ProbeScope ps("gru.dx_gemm", c.st);
-    if (xcat_enabled()) {
-        // wx_cat: the forward's packed copy of the x rows still sits in the workspace (backward follows the forward of the
-        // same step on the same weights: every gradient here is meaningless otherwise); VQA_HOT_REPACK=1 packs it again
-        static const bool repack = [] { const char* e = getenv("VQA_HOT_REPACK"); return e != nullptr && atoi(e) != 0; }();
-        if (repack)
-            TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-        TRY(gemm_f32(c, 0, 1, T * B, W, 3 * H, dxp, (int)(3 * H), c.f("wx_cat"), (int)(3 * H), dx, (int)W));
-    } else {
-        TRY(gemm_f32(c, 0, 1, T * B, W, 2 * H, dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
-        TRY(gemm_f32(c, 0, 1, T * B, W, H, dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
-    }
+        ProbeScope ps("gru.dx_gemm", c.st);
+        if (xcat_enabled()) {
+            // wx_cat: the forward's packed copy of the x rows still sits in the workspace (backward follows the forward of the
+            // same step on the same weights: every gradient here is meaningless otherwise); VQA_HOT_REPACK=1 packs it again
+            if (repack_enabled())
+                TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
+            TRY(gemm_f32(c, 0, 1, T * B, W, 3 * H, dxp, (int)(3 * H), c.f("wx_cat"), (int)(3 * H), dx, (int)W));
+        } else {
+            TRY(gemm_f32(c, 0, 1, T * B, W, 2 * H, dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
+            TRY(gemm_f32(c, 0, 1, T * B, W, H, dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
+        }
     }
     ProbeScope ps_embed("embed.bwd", c.st);
-    if (G->embed != nullptr)
-        TRY(vqa_embed_bwd_len_det(dx, bt->q_intseq, bt->q_intseq_len, G->embed, (int)B, (int)T, (int)W, dims->Vq,
-                                  (dims->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
+    if (s.G->embed != nullptr)
+        TRY(vqa_embed_bwd_len_det(dx, bt->q_intseq, bt->q_intseq_len, s.G->embed, (int)B, (int)T, (int)W, s.d.Vq,
+                                  (s.d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
     if (embed_slice_sq != nullptr)
         TRY(vqa_sumsq(dx, T * B * W, nullptr, embed_slice_sq, c.f("sumsq_ws"), c.L.find("sumsq_ws")->n, c.st));
-    }   // phase 2
+    return VQA_OK;
+}
 
-    if ((phases & 4) && G->gru_wg != nullptr) {
-        {
+// phase 4: the gate kernel's weight and bias gradients; in the packed form the x rows and biases of BOTH kernels (the
+// candidate's bucket is reduced after phase 4)
+int bwd_gate_weights(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* G = s.G;
+    const int64_t B = s.B, H = s.H, T = s.T, W = s.W, Wp = s.Wp;
+    float* dxp = s.dxp;
+    {
         ProbeScope ps("gru.dwx_gemm", c.st);
-        if (xcat_enabled()) {   // x rows of BOTH kernels' gradients (the candidate's bucket is reduced after phase 4)
+        if (xcat_enabled()) {
             // rows 0..W-1: x rows of both kernels' gradients; row W (the constant input): both bias gradients
             TRY(gemm_f32(c, 1, 0, Wp, 3 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), c.f("dwx_cat"), (int)(3 * H)));
             TRY(vqa_gru_unpack_dwx_bias(c.f("dwx_cat"), G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc, (int)W, (int)H, c.st));
@@ -1196,19 +1376,63 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
             TRY(gemm_f32(c, 1, 0, W, 2 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), G->gru_wg, (int)(2 * H)));
             TRY(colsum(c, dxp, T * B, 2 * H, (int)(3 * H), G->gru_bg));
         }
-        }
-        ProbeScope ps("gru.dwh_gemm", c.st);
-        TRY(gemm_f32(c, 1, 0, H, 2 * H, T * B, hs, (int)H, dxp, (int)(3 * H), G->gru_wg + W * 2 * H, (int)(2 * H)));
-    }   // phase 3: gates
-    if ((phases & 8) && G->gru_wg != nullptr) {
-        if (!xcat_enabled()) {
-            ProbeScope ps("gru.dwx_gemm", c.st);
-            TRY(gemm_f32(c, 1, 0, W, H, T * B, c.f("x_tm"), (int)Wp, dxp + 2 * H, (int)(3 * H), G->gru_wc, (int)H));
-            TRY(colsum(c, dxp + 2 * H, T * B, H, (int)(3 * H), G->gru_bc));
-        }
-        ProbeScope ps("gru.dwh_gemm", c.st);
-        TRY(gemm_f32(c, 1, 0, H, H, T * B, c.f("gru_rh"), (int)H, dxp + 2 * H, (int)(3 * H), G->gru_wc + W * H, (int)H));
-    }   // phase 4: candidate
+    }
+    ProbeScope ps("gru.dwh_gemm", c.st);
+    return gemm_f32(c, 1, 0, H, 2 * H, T * B, s.hs, (int)H, dxp, (int)(3 * H), G->gru_wg + W * 2 * H, (int)(2 * H));
+}
+
+// phase 8: the candidate kernel's weight and bias gradients (its x rows and bias only in the two-GEMM form)
+int bwd_cand_weights(const Step& s) {
+    const Ctx& c = s.c;
+    const vqa_params_t* G = s.G;
+    const int64_t B = s.B, H = s.H, T = s.T, W = s.W, Wp = s.Wp;
+    float* dxp = s.dxp;
+    if (!xcat_enabled()) {
+        ProbeScope ps("gru.dwx_gemm", c.st);
+        TRY(gemm_f32(c, 1, 0, W, H, T * B, c.f("x_tm"), (int)Wp, dxp + 2 * H, (int)(3 * H), G->gru_wc, (int)H));
+        TRY(colsum(c, dxp + 2 * H, T * B, H, (int)(3 * H), G->gru_bc));
+    }
+    ProbeScope ps("gru.dwh_gemm", c.st);
+    return gemm_f32(c, 1, 0, H, H, T * B, c.f("gru_rh"), (int)H, dxp + 2 * H, (int)(3 * H), G->gru_wc + W * H, (int)H);
+}
+
+}  // namespace
+
+// phases (bit mask), in dependency order:
+//   1  head .. attention .. v_linear_v / q_linear_v / score gradients      (complete after this phase)
+//   2  GRU back-propagation through time, dx, embedding scatter-add, slice sum of squares
+//   4  GRU gate weight / bias gradients (the larger half, 10.8 MB at H 1024)
+//   8  GRU candidate weight / bias gradients (5.4 MB) -- the only all-reduce nothing is left to overlap with
+// so a data-parallel caller can start all-reducing each gradient bucket while the next phase runs.
+extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_params_t* G,
+                                          const vqa_batch_t* bt, void* workspace, int64_t workspace_bytes,
+                                          float* embed_slice_sq, int phases, void* stream) {
+    VQA_REQUIRE(dims_ok(dims) && P && G && bt && workspace, VQA_ERR_ARG);
+    Step s(dims, P, G, bt, workspace, stream);
+    VQA_REQUIRE(workspace_bytes >= s.L.total, VQA_ERR_WORKSPACE);
+    ProbeScope ps_all("backward", s.c.st);
+    if (s.mt == VQA_MODEL_LEGACY_VQA) return (phases & 1) ? legacy_vqa_backward(s.c, P, G, bt, embed_slice_sq) : VQA_OK;
+    s.bind_bwd();
+    s.pair = ln_pair_ok(s.d, P);
+
+    if (phases & 1) {
+        TRY(bwd_head(s));
+        TRY(bwd_joint(s));
+        if (s.mt == VQA_MODEL_ENT) TRY(bwd_entropy(s));
+        TRY(bwd_linear_l(s));
+        TRY(bwd_question_code(s));
+        TRY(bwd_attention(s));
+        TRY(bwd_q_linear_v(s));
+        TRY(side_wait(s));
+    }
+    if (s.mt == VQA_MODEL_BI) {
+        if (phases & 2) TRY(bi_question_bwd_bptt(s.c, P, G, bt, s.dh, embed_slice_sq));
+        if (phases & 12) TRY(bi_question_bwd_weights(s.c, G, phases));
+        return VQA_OK;
+    }
+    if (phases & 2) TRY(bwd_bptt(s, embed_slice_sq));
+    if ((phases & 4) && G->gru_wg != nullptr) TRY(bwd_gate_weights(s));
+    if ((phases & 8) && G->gru_wg != nullptr) TRY(bwd_cand_weights(s));
     return VQA_OK;
 }
 

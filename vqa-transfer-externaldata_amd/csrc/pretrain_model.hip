@@ -88,10 +88,6 @@ __global__ __launch_bounds__(256) void gather_rows2_kernel(const uint32_t* __res
     }
 }
 
-// row stride of the time-major GRU inputs: W word-vector columns, the constant 1 (its row of the x-part weight gradient
-// is the bias gradient), zero padding to 16 bytes
-inline int64_t x_stride(int64_t W) { return ((W + 1 + 3) / 4) * 4; }
-
 // ---------------------------------------------------------------- workspace layout
 struct Entry { std::string name; int64_t off, n; };
 struct Layout {
@@ -117,18 +113,10 @@ const char* const KIND[2] = {"obj", "attr"};
 const char* const HEAD[3] = {"bf", "ws", "ew"};      // blank fill, word set, enwiki context
 const char* const TASK[3] = {"blank_fill", "wordset", "enwiki"};
 
-int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
-
 bool dims_ok(const vqa_pretrain_dims_t* d) {
     return d && d->B > 0 && d->n > 0 && d->n <= 8 && d->R > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->A > 0 &&
            d->Vq > 0 && d->n_ws > 0 && d->L > 0 && d->H % 4 == 0 && d->D % 4 == 0;
 }
-
-#define TRY(x)                           \
-    do {                                 \
-        int rc__ = (x);                  \
-        if (rc__ != VQA_OK) return rc__; \
-    } while (0)
 
 struct Ctx {
     const vqa_pretrain_dims_t& d;

@@ -36,6 +36,19 @@ struct ProbeScope {
     ProbeScope& operator=(const ProbeScope&) = delete;
 };
 
+// early return of a host composition on the first failing call
+#define TRY(x)                           \
+    do {                                 \
+        int rc__ = (x);                  \
+        if (rc__ != VQA_OK) return rc__; \
+    } while (0)
+
+static inline int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
+
+// row stride of the time-major GRU inputs (x_tm): W word-vector columns, the constant 1 (its row of the x-part weight
+// gradient is the bias gradient), zero padding to 16 bytes
+static inline int64_t x_stride(int64_t W) { return ((W + 1 + 3) / 4) * 4; }
+
 static inline bool vqa_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // integer tuning override from the environment; callers keep the value in a function-local static (read once)

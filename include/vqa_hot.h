@@ -260,6 +260,12 @@ int vqa_gru_persistent_set_census(unsigned* dev_words);   /* placement study (to
 int vqa_gru_seq_fwd_ws(const float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs, float* r,
                        float* u, float* c, float* rh, int T, int B, int H, void* ws, void* stream);
 int vqa_gru_ws_supported(int T, int B, int H);
+/* vqa_gru_seq_fwd_ws with a promise: h0_zero != 0 says that hs[0] is all zeros and that the caller has written them (the
+ * back-propagation and the weight-gradient GEMMs still read that block of the tape).  Step 0 of the recurrence then
+ * multiplies by nothing: h_0 W_g and (r h_0) W_c are zero, r | u = sigmoid(xp[0]), c = tanh(xp_c[0]), rh = 0.  Every
+ * output equals the general call's (a -0 may come out as +0); h0_zero == 0 is vqa_gru_seq_fwd_ws. */
+int vqa_gru_seq_fwd_ws_ex(const float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs, float* r,
+                          float* u, float* c, float* rh, int T, int B, int H, int h0_zero, void* ws, void* stream);
 /* The back-propagation through time in the same frame (one launch, W_g^T / W_c^T slabs resident): dxp [T,B,3H] =
  * (dr_pre | du_pre | dc_pre) from dh_T [B,H] -- read only here, unlike vqa_gru_seq_bwd -- and the forward tape; d_outs
  * [T,B,H] or NULL as in vqa_gru_seq_bwd_outs.  256 < B <= 512, H = 1024 (vqa_gru_ws_bwd_supported); `ws` as above (one
@@ -267,7 +273,19 @@ int vqa_gru_ws_supported(int T, int B, int H);
 int vqa_gru_seq_bwd_ws(const float* dh_T, const float* d_outs, const float* Wg_h, const float* Wc_h, const int32_t* len,
                        const float* hs, const float* r, const float* u, const float* c, float* dxp, int T, int B, int H,
                        void* ws, void* stream);
+/* vqa_gru_seq_bwd_ws on a tape whose hs[0] is all zeros (h0_zero != 0, the promise of vqa_gru_seq_fwd_ws_ex): the
+ * products dc_pre W_c^T of step 0 feed only dr_pre[0] = drh h_0 r (1 - r) = 0 and are not formed; dxp[0] is written as
+ * (0 | du_pre | dc_pre).  Same values as the general call; h0_zero == 0 is vqa_gru_seq_bwd_ws. */
+int vqa_gru_seq_bwd_ws_ex(const float* dh_T, const float* d_outs, const float* Wg_h, const float* Wc_h, const int32_t* len,
+                          const float* hs, const float* r, const float* u, const float* c, float* dxp, int T, int B, int H,
+                          int h0_zero, void* ws, void* stream);
 int vqa_gru_ws_bwd_supported(int T, int B, int H);
+/* What vqa_fusion_forward / _backward save on the question GRU's zero initial state, which they write themselves: bit 0 =
+ * the weight-stationary recurrence runs with h0_zero, bit 1 = the two recurrent weight-gradient GEMMs skip the rows of
+ * t = 0 (K = (T-1) B; those two gradient blocks then differ from mode 0 in their last bits, the summation being split
+ * elsewhere; bit 0 changes no result).  -1 = back to the default (the environment variable VQA_HOT_GRU_H0SKIP, else 1:
+ * bit 1 is opt-in, because a training run's numbers move with those last bits).  Returns the mode now in force. */
+int vqa_gru_h0skip_set_mode(int mode);
 int64_t vqa_gru_ws_workspace_bytes(int T);
 int vqa_gru_ws_set_mode(int mode);      /* bit 0: forward, bit 1: back-propagation, wherever they apply; -1 = 3 (default) */
 int vqa_gru_ws_set_form(int form);      /* tuning: 0 = sub-phase tails inside the next matrix stream (default), 1 = plain order */

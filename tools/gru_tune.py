@@ -23,6 +23,8 @@ r = torch.empty(T, B, H, device="cuda"); u = torch.empty_like(r); c = torch.empt
 dhT0 = torch.randn(B, H, device="cuda", generator=g); dhT = dhT0.clone()
 dxp = torch.empty(T, B, 3 * H, device="cuda"); dhs = torch.empty(B, H, device="cuda")
 P = lambda t: C.c_void_p(t.data_ptr())
+# WS=1 / WSB=1 with WS_H0ZERO=1: the zero-state promise (hs[0] above is zero); the phase stamps are taken without it only
+H0ZERO = int(os.environ.get("WS_H0ZERO", 0))
 
 
 def fwd():
@@ -109,7 +111,7 @@ if os.environ.get("WS") == "1":
     ws = torch.empty(int(lib.vqa_gru_ws_workspace_bytes(T)) // 4, dtype=torch.float32, device="cuda").fill_(float("nan"))
 
     def fwd_ws():
-        _lib.check(lib.vqa_gru_seq_fwd_ws(P(xp), P(Wg), P(Wc), P(ln), P(hs), P(r), P(u), P(c), P(rh), T, B, H, P(ws), None), "fwd_ws")
+        _lib.check(lib.vqa_gru_seq_fwd_ws_ex(P(xp), P(Wg), P(Wc), P(ln), P(hs), P(r), P(u), P(c), P(rh), T, B, H, H0ZERO, P(ws), None), "fwd_ws")
 
     lib.vqa_gru_ws_set_form(int(os.environ.get("WS_FORM", 0)))      # 1: plain sub-phase order (stamps only there)
     fwd(); torch.cuda.synchronize()
@@ -119,7 +121,7 @@ if os.environ.get("WS") == "1":
     hs[1:].fill_(float("nan"))
     stamps = torch.zeros(2048, dtype=torch.int64, device="cuda")
     big = torch.empty(1 << 28, dtype=torch.float32, device="cuda"); big.zero_()      # the stamped launch starts from cold caches
-    lib.vqa_gru_ws_set_stamps(P(stamps)); fwd_ws(); torch.cuda.synchronize(); lib.vqa_gru_ws_set_stamps(None)
+    lib.vqa_gru_ws_set_stamps(None if H0ZERO else P(stamps)); fwd_ws(); torch.cuda.synchronize(); lib.vqa_gru_ws_set_stamps(None)
     words = ws[:1024].view(torch.int32)
     print("ws: flags (min, max per half-chain)", [(int(words[32 * i: 32 * i + 32].min()), int(words[32 * i: 32 * i + 32].max())) for i in range(16)],
           "error word", int(words[512]), "workgroups per XCD", words[576:584].tolist(), flush=True)
@@ -163,7 +165,7 @@ if os.environ.get("WSB") == "1":
     dxp_ws = torch.full_like(dxp, float("nan"))
 
     def bwd_ws():
-        _lib.check(lib.vqa_gru_seq_bwd_ws(P(dhT0), None, P(Wg), P(Wc), P(ln), P(hs), P(r), P(u), P(c), P(dxp_ws), T, B, H, P(ws), None), "bwd_ws")
+        _lib.check(lib.vqa_gru_seq_bwd_ws_ex(P(dhT0), None, P(Wg), P(Wc), P(ln), P(hs), P(r), P(u), P(c), P(dxp_ws), T, B, H, H0ZERO, P(ws), None), "bwd_ws")
 
     fwd(); bwd(); torch.cuda.synchronize()
     bwd_ws(); torch.cuda.synchronize()

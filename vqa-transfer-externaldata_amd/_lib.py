@@ -175,8 +175,10 @@ SIGNATURES = {
     "vqa_gru_set_persistent": (_I, [_I]),
     "vqa_gru_persistent_set_census": (_I, [_P]),
     "vqa_gru_seq_fwd_ws": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "vqa_gru_seq_fwd_ws_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "vqa_gru_ws_supported": (_I, [_I, _I, _I]),
     "vqa_gru_seq_bwd_ws": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "vqa_gru_seq_bwd_ws_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "vqa_gru_ws_bwd_supported": (_I, [_I, _I, _I]),
     "vqa_gru_ws_workspace_bytes": (_L, [_I]),
     "vqa_gru_ws_set_mode": (_I, [_I]),
@@ -221,6 +223,7 @@ SIGNATURES = {
     "vqa_attn_pool_bwd_rep": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_vtail_supported": (_I, [_I, _I, _I, _I]),
     "vqa_vtail_set_mode": (_I, [_I]),
+    "vqa_gru_h0skip_set_mode": (_I, [_I]),
     "vqa_attn_pool_bwd_ds": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_ln_relu_att_bwd": (_I, [_P, _P, _P, _P, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
     "vqa_colsum_vtail_workspace_floats": (_L, [_I, _I]),

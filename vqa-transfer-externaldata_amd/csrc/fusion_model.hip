@@ -222,6 +222,10 @@ struct Ctx {
 //   VQA_HOT_GATHER=fused    the feature gather inside v_linear_v's GEMM (anything else: a pass of its own; unset: the flag)
 //   VQA_HOT_LN_PAIR=0       pooled_linear_l and q_linear_l as two LayerNorm launches plus the element-wise product
 //   VQA_HOT_VTAIL=0         v_linear_v's LayerNorm backward and the score gradient as separate calls (vqa_vtail_set_mode)
+//   VQA_HOT_GRU_H0SKIP=n    what the question GRU's zero initial state saves (default 1; vqa_gru_h0skip_set_mode): bit 0 the
+//                           matrix streams of step 0 in the weight-stationary recurrence (same results), bit 1 the rows of
+//                           step 0 in the two recurrent weight-gradient GEMMs (opt-in: another split-k boundary, so those
+//                           two gradients and with them a training run's numbers move at rounding level)
 inline bool env_on(const char* name, bool dflt) {
     const char* e = getenv(name);
     return e == nullptr ? dflt : atoi(e) != 0;
@@ -240,6 +244,20 @@ int g_vtail_mode = -1;
 inline int vtail_mode() {
     if (g_vtail_mode < 0) g_vtail_mode = env_on("VQA_HOT_VTAIL", true) ? 1 : 0;
     return g_vtail_mode;
+}
+// fwd_question clears hs[0] itself (dynamic_rnn without an initial state), so h_0 W_g, (r h_0) W_c and the rows of t = 0
+// in hs[0..T-1]^T dxp and gru_rh^T dxp_c are zero by construction.  Bit 0: the weight-stationary recurrence is told so
+// (vqa_gru_seq_fwd_ws_ex / _bwd_ws_ex, h0_zero); bit 1: the two gru.dwh_gemm calls start at row B of their operands.
+// Bit 0 is on by default: it leaves every result as it was.  Bit 1 is measured faster (profiles/r14_h0skip_ab.txt) but sums the
+// two gradients in another order, and a training run must compute what it computed: opt-in.
+// vqa_gru_h0skip_set_mode overrides the environment, and a negative mode has it read again.
+int g_h0skip_mode = -1;
+inline int h0skip_mode() {
+    if (g_h0skip_mode < 0) {
+        const char* e = getenv("VQA_HOT_GRU_H0SKIP");
+        g_h0skip_mode = e == nullptr ? 1 : (atoi(e) & 3);
+    }
+    return g_h0skip_mode;
 }
 int side_max_blocks() {
     static int v = -1;
@@ -656,6 +674,11 @@ extern "C" int vqa_vtail_set_mode(int mode) {
     return vtail_mode();
 }
 
+extern "C" int vqa_gru_h0skip_set_mode(int mode) {
+    g_h0skip_mode = mode < 0 ? -1 : (mode & 3);
+    return h0skip_mode();
+}
+
 namespace {
 
 // Everything one forward or backward call derives from its arguments, computed once and handed to every stage.  The
@@ -823,8 +846,8 @@ int fwd_question(Step& s) {
         ProbeScope ps("gru.fwd", c.st);
         switch (gru_form(GRU_FWD, T, B, H, bt->live_rows)) {
             case GRU_WS:
-                TRY(vqa_gru_seq_fwd_ws(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), c.f("gru_rh"),
-                                       (int)T, (int)B, (int)H, c.f("gru_ws"), c.st));
+                TRY(vqa_gru_seq_fwd_ws_ex(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), c.f("gru_rh"),
+                                          (int)T, (int)B, (int)H, h0skip_mode() & 1, c.f("gru_ws"), c.st));      // hs[0]: cleared above
                 break;
             case GRU_LIVE:
                 TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
@@ -1317,8 +1340,9 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
         ProbeScope ps("gru.bwd", c.st);
         switch (gru_form(GRU_BWD, T, B, H, bt->live_rows)) {
             case GRU_WS:
-                TRY(vqa_gru_seq_bwd_ws(dh, nullptr, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), dxp,
-                                       (int)T, (int)B, (int)H, c.f("gru_ws"), c.st));
+                // (hs[0] of this tape: fwd_question's zeros)
+                TRY(vqa_gru_seq_bwd_ws_ex(dh, nullptr, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), dxp,
+                                          (int)T, (int)B, (int)H, h0skip_mode() & 1, c.f("gru_ws"), c.st));
                 break;
             case GRU_LIVE:
                 TRY(vqa_gru_seq_bwd_live(dh, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
@@ -1359,6 +1383,20 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
     return VQA_OK;
 }
 
+// A recurrent weight gradient dW [H,N] = tape[0..T-1]^T dxp_part (gru.dwh_gemm).  The tape's rows of t = 0 are h_0 (gate
+// kernel) or r * h_0 (candidate kernel): zeros, since fwd_question cleared hs[0].  With bit 1 of h0skip_mode() the product
+// starts at row B of both operands, K = (T-1) B; at T = 1 nothing is left and the block, which the GEMM overwrites, is
+// cleared (rows W.. of a [W+H,N] gradient: contiguous).
+int dwh_gemm(const Step& s, const float* tape, const float* dxp_part, int64_t N, float* dW) {
+    const Ctx& c = s.c;
+    const int64_t B = s.B, H = s.H, T = s.T;
+    if (!(h0skip_mode() & 2))
+        return gemm_f32(c, 1, 0, H, N, T * B, tape, (int)H, dxp_part, (int)(3 * H), dW, (int)N);
+    if (T == 1)
+        return hipMemsetAsync(dW, 0, (size_t)(H * N) * sizeof(float), c.st) == hipSuccess ? VQA_OK : VQA_ERR_LAUNCH;
+    return gemm_f32(c, 1, 0, H, N, (T - 1) * B, tape + B * H, (int)H, dxp_part + B * 3 * H, (int)(3 * H), dW, (int)N);
+}
+
 // phase 4: the gate kernel's weight and bias gradients; in the packed form the x rows and biases of BOTH kernels (the
 // candidate's bucket is reduced after phase 4)
 int bwd_gate_weights(const Step& s) {
@@ -1378,7 +1416,7 @@ int bwd_gate_weights(const Step& s) {
         }
     }
     ProbeScope ps("gru.dwh_gemm", c.st);
-    return gemm_f32(c, 1, 0, H, 2 * H, T * B, s.hs, (int)H, dxp, (int)(3 * H), G->gru_wg + W * 2 * H, (int)(2 * H));
+    return dwh_gemm(s, s.hs, dxp, 2 * H, G->gru_wg + W * 2 * H);
 }
 
 // phase 8: the candidate kernel's weight and bias gradients (its x rows and bias only in the two-GEMM form)
@@ -1393,7 +1431,7 @@ int bwd_cand_weights(const Step& s) {
         TRY(colsum(c, dxp + 2 * H, T * B, H, (int)(3 * H), G->gru_bc));
     }
     ProbeScope ps("gru.dwh_gemm", c.st);
-    return gemm_f32(c, 1, 0, H, H, T * B, c.f("gru_rh"), (int)H, dxp + 2 * H, (int)(3 * H), G->gru_wc + W * H, (int)H);
+    return dwh_gemm(s, c.f("gru_rh"), dxp + 2 * H, H, G->gru_wc + W * H);
 }
 
 }  // namespace

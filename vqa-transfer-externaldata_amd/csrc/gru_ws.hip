@@ -81,6 +81,7 @@ struct WsArgs {
     unsigned long long* stamps;   // optional timing study: workgroup 0 records (wait, compute, done) per sub-phase
     int handoff_sc1;      // tuning: hand-offs as write-through stores (drops the line from the XCD's L2)
     int dbg;              // timing study (results garbage): 1 tape stores dropped, 2 hand-off stores dropped, 4 xp loads dropped
+    int h0_zero;          // the caller wrote zeros to hs[0]: step 0 has no matrix product (h_0 W_g = (r h_0) W_c = 0), only its tails
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t ws_rs(const float* p, int64_t bytes) {
@@ -252,10 +253,10 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd_kernel(WsArgs a) {
         const int grow = row_base + 32 * hf + e_row;
         ok[hf] = grow < B;
         o_std[hf] = (unsigned)(((int64_t)grow * H + 32 * j + e_col) * 4);
-        h_own[hf] = ok[hf] ? ws_load(rs_hs, o_std[hf]) : (f32x4n)(0.f);
+        h_own[hf] = (ok[hf] && !a.h0_zero) ? ws_load(rs_hs, o_std[hf]) : (f32x4n)(0.f);
         u_own[hf] = (f32x4n)(0.f);
         len_own[hf] = ok[hf] ? a.len[grow] : 0;
-        if (hf < halves) ws_store(rs_hF, frag_st(0, hf), h_own[hf], a.handoff_sc1 != 0);
+        if (hf < halves && !a.h0_zero) ws_store(rs_hF, frag_st(0, hf), h_own[hf], a.handoff_sc1 != 0);
     }
     __syncthreads();                    // the candidate slab is in LDS
     for (int hf = 0; hf < halves; ++hf) ws_arrive(a.sync + 32 * (2 * chain + hf), j, 1u);
@@ -268,10 +269,16 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd_kernel(WsArgs a) {
     unsigned long long* stamp = (a.stamps != nullptr && blockIdx.x == 0 && tid == 0) ? a.stamps : nullptr;
 
     // the first sub-phase's operand: G(0, 0) needs every CU's share of h_0
-    ws_wait(a.sync + 32 * (2 * chain), 1u, err, a.spin_limit);
-    fill(rs_hF, frag_ld(0, 0));
+    if (!a.h0_zero) {
+        ws_wait(a.sync + 32 * (2 * chain), 1u, err, a.spin_limit);
+        fill(rs_hF, frag_ld(0, 0));
+    }
 
     for (int t = 0; t < T; ++t) {
+        // h_0 = 0 by the caller's promise: the four products of step 0 are zero tiles.  No MFMA, no operand fragment, no
+        // wait for one; the tails run on zero accumulators with their stores, hand-offs and arrivals (the flag epochs count
+        // the skipped sub-phases), and the first wait is the one in front of G(0,1).
+        const bool mm = !(a.h0_zero && t == 0);
         // ================================================================ gates: r | u = sigmoid(h W_g + xp)
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -284,28 +291,30 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd_kernel(WsArgs a) {
                 f32x16 accR, accU;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) { accR[q] = 0.f; accU[q] = 0.f; }
+                if (mm) {
 #pragma unroll
-                for (int m = 0; m < 32; ++m) {
-                    const f32x4n av = ring[m % WS_RING];
+                    for (int m = 0; m < 32; ++m) {
+                        const f32x4n av = ring[m % WS_RING];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (m < WS_AG_OCT) {
-                            WS_MFMA_AGPR_B(accR, av[i], wg[0][m][i]);
-                            WS_MFMA_AGPR_B(accU, av[i], wg[1][m][i]);
-                        } else {
-                            WS_MFMA_VGPR_B(accR, av[i], wg[0][m][i]);
-                            WS_MFMA_VGPR_B(accU, av[i], wg[1][m][i]);
+                        for (int i = 0; i < 4; ++i) {
+                            if (m < WS_AG_OCT) {
+                                WS_MFMA_AGPR_B(accR, av[i], wg[0][m][i]);
+                                WS_MFMA_AGPR_B(accU, av[i], wg[1][m][i]);
+                            } else {
+                                WS_MFMA_VGPR_B(accR, av[i], wg[0][m][i]);
+                                WS_MFMA_VGPR_B(accU, av[i], wg[1][m][i]);
+                            }
                         }
+                        // the refill of this slot stays HERE (left alone, the scheduler sinks every load to its use,
+                        // one exposed L2 round trip per octet: the loop then runs at half the matrix rate)
+                        if (m + WS_RING < 32) ring[m % WS_RING] = ws_load(rs_hF, base + (m + WS_RING) * 1024);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    // the refill of this slot stays HERE (left alone, the scheduler sinks every load to its use,
-                    // one exposed L2 round trip per octet: the loop then runs at half the matrix rate)
-                    if (m + WS_RING < 32) ring[m % WS_RING] = ws_load(rs_hF, base + (m + WS_RING) * 1024);
-                    __builtin_amdgcn_sched_barrier(0);
+                    WS_MFMA_DRAIN();
                 }
-                WS_MFMA_DRAIN();
                 if (stamp) stamp[1] = wall_clock64();
                 // ---- what comes next on this CU: G(1,t) after G(0,t); C(0,t) after G(1,t) (or after G(0,t) alone)
-                if (halves == 2) {      // its producers finished a sub-phase ago: fetch its first fragments now
+                if (halves == 2 && mm) {      // its producers finished a sub-phase ago: fetch its first fragments now
                     if (hf == 0) { ws_wait(a.sync + 32 * (2 * chain + 1), 1u + 2 * t, err, a.spin_limit); fill(rs_hF, frag_ld(t, 1)); }
                     else { ws_wait(a.sync + 32 * (2 * chain), 2u + 2 * t, err, a.spin_limit); fill(rs_rhF, frag_ld(t, 0)); }
                 }
@@ -348,7 +357,7 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd_kernel(WsArgs a) {
                     ws_store(rs_rh, o, rhv, false);
                 }
                 ws_arrive(ctr, j, 2u + 2 * t);          // (its barrier also frees the scratch for the next sub-phase)
-                if (halves == 1) { ws_wait(ctr, 2u + 2 * t, err, a.spin_limit); fill(rs_rhF, frag_ld(t, 0)); }
+                if (halves == 1 && mm) { ws_wait(ctr, 2u + 2 * t, err, a.spin_limit); fill(rs_rhF, frag_ld(t, 0)); }
                 if (stamp) { stamp[2] = wall_clock64(); stamp += 3; }
             }
         }
@@ -367,24 +376,26 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd_kernel(WsArgs a) {
                 bq[0] = *reinterpret_cast<const f32x4n*>(Wl + ((32 * w) * 64 + lane) * 4);
                 bq[1] = *reinterpret_cast<const f32x4n*>(Wl + ((32 * w + 1) * 64 + lane) * 4);
                 __builtin_amdgcn_sched_barrier(0);
+                if (mm) {
 #pragma unroll
-                for (int m = 0; m < 32; ++m) {
-                    const f32x4n av = ring[m % WS_RING];
-                    const f32x4n bv = bq[m & 1];
-                    if (m + 2 < 32) bq[m & 1] = *reinterpret_cast<const f32x4n*>(Wl + ((32 * w + m + 2) * 64 + lane) * 4);
+                    for (int m = 0; m < 32; ++m) {
+                        const f32x4n av = ring[m % WS_RING];
+                        const f32x4n bv = bq[m & 1];
+                        if (m + 2 < 32) bq[m & 1] = *reinterpret_cast<const f32x4n*>(Wl + ((32 * w + m + 2) * 64 + lane) * 4);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (m & 1) acc1 = WS_MFMA(av[i], bv[i], acc1);
-                        else acc0 = WS_MFMA(av[i], bv[i], acc0);
+                        for (int i = 0; i < 4; ++i) {
+                            if (m & 1) acc1 = WS_MFMA(av[i], bv[i], acc1);
+                            else acc0 = WS_MFMA(av[i], bv[i], acc0);
+                        }
+                        if (m + WS_RING < 32) ring[m % WS_RING] = ws_load(rs_rhF, base + (m + WS_RING) * 1024);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (m + WS_RING < 32) ring[m % WS_RING] = ws_load(rs_rhF, base + (m + WS_RING) * 1024);
-                    __builtin_amdgcn_sched_barrier(0);
                 }
                 acc0 += acc1;
                 if (stamp) stamp[1] = wall_clock64();
                 // ---- next on this CU: C(1,t) after C(0,t); G(0,t+1) after C(1,t) (or after C(0,t) alone)
                 if (halves == 2) {
-                    if (hf == 0) { ws_wait(a.sync + 32 * (2 * chain + 1), 2u + 2 * t, err, a.spin_limit); fill(rs_rhF, frag_ld(t, 1)); }
+                    if (hf == 0) { if (mm) { ws_wait(a.sync + 32 * (2 * chain + 1), 2u + 2 * t, err, a.spin_limit); fill(rs_rhF, frag_ld(t, 1)); } }
                     else if (t + 1 < T) { ws_wait(a.sync + 32 * (2 * chain), 3u + 2 * t, err, a.spin_limit); fill(rs_hF, frag_ld(t + 1, 0)); }
                 }
 #pragma unroll
@@ -536,10 +547,10 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd2_kernel(WsArgs a) {
         o_std[hf] = (unsigned)(((int64_t)grow * H + 32 * j + e_col) * 4);
         o_xp[hf] = (unsigned)(((int64_t)grow * 3 * H + 32 * j + e_col) * 4);
         if (!ok[hf]) { o_std[hf] = 0xFFFFFFF0u; o_xp[hf] = 0xFFFFFFF0u; }       // past the end: loads give 0, stores vanish
-        h_own[hf] = ws_load(rs_hs, o_std[hf]);
+        h_own[hf] = a.h0_zero ? (f32x4n)(0.f) : ws_load(rs_hs, o_std[hf]);
         u_own[hf] = (f32x4n)(0.f);
         len_own[hf] = ok[hf] ? a.len[grow] : 0;
-        ws_store2(rs_hF, frag_v, frag_st(0, hf), h_own[hf], a.handoff_sc1 != 0);
+        if (!a.h0_zero) ws_store2(rs_hF, frag_v, frag_st(0, hf), h_own[hf], a.handoff_sc1 != 0);
     }
     __syncthreads();
     ws_arrive(ctr0, j, 1u);
@@ -679,9 +690,33 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd2_kernel(WsArgs a) {
     };
 
     f32x4n ring[16];                    // the candidate streams use slots 0..7
-    ws_wait(ctr0, 1u, err, a.spin_limit);
+    f32x16 gR0, gU0, gR1, gU1, cA0, cA1;
 #pragma unroll
-    for (int m = 0; m < 8; ++m) ring[m] = ws_load2(rs_hF, lane16, frag_ld(0, 0) + m * 1024);
+    for (int q = 0; q < 16; ++q) cA1[q] = 0.f;
+    // h_0 = 0 by the caller's promise (a.h0_zero): the four products of step 0 are zero tiles, so G(0,0) G(1,0) C(0,0)
+    // C(1,0) have no matrix stream.  Their tails run back to back on zero accumulators (cA1 is one): the same gate math,
+    // tape stores, hand-offs and flag epochs as inside a stream, each closed by ws_arrive as the last tail of the launch
+    // is (no younger loads follow the hand-off store here, so the tails' own vmcnt(2) would not cover it).  Nothing of
+    // step 0 waits for another CU.  The tail of C(1,0) is left where it always runs, in the gaps of G(0,1).
+    const int t0 = a.h0_zero ? 1 : 0;
+    if (a.h0_zero) {
+        xp_fetch(0, 0, 0);
+        xp_fetch(0, 0, 1);
+#pragma unroll
+        for (int k = 1; k <= 39; ++k) g_tail(k, 0, 0, cA1, cA1, ctr0);
+        ws_arrive(ctr0, j, 2u);
+#pragma unroll
+        for (int k = 1; k <= 39; ++k) g_tail(k, 0, 1, cA1, cA1, ctr1);
+        ws_arrive(ctr1, j, 2u);
+#pragma unroll
+        for (int k = 1; k <= 39; ++k) c_tail(k, 0, 0, cA1, ctr0, true);
+        ws_arrive(ctr0, j, 3u);
+    }
+    if (t0 < T) {                       // the first stream's operand: every CU's share of h_0, or of h_1
+        ws_wait(ctr0, 1u + 2u * t0, err, a.spin_limit);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) ring[m] = ws_load2(rs_hF, lane16, frag_ld(t0, 0) + m * 1024);
+    }
 
     // one sub-phase's matrix stream: 32 octets of this wave's k quarter, HOOK(slot - 4) in every slot
     // (cur: this sub-phase's fragments; nxt: the next one's, fetched into the ring slots as they fall free)
@@ -740,14 +775,11 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_fwd2_kernel(WsArgs a) {
         }                                                                                                      \
     }
 
-    f32x16 gR0, gU0, gR1, gU1, cA0, cA1;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) cA1[q] = 0.f;
     unsigned long long* stamp = (a.stamps != nullptr && blockIdx.x == 0 && tid == 0) ? a.stamps : nullptr;
     if (stamp) { stamp[2046] = t_entry; stamp[2047] = wall_clock64(); }      // prologue: entry -> first stream
     long long* slots = (WS_SLOTS && stamp != nullptr) ? reinterpret_cast<long long*>(a.stamps) + 1024 : nullptr;      // 4 x 128 slot stamps of step 5
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = t0; t < T; ++t) {
         const unsigned n = (unsigned)(2 * t);
         // ---------------- G(0,t); in its gaps: the tail of C(1,t-1), then the way into G(1,t)
         if (stamp) { *stamp++ = wall_clock64(); *stamp++ = clock64(); }
@@ -841,6 +873,7 @@ struct WsBwdArgs {
     int T, B;
     unsigned spin_limit;
     unsigned long long* stamps;
+    int h0_zero;          // hs[0] is all zeros: dr_pre of step 0 is zero and nothing reads A(hf,0)'s product
 };
 
 #define WS_MFMA_VGPR_B0(acc, a, b) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, 0" : "=v"(acc) : "v"(a), "v"(b))
@@ -926,11 +959,18 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
     const int cfetch = e_row * 32 + (((e_col >> 2) ^ ((e_row >> 1) & 7)) << 2);
 
     // first half of a step from g (= dL/dh_t of this thread's float4): dc_pre, du_pre out, acc_own / hp_own updated
-    auto half_step = [&](int t, int hf, f32x4n g, f32x4n uv, f32x4n cv, f32x4n hp, f32x4n& dc, f32x4n& du) {
+    // The rounding of 1 - c^2 is spelled out.  Left to the compiler's contraction, the copies of this step came out
+    // differently -- inside a stream's gaps element 0 as fma(-c, c, 1) and elements 1..3 as a product and a difference, in
+    // the prologue all four unfused, in a tail that runs on its own (the zero-state form's last one) all four unfused
+    // again -- and the zero-state form must leave the bits of the general one.  fma0 keeps each place as it was built
+    // before: true in the tails of the B streams, false in the prologue.
+    auto half_step = [&](int t, int hf, f32x4n g, f32x4n uv, f32x4n cv, f32x4n hp, f32x4n& dc, f32x4n& du, bool fma0) {
+#pragma clang fp contract(off)
         const bool run = t < len_own[hf];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            dc[i] = run ? g[i] * (1.f - uv[i]) * (1.f - cv[i] * cv[i]) : 0.f;
+            const float omc2 = (fma0 && i == 0) ? __builtin_fmaf(-cv[i], cv[i], 1.f) : 1.f - cv[i] * cv[i];
+            dc[i] = run ? g[i] * (1.f - uv[i]) * omc2 : 0.f;
             du[i] = run ? g[i] * (hp[i] - cv[i]) * uv[i] * (1.f - uv[i]) : 0.f;
             acc_own[hf][i] = run ? g[i] * uv[i] : g[i];
         }
@@ -951,7 +991,7 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
         const f32x4n uv = ws_load2(rs_u, o_std[hf], (unsigned)t * bh_step), cv = ws_load2(rs_c, o_std[hf], (unsigned)t * bh_step);
         const f32x4n hp = ws_load2(rs_hs, o_std[hf], (unsigned)t * bh_step);
         f32x4n dc, du;
-        half_step(t, hf, g, uv, cv, hp, dc, du);
+        half_step(t, hf, g, uv, cv, hp, dc, du, false);
         ws_store2(rs_dxp, o_xp[hf], (unsigned)t * xp_step + 2 * H * 4, dc, false);
         ws_store2(rs_dxp, o_xp[hf], (unsigned)t * xp_step + H * 4, du, false);
         ws_store2(rs_duF, frag_v, frag_st(t, hf), du, false);
@@ -1012,7 +1052,7 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
             va = p0[0] + p0[1] + p0[2] + p0[3] + acc_own[hf];
             if (a.d_outs != nullptr) va += td[hf];
         }
-        if (k == 17 && live) half_step(t - 1, hf, va, tu[hf], tc[hf], th[hf], va, vb);      // va = dc_pre, vb = du_pre afterwards
+        if (k == 17 && live) half_step(t - 1, hf, va, tu[hf], tc[hf], th[hf], va, vb, true);      // va = dc_pre, vb = du_pre afterwards
         if (k == 33) ws_store2(rs_dxp, live ? o_xp[hf] : OOB, ws_uni((unsigned)(t - 1) * xp_step + 2 * H * 4), va, false);
         if (k == 35) ws_store2(rs_dxp, live ? o_xp[hf] : OOB, ws_uni((unsigned)(t - 1) * xp_step + H * 4), vb, false);
         if (k == 37) ws_store2(rs_duF, live ? frag_v : OOB, ws_uni(frag_st(t - 1, hf)), vb, false);
@@ -1031,10 +1071,15 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
         }
     };
 
+    // h_0 = 0 by the caller's promise (a.h0_zero): dr_pre of step 0 = drh h_0 r (1 - r) is zero and nothing else reads
+    // the product of A(hf,0), so the loop below ends behind step 1 and step 0 is finished after it without a stream
+    const int steps = a.h0_zero ? T - 1 : T;
     f32x4n ring[16];                    // the A streams use slots 0..7
-    ws_wait(ctr0, 1u, err, a.spin_limit);
+    if (steps > 0) {
+        ws_wait(ctr0, 1u, err, a.spin_limit);
 #pragma unroll
-    for (int m = 0; m < 8; ++m) ring[m] = ws_load2(rs_dcF, lane16, frag_a(T - 1, 0) + m * 1024);
+        for (int m = 0; m < 8; ++m) ring[m] = ws_load2(rs_dcF, lane16, frag_a(T - 1, 0) + m * 1024);
+    }
 
     // A stream: 32 octets against the LDS slab (128 slots of one MFMA); B stream: 64 octets against the register slab
     // (128 slots of two MFMAs).  HOOK(slot - 4) in every slot; the ring's last 8 refills fetch the NEXT stream's head.
@@ -1094,7 +1139,7 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) pB1[q] = 0.f;
 
-    for (int s = 0; s < T; ++s) {
+    for (int s = 0; s < steps; ++s) {
         const int t = T - 1 - s;
         const unsigned n = (unsigned)(2 * s);
         const bool more = t > 0;        // the B streams of this step exist
@@ -1144,10 +1189,23 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
             pB1 += x;
         }
     }
-    // ---------------- the tail of A(1,0), on its own
+    if (!a.h0_zero) {
+        // ---------------- the tail of A(1,0), on its own
 #pragma unroll
-    for (int k = 1; k <= 39; ++k) a_tail(k, 0, 1, pA1, ctr1, 2u * T);
-    ws_arrive(ctr1, j, 2u * T);
+        for (int k = 1; k <= 39; ++k) a_tail(k, 0, 1, pA1, ctr1, 2u * T);
+        ws_arrive(ctr1, j, 2u * T);
+    } else {
+        // ---------------- step 0 without its A streams: the tail of B(1,1) on its own (du_pre, dc_pre of half-chain 1; at
+        // T = 1 both halves' came from dh_T above), then dxp[0] = (0 | du_pre | dc_pre); the flags end where they always do
+        if (T > 1) {
+#pragma unroll
+            for (int k = 1; k <= 39; ++k) b_tail(k, 1, 1, pB1, ctr1, 2u * T - 1u, true);
+        }
+        ws_store2(rs_dxp, o_xp[0], 0u, (f32x4n)(0.f), false);
+        ws_store2(rs_dxp, o_xp[1], 0u, (f32x4n)(0.f), false);
+        ws_arrive(ctr0, j, 2u * T);
+        ws_arrive(ctr1, j, 2u * T);
+    }
 #undef WS_A_STREAM
 #undef WS_B_STREAM
 }
@@ -1226,8 +1284,11 @@ extern "C" int64_t vqa_gru_ws_workspace_bytes(int T) {
 // with hs[0] given, r,u,c,rh [T,B,H]).  `ws`: vqa_gru_ws_workspace_bytes(T) of device memory (contents irrelevant).
 // After the stream has run, a non-zero word at ((unsigned*)ws)[512] reports a barrier time-out of THIS launch (results
 // invalid); word [1023] is set with it and never cleared by a launch (the caller zeroes it once and may look later).
-extern "C" int vqa_gru_seq_fwd_ws(const float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
-                                  float* r, float* u, float* c, float* rh, int T, int B, int H, void* ws, void* stream) {
+// h0_zero != 0: the caller has written zeros to hs[0] and says so; step 0 then runs without its matrix streams (the tape
+// and hs come out as from the general call, a -0 possibly as +0).  hs[0] is not read, and not written.
+extern "C" int vqa_gru_seq_fwd_ws_ex(const float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
+                                     float* r, float* u, float* c, float* rh, int T, int B, int H, int h0_zero, void* ws,
+                                     void* stream) {
     VQA_REQUIRE(xp && Wg_h && Wc_h && len && hs && r && u && c && rh && ws, VQA_ERR_ARG);
     VQA_REQUIRE(vqa_gru_ws_supported(T, B, H) == 1, VQA_ERR_UNSUPPORTED);
     VQA_REQUIRE((int64_t)T * B * 3 * H * 4 < 0x7FFFFFF0ll && vqa_aligned16(ws), VQA_ERR_UNSUPPORTED);
@@ -1243,6 +1304,7 @@ extern "C" int vqa_gru_seq_fwd_ws(const float* xp, const float* Wg_h, const floa
     a.stamps = g_ws_stamps;
     a.handoff_sc1 = (g_ws_form & 2) ? 1 : 0;
     a.dbg = (g_ws_form >> 4) & 7;
+    a.h0_zero = h0_zero ? 1 : 0;
     // more than 256 rows: chains of 64 rows = two half-chains in anti-phase, tails inside the matrix stream; up to 256
     // rows: chains of 32 rows so that all eight XCDs work (one half-chain each, the plain sub-phase order)
     a.chain_rows = B > 256 ? 64 : 32;
@@ -1252,6 +1314,10 @@ extern "C" int vqa_gru_seq_fwd_ws(const float* xp, const float* Wg_h, const floa
         hipLaunchKernelGGL(gru_ws_fwd_kernel, dim3(WS_CHAINS * WS_CU), dim3(WS_NT), WS_LDS, st, a);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
+}
+extern "C" int vqa_gru_seq_fwd_ws(const float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
+                                  float* r, float* u, float* c, float* rh, int T, int B, int H, void* ws, void* stream) {
+    return vqa_gru_seq_fwd_ws_ex(xp, Wg_h, Wc_h, len, hs, r, u, c, rh, T, B, H, 0, ws, stream);
 }
 
 // 1 when the weight-stationary back-propagation applies: as the forward form, and more than 256 rows (it exists in the
@@ -1266,9 +1332,11 @@ extern "C" int vqa_gru_ws_bwd_supported(int T, int B, int H) {
 // Whole back-propagation through time in one launch: dxp [T,B,3H] = (dr_pre | du_pre | dc_pre) from dh_T [B,H] (read
 // only, unlike vqa_gru_seq_bwd) and the forward tape; d_outs [T,B,H] or NULL as in vqa_gru_seq_bwd_outs.  `ws` as in
 // vqa_gru_seq_fwd_ws (the same buffer may serve both: the calls do not overlap on a stream).
-extern "C" int vqa_gru_seq_bwd_ws(const float* dh_T, const float* d_outs, const float* Wg_h, const float* Wc_h,
-                                  const int32_t* len, const float* hs, const float* r, const float* u, const float* c,
-                                  float* dxp, int T, int B, int H, void* ws, void* stream) {
+// h0_zero != 0: the tape's hs[0] is all zeros by the caller's word; the A streams of step 0 are not run and dxp[0] is
+// written as (0 | du_pre | dc_pre).
+extern "C" int vqa_gru_seq_bwd_ws_ex(const float* dh_T, const float* d_outs, const float* Wg_h, const float* Wc_h,
+                                     const int32_t* len, const float* hs, const float* r, const float* u, const float* c,
+                                     float* dxp, int T, int B, int H, int h0_zero, void* ws, void* stream) {
     VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && hs && r && u && c && dxp && ws, VQA_ERR_ARG);
     VQA_REQUIRE(vqa_gru_ws_bwd_supported(T, B, H) == 1, VQA_ERR_UNSUPPORTED);
     VQA_REQUIRE((int64_t)T * B * 3 * H * 4 < 0x7FFFFFF0ll && vqa_aligned16(ws) && vqa_aligned16(Wg_h) && vqa_aligned16(Wc_h),
@@ -1284,7 +1352,13 @@ extern "C" int vqa_gru_seq_bwd_ws(const float* dh_T, const float* d_outs, const 
     a.T = T; a.B = B;
     a.spin_limit = 2000000u;
     a.stamps = g_ws_stamps;
+    a.h0_zero = h0_zero ? 1 : 0;
     hipLaunchKernelGGL(gru_ws_bwd2_kernel, dim3(WS_CHAINS * WS_CU), dim3(WS_NT), WS_LDS, st, a);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
+}
+extern "C" int vqa_gru_seq_bwd_ws(const float* dh_T, const float* d_outs, const float* Wg_h, const float* Wc_h,
+                                  const int32_t* len, const float* hs, const float* r, const float* u, const float* c,
+                                  float* dxp, int T, int B, int H, void* ws, void* stream) {
+    return vqa_gru_seq_bwd_ws_ex(dh_T, d_outs, Wg_h, Wc_h, len, hs, r, u, c, dxp, T, B, H, 0, ws, stream);
 }

@@ -45,6 +45,11 @@ const char* vqa_hot_error_string(int code);
  * (the whole-model forward fuses the feature rows into v_linear_v's GEMM, vqa_gemm_f32_gather). */
 int vqa_gather_features(const float* table, const int32_t* nbox_table, const int64_t* idx,
                         float* V, int32_t* nb, int B, int R, int D, int64_t N, void* stream);
+/* The same gather for a table that is bf16 at rest (VQA_FLAG_BF16_FEATURES): table [N,R,D] and V [B,R,D] hold raw 16-bit
+ * bf16 patterns, which are copied, never converted.  Same clamp of out-of-range indices, same num_boxes gather, same
+ * meaning of V == NULL.  R * D % 4 == 0 and 8-byte aligned table / V (VQA_ERR_ALIGN otherwise). */
+int vqa_gather_features_bf16(const uint16_t* table, const int32_t* nbox_table, const int64_t* idx,
+                             uint16_t* V, int32_t* nb, int B, int R, int D, int64_t N, void* stream);
 
 /* ---------------------------------------------------------------- a3 / K3
  * tf.nn.embedding_lookup(glove_map, q_intseq)  vqa/model_vlmap_answer.py:134.
@@ -313,6 +318,17 @@ int vqa_attn_pool_fwd(const float* v, const float* qv, const float* V, const int
 int vqa_attn_pool_bwd(const float* dpooled, const float* v, const float* qv, const float* V, const float* att,
                       const float* w, const uint8_t* keepmask, float keep_prob, float* dv, float* dqv,
                       float* part_dw, float* part_db, int B, int R, int H, int D, void* stream);
+/* The same two for a pooled memory V [B,R,D] of raw bf16 patterns (VQA_FLAG_BF16_FEATURES: V_ft gathered from a bf16
+ * table), one query per memory.  Shape by shape they run the kernel class of the f32 entry points (generic, or the
+ * loads-in-flight kernels of the models' shape); a lane loads the four d it loads there as 8 bytes and widens them with
+ * a 16-bit shift, so every sum keeps its order: att, pooled, dv, dqv, part_dw and part_db are bit for bit those of the
+ * f32 entry points on the widened V.  V 8-byte aligned; everything else as above. */
+int vqa_attn_pool_fwd_v16(const float* v, const float* qv, const uint16_t* V, const int32_t* nb, const float* w,
+                          const float* bias, const uint8_t* keepmask, float keep_prob, float* att, float* pooled,
+                          int B, int R, int H, int D, void* stream);
+int vqa_attn_pool_bwd_v16(const float* dpooled, const float* v, const float* qv, const uint16_t* V, const float* att,
+                          const float* w, const uint8_t* keepmask, float keep_prob, float* dv, float* dqv,
+                          float* part_dw, float* part_db, int B, int R, int H, int D, void* stream);
 
 /* `rep` queries per memory (the cfg-5 pre-training model attends n = 5 key boxes per image over the
  * same regions, vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py:323-364, without materialising the
@@ -352,6 +368,9 @@ int vqa_vtail_supported(int rep, int R, int H, int D);
 int vqa_vtail_set_mode(int mode);
 int vqa_attn_pool_bwd_ds(const float* dpooled, const float* V, const float* att, float* ds, float* part_db, int B, int rep,
                          int R, int H, int D, void* stream);
+/* vqa_attn_pool_bwd_ds for V [B,R,D] of raw bf16 patterns (8-byte aligned): the bits of the f32 form on the widened V */
+int vqa_attn_pool_bwd_ds_v16(const float* dpooled, const uint16_t* V, const float* att, float* ds, float* part_db, int B,
+                             int rep, int R, int H, int D, void* stream);
 int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
                         const float* pre, const float* mean, const float* rstd, const float* gamma, const float* beta,
                         float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, float* dqv, float* part_dw,
@@ -552,6 +571,19 @@ typedef struct {
                                      * an f32 product.  With the flag set "gemm_ws" also covers
                                      * vqa_gemm_bf16_workspace_floats of the routed shapes; with it clear every layout is
                                      * what it was. */
+#define VQA_FLAG_BF16_FEATURES 16   /* opt-in on top of VQA_FLAG_BF16_GEMM: the region-feature table is bf16 AT REST.
+                                     * vqa_batch_t.table then points at [N_img,R,D] raw 16-bit bf16 patterns and the
+                                     * workspace tensor "V_ft" holds B * R * D bf16 elements (vqa_fusion_tensor reports that
+                                     * count; vqa_fusion_workspace_bytes shrinks by the 2 B R D bytes V_ft gives up).  The
+                                     * step then runs vqa_gather_features_bf16, vqa_gemm_bf16_a16 for v_linear_v's forward and
+                                     * its dW = V_ft^T d_pre (side stream and max_blocks included), vqa_attn_pool_fwd_v16,
+                                     * and vqa_attn_pool_bwd_v16 or vqa_attn_pool_bwd_ds_v16 (vqa_vtail_set_mode 0 / 1).
+                                     * Rounding is idempotent and every summation order is kept, so a step on a bf16 table
+                                     * equals, bit for bit, the VQA_FLAG_BF16_GEMM step on that table widened to f32.
+                                     * pooled_V_ft and everything downstream stay f32, as does the question encoder.
+                                     * Valid only with VQA_FLAG_BF16_GEMM, without VQA_FLAG_FUSED_GATHER, for model types 0
+                                     * and 1: any other combination makes vqa_fusion_workspace_bytes / _tensor / _forward /
+                                     * _backward / _backward_phases return VQA_ERR_ARG, and nothing is launched. */
 
 /* One FC(+LN) layer: weights [in,out], biases [out], LayerNorm beta/gamma [out] (NULL if no LN). */
 typedef struct { float *w, *b, *beta, *gamma; } vqa_fc_t;
@@ -597,7 +629,8 @@ typedef struct {
 } vqa_params_t;
 
 typedef struct {
-    const float* table;                 /* [N_img,R,D] */
+    const float* table;                 /* [N_img,R,D]; with VQA_FLAG_BF16_FEATURES the same pointer is read as
+                                         * const uint16_t* [N_img,R,D]: raw bf16 patterns (no member moves) */
     const int32_t* nbox_table;          /* [N_img] */
     const int64_t* image_idx;           /* [B] */
     const int32_t* q_intseq;            /* [B,T] zero padded */
@@ -622,7 +655,8 @@ int64_t vqa_fusion_workspace_bytes(const vqa_dims_t* dims);
 /* Byte offset / element count of a named intermediate inside the workspace
  * (names follow the reference's mid_result/output keys: V_ft, num_V_ft,
  * v_linear_v, condition, q_linear_v, att_score, pooled_V_ft, pooled_linear_l,
- * l_linear_l, joint, logit, pred, stats, report, dx_embed, ...). */
+ * l_linear_l, joint, logit, pred, stats, report, dx_embed, ...).  Elements are 4 bytes wide, except "V_ft" under
+ * VQA_FLAG_BF16_FEATURES: n_elems = B * R * D elements of 2 bytes (raw bf16 patterns). */
 int vqa_fusion_tensor(const vqa_dims_t* dims, const char* name, int64_t* offset_bytes, int64_t* n_elems);
 int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* params, const vqa_batch_t* batch,
                        void* workspace, int64_t workspace_bytes, int want_dz, void* stream);
@@ -1025,6 +1059,14 @@ int64_t vqa_gemm_bf16_workspace_floats(int M, int N, int K, int split_k);
 int vqa_gemm_bf16(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                   int ldc, const float* bias, const float* D, int ldd, int split_k, float* workspace,
                   int64_t workspace_floats, int max_blocks, void* stream);
+/* vqa_gemm_bf16 with a left operand that is bf16 in HBM already (raw 16-bit patterns, lda in ELEMENTS); B, bias, D and C f32
+ * as above.  A thread fetches the four elements it fetches there as 8 bytes and stores them to LDS unconverted, so LDS --
+ * and every bit of C -- is that of vqa_gemm_bf16 on the widened A.  NN, TN and NT, any M, N, K >= 1, ragged edges, split k
+ * (workspace: vqa_gemm_bf16_workspace_floats) and max_blocks as above; a base or lda * 2 bytes that is not 8-byte aligned
+ * takes the element-wise load path.  Same error returns. */
+int vqa_gemm_bf16_a16(int transA, int transB, int M, int N, int K, const uint16_t* A, int lda, const float* B, int ldb,
+                      float* C, int ldc, const float* bias, const float* D, int ldd, int split_k, float* workspace,
+                      int64_t workspace_floats, int max_blocks, void* stream);
 /* Short-K GEMM with the left operand stationary in registers (csrc/gemm_shortk.hip):
  *   C[M,N] = [relu]( (A[M,K] * B[K,N]) * scale[n] + bias[n] + D[M,N] )     row-major, bias / scale / D optional (NULL)
  * for K <= 512 -- the packed x-projection of the GRU (K = 300; replaces the x half of GRUCell's two matmuls,

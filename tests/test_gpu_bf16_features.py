@@ -1,0 +1,374 @@
+"""The region-feature table at rest as bf16 (FusionEngine(precision="bf16", features="bf16"), VQA_FLAG_BF16_FEATURES) on
+the GPU.  Rounding to bf16 is idempotent and the new kernels keep every element assignment and summation order of their
+f32-operand twins, so EVERY comparison here is exact: vqa_gather_features_bf16 against the clamped rows,
+vqa_gemm_bf16_a16 against vqa_gemm_bf16 on the widened operand (and, with R.OP_TOL of tests/bf16_ref.py as it stands,
+against the float64 product), vqa_attn_pool_fwd_v16 / vqa_attn_pool_bwd_v16 / vqa_attn_pool_bwd_ds_v16 against the f32-V
+entry points on the widened memory, and the whole step against the bf16 engine bound to the widened table -- which
+tests/test_gpu_bf16.py pins to the float64 reference."""
+import argparse
+import ctypes as C
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import vqa_oracle as O
+from tests import bf16_ref as R
+from tests.gpu_util import dev, dev_batch, make_case, make_engine
+
+pytestmark = pytest.mark.gpu
+
+
+def _ops():
+    from vqa_transfer_externaldata_amd import ops
+    return ops
+
+
+def _lib():
+    from vqa_transfer_externaldata_amd import _lib
+    return _lib
+
+
+def _same_bits(a, b):
+    """two bf16 tensors hold the same 16-bit patterns"""
+    return a.dtype == b.dtype == torch.bfloat16 and a.shape == b.shape and torch.equal(a.contiguous().view(torch.int16), b.contiguous().view(torch.int16))
+
+
+# ---------------------------------------------------------------------------------------------------------- gather
+# [7,6,24]: the issue's case (rows of 288 bytes: 16-byte words); [5,3,4]: rows of 24 bytes (8-byte words); [4,5,2048]:
+# more than one workgroup per row
+@pytest.mark.parametrize("N,Rg,D", [(7, 6, 24), (5, 3, 4), (4, 5, 2048)])
+def test_gather_features_bf16_copies_the_clamped_rows(N, Rg, D):
+    ops = _ops()
+    g = torch.Generator().manual_seed(N)
+    table = torch.randn(N, Rg, D, generator=g).to(torch.bfloat16).cuda()
+    nbox = torch.randint(1, Rg + 1, (N,), generator=g, dtype=torch.int32).cuda()
+    idx = torch.tensor([-1, N + 3, 0, N - 1, 2, 2, -7, N], dtype=torch.int64).cuda()
+    V, nb = ops.gather_features_bf16(table, nbox, idx)
+    want = idx.clamp(0, N - 1)
+    assert V.dtype == torch.bfloat16 and _same_bits(V, table[want])
+    assert torch.equal(nb, nbox[want])
+    # V == NULL: num_boxes only
+    lib = _lib().load()
+    nb2 = torch.full_like(nb, -5)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.vqa_gather_features_bf16(p(table), p(nbox), p(idx), None, p(nb2), idx.numel(), Rg, D, N, st) == 0
+    assert torch.equal(nb2, nb)
+
+
+# ---------------------------------------------------------------------------------------------------------- GEMM
+def _pair(A16, B, tA, tB, what, **kw):
+    """gemm_bf16_a16(A16, ...) == gemm_bf16(A16.float(), ...) bit for bit, and within R.OP_TOL of the float64 product"""
+    ops = _ops()
+    A32 = A16.float().contiguous()
+    got = ops.gemm_bf16_a16(A16, B, transA=tA, transB=tB, **kw)
+    want = ops.gemm_bf16(A32, B, transA=tA, transB=tB, **kw)
+    assert torch.isfinite(got).all(), what
+    assert torch.equal(got, want), (what, float((got - want).abs().max()))
+    ratio = R.op_ratio(got, A32, B, tA, tB, kw.get("bias"), kw.get("add"))
+    print("%s: ratio %.3e" % (what, ratio))
+    assert ratio <= R.OP_TOL, (what, ratio)
+    return got
+
+
+SHAPES = [(1, 1, 1), (33, 17, 5), (130, 132, 70), (128, 128, 64), (257, 96, 100)]
+
+
+@pytest.mark.parametrize("lay", ["NN", "TN", "NT"])
+@pytest.mark.parametrize("M,N,K", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
+def test_gemm_bf16_a16_equals_gemm_bf16_on_the_widened_operand(lay, M, N, K):
+    for seed in (0, 1):
+        A, B, bias, add, tA, tB = R.op_case(lay, M, N, K, seed, device="cuda", bias=True, add=True)
+        A16 = A.to(torch.bfloat16)
+        _pair(A16, B, tA, tB, "%s %dx%dx%d plain" % (lay, M, N, K))
+        _pair(A16, B, tA, tB, "%s %dx%dx%d bias add" % (lay, M, N, K), bias=bias, add=add)
+
+
+@pytest.mark.parametrize("split", [1, 2, 0])
+def test_gemm_bf16_a16_split_k(split):
+    # TN with a summed dimension of 288 (nine k tiles: ranges of 160 + 128 at split 2)
+    A, B, bias, add, tA, tB = R.op_case("TN", 70, 40, 288, 3, device="cuda", bias=True, add=True)
+    _pair(A.to(torch.bfloat16), B, tA, tB, "TN 70x40x288 split %d" % split, bias=bias, add=add, split_k=split)
+    # a summed dimension deep enough for the automatic choice to cut it (one tile, K 1024: four ranges), NN and TN
+    lib = _lib().load()
+    assert lib.vqa_gemm_bf16_workspace_floats(64, 64, 1024, 0) == 4 * 64 * 64
+    for lay in ("NN", "TN"):
+        A, B, bias, add, tA, tB = R.op_case(lay, 64, 64, 1024, 4, device="cuda", bias=True, add=True)
+        _pair(A.to(torch.bfloat16), B, tA, tB, "%s 64x64x1024 split %d" % (lay, split), bias=bias, add=add, split_k=split)
+
+
+@pytest.mark.parametrize("lay", ["NN", "TN", "NT"])
+def test_gemm_bf16_a16_unaligned_operand_max_blocks_and_in_place_addend(lay):
+    ops = _ops()
+    M, N, K = 130, 132, 70
+    A, B, bias, add, tA, tB = R.op_case(lay, M, N, K, 6, device="cuda", bias=True, add=True)
+    A16 = A.to(torch.bfloat16)
+    ref = _pair(A16, B, tA, tB, "%s aligned" % lay, bias=bias)
+    # an odd leading dimension and a base one element (2 bytes) off: the element-wise load path, same bits
+    wide = torch.zeros(A16.shape[0], A16.shape[1] + 3, dtype=torch.bfloat16, device="cuda")
+    wide[:, 1:1 + A16.shape[1]] = A16
+    view = wide[:, 1:1 + A16.shape[1]]
+    assert view.stride(0) % 2 == 1 and view.data_ptr() % 8 == 2
+    assert torch.equal(_pair(view, B, tA, tB, "%s odd lda, base + 1" % lay, bias=bias), ref)
+    # 8-byte aligned but not 16: the 8-byte vector path on a base the f32 twin never sees
+    wide4 = torch.zeros(A16.shape[0], A16.shape[1] + 6, dtype=torch.bfloat16, device="cuda")
+    wide4[:, 4:4 + A16.shape[1]] = A16
+    view4 = wide4[:, 4:4 + A16.shape[1]]
+    assert view4.stride(0) % 4 == 0 and view4.data_ptr() % 16 == 8
+    assert torch.equal(_pair(view4, B, tA, tB, "%s base + 4" % lay, bias=bias), ref)
+    # at most three persistent workgroups over the 4 tiles (x 2 k ranges)
+    assert torch.equal(_pair(A16, B, tA, tB, "%s max_blocks 3" % lay, bias=bias, max_blocks=3), ref)
+    _pair(A16, B, tA, tB, "%s max_blocks 3 split 2" % lay, bias=bias, add=add, split_k=2, max_blocks=3)
+    # bias plus an addend that is the output itself
+    acc, acc32 = add.clone(), add.clone()
+    ops.gemm_bf16_a16(A16, B, transA=tA, transB=tB, bias=bias, add=acc, out=acc)
+    ops.gemm_bf16(A16.float(), B, transA=tA, transB=tB, bias=bias, add=acc32, out=acc32)
+    assert torch.equal(acc, acc32)
+    assert R.op_ratio(acc, A16.float(), B, tA, tB, bias, add) <= R.OP_TOL
+
+
+@pytest.mark.parametrize("lay,M,N,K", [("NN", 288, 1024, 2048), ("TN", 2048, 1024, 288)])
+def test_gemm_bf16_a16_one_slice_of_the_real_shape(lay, M, N, K):
+    A, B, bias, _, tA, tB = R.op_case(lay, M, N, K, 2, device="cuda", bias=True)
+    _pair(A.to(torch.bfloat16), B, tA, tB, "%s %dx%dx%d" % (lay, M, N, K), bias=bias if lay == "NN" else None)
+
+
+def test_gemm_bf16_a16_argument_checks_launch_nothing():
+    lib = _lib().load()
+    A = torch.ones(256, 2048, dtype=torch.bfloat16, device="cuda")
+    B = torch.ones(2048, 256, device="cuda")
+    out = torch.full((256, 256), 7.0, device="cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    call = lambda *a: lib.vqa_gemm_bf16_a16(*a)
+    assert call(0, 0, 256, 256, 2048, None, 2048, p(B), 256, p(out), 256, None, None, 0, 1, None, 0, 0, st) == -1       # null A
+    assert call(0, 0, 256, 256, 2048, p(A), 2048, None, 256, p(out), 256, None, None, 0, 1, None, 0, 0, st) == -1       # null B
+    assert call(0, 0, 256, 256, 2048, p(A), 2048, p(B), 256, None, 256, None, None, 0, 1, None, 0, 0, st) == -1         # null C
+    assert call(0, 0, 256, 256, 2048, p(A), 2047, p(B), 256, p(out), 256, None, None, 0, 1, None, 0, 0, st) == -1       # lda < K
+    assert call(1, 0, 256, 256, 2048, p(A), 255, p(B), 256, p(out), 256, None, None, 0, 1, None, 0, 0, st) == -1        # transA: lda < M
+    assert call(1, 1, 256, 256, 2048, p(A), 2048, p(B), 2048, p(out), 256, None, None, 0, 1, None, 0, 0, st) == -4      # both transposed
+    assert call(0, 0, 256, 256, 2048, p(A), 2048, p(B), 256, p(out), 256, None, None, 0, 4, None, 0, 0, st) == -5       # split k, no workspace
+    ws = torch.zeros(4 * 256 * 256 - 1, device="cuda")
+    assert call(0, 0, 256, 256, 2048, p(A), 2048, p(B), 256, p(out), 256, None, None, 0, 4, p(ws), ws.numel(), 0, st) == -5   # too small
+    torch.cuda.synchronize()
+    assert (out == 7.0).all() and (ws == 0).all()                                     # nothing was launched
+
+
+# ---------------------------------------------------------------------------------------------------------- attention
+def _attn_case(B, Rg, H, D, seed, full_row=0):
+    g = torch.Generator().manual_seed(seed)
+    v = torch.randn(B, Rg, H, generator=g).cuda()
+    qv = torch.randn(B, H, generator=g).cuda()
+    V16 = torch.randn(B, Rg, D, generator=g).to(torch.bfloat16).cuda()
+    nb = torch.tensor([Rg if i == full_row else 1 + (3 * i) % Rg for i in range(B)], dtype=torch.int32)   # 1..R, one full row
+    w = (torch.randn(H, generator=g) / H ** 0.5).cuda()
+    bias = torch.randn(1, generator=g).cuda()
+    keep = (torch.rand(B, Rg, H, generator=g) < 0.8).to(torch.uint8).cuda()
+    dpooled = torch.randn(B, D, generator=g).cuda()
+    return v, qv, V16, nb.cuda(), w, bias, keep, dpooled
+
+
+def _attn_equal(B, Rg, H, D, seed, with_mask, expect_ds):
+    ops, L = _ops(), _lib()
+    v, qv, V16, nb, w, bias, keep, dpooled = _attn_case(B, Rg, H, D, seed)
+    V32 = V16.float()
+    assert int(nb.max()) == Rg and int(nb.min()) < Rg
+    km, kp = (keep, 0.8) if with_mask else (None, 1.0)
+    att, pooled = ops.attn_pool_fwd_v16(v, qv, V16, nb, w, bias, km, kp)
+    att32, pooled32 = ops.attn_pool_fwd(v, qv, V32, nb, w, bias, km, kp)
+    assert torch.isfinite(pooled).all() and torch.equal(att, att32) and torch.equal(pooled, pooled32)
+    got = ops.attn_pool_bwd_v16(dpooled, v, qv, V16, att, w, km, kp)
+    want = ops.attn_pool_bwd(dpooled, v, qv, V32, att, w, km, kp)
+    for name, a, b in zip(("dv", "dqv", "dw", "db"), got, want):
+        assert torch.isfinite(a).all() and torch.equal(a, b), name
+    if expect_ds:
+        ds, pdb = ops.attn_pool_bwd_ds_v16(dpooled, V16, att)
+        ds32, pdb32 = ops.attn_pool_bwd_ds(dpooled, V32, att)
+        assert torch.isfinite(ds).all() and torch.equal(ds, ds32) and torch.equal(pdb, pdb32)
+    else:      # the chain exists at one shape only: both forms say so
+        for f, Vx in ((ops.attn_pool_bwd_ds_v16, V16), (ops.attn_pool_bwd_ds, V32)):
+            with pytest.raises(L.VqaHotError, match="unsupported"):
+                f(dpooled, Vx, att)
+
+
+# generic kernels: B 3, R 5, H 8, D 12; the loads-in-flight kernels of the models' shape: B 4, R 36, H 1024, D 2048; the
+# forward's other instantiations (H 256, two 2048-wide column groups) over a short memory
+ATTN_SHAPES = [("generic", 3, 5, 8, 12, False), ("fast", 4, 36, 1024, 2048, True), ("fast-fwd-h256-d4096", 2, 7, 256, 4096, False)]
+
+
+@pytest.mark.parametrize("with_mask", [False, True], ids=["nomask", "mask"])
+@pytest.mark.parametrize("name,B,Rg,H,D,ds", ATTN_SHAPES, ids=[s[0] for s in ATTN_SHAPES])
+def test_attention_over_a_bf16_memory_equals_the_f32_entry_points(name, B, Rg, H, D, ds, with_mask):
+    _attn_equal(B, Rg, H, D, 11, with_mask, ds)
+
+
+def test_generic_attention_kernels_at_the_models_shape():
+    """vqa_attn_set_fast(0): the generic kernels' strided loops over many columns, bf16 memory against f32 memory"""
+    lib = _lib().load()
+    lib.vqa_attn_set_fast(0)
+    try:
+        _attn_equal(2, 36, 1024, 2048, 12, True, True)
+    finally:
+        lib.vqa_attn_set_fast(1)
+
+
+# ---------------------------------------------------------------------------------------------------------- the step
+def _engine(model_type, p, table_dev, nbox, am, B, Rg, T, dims, **kw):
+    from vqa_transfer_externaldata_amd import fusion as F
+    eng = F.FusionEngine(model_type=model_type, B=B, R=Rg, T=T, N_img=table_dev.shape[0],
+                         params={k: v.astype(np.float32) for k, v in p.items() if not O.is_const(k)}, **dims, **kw)
+    eng.bind_inputs(table=table_dev, nbox_table=dev(nbox), answer_masks={k: dev(v.astype(np.float32)) for k, v in am.items()})
+    return eng
+
+
+STEP_CASES = [c for c in R.MODEL_CASES if c[0] in ("small", "full_dims")]
+WATCHED = ("logit", "pooled_V_ft", "report", "att_score", "pred", "d_pre_v")
+
+
+def _steps_equal(model_type, case):
+    name, dims, B, Rg, T, N = case
+    p, table, nbox, batch, am, masks = make_case(R.MODEL_SEED, model_type, B, Rg, T, N, dims)
+    T16 = dev(table.astype(np.float32)).to(torch.bfloat16)
+    X = _engine(model_type, p, T16.float(), nbox, am, B, Rg, T, dims, precision="bf16", deterministic=True)
+    Y = _engine(model_type, p, T16, nbox, am, B, Rg, T, dims, precision="bf16", features="bf16", deterministic=True)
+    assert (X.features, Y.features) == ("f32", "bf16") and Y.dims.flags & 16 and not X.dims.flags & 16
+    assert Y.workspace.numel() < X.workspace.numel()
+    assert abs((X.workspace.numel() - Y.workspace.numel()) - 2 * B * Rg * dims["D"]) < 256
+    db = dev_batch(batch)
+    ka, kj = dev(masks["att"].astype(np.uint8)), dev(masks["joint"].astype(np.uint8))
+    for step in (1, 2):
+        for e in (X, Y):
+            e.train_step(db, ka, kj, 1e-3)
+        torch.cuda.synchronize()
+        assert torch.isfinite(Y.grad_flat).all()
+        for n in X.train_names:
+            assert torch.equal(X.grads[n], Y.grads[n]), (step, n)
+        assert torch.equal(X.grad_flat, Y.grad_flat), step                  # the slice sum of squares in the tail included
+        for n in WATCHED:
+            assert torch.equal(X.tensor(n), Y.tensor(n)), (step, n)
+        assert X.report() == Y.report()
+        vft = Y.tensor("V_ft")
+        assert vft.dtype == torch.bfloat16 and vft.numel() == B * Rg * dims["D"]
+        assert _same_bits(vft.view(B, Rg, dims["D"]), T16[db["image_idx"]])
+        assert torch.equal(X.tensor("V_ft").view(B, Rg, dims["D"]), T16[db["image_idx"]].float())
+    for n in X.params:
+        assert torch.equal(X.params[n], Y.params[n]), n
+    assert torch.equal(X.train_flat, Y.train_flat) and torch.equal(X.m_flat, Y.m_flat) and torch.equal(X.v_flat, Y.v_flat)
+    # the eval forward: no dropout, no dz
+    for e in (X, Y):
+        e.forward(db, None, None, want_dz=False)
+    torch.cuda.synchronize()
+    for n in ("logit", "pooled_V_ft", "report", "pred", "att_score"):
+        assert torch.equal(X.tensor(n), Y.tensor(n)), ("eval", n)
+
+
+@pytest.mark.parametrize("model_type", R.MODEL_TYPES)
+def test_step_on_a_bf16_table_equals_the_bf16_step_on_the_widened_table_small(model_type):
+    _steps_equal(model_type, STEP_CASES[0])
+
+
+@pytest.mark.parametrize("vtail", [0, 1], ids=["separate-calls", "fused-chain"])
+@pytest.mark.parametrize("model_type", R.MODEL_TYPES)
+def test_step_on_a_bf16_table_equals_the_bf16_step_on_the_widened_table_full_dims(model_type, vtail):
+    """R 36, H 1024, D 2048: the loads-in-flight attention kernels, and both backward routes of vqa_vtail_set_mode"""
+    lib = _lib().load()
+    assert STEP_CASES[1][0] == "full_dims"
+    assert lib.vqa_vtail_set_mode(vtail) == vtail
+    try:
+        _steps_equal(model_type, STEP_CASES[1])
+    finally:
+        lib.vqa_vtail_set_mode(-1)
+
+
+@pytest.mark.parametrize("model_type", R.MODEL_TYPES)
+def test_features_f32_is_bitwise_the_engine_without_the_argument(model_type):
+    dims, B, Rg, T, N = R.MED, 32, 36, 14, 64
+    p, table, nbox, batch, am, masks = make_case(31, model_type, B, Rg, T, N, dims)
+    db = dev_batch(batch)
+    ka, kj = dev(masks["att"].astype(np.uint8)), dev(masks["joint"].astype(np.uint8))
+    for precision in ("f32", "bf16"):
+        res = []
+        for kw in ({}, {"features": "f32"}):
+            eng = make_engine(model_type, p, table, nbox, am, B, Rg, T, dims, deterministic=True, precision=precision, **kw)
+            assert eng.features == "f32" and not eng.dims.flags & 16 and eng.tensor("V_ft").dtype == torch.float32
+            for _ in range(2):
+                eng.train_step(db, ka, kj, 1e-3)
+            torch.cuda.synchronize()
+            res.append((float(eng.loss()), eng.grad_flat.clone(), eng.train_flat.clone(), eng.workspace.numel()))
+        (l0, g0, t0, w0), (l1, g1, t1, w1) = res
+        assert l0 == l1 and torch.equal(g0, g1) and torch.equal(t0, t1) and w0 == w1
+
+
+def test_refusals():
+    dims, B, Rg, T, N = R.SMALL, 5, 6, 7, 9
+    p, table, nbox, batch, am, masks = make_case(3, "vlmap_answer", B, Rg, T, N, dims)
+    with pytest.raises(ValueError, match="precision"):
+        make_engine("vlmap_answer", p, table, nbox, am, B, Rg, T, dims, features="bf16")
+    with pytest.raises(ValueError, match="precision"):
+        make_engine("vlmap_answer", p, table, nbox, am, B, Rg, T, dims, precision="f32", features="bf16")
+    with pytest.raises(ValueError, match="fused_gather"):
+        make_engine("vlmap_answer", p, table, nbox, am, B, Rg, T, dims, precision="bf16", features="bf16", fused_gather=True)
+    for bad in ("fp16", "BF16", None, 16):
+        with pytest.raises(ValueError, match="features"):
+            make_engine("vlmap_answer", p, table, nbox, am, B, Rg, T, dims, precision="bf16", features=bad)
+    for mt in ("standard_word2vec", "standard_testmask", "vlmap_answer_vqa_all2", "vlmap_answer_noc", "vlmap_answer_adapt"):
+        pm, tm, nm, _, amm, _ = make_case(3, mt, B, Rg, T, N, dims)
+        with pytest.raises(ValueError, match="bf16"):
+            make_engine(mt, pm, tm, nm, amm, B, Rg, T, dims, precision="bf16", features="bf16")
+    # a table of another dtype, on the host, or of another shape is refused, never converted
+    T32 = dev(table.astype(np.float32))
+    kw = dict(precision="bf16", features="bf16")
+    for bad in (T32, T32.half(), T32.to(torch.bfloat16).cpu(), T32.to(torch.bfloat16)[:, :, :-4], T32.to(torch.bfloat16)[:, :-1],
+                table.astype(np.float32)):
+        with pytest.raises(ValueError, match="bfloat16"):
+            _engine("vlmap_answer", p, bad, nbox, am, B, Rg, T, dims, **kw)
+    eng = _engine("vlmap_answer", p, T32.to(torch.bfloat16), nbox, am, B, Rg, T, dims, **kw)
+    assert eng.dims.flags & _lib().FLAG_BF16_FEATURES == 16
+
+
+# ---------------------------------------------------------------------------------------------------------- trainer
+def test_trainer_features_bf16_learns_and_its_checkpoint_loads_in_an_f32_evaler(tmp_path):
+    from tests.test_gpu_bf16 import _features
+    from vqa_transfer_externaldata_amd import evaler, input_ops_vqa as io, trainer
+    c = trainer.parse_config(["--batch_size", "32", "--max_train_iter", "12", "--train_average_iter", "4",
+                              "--val_average_iter", "2", "--validation_step", "6", "--checkpoint_step", "6",
+                              "--heavy_summary_step", "6", "--model_type", "standard", "--learning_rate", "0.002",
+                              "--precision", "bf16", "--features", "bf16"])
+    Vq, A = 60, 40
+    c.vocab = {"vocab": ["w%d" % i for i in range(Vq)], "dict": {"w%d" % i: i for i in range(Vq)}}
+    c.answer_dict = {"vocab": ["a%d" % i for i in range(A)], "dict": {"a%d" % i: i for i in range(A)},
+                     "num_train_answer": 30, "is_object": [i % 2 for i in range(A)],
+                     "is_attribute": [1 - i % 2 for i in range(A)]}
+    c.synthetic = 1
+    c.train_dir = str(tmp_path / "run_features_bf16")
+    c.tf_record_dir = str(tmp_path / "data")
+    ds = {"train": io.synthetic_split(96, 24, Vq, A, seed=1), "val": io.synthetic_split(40, 24, Vq, A, seed=2),
+          "testval": io.synthetic_split(40, 24, Vq, A, seed=3)}
+    feats = _features()
+    t = trainer.Trainer(c, datasets=ds, image_features=feats)
+    eng = t.model.engine
+    assert (eng.precision, eng.features) == ("bf16", "bf16")
+    assert eng._table.dtype == torch.bfloat16 and eng._table.is_cuda
+    assert _same_bits(eng._table, torch.from_numpy(feats["features"]).to(torch.bfloat16).cuda())      # rounded once, at load
+    val_loss = lambda: float(np.mean([t.run_val_step(False, "val")[2] for _ in range(4)]))   # dropout off, same split
+    loss0 = val_loss()
+    t.run_train_step(True)
+    t.train()
+    loss1 = val_loss()
+    print("validation loss before / after 13 train steps on a bf16 table: %.5f / %.5f" % (loss0, loss1))
+    assert np.isfinite(loss0) and np.isfinite(loss1) and loss1 < loss0
+    assert all(torch.isfinite(v).all() for v in t.model.variables().values())
+    ckpt = os.path.join(c.train_dir, "model-8")
+    assert os.path.exists(ckpt)
+    sd = torch.load(ckpt)
+    assert all(v.dtype in (torch.float32, torch.int64) for v in sd.values())           # checkpoints are those of f32
+    ec = argparse.Namespace(**vars(c))
+    ec.checkpoint, ec.split, ec.max_iter, ec.dump_heavy_output, ec.precision, ec.features = ckpt, "testval", -1, False, "f32", "f32"
+    ev = evaler.Evaler(ec, image_features=_features(), data=ds["testval"])
+    assert (ev.model.engine.precision, ev.model.engine.features) == ("f32", "f32")
+    ev.eval()
+    saved = pickle.load(open(ev.save_pkl, "rb"))
+    assert len(saved["qid2result"]) == 40 and np.isfinite(saved["avg_eval_report"]["answer_report_loss"])

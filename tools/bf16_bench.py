@@ -6,7 +6,13 @@ bf16 x 3 experiment, alternated in ONE process on one box:
   (c) the whole configs[1] train step (bench.py's synthetic bs-512 case), precision "f32" and "bf16" alternated
   (d) the error ratios of tests/test_gpu_bf16.py: max |got - ref| / (|A^||B^|) against the float64 reference of the op
 
+  (e) --ab_features (this leg alone): the feature table at rest as bf16 -- engine X (precision "bf16", the table widened
+      to f32) against engine Y (precision "bf16", features "bf16") alternated step by step at bs 512, full dims, the
+      median of 20 steps repeated 5 times (the spread of X's own medians is the yardstick of the difference), then the
+      five kernels of the mode in both forms: the two GEMMs that read V_ft, the gather, the three attention entry points
+
 usage: bf16_bench.py [--iters 20] [--step-iters 12] [--skip-ops] [--skip-step] [--skip-errors] [--step-precisions bf16]
+       bf16_bench.py --ab_features [--iters 20] [--repeats 5]
 Every time is the median of the timed iterations after 3 warm-up iterations (device events); the achieved byte rate is
 the algorithmic traffic 4 (MK + KN + MN) over that time, as a fraction of the 6.3 TB/s a copy achieves on the MI355X."""
 import argparse
@@ -146,6 +152,101 @@ def bench_step(iters, precisions=("f32", "bf16")):
         print("%s / %s step time: %.2fx" % (precisions[0], precisions[1], res[0][0] / res[1][0]), flush=True)
 
 
+def bench_ab_features(iters, repeats):
+    import bench as BENCH
+    from vqa_transfer_externaldata_amd import fusion as F
+    cfg = dict(BENCH.CFG)
+    dev = torch.device("cuda", 0)
+    params = BENCH.synth_params("vlmap_answer", cfg, seed=1234)
+    table, nbox, am, batches = BENCH.synth_inputs(cfg, seed=1234, device=dev)
+    T16 = table.to(torch.bfloat16)
+    del table
+    T32 = T16.float()                    # X's table: f32 at rest, values already bf16-representable
+    B, Rg, D, H = cfg["B"], cfg["R"], cfg["D"], cfg["H"]
+    engs = {}
+    for name, kw, tab in (("X", {}, T32), ("Y", {"features": "bf16"}, T16)):
+        e = F.FusionEngine(model_type="vlmap_answer", B=B, R=Rg, D=D, H=H, T=cfg["T"], W=cfg["W"], A=cfg["A"], Vq=cfg["Vq"],
+                           N_img=cfg["N_img"], params=params, device=dev, precision="bf16", **kw)
+        e.bind_inputs(table=tab, nbox_table=nbox, answer_masks=am)
+        engs[name] = e
+    count = {"X": 0, "Y": 0}
+
+    def step(name):
+        e, i = engs[name], count[name]
+        ka, kj = e.make_keep_masks(seed=99, step=i)
+        e.train_step(batches[i % len(batches)], ka, kj, 1e-3)
+        count[name] += 1
+
+    print("== (e) feature table at rest: X = precision bf16 on the widened f32 table, Y = precision bf16 + features bf16")
+    print("resident table %d x %d x %d: f32 %.1f MB, bf16 %.1f MB; V_ft per step: f32 %.1f MB, bf16 %.1f MB; workspace X %.1f MB, Y %.1f MB"
+          % (cfg["N_img"], Rg, D, T32.numel() * 4 / 1e6, T16.numel() * 2 / 1e6, B * Rg * D * 4 / 1e6, B * Rg * D * 2 / 1e6,
+             engs["X"].workspace.numel() / 1e6, engs["Y"].workspace.numel() / 1e6), flush=True)
+    meds = {"X": [], "Y": []}
+    for r in range(repeats):
+        res = alternate_us([lambda: step("X"), lambda: step("Y")], iters)
+        for name, (med, best) in zip(("X", "Y"), res):
+            meds[name].append(med)
+        print("repeat %d: X median %.3f ms (best %.3f)   Y median %.3f ms (best %.3f)   X / Y %.4f"
+              % (r, res[0][0] / 1e3, res[0][1] / 1e3, res[1][0] / 1e3, res[1][1] / 1e3, res[0][0] / res[1][0]), flush=True)
+    mx, my = sorted(meds["X"])[repeats // 2], sorted(meds["Y"])[repeats // 2]
+    spread = max(meds["X"]) - min(meds["X"])
+    print("median of the %d medians: X %.3f ms, Y %.3f ms, X - Y = %.1f us; spread (max - min) of X's medians %.1f us, of Y's %.1f us"
+          % (repeats, mx / 1e3, my / 1e3, mx - my, spread, max(meds["Y"]) - min(meds["Y"])))
+    print("verdict: Y is %s" % ("faster than X by more than X's own spread" if mx - my > spread else
+                                "NOT faster than X by more than X's own spread"), flush=True)
+    same = torch.equal(engs["X"].train_flat, engs["Y"].train_flat)
+    print("parameters after %d steps each: %s (non-deterministic embedding scatter-add: equality is not required here)"
+          % (count["X"], "bitwise equal" if same else "differ"), flush=True)
+    del engs
+    torch.cuda.empty_cache()
+
+    # ---- the five kernels, both forms alternated; bytes: what the kernel must move (operands once, result once)
+    from tests import bf16_ref as R
+    print("== (e) kernels, f32 operand | bf16 operand, alternated, median us (best us)")
+
+    def line(name, fs, bytes32, bytes16):
+        (m32, b32), (m16, b16) = alternate_us(fs, iters)
+        print("%-34s f32 %8.1f (%8.1f)  %5.2f TB/s | bf16 %8.1f (%8.1f)  %5.2f TB/s | f32 / bf16 = %.3fx"
+              % (name, m32, b32, bytes32 / m32 / 1e6, m16, b16, bytes16 / m16 / 1e6, m32 / m16), flush=True)
+
+    for name, lay, M, N, K in (("v_linear_v fwd NN 18432x1024x2048", "NN", 18432, 1024, 2048),
+                               ("v_linear_v dW  TN 2048x1024x18432", "TN", 2048, 1024, 18432)):
+        A, Bm, bias, _, tA, tB = R.op_case(lay, M, N, K, seed=0, device="cuda", bias=True)
+        A16 = A.to(torch.bfloat16)
+        A32 = A16.float()
+        del A
+        o32, o16 = torch.empty(M, N, device="cuda"), torch.empty(M, N, device="cuda")
+        line(name, [lambda: ops.gemm_bf16(A32, Bm, transA=tA, transB=tB, bias=bias, out=o32),
+                    lambda: ops.gemm_bf16_a16(A16, Bm, transA=tA, transB=tB, bias=bias, out=o16)],
+             4.0 * (M * K + K * N + M * N), 2.0 * M * K + 4.0 * (K * N + M * N))
+        assert torch.equal(o32, o16)
+        del A16, A32, o32, o16
+    idx = batches[0]["image_idx"]
+    line("gather [512,36,2048]", [lambda: ops.gather_features(T32, nbox, idx), lambda: ops.gather_features_bf16(T16, nbox, idx)],
+         2 * 4.0 * B * Rg * D, 2 * 2.0 * B * Rg * D)
+    g = torch.Generator(device=dev).manual_seed(5)
+    v = torch.randn(B, Rg, H, generator=g, device=dev)
+    qv = torch.randn(B, H, generator=g, device=dev)
+    V16 = ops.gather_features_bf16(T16, nbox, idx)[0]
+    V32 = V16.float()
+    nb = torch.full((B,), Rg, dtype=torch.int32, device=dev)
+    w = torch.randn(H, generator=g, device=dev) / H ** 0.5
+    bias = torch.zeros(1, device=dev)
+    keep = (torch.rand(B, Rg, H, generator=g, device=dev) < 0.8).to(torch.uint8)
+    dp = torch.randn(B, D, generator=g, device=dev)
+    att, _ = ops.attn_pool_fwd(v, qv, V32, nb, w, bias, keep, 0.8)
+    vb, mb = 4.0 * B * Rg * H, 1.0 * B * Rg * H
+    line("attn_pool_fwd", [lambda: ops.attn_pool_fwd(v, qv, V32, nb, w, bias, keep, 0.8),
+                           lambda: ops.attn_pool_fwd_v16(v, qv, V16, nb, w, bias, keep, 0.8)],
+         vb + mb + 4.0 * B * Rg * D, vb + mb + 2.0 * B * Rg * D)
+    line("attn_pool_bwd (+ 2 colsums)", [lambda: ops.attn_pool_bwd(dp, v, qv, V32, att, w, keep, 0.8),
+                                         lambda: ops.attn_pool_bwd_v16(dp, v, qv, V16, att, w, keep, 0.8)],
+         2 * vb + mb + 4.0 * B * Rg * D, 2 * vb + mb + 2.0 * B * Rg * D)
+    line("attn_pool_bwd_ds", [lambda: ops.attn_pool_bwd_ds(dp, V32, att), lambda: ops.attn_pool_bwd_ds_v16(dp, V16, att)],
+         4.0 * B * Rg * D, 2.0 * B * Rg * D)
+    print("(every op call allocates its outputs inside the timed region, the same on both sides)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -155,9 +256,14 @@ def main():
     ap.add_argument("--skip-ops", action="store_true")
     ap.add_argument("--step-precisions", nargs="+", default=["f32", "bf16"], choices=["f32", "bf16"],
                     help="the engines of part (c); one name = that step alone (for a kernel trace)")
+    ap.add_argument("--ab_features", action="store_true", help="leg (e) alone: f32 against bf16 feature table")
+    ap.add_argument("--repeats", type=int, default=5, help="repeated medians of leg (e)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bf16_bench.py needs a GPU: a time taken elsewhere says nothing")
+    if args.ab_features:
+        bench_ab_features(args.iters, args.repeats)
+        return
     if not args.skip_errors:
         bench_errors()
     if not args.skip_ops:

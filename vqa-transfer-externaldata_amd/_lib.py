@@ -30,6 +30,7 @@ FLAG_DETERMINISTIC = 1
 FLAG_FUSED_GATHER = 2
 FLAG_SHARED_LN = 4
 FLAG_BF16_GEMM = 8
+FLAG_BF16_FEATURES = 16
 
 
 class Fc(C.Structure):
@@ -149,6 +150,7 @@ SIGNATURES = {
     "vqa_hot_version": (_I, []),
     "vqa_hot_error_string": (C.c_char_p, [_I]),
     "vqa_gather_features": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _L, _P]),
+    "vqa_gather_features_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _L, _P]),
     "vqa_embed_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_gru_pack_wx": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vqa_gru_unpack_dwx": (_I, [_P, _P, _P, _I, _I, _P]),
@@ -219,12 +221,15 @@ SIGNATURES = {
     "vqa_attn_set_fast": (_I, [_I]),
     "vqa_attn_pool_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_fwd_v16": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_bwd_v16": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_fwd_rep": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_bwd_rep": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_vtail_supported": (_I, [_I, _I, _I, _I]),
     "vqa_vtail_set_mode": (_I, [_I]),
     "vqa_gru_h0skip_set_mode": (_I, [_I]),
     "vqa_attn_pool_bwd_ds": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_bwd_ds_v16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_ln_relu_att_bwd": (_I, [_P, _P, _P, _P, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
     "vqa_colsum_vtail_workspace_floats": (_L, [_I, _I]),
     "vqa_colsum_vtail": (_I, [_P] * 5 + [_I, _I] + [_P] * 6 + [_L, _P]),
@@ -300,6 +305,7 @@ SIGNATURES = {
     "vqa_gemm_bf16x3_set_mode": (_I, [_I]),
     "vqa_gemm_bf16_workspace_floats": (_L, [_I, _I, _I, _I]),
     "vqa_gemm_bf16": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _L, _I, _P]),
+    "vqa_gemm_bf16_a16": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _L, _I, _P]),
     "vqa_probe_disable": (_I, []),
     "vqa_fusion_workspace_bytes": (_L, [C.POINTER(Dims)]),
     "vqa_fusion_tensor": (_I, [C.POINTER(Dims), C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -21,11 +21,41 @@ namespace {
 
 constexpr int MAX_R = 1024;
 
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+
+// The pooled memory V is f32, or bf16 at rest (VQA_FLAG_BF16_FEATURES; the _v16 entry points): VT = float or uint16_t (raw
+// bf16 patterns).  A lane that loads four consecutive d as one 16-byte vector loads the same four d of a bf16 memory as 8
+// bytes and widens them with a 16-bit shift, so every sum below keeps its elements and its order: the outputs are
+// bit for bit those of the f32 kernels on the widened values.  Raw: what stays in registers between the load and the use.
+template <typename VT> struct VMem;
+template <> struct VMem<float> {
+    typedef f32x4v Raw;
+    static __device__ __forceinline__ Raw load(const float* __restrict__ p, int64_t i4) { return reinterpret_cast<const f32x4v*>(p)[i4]; }
+    static __device__ __forceinline__ f32x4v widen(Raw r) { return r; }
+    static __device__ __forceinline__ float4 load_f4(const float* __restrict__ p, int64_t i4) { return reinterpret_cast<const float4*>(p)[i4]; }
+};
+template <> struct VMem<uint16_t> {
+    typedef u32x2v Raw;
+    static __device__ __forceinline__ Raw load(const uint16_t* __restrict__ p, int64_t i4) { return reinterpret_cast<const u32x2v*>(p)[i4]; }
+    static __device__ __forceinline__ f32x4v widen(Raw r) {
+        f32x4v x;
+        x.x = __uint_as_float(r.x << 16); x.y = __uint_as_float(r.x & 0xFFFF0000u);
+        x.z = __uint_as_float(r.y << 16); x.w = __uint_as_float(r.y & 0xFFFF0000u);
+        return x;
+    }
+    static __device__ __forceinline__ float4 load_f4(const uint16_t* __restrict__ p, int64_t i4) {
+        const f32x4v x = widen(load(p, i4));
+        return make_float4(x.x, x.y, x.z, x.w);
+    }
+};
+
 // 512 threads: twice the waves (and loads in flight) per sample of the 256-thread form; the kernel is a
 // pure stream over v, the keep mask and V (~480 KB per sample)
 constexpr int FWD_THREADS = 512;
+template <typename VT>
 __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
-    const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
+    const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
     int H, int D, int rep) {
@@ -36,7 +66,7 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
     const int mem = b / rep;
     const float* vb = v + (int64_t)mem * R * H;
     const uint8_t* mb = keepmask ? keepmask + (int64_t)b * R * H : nullptr;
-    const float* Vb = V + (int64_t)mem * R * D;
+    const VT* Vb = V + (int64_t)mem * R * D;
 
     for (int h = threadIdx.x; h < H; h += FWD_THREADS) qw[h] = qv[(int64_t)b * H + h] * w[h];
     __syncthreads();
@@ -91,7 +121,7 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
 #pragma unroll 6
         for (int r = 0; r < R; ++r) {
             const float a = s[r];
-            const float4 x = reinterpret_cast<const float4*>(Vb + (int64_t)r * D)[du];
+            const float4 x = VMem<VT>::load_f4(Vb + (int64_t)r * D, du);
             acc.x += a * x.x; acc.y += a * x.y; acc.z += a * x.z; acc.w += a * x.w;
         }
         reinterpret_cast<float4*>(pooled + (int64_t)b * D)[du] = acc;
@@ -115,7 +145,6 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
 #define VQA_ATTN_POOL_BATCH 7
 #endif
 constexpr int FAST_PF = VQA_ATTN_PF, FAST_POOL_BATCH = VQA_ATTN_POOL_BATCH;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // scores of CNT rows (row0, row0 + 8, ...) of one wave: every load of the batch is issued before the first use
 template <int H4L, int CNT, bool MASK>
@@ -154,9 +183,9 @@ __device__ __forceinline__ void attn_score_rows(const f32x4v* __restrict__ vb4, 
     }
 }
 
-template <int H4L, int D4T, bool MASK>
+template <int H4L, int D4T, bool MASK, typename VT = float>
 __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
-    const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
+    const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
     int rep) {
@@ -168,14 +197,14 @@ __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
     const int mem = b / rep;
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
     const unsigned* mb4 = MASK ? reinterpret_cast<const unsigned*>(keepmask + (int64_t)b * R * H) : nullptr;
-    const f32x4v* Vb4 = reinterpret_cast<const f32x4v*>(V + (int64_t)mem * R * D);
+    const VT* Vb = V + (int64_t)mem * R * D;
 
     // (a) first rows of this thread's V columns
-    f32x4v xv[FAST_PF][D4T];
+    typename VMem<VT>::Raw xv[FAST_PF][D4T];
 #pragma unroll
     for (int j = 0; j < FAST_PF; ++j)
 #pragma unroll
-        for (int c = 0; c < D4T; ++c) xv[j][c] = Vb4[(int64_t)min(j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS];
+        for (int c = 0; c < D4T; ++c) xv[j][c] = VMem<VT>::load(Vb, (int64_t)min(j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
 
     for (int h = threadIdx.x; h < H; h += FWD_THREADS) qw[h] = qv[(int64_t)b * H + h] * w[h];
     const float bias0 = bias[0];
@@ -218,19 +247,20 @@ __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
     for (int j = 0; j < FAST_PF; ++j) {
         const float a = (j < R) ? s[min(j, R - 1)] : 0.f;
 #pragma unroll
-        for (int c = 0; c < D4T; ++c) acc[c] += a * xv[j][c];
+        for (int c = 0; c < D4T; ++c) acc[c] += a * VMem<VT>::widen(xv[j][c]);
     }
     for (int r0 = FAST_PF; r0 < R; r0 += FAST_POOL_BATCH) {
-        f32x4v y[FAST_POOL_BATCH][D4T];
+        typename VMem<VT>::Raw y[FAST_POOL_BATCH][D4T];
 #pragma unroll
         for (int j = 0; j < FAST_POOL_BATCH; ++j)
 #pragma unroll
-            for (int c = 0; c < D4T; ++c) y[j][c] = Vb4[(int64_t)min(r0 + j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS];
+            for (int c = 0; c < D4T; ++c)
+                y[j][c] = VMem<VT>::load(Vb, (int64_t)min(r0 + j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
 #pragma unroll
         for (int j = 0; j < FAST_POOL_BATCH; ++j) {
             const float a = (r0 + j < R) ? s[min(r0 + j, R - 1)] : 0.f;
 #pragma unroll
-            for (int c = 0; c < D4T; ++c) acc[c] += a * y[j][c];
+            for (int c = 0; c < D4T; ++c) acc[c] += a * VMem<VT>::widen(y[j][c]);
         }
     }
 #pragma unroll
@@ -448,10 +478,10 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel
 // phase gives every float4 column of v to TWO threads that take alternate rows (dv rows are
 // independent; the per-query column sums are combined through LDS).
 constexpr int BWD_THREADS = 512;
-template <int REP>
+template <int REP, typename VT = float>
 __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
     const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
-    const float* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
+    const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
     float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, int D, int rep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[D] | ds[REP][R] | comb[REP][H]
@@ -461,7 +491,7 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
     const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int NW = BWD_THREADS / 64;
     const float* vb = v + (int64_t)mem * R * H;
-    const float* Vb = V + (int64_t)mem * R * D;
+    const VT* Vb = V + (int64_t)mem * R * D;
     const int D4 = D / 4;
 
     for (int j = 0; j < rep; ++j) {
@@ -475,7 +505,7 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
             float acc = 0.f;
 #pragma unroll 8
             for (int du = lane; du < D4; du += 64) {
-                const float4 x = reinterpret_cast<const float4*>(Vb + (int64_t)r * D)[du];
+                const float4 x = VMem<VT>::load_f4(Vb + (int64_t)r * D, du);
                 const float4 g = reinterpret_cast<const float4*>(dp)[du];
                 acc += x.x * g.x + x.y * g.y + x.z * g.z + x.w * g.w;
             }
@@ -569,10 +599,10 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
 // the dv phase keeps four rows (+ their REP mask words) per thread in flight.  Same per-lane summation order.
 // DD = 1024 (REP 5 only is dispatched): the adapted memory of the pre-training model; D4 is then half a workgroup, so
 // half of the threads stage dpooled and a wave's V row is 4 float4 per lane instead of 8.
-template <int REP, bool MASK, int DD = 2048>
+template <int REP, bool MASK, int DD = 2048, typename VT = float>
 __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
-    const float* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
+    const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
     float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H) {
     constexpr int D = DD, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64, RB = 4;
@@ -594,15 +624,15 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     }
     __syncthreads();
     // datt[j][r] = <dpooled[q0 + j], V[mem, r]>
-    const f32x4v* Vb4 = reinterpret_cast<const f32x4v*>(V + (int64_t)mem * R * D);
+    const VT* Vb = V + (int64_t)mem * R * D;
     for (int r0 = wave; r0 < R; r0 += 2 * NW) {
         const int rb = min(r0 + NW, R - 1);
         const bool okb = r0 + NW < R;
-        f32x4v xa[DL], xb[DL];
+        typename VMem<VT>::Raw ra[DL], rbw[DL];
 #pragma unroll
         for (int k = 0; k < DL; ++k) {
-            xa[k] = Vb4[(int64_t)r0 * D4 + lane + 64 * k];
-            xb[k] = Vb4[(int64_t)rb * D4 + lane + 64 * k];
+            ra[k] = VMem<VT>::load(Vb, (int64_t)r0 * D4 + lane + 64 * k);
+            rbw[k] = VMem<VT>::load(Vb, (int64_t)rb * D4 + lane + 64 * k);
         }
 #pragma unroll
         for (int j = 0; j < REP; ++j) {
@@ -610,8 +640,9 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
 #pragma unroll
             for (int k = 0; k < DL; ++k) {
                 const f32x4v g = dp4[j * D4 + lane + 64 * k];
-                a += xa[k].x * g.x + xa[k].y * g.y + xa[k].z * g.z + xa[k].w * g.w;
-                b += xb[k].x * g.x + xb[k].y * g.y + xb[k].z * g.z + xb[k].w * g.w;
+                const f32x4v xa = VMem<VT>::widen(ra[k]), xb = VMem<VT>::widen(rbw[k]);
+                a += xa.x * g.x + xa.y * g.y + xa.z * g.z + xa.w * g.w;
+                b += xb.x * g.x + xb.y * g.y + xb.z * g.z + xb.w * g.w;
             }
             a = wave_sum(a);
             b = wave_sum(b);
@@ -706,8 +737,9 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
 // and part_db hold the bits of that kernel.  The score gradient ds [B,R] leaves the CU instead of dv [B,R,H]: dv is
 // ds[b,r] x (keep/keep_prob * qv * w), which the LayerNorm backward of v_linear_v forms in registers
 // (layernorm.hip: ln_att_bwd_reg_kernel), so neither v nor the keep mask is read here.
+template <typename VT>
 __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_ds_kernel(const float* __restrict__ dpooled,
-                                                                       const float* __restrict__ V,
+                                                                       const VT* __restrict__ V,
                                                                        const float* __restrict__ att,
                                                                        float* __restrict__ ds_out,
                                                                        float* __restrict__ part_db, int R) {
@@ -724,22 +756,23 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_ds_kernel(const flo
         dp4[threadIdx.x] = t;
     }
     __syncthreads();
-    const f32x4v* Vb4 = reinterpret_cast<const f32x4v*>(V + (int64_t)mem * R * D);
+    const VT* Vb = V + (int64_t)mem * R * D;
     for (int r0 = wave; r0 < R; r0 += 2 * NW) {
         const int rb = min(r0 + NW, R - 1);
         const bool okb = r0 + NW < R;
-        f32x4v xa[DL], xb[DL];
+        typename VMem<VT>::Raw ra[DL], rbw[DL];
 #pragma unroll
         for (int k = 0; k < DL; ++k) {
-            xa[k] = Vb4[(int64_t)r0 * D4 + lane + 64 * k];
-            xb[k] = Vb4[(int64_t)rb * D4 + lane + 64 * k];
+            ra[k] = VMem<VT>::load(Vb, (int64_t)r0 * D4 + lane + 64 * k);
+            rbw[k] = VMem<VT>::load(Vb, (int64_t)rb * D4 + lane + 64 * k);
         }
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int k = 0; k < DL; ++k) {
             const f32x4v g = dp4[lane + 64 * k];
-            a += xa[k].x * g.x + xa[k].y * g.y + xa[k].z * g.z + xa[k].w * g.w;
-            b += xb[k].x * g.x + xb[k].y * g.y + xb[k].z * g.z + xb[k].w * g.w;
+            const f32x4v xa = VMem<VT>::widen(ra[k]), xb = VMem<VT>::widen(rbw[k]);
+            a += xa.x * g.x + xa.y * g.y + xa.z * g.z + xa.w * g.w;
+            b += xb.x * g.x + xb.y * g.y + xb.z * g.z + xb.w * g.w;
         }
         a = wave_sum(a);
         b = wave_sum(b);
@@ -763,6 +796,21 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_ds_kernel(const flo
 
 int g_attn_fast = 1;   // tuning / A-B switch (vqa_attn_set_fast)
 
+// base address of a pooled memory whose lanes load four consecutive elements at once: 16 bytes of f32, 8 of bf16
+template <typename VT>
+inline bool v_aligned(const VT* V) { return (reinterpret_cast<uintptr_t>(V) & (4 * sizeof(VT) - 1)) == 0; }
+template <typename VT>
+constexpr bool v_is_f32() { return sizeof(VT) == sizeof(float); }
+
+template <typename VT>
+int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
+                 const uint8_t* keepmask, float keep_prob, float* att, float* pooled, int B, int rep, int R, int H, int D,
+                 void* stream);
+template <typename VT>
+int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
+                 const uint8_t* keepmask, float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
+                 int R, int H, int D, void* stream);
+
 }  // namespace
 
 extern "C" int vqa_attn_set_fast(int on) {
@@ -781,12 +829,28 @@ extern "C" int vqa_attn_pool_fwd(const float* v, const float* qv, const float* V
 extern "C" int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const float* V, const int32_t* nb,
                                      const float* w, const float* bias, const uint8_t* keepmask, float keep_prob,
                                      float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
+    return attn_fwd_run<float>(v, qv, V, nb, w, bias, keepmask, keep_prob, att, pooled, B, rep, R, H, D, stream);
+}
+
+// bf16 memory (raw patterns), one query per memory: the kernels vqa_attn_pool_fwd selects for the shape, V loads 8 bytes wide
+extern "C" int vqa_attn_pool_fwd_v16(const float* v, const float* qv, const uint16_t* V, const int32_t* nb, const float* w,
+                                     const float* bias, const uint8_t* keepmask, float keep_prob, float* att,
+                                     float* pooled, int B, int R, int H, int D, void* stream) {
+    return attn_fwd_run<uint16_t>(v, qv, V, nb, w, bias, keepmask, keep_prob, att, pooled, B, 1, R, H, D, stream);
+}
+
+namespace {
+template <typename VT>
+int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
+                 const uint8_t* keepmask, float keep_prob, float* att, float* pooled, int B, int rep, int R, int H, int D,
+                 void* stream) {
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
     VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
+    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);      // several queries per memory: f32 memory only
     VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
-    VQA_REQUIRE(vqa_aligned16(v) && vqa_aligned16(V) && vqa_aligned16(pooled), VQA_ERR_ALIGN);
+    VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(pooled), VQA_ERR_ALIGN);
     VQA_REQUIRE(keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0, VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
     const size_t lds = (size_t)(H + R) * sizeof(float);
@@ -798,17 +862,21 @@ extern "C" int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const floa
     // D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
     const bool fast1024 = g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
                           vqa_aligned16(qv) && vqa_aligned16(w);
-    if (fast1024) {
-        const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
-        if (keepmask != nullptr)
-            hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, true, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
-                               nb, w, bias, keepmask, ik, att, pooled, R);
-        else
-            hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, false, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
-                               nb, w, bias, keepmask, ik, att, pooled, R);
-    } else if (fast && rep == 5 && g_attn_fast != 3) {
-        // one workgroup per memory for the pre-training model's 5 queries per image
-        const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
+    if constexpr (v_is_f32<VT>()) {      // the kernels with several queries per memory (rep == 1 for a bf16 memory, above)
+        if (fast1024) {
+            const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
+            if (keepmask != nullptr)
+                hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, true, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
+                                   nb, w, bias, keepmask, ik, att, pooled, R);
+            else
+                hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, false, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
+                                   nb, w, bias, keepmask, ik, att, pooled, R);
+            VQA_CHECK_LAUNCH();
+            return VQA_OK;
+        }
+        if (fast && rep == 5 && g_attn_fast != 3) {
+            // one workgroup per memory for the pre-training model's 5 queries per image
+            const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
 #define VQA_ATTN_REP5(h4l, d4t)                                                                                        \
     do {                                                                                                                \
         if (keepmask != nullptr)                                                                                        \
@@ -818,23 +886,27 @@ extern "C" int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const floa
             hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<h4l, d4t, false, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, \
                                qv, V, nb, w, bias, keepmask, ik, att, pooled, R);                                       \
     } while (0)
-        const int h4l = H / 256, d4t = D / 2048;
-        if (d4t == 1) {
-            if (h4l == 1) VQA_ATTN_REP5(1, 1); else if (h4l == 2) VQA_ATTN_REP5(2, 1);
-            else if (h4l == 3) VQA_ATTN_REP5(3, 1); else VQA_ATTN_REP5(4, 1);
-        } else {
-            if (h4l == 1) VQA_ATTN_REP5(1, 2); else if (h4l == 2) VQA_ATTN_REP5(2, 2);
-            else if (h4l == 3) VQA_ATTN_REP5(3, 2); else VQA_ATTN_REP5(4, 2);
-        }
+            const int h4l = H / 256, d4t = D / 2048;
+            if (d4t == 1) {
+                if (h4l == 1) VQA_ATTN_REP5(1, 1); else if (h4l == 2) VQA_ATTN_REP5(2, 1);
+                else if (h4l == 3) VQA_ATTN_REP5(3, 1); else VQA_ATTN_REP5(4, 1);
+            } else {
+                if (h4l == 1) VQA_ATTN_REP5(1, 2); else if (h4l == 2) VQA_ATTN_REP5(2, 2);
+                else if (h4l == 3) VQA_ATTN_REP5(3, 2); else VQA_ATTN_REP5(4, 2);
+            }
 #undef VQA_ATTN_REP5
-    } else if (fast) {
+            VQA_CHECK_LAUNCH();
+            return VQA_OK;
+        }
+    }
+    if (fast) {
 #define VQA_ATTN_FAST(h4l, d4t)                                                                                         \
     do {                                                                                                                \
         if (keepmask != nullptr)                                                                                        \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, true>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
+            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, true, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
                                qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep);                                  \
         else                                                                                                            \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, false>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
+            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, false, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
                                qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep);                                  \
     } while (0)
         const int h4l = H / 256, d4t = D / 2048;
@@ -847,12 +919,13 @@ extern "C" int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const floa
         }
 #undef VQA_ATTN_FAST
     } else {
-        hipLaunchKernelGGL(attn_pool_fwd_kernel, dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias,
+        hipLaunchKernelGGL(attn_pool_fwd_kernel<VT>, dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias,
                            keepmask, ik, att, pooled, R, H, D, rep);
     }
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
+}  // namespace
 
 extern "C" int vqa_attn_pool_bwd(const float* dpooled, const float* v, const float* qv, const float* V,
                                  const float* att, const float* w, const uint8_t* keepmask, float keep_prob, float* dv,
@@ -865,12 +938,29 @@ extern "C" int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const
                                      const float* att, const float* w, const uint8_t* keepmask, float keep_prob,
                                      float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R,
                                      int H, int D, void* stream) {
+    return attn_bwd_run<float>(dpooled, v, qv, V, att, w, keepmask, keep_prob, dv, dqv, part_dw, part_db, B, rep, R, H, D,
+                               stream);
+}
+
+extern "C" int vqa_attn_pool_bwd_v16(const float* dpooled, const float* v, const float* qv, const uint16_t* V,
+                                     const float* att, const float* w, const uint8_t* keepmask, float keep_prob, float* dv,
+                                     float* dqv, float* part_dw, float* part_db, int B, int R, int H, int D, void* stream) {
+    return attn_bwd_run<uint16_t>(dpooled, v, qv, V, att, w, keepmask, keep_prob, dv, dqv, part_dw, part_db, B, 1, R, H, D,
+                                  stream);
+}
+
+namespace {
+template <typename VT>
+int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
+                 const uint8_t* keepmask, float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
+                 int R, int H, int D, void* stream) {
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
     VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
+    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);      // several queries per memory: f32 memory only
     VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
-    VQA_REQUIRE(vqa_aligned16(v) && vqa_aligned16(V) && vqa_aligned16(dv) && vqa_aligned16(dqv) &&
+    VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(dv) && vqa_aligned16(dqv) &&
                     vqa_aligned16(part_dw) && vqa_aligned16(qv) && vqa_aligned16(w),
                 VQA_ERR_ALIGN);
     VQA_REQUIRE(keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0, VQA_ERR_ALIGN);
@@ -882,29 +972,33 @@ extern "C" int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const
     if (g_attn_fast && (rep == 1 || rep == 5) && D == 2048 && H == 1024 && R <= 40 && vqa_aligned16(dpooled)) {
         const size_t l = (size_t)(rep * D + rep * 40 + rep * H) * sizeof(float);
 #define VQA_ATTN_BWD_FAST(r, mk)                                                                                       \
-    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<r, mk>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, \
+    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<r, mk, 2048, VT>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, \
                        keepmask, ik, dv, dqv, part_dw, part_db, R, H)
         if (rep == 1) { if (keepmask) VQA_ATTN_BWD_FAST(1, true); else VQA_ATTN_BWD_FAST(1, false); }
-        else { if (keepmask) VQA_ATTN_BWD_FAST(5, true); else VQA_ATTN_BWD_FAST(5, false); }
+        else if constexpr (v_is_f32<VT>()) { if (keepmask) VQA_ATTN_BWD_FAST(5, true); else VQA_ATTN_BWD_FAST(5, false); }
 #undef VQA_ATTN_BWD_FAST
         VQA_CHECK_LAUNCH();
         return VQA_OK;
     }
-    if (g_attn_fast && rep == 5 && D == 1024 && H == 1024 && R <= 40 && vqa_aligned16(dpooled)) {
-        // the 1024-wide memory at 5 queries per memory; rep 1 at D 1024 stays on the generic kernel below
-        const size_t l = (size_t)(5 * D + 5 * 40 + 5 * H) * sizeof(float);
-        if (keepmask)
-            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, true, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
-                               V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
-        else
-            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, false, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
-                               V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
-        VQA_CHECK_LAUNCH();
-        return VQA_OK;
+    if constexpr (v_is_f32<VT>()) {
+        if (g_attn_fast && rep == 5 && D == 1024 && H == 1024 && R <= 40 && vqa_aligned16(dpooled)) {
+            // the 1024-wide memory at 5 queries per memory; rep 1 at D 1024 stays on the generic kernel below
+            const size_t l = (size_t)(5 * D + 5 * 40 + 5 * H) * sizeof(float);
+            if (keepmask)
+                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, true, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
+                                   V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
+            else
+                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, false, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
+                                   V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
+            VQA_CHECK_LAUNCH();
+            return VQA_OK;
+        }
     }
     if (rep == 1)
-        hipLaunchKernelGGL(attn_pool_bwd_kernel<1>, dim3(B), dim3(BWD_THREADS), lds_for(1), st, dpooled, v, qv, V, att, w,
+        hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT>), dim3(B), dim3(BWD_THREADS), lds_for(1), st, dpooled, v, qv, V, att, w,
                            keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
+    else if constexpr (!v_is_f32<VT>())
+        return VQA_ERR_UNSUPPORTED;
     else if (rep <= 5)
         hipLaunchKernelGGL(attn_pool_bwd_kernel<5>, dim3(B), dim3(BWD_THREADS), lds_for(5), st, dpooled, v, qv, V, att, w,
                            keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
@@ -914,6 +1008,7 @@ extern "C" int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
+}  // namespace
 
 // The chain v_linear_v's LayerNorm -> attention score and its gradient at the one shape of the register-resident
 // LayerNorm kernels and the fast attention kernels: one query per memory, 36 regions, 1024 hidden units, 2048 features.
@@ -927,8 +1022,20 @@ extern "C" int vqa_attn_pool_bwd_ds(const float* dpooled, const float* V, const 
     VQA_REQUIRE(vqa_vtail_supported(rep, R, H, D), VQA_ERR_UNSUPPORTED);
     VQA_REQUIRE(vqa_aligned16(dpooled) && vqa_aligned16(V), VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
-    hipLaunchKernelGGL(attn_pool_bwd_ds_kernel, dim3(B), dim3(BWD_THREADS), 0, (hipStream_t)stream, dpooled, V, att, ds,
+    hipLaunchKernelGGL(attn_pool_bwd_ds_kernel<float>, dim3(B), dim3(BWD_THREADS), 0, (hipStream_t)stream, dpooled, V, att, ds,
                        part_db, R);
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+extern "C" int vqa_attn_pool_bwd_ds_v16(const float* dpooled, const uint16_t* V, const float* att, float* ds, float* part_db,
+                                        int B, int rep, int R, int H, int D, void* stream) {
+    VQA_REQUIRE(dpooled && V && att && ds && part_db && B >= 0, VQA_ERR_ARG);
+    VQA_REQUIRE(vqa_vtail_supported(rep, R, H, D), VQA_ERR_UNSUPPORTED);
+    VQA_REQUIRE(vqa_aligned16(dpooled) && v_aligned(V), VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    hipLaunchKernelGGL(attn_pool_bwd_ds_kernel<uint16_t>, dim3(B), dim3(BWD_THREADS), 0, (hipStream_t)stream, dpooled, V, att,
+                       ds, part_db, R);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }

@@ -43,13 +43,14 @@ struct Layout {
 inline bool has_tuned_head(int mt) { return mt == VQA_MODEL_VQA_ALL2 || mt == VQA_MODEL_VQA_ALL; }      // a second, trainable head on `joint`
 inline bool train_loss_masked(int mt) { return mt != VQA_MODEL_STANDARD; }      // train loss masked by the train-answer mask
 inline bool bf16_routed(int mt) { return mt == VQA_MODEL_VLMAP_ANSWER || mt == VQA_MODEL_STANDARD; }      // every dense product on VQA_FLAG_BF16_GEMM's routed list
+inline bool feat16(const vqa_dims_t& d) { return (d.flags & VQA_FLAG_BF16_FEATURES) != 0; }      // table and V_ft are bf16 patterns
 
 void legacy_vqa_layout(Layout& L, const vqa_dims_t& d, int64_t& gw);      // csrc/legacy_vqa.inc (model_type 13)
 
 Layout make_layout(const vqa_dims_t& d) {
     Layout L;
     const int64_t B = d.B, R = d.R, D = d.D, H = d.H, T = d.T, W = d.W, A = d.A;
-    L.add("V_ft", B * R * D);
+    L.add("V_ft", B * R * D, feat16(d) ? 2 : 4);
     L.add("num_V_ft", B);
     L.add("pre_v", B * R * H);
     L.add("v_linear_v", B * R * H);
@@ -198,6 +199,7 @@ struct Ctx {
     int lane;   // 0 = caller's stream, 1 = side stream (own scratch so the two never share a buffer)
     float* f(const char* name) const { return reinterpret_cast<float*>(ws + L.find(name)->off); }
     int32_t* i32(const char* name) const { return reinterpret_cast<int32_t*>(ws + L.find(name)->off); }
+    uint16_t* u16(const char* name) const { return reinterpret_cast<uint16_t*>(ws + L.find(name)->off); }
     float* gemm_ws() const { return f(lane ? "gemm_ws1" : "gemm_ws"); }
     float* colsum_ws() const { return f(lane ? "colsum_ws1" : "colsum_ws"); }
     float* part(int i) const {
@@ -410,6 +412,16 @@ int gemm(const Ctx& c, int tA, int tB, int64_t M, int64_t N, int64_t K, const fl
                              c.gemm_ws_floats(), c.lane ? side_max_blocks() : 0, c.st);
     return gemm_f32(c, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd);
 }
+// A dense layer's product whose LEFT operand is the layer's input x (forward, dW).  Under VQA_FLAG_BF16_FEATURES the
+// workspace's V_ft holds bf16 patterns, and the two products that read it (v_linear_v's forward and dW) take the GEMM whose
+// left operand is bf16 in HBM; every other x is f32.
+int gemm_x(const Ctx& c, int tA, int64_t M, int64_t N, int64_t K, const float* x, int ldx, const float* B, int ldb, float* C,
+           int ldc, const float* bias = nullptr) {
+    if (feat16(c.d) && x == c.f("V_ft"))
+        return vqa_gemm_bf16_a16(tA, 0, (int)M, (int)N, (int)K, c.u16("V_ft"), ldx, B, ldb, C, ldc, bias, nullptr, 0, 0,
+                                 c.gemm_ws(), c.gemm_ws_floats(), c.lane ? side_max_blocks() : 0, c.st);
+    return gemm(c, tA, 0, M, N, K, x, ldx, B, ldb, C, ldc, bias);
+}
 int colsum(const Ctx& c, const float* X, int64_t M, int64_t N, int ldx, float* out) {
     return vqa_colsum(X, (int)M, (int)N, ldx, out, c.colsum_ws(), c.colsum_ws_floats(), c.st);
 }
@@ -420,6 +432,8 @@ bool dims_ok(const vqa_dims_t* d) {
         return false;
     // bf16 mode: the two model types whose every dense product is on the routed list, and no gather-fused GEMM
     if ((d->flags & VQA_FLAG_BF16_GEMM) && (!bf16_routed(d->model_type) || (d->flags & VQA_FLAG_FUSED_GATHER))) return false;
+    // a bf16 table: only inside the bf16 mode (which brings the two conditions above with it)
+    if ((d->flags & VQA_FLAG_BF16_FEATURES) && !(d->flags & VQA_FLAG_BF16_GEMM)) return false;
     if (d->model_type == VQA_MODEL_LEGACY_VQA)      // 16-byte rows everywhere; the scoring kernel keeps one H-row in LDS
         return d->map_dim > 0 && d->La > 0 && d->H % 4 == 0 && d->D % 4 == 0 && d->map_dim % 4 == 0 && d->W % 4 == 0 && d->H <= 1024 && d->Vq > 3;
     if (d->model_type == VQA_MODEL_BI) return d->H % 8 == 0;      // two cells of H / 2 units, 16-byte rows each
@@ -437,7 +451,7 @@ int fc_ln_relu_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N
                    float keep_prob) {
     {
         ProbeScope ps(rows > 1 ? "v_linear_v.fwd_gemm" : "fc.fwd_gemm", c.st);
-        TRY(gemm(c, 0, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
+        TRY(gemm_x(c, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
     }
     ProbeScope ps(rows > 1 ? "v_linear_v.ln_fwd" : "fc.ln_fwd", c.st);
     return vqa_ln_relu_fwd(c.f(pre), p.gamma, p.beta, keep, keep_prob, c.f(y), c.f(mean), c.f(rstd), (int)(M / rows),
@@ -456,7 +470,7 @@ int fc_bwd_tail(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, c
             TRY(vqa_colsum3(pa, pb, pc, (int)G, (int)N, (int)N, g->gamma, g->beta, g->b, c.colsum_ws(), c.colsum_ws_floats(), c.st));
         }
         ProbeScope ps(rows > 1 ? "v_linear_v.dw_gemm" : "fc.dw_gemm", c.st);
-        TRY(gemm(c, 1, 0, K, N, M, x, (int)K, d_pre, (int)N, g->w, (int)N));  // dW = x^T * d_pre
+        TRY(gemm_x(c, 1, K, N, M, x, (int)K, d_pre, (int)N, g->w, (int)N));  // dW = x^T * d_pre
     }
     if (dx != nullptr) {
         ProbeScope ps("fc.dx_gemm", c.st);
@@ -780,8 +794,12 @@ int fwd_visual(const Step& s) {
     // a1: V_ft = features[image_idx] (a pass of its own, or inside the GEMM below), num_V_ft = num_boxes[image_idx]
     {
         ProbeScope ps("gather", cv.st);
-        TRY(vqa_gather_features(bt->table, bt->nbox_table, bt->image_idx, s.fuse_gather ? nullptr : cv.f("V_ft"),
-                                cv.i32("num_V_ft"), (int)B, (int)R, (int)D, s.d.N_img, cv.st));
+        if (feat16(s.d))      // (never fused: dims_ok)
+            TRY(vqa_gather_features_bf16(reinterpret_cast<const uint16_t*>(bt->table), bt->nbox_table, bt->image_idx,
+                                         cv.u16("V_ft"), cv.i32("num_V_ft"), (int)B, (int)R, (int)D, s.d.N_img, cv.st));
+        else
+            TRY(vqa_gather_features(bt->table, bt->nbox_table, bt->image_idx, s.fuse_gather ? nullptr : cv.f("V_ft"),
+                                    cv.i32("num_V_ft"), (int)B, (int)R, (int)D, s.d.N_img, cv.st));
     }
     // a2: v_linear_v, LN statistics over the whole [R,H] block of a sample
     if (s.fuse_gather) {
@@ -908,6 +926,10 @@ int fwd_q_linear_v(const Step& s) {
 int fwd_attention(const Step& s) {
     const Ctx& c = s.c;
     ProbeScope ps("attn_pool.fwd", c.st);
+    if (feat16(s.d))
+        return vqa_attn_pool_fwd_v16(c.f("v_linear_v"), c.f("q_linear_v"), c.u16("V_ft"), c.i32("num_V_ft"), s.P->score.w,
+                                     s.P->score.b, s.bt->keep_att, s.d.keep_att, c.f("att_score"), c.f("pooled_V_ft"),
+                                     (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
     return vqa_attn_pool_fwd(c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
                              c.i32("num_V_ft"), s.P->score.w, s.P->score.b, s.bt->keep_att, s.d.keep_att, c.f("att_score"),
                              c.f("pooled_V_ft"), (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
@@ -1267,8 +1289,12 @@ int bwd_attention(Step& s) {
     if (vtail_ok(s, *s.sd)) {
         {
             ProbeScope ps("attn_pool.bwd", c.st);
-            TRY(vqa_attn_pool_bwd_ds(c.f("d_pooled"), c.f("V_ft"), c.f("att_score"), c.f("ds"), c.f("part_db"), (int)B, 1, (int)R,
-                                     (int)H, (int)D, c.st));
+            if (feat16(s.d))
+                TRY(vqa_attn_pool_bwd_ds_v16(c.f("d_pooled"), c.u16("V_ft"), c.f("att_score"), c.f("ds"), c.f("part_db"), (int)B,
+                                             1, (int)R, (int)H, (int)D, c.st));
+            else
+                TRY(vqa_attn_pool_bwd_ds(c.f("d_pooled"), c.f("V_ft"), c.f("att_score"), c.f("ds"), c.f("part_db"), (int)B, 1,
+                                         (int)R, (int)H, (int)D, c.st));
         }
         {
             ProbeScope ps("v_linear_v.ln_bwd", c.st);
@@ -1280,13 +1306,18 @@ int bwd_attention(Step& s) {
                                  c.colsum_ws_floats(), c.st));
         }
         ProbeScope ps("v_linear_v.dw_gemm", c.st);
-        return gemm(c, 1, 0, D, H, B * R, c.f("V_ft"), (int)D, c.f("d_pre_v"), (int)H, G->v_linear_v.w, (int)H);  // dW = x^T * d_pre
+        return gemm_x(c, 1, D, H, B * R, c.f("V_ft"), (int)D, c.f("d_pre_v"), (int)H, G->v_linear_v.w, (int)H);  // dW = x^T * d_pre
     }
     {
         ProbeScope ps("attn_pool.bwd", c.st);
-        TRY(vqa_attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
-                              c.f("att_score"), P->score.w, bt->keep_att, s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
-                              c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
+        if (feat16(s.d))
+            TRY(vqa_attn_pool_bwd_v16(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.u16("V_ft"), c.f("att_score"),
+                                      P->score.w, bt->keep_att, s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
+                                      c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
+        else
+            TRY(vqa_attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
+                                  c.f("att_score"), P->score.w, bt->keep_att, s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
+                                  c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
     }
     if (s.mt == VQA_MODEL_ADAPT) {
         // the pooled memory is trainable here: d v_adapt = att (x) d pooled, then LN[R,H] + ReLU + FC backward (V_ft is an

@@ -18,6 +18,10 @@
 // Split k cuts K into ranges (multiples of 32) whose partial products go to dense M x N slabs of the workspace and are
 // summed in range order by a second kernel (bias rides in slab 0, D is added last): same inputs, same bits.
 // max_blocks > 0: at most that many workgroups walk the (range, tile) units persistently.
+//
+// vqa_gemm_bf16_a16 (VQA_FLAG_BF16_FEATURES): the same kernel with a left operand that is bf16 in HBM already (the
+// region-feature table at rest).  A thread fetches the same four elements as 8 bytes instead of 16 and stores them to LDS
+// unconverted, so LDS -- and with it every bit of C -- is that of vqa_gemm_bf16 on the widened operand.
 #include <algorithm>
 
 #include "vqa_common.h"
@@ -28,6 +32,12 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4n __attribute__((ext_vector_type(4)));
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+
+// what a thread holds of an operand between its fetch and its LDS store: four consecutive elements as they are in HBM
+template <typename T> struct Quad;
+template <> struct Quad<float> { typedef f32x4n type; };
+template <> struct Quad<uint16_t> { typedef u16x4 type; };      // raw bf16 patterns
 
 constexpr int BM = 128, BN = 128, BK = 32, NT = 256;
 constexpr int RS = 40;                       // bf16 per LDS row: 32 k + 8 pad = 80 bytes
@@ -44,16 +54,29 @@ __device__ __forceinline__ f32x4n load4(const float* __restrict__ p, int valid, 
     if (valid > 3) v[3] = p[3];
     return v;
 }
+// the same for bf16 elements; vec: p is 8-byte aligned
+__device__ __forceinline__ u16x4 load4(const uint16_t* __restrict__ p, int valid, bool vec) {
+    u16x4 v = {0, 0, 0, 0};
+    if (valid >= 4 && vec) return *reinterpret_cast<const u16x4*>(p);
+    if (valid > 0) v[0] = p[0];
+    if (valid > 1) v[1] = p[1];
+    if (valid > 2) v[2] = p[2];
+    if (valid > 3) v[3] = p[3];
+    return v;
+}
 __device__ __forceinline__ int clamp4(int n) { return n < 0 ? 0 : (n > 4 ? 4 : n); }
+// an element on its way into LDS: f32 is rounded to bf16 (nearest even), a bf16 pattern goes through as it is
+__device__ __forceinline__ __bf16 to_lds(float x) { return (__bf16)x; }
+__device__ __forceinline__ __bf16 to_lds(uint16_t x) { return __builtin_bit_cast(__bf16, x); }
 
 // One operand tile of 128 (rows: m of A, n of B) x 32 (k) in two storage forms:
 //   KM = false: stored [row][k] (k contiguous).  Thread -> (row = idx / 8, 4 consecutive k), idx = tid + i * 256.
 //   KM = true : stored [k][row] (row contiguous).  Thread -> a 4 (k) x 4 (row) block, transposed in registers.
 // P points at the matrix, r0 / rows: the tile's first row and the matrix' row count, k0 / kend: this k tile and the end of
 // the k range.
-template <bool KM>
-__device__ __forceinline__ void fetch_tile(f32x4n (&r)[4], const float* __restrict__ P, int64_t ld, int r0, int rows, int k0,
-                                           int kend, bool vec, int tid) {
+template <bool KM, typename T>
+__device__ __forceinline__ void fetch_tile(typename Quad<T>::type (&r)[4], const T* __restrict__ P, int64_t ld, int r0, int rows,
+                                           int k0, int kend, bool vec, int tid) {
     if (KM) {
         const int bk4 = (tid % 8) * 4, br4 = (tid / 8) * 4;
         const int valid = clamp4(rows - (r0 + br4));
@@ -71,15 +94,15 @@ __device__ __forceinline__ void fetch_tile(f32x4n (&r)[4], const float* __restri
         }
     }
 }
-template <bool KM>
-__device__ __forceinline__ void stage_tile(__bf16* __restrict__ s, const f32x4n (&r)[4], int tid) {
+template <bool KM, typename Q>
+__device__ __forceinline__ void stage_tile(__bf16* __restrict__ s, const Q (&r)[4], int tid) {
     if (KM) {
         const int bk4 = (tid % 8) * 4, br4 = (tid / 8) * 4;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                 // row br4 + j of the tile: its four consecutive k
             bf16x4 h;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) h[i] = (__bf16)r[i][j];
+            for (int i = 0; i < 4; ++i) h[i] = to_lds(r[i][j]);
             *reinterpret_cast<bf16x4*>(s + (br4 + j) * RS + bk4) = h;
         }
     } else {
@@ -88,16 +111,17 @@ __device__ __forceinline__ void stage_tile(__bf16* __restrict__ s, const f32x4n 
             const int idx = tid + i * NT;
             bf16x4 h;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = (__bf16)r[i][j];
+            for (int j = 0; j < 4; ++j) h[j] = to_lds(r[i][j]);
             *reinterpret_cast<bf16x4*>(s + (idx / 8) * RS + (idx % 8) * 4) = h;
         }
     }
 }
 
 // A_KM: A stored [K][M] (transA); B_KM: B stored [K][N] (no transB).  Unit u = z * tiles + tile: k range z of the tile;
-// with split k (slab > 0) C is the workspace, ldc = N, and slab z receives the partial product.
-template <bool A_KM, bool B_KM>
-__global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B,
+// with split k (slab > 0) C is the workspace, ldc = N, and slab z receives the partial product.  AT: element type of A in
+// HBM (float, or uint16_t = bf16 patterns).
+template <bool A_KM, bool B_KM, typename AT>
+__global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const AT* __restrict__ A, int lda, const float* __restrict__ B,
                                                           int ldb, float* Cbase, int ldc,
                                                           const float* __restrict__ bias0, const float* D0,
                                                           int ldd, int M, int N, int K, int tiles_n, int tiles, int units,
@@ -115,7 +139,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const float* __restric
         const float* bias = z > 0 ? nullptr : bias0;
         const float* D = z > 0 ? nullptr : D0;
 
-        f32x4n ra[4], rb[4];
+        typename Quad<AT>::type ra[4];
+        f32x4n rb[4];
         auto fetch = [&](int k0) {
             fetch_tile<A_KM>(ra, A, lda, m0, M, k0, kend, vecA != 0, tid);
             fetch_tile<B_KM>(rb, B, ldb, n0, N, k0, kend, vecB != 0, tid);
@@ -220,15 +245,16 @@ void plan_split(int M, int N, int K, int split_k, int* split, int* kps) {
     *split = (K + per - 1) / per;
 }
 
-template <bool A_KM, bool B_KM>
-int launch(const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* D, int ldd, int M,
+template <bool A_KM, bool B_KM, typename AT>
+int launch(const AT* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* D, int ldd, int M,
            int N, int K, int split, int kps, int64_t slab, int max_blocks, hipStream_t st) {
     const int tiles_n = (N + BN - 1) / BN;
     const int64_t tiles = (int64_t)((M + BM - 1) / BM) * tiles_n, units = tiles * split;
     if (units > 0x7fffffff) return VQA_ERR_ARG;
-    const int vecA = (lda % 4 == 0 && vqa_aligned16(A)) ? 1 : 0, vecB = (ldb % 4 == 0 && vqa_aligned16(B)) ? 1 : 0;
+    // four elements in one load: 16 bytes of f32, 8 bytes of bf16
+    const int vecA = (lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & (4 * sizeof(AT) - 1)) == 0) ? 1 : 0, vecB = (ldb % 4 == 0 && vqa_aligned16(B)) ? 1 : 0;
     const int grid = max_blocks > 0 ? (int)std::min<int64_t>(units, max_blocks) : (int)units;
-    hipLaunchKernelGGL((gemm_bf16_kernel<A_KM, B_KM>), dim3((unsigned)grid), dim3(NT), 0, st, A, lda, B, ldb, C, ldc, bias, D, ldd,
+    hipLaunchKernelGGL((gemm_bf16_kernel<A_KM, B_KM, AT>), dim3((unsigned)grid), dim3(NT), 0, st, A, lda, B, ldb, C, ldc, bias, D, ldd,
                        M, N, K, tiles_n, (int)tiles, (int)units, kps, slab, vecA, vecB);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
@@ -245,9 +271,11 @@ extern "C" int64_t vqa_gemm_bf16_workspace_floats(int M, int N, int K, int split
     return split > 1 ? (int64_t)split * M * N : 0;
 }
 
-extern "C" int vqa_gemm_bf16(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
-                             float* C, int ldc, const float* bias, const float* D, int ldd, int split_k, float* workspace,
-                             int64_t workspace_floats, int max_blocks, void* stream) {
+namespace {
+template <typename AT>
+int gemm_bf16_run(int transA, int transB, int M, int N, int K, const AT* A, int lda, const float* B, int ldb, float* C, int ldc,
+                  const float* bias, const float* D, int ldd, int split_k, float* workspace, int64_t workspace_floats,
+                  int max_blocks, void* stream) {
     VQA_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, VQA_ERR_ARG);
     VQA_REQUIRE(!(transA && transB), VQA_ERR_UNSUPPORTED);
     VQA_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N && (D == nullptr || ldd >= N), VQA_ERR_ARG);
@@ -266,11 +294,11 @@ extern "C" int vqa_gemm_bf16(int transA, int transB, int M, int N, int K, const 
     const float* Dk = split > 1 ? nullptr : D;                // with slabs D joins in the reduction
     int rc;
     if (transA)
-        rc = launch<true, true>(A, lda, B, ldb, out, ldo, bias, Dk, ldd, M, N, K, split, kps, slab, max_blocks, st);
+        rc = launch<true, true, AT>(A, lda, B, ldb, out, ldo, bias, Dk, ldd, M, N, K, split, kps, slab, max_blocks, st);
     else if (transB)
-        rc = launch<false, false>(A, lda, B, ldb, out, ldo, bias, Dk, ldd, M, N, K, split, kps, slab, max_blocks, st);
+        rc = launch<false, false, AT>(A, lda, B, ldb, out, ldo, bias, Dk, ldd, M, N, K, split, kps, slab, max_blocks, st);
     else
-        rc = launch<false, true>(A, lda, B, ldb, out, ldo, bias, Dk, ldd, M, N, K, split, kps, slab, max_blocks, st);
+        rc = launch<false, true, AT>(A, lda, B, ldb, out, ldo, bias, Dk, ldd, M, N, K, split, kps, slab, max_blocks, st);
     if (rc != VQA_OK || split <= 1) return rc;
     const int64_t n = (int64_t)M * N;
     int grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
@@ -278,4 +306,20 @@ extern "C" int vqa_gemm_bf16(int transA, int transB, int M, int N, int K, const 
     hipLaunchKernelGGL(gemm_bf16_reduce_kernel, dim3(grid), dim3(256), 0, st, workspace, C, ldc, D, ldd, M, N, split);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
+}
+}  // namespace
+
+extern "C" int vqa_gemm_bf16(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                             float* C, int ldc, const float* bias, const float* D, int ldd, int split_k, float* workspace,
+                             int64_t workspace_floats, int max_blocks, void* stream) {
+    return gemm_bf16_run<float>(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd, split_k, workspace,
+                                workspace_floats, max_blocks, stream);
+}
+
+// A: bf16 patterns in HBM, lda in elements; everything else as vqa_gemm_bf16 (workspace: vqa_gemm_bf16_workspace_floats)
+extern "C" int vqa_gemm_bf16_a16(int transA, int transB, int M, int N, int K, const uint16_t* A, int lda, const float* B,
+                                 int ldb, float* C, int ldc, const float* bias, const float* D, int ldd, int split_k,
+                                 float* workspace, int64_t workspace_floats, int max_blocks, void* stream) {
+    return gemm_bf16_run<uint16_t>(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd, split_k, workspace,
+                                   workspace_floats, max_blocks, stream);
 }

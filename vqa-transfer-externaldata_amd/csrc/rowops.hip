@@ -34,6 +34,25 @@ __global__ __launch_bounds__(256) void gather_features_kernel(const float* __res
         for (int64_t i = n4 * 4 + threadIdx.x; i < row_floats; i += 256) d[i] = s[i];
 }
 
+// The same for a table that is bf16 at rest (VQA_FLAG_BF16_FEATURES): rows of raw 16-bit patterns, copied as VT words
+// (uint4 where rows and bases are 16-byte aligned, else uint2).
+template <typename VT>
+__global__ __launch_bounds__(256) void gather_features_bf16_kernel(const uint16_t* __restrict__ table,
+                                                                   const int32_t* __restrict__ nbox_table,
+                                                                   const int64_t* __restrict__ idx, uint16_t* __restrict__ V,
+                                                                   int32_t* __restrict__ nb, int B, int64_t row_elems,
+                                                                   int64_t N) {
+    const int b = blockIdx.x;
+    int64_t src = idx[b];
+    if (src < 0) src = 0;
+    if (src >= N) src = N - 1;  // the clamp of gather_features_kernel
+    if (blockIdx.y == 0 && threadIdx.x == 0 && nb != nullptr) nb[b] = nbox_table[src];
+    const VT* s = reinterpret_cast<const VT*>(table + src * row_elems);
+    VT* d = reinterpret_cast<VT*>(V + (int64_t)b * row_elems);
+    const int64_t nv = row_elems * 2 / (int64_t)sizeof(VT);      // the host chose VT so that this is exact
+    for (int64_t i = blockIdx.y * 256 + threadIdx.x; i < nv; i += (int64_t)gridDim.y * 256) d[i] = s[i];
+}
+
 // ------------------------------------------------------------------ a3
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const float* __restrict__ E, const int32_t* __restrict__ q,
                                                         float* __restrict__ x, int B, int T, int W, int Vq, int ldx) {
@@ -494,6 +513,27 @@ extern "C" int vqa_gather_features(const float* table, const int32_t* nbox_table
     const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(row / 4, 256 * 4), 16));
     hipLaunchKernelGGL(gather_features_kernel, dim3(B, chunks), dim3(256), 0, (hipStream_t)stream, table, nbox_table,
                        idx, V, nb, B, row, N);
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
+extern "C" int vqa_gather_features_bf16(const uint16_t* table, const int32_t* nbox_table, const int64_t* idx, uint16_t* V,
+                                        int32_t* nb, int B, int R, int D, int64_t N, void* stream) {
+    VQA_REQUIRE(table && idx && (V || nb) && B >= 0 && R > 0 && D > 0 && N > 0, VQA_ERR_ARG);
+    VQA_REQUIRE(nb == nullptr || nbox_table != nullptr, VQA_ERR_ARG);
+    const auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    VQA_REQUIRE(al(table, 8) && al(V, 8) && ((int64_t)R * D) % 4 == 0, VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    const int64_t row = V != nullptr ? (int64_t)R * D : 0;      // V == NULL: num_boxes only
+    const bool wide = row % 8 == 0 && al(table, 16) && al(V, 16);
+    const int64_t nv = wide ? row / 8 : row / 4;
+    const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(nv, 256 * 4), 16));
+    if (wide)
+        hipLaunchKernelGGL(gather_features_bf16_kernel<uint4>, dim3(B, chunks), dim3(256), 0, (hipStream_t)stream, table,
+                           nbox_table, idx, V, nb, B, row, N);
+    else
+        hipLaunchKernelGGL(gather_features_bf16_kernel<uint2>, dim3(B, chunks), dim3(256), 0, (hipStream_t)stream, table,
+                           nbox_table, idx, V, nb, B, row, N);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }

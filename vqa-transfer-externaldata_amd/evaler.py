@@ -199,6 +199,8 @@ _FLAGS = (("--image_dir", dict(type=str, default="data/VQA_v2/images")),
           ("--batch_size", dict(type=int, default=512)),
           ("--precision", dict(type=str, default="f32", choices=["f32", "bf16"],
                                help="bf16: the dense layers' products with bf16 operands in the matrix unit (not in the reference)")),
+          ("--features", dict(type=str, default="f32", choices=["f32", "bf16"],
+                              help="bf16 (only with --precision bf16): the region-feature table lives in HBM as bf16")),
           ("--debug", dict(type=int, default=0, help="0: normal, 1: debug")),
           ("--dump_heavy_output", dict(action="store_true", default=False)))
 

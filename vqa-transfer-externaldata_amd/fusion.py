@@ -66,6 +66,7 @@ LATENT_LOSS_WEIGHT = 0.1      # vqa/model_vlmap_answer_full.py:33
 
 PRECISIONS = ("f32", "bf16")
 BF16_MODEL_TYPES = ("vlmap_answer", "standard")       # include/vqa_hot.h, VQA_FLAG_BF16_GEMM
+FEATURE_FORMATS = ("f32", "bf16")                     # FusionEngine(features=...): the feature table at rest
 
 
 def scope_names(model_type):
@@ -257,8 +258,14 @@ class FusionEngine:
     def __init__(self, *, model_type, B, R, D, H, T, W, A, Vq, N_img, params, device="cuda:0",
                  keep_att=0.8, keep_joint=0.5, global_batch=None, deterministic=None, answer_glove=None,
                  fused_gather=False, num_marginal=NUM_MARGINAL, ent_cols=None, map_dim=None, ft_vlmap=False,
-                 glove_fixed=None, answers=None, precision="f32"):
-        """precision="bf16": opt-in mixed precision -- the dense layers' products (forward, dW, dx of v_linear_v,
+                 glove_fixed=None, answers=None, precision="f32", features="f32"):
+        """features="bf16" (opt-in, only with precision="bf16"): the region-feature table is bf16 at rest -- bind_inputs
+        takes a torch.bfloat16 table [N,R,D] (model_vlmap_answer.features_to_bf16 makes one), the gathered V_ft is bf16 in
+        the workspace, and v_linear_v's forward and dW GEMMs and the attention kernels read it as it is
+        (VQA_FLAG_BF16_FEATURES).  Half the resident feature memory and half the traffic of the step's largest stream; the
+        step equals, bit for bit, the precision="bf16" step on the same table widened to f32.  pooled_V_ft and everything
+        downstream stay f32.  Model types vlmap_answer and standard, not together with fused_gather.
+        precision="bf16": opt-in mixed precision -- the dense layers' products (forward, dW, dx of v_linear_v,
         q_linear_v, pooled_linear_l, q_linear_l, joint_fc and the answer head) round both operands to bf16 on their way
         into the matrix unit (vqa_gemm_bf16); parameters, Adam slots, activations, gradients and accumulation stay f32,
         the question encoder and everything that is not a GEMM stay f32, so checkpoints and data parallelism are those
@@ -283,7 +290,13 @@ class FusionEngine:
             raise ValueError("precision='bf16' covers the model types %s, not %r" % (BF16_MODEL_TYPES, model_type))
         if precision == "bf16" and fused_gather:
             raise ValueError("precision='bf16' cannot be combined with fused_gather (the gather-fused GEMM has no bf16 form)")
+        if features not in FEATURE_FORMATS:
+            raise ValueError("features must be one of %s, not %r" % (FEATURE_FORMATS, features))
+        if features == "bf16" and precision != "bf16":
+            raise ValueError("features='bf16' needs precision='bf16' (the f32 products read an f32 table)")
+        # (features='bf16' with fused_gather or another model type: refused above, as precision='bf16' is)
         self.precision = precision
+        self.features = features
         self.device = torch.device(device)
         self.model_type = model_type
         self.sc = scope_names(model_type)
@@ -293,7 +306,8 @@ class FusionEngine:
                               inv_global_batch=1.0 / float(global_batch or B),
                               flags=(_lib.FLAG_DETERMINISTIC if deterministic else 0) |
                                     (_lib.FLAG_FUSED_GATHER if fused_gather else 0) |
-                                    (_lib.FLAG_BF16_GEMM if precision == "bf16" else 0),
+                                    (_lib.FLAG_BF16_GEMM if precision == "bf16" else 0) |
+                                    (_lib.FLAG_BF16_FEATURES if features == "bf16" else 0),
                               num_marginal=int(num_marginal) if model_type == "vlmap_answer_ent" else 0,
                               ent_cols=int(ent_cols or A) if model_type == "vlmap_answer_ent" else 0,
                               extra_weight={"vlmap_answer_ent": W_ENTROPY, "vlmap_answer_full": LATENT_LOSS_WEIGHT}.get(model_type, 0.0))
@@ -477,6 +491,10 @@ class FusionEngine:
         off, n = C.c_int64(), C.c_int64()
         _lib.check(self.lib.vqa_fusion_tensor(C.byref(self.dims), name.encode(), C.byref(off), C.byref(n)),
                    "vqa_fusion_tensor(%s)" % name)
+        if name == "V_ft" and self.features == "bf16":      # the one 16-bit tensor of the workspace
+            t = self.workspace[off.value:off.value + 2 * n.value].view(torch.bfloat16)
+            self._tensor_cache[name] = t
+            return t
         raw = self.workspace[off.value:off.value + 4 * n.value]
         t = raw.view(torch.int32 if name in _INT_TENSORS else torch.float32)
         self._tensor_cache[name] = t
@@ -487,7 +505,15 @@ class FusionEngine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def bind_inputs(self, *, table, nbox_table, answer_masks):
-        """Device-resident feature table [N,R,D] f32, num_boxes i32 [N], float [A] masks."""
+        """Device-resident feature table [N,R,D] f32 (torch.bfloat16 with features="bf16": never converted here),
+        num_boxes i32 [N], float [A] masks."""
+        if self.features == "bf16":
+            d = self.dims
+            if not (torch.is_tensor(table) and table.dtype == torch.bfloat16 and table.is_cuda and table.is_contiguous()
+                    and table.dim() == 3 and tuple(table.shape[1:]) == (d.R, d.D)):
+                raise ValueError("features='bf16' needs a contiguous torch.bfloat16 device table [N, %d, %d] (got %s %s); "
+                                 "model_vlmap_answer.features_to_bf16 converts an f32 array"
+                                 % (d.R, d.D, getattr(table, "dtype", type(table)), tuple(getattr(table, "shape", ()))))
         self._table, self._nbox = table, nbox_table
         self._amask = answer_masks
         if self.model_type == "vlmap_answer_ent" and not self._ent_cols_given:

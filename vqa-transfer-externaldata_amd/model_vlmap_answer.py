@@ -153,6 +153,38 @@ def load_image_features(path):
             int(z["max_box_num"]), int(z["vfeat_dim"]))
 
 
+FEATURE_CHUNK_BYTES = 256 << 20
+
+
+def features_to_bf16(features, device=None, chunk_bytes=FEATURE_CHUNK_BYTES):
+    """The bf16 feature table of FusionEngine(features="bf16") from an f32 feature array [N, ...] (ndarray, np.memmap view
+    of a feature file, or tensor): a torch.bfloat16 tensor of the same shape on `device` (None: where the input lives; the
+    host for arrays).  Every element is rounded to the nearest bf16, ties to even; +-0 and +-inf keep their patterns, a
+    NaN stays a NaN, an f32 beyond the largest bf16 rounds to inf.  The array is walked in slices of at most `chunk_bytes`
+    along its first axis, each rounded where it lives and then moved, so no second full-size f32 copy ever exists on the
+    host or on the device.  The feature file itself stays f32 (load_image_features)."""
+    is_t = torch.is_tensor(features)
+    if not is_t and not isinstance(features, np.ndarray):
+        features = np.asarray(features)
+    if (features.dtype != torch.float32) if is_t else (features.dtype != np.float32):
+        raise ValueError("features_to_bf16 converts float32 features, not %s" % (features.dtype,))
+    shape = tuple(features.shape)
+    dev = torch.device(device) if device is not None else (features.device if is_t else torch.device("cpu"))
+    out = torch.empty(shape, dtype=torch.bfloat16, device=dev)
+    if len(shape) == 0 or out.numel() == 0:
+        if out.numel():
+            out.copy_((features if is_t else torch.from_numpy(np.array(features))).to(torch.bfloat16))
+        return out
+    row_bytes = 4 * max(out.numel() // shape[0], 1)
+    rows = max(1, int(chunk_bytes) // row_bytes)
+    for lo in range(0, shape[0], rows):
+        part = features[lo:lo + rows]
+        if not is_t:
+            part = torch.from_numpy(np.array(part))      # a private, writable copy of this slice only
+        out[lo:lo + rows].copy_(part.to(torch.bfloat16))
+    return out
+
+
 class Model(object):
     MODEL_TYPE = "vlmap_answer"
 
@@ -275,9 +307,12 @@ class Model(object):
                              W=W_DIM, A=self.num_answer, Vq=Vq, N_img=len(self.features),
                              params=self._initial_params(shapes), device=self.device,
                              global_batch=getattr(self.config, "global_batch", None),
-                             precision=getattr(self.config, "precision", "f32"), **self._engine_kwargs())
+                             precision=getattr(self.config, "precision", "f32"),
+                             features=getattr(self.config, "features", "f32"), **self._engine_kwargs())
         eng.bind_inputs(
-            table=self._to_dev(self.features, torch.float32),        # the whole table lives in HBM (a1)
+            # the whole table lives in HBM (a1): f32, or rounded to bf16 slice by slice on its way up (--features bf16)
+            table=(features_to_bf16(self.features, self.device) if eng.features == "bf16"
+                   else self._to_dev(self.features, torch.float32)),
             nbox_table=self._to_dev(self.num_boxes, torch.int32),
             answer_masks={"train": self._to_dev(self.train_answer_mask, torch.float32),
                           "obj": self._to_dev(self.obj_answer_mask, torch.float32),

@@ -53,6 +53,20 @@ def gather_features(table, nbox_table, idx):
     return V, nb
 
 
+def gather_features_bf16(table, nbox_table, idx):
+    """gather_features for a table that is bf16 at rest: table [N,R,D] torch.bfloat16 -> V [B,R,D] torch.bfloat16 (the
+    16-bit patterns are copied, never converted), nb i32 [B]."""
+    lib = _lib.load()
+    assert table.dtype == torch.bfloat16 and table.is_contiguous()
+    N, R, D = table.shape
+    B = idx.numel()
+    V = torch.empty(B, R, D, dtype=torch.bfloat16, device=table.device)
+    nb = torch.empty(B, dtype=torch.int32, device=table.device)
+    _lib.check(lib.vqa_gather_features_bf16(_p(table), _p(nbox_table), _p(idx), _p(V), _p(nb), B, R, D, N, _st(table)),
+               "vqa_gather_features_bf16")
+    return V, nb
+
+
 def embed_fwd(E, q):
     lib = _lib.load()
     B, T = q.shape
@@ -141,6 +155,42 @@ def attn_pool_bwd(dpooled, v, qv, V, att, w, keepmask=None, keep_prob=1.0):
     return dv, dqv, colsum(pdw), colsum(pdb)
 
 
+def attn_pool_fwd_v16(v, qv, V16, nb, w, bias, keepmask=None, keep_prob=1.0):
+    """attn_pool_fwd over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_fwd on V16.float()."""
+    lib = _lib.load()
+    assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
+    B, R, H = v.shape
+    D = V16.shape[2]
+    att, pooled = _f32(B, R, like=v), _f32(B, D, like=v)
+    _lib.check(lib.vqa_attn_pool_fwd_v16(_p(v), _p(qv), _p(V16), _p(nb), _p(w), _p(bias), _p(keepmask), keep_prob, _p(att),
+                                         _p(pooled), B, R, H, D, _st(v)), "vqa_attn_pool_fwd_v16")
+    return att, pooled
+
+
+def attn_pool_bwd_v16(dpooled, v, qv, V16, att, w, keepmask=None, keep_prob=1.0):
+    """attn_pool_bwd over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_bwd on V16.float()."""
+    lib = _lib.load()
+    assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
+    B, R, H = v.shape
+    D = V16.shape[2]
+    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
+    pdw, pdb = _f32(B, H, like=v), _f32(B, 1, like=v)
+    _lib.check(lib.vqa_attn_pool_bwd_v16(_p(dpooled), _p(v), _p(qv), _p(V16), _p(att), _p(w), _p(keepmask), keep_prob,
+                                         _p(dv), _p(dqv), _p(pdw), _p(pdb), B, R, H, D, _st(v)), "vqa_attn_pool_bwd_v16")
+    return dv, dqv, colsum(pdw), colsum(pdb)
+
+
+def attn_pool_bwd_ds_v16(dpooled, V16, att):
+    """attn_pool_bwd_ds over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_bwd_ds on V16.float()."""
+    lib = _lib.load()
+    assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
+    B, R, D = V16.shape
+    ds, pdb = _f32(B, R, like=dpooled), _f32(B, like=dpooled)
+    _lib.check(lib.vqa_attn_pool_bwd_ds_v16(_p(dpooled), _p(V16), _p(att), _p(ds), _p(pdb), B, 1, R, 1024, D, _st(V16)),
+               "vqa_attn_pool_bwd_ds_v16")
+    return ds, pdb
+
+
 def attn_pool_bwd_ds(dpooled, V, att):
     """The attention backward up to the gradient of the raw scores: ds [B,R] and the per-sample score-bias partial [B]
     (one query per memory, R 36, H 1024, D 2048: vqa_vtail_supported)."""
@@ -223,7 +273,7 @@ def gemm_bf16x3_ex(A, B, transA=False, bias=None, split_k=1, out=None):
     return Cm
 
 
-def gemm_bf16(A, B, transA=False, transB=False, bias=None, add=None, split_k=0, out=None):
+def gemm_bf16(A, B, transA=False, transB=False, bias=None, add=None, split_k=0, out=None, max_blocks=0):
     """C = op(A) @ op(B) (+bias) (+add) with both operands rounded to bf16 (nearest even) on their way into the matrix
     unit, f32 accumulation, f32 result (csrc/gemm_bf16.hip; the product of FusionEngine(precision="bf16")).  NN, TN and NT,
     any shape.  split_k: 0 = chosen from the shape, 1 = one k range, n > 1 = n ranges summed in range order."""
@@ -238,7 +288,26 @@ def gemm_bf16(A, B, transA=False, transB=False, bias=None, add=None, split_k=0, 
     ws = _f32(max(nws, 4), like=A)
     _lib.check(lib.vqa_gemm_bf16(int(transA), int(transB), M, N, K, _p(A), A.stride(0), _p(B), B.stride(0), _p(Cm),
                                  Cm.stride(0), _p(bias), _p(add), add.stride(0) if add is not None else 0, split_k, _p(ws),
-                                 ws.numel(), 0, _st(A)), "vqa_gemm_bf16")
+                                 ws.numel(), max_blocks, _st(A)), "vqa_gemm_bf16")
+    return Cm
+
+
+def gemm_bf16_a16(A16, B, transA=False, transB=False, bias=None, add=None, split_k=0, out=None, max_blocks=0):
+    """gemm_bf16 with a left operand that is bf16 in HBM already (A16: torch.bfloat16, rows contiguous): the 16-bit patterns
+    go to LDS unconverted, so the result holds the bits of gemm_bf16(A16.float(), ...).  max_blocks > 0: persistent launch
+    with at most that many workgroups."""
+    lib = _lib.load()
+    assert A16.dtype == torch.bfloat16 and B.dtype == torch.float32 and A16.stride(-1) == 1 and B.stride(-1) == 1
+    M, K = (A16.shape[1], A16.shape[0]) if transA else (A16.shape[0], A16.shape[1])
+    N = B.shape[0] if transB else B.shape[1]
+    assert (B.shape[1] if transB else B.shape[0]) == K
+    Cm = out if out is not None else _f32(M, N, like=B)
+    assert Cm.dtype == torch.float32 and tuple(Cm.shape) == (M, N) and Cm.stride(1) == 1
+    nws = int(lib.vqa_gemm_bf16_workspace_floats(M, N, K, split_k))
+    ws = _f32(max(nws, 4), like=B)
+    _lib.check(lib.vqa_gemm_bf16_a16(int(transA), int(transB), M, N, K, _p(A16), A16.stride(0), _p(B), B.stride(0), _p(Cm),
+                                     Cm.stride(0), _p(bias), _p(add), add.stride(0) if add is not None else 0, split_k,
+                                     _p(ws), ws.numel(), max_blocks, _st(B)), "vqa_gemm_bf16_a16")
     return Cm
 
 

@@ -327,6 +327,9 @@ def build_parser():
     parser.add_argument("--precision", type=str, default="f32", choices=["f32", "bf16"],
                         help="bf16: the dense layers' products with bf16 operands in the matrix unit, f32 master weights and "
                              "accumulation (vlmap_answer and standard; not in the reference; checkpoints are those of f32)")
+    parser.add_argument("--features", type=str, default="f32", choices=["f32", "bf16"],
+                        help="bf16 (only with --precision bf16): the region-feature table is rounded to bf16 once at load and "
+                             "kept in HBM as bf16 -- half the feature memory and gather traffic; the feature file stays f32")
     parser.add_argument("--debug", type=int, default=0, help="0: normal, 1: debug")
     return parser
 

@@ -468,6 +468,34 @@ int vqa_clip_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, c
 /* explicit dropout keep-mask (counter-based, reproducible): out[i] = u(seed,i) < keep_prob */
 int vqa_dropout_mask(uint8_t* out, int64_t n, uint64_t seed, uint64_t offset, float keep_prob, void* stream);
 
+/* Seeded dropout: the entry points above that take a keep mask, with the mask's bits COMPUTED in the kernel instead of
+ * loaded.  Each takes (seed, offset, keep_prob) where its explicit form takes (keepmask, keep_prob); `offset` is the
+ * stream position of the site's element 0, with the meaning it has in vqa_dropout_mask, so a seeded call is bit for bit
+ * the explicit call on the mask vqa_dropout_mask(mask, n, seed, offset, keep_prob) writes: the same kernel (the same
+ * choice of generic / loads-in-flight / register-resident form, under vqa_attn_set_fast and vqa_ln_set_fast), which forms
+ * the 4-byte mask word of four consecutive h (or columns) where the explicit form loads it.  Costs one 64-bit hash per
+ * word in every consuming kernel; saves the mask buffer, its launch, one write and two reads of it per step.
+ * Checked before any HIP call: a NULL required pointer or keep_prob <= 0 -> VQA_ERR_ARG; offset % 4 != 0, a row length
+ * (H, N) that is no multiple of 4, or pointers whose alignment would send the explicit form to its one-column kernels
+ * -> VQA_ERR_ALIGN; rep != 1 -> VQA_ERR_UNSUPPORTED (one query per memory; the kernels with several stay explicit).
+ * V: the pooled memory, const float* (v_bf16 == 0) or const uint16_t* raw bf16 patterns (v_bf16 != 0, the _v16 kernels). */
+int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int v_bf16, const int32_t* nb, const float* w,
+                             const float* bias, uint64_t seed, uint64_t offset, float keep_prob, float* att, float* pooled,
+                             int B, int rep, int R, int H, int D, void* stream);
+int vqa_attn_pool_bwd_seeded(const float* dpooled, const float* v, const float* qv, const void* V, int v_bf16,
+                             const float* att, const float* w, uint64_t seed, uint64_t offset, float keep_prob, float* dv,
+                             float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H, int D, void* stream);
+int vqa_ln_act_fwd_seeded(const float* pre, const float* gamma, const float* beta, uint64_t seed, uint64_t offset,
+                          float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act, void* stream);
+int vqa_ln_act_bwd_seeded(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma,
+                          const float* beta, uint64_t seed, uint64_t offset, float keep_prob, float* dpre,
+                          float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows, int N, int act,
+                          void* stream);
+int vqa_ln_relu_att_bwd_seeded(const float* ds, const float* qv, const float* w, uint64_t seed, uint64_t offset,
+                               float keep_prob, const float* pre, const float* mean, const float* rstd, const float* gamma,
+                               const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
+                               float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream);
+
 /* ------------------------------------------------------------------------
  * Whole fusion model (vqa/model_vlmap_answer.py:102-288 / vqa/model_standard.py:193-374)
  * and its backward, as one host call each.
@@ -649,7 +677,20 @@ typedef struct {
     const uint8_t* keep_word;           /* model_type 12: keep-mask of the word attention's dropout [B,T,H] or NULL */
     const int32_t* answer_intseq;       /* model_type 13: token ids of the candidate answers [A, La], zero padded */
     const int32_t* answer_intseq_len;   /* model_type 13: [A] */
+    /* Seeded dropout (zero-filled: every site reads its mask pointer above, as before).  Bit i of keep_seeded set: site
+     * i has no mask buffer -- its pointer above must be NULL, VQA_ERR_ARG otherwise -- and draws its keep bits from
+     * (keep_seed, the site's offset below) inside the kernels that consume them (the *_seeded entry points; offsets
+     * multiples of 4).  The same struct goes to vqa_fusion_backward, which regenerates the same bits; nothing is kept in
+     * the library. */
+    uint64_t keep_seed;
+    uint64_t keep_att_off, keep_joint_off, keep_joint2_off, keep_tile_off, keep_word_off;
+    int32_t keep_seeded;                /* VQA_KEEP_SITE_* bits */
 } vqa_batch_t;
+#define VQA_KEEP_SITE_ATT 1             /* keep_att   / keep_att_off */
+#define VQA_KEEP_SITE_JOINT 2           /* keep_joint / keep_joint_off */
+#define VQA_KEEP_SITE_JOINT2 4          /* keep_joint2 / keep_joint2_off */
+#define VQA_KEEP_SITE_TILE 8            /* keep_tile  / keep_tile_off */
+#define VQA_KEEP_SITE_WORD 16           /* keep_word  / keep_word_off */
 
 int64_t vqa_fusion_workspace_bytes(const vqa_dims_t* dims);
 /* Byte offset / element count of a named intermediate inside the workspace

@@ -1,0 +1,341 @@
+"""Seeded dropout: the keep bits of a dropout site computed inside the kernels that consume them
+(vqa_attn_pool_fwd_seeded, vqa_attn_pool_bwd_seeded, vqa_ln_act_fwd_seeded, vqa_ln_act_bwd_seeded,
+vqa_ln_relu_att_bwd_seeded; FusionEngine.forward(dropout=(seed, step)); config.inline_dropout).
+
+The reference everywhere is the explicit-mask path fed by vqa_dropout_mask(seed, offset, keep): the same kernel reads from a
+buffer the word the seeded form computes.  Every comparison is torch.equal; there is no tolerance."""
+import argparse
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import bi_oracle as BO
+from oracle import vqa_oracle as O
+from tests import bf16_ref as R
+from tests import keep_ref as K
+from tests.gpu_util import dev, dev_batch, make_case, make_engine
+
+pytestmark = pytest.mark.gpu
+
+SEED = 123
+OFFSETS = (0, 4 * 12345, (3 << 40) + 4 * 7)
+KEEPS = (0.8, 0.5, 1.0)
+
+
+def _ops():
+    from vqa_transfer_externaldata_amd import ops
+    return ops
+
+
+def _lib():
+    from vqa_transfer_externaldata_amd import _lib
+    return _lib
+
+
+def _randn(g, *shape):
+    return torch.randn(*shape, generator=g).cuda()
+
+
+def _same(x, y, what):
+    if isinstance(x, (tuple, list)):
+        assert len(x) == len(y)
+        for i, (a, b) in enumerate(zip(x, y)):
+            _same(a, b, what + (i,))
+    else:
+        assert torch.equal(x, y), what
+
+
+# ------------------------------------------------------------------------------------------------------ the generator
+@pytest.mark.parametrize("seed,offset,keep", [(123, 0, 0.8), (9, (3 << 40) + 49380, 0.5), (77, (1 << 40) + 3, 0.8),
+                                              (9, 0, 1.0), (123, 4 * 12345 + 1, 0.5)])
+@pytest.mark.parametrize("n", [1000, 1 << 16])
+def test_dropout_mask_equals_the_numpy_restatement(n, seed, offset, keep):
+    got = _ops().dropout_mask(n, seed, offset, keep, "cuda").cpu().numpy()
+    assert np.array_equal(got, K.keep_bits(n, seed, offset, keep))
+
+
+# ------------------------------------------------------------------------------------------------------ attention
+# (name, B, R, H, D, vqa_attn_set_fast or None): the generic kernels, the loads-in-flight pair of the models' shape, another
+# instantiation of the loads-in-flight forward, and the generic kernels at the models' shape
+ATT_CASES = [("generic", 3, 5, 8, 12, None), ("fast", 4, 36, 1024, 2048, None), ("fast-fwd-h256-d4096", 2, 7, 256, 4096, None),
+             ("generic-at-the-models-shape", 2, 36, 1024, 2048, 0)]
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32-memory", "bf16-memory"])
+@pytest.mark.parametrize("name,B,Rg,H,D,fast", ATT_CASES, ids=[c[0] for c in ATT_CASES])
+def test_attention_seeded_equals_explicit(name, B, Rg, H, D, fast, bf16):
+    ops, lib = _ops(), _lib().load()
+    g = torch.Generator().manual_seed(7)
+    v, qv, w, bias, dpooled = _randn(g, B, Rg, H), _randn(g, B, H), _randn(g, H), _randn(g, 1), _randn(g, B, D)
+    V = _randn(g, B, Rg, D)
+    if bf16:
+        V = V.to(torch.bfloat16)
+    nb = torch.randint(1, Rg + 1, (B,), generator=g).int()
+    nb[-1] = Rg
+    nb = nb.cuda()
+    fwd, bwd = (ops.attn_pool_fwd_v16, ops.attn_pool_bwd_v16) if bf16 else (ops.attn_pool_fwd, ops.attn_pool_bwd)
+    if fast is not None:
+        lib.vqa_attn_set_fast(fast)
+    try:
+        for off in OFFSETS:
+            for keep in KEEPS:
+                mask = ops.dropout_mask(B * Rg * H, SEED, off, keep, "cuda")
+                x = fwd(v, qv, V, nb, w, bias, keepmask=mask, keep_prob=keep)
+                y = fwd(v, qv, V, nb, w, bias, keep_seed=(SEED, off), keep_prob=keep)
+                _same(x, y, (name, "fwd", off, keep))
+                assert torch.isfinite(x[1]).all()
+                x = bwd(dpooled, v, qv, V, x[0], w, keepmask=mask, keep_prob=keep)
+                y = bwd(dpooled, v, qv, V, y[0], w, keep_seed=(SEED, off), keep_prob=keep)
+                _same(x, y, (name, "bwd", off, keep))
+    finally:
+        lib.vqa_attn_set_fast(1)
+    # the mask matters: another seed gives other scores
+    z = fwd(v, qv, V, nb, w, bias, keep_seed=(SEED + 1, 0), keep_prob=0.5)
+    assert not torch.equal(z[0], fwd(v, qv, V, nb, w, bias, keep_seed=(SEED, 0), keep_prob=0.5)[0])
+
+
+def test_ln_relu_att_bwd_seeded_equals_explicit():
+    ops = _ops()
+    B, Rg, H = 2, 36, 1024
+    g = torch.Generator().manual_seed(8)
+    ds, qv, w, pre = _randn(g, B, Rg), _randn(g, B, H), _randn(g, H), _randn(g, B, Rg, H)
+    gamma, beta = 1 + 0.1 * _randn(g, H), 0.1 * _randn(g, H)
+    _, mean, rstd = ops.ln_relu_fwd(pre.view(B * Rg, H), gamma, beta, rows=Rg)
+    for off in OFFSETS:
+        for keep in KEEPS:
+            mask = ops.dropout_mask(B * Rg * H, SEED, off, keep, "cuda")
+            x = ops.ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keepmask=mask, keep_prob=keep)
+            y = ops.ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keep_seed=(SEED, off), keep_prob=keep)
+            _same(x, y, ("ln_relu_att_bwd", off, keep))
+
+
+# ------------------------------------------------------------------------------------------------------ LayerNorm
+# (rows, N): one row per group at 8, 2048 and 2052 columns (generic kernels; 2052: a partial pass over the column units);
+# 36 x 1024, 5 x 1024 and 8 x 2048: the three register-resident forms under vqa_ln_set_fast(1), generic under (0)
+LN_CASES = [(1, 8), (1, 2048), (1, 2052), (36, 1024), (5, 1024), (8, 2048)]
+
+
+@pytest.mark.parametrize("ln_fast", [1, 0], ids=["ln-fast", "ln-generic"])
+@pytest.mark.parametrize("rows,N", LN_CASES)
+def test_layernorm_seeded_equals_explicit(rows, N, ln_fast):
+    ops, lib = _ops(), _lib().load()
+    G = 3
+    g = torch.Generator().manual_seed(9)
+    pre, dy = _randn(g, G * rows, N), _randn(g, G * rows, N)
+    gamma, beta = 1 + 0.1 * _randn(g, N), 0.1 * _randn(g, N)
+    lib.vqa_ln_set_fast(ln_fast)
+    try:
+        for off in OFFSETS:
+            for keep in KEEPS:
+                mask = ops.dropout_mask(G * rows * N, SEED, off, keep, "cuda")
+                kx, ky = dict(keepmask=mask, keep_prob=keep), dict(keep_seed=(SEED, off), keep_prob=keep)
+                x = ops.ln_relu_fwd(pre, gamma, beta, rows=rows, **kx)
+                y = ops.ln_relu_fwd(pre, gamma, beta, rows=rows, **ky)
+                _same(x, y, ("ln_relu_fwd", off, keep))
+                _same(ops.ln_relu_bwd(dy, pre, x[1], x[2], gamma, beta, rows=rows, **kx),
+                      ops.ln_relu_bwd(dy, pre, y[1], y[2], gamma, beta, rows=rows, **ky), ("ln_relu_bwd", off, keep))
+                _same(ops.ln_relu_bwd(dy, pre, x[1], x[2], gamma, beta, rows=rows, want_params=False, **kx)[0],
+                      ops.ln_relu_bwd(dy, pre, y[1], y[2], gamma, beta, rows=rows, want_params=False, **ky)[0],
+                      ("ln_relu_bwd no params", off, keep))
+                for act in ("relu", "tanh"):
+                    x = ops.ln_act_fwd(pre, gamma, beta, rows=rows, act=act, **kx)
+                    y = ops.ln_act_fwd(pre, gamma, beta, rows=rows, act=act, **ky)
+                    _same(x, y, ("ln_act_fwd", act, off, keep))
+                    _same(ops.ln_act_bwd(dy, pre, x[1], x[2], gamma, beta, rows=rows, act=act, **kx),
+                          ops.ln_act_bwd(dy, pre, y[1], y[2], gamma, beta, rows=rows, act=act, **ky), ("ln_act_bwd", act, off, keep))
+        if pre.numel() >= 4096:       # the bits are applied: half of what the ReLU leaves is dropped
+            zeros = lambda t: float((t == 0).float().mean())
+            y0 = ops.ln_relu_fwd(pre, gamma, beta, rows=rows)[0]
+            y = ops.ln_relu_fwd(pre, gamma, beta, rows=rows, keep_seed=(SEED, 0), keep_prob=0.5)[0]
+            assert 0.15 < zeros(y) - zeros(y0) < 0.35
+    finally:
+        lib.vqa_ln_set_fast(1)
+
+
+# ------------------------------------------------------------------------------------------------------ refusals
+def test_refusals():
+    ops, L = _ops(), _lib()
+    lib = L.load()
+    B, Rg, H, D = 5, 4, 8, 12
+    g = torch.Generator().manual_seed(10)
+    v, qv, V, w, bias = _randn(g, B, Rg, H), _randn(g, B, H), _randn(g, B, Rg, D), _randn(g, H), _randn(g, 1)
+    nb = torch.full((B,), Rg, dtype=torch.int32).cuda()
+    att, pooled = torch.empty(B, Rg).cuda(), torch.empty(B, D).cuda()
+    p = lambda t: t.data_ptr()
+    with pytest.raises(L.VqaHotError, match="unsupported"):        # five queries per memory: the pre-training kernels stay explicit
+        L.check(lib.vqa_attn_pool_fwd_seeded(p(v), p(qv), p(V), 0, p(nb), p(w), p(bias), SEED, 0, 0.8, p(att), p(pooled), 1, 5,
+                                             Rg, H, D, None), "vqa_attn_pool_fwd_seeded")
+    with pytest.raises(L.VqaHotError, match="aligned"):
+        ops.attn_pool_fwd(v, qv, V, nb, w, bias, keep_seed=(SEED, 2), keep_prob=0.8)
+    with pytest.raises(L.VqaHotError, match="aligned"):
+        ops.ln_relu_fwd(v.view(B * Rg, H), w, w, keep_seed=(SEED, 6), keep_prob=0.5)
+    mask = ops.dropout_mask(B * Rg * H, SEED, 0, 0.8, "cuda")
+    with pytest.raises(ValueError, match="mutually exclusive"):
+        ops.attn_pool_fwd(v, qv, V, nb, w, bias, keepmask=mask, keep_seed=(SEED, 0), keep_prob=0.8)
+    with pytest.raises(ValueError, match="mutually exclusive"):
+        ops.ln_act_bwd(v.view(B * Rg, H), v.view(B * Rg, H), bias, bias, w, w, keepmask=mask, keep_seed=(SEED, 0), keep_prob=0.8)
+    name, dims, Be, Re, T, N = R.MODEL_CASES[0]
+    pp, table, nbox, batch, am, masks = make_case(R.MODEL_SEED, "vlmap_answer", Be, Re, T, N, dims)
+    eng = make_engine("vlmap_answer", pp, table, nbox, am, Be, Re, T, dims)
+    db = dev_batch(batch)
+    ka, kj = eng.make_keep_masks(SEED, 0)
+    with pytest.raises(ValueError, match="keep_"):
+        eng.forward(db, keep_att=ka, dropout=(SEED, 0))
+    with pytest.raises(ValueError, match="keep_"):
+        eng.train_step(db, None, kj, 1e-3, dropout=(SEED, 0))
+    with pytest.raises(ValueError, match="replay"):
+        eng.train_step_graph(db, 1e-3, SEED, 0, dropout=(SEED, 0))
+
+
+# ------------------------------------------------------------------------------------------------------ the step
+WATCHED = ("logit", "att_score", "pooled_V_ft", "joint", "pred")
+MASK_ATTRS = ("_keep_att", "_keep_joint", "_keep_joint2", "_keep_tile", "_keep_word")
+NUM_MARGINAL = 7
+
+
+def _step_case(model_type, case):
+    name, dims, B, Rg, T, N = case
+    if model_type == "vlmap_finetune":
+        rng = np.random.default_rng(R.MODEL_SEED)
+        p = O.perturb_ln_params(BO.init_params(rng, **dims), rng)
+        table, nbox = O.make_table(rng, N, Rg, dims["D"], full_boxes=False)
+        batch = O.make_batch(rng, B, T, dims["Vq"], dims["A"], N)
+        am = O.make_answer_masks(rng, dims["A"], int(dims["A"] * 0.75), exist_all=False)
+    else:
+        p, table, nbox, batch, am, _ = make_case(R.MODEL_SEED, model_type, B, Rg, T, N, dims, num_marginal=NUM_MARGINAL)
+    return p, table, nbox, batch, am
+
+
+def _engine(model_type, p, table, nbox, am, B, Rg, T, dims, **kw):
+    """tests/gpu_util.make_engine, with the table converted for features="bf16" (which takes a torch.bfloat16 table)"""
+    from vqa_transfer_externaldata_amd import fusion as F
+    t = dev(table.astype(np.float32))
+    if kw.get("features") == "bf16":
+        t = t.to(torch.bfloat16)
+    eng = F.FusionEngine(model_type=model_type, B=B, R=Rg, T=T, N_img=table.shape[0],
+                         params={k: v.astype(np.float32) for k, v in p.items() if not O.is_const(k)}, **dims, **kw)
+    eng.bind_inputs(table=t, nbox_table=dev(nbox), answer_masks={k: dev(v.astype(np.float32)) for k, v in am.items()})
+    return eng
+
+
+def _explicit_masks(eng, step, **kw):
+    """the masks of every dropout site the model type has, from make_keep_masks and its siblings"""
+    ka, kj = eng.make_keep_masks(SEED, step, **kw)
+    extra = {}
+    if "keep_joint2" in eng.keep_sites():
+        extra["keep_joint2"] = eng.make_keep_mask_joint2(SEED, step, **kw)
+    if "keep_tile" in eng.keep_sites():
+        extra["keep_tile"] = eng.make_keep_mask_tile(SEED, step, **kw)
+    if "keep_word" in eng.keep_sites():
+        extra["keep_word"] = eng.make_keep_mask_word(SEED, step, **kw)
+    return ka, kj, extra
+
+
+def _steps_equal(model_type, case, **ekw):
+    name, dims, B, Rg, T, N = case
+    p, table, nbox, batch, am = _step_case(model_type, case)
+    if model_type == "vlmap_answer_ent":
+        ekw["num_marginal"] = NUM_MARGINAL
+    X = _engine(model_type, p, table, nbox, am, B, Rg, T, dims, deterministic=True, **ekw)
+    Y = _engine(model_type, p, table, nbox, am, B, Rg, T, dims, deterministic=True, **ekw)
+    db = dev_batch(batch)
+    for step in (3, 4):
+        ka, kj, extra = _explicit_masks(X, step)
+        X.train_step(db, ka, kj, 1e-3, **extra)
+        Y.train_step(db, lr=1e-3, dropout=(SEED, step))
+        torch.cuda.synchronize()
+        assert torch.isfinite(Y.grad_flat).all()
+        for n in X.train_names:
+            assert torch.equal(X.grads[n], Y.grads[n]), (step, n)
+        assert torch.equal(X.grad_flat, Y.grad_flat), step
+        for n in WATCHED:
+            assert torch.equal(X.tensor(n), Y.tensor(n)), (step, n)
+        assert X.report() == Y.report()
+    for n in X.params:
+        assert torch.equal(X.params[n], Y.params[n]), n
+    assert torch.equal(X.train_flat, Y.train_flat) and torch.equal(X.m_flat, Y.m_flat) and torch.equal(X.v_flat, Y.v_flat)
+    assert not any(hasattr(Y, a) for a in MASK_ATTRS)
+    assert all(hasattr(X, "_" + s) for s in X.keep_sites()) and len(X.keep_sites()) >= 2
+    # dropout does something here: the seeded step differs from the step without dropout
+    Y.forward(db, dropout=(SEED, 5), want_dz=False)
+    with_dropout = Y.tensor("logit").clone()
+    # dropout=None and no masks: today's forward without dropout
+    X.forward(db, None, None, want_dz=False)
+    Y.forward(db, dropout=None, want_dz=False)
+    torch.cuda.synchronize()
+    for n in WATCHED:
+        assert torch.equal(X.tensor(n), Y.tensor(n)), ("no dropout", n)
+    assert not torch.equal(with_dropout, Y.tensor("logit"))
+
+
+STEP_TYPES = ["vlmap_answer", "standard", "vlmap_answer_noc", "vlmap_answer_adapt", "vlmap_answer_ent", "vlmap_finetune"]
+SMALL_CASE = [c for c in R.MODEL_CASES if c[0] == "small"][0]
+FULL_CASE = [c for c in R.MODEL_CASES if c[0] == "full_dims"][0]
+
+
+@pytest.mark.parametrize("model_type", STEP_TYPES)
+def test_seeded_step_equals_explicit_step_small(model_type):
+    _steps_equal(model_type, SMALL_CASE)
+
+
+@pytest.mark.parametrize("vtail", [0, 1], ids=["separate-calls", "fused-chain"])
+@pytest.mark.parametrize("model_type", ["vlmap_answer", "standard"])
+def test_seeded_step_equals_explicit_step_full_dims(model_type, vtail):
+    """R 36, H 1024, D 2048: the loads-in-flight attention kernels, the register-resident LayerNorm of v_linear_v, and both
+    backward routes of vqa_vtail_set_mode"""
+    lib = _lib().load()
+    assert lib.vqa_vtail_set_mode(vtail) == vtail
+    try:
+        _steps_equal(model_type, FULL_CASE)
+    finally:
+        lib.vqa_vtail_set_mode(-1)
+
+
+def test_seeded_step_equals_explicit_step_full_dims_bf16_features():
+    _steps_equal("vlmap_answer", FULL_CASE, precision="bf16", features="bf16")
+
+
+def test_shards_draw_the_bits_of_the_whole_batch():
+    name, dims, _, Rg, T, N = SMALL_CASE
+    B = 8
+    p, table, nbox, batch, am, _ = make_case(R.MODEL_SEED, "vlmap_answer", B, Rg, T, N, dims)
+    whole = make_engine("vlmap_answer", p, table, nbox, am, B, Rg, T, dims, deterministic=True)
+    whole.forward(dev_batch(batch), dropout=(SEED, 3), want_dz=False)
+    for lo in (0, 4):
+        shard = make_engine("vlmap_answer", p, table, nbox, am, 4, Rg, T, dims, deterministic=True, global_batch=B)
+        sb = dev_batch({k: v[lo:lo + 4] for k, v in batch.items()})
+        shard.forward(sb, dropout=(SEED, 3), row_offset=lo, global_rows=B, want_dz=False)
+        torch.cuda.synchronize()
+        for n in ("att_score", "joint", "logit"):
+            w = whole.tensor(n).view(B, -1)[lo:lo + 4]
+            assert torch.equal(shard.tensor(n).view(4, -1), w), (lo, n)
+    # (and the rows differ from each other's bits: shard 1 without its row offset is not rows 4-7)
+    shard.forward(sb, dropout=(SEED, 3), row_offset=0, global_rows=B, want_dz=False)
+    assert not torch.equal(shard.tensor("joint").view(4, -1), whole.tensor("joint").view(B, -1)[4:])
+
+
+# ------------------------------------------------------------------------------------------------------ the model class
+def test_trainer_and_evaler_with_inline_dropout_equal_the_explicit_run(tmp_path):
+    from tests.test_gpu_trainer import _config, _datasets, _features
+    from vqa_transfer_externaldata_amd import evaler, trainer
+    losses, pkls = {}, {}
+    for inline in (False, True):
+        c, Vq, A = _config(tmp_path / str(inline), "vlmap_answer", inline_dropout=inline)
+        ds = _datasets(Vq, A)
+        t = trainer.Trainer(c, datasets=ds, image_features=_features())
+        losses[inline] = [float(t.run_train_step(False)[2]) for _ in range(3)]
+        assert hasattr(t.model.engine, "_keep_att") != inline
+        ckpt = t.save_checkpoint()
+        ec = argparse.Namespace(**vars(c))
+        ec.checkpoint, ec.split, ec.max_iter, ec.dump_heavy_output = ckpt, "testval", -1, False
+        ev = evaler.Evaler(ec, image_features=_features(), data=ds["testval"])
+        ev.eval()
+        pkls[inline] = pickle.load(open(ev.save_pkl, "rb"))
+    assert losses[True] == losses[False] and all(np.isfinite(losses[True]))
+    assert pkls[True] == pkls[False] and len(pkls[True]["qid2result"]) == 40
+    assert trainer.parse_config(["--inline_dropout"]).inline_dropout and not trainer.parse_config([]).inline_dropout
+    assert evaler.build_parser().parse_args(["--checkpoint", "x", "--inline_dropout"]).inline_dropout
+    from vqa_transfer_externaldata_amd import eval_multiple_model as EMM
+    assert EMM.build_parser().parse_args(["--inline_dropout"]).inline_dropout

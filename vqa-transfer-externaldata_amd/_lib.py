@@ -56,7 +56,14 @@ class Batch(C.Structure):
                 ("train_mask", C.c_void_p), ("obj_mask", C.c_void_p), ("attr_mask", C.c_void_p),
                 ("exist_mask", C.c_void_p), ("keep_att", C.c_void_p), ("keep_joint", C.c_void_p),
                 ("keep_joint2", C.c_void_p), ("live_rows", C.c_void_p), ("noise", C.c_void_p), ("keep_tile", C.c_void_p),
-                ("keep_word", C.c_void_p), ("answer_intseq", C.c_void_p), ("answer_intseq_len", C.c_void_p)]
+                ("keep_word", C.c_void_p), ("answer_intseq", C.c_void_p), ("answer_intseq_len", C.c_void_p),
+                ("keep_seed", C.c_uint64), ("keep_att_off", C.c_uint64), ("keep_joint_off", C.c_uint64),
+                ("keep_joint2_off", C.c_uint64), ("keep_tile_off", C.c_uint64), ("keep_word_off", C.c_uint64),
+                ("keep_seeded", C.c_int32)]
+
+
+# VQA_KEEP_SITE_*: bits of Batch.keep_seeded, by the name of the site's mask pointer / offset member
+KEEP_SITE = {"keep_att": 1, "keep_joint": 2, "keep_joint2": 4, "keep_tile": 8, "keep_word": 16}
 
 
 class PtDims(C.Structure):
@@ -143,7 +150,7 @@ class SoftmaxPair(C.Structure):
                 ("dzv", C.c_void_p), ("dzl", C.c_void_p)]
 
 
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_P, _I, _L, _F, _U = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); every symbol declared in include/vqa_hot.h
 SIGNATURES = {
@@ -231,6 +238,11 @@ SIGNATURES = {
     "vqa_attn_pool_bwd_ds": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_bwd_ds_v16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_ln_relu_att_bwd": (_I, [_P, _P, _P, _P, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_fwd_seeded": (_I, [_P, _P, _P, _I, _P, _P, _P, _U, _U, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_bwd_seeded": (_I, [_P, _P, _P, _P, _I, _P, _P, _U, _U, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_ln_act_fwd_seeded": (_I, [_P, _P, _P, _U, _U, _F, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "vqa_ln_act_bwd_seeded": (_I, [_P, _P, _P, _P, _P, _P, _U, _U, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "vqa_ln_relu_att_bwd_seeded": (_I, [_P, _P, _P, _U, _U, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
     "vqa_colsum_vtail_workspace_floats": (_L, [_I, _I]),
     "vqa_colsum_vtail": (_I, [_P] * 5 + [_I, _I] + [_P] * 6 + [_L, _P]),
     "vqa_loss_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _I, _I, _P]),

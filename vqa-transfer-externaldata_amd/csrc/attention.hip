@@ -53,12 +53,12 @@ template <> struct VMem<uint16_t> {
 // 512 threads: twice the waves (and loads in flight) per sample of the 256-thread form; the kernel is a
 // pure stream over v, the keep mask and V (~480 KB per sample)
 constexpr int FWD_THREADS = 512;
-template <typename VT>
+template <typename VT, int KP = KEEP_BYTES, typename... KS>
 __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
     const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
-    int H, int D, int rep) {
+    int H, int D, int rep, KS... ks) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[H] | s[R]
     float* qw = lds;
     float* s = lds + H;
@@ -79,7 +79,13 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
         for (int hu = lane; hu < H4; hu += 64) {
             const float4 x = reinterpret_cast<const float4*>(vr)[hu];
             const float4 q = reinterpret_cast<const float4*>(qw)[hu];
-            if (mb != nullptr) {
+            if constexpr (KP == KEEP_SEEDED) {
+                const KeepSeed sd = keep_seed_of(ks...);
+                const uchar4 m = keep_uchar4(keep_word4(sd.key, sd.word0 + ((uint64_t)b * R + r) * H4 + hu, sd.thr));
+                // (the explicit form's two branches share ONE add, `acc += masked ? sum * inv_keep : sum`, so hipcc rounds the
+                // product there; alone in its loop it would become fma(sum, inv_keep, acc) -- other bits)
+                acc += mul_rounded(x.x * q.x * m.x + x.y * q.y * m.y + x.z * q.z * m.z + x.w * q.w * m.w, inv_keep);
+            } else if (mb != nullptr) {
                 const uchar4 m = reinterpret_cast<const uchar4*>(mb + (int64_t)r * H)[hu];
                 acc += (x.x * q.x * m.x + x.y * q.y * m.y + x.z * q.z * m.z + x.w * q.w * m.w) * inv_keep;
             } else {
@@ -147,10 +153,11 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
 constexpr int FAST_PF = VQA_ATTN_PF, FAST_POOL_BATCH = VQA_ATTN_POOL_BATCH;
 
 // scores of CNT rows (row0, row0 + 8, ...) of one wave: every load of the batch is issued before the first use
-template <int H4L, int CNT, bool MASK>
+// (KEEP_SEEDED: sq.word0 = the word index of this query's mask)
+template <int H4L, int CNT, int KP, typename... KS>
 __device__ __forceinline__ void attn_score_rows(const f32x4v* __restrict__ vb4, const unsigned* __restrict__ mb4,
                                                 const f32x4v* qw4, float* s, int R, int row0, float inv_keep, float bias0,
-                                                int lane, bool sync_first) {
+                                                int lane, bool sync_first, KS... sq) {
     constexpr int H4 = H4L * 64;
     f32x4v x[CNT][H4L];
     unsigned m[CNT][H4L];
@@ -160,7 +167,11 @@ __device__ __forceinline__ void attn_score_rows(const f32x4v* __restrict__ vb4, 
 #pragma unroll
         for (int k = 0; k < H4L; ++k) {
             x[i][k] = vb4[(int64_t)r * H4 + lane + 64 * k];
-            if (MASK) m[i][k] = mb4[(int64_t)r * H4 + lane + 64 * k];
+            if (KP == KEEP_BYTES) m[i][k] = mb4[(int64_t)r * H4 + lane + 64 * k];
+            if constexpr (KP == KEEP_SEEDED) {
+                const KeepSeed sd = keep_seed_of(sq...);
+                m[i][k] = keep_word4(sd.key, sd.word0 + (uint64_t)r * H4 + lane + 64 * k, sd.thr);
+            }
         }
     }
     if (sync_first) __syncthreads();                 // qw is complete
@@ -170,7 +181,7 @@ __device__ __forceinline__ void attn_score_rows(const f32x4v* __restrict__ vb4, 
 #pragma unroll
         for (int k = 0; k < H4L; ++k) {
             const f32x4v q = qw4[lane + 64 * k];
-            if (MASK) {
+            if (KP != KEEP_NONE) {
                 const unsigned mm = m[i][k];
                 acc += (x[i][k].x * q.x * (float)(mm & 0xFFu) + x[i][k].y * q.y * (float)((mm >> 8) & 0xFFu) +
                         x[i][k].z * q.z * (float)((mm >> 16) & 0xFFu) + x[i][k].w * q.w * (float)(mm >> 24)) * inv_keep;
@@ -183,12 +194,12 @@ __device__ __forceinline__ void attn_score_rows(const f32x4v* __restrict__ vb4, 
     }
 }
 
-template <int H4L, int D4T, bool MASK, typename VT = float>
+template <int H4L, int D4T, int KP, typename VT = float, typename... KS>
 __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
     const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
-    int rep) {
+    int rep, KS... ks) {
     constexpr int H = H4L * 256, D = D4T * 2048, D4 = D / 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[H] | s[R]
     float* qw = lds;
@@ -196,7 +207,7 @@ __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // b = query index
     const int mem = b / rep;
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
-    const unsigned* mb4 = MASK ? reinterpret_cast<const unsigned*>(keepmask + (int64_t)b * R * H) : nullptr;
+    const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + (int64_t)b * R * H) : nullptr;
     const VT* Vb = V + (int64_t)mem * R * D;
 
     // (a) first rows of this thread's V columns
@@ -211,8 +222,15 @@ __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
 
     // (b) scores: wave `wave` owns rows wave + 8 i, i < 5 (R <= 40)
     const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
-    attn_score_rows<H4L, 3, MASK>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
-    attn_score_rows<H4L, 2, MASK>(vb4, mb4, qw4, s, R, wave + 24, inv_keep, bias0, lane, false);
+    if constexpr (KP == KEEP_SEEDED) {
+        KeepSeed sq = keep_seed_of(ks...);
+        sq.word0 += (uint64_t)b * R * (H / 4);
+        attn_score_rows<H4L, 3, KP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
+        attn_score_rows<H4L, 2, KP>(vb4, mb4, qw4, s, R, wave + 24, inv_keep, bias0, lane, false, sq);
+    } else {
+        attn_score_rows<H4L, 3, KP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
+        attn_score_rows<H4L, 2, KP>(vb4, mb4, qw4, s, R, wave + 24, inv_keep, bias0, lane, false);
+    }
     __syncthreads();
 
     if (wave == 0) {
@@ -478,12 +496,13 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel
 // phase gives every float4 column of v to TWO threads that take alternate rows (dv rows are
 // independent; the per-query column sums are combined through LDS).
 constexpr int BWD_THREADS = 512;
-template <int REP, typename VT = float>
+template <int REP, typename VT = float, int KP = KEEP_BYTES, typename... KS>
 __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
     const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
     const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
-    float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, int D, int rep) {
+    float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, int D, int rep, KS... ks) {
+    static_assert(KP != KEEP_SEEDED || REP == 1, "seeded keep bits: one query per memory");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[D] | ds[REP][R] | comb[REP][H]
     float* dp = lds;
     float* ds = lds + D;
@@ -554,7 +573,12 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
                     if (j < rep) {
                         const float d = ds[j * R + r];
                         float4 g = make_float4(d, d, d, d);
-                        if (keepmask != nullptr) {
+                        if constexpr (KP == KEEP_SEEDED) {
+                            const KeepSeed sd = keep_seed_of(ks...);
+                            const uchar4 m =
+                                keep_uchar4(keep_word4(sd.key, sd.word0 + ((uint64_t)(mem * rep + j) * R + r) * H4 + hu, sd.thr));
+                            g.x *= m.x * inv_keep; g.y *= m.y * inv_keep; g.z *= m.z * inv_keep; g.w *= m.w * inv_keep;
+                        } else if (keepmask != nullptr) {
                             const uchar4 m =
                                 reinterpret_cast<const uchar4*>(keepmask + ((int64_t)(mem * rep + j) * R + r) * H)[hu];
                             g.x *= m.x * inv_keep; g.y *= m.y * inv_keep; g.z *= m.z * inv_keep; g.w *= m.w * inv_keep;
@@ -599,14 +623,15 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
 // the dv phase keeps four rows (+ their REP mask words) per thread in flight.  Same per-lane summation order.
 // DD = 1024 (REP 5 only is dispatched): the adapted memory of the pre-training model; D4 is then half a workgroup, so
 // half of the threads stage dpooled and a wave's V row is 4 float4 per lane instead of 8.
-template <int REP, bool MASK, int DD = 2048, typename VT = float>
+template <int REP, int KP, int DD = 2048, typename VT = float, typename... KS>
 __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
     const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
-    float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H) {
+    float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, KS... ks) {
     constexpr int D = DD, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64, RB = 4;
     static_assert(REP <= NW, "one softmax wave per query");
+    static_assert(KP != KEEP_SEEDED || REP == 1, "seeded keep bits: one query per memory");
     static_assert(D4 <= BWD_THREADS && D4 % 64 == 0, "dpooled is staged with one float4 per thread");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[REP][D] | ds[REP][40] | comb[REP][H]
     float* ds = lds + REP * D;
@@ -669,7 +694,7 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     const int H4 = H / 4;
     const int half = threadIdx.x / (BWD_THREADS / 2), tcol = threadIdx.x % (BWD_THREADS / 2);
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
-    const unsigned* mk4 = MASK ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
+    const unsigned* mk4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
     f32x4v* dv4 = reinterpret_cast<f32x4v*>(dv + (int64_t)mem * R * H);
     for (int hu0 = 0; hu0 < H4; hu0 += BWD_THREADS / 2) {       // H == 1024: one pass, every thread has a column
         const int hu = hu0 + tcol;
@@ -687,9 +712,13 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
             for (int i = 0; i < RB; ++i) {
                 const int r = min(rb + 2 * i, R - 1);
                 x[i] = vb4[(int64_t)r * H4 + hu];
-                if (MASK) {
+                if (KP == KEEP_BYTES) {
 #pragma unroll
                     for (int j = 0; j < REP; ++j) m[i][j] = mk4[((int64_t)j * R + r) * H4 + hu];
+                }
+                if constexpr (KP == KEEP_SEEDED) {      // (REP == 1: the mask of query q0)
+                    const KeepSeed sd = keep_seed_of(ks...);
+                    m[i][0] = keep_word4(sd.key, sd.word0 + ((uint64_t)q0 * R + r) * H4 + hu, sd.thr);
                 }
             }
 #pragma unroll
@@ -701,7 +730,7 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
                 for (int j = 0; j < REP; ++j) {
                     const float d = ds[j * 40 + r];
                     f32x4v g = (f32x4v)(d);
-                    if (MASK) {
+                    if (KP != KEEP_NONE) {
                         const unsigned mm = m[i][j];
                         g.x *= (float)(mm & 0xFFu) * inv_keep; g.y *= (float)((mm >> 8) & 0xFFu) * inv_keep;
                         g.z *= (float)((mm >> 16) & 0xFFu) * inv_keep; g.w *= (float)(mm >> 24) * inv_keep;
@@ -805,11 +834,11 @@ constexpr bool v_is_f32() { return sizeof(VT) == sizeof(float); }
 template <typename VT>
 int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
                  const uint8_t* keepmask, float keep_prob, float* att, float* pooled, int B, int rep, int R, int H, int D,
-                 void* stream);
+                 void* stream, const KeepSeed* sd = nullptr);
 template <typename VT>
 int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
                  const uint8_t* keepmask, float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
-                 int R, int H, int D, void* stream);
+                 int R, int H, int D, void* stream, const KeepSeed* sd = nullptr);
 
 }  // namespace
 
@@ -843,7 +872,7 @@ namespace {
 template <typename VT>
 int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
                  const uint8_t* keepmask, float keep_prob, float* att, float* pooled, int B, int rep, int R, int H, int D,
-                 void* stream) {
+                 void* stream, const KeepSeed* sd) {      // sd: the keep bits come from the stream (rep == 1, keepmask NULL)
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
@@ -854,7 +883,7 @@ int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb
     VQA_REQUIRE(keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0, VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
     const size_t lds = (size_t)(H + R) * sizeof(float);
-    const float ik = keepmask ? 1.f / keep_prob : 1.f;
+    const float ik = (keepmask || sd) ? 1.f / keep_prob : 1.f;
     hipStream_t st = (hipStream_t)stream;
     const bool fast = g_attn_fast && (rep == 1 || rep == 5 || g_attn_fast > 1) && R <= 40 && H % 256 == 0 && H <= 1024 && D % 2048 == 0 && D <= 4096 &&
                       vqa_aligned16(qv) && vqa_aligned16(w);
@@ -902,11 +931,14 @@ int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb
     if (fast) {
 #define VQA_ATTN_FAST(h4l, d4t)                                                                                         \
     do {                                                                                                                \
-        if (keepmask != nullptr)                                                                                        \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, true, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
+        if (sd != nullptr)                                                                                              \
+            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, KEEP_SEEDED, VT, KeepSeed>), dim3(B * rep),         \
+                               dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep, *sd); \
+        else if (keepmask != nullptr)                                                                                   \
+            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, KEEP_BYTES, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
                                qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep);                                  \
         else                                                                                                            \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, false, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
+            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, KEEP_NONE, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
                                qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep);                                  \
     } while (0)
         const int h4l = H / 256, d4t = D / 2048;
@@ -918,6 +950,9 @@ int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb
             else if (h4l == 3) VQA_ATTN_FAST(3, 2); else VQA_ATTN_FAST(4, 2);
         }
 #undef VQA_ATTN_FAST
+    } else if (sd != nullptr) {
+        hipLaunchKernelGGL((attn_pool_fwd_kernel<VT, KEEP_SEEDED, KeepSeed>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V,
+                           nb, w, bias, keepmask, ik, att, pooled, R, H, D, rep, *sd);
     } else {
         hipLaunchKernelGGL(attn_pool_fwd_kernel<VT>, dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias,
                            keepmask, ik, att, pooled, R, H, D, rep);
@@ -953,7 +988,7 @@ namespace {
 template <typename VT>
 int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
                  const uint8_t* keepmask, float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
-                 int R, int H, int D, void* stream) {
+                 int R, int H, int D, void* stream, const KeepSeed* sd) {
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
@@ -965,7 +1000,7 @@ int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT
                 VQA_ERR_ALIGN);
     VQA_REQUIRE(keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0, VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
-    const float ik = keepmask ? 1.f / keep_prob : 1.f;
+    const float ik = (keepmask || sd) ? 1.f / keep_prob : 1.f;
     hipStream_t st = (hipStream_t)stream;
     auto lds_for = [&](int REPt) { return (size_t)(D + ((REPt * R + 3) / 4) * 4 + REPt * H) * sizeof(float); };
     VQA_REQUIRE(lds_for(rep == 1 ? 1 : rep <= 5 ? 5 : 8) <= 64 * 1024, VQA_ERR_UNSUPPORTED);
@@ -974,8 +1009,11 @@ int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT
 #define VQA_ATTN_BWD_FAST(r, mk)                                                                                       \
     hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<r, mk, 2048, VT>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, \
                        keepmask, ik, dv, dqv, part_dw, part_db, R, H)
-        if (rep == 1) { if (keepmask) VQA_ATTN_BWD_FAST(1, true); else VQA_ATTN_BWD_FAST(1, false); }
-        else if constexpr (v_is_f32<VT>()) { if (keepmask) VQA_ATTN_BWD_FAST(5, true); else VQA_ATTN_BWD_FAST(5, false); }
+        if (rep == 1 && sd != nullptr)
+            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<1, KEEP_SEEDED, 2048, VT, KeepSeed>), dim3(B), dim3(BWD_THREADS), l, st,
+                               dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H, *sd);
+        else if (rep == 1) { if (keepmask) VQA_ATTN_BWD_FAST(1, KEEP_BYTES); else VQA_ATTN_BWD_FAST(1, KEEP_NONE); }
+        else if constexpr (v_is_f32<VT>()) { if (keepmask) VQA_ATTN_BWD_FAST(5, KEEP_BYTES); else VQA_ATTN_BWD_FAST(5, KEEP_NONE); }
 #undef VQA_ATTN_BWD_FAST
         VQA_CHECK_LAUNCH();
         return VQA_OK;
@@ -985,16 +1023,19 @@ int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT
             // the 1024-wide memory at 5 queries per memory; rep 1 at D 1024 stays on the generic kernel below
             const size_t l = (size_t)(5 * D + 5 * 40 + 5 * H) * sizeof(float);
             if (keepmask)
-                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, true, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
+                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, KEEP_BYTES, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
                                    V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
             else
-                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, false, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
+                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, KEEP_NONE, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
                                    V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
             VQA_CHECK_LAUNCH();
             return VQA_OK;
         }
     }
-    if (rep == 1)
+    if (rep == 1 && sd != nullptr)
+        hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT, KEEP_SEEDED, KeepSeed>), dim3(B), dim3(BWD_THREADS), lds_for(1), st, dpooled, v,
+                           qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep, *sd);
+    else if (rep == 1)
         hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT>), dim3(B), dim3(BWD_THREADS), lds_for(1), st, dpooled, v, qv, V, att, w,
                            keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
     else if constexpr (!v_is_f32<VT>())
@@ -1009,6 +1050,37 @@ int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT
     return VQA_OK;
 }
 }  // namespace
+
+// The keep bits of the score's dropout computed in the kernel instead of loaded: the kernels the explicit entry points
+// select for the shape (same route selection), instantiated with KEEP_SEEDED.  One query per memory.
+extern "C" int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int v_bf16, const int32_t* nb,
+                                        const float* w, const float* bias, uint64_t seed, uint64_t offset, float keep_prob,
+                                        float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
+    VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
+    VQA_REQUIRE_KEEP_SEED(offset, H, keep_prob);
+    VQA_REQUIRE(rep == 1, VQA_ERR_UNSUPPORTED);
+    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
+    if (v_bf16)
+        return attn_fwd_run<uint16_t>(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, nullptr, keep_prob, att, pooled, B, 1,
+                                      R, H, D, stream, &sd);
+    return attn_fwd_run<float>(v, qv, static_cast<const float*>(V), nb, w, bias, nullptr, keep_prob, att, pooled, B, 1, R, H, D,
+                               stream, &sd);
+}
+
+extern "C" int vqa_attn_pool_bwd_seeded(const float* dpooled, const float* v, const float* qv, const void* V, int v_bf16,
+                                        const float* att, const float* w, uint64_t seed, uint64_t offset, float keep_prob,
+                                        float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H,
+                                        int D, void* stream) {
+    VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
+    VQA_REQUIRE_KEEP_SEED(offset, H, keep_prob);
+    VQA_REQUIRE(rep == 1, VQA_ERR_UNSUPPORTED);
+    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
+    if (v_bf16)
+        return attn_bwd_run<uint16_t>(dpooled, v, qv, static_cast<const uint16_t*>(V), att, w, nullptr, keep_prob, dv, dqv,
+                                      part_dw, part_db, B, 1, R, H, D, stream, &sd);
+    return attn_bwd_run<float>(dpooled, v, qv, static_cast<const float*>(V), att, w, nullptr, keep_prob, dv, dqv, part_dw,
+                               part_db, B, 1, R, H, D, stream, &sd);
+}
 
 // The chain v_linear_v's LayerNorm -> attention score and its gradient at the one shape of the register-resident
 // LayerNorm kernels and the fast attention kernels: one query per memory, 36 regions, 1024 hidden units, 2048 features.

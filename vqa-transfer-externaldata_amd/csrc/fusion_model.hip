@@ -445,17 +445,90 @@ bool dims_ok(const vqa_dims_t* d) {
 // K of pooled_linear_l = width of what the attention pools: v_adapt [R,H] for vlmap_answer_adapt, V_ft [R,D] otherwise
 inline int64_t pooled_dim(const vqa_dims_t& d) { return d.model_type == VQA_MODEL_ADAPT ? d.H : d.D; }
 
+// One dropout site of the step (VQA_KEEP_SITE_*): the explicit mask of the batch (or NULL: no dropout), or, where the
+// site's bit of vqa_batch_t.keep_seeded is set, the stream position its bits are drawn from inside the consuming kernels.
+// Every mask site of the forward and the backward resolves through keep_site() and calls the op through the members below,
+// which pick the explicit or the seeded entry point; the batch struct carries everything, nothing is remembered here.
+struct KeepSite {
+    const uint8_t* mask;
+    bool seeded;
+    uint64_t seed, off;
+
+    int ln_relu_fwd(const float* pre, const float* gamma, const float* beta, float keep_prob, float* y, float* mean, float* rstd,
+                    int G, int rows, int N, void* st) const {
+        if (seeded) return vqa_ln_act_fwd_seeded(pre, gamma, beta, seed, off, keep_prob, y, mean, rstd, G, rows, N, 0, st);
+        return vqa_ln_relu_fwd(pre, gamma, beta, mask, keep_prob, y, mean, rstd, G, rows, N, st);
+    }
+    int ln_relu_bwd(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                    float keep_prob, float* dpre, float* pdg, float* pdb, float* pdbias, int G, int rows, int N, void* st) const {
+        if (seeded)
+            return vqa_ln_act_bwd_seeded(dy, pre, mean, rstd, gamma, beta, seed, off, keep_prob, dpre, pdg, pdb, pdbias, G, rows, N,
+                                         0, st);
+        return vqa_ln_relu_bwd(dy, pre, mean, rstd, gamma, beta, mask, keep_prob, dpre, pdg, pdb, pdbias, G, rows, N, st);
+    }
+    // V: float, or raw bf16 patterns (v16)
+    int attn_pool_fwd(const float* v, const float* qv, const void* V, bool v16, const int32_t* nb, const float* w, const float* bias,
+                      float keep_prob, float* att, float* pooled, int B, int R, int H, int D, void* st) const {
+        if (seeded) return vqa_attn_pool_fwd_seeded(v, qv, V, v16 ? 1 : 0, nb, w, bias, seed, off, keep_prob, att, pooled, B, 1, R, H, D, st);
+        if (v16)
+            return vqa_attn_pool_fwd_v16(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, mask, keep_prob, att, pooled, B, R, H, D, st);
+        return vqa_attn_pool_fwd(v, qv, static_cast<const float*>(V), nb, w, bias, mask, keep_prob, att, pooled, B, R, H, D, st);
+    }
+    int attn_pool_bwd(const float* dpooled, const float* v, const float* qv, const void* V, bool v16, const float* att, const float* w,
+                      float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int R, int H, int D,
+                      void* st) const {
+        if (seeded)
+            return vqa_attn_pool_bwd_seeded(dpooled, v, qv, V, v16 ? 1 : 0, att, w, seed, off, keep_prob, dv, dqv, part_dw, part_db, B, 1,
+                                            R, H, D, st);
+        if (v16)
+            return vqa_attn_pool_bwd_v16(dpooled, v, qv, static_cast<const uint16_t*>(V), att, w, mask, keep_prob, dv, dqv, part_dw,
+                                         part_db, B, R, H, D, st);
+        return vqa_attn_pool_bwd(dpooled, v, qv, static_cast<const float*>(V), att, w, mask, keep_prob, dv, dqv, part_dw, part_db, B, R,
+                                 H, D, st);
+    }
+    int ln_relu_att_bwd(const float* ds, const float* qv, const float* w, float keep_prob, const float* pre, const float* mean,
+                        const float* rstd, const float* gamma, const float* beta, float* dpre, float* pdg, float* pdb, float* pdbias,
+                        float* dqv, float* part_dw, int B, int R, int H, int D, void* st) const {
+        if (seeded)
+            return vqa_ln_relu_att_bwd_seeded(ds, qv, w, seed, off, keep_prob, pre, mean, rstd, gamma, beta, dpre, pdg, pdb, pdbias, dqv,
+                                              part_dw, B, 1, R, H, D, st);
+        return vqa_ln_relu_att_bwd(ds, qv, w, mask, keep_prob, pre, mean, rstd, gamma, beta, dpre, pdg, pdb, pdbias, dqv, part_dw, B, 1, R,
+                                   H, D, st);
+    }
+};
+const KeepSite NO_KEEP = {nullptr, false, 0, 0};      // a layer without dropout
+
+KeepSite keep_site(const vqa_batch_t* bt, int site) {
+    const bool sd = (bt->keep_seeded & site) != 0;
+    switch (site) {
+        case VQA_KEEP_SITE_ATT: return {bt->keep_att, sd, bt->keep_seed, bt->keep_att_off};
+        case VQA_KEEP_SITE_JOINT: return {bt->keep_joint, sd, bt->keep_seed, bt->keep_joint_off};
+        case VQA_KEEP_SITE_JOINT2: return {bt->keep_joint2, sd, bt->keep_seed, bt->keep_joint2_off};
+        case VQA_KEEP_SITE_TILE: return {bt->keep_tile, sd, bt->keep_seed, bt->keep_tile_off};
+        default: return {bt->keep_word, sd, bt->keep_seed, bt->keep_word_off};
+    }
+}
+// a seeded site has no mask buffer, and no bit beyond the five sites is set
+bool keep_sites_ok(const vqa_batch_t* bt) {
+    if (bt->keep_seeded & ~31) return false;
+    for (int site = 1; site <= VQA_KEEP_SITE_WORD; site <<= 1) {
+        const KeepSite k = keep_site(bt, site);
+        if (k.seeded && k.mask != nullptr) return false;
+    }
+    return true;
+}
+
 // FC + LN + ReLU forward (modules.fc_layer, vlmap/modules.py:630-650)
 int fc_ln_relu_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, const vqa_fc_t& p, int rows,
-                   const char* pre, const char* y, const char* mean, const char* rstd, const uint8_t* keep,
+                   const char* pre, const char* y, const char* mean, const char* rstd, const KeepSite& keep,
                    float keep_prob) {
     {
         ProbeScope ps(rows > 1 ? "v_linear_v.fwd_gemm" : "fc.fwd_gemm", c.st);
         TRY(gemm_x(c, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
     }
     ProbeScope ps(rows > 1 ? "v_linear_v.ln_fwd" : "fc.ln_fwd", c.st);
-    return vqa_ln_relu_fwd(c.f(pre), p.gamma, p.beta, keep, keep_prob, c.f(y), c.f(mean), c.f(rstd), (int)(M / rows),
-                           rows, (int)N, c.st);
+    return keep.ln_relu_fwd(c.f(pre), p.gamma, p.beta, keep_prob, c.f(y), c.f(mean), c.f(rstd), (int)(M / rows), rows, (int)N,
+                            c.st);
 }
 
 // the FC half of the backward once d_pre is known: parameter gradients from the per-group partials (g.w == NULL => frozen
@@ -483,14 +556,14 @@ int fc_bwd_tail(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, c
 // grads (g.w == NULL => frozen layer); optional dx = d_pre * W^T (+ dx_add).
 int fc_ln_relu_bwd(const Ctx& c, const float* dy, const float* x, int64_t M, int64_t K, int64_t N, const vqa_fc_t& p,
                    const vqa_fc_t* g, int rows, const char* pre, const char* mean, const char* rstd,
-                   const uint8_t* keep, float keep_prob, const char* d_pre, float* dx, bool dx_accumulate) {
+                   const KeepSite& keep, float keep_prob, const char* d_pre, float* dx, bool dx_accumulate) {
     const bool train = g != nullptr && g->w != nullptr;
     const int64_t G = M / rows;
     {
         ProbeScope ps(rows > 1 ? "v_linear_v.ln_bwd" : "fc.ln_bwd", c.st);
-        TRY(vqa_ln_relu_bwd(dy, c.f(pre), c.f(mean), c.f(rstd), p.gamma, p.beta, keep, keep_prob, c.f(d_pre),
-                            train ? c.part(0) : nullptr, train ? c.part(1) : nullptr,
-                            train ? c.part(2) : nullptr, (int)G, rows, (int)N, c.st));
+        TRY(keep.ln_relu_bwd(dy, c.f(pre), c.f(mean), c.f(rstd), p.gamma, p.beta, keep_prob, c.f(d_pre),
+                             train ? c.part(0) : nullptr, train ? c.part(1) : nullptr,
+                             train ? c.part(2) : nullptr, (int)G, rows, (int)N, c.st));
     }
     return fc_bwd_tail(c, x, M, K, N, p, g, rows, c.f(d_pre), c.part(0), c.part(1), c.part(2), dx, dx_accumulate);
 }
@@ -544,14 +617,14 @@ int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt) 
     TRY(vqa_bi_outputs_fwd(c.f("hs"), c.f("hs_bw"), bt->q_intseq_len, c.f("q_L_map"), c.f("q_L_ft"), (int)B, (int)T, (int)h, c.st));
     // keys: fc_layer on [B,T,H] -- LayerNorm over the whole [T,H] block of a question, padded positions included
     TRY(fc_ln_relu_fwd(c, c.f("q_L_map"), B * T, H, H, P->q_att_key, (int)T, "pre_key", "q_att_key", "mean_key", "rstd_key",
-                       nullptr, 1.f));
+                       NO_KEEP, 1.f));
     TRY(fc_ln_relu_fwd(c, c.f("q_L_ft"), B, H, H, P->q_att_query, 1, "pre_query", "q_att_query", "mean_query", "rstd_query",
-                       nullptr, 1.f));
-    TRY(fc_ln_relu_fwd(c, c.f("e2"), B * T, W, H, P->v_word_fc, (int)T, "pre_vw", "q_v_ft", "mean_vw", "rstd_vw", nullptr, 1.f));
+                       NO_KEEP, 1.f));
+    TRY(fc_ln_relu_fwd(c, c.f("e2"), B * T, W, H, P->v_word_fc, (int)T, "pre_vw", "q_v_ft", "mean_vw", "rstd_vw", NO_KEEP, 1.f));
     ProbeScope ps("attn_pool.fwd", c.st);
-    return vqa_attn_pool_fwd(c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), bt->q_intseq_len, P->word_score.w,
-                             P->word_score.b, bt->keep_word, d.keep_att, c.f("w_att_score"), c.f("pooled_q_v"), (int)B, (int)T,
-                             (int)H, (int)H, c.st);
+    return keep_site(bt, VQA_KEEP_SITE_WORD)
+        .attn_pool_fwd(c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), false, bt->q_intseq_len, P->word_score.w, P->word_score.b,
+                       d.keep_att, c.f("w_att_score"), c.f("pooled_q_v"), (int)B, (int)T, (int)H, (int)H, c.st);
 }
 
 // everything between d(pooled_q_v) / d(q_L_ft) and the two recurrences' inputs: word attention, v_word_fc (+ the second
@@ -561,9 +634,10 @@ int bi_question_bwd_head(const Ctx& c, const vqa_params_t* P, const vqa_params_t
     const int64_t B = d.B, H = d.H, T = d.T, W = d.W;
     {
         ProbeScope ps("attn_pool.bwd", c.st);
-        TRY(vqa_attn_pool_bwd(c.f("d_pooled_qv"), c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), c.f("w_att_score"),
-                              P->word_score.w, bt->keep_word, d.keep_att, c.f("d_key"), c.f("d_query"), c.f("part_wdw"),
-                              c.f("part_wdb"), (int)B, (int)T, (int)H, (int)H, c.st));
+        TRY(keep_site(bt, VQA_KEEP_SITE_WORD)
+                .attn_pool_bwd(c.f("d_pooled_qv"), c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), false, c.f("w_att_score"),
+                               P->word_score.w, d.keep_att, c.f("d_key"), c.f("d_query"), c.f("part_wdw"), c.f("part_wdb"), (int)B,
+                               (int)T, (int)H, (int)H, c.st));
         if (G->word_score.w != nullptr) {
             TRY(colsum(c, c.f("part_wdw"), B, H, (int)H, G->word_score.w));
             TRY(colsum(c, c.f("part_wdb"), B, 1, 1, G->word_score.b));
@@ -574,7 +648,7 @@ int bi_question_bwd_head(const Ctx& c, const vqa_params_t* P, const vqa_params_t
     const bool e2_train = G->embed2 != nullptr;
     if (G->v_word_fc.w != nullptr || e2_train)
         TRY(fc_ln_relu_bwd(c, c.f("d_qvft"), c.f("e2"), B * T, W, H, P->v_word_fc, &G->v_word_fc, (int)T, "pre_vw", "mean_vw",
-                           "rstd_vw", nullptr, 1.f, "d_pre_vw", e2_train ? c.f("d_e2") : nullptr, false));
+                           "rstd_vw", NO_KEEP, 1.f, "d_pre_vw", e2_train ? c.f("d_e2") : nullptr, false));
     if (e2_train) {      // V_WordMap: scatter-add of the batch-major slices (every position, padding included) + their norm
         ProbeScope ps("embed.bwd", c.st);
         TRY(vqa_embed_bwd_len_det(c.f("d_e2"), bt->q_intseq, nullptr, G->embed2, (int)(B * T), 1, (int)W, d.Vq,
@@ -582,9 +656,9 @@ int bi_question_bwd_head(const Ctx& c, const vqa_params_t* P, const vqa_params_t
         TRY(vqa_sumsq(c.f("d_e2"), B * T * W, nullptr, c.f("sq_e2"), c.f("sumsq_ws2"), c.L.find("sumsq_ws2")->n, c.st));
     }
     TRY(fc_ln_relu_bwd(c, c.f("d_query"), c.f("q_L_ft"), B, H, H, P->q_att_query, &G->q_att_query, 1, "pre_query", "mean_query",
-                       "rstd_query", nullptr, 1.f, "d_pre_query", dh, true));
+                       "rstd_query", NO_KEEP, 1.f, "d_pre_query", dh, true));
     return fc_ln_relu_bwd(c, c.f("d_key"), c.f("q_L_map"), B * T, H, H, P->q_att_key, &G->q_att_key, (int)T, "pre_key", "mean_key",
-                          "rstd_key", nullptr, 1.f, "d_pre_key", c.f("d_qmap"), false);
+                          "rstd_key", NO_KEEP, 1.f, "d_pre_key", c.f("d_qmap"), false);
 }
 
 // phase 2: both BPTTs, the gradient wrt the looked-up embeddings, LearnGloVe's scatter-add and the slice norm
@@ -814,12 +888,12 @@ int fwd_visual(const Step& s) {
                             cv.f("mean_v"), cv.f("rstd_v"), (int)B, (int)R, (int)H, cv.st));
     } else {
         TRY(fc_ln_relu_fwd(cv, cv.f("V_ft"), B * R, D, H, P->v_linear_v, (int)R, "pre_v", "v_linear_v", "mean_v", "rstd_v",
-                           nullptr, 1.f));
+                           NO_KEEP, 1.f));
     }
     if (s.mt == VQA_MODEL_ADAPT) {     // v_adapt: a second FC + LN[R,H] + ReLU on the same V_ft (:132-135)
         VQA_REQUIRE(P->v_adapt.w != nullptr && P->v_adapt.gamma != nullptr, VQA_ERR_ARG);
         TRY(fc_ln_relu_fwd(cv, cv.f("V_ft"), B * R, D, H, P->v_adapt, (int)R, "pre_va", "v_adapt", "mean_va", "rstd_va",
-                           nullptr, 1.f));
+                           NO_KEEP, 1.f));
     }
     return VQA_OK;
 }
@@ -919,20 +993,18 @@ int fwd_question_code(Step& s) {
 
 // a5
 int fwd_q_linear_v(const Step& s) {
-    return fc_ln_relu_fwd(s.c, s.qv_in, s.B, s.H, s.H, s.P->q_linear_v, 1, "pre_qv", "q_linear_v", "mean_qv", "rstd_qv", nullptr, 1.f);
+    return fc_ln_relu_fwd(s.c, s.qv_in, s.B, s.H, s.H, s.P->q_linear_v, 1, "pre_qv", "q_linear_v", "mean_qv", "rstd_qv", NO_KEEP, 1.f);
 }
 
 // a6 + a7: Hadamard attention and pooling (vlmap_answer_adapt pools v_adapt [R,H] instead of V_ft [R,D])
 int fwd_attention(const Step& s) {
     const Ctx& c = s.c;
     ProbeScope ps("attn_pool.fwd", c.st);
-    if (feat16(s.d))
-        return vqa_attn_pool_fwd_v16(c.f("v_linear_v"), c.f("q_linear_v"), c.u16("V_ft"), c.i32("num_V_ft"), s.P->score.w,
-                                     s.P->score.b, s.bt->keep_att, s.d.keep_att, c.f("att_score"), c.f("pooled_V_ft"),
-                                     (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
-    return vqa_attn_pool_fwd(c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
-                             c.i32("num_V_ft"), s.P->score.w, s.P->score.b, s.bt->keep_att, s.d.keep_att, c.f("att_score"),
-                             c.f("pooled_V_ft"), (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
+    const bool v16 = feat16(s.d);
+    const void* V = v16 ? (const void*)c.u16("V_ft") : (const void*)c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft");
+    return keep_site(s.bt, VQA_KEEP_SITE_ATT)
+        .attn_pool_fwd(c.f("v_linear_v"), c.f("q_linear_v"), V, v16, c.i32("num_V_ft"), s.P->score.w, s.P->score.b, s.d.keep_att,
+                       c.f("att_score"), c.f("pooled_V_ft"), (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
 }
 
 // a8: pooled_linear_l and q_linear_l; the paired form also leaves their product in joint_in
@@ -943,8 +1015,8 @@ int fwd_linear_l(Step& s) {
     s.pair = ln_pair_ok(s.d, P);
     if (!s.pair) {
         TRY(fc_ln_relu_fwd(c, c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, 1, "pre_pl", "pooled_linear_l", "mean_pl",
-                           "rstd_pl", nullptr, 1.f));
-        return fc_ln_relu_fwd(c, s.lin_in, B, H, H, P->q_linear_l, 1, "pre_ll", "l_linear_l", "mean_ll", "rstd_ll", nullptr, 1.f);
+                           "rstd_pl", NO_KEEP, 1.f));
+        return fc_ln_relu_fwd(c, s.lin_in, B, H, H, P->q_linear_l, 1, "pre_ll", "l_linear_l", "mean_ll", "rstd_ll", NO_KEEP, 1.f);
     }
     {
         ProbeScope ps("fc.fwd_gemm", c.st);
@@ -969,16 +1041,16 @@ int fwd_joint(const Step& s) {
         // on l_linear_l, each FC + LN + ReLU + dropout .5 ("joint" holds v_joint)
         VQA_REQUIRE(P->joint2.w != nullptr && P->head2.w != nullptr, VQA_ERR_ARG);
         TRY(fc_ln_relu_fwd(c, c.f("pooled_linear_l"), B, H, 2 * H, P->joint_fc, 1, "pre_j", "joint", "mean_j", "rstd_j",
-                           bt->keep_joint, s.d.keep_joint));
+                           keep_site(bt, VQA_KEEP_SITE_JOINT), s.d.keep_joint));
         return fc_ln_relu_fwd(c, c.f("l_linear_l"), B, H, 2 * H, P->joint2, 1, "pre_jl", "l_joint", "mean_jl", "rstd_jl",
-                              bt->keep_joint2, s.d.keep_joint);
+                              keep_site(bt, VQA_KEEP_SITE_JOINT2), s.d.keep_joint);
     }
     if (!s.pair) {
         ProbeScope ps("eltwise", c.st);
         TRY(vqa_mul(c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("joint_in"), B * H, c.st));
     }
-    return fc_ln_relu_fwd(c, c.f("joint_in"), B, H, 2 * H, P->joint_fc, 1, "pre_j", "joint", "mean_j", "rstd_j", bt->keep_joint,
-                          s.d.keep_joint);
+    return fc_ln_relu_fwd(c, c.f("joint_in"), B, H, 2 * H, P->joint_fc, 1, "pre_j", "joint", "mean_j", "rstd_j",
+                          keep_site(bt, VQA_KEEP_SITE_JOINT), s.d.keep_joint);
 }
 
 // a10: the answer head
@@ -1043,8 +1115,9 @@ int fwd_loss(const Step& s, int want_dz) {
         TRY(vqa_tile_mul_fwd(c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("tile_in"), (int)B, (int)M, (int)H, c.st));
         TRY(gemm(c, 0, 0, B * M, 2 * H, H, c.f("tile_in"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("pre_tj"), (int)(2 * H),
                  P->joint_fc.b));
-        TRY(vqa_ln_relu_fwd(c.f("pre_tj"), P->joint_fc.gamma, P->joint_fc.beta, bt->keep_tile, s.d.keep_joint,
-                            c.f("tile_joint"), c.f("mean_tj"), c.f("rstd_tj"), (int)B, (int)M, (int)(2 * H), c.st));
+        TRY(keep_site(bt, VQA_KEEP_SITE_TILE)
+                .ln_relu_fwd(c.f("pre_tj"), P->joint_fc.gamma, P->joint_fc.beta, s.d.keep_joint, c.f("tile_joint"), c.f("mean_tj"),
+                             c.f("rstd_tj"), (int)B, (int)M, (int)(2 * H), c.st));
         TRY(gemm(c, 0, 0, B * M, C, 2 * H, c.f("tile_joint"), (int)(2 * H), P->head.w, (int)A, c.f("tile_z"), (int)C, P->head.b));
         TRY(vqa_marginal_entropy(c.f("tile_z"), bt->train_mask, bt->exist_mask, s.d.extra_weight * s.d.inv_global_batch,
                                  c.f("marginal_prob"), c.f("extra_row"), (int)B, (int)M, (int)C, (int)C, want_dz, c.st));
@@ -1059,6 +1132,7 @@ int fwd_loss(const Step& s, int want_dz) {
 extern "C" int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_batch_t* bt,
                                   void* workspace, int64_t workspace_bytes, int want_dz, void* stream) {
     VQA_REQUIRE(dims_ok(dims) && P && bt && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(keep_sites_ok(bt), VQA_ERR_ARG);
     Step s(dims, P, nullptr, bt, workspace, stream);
     VQA_REQUIRE(workspace_bytes >= s.L.total, VQA_ERR_WORKSPACE);
     VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
@@ -1144,13 +1218,13 @@ int bwd_joint(const Step& s) {
         }
         TRY(gemm(c, 0, 1, B, 2 * H, A, c.f("dlogit"), (int)A, P->head2.w, (int)A, c.f("d_ljoint"), (int)(2 * H)));
         TRY(fc_ln_relu_bwd(c, c.f("d_joint"), c.f("pooled_linear_l"), B, H, 2 * H, P->joint_fc, &G->joint_fc, 1, "pre_j",
-                           "mean_j", "rstd_j", bt->keep_joint, s.d.keep_joint, "d_pre_j", c.f("d_pl"), false));
+                           "mean_j", "rstd_j", keep_site(bt, VQA_KEEP_SITE_JOINT), s.d.keep_joint, "d_pre_j", c.f("d_pl"), false));
         return fc_ln_relu_bwd(c, c.f("d_ljoint"), c.f("l_linear_l"), B, H, 2 * H, P->joint2, &G->joint2, 1, "pre_jl", "mean_jl",
-                              "rstd_jl", bt->keep_joint2, s.d.keep_joint, "d_pre_jl", c.f("d_ll"), false);
+                              "rstd_jl", keep_site(bt, VQA_KEEP_SITE_JOINT2), s.d.keep_joint, "d_pre_jl", c.f("d_ll"), false);
     }
     // joint_fc (dropout mask folded into the LN/ReLU backward)
     TRY(fc_ln_relu_bwd(c, c.f("d_joint"), c.f("joint_in"), B, H, 2 * H, P->joint_fc, &G->joint_fc, 1, "pre_j", "mean_j",
-                       "rstd_j", bt->keep_joint, s.d.keep_joint, "d_pre_j", c.f("d_joint_in"), false));
+                       "rstd_j", keep_site(bt, VQA_KEEP_SITE_JOINT), s.d.keep_joint, "d_pre_j", c.f("d_joint_in"), false));
     if (!s.pair) {
         ProbeScope ps("eltwise", c.st);
         TRY(vqa_mul_bwd(c.f("d_joint_in"), c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("d_pl"), c.f("d_ll"), B * H,
@@ -1168,9 +1242,9 @@ int bwd_entropy(const Step& s) {
     ProbeScope ps("ent.bwd", c.st);
     const int64_t M = s.d.num_marginal, C = s.d.ent_cols;
     TRY(gemm(c, 0, 1, B * M, 2 * H, C, c.f("tile_z"), (int)C, P->head.w, (int)A, c.f("d_tile_joint"), (int)(2 * H)));
-    TRY(vqa_ln_relu_bwd(c.f("d_tile_joint"), c.f("pre_tj"), c.f("mean_tj"), c.f("rstd_tj"), P->joint_fc.gamma,
-                        P->joint_fc.beta, s.bt->keep_tile, s.d.keep_joint, c.f("d_pre_tj"), nullptr, nullptr, nullptr,
-                        (int)B, (int)M, (int)(2 * H), c.st));
+    TRY(keep_site(s.bt, VQA_KEEP_SITE_TILE)
+            .ln_relu_bwd(c.f("d_tile_joint"), c.f("pre_tj"), c.f("mean_tj"), c.f("rstd_tj"), P->joint_fc.gamma, P->joint_fc.beta,
+                         s.d.keep_joint, c.f("d_pre_tj"), nullptr, nullptr, nullptr, (int)B, (int)M, (int)(2 * H), c.st));
     TRY(gemm(c, 0, 1, B * M, H, 2 * H, c.f("d_pre_tj"), (int)(2 * H), P->joint_fc.w, (int)(2 * H), c.f("d_tile_in"), (int)H));
     // (paired LayerNorm backward: d_ll holds only this extra gradient and is added inside that kernel)
     return vqa_tile_mul_bwd(c.f("d_tile_in"), c.f("pooled_linear_l"), c.f("d_ll"), (int)B, (int)M, (int)H, s.pair ? 0 : 1, c.st);
@@ -1185,7 +1259,7 @@ int bwd_linear_l(const Step& s) {
     const int64_t B = s.B, H = s.H, Dp = s.Dp;
     if (!s.pair)
         return fc_ln_relu_bwd(c, c.f("d_pl"), c.f("pooled_V_ft"), B, Dp, H, P->pooled_linear_l, &G->pooled_linear_l, 1, "pre_pl",
-                              "mean_pl", "rstd_pl", nullptr, 1.f, "d_pre_pl", c.f("d_pooled"), false);
+                              "mean_pl", "rstd_pl", NO_KEEP, 1.f, "d_pre_pl", c.f("d_pooled"), false);
     const bool tr_pl = G->pooled_linear_l.w != nullptr, tr_ll = G->q_linear_l.w != nullptr;
     ProbeScope ps("fc.ln_bwd", c.st);
     TRY(vqa_ln_pair_mul_bwd(c.f("d_joint_in"), s.mt == VQA_MODEL_ENT ? c.f("d_ll") : nullptr, c.f("pre_pl"), c.f("pre_ll"),
@@ -1205,7 +1279,7 @@ int q_linear_l_bwd(const Step& s, const float* x, float* dx) {
     if (s.pair)
         return fc_bwd_tail(c, x, B, H, H, s.P->q_linear_l, &s.G->q_linear_l, 1, c.f("d_pre_ll"), c.f("part_a1"), c.f("part_b1"),
                            c.f("part_c1"), dx, false);
-    return fc_ln_relu_bwd(c, c.f("d_ll"), x, B, H, H, s.P->q_linear_l, &s.G->q_linear_l, 1, "pre_ll", "mean_ll", "rstd_ll", nullptr,
+    return fc_ln_relu_bwd(c, c.f("d_ll"), x, B, H, H, s.P->q_linear_l, &s.G->q_linear_l, 1, "pre_ll", "mean_ll", "rstd_ll", NO_KEEP,
                           1.f, "d_pre_ll", dx, false);
 }
 
@@ -1298,9 +1372,10 @@ int bwd_attention(Step& s) {
         }
         {
             ProbeScope ps("v_linear_v.ln_bwd", c.st);
-            TRY(vqa_ln_relu_att_bwd(c.f("ds"), c.f("q_linear_v"), P->score.w, bt->keep_att, s.d.keep_att, c.f("pre_v"),
-                                    c.f("mean_v"), c.f("rstd_v"), P->v_linear_v.gamma, P->v_linear_v.beta, c.f("d_pre_v"), c.part(0),
-                                    c.part(1), c.part(2), c.f("d_qv"), c.f("part_dw"), (int)B, 1, (int)R, (int)H, (int)D, c.st));
+            TRY(keep_site(bt, VQA_KEEP_SITE_ATT)
+                    .ln_relu_att_bwd(c.f("ds"), c.f("q_linear_v"), P->score.w, s.d.keep_att, c.f("pre_v"), c.f("mean_v"),
+                                     c.f("rstd_v"), P->v_linear_v.gamma, P->v_linear_v.beta, c.f("d_pre_v"), c.part(0), c.part(1),
+                                     c.part(2), c.f("d_qv"), c.f("part_dw"), (int)B, (int)R, (int)H, (int)D, c.st));
             TRY(vqa_colsum_vtail(c.part(0), c.part(1), c.part(2), c.f("part_dw"), c.f("part_db"), (int)B, (int)H,
                                  G->v_linear_v.gamma, G->v_linear_v.beta, G->v_linear_v.b, G->score.w, G->score.b, c.colsum_ws(),
                                  c.colsum_ws_floats(), c.st));
@@ -1310,21 +1385,19 @@ int bwd_attention(Step& s) {
     }
     {
         ProbeScope ps("attn_pool.bwd", c.st);
-        if (feat16(s.d))
-            TRY(vqa_attn_pool_bwd_v16(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.u16("V_ft"), c.f("att_score"),
-                                      P->score.w, bt->keep_att, s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
-                                      c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
-        else
-            TRY(vqa_attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft"),
-                                  c.f("att_score"), P->score.w, bt->keep_att, s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
-                                  c.f("part_db"), (int)B, (int)R, (int)H, (int)Dp, c.st));
+        const bool v16 = feat16(s.d);
+        const void* V = v16 ? (const void*)c.u16("V_ft") : (const void*)c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft");
+        TRY(keep_site(bt, VQA_KEEP_SITE_ATT)
+                .attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), V, v16, c.f("att_score"), P->score.w,
+                               s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"), c.f("part_db"), (int)B, (int)R, (int)H,
+                               (int)Dp, c.st));
     }
     if (s.mt == VQA_MODEL_ADAPT) {
         // the pooled memory is trainable here: d v_adapt = att (x) d pooled, then LN[R,H] + ReLU + FC backward (V_ft is an
         // input: parameters only), like v_linear_v's
         TRY(vqa_outer_rows(c.f("att_score"), c.f("d_pooled"), c.f("d_va"), (int)B, (int)R, (int)H, c.st));
         TRY(fc_ln_relu_bwd(c, c.f("d_va"), c.f("V_ft"), B * R, D, H, P->v_adapt, &G->v_adapt, (int)R, "pre_va", "mean_va",
-                           "rstd_va", nullptr, 1.f, "d_pre_va", nullptr, false));
+                           "rstd_va", NO_KEEP, 1.f, "d_pre_va", nullptr, false));
     }
     if (G->score.w != nullptr) {
         ProbeScope ps("attn_pool.bwd", c.st);
@@ -1336,7 +1409,7 @@ int bwd_attention(Step& s) {
     s.forked = fork_side(c, *s.sd);
     const Ctx cv = s.side_ctx();
     TRY(fc_ln_relu_bwd(cv, cv.f("d_v"), cv.f("V_ft"), B * R, D, H, P->v_linear_v, &G->v_linear_v, (int)R, "pre_v",
-                       "mean_v", "rstd_v", nullptr, 1.f, "d_pre_v", nullptr, false));
+                       "mean_v", "rstd_v", NO_KEEP, 1.f, "d_pre_v", nullptr, false));
     return side_record(s);
 }
 
@@ -1347,12 +1420,12 @@ int bwd_q_linear_v(const Step& s) {
     if (s.mt == VQA_MODEL_BI) {
         // q_linear_v read pooled_q_v; from there back through the question self-attention into d q_L_ft (dh) / d q_L_map
         TRY(fc_ln_relu_bwd(c, c.f("d_qv"), c.f("pooled_q_v"), B, H, H, s.P->q_linear_v, &s.G->q_linear_v, 1, "pre_qv", "mean_qv",
-                           "rstd_qv", nullptr, 1.f, "d_pre_qv", c.f("d_pooled_qv"), false));
+                           "rstd_qv", NO_KEEP, 1.f, "d_pre_qv", c.f("d_pooled_qv"), false));
         return bi_question_bwd_head(c, s.P, s.G, s.bt, s.dh);
     }
     // q_linear_v: dh += ...
     return fc_ln_relu_bwd(c, c.f("d_qv"), s.h, B, H, H, s.P->q_linear_v, &s.G->q_linear_v, 1, "pre_qv", "mean_qv", "rstd_qv",
-                          nullptr, 1.f, "d_pre_qv", s.dh, true);
+                          NO_KEEP, 1.f, "d_pre_qv", s.dh, true);
 }
 
 // phase 2: GRU back-propagation through time (gate math fused into the GEMM epilogues), dx, embedding scatter-add, slice
@@ -1477,6 +1550,7 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
                                           const vqa_batch_t* bt, void* workspace, int64_t workspace_bytes,
                                           float* embed_slice_sq, int phases, void* stream) {
     VQA_REQUIRE(dims_ok(dims) && P && G && bt && workspace, VQA_ERR_ARG);
+    VQA_REQUIRE(keep_sites_ok(bt), VQA_ERR_ARG);
     Step s(dims, P, G, bt, workspace, stream);
     VQA_REQUIRE(workspace_bytes >= s.L.total, VQA_ERR_WORKSPACE);
     ProbeScope ps_all("backward", s.c.st);

@@ -32,6 +32,10 @@ struct Vec<4> {
         const uchar4 t = *reinterpret_cast<const uchar4*>(p);
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     }
+    __device__ __forceinline__ void set_mask(unsigned w) {       // the 4-byte word load_mask reads, computed (keep_word4)
+        const uchar4 t = keep_uchar4(w);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
 };
 template <>
 struct Vec<1> {
@@ -39,14 +43,16 @@ struct Vec<1> {
     __device__ __forceinline__ void load(const float* p) { v[0] = p[0]; }
     __device__ __forceinline__ void store(float* p) const { p[0] = v[0]; }
     __device__ __forceinline__ void load_mask(const uint8_t* p) { v[0] = p[0]; }
+    __device__ __forceinline__ void set_mask(unsigned) {}      // (seeded keep bits come four at a time: Vec<4> only)
 };
 
 // blockDim.x = CUt * RY ; cx = tid % CUt, ry = tid / CUt
-template <int U>
+template <int U, int KP = KEEP_BYTES, typename... KS>
 __global__ void ln_relu_fwd_kernel(const float* __restrict__ pre, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, const uint8_t* __restrict__ keepmask,
                                    float inv_keep, float* __restrict__ y, float* __restrict__ mean_out,
-                                   float* __restrict__ rstd_out, int rows, int N, int CUt, int RY, int act) {
+                                   float* __restrict__ rstd_out, int rows, int N, int CUt, int RY, int act, KS... ks) {
+    static_assert(KP != KEEP_SEEDED || U == 4, "seeded keep bits come in words of four columns");
     __shared__ float red[16];
     const int g = blockIdx.x;
     const int cx = threadIdx.x % CUt, ry = threadIdx.x / CUt;
@@ -79,12 +85,15 @@ __global__ void ln_relu_fwd_kernel(const float* __restrict__ pre, const float* _
             const int64_t off = base + (int64_t)r * N + cu * U;
             Vec<U> x, o; x.load(pre + off);
             Vec<U> km;
-            if (keepmask != nullptr) km.load_mask(keepmask + off);
+            if constexpr (KP == KEEP_SEEDED) {
+                const KeepSeed sd = keep_seed_of(ks...);
+                km.set_mask(keep_word4(sd.key, sd.word0 + (uint64_t)(off >> 2), sd.thr));
+            } else if (keepmask != nullptr) km.load_mask(keepmask + off);
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 const float ln = (x.v[j] - mean) * rstd * ga.v[j] + be.v[j];
                 float v = act == 0 ? fmaxf(ln, 0.f) : tanhf(ln);
-                if (keepmask != nullptr) v = v * km.v[j] * inv_keep;
+                if (KP == KEEP_SEEDED || keepmask != nullptr) v = v * km.v[j] * inv_keep;
                 o.v[j] = v;
             }
             o.store(y + off);
@@ -117,13 +126,14 @@ __device__ __forceinline__ void col_reduce_store(float* buf, const float (&val)[
     }
 }
 
-template <int U>
+template <int U, int KP = KEEP_BYTES, typename... KS>
 __global__ void ln_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ pre,
                                    const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dpre,
                                    float* __restrict__ part_dgamma, float* __restrict__ part_dbeta,
-                                   float* __restrict__ part_dbias, int rows, int N, int CUt, int RY, int act) {
+                                   float* __restrict__ part_dbias, int rows, int N, int CUt, int RY, int act, KS... ks) {
+    static_assert(KP != KEEP_SEEDED || U == 4, "seeded keep bits come in words of four columns");
     extern __shared__ __attribute__((aligned(16))) float dyn[];  // [2][RY*CUt*U] when RY > 1
     __shared__ float red[16];
     const int g = blockIdx.x;
@@ -149,13 +159,16 @@ __global__ void ln_relu_bwd_kernel(const float* __restrict__ dy, const float* __
                 const int64_t off = base + (int64_t)r * N + cu * U;
                 Vec<U> x, d; x.load(pre + off); d.load(dy + off);
                 Vec<U> km;
-                if (keepmask != nullptr) km.load_mask(keepmask + off);
+                if constexpr (KP == KEEP_SEEDED) {
+                    const KeepSeed sd = keep_seed_of(ks...);
+                    km.set_mask(keep_word4(sd.key, sd.word0 + (uint64_t)(off >> 2), sd.thr));
+                } else if (keepmask != nullptr) km.load_mask(keepmask + off);
 #pragma unroll
                 for (int j = 0; j < U; ++j) {
                     const float xh = (x.v[j] - mean) * rstd;
                     const float ln = xh * ga.v[j] + be.v[j];
                     float gg = d.v[j];
-                    if (keepmask != nullptr) gg = gg * km.v[j] * inv_keep;
+                    if (KP == KEEP_SEEDED || keepmask != nullptr) gg = gg * km.v[j] * inv_keep;
                     float dln;
                     if (act == 0) dln = ln > 0.f ? gg : 0.f;
                     else { const float th = tanhf(ln); dln = gg * (1.f - th * th); }
@@ -186,13 +199,16 @@ __global__ void ln_relu_bwd_kernel(const float* __restrict__ dy, const float* __
                 const int64_t off = base + (int64_t)r * N + cu * U;
                 Vec<U> x, d, o; x.load(pre + off); d.load(dy + off);
                 Vec<U> km;
-                if (keepmask != nullptr) km.load_mask(keepmask + off);
+                if constexpr (KP == KEEP_SEEDED) {
+                    const KeepSeed sd = keep_seed_of(ks...);
+                    km.set_mask(keep_word4(sd.key, sd.word0 + (uint64_t)(off >> 2), sd.thr));
+                } else if (keepmask != nullptr) km.load_mask(keepmask + off);
 #pragma unroll
                 for (int j = 0; j < U; ++j) {
                     const float xh = (x.v[j] - mean) * rstd;
                     const float ln = xh * ga.v[j] + be.v[j];
                     float gg = d.v[j];
-                    if (keepmask != nullptr) gg = gg * km.v[j] * inv_keep;
+                    if (KP == KEEP_SEEDED || keepmask != nullptr) gg = gg * km.v[j] * inv_keep;
                     float dln;
                     if (act == 0) dln = ln > 0.f ? gg : 0.f;
                     else { const float th = tanhf(ln); dln = gg * (1.f - th * th); }
@@ -221,17 +237,17 @@ constexpr int REG_CUT = 256, REG_RY = 4;
 // (the 36-row kernel must not grow: 117 VGPRs in the backward); otherwise rows <= REG_RY * RPT, row indices are
 // clamped for the (unconditional) loads and rows past the group count for nothing.  Per-thread element order as in
 // the generic kernels: column units outer, rows inner.
-template <int RPT, int CPT, bool MASK, bool EXACT>
+template <int RPT, int CPT, int KP, bool EXACT, typename... KS>
 __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_fwd_reg_kernel(
     const float* __restrict__ pre, const float* __restrict__ gamma, const float* __restrict__ beta,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ y, float* __restrict__ mean_out,
-    float* __restrict__ rstd_out, int rows) {
+    float* __restrict__ rstd_out, int rows, KS... ks) {
     constexpr int N4 = REG_CUT * CPT;
     __shared__ float red[16];
     const int g = blockIdx.x, cx = threadIdx.x % REG_CUT, ry = threadIdx.x / REG_CUT;
     const int64_t base4 = (int64_t)g * rows * N4;
     const f32x4v* p4 = reinterpret_cast<const f32x4v*>(pre) + base4;
-    const unsigned* m4 = MASK ? reinterpret_cast<const unsigned*>(keepmask) + base4 : nullptr;
+    const unsigned* m4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask) + base4 : nullptr;
     const float invL = 1.f / ((float)rows * (float)(N4 * 4));
     f32x4v x[CPT][RPT];
     unsigned km[CPT][RPT];
@@ -245,7 +261,11 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_fwd_reg_kernel(
             const int r = EXACT ? ry + REG_RY * i : min(ry + REG_RY * i, rows - 1);
             const int o = r * N4 + cx + REG_CUT * c;
             x[c][i] = p4[o];
-            if (MASK) km[c][i] = m4[o];
+            if (KP == KEEP_BYTES) km[c][i] = m4[o];
+            if constexpr (KP == KEEP_SEEDED) {
+                const KeepSeed sd = keep_seed_of(ks...);
+                km[c][i] = keep_word4(sd.key, sd.word0 + (uint64_t)(base4 + o), sd.thr);
+            }
         }
     float s = 0.f;
 #pragma unroll
@@ -278,7 +298,7 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_fwd_reg_kernel(
             for (int j = 0; j < 4; ++j) {
                 const float ln = (x[c][i][j] - mean) * rstd * ga[j] + be[j];
                 float v = fmaxf(ln, 0.f);                           // ReLU only (tanh layers use the generic kernel)
-                if (MASK) v = v * (float)((km[c][i] >> (8 * j)) & 0xFFu) * inv_keep;
+                if (KP != KEEP_NONE) v = v * (float)((km[c][i] >> (8 * j)) & 0xFFu) * inv_keep;
                 o[j] = v;
             }
             if (ok[i]) y4[(ry + REG_RY * i) * N4 + cx + REG_CUT * c] = o;
@@ -286,12 +306,12 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_fwd_reg_kernel(
     }
 }
 
-template <int RPT, int CPT, bool MASK, bool EXACT>
+template <int RPT, int CPT, int KP, bool EXACT, typename... KS>
 __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_bwd_reg_kernel(
     const float* __restrict__ dy, const float* __restrict__ pre, const float* __restrict__ mean_in,
     const float* __restrict__ rstd_in, const float* __restrict__ gamma, const float* __restrict__ beta,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dpre, float* __restrict__ part_dgamma,
-    float* __restrict__ part_dbeta, float* __restrict__ part_dbias, int rows) {
+    float* __restrict__ part_dbeta, float* __restrict__ part_dbias, int rows, KS... ks) {
     constexpr int N4 = REG_CUT * CPT, N = N4 * 4;
     extern __shared__ __attribute__((aligned(16))) float dyn[];  // [2][RY*CUt*4]
     __shared__ float red[16];
@@ -299,7 +319,7 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_bwd_reg_kernel(
     const int64_t base4 = (int64_t)g * rows * N4;
     const f32x4v* p4 = reinterpret_cast<const f32x4v*>(pre) + base4;
     const f32x4v* d4 = reinterpret_cast<const f32x4v*>(dy) + base4;
-    const unsigned* m4 = MASK ? reinterpret_cast<const unsigned*>(keepmask) + base4 : nullptr;
+    const unsigned* m4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask) + base4 : nullptr;
     const float invL = 1.f / ((float)rows * (float)N);
     const float mean = mean_in[g], rstd = rstd_in[g];
     float* buf0 = dyn;
@@ -317,7 +337,11 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_bwd_reg_kernel(
             const int o = r * N4 + cx + REG_CUT * c;
             x[c][i] = p4[o];
             d[c][i] = d4[o];
-            if (MASK) km[c][i] = m4[o];
+            if (KP == KEEP_BYTES) km[c][i] = m4[o];
+            if constexpr (KP == KEEP_SEEDED) {
+                const KeepSeed sd = keep_seed_of(ks...);
+                km[c][i] = keep_word4(sd.key, sd.word0 + (uint64_t)(base4 + o), sd.thr);
+            }
         }
     float s1 = 0.f, s2 = 0.f;
     // pass 1 (registers only): d is overwritten by dxh = dln * gamma, x by xhat
@@ -333,7 +357,7 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_bwd_reg_kernel(
                 const float xh = (x[c][i][j] - mean) * rstd;
                 const float ln = xh * ga[j] + be[j];
                 float gg = ok[i] ? d[c][i][j] : 0.f;
-                if (MASK) gg = gg * (float)((km[c][i] >> (8 * j)) & 0xFFu) * inv_keep;
+                if (KP != KEEP_NONE) gg = gg * (float)((km[c][i] >> (8 * j)) & 0xFFu) * inv_keep;
                 const float dln = ln > 0.f ? gg : 0.f;                    // ReLU only (tanh layers use the generic kernel)
                 const float dxh = dln * ga[j];
                 s1 += dxh; s2 += dxh * xh; cb[j] += dln; cg[j] += dln * xh;
@@ -383,17 +407,13 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_bwd_reg_kernel(
 // In one block the instruction selector is free to order the 36 elements' chains breadth first -- every mask factor,
 // ln and dln at once beside x and dxh -- and the kernel spills 30 to 70 registers; row by row a row's mask word and ds
 // die as its four dxh appear.
-__device__ __forceinline__ float mul_rounded(float a, float b) {      // a product that no later add absorbs into an fma
-#pragma clang fp contract(off)
-    return a * b;
-}
-template <bool MASK>
+template <int KP, typename... KS>
 __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_att_bwd_reg_kernel(
     const float* __restrict__ ds, const float* __restrict__ qv, const float* __restrict__ w,
     const uint8_t* __restrict__ keep_att, float inv_keep, const float* __restrict__ pre, const float* __restrict__ mean_in,
     const float* __restrict__ rstd_in, const float* __restrict__ gamma, const float* __restrict__ beta,
     float* __restrict__ dpre, float* __restrict__ part_dgamma, float* __restrict__ part_dbeta,
-    float* __restrict__ part_dbias, float* __restrict__ dqv, float* __restrict__ part_dw, int rpt) {
+    float* __restrict__ part_dbias, float* __restrict__ dqv, float* __restrict__ part_dw, int rpt, KS... ks) {
     constexpr int RPT = 9, N4 = REG_CUT, N = N4 * 4, ROWS = REG_RY * RPT;
     extern __shared__ __attribute__((aligned(16))) float dyn[];  // [2][RY*CUt*4]
     __shared__ float red[16];
@@ -401,7 +421,7 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_att_bwd_reg_kernel(
     const int g = blockIdx.x, cx = threadIdx.x % REG_CUT, ry = __builtin_amdgcn_readfirstlane(threadIdx.x / REG_CUT);
     const int64_t base4 = (int64_t)g * ROWS * N4;
     const f32x4v* p4 = reinterpret_cast<const f32x4v*>(pre) + base4;
-    const unsigned* m4 = MASK ? reinterpret_cast<const unsigned*>(keep_att) + base4 : nullptr;
+    const unsigned* m4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keep_att) + base4 : nullptr;
     const float invL = 1.f / ((float)ROWS * (float)N);
     const float mean = mean_in[g], rstd = rstd_in[g];
     float* buf0 = dyn;
@@ -413,7 +433,11 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_att_bwd_reg_kernel(
     for (int i = 0; i < RPT; ++i) {
         const int o = (ry + REG_RY * i) * N4 + cx;
         x[i] = p4[o];
-        if (MASK) km[i] = m4[o];
+        if (KP == KEEP_BYTES) km[i] = m4[o];
+        if constexpr (KP == KEEP_SEEDED) {
+            const KeepSeed sd = keep_seed_of(ks...);
+            km[i] = keep_word4(sd.key, sd.word0 + (uint64_t)(base4 + o), sd.thr);
+        }
         dsr[i] = ds[(int64_t)g * ROWS + ry + REG_RY * i];
         d[i] = (f32x4v)(0.f);
     }
@@ -442,7 +466,7 @@ __global__ __launch_bounds__(REG_CUT * REG_RY) void ln_att_bwd_reg_kernel(
                     const float ln = xh * ga[j] + be[j];
                     // dy, as the attention backward forms dv: g = ds * (keep * inv_keep), dv = 0 + g * qv * w
                     float gj = dsr[i];
-                    if (MASK) gj *= (float)((km[i] >> (8 * j)) & 0xFFu) * inv_keep;
+                    if (KP != KEEP_NONE) gj *= (float)((km[i] >> (8 * j)) & 0xFFu) * inv_keep;
                     gv[j] = gj;
                     rv[j] = fmaxf(__builtin_fmaf(__builtin_fmaf(-xsum, invL, x[i][j]) * rstd, ga[j], be[j]), 0.f);
                     float gg = 0.f;
@@ -746,34 +770,43 @@ extern "C" int vqa_ln_relu_fwd(const float* pre, const float* gamma, const float
     return vqa_ln_act_fwd(pre, gamma, beta, keepmask, keep_prob, y, mean, rstd, G, rows, N, 0, stream);
 }
 
-extern "C" int vqa_ln_act_fwd(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
-                              float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
-                              void* stream) {
+// sd: the keep bits come from the stream (keepmask NULL); the route is the explicit form's, and the route of single
+// columns, which has no 4-byte mask words, is refused
+static int ln_act_fwd_run(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
+                          float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
+                          void* stream, const KeepSeed* sd) {
     VQA_REQUIRE(act == 0 || act == 1, VQA_ERR_ARG);
     VQA_REQUIRE(pre && gamma && beta && y && mean && rstd && G >= 0 && rows > 0 && N > 0, VQA_ERR_ARG);
     VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
-    if (G == 0) return VQA_OK;
     Shape s = pick(pre, y, nullptr, rows, N, keepmask != nullptr);
     if (s.U == 4 && !(vqa_aligned16(gamma) && vqa_aligned16(beta) &&
                       (keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0)))
         s = Shape{1, std::min(256, ((std::min(N, 256) + 63) / 64) * 64), s.RY, 0};
+    VQA_REQUIRE(sd == nullptr || s.U == 4, VQA_ERR_ALIGN);
+    if (G == 0) return VQA_OK;
     s.threads = s.CUt * s.RY;
-    const float inv_keep = keepmask ? 1.f / keep_prob : 1.f;
+    const float inv_keep = (keepmask || sd) ? 1.f / keep_prob : 1.f;
     hipStream_t st = (hipStream_t)stream;
     const int rm = act == 0 ? reg_mode(s.U, rows, N) : 0;
     if (rm != 0) {
 #define VQA_LN_FWD_REG(rpt, cpt, exact)                                                                                    \
     do {                                                                                                                 \
-        if (keepmask != nullptr)                                                                                         \
-            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, true, exact>), dim3(G), dim3(REG_CUT * REG_RY), 0, st, pre,    \
+        if (sd != nullptr)                                                                                               \
+            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, KEEP_SEEDED, exact, KeepSeed>), dim3(G), dim3(REG_CUT * REG_RY), \
+                               0, st, pre, gamma, beta, keepmask, inv_keep, y, mean, rstd, rows, *sd);                   \
+        else if (keepmask != nullptr)                                                                                    \
+            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, KEEP_BYTES, exact>), dim3(G), dim3(REG_CUT * REG_RY), 0, st, pre, \
                                gamma, beta, keepmask, inv_keep, y, mean, rstd, rows);                                    \
         else                                                                                                             \
-            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, false, exact>), dim3(G), dim3(REG_CUT * REG_RY), 0, st, pre,   \
+            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, KEEP_NONE, exact>), dim3(G), dim3(REG_CUT * REG_RY), 0, st, pre, \
                                gamma, beta, keepmask, inv_keep, y, mean, rstd, rows);                                    \
     } while (0)
         if (rm == 1) VQA_LN_FWD_REG(9, 1, true); else if (rm == 2) VQA_LN_FWD_REG(2, 1, false); else VQA_LN_FWD_REG(2, 2, false);
 #undef VQA_LN_FWD_REG
-    } else if (s.U == 4)
+    } else if (sd != nullptr)
+        hipLaunchKernelGGL((ln_relu_fwd_kernel<4, KEEP_SEEDED, KeepSeed>), dim3(G), dim3(s.threads), 0, st, pre, gamma, beta,
+                           keepmask, inv_keep, y, mean, rstd, rows, N, s.CUt, s.RY, act, *sd);
+    else if (s.U == 4)
         hipLaunchKernelGGL(ln_relu_fwd_kernel<4>, dim3(G), dim3(s.threads), 0, st, pre, gamma, beta, keepmask, inv_keep,
                            y, mean, rstd, rows, N, s.CUt, s.RY, act);
     else
@@ -781,6 +814,21 @@ extern "C" int vqa_ln_act_fwd(const float* pre, const float* gamma, const float*
                            y, mean, rstd, rows, N, s.CUt, s.RY, act);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
+}
+
+extern "C" int vqa_ln_act_fwd(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
+                              float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
+                              void* stream) {
+    return ln_act_fwd_run(pre, gamma, beta, keepmask, keep_prob, y, mean, rstd, G, rows, N, act, stream, nullptr);
+}
+
+extern "C" int vqa_ln_act_fwd_seeded(const float* pre, const float* gamma, const float* beta, uint64_t seed, uint64_t offset,
+                                     float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
+                                     void* stream) {
+    VQA_REQUIRE(pre && gamma && beta && y && mean && rstd, VQA_ERR_ARG);
+    VQA_REQUIRE_KEEP_SEED(offset, N, keep_prob);
+    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
+    return ln_act_fwd_run(pre, gamma, beta, nullptr, keep_prob, y, mean, rstd, G, rows, N, act, stream, &sd);
 }
 
 extern "C" int vqa_ln_relu_bwd(const float* dy, const float* pre, const float* mean, const float* rstd,
@@ -791,23 +839,24 @@ extern "C" int vqa_ln_relu_bwd(const float* dy, const float* pre, const float* m
                           part_dbias, G, rows, N, 0, stream);
 }
 
-extern "C" int vqa_ln_act_bwd(const float* dy, const float* pre, const float* mean, const float* rstd,
-                              const float* gamma, const float* beta, const uint8_t* keepmask, float keep_prob,
-                              float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
-                              int N, int act, void* stream) {
+static int ln_act_bwd_run(const float* dy, const float* pre, const float* mean, const float* rstd,
+                          const float* gamma, const float* beta, const uint8_t* keepmask, float keep_prob,
+                          float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
+                          int N, int act, void* stream, const KeepSeed* sd) {
     VQA_REQUIRE(act == 0 || act == 1, VQA_ERR_ARG);
     VQA_REQUIRE(dy && pre && mean && rstd && gamma && beta && dpre && G >= 0 && rows > 0 && N > 0, VQA_ERR_ARG);
     VQA_REQUIRE((part_dgamma == nullptr) == (part_dbeta == nullptr), VQA_ERR_ARG);
     VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
-    if (G == 0) return VQA_OK;
     Shape s = pick(pre, dy, dpre, rows, N, keepmask != nullptr);
     if (s.U == 4 && !(vqa_aligned16(gamma) && vqa_aligned16(beta) &&
                       (keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0) &&
                       (part_dgamma == nullptr || (vqa_aligned16(part_dgamma) && vqa_aligned16(part_dbeta))) &&
                       (part_dbias == nullptr || vqa_aligned16(part_dbias))))
         s = Shape{1, std::min(256, ((std::min(N, 256) + 63) / 64) * 64), s.RY, 0};
+    VQA_REQUIRE(sd == nullptr || s.U == 4, VQA_ERR_ALIGN);
+    if (G == 0) return VQA_OK;
     s.threads = s.CUt * s.RY;
-    const float inv_keep = keepmask ? 1.f / keep_prob : 1.f;
+    const float inv_keep = (keepmask || sd) ? 1.f / keep_prob : 1.f;
     const size_t dyn = s.RY > 1 ? (size_t)2 * s.RY * s.CUt * s.U * sizeof(float) : 0;
     hipStream_t st = (hipStream_t)stream;
     const int rm = act == 0 ? reg_mode(s.U, rows, N) : 0;
@@ -815,18 +864,26 @@ extern "C" int vqa_ln_act_bwd(const float* dy, const float* pre, const float* me
         const size_t dyn_reg = (size_t)2 * REG_RY * REG_CUT * 4 * sizeof(float);
 #define VQA_LN_BWD_REG(rpt, cpt, exact)                                                                                    \
     do {                                                                                                                 \
-        if (keepmask != nullptr)                                                                                         \
-            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, true, exact>), dim3(G), dim3(REG_CUT * REG_RY), dyn_reg, st,   \
+        if (sd != nullptr)                                                                                               \
+            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, KEEP_SEEDED, exact, KeepSeed>), dim3(G), dim3(REG_CUT * REG_RY), \
+                               dyn_reg, st, dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma,     \
+                               part_dbeta, part_dbias, rows, *sd);                                                       \
+        else if (keepmask != nullptr)                                                                                    \
+            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, KEEP_BYTES, exact>), dim3(G), dim3(REG_CUT * REG_RY), dyn_reg, st, \
                                dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta,      \
                                part_dbias, rows);                                                                        \
         else                                                                                                             \
-            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, false, exact>), dim3(G), dim3(REG_CUT * REG_RY), dyn_reg, st,  \
+            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, KEEP_NONE, exact>), dim3(G), dim3(REG_CUT * REG_RY), dyn_reg, st, \
                                dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta,      \
                                part_dbias, rows);                                                                        \
     } while (0)
         if (rm == 1) VQA_LN_BWD_REG(9, 1, true); else if (rm == 2) VQA_LN_BWD_REG(2, 1, false); else VQA_LN_BWD_REG(2, 2, false);
 #undef VQA_LN_BWD_REG
-    } else if (s.U == 4)
+    } else if (sd != nullptr)
+        hipLaunchKernelGGL((ln_relu_bwd_kernel<4, KEEP_SEEDED, KeepSeed>), dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd,
+                           gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act,
+                           *sd);
+    else if (s.U == 4)
         hipLaunchKernelGGL(ln_relu_bwd_kernel<4>, dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd, gamma, beta,
                            keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act);
     else
@@ -836,10 +893,30 @@ extern "C" int vqa_ln_act_bwd(const float* dy, const float* pre, const float* me
     return VQA_OK;
 }
 
-extern "C" int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
-                                   const float* pre, const float* mean, const float* rstd, const float* gamma,
-                                   const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
-                                   float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream) {
+extern "C" int vqa_ln_act_bwd(const float* dy, const float* pre, const float* mean, const float* rstd,
+                              const float* gamma, const float* beta, const uint8_t* keepmask, float keep_prob,
+                              float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
+                              int N, int act, void* stream) {
+    return ln_act_bwd_run(dy, pre, mean, rstd, gamma, beta, keepmask, keep_prob, dpre, part_dgamma, part_dbeta, part_dbias, G,
+                          rows, N, act, stream, nullptr);
+}
+
+extern "C" int vqa_ln_act_bwd_seeded(const float* dy, const float* pre, const float* mean, const float* rstd,
+                                     const float* gamma, const float* beta, uint64_t seed, uint64_t offset, float keep_prob,
+                                     float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
+                                     int N, int act, void* stream) {
+    VQA_REQUIRE(dy && pre && mean && rstd && gamma && beta && dpre, VQA_ERR_ARG);
+    VQA_REQUIRE_KEEP_SEED(offset, N, keep_prob);
+    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
+    return ln_act_bwd_run(dy, pre, mean, rstd, gamma, beta, nullptr, keep_prob, dpre, part_dgamma, part_dbeta, part_dbias, G,
+                          rows, N, act, stream, &sd);
+}
+
+static int ln_relu_att_bwd_run(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
+                               const float* pre, const float* mean, const float* rstd, const float* gamma,
+                               const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
+                               float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream,
+                               const KeepSeed* sd) {
     VQA_REQUIRE(ds && qv && w && pre && mean && rstd && gamma && beta && dpre && part_dgamma && part_dbeta && part_dbias && dqv &&
                     part_dw && B >= 0,
                 VQA_ERR_ARG);
@@ -851,15 +928,42 @@ extern "C" int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float
                     (keep_att == nullptr || (reinterpret_cast<uintptr_t>(keep_att) & 3u) == 0),
                 VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
-    const float inv_keep = keep_att ? 1.f / keep_prob : 1.f;
+    const float inv_keep = (keep_att || sd) ? 1.f / keep_prob : 1.f;
     const size_t dyn_reg = (size_t)2 * REG_RY * REG_CUT * 4 * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (keep_att != nullptr)
-        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<true>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
+    if (sd != nullptr)
+        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<KEEP_SEEDED, KeepSeed>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w,
+                           keep_att, inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw,
+                           9, *sd);
+    else if (keep_att != nullptr)
+        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<KEEP_BYTES>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
                            inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw, 9);
     else
-        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<false>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
+        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<KEEP_NONE>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
                            inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw, 9);
     VQA_CHECK_LAUNCH();
     return VQA_OK;
+}
+
+extern "C" int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
+                                   const float* pre, const float* mean, const float* rstd, const float* gamma,
+                                   const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
+                                   float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream) {
+    return ln_relu_att_bwd_run(ds, qv, w, keep_att, keep_prob, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta,
+                               part_dbias, dqv, part_dw, B, rep, R, H, D, stream, nullptr);
+}
+
+extern "C" int vqa_ln_relu_att_bwd_seeded(const float* ds, const float* qv, const float* w, uint64_t seed, uint64_t offset,
+                                          float keep_prob, const float* pre, const float* mean, const float* rstd,
+                                          const float* gamma, const float* beta, float* dpre, float* part_dgamma,
+                                          float* part_dbeta, float* part_dbias, float* dqv, float* part_dw, int B, int rep,
+                                          int R, int H, int D, void* stream) {
+    VQA_REQUIRE(ds && qv && w && pre && mean && rstd && gamma && beta && dpre && part_dgamma && part_dbeta && part_dbias && dqv &&
+                    part_dw,
+                VQA_ERR_ARG);
+    VQA_REQUIRE_KEEP_SEED(offset, H, keep_prob);
+    VQA_REQUIRE(rep == 1, VQA_ERR_UNSUPPORTED);
+    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
+    return ln_relu_att_bwd_run(ds, qv, w, nullptr, keep_prob, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta,
+                               part_dbias, dqv, part_dw, B, rep, R, H, D, stream, &sd);
 }

@@ -379,25 +379,7 @@ __global__ __launch_bounds__(256) void colsum4x4p1_kernel(Colsum5 a, int M, int 
 }
 
 // ------------------------------------------------------------------ dropout keep-mask
-// Counter-based generator (splitmix64 finaliser on seed ^ counter): the mask of
-// element i depends only on (seed, offset + i), so forward, backward and the test
-// harness regenerate identical masks.
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// one 64-bit hash serves the four positions of an aligned group (16-bit uniforms: keep probabilities resolve to
-// 1.5e-5): the generator, not the 1 byte per element it writes, bounded the kernel at 1.3 TB/s with a hash per position
-__device__ __forceinline__ unsigned keep_thr(float keep) {
-    const float t = keep * 65536.0f;
-    return t <= 0.f ? 0u : (t >= 65536.0f ? 65536u : (unsigned)t);
-}
-__device__ __forceinline__ unsigned keep_bit(uint64_t key, uint64_t pos, unsigned thr) {
-    const uint64_t r = mix64(key ^ (pos >> 2));
-    return ((unsigned)(r >> (16 * (pos & 3))) & 0xFFFFu) < thr ? 1u : 0u;
-}
+// mix64 / keep_thr / keep_bit / keep_word4: vqa_common.h (the kernels that consume a mask share the definition)
 // 16 mask bytes per lane and store (one 16-byte store instead of sixteen 1-byte ones); `out` 16-byte aligned
 __global__ __launch_bounds__(256) void dropout_mask_kernel(uint8_t* __restrict__ out, int64_t n, uint64_t seed,
                                                            uint64_t offset, float keep) {
@@ -408,13 +390,7 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(uint8_t* __restrict__
         for (int64_t g = blockIdx.x * 256 + threadIdx.x; g < n16; g += (int64_t)gridDim.x * 256) {
             unsigned w[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint64_t r = mix64(key ^ ((offset + (uint64_t)(g * 16 + q * 4)) >> 2));
-                unsigned v = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) v |= ((((unsigned)(r >> (16 * b))) & 0xFFFFu) < thr ? 1u : 0u) << (8 * b);
-                w[q] = v;
-            }
+            for (int q = 0; q < 4; ++q) w[q] = keep_word4(key, (offset + (uint64_t)(g * 16 + q * 4)) >> 2, thr);
             reinterpret_cast<uint4*>(out)[g] = make_uint4(w[0], w[1], w[2], w[3]);
         }
     } else {

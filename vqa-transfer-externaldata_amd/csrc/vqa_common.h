@@ -81,6 +81,66 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// ------------------------------------------------------------------ dropout keep bits
+// Counter-based generator (splitmix64 finaliser on seed ^ counter): the keep bit of stream position p depends only on
+// (seed, p), so vqa_dropout_mask, the forward and the backward produce identical bits, and a kernel that consumes a
+// mask can compute the bits it would otherwise load (the *_seeded entry points).
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// one 64-bit hash serves the four positions of an aligned group (16-bit uniforms: keep probabilities resolve to
+// 1.5e-5): the generator, not the 1 byte per element it writes, bounded the kernel at 1.3 TB/s with a hash per position
+__host__ __device__ __forceinline__ unsigned keep_thr(float keep) {
+    const float t = keep * 65536.0f;
+    return t <= 0.f ? 0u : (t >= 65536.0f ? 65536u : (unsigned)t);
+}
+__device__ __forceinline__ unsigned keep_bit(uint64_t key, uint64_t pos, unsigned thr) {
+    const uint64_t r = mix64(key ^ (pos >> 2));
+    return ((unsigned)(r >> (16 * (pos & 3))) & 0xFFFFu) < thr ? 1u : 0u;
+}
+// the four mask bytes (0/1, position 4 * word_index in the low byte) of stream positions 4 * word_index .. + 3: the
+// 4-byte word vqa_dropout_mask writes there, and the word a consuming kernel loads from a mask whose element 0 sits at a
+// stream position that is a multiple of 4
+__device__ __forceinline__ unsigned keep_word4(uint64_t key, uint64_t word_index, unsigned thr) {
+    const uint64_t r = mix64(key ^ word_index);
+    unsigned v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) v |= ((((unsigned)(r >> (16 * b))) & 0xFFFFu) < thr ? 1u : 0u) << (8 * b);
+    return v;
+}
+
+__device__ __forceinline__ uchar4 keep_uchar4(unsigned w) {      // the word as a kernel that loads uchar4 sees it
+    return make_uchar4((unsigned char)(w & 0xFFu), (unsigned char)((w >> 8) & 0xFFu), (unsigned char)((w >> 16) & 0xFFu),
+                       (unsigned char)(w >> 24));
+}
+
+// Where a kernel's keep factors come from: nowhere (no dropout), a uint8 mask in memory, or the stream itself.
+// (The generic kernels decide between the first two at run time, by the mask pointer: their KEEP_BYTES covers both.)
+enum KeepPolicy { KEEP_NONE = 0, KEEP_BYTES = 1, KEEP_SEEDED = 2 };
+// The by-value argument of a KEEP_SEEDED instantiation: key = mix64(seed), word0 = the word index (stream position / 4)
+// of the site's element 0, thr = keep_thr(keep_prob).  Kernels take it as a trailing parameter pack, `KS... ks`, that is
+// empty for the other two policies, so those instantiations keep the argument list they had.
+struct KeepSeed { uint64_t key, word0; unsigned thr; };
+static inline KeepSeed keep_seed_make(uint64_t seed, uint64_t offset, float keep_prob) {
+    return KeepSeed{mix64(seed), offset >> 2, keep_thr(keep_prob)};
+}
+__device__ __forceinline__ KeepSeed keep_seed_of() { return KeepSeed{0, 0, 0}; }
+__device__ __forceinline__ KeepSeed keep_seed_of(KeepSeed s) { return s; }
+// the argument checks every *_seeded entry point shares (after its NULL checks, before any HIP call)
+#define VQA_REQUIRE_KEEP_SEED(offset, row_len, keep_prob)                                 \
+    do {                                                                                  \
+        VQA_REQUIRE((keep_prob) > 0.f, VQA_ERR_ARG);                                      \
+        VQA_REQUIRE(((offset) & 3u) == 0 && (row_len) % 4 == 0, VQA_ERR_ALIGN);           \
+    } while (0)
+
+__device__ __forceinline__ float mul_rounded(float a, float b) {      // a product that no later add absorbs into an fma
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 __device__ __forceinline__ float sigmoidf_stable(float x) {
     // same value as the oracle's piecewise logistic to rounding
     if (x >= 0.f) return 1.f / (1.f + expf(-x));

@@ -527,8 +527,17 @@ class FusionEngine:
                 self.dims.ent_cols = cols
                 self._grow_workspace()
 
-    def _batch_struct(self, batch, keep_att, keep_joint, keep_joint2=None, noise=None, keep_tile=None, keep_word=None):
+    def _batch_struct(self, batch, keep_att, keep_joint, keep_joint2=None, noise=None, keep_tile=None, keep_word=None,
+                      dropout=None, row_offset=0, global_rows=None):
         d = self.dims
+        seeded = {}
+        if dropout is not None:
+            if any(k is not None for k in (keep_att, keep_joint, keep_joint2, keep_tile, keep_word)):
+                raise ValueError("dropout=(seed, step) draws every keep bit inside the kernels: pass no keep_* mask with it")
+            seed, step = dropout
+            off = self.keep_offsets(int(step), row_offset, global_rows)
+            seeded = dict(keep_seed=int(seed), keep_seeded=sum(_lib.KEEP_SITE[k] for k in self.keep_sites()),
+                          **{k + "_off": off[k] for k in self.keep_sites()})
         if keep_word is not None:
             assert keep_word.dtype == torch.uint8 and keep_word.numel() == d.B * d.T * d.H
         if self.model_type == "vlmap_answer_full":
@@ -567,15 +576,19 @@ class FusionEngine:
             keep_tile=keep_tile.data_ptr() if keep_tile is not None else None,
             keep_word=keep_word.data_ptr() if keep_word is not None else None,
             answer_intseq=self._answers[0].data_ptr() if self._answers is not None else None,
-            answer_intseq_len=self._answers[1].data_ptr() if self._answers is not None else None)
+            answer_intseq_len=self._answers[1].data_ptr() if self._answers is not None else None, **seeded)
 
     def forward(self, batch, keep_att=None, keep_joint=None, want_dz=True, keep_joint2=None, noise=None, keep_tile=None,
-                keep_word=None):
-        """keep_joint2: vlmap_answer_noc only -- the keep-mask of l_joint (keep_joint is v_joint's);
+                keep_word=None, dropout=None, row_offset=0, global_rows=None):
+        """dropout=(seed, step): seeded dropout -- every dropout site of the model type draws the keep bits that
+        make_keep_masks(seed, step, row_offset, global_rows) and its siblings would write, inside the kernels that consume
+        them; no mask buffer exists and no keep_* argument may be given (ValueError).  Bit for bit the explicit-mask step.
+        keep_joint2: vlmap_answer_noc only -- the keep-mask of l_joint (keep_joint is v_joint's);
         noise: vlmap_answer_full only -- standard-normal draws [B, H] of the reparameterisation (make_noise);
         keep_tile: vlmap_answer_ent only -- keep-mask [B, num_marginal, 2H] of the pairings' dropout (make_keep_mask_tile);
         keep_word: vlmap_finetune / vlmap_only -- keep-mask [B, T, H] of the word attention's dropout (make_keep_mask_word)"""
-        self._bs = self._batch_struct(batch, keep_att, keep_joint, keep_joint2, noise, keep_tile, keep_word)
+        self._bs = self._batch_struct(batch, keep_att, keep_joint, keep_joint2, noise, keep_tile, keep_word, dropout,
+                                      row_offset, global_rows)
         _lib.check(self.lib.vqa_fusion_forward(C.byref(self.dims), C.byref(self._p_struct), C.byref(self._bs),
                                                C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
                                                1 if want_dz else 0, self._stream()), "vqa_fusion_forward")
@@ -629,10 +642,13 @@ class FusionEngine:
                                           self.n_train, C.c_void_p(self.norm_sq.data_ptr()), float(self.clip_norm), lr_t,
                                           ADAM_B1, ADAM_B2, ADAM_EPS, self._stream()), "vqa_clip_adam")
 
-    def train_step(self, batch, keep_att, keep_joint, lr, allreduce=None, keep_joint2=None, noise=None, keep_tile=None,
-                   keep_word=None):
+    def train_step(self, batch, keep_att=None, keep_joint=None, lr=None, allreduce=None, keep_joint2=None, noise=None,
+                   keep_tile=None, keep_word=None, dropout=None, row_offset=0, global_rows=None):
+        """dropout / row_offset / global_rows: seeded dropout, as in forward (then without keep_* masks)"""
+        if lr is None:
+            raise TypeError("train_step needs the learning rate lr")
         self.forward(batch, keep_att, keep_joint, want_dz=True, keep_joint2=keep_joint2, noise=noise, keep_tile=keep_tile,
-                     keep_word=keep_word)
+                     keep_word=keep_word, dropout=dropout, row_offset=row_offset, global_rows=global_rows)
         if allreduce is not None and hasattr(allreduce, "start"):
             self.backward(reducer=allreduce)          # bucketed, overlapped with the backward phases
         else:
@@ -642,7 +658,7 @@ class FusionEngine:
         self.optimizer_step(lr)
 
     # ------------------------------------------------------------------ whole step as one hipGraph replay
-    def train_step_graph(self, batch, lr, seed, step):
+    def train_step_graph(self, batch, lr, seed, step, dropout=None):
         """One train step = refresh the step's inputs in place + ONE vqa_graph_launch.
         The first call for a shape (B, T, live_rows) captures forward -> backward -> device-side Adam rate -> norm ->
         clip + Adam on a private stream into an executable graph (csrc/graph.hip); later calls copy the batch into the
@@ -652,7 +668,12 @@ class FusionEngine:
         The Adam step count lives on the device (vqa_adam_lr_step) and is kept equal to self.step_count.
         EXPERIMENTAL and not the default anywhere: on this ROCm release replay is SLOWER than eager launches (3.96 against
         3.54 ms per bs-512 step, profiles/r4_graph_bench.txt), and mixing eager train_step calls with replays on ONE engine
-        gave run-to-run differences in two of five model types (tools/dbg/graph_dbg.py) -- use an engine either way."""
+        gave run-to-run differences in two of five model types (tools/dbg/graph_dbg.py) -- use an engine either way.
+        Dropout stays explicit here: a seeded step passes seed and offsets to its kernels BY VALUE, so a replay could not
+        advance them (the masks are buffers the graph re-reads after they are regenerated in place)."""
+        if dropout is not None:
+            raise ValueError("train_step_graph keeps explicit dropout masks: seed and offsets of a seeded step are by-value "
+                             "kernel arguments, which a graph replay cannot advance")
         d = self.dims
         live = batch.get("live_rows")
         live_key = None if live is None else tuple(int(x) for x in np.asarray(live))
@@ -811,6 +832,30 @@ class FusionEngine:
         """the scalar optimize_loss minimises: sum of the model's `losses` (vqa/model_vlmap_answer.py:304-306)"""
         return self.tensor("report")[15 if self.model_type in self.EXTRA_REPORT_KEYS else 0]
 
+    def keep_sites(self):
+        """the dropout sites of this model type, by the name of their mask in vqa_batch_t"""
+        if self.model_type == "vqa":
+            return ()
+        return ("keep_att", "keep_joint") + (("keep_joint2",) if self.model_type in NOC_FAMILY else ()) + \
+            (("keep_tile",) if self.model_type == "vlmap_answer_ent" else ()) + \
+            (("keep_word",) if self.model_type in BI_FAMILY else ())
+
+    def keep_offsets(self, step, row_offset=0, global_rows=None):
+        """Stream position of element 0 of every dropout site's mask at `step`: the one place that lays the (seed, step)
+        stream out, for the explicit masks (make_keep_mask*) and for seeded dropout (forward(dropout=...)).  The stream
+        is indexed by the GLOBAL batch row (row_offset, global_rows: see make_keep_masks).  keep_att and keep_joint share
+        the region at 0; l_joint of vlmap_answer_noc, the pairings of vlmap_answer_ent and the word attention of
+        vlmap_finetune have regions of their own at 1, 2 and 3 << 40."""
+        d = self.dims
+        Bg = int(global_rows) if global_rows is not None else d.B
+        base = step * (Bg * d.R * d.H + Bg * 2 * d.H)
+        tile_row, word_row = d.num_marginal * 2 * d.H, d.T * d.H
+        return {"keep_att": base + row_offset * d.R * d.H,
+                "keep_joint": base + Bg * d.R * d.H + row_offset * 2 * d.H,
+                "keep_joint2": (1 << 40) + step * (Bg * 2 * d.H) + row_offset * 2 * d.H,
+                "keep_tile": (2 << 40) + step * (Bg * tile_row) + row_offset * tile_row,
+                "keep_word": (3 << 40) + step * (Bg * word_row) + row_offset * word_row}
+
     def make_keep_masks(self, seed, step, row_offset=0, global_rows=None):
         """Reproducible dropout keep-masks for (seed, step) -- the explicit stand-in for
         tf.nn.dropout's internal RNG (vlmap/modules.py:82, model_vlmap_answer.py:180).
@@ -818,30 +863,25 @@ class FusionEngine:
         (row_offset) and the global batch size, and draws exactly the bits one process running the whole batch
         would draw for those rows -- ranks never reuse each other's bits."""
         d = self.dims
-        Bg = int(global_rows) if global_rows is not None else d.B
         n_att, n_j = d.B * d.R * d.H, d.B * 2 * d.H
         if not hasattr(self, "_keep_att"):
             self._keep_att = torch.empty(n_att, dtype=torch.uint8, device=self.device)
             self._keep_joint = torch.empty(n_j, dtype=torch.uint8, device=self.device)
-        off = step * (Bg * d.R * d.H + Bg * 2 * d.H)
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_att.data_ptr()), n_att, seed,
-                                             off + row_offset * d.R * d.H, d.keep_att, self._stream()),
-                   "vqa_dropout_mask")
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_joint.data_ptr()), n_j, seed,
-                                             off + Bg * d.R * d.H + row_offset * 2 * d.H, d.keep_joint,
+        off = self.keep_offsets(step, row_offset, global_rows)
+        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_att.data_ptr()), n_att, seed, off["keep_att"], d.keep_att,
                                              self._stream()), "vqa_dropout_mask")
+        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_joint.data_ptr()), n_j, seed, off["keep_joint"],
+                                             d.keep_joint, self._stream()), "vqa_dropout_mask")
         return self._keep_att, self._keep_joint
 
     def make_keep_mask_word(self, seed, step, row_offset=0, global_rows=None):
         """vlmap_finetune / vlmap_only: keep-mask [B, T, H] of the question self-attention's tf.nn.dropout(., 0.8)
         (modules.hadamard_attention under scope word_attention), its own region of the (seed, step) stream"""
         d = self.dims
-        Bg = int(global_rows) if global_rows is not None else d.B
-        per_row = d.T * d.H
-        n = d.B * per_row
+        n = d.B * d.T * d.H
         if not hasattr(self, "_keep_word"):
             self._keep_word = torch.empty(n, dtype=torch.uint8, device=self.device)
-        off = (3 << 40) + step * (Bg * per_row) + row_offset * per_row
+        off = self.keep_offsets(step, row_offset, global_rows)["keep_word"]
         _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_word.data_ptr()), n, seed, off, d.keep_att,
                                              self._stream()), "vqa_dropout_mask")
         return self._keep_word
@@ -850,12 +890,10 @@ class FusionEngine:
         """vlmap_answer_ent: keep-mask [B, num_marginal, 2H] of tf.nn.dropout(tile_joint, 0.5)
         (vqa/model_vlmap_answer_ent.py:205), its own region of the (seed, step) stream, indexed by the global batch row"""
         d = self.dims
-        Bg = int(global_rows) if global_rows is not None else d.B
-        per_row = d.num_marginal * 2 * d.H
-        n = d.B * per_row
+        n = d.B * d.num_marginal * 2 * d.H
         if not hasattr(self, "_keep_tile"):
             self._keep_tile = torch.empty(n, dtype=torch.uint8, device=self.device)
-        off = (2 << 40) + step * (Bg * per_row) + row_offset * per_row
+        off = self.keep_offsets(step, row_offset, global_rows)["keep_tile"]
         _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_tile.data_ptr()), n, seed, off, d.keep_joint,
                                              self._stream()), "vqa_dropout_mask")
         return self._keep_tile
@@ -877,11 +915,10 @@ class FusionEngine:
     def make_keep_mask_joint2(self, seed, step, row_offset=0, global_rows=None):
         """vlmap_answer_noc: the second dropout site's keep-mask (l_joint), from its own region of the same stream"""
         d = self.dims
-        Bg = int(global_rows) if global_rows is not None else d.B
         n_j = d.B * 2 * d.H
         if not hasattr(self, "_keep_joint2"):
             self._keep_joint2 = torch.empty(n_j, dtype=torch.uint8, device=self.device)
-        off = (1 << 40) + step * (Bg * 2 * d.H) + row_offset * 2 * d.H      # far beyond the two masks of make_keep_masks
+        off = self.keep_offsets(step, row_offset, global_rows)["keep_joint2"]      # far beyond the two masks of make_keep_masks
         _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_joint2.data_ptr()), n_j, seed, off, d.keep_joint,
                                              self._stream()), "vqa_dropout_mask")
         return self._keep_joint2

@@ -365,7 +365,8 @@ class Model(object):
         return {}
 
     def _variant_inputs(self, eng, seed, row_offset, global_rows, dropout_off):
-        """extra per-step inputs of a variant as keyword arguments of FusionEngine.forward (noise, keep_tile)"""
+        """extra per-step inputs of a variant as keyword arguments of FusionEngine.forward (noise, keep_tile); a variant's
+        mask is left out under config.inline_dropout, like the common ones"""
         return {}
 
     def build(self):
@@ -378,9 +379,14 @@ class Model(object):
         else:
             self._engine.resize(B, T, gb)
         eng = self._engine
-        kj2 = None
+        kj2 = seeded = None
         if getattr(self.config, "dropout_off", False):
             ka = kj = None
+        elif getattr(self.config, "inline_dropout", False):
+            # the same bits, drawn inside the kernels that consume them (FusionEngine.forward(dropout=...)): no mask buffers
+            ka = kj = None
+            seeded = dict(dropout=(int(getattr(self.config, "seed", 123)), self._step),
+                          row_offset=int(getattr(self.config, "shard_row_offset", 0) or 0), global_rows=gb)
         else:   # tf.nn.dropout is applied unconditionally in the reference (also at eval time)
             # under data parallelism the stream is indexed by the global row (config.shard_row_offset, global_batch)
             ka, kj = eng.make_keep_masks(int(getattr(self.config, "seed", 123)), self._step,
@@ -394,7 +400,7 @@ class Model(object):
                                         bool(getattr(self.config, "dropout_off", False)))
         self._step += 1
         self._db, self._keep = db, (ka, kj)
-        eng.forward(db, ka, kj, want_dz=self.is_train, keep_joint2=kj2, **extra_in)
+        eng.forward(db, ka, kj, want_dz=self.is_train, keep_joint2=kj2, **extra_in, **(seeded or {}))
 
         d = eng.dims
         A, R = d.A, d.R

@@ -19,7 +19,7 @@ class Model(_Base):
         return {"num_marginal": int(getattr(self.config, "num_marginal", F.NUM_MARGINAL))}
 
     def _variant_inputs(self, eng, seed, row_offset, global_rows, dropout_off):
-        if dropout_off:
+        if dropout_off or getattr(self.config, "inline_dropout", False):
             return {}
         return {"keep_tile": eng.make_keep_mask_tile(seed, self._step, row_offset=row_offset, global_rows=global_rows)}
 

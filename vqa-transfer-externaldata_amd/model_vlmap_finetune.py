@@ -28,7 +28,7 @@ class Model(_Base):
         super().__init__(batch, config, is_train=is_train, image_features=image_features)
 
     def _variant_inputs(self, eng, seed, row_offset, global_rows, dropout_off):
-        if dropout_off:
+        if dropout_off or getattr(self.config, "inline_dropout", False):
             return {}
         return {"keep_word": eng.make_keep_mask_word(seed, self._step, row_offset=row_offset, global_rows=global_rows)}
 

@@ -85,7 +85,20 @@ def embed_bwd(dx_tm, q, Vq, lens=None):
     return dE
 
 
-def ln_relu_fwd(pre, gamma, beta, rows=1, keepmask=None, keep_prob=1.0):
+def _seeded(keepmask, keep_seed):
+    """keep_seed=(seed, offset): the op draws its keep bits from the stream of dropout_mask(n, seed, offset, keep_prob) inside
+    its kernel (the vqa_*_seeded entry points) instead of reading `keepmask`; one or the other."""
+    if keep_seed is None:
+        return None
+    if keepmask is not None:
+        raise ValueError("keepmask and keep_seed are mutually exclusive")
+    seed, offset = keep_seed
+    return C.c_uint64(int(seed)), C.c_uint64(int(offset))
+
+
+def ln_relu_fwd(pre, gamma, beta, rows=1, keepmask=None, keep_prob=1.0, keep_seed=None):
+    if _seeded(keepmask, keep_seed):
+        return ln_act_fwd(pre, gamma, beta, rows, "relu", None, keep_prob, keep_seed)
     lib = _lib.load()
     M, N = pre.shape
     G = M // rows
@@ -117,7 +130,7 @@ def colsum3(X0, X1, X2):
     return outs
 
 
-def ln_relu_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, keepmask=None, keep_prob=1.0, want_params=True):
+def ln_relu_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, keepmask=None, keep_prob=1.0, want_params=True, keep_seed=None):
     lib = _lib.load()
     M, N = pre.shape
     G = M // rows
@@ -125,16 +138,48 @@ def ln_relu_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, keepmask=None, keep_pr
     pg = _f32(G, N, like=pre) if want_params else None
     pb = _f32(G, N, like=pre) if want_params else None
     pbias = _f32(G, N, like=pre) if want_params else None
-    _lib.check(lib.vqa_ln_relu_bwd(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(keepmask), keep_prob,
-                                   _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, _st(pre)), "vqa_ln_relu_bwd")
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        _lib.check(lib.vqa_ln_act_bwd_seeded(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), sd[0], sd[1], keep_prob,
+                                             _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, 0, _st(pre)),
+                   "vqa_ln_act_bwd_seeded")
+    else:
+        _lib.check(lib.vqa_ln_relu_bwd(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(keepmask), keep_prob,
+                                       _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, _st(pre)), "vqa_ln_relu_bwd")
     if not want_params:
         return dpre, None, None, None
     dgamma, dbeta, dbias = colsum3(pg, pb, pbias)
     return dpre, dgamma, dbeta, dbias
 
 
-def attn_pool_fwd(v, qv, V, nb, w, bias, keepmask=None, keep_prob=1.0):
+def _attn_fwd_seeded(v, qv, V, nb, w, bias, sd, keep_prob):
+    lib = _lib.load()
+    B, R, H = v.shape
+    D = V.shape[2]
+    att, pooled = _f32(B, R, like=v), _f32(B, D, like=v)
+    _lib.check(lib.vqa_attn_pool_fwd_seeded(_p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(nb), _p(w), _p(bias), sd[0],
+                                            sd[1], keep_prob, _p(att), _p(pooled), B, 1, R, H, D, _st(v)),
+               "vqa_attn_pool_fwd_seeded")
+    return att, pooled
+
+
+def _attn_bwd_seeded(dpooled, v, qv, V, att, w, sd, keep_prob):
+    lib = _lib.load()
+    B, R, H = v.shape
+    D = V.shape[2]
+    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
+    pdw, pdb = _f32(B, H, like=v), _f32(B, 1, like=v)
+    _lib.check(lib.vqa_attn_pool_bwd_seeded(_p(dpooled), _p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(att), _p(w),
+                                            sd[0], sd[1], keep_prob, _p(dv), _p(dqv), _p(pdw), _p(pdb), B, 1, R, H, D, _st(v)),
+               "vqa_attn_pool_bwd_seeded")
+    return dv, dqv, colsum(pdw), colsum(pdb)
+
+
+def attn_pool_fwd(v, qv, V, nb, w, bias, keepmask=None, keep_prob=1.0, keep_seed=None):
     """modules.hadamard_attention + modules.attention_pooling."""
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        return _attn_fwd_seeded(v, qv, V, nb, w, bias, sd, keep_prob)
     lib = _lib.load()
     B, R, H = v.shape
     D = V.shape[2]
@@ -144,7 +189,10 @@ def attn_pool_fwd(v, qv, V, nb, w, bias, keepmask=None, keep_prob=1.0):
     return att, pooled
 
 
-def attn_pool_bwd(dpooled, v, qv, V, att, w, keepmask=None, keep_prob=1.0):
+def attn_pool_bwd(dpooled, v, qv, V, att, w, keepmask=None, keep_prob=1.0, keep_seed=None):
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        return _attn_bwd_seeded(dpooled, v, qv, V, att, w, sd, keep_prob)
     lib = _lib.load()
     B, R, H = v.shape
     D = V.shape[2]
@@ -155,10 +203,13 @@ def attn_pool_bwd(dpooled, v, qv, V, att, w, keepmask=None, keep_prob=1.0):
     return dv, dqv, colsum(pdw), colsum(pdb)
 
 
-def attn_pool_fwd_v16(v, qv, V16, nb, w, bias, keepmask=None, keep_prob=1.0):
+def attn_pool_fwd_v16(v, qv, V16, nb, w, bias, keepmask=None, keep_prob=1.0, keep_seed=None):
     """attn_pool_fwd over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_fwd on V16.float()."""
     lib = _lib.load()
     assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        return _attn_fwd_seeded(v, qv, V16, nb, w, bias, sd, keep_prob)
     B, R, H = v.shape
     D = V16.shape[2]
     att, pooled = _f32(B, R, like=v), _f32(B, D, like=v)
@@ -167,10 +218,13 @@ def attn_pool_fwd_v16(v, qv, V16, nb, w, bias, keepmask=None, keep_prob=1.0):
     return att, pooled
 
 
-def attn_pool_bwd_v16(dpooled, v, qv, V16, att, w, keepmask=None, keep_prob=1.0):
+def attn_pool_bwd_v16(dpooled, v, qv, V16, att, w, keepmask=None, keep_prob=1.0, keep_seed=None):
     """attn_pool_bwd over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_bwd on V16.float()."""
     lib = _lib.load()
     assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        return _attn_bwd_seeded(dpooled, v, qv, V16, att, w, sd, keep_prob)
     B, R, H = v.shape
     D = V16.shape[2]
     dv, dqv = torch.empty_like(v), torch.empty_like(qv)
@@ -202,7 +256,7 @@ def attn_pool_bwd_ds(dpooled, V, att):
     return ds, pdb
 
 
-def ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keepmask=None, keep_prob=1.0):
+def ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keepmask=None, keep_prob=1.0, keep_seed=None):
     """v_linear_v's LayerNorm + ReLU backward with dy = ds x (keep / keep_prob * qv * w) formed in registers; also the
     attention backward's dqv and score-weight partial.  pre [B,R,H] -> dpre, (part_dgamma, part_dbeta, part_dbias) [B,H],
     dqv [B,H], part_dw [B,H]."""
@@ -210,6 +264,12 @@ def ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keepmask=None, keep
     B, R, H = pre.shape
     dpre = torch.empty_like(pre)
     pg, pb, pbias, dqv, pdw = (_f32(B, H, like=pre) for _ in range(5))
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        _lib.check(lib.vqa_ln_relu_att_bwd_seeded(_p(ds), _p(qv), _p(w), sd[0], sd[1], keep_prob, _p(pre), _p(mean), _p(rstd),
+                                                  _p(gamma), _p(beta), _p(dpre), _p(pg), _p(pb), _p(pbias), _p(dqv), _p(pdw), B,
+                                                  1, R, H, 2048, _st(pre)), "vqa_ln_relu_att_bwd_seeded")
+        return dpre, (pg, pb, pbias), dqv, pdw
     _lib.check(lib.vqa_ln_relu_att_bwd(_p(ds), _p(qv), _p(w), _p(keepmask), keep_prob, _p(pre), _p(mean), _p(rstd),
                                        _p(gamma), _p(beta), _p(dpre), _p(pg), _p(pb), _p(pbias), _p(dqv), _p(pdw), B, 1, R,
                                        H, 2048, _st(pre)), "vqa_ln_relu_att_bwd")
@@ -341,24 +401,36 @@ def sumsq(g, extra=None):
 
 
 # ---------------------------------------------------------------- ops used by the pre-training model
-def ln_act_fwd(pre, gamma, beta, rows=1, act="relu", keepmask=None, keep_prob=1.0):
+def ln_act_fwd(pre, gamma, beta, rows=1, act="relu", keepmask=None, keep_prob=1.0, keep_seed=None):
     """modules.fc_layer's layer_norm + activation ('relu' | 'tanh') (+ dropout)."""
     lib = _lib.load()
     M, N = pre.shape
     G = M // rows
     y = torch.empty_like(pre)
     mean, rstd = _f32(G, like=pre), _f32(G, like=pre)
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        _lib.check(lib.vqa_ln_act_fwd_seeded(_p(pre), _p(gamma), _p(beta), sd[0], sd[1], keep_prob, _p(y), _p(mean), _p(rstd), G,
+                                             rows, N, 0 if act == "relu" else 1, _st(pre)), "vqa_ln_act_fwd_seeded")
+        return y, mean, rstd
     _lib.check(lib.vqa_ln_act_fwd(_p(pre), _p(gamma), _p(beta), _p(keepmask), keep_prob, _p(y), _p(mean), _p(rstd), G,
                                   rows, N, 0 if act == "relu" else 1, _st(pre)), "vqa_ln_act_fwd")
     return y, mean, rstd
 
 
-def ln_act_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, act="relu", keepmask=None, keep_prob=1.0):
+def ln_act_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, act="relu", keepmask=None, keep_prob=1.0, keep_seed=None):
     lib = _lib.load()
     M, N = pre.shape
     G = M // rows
     dpre = torch.empty_like(pre)
     pg, pb, pbias = _f32(G, N, like=pre), _f32(G, N, like=pre), _f32(G, N, like=pre)
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        _lib.check(lib.vqa_ln_act_bwd_seeded(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), sd[0], sd[1], keep_prob,
+                                             _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, 0 if act == "relu" else 1,
+                                             _st(pre)), "vqa_ln_act_bwd_seeded")
+        dgamma, dbeta, dbias = colsum3(pg, pb, pbias)
+        return dpre, dgamma, dbeta, dbias
     _lib.check(lib.vqa_ln_act_bwd(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(keepmask), keep_prob,
                                   _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, 0 if act == "relu" else 1,
                                   _st(pre)), "vqa_ln_act_bwd")

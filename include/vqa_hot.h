@@ -990,7 +990,12 @@ int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t* dims, cons
  * x [B,Hi,Wi,Ci], w HWIO [kh,kw,Ci,Co] (TF layout), explicit top/left zero padding, output
  * [B,Ho,Wo,Co]; scale/shift/residual may be NULL.  1x1/stride-1 -> plain MFMA GEMM, otherwise an
  * implicit GEMM (needs Ci % 32 == 0, or Ci == 4 with kh*kw*4 a multiple of 32).  Replaces slim conv2d/conv2d_same + batch_norm(is_training=
- * False) + relu of resnet_v1 (vlmap/modules.py:143-191) and modules.conv2d (:552-572). */
+ * False) + relu of resnet_v1 (vlmap/modules.py:143-191) and modules.conv2d (:552-572).
+ * The 1x1/stride-1 route (no padding, Ho == Hi, Wo == Wi) puts no condition on Ci, Co or the pointers' alignment: what
+ * the 16-byte loaders cannot serve (Ci or Co no multiple of 4, a misaligned x or w) runs on the GEMM's edge loader and is
+ * accepted.  The implicit route returns VQA_ERR_ALIGN for a Ci outside its condition or an x that is not 16-byte
+ * aligned, VQA_ERR_UNSUPPORTED for Co % 4 != 0, a w that is not 16-byte aligned or an operand of 4 GiB or more; both
+ * return VQA_ERR_ARG for a NULL x / w / y or a non-positive size.  A refused call writes nothing. */
 int vqa_conv2d_nhwc(const float* x, int B, int Hi, int Wi, int Ci, const float* w, int kh, int kw, int Co,
                     int stride, int pad_t, int pad_l, int Ho, int Wo, const float* scale, const float* shift,
                     const float* residual, int relu, float* y, void* stream);

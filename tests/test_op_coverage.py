@@ -17,7 +17,6 @@ ALLOWED = {
     "vqa_pretrain_workspace_bytes": "host-only layout query, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
     "vqa_pretrain_tensor": "host-only layout query, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
     "vqa_gemm_bf16x3_workspace_floats": "host-only size query behind ops.gemm_bf16x3_ex (test_gpu_ops.py)",
-    "vqa_conv2d_bwd_workspace_floats": "host-only size query of the extractor's backward, tests/host_abi_exercise.py",
     # knobs, debug and profiling hooks
     "vqa_gemm_bf16x3_set_mode": "tuning knob of the experimental bf16x3 GEMM",
     "vqa_gemm_shortk_set_mode": "tuning knob of the short-K GEMM",
@@ -41,10 +40,6 @@ ALLOWED = {
     "vqa_gemm_shortk_nn": "ops.gemm_shortk, test_gpu_ops.py::test_shortk_gemm_matches_float64",
     "vqa_gru_fill_finished": "vqa_gru_seq_fwd_live's finished rows, test_gpu_gru_f64.py (form live)",
     "vqa_gru_zero_finished": "vqa_gru_seq_bwd_live's finished rows, test_gpu_gru_f64.py (form live: dxp exactly 0)",
-    "vqa_pad_c3c4_nhwc": "extractor pieces through vfeat.py, test_gpu_vfeat.py::test_full_resnet101_448_matches_oracle_f64",
-    "vqa_maxpool3x3s2_same_nhwc": "test_gpu_vfeat.py::test_maxpool_subsample_crop_bit_exact_or_close",
-    "vqa_subsample_nhwc": "test_gpu_vfeat.py::test_maxpool_subsample_crop_bit_exact_or_close",
-    "vqa_crop_and_resize_nhwc": "test_gpu_vfeat.py::test_maxpool_subsample_crop_bit_exact_or_close",
     "vqa_loss2_fwd": "two-headed loss, test_gpu_fusion.py::test_vqa_all2_two_heads_and_dead_branch",
     "vqa_rowmin_mask_fwd": "test_gpu_fusion.py::test_vqa_all_row_minimum_substitution_on_the_gpu",
     "vqa_rowmin_mask_bwd": "test_gpu_fusion.py::test_vqa_all_row_minimum_substitution_on_the_gpu",
@@ -66,6 +61,10 @@ ATTN = ["attn_pool_fwd", "attn_pool_bwd", "attn_pool_fwd_rep", "attn_pool_bwd_re
 # the f32 GEMM entry points and knobs tests/test_gpu_gemm_f64.py pins to the float64 reference of tests/gemm_ref.py, route by route
 GEMM = ["gemm_f32", "gemm_f32_ex", "gemm_f32_gather", "gemm_set_config", "gemm_set_order", "gemm_set_max_blocks",
         "gemm_set_tall_config", "gemm_workspace_floats"]
+
+# the f32 extractor entry points and knobs tests/test_gpu_conv_f64.py pins to the float64 reference of tests/conv_ref.py, route by route
+CONV = ["conv2d_nhwc", "conv2d_nhwc_bwd", "conv2d_bwd_workspace_floats", "conv_set_config", "pad_c3c4_nhwc",
+        "maxpool3x3s2_same_nhwc", "subsample_nhwc", "crop_and_resize_nhwc"]
 
 
 def _declared(repo_root):
@@ -117,3 +116,14 @@ def test_the_f32_gemm_stays_pinned_by_its_float64_test(repo_root):
     assert not set("vqa_" + k for k in GEMM) & set(ALLOWED)
     declared = set(_declared(repo_root))
     assert all("vqa_" + k in declared for k in GEMM)
+
+
+def test_the_f32_extractor_kernels_stay_pinned_by_their_float64_test(repo_root):
+    text = open(os.path.join(repo_root, "tests", "test_gpu_conv_f64.py")).read()
+    calls = set(re.findall(r"\blib\.(vqa_[a-z0-9_]+)\(", text))
+    missing = ["vqa_" + k for k in CONV if "vqa_" + k not in calls]
+    assert not missing, "tests/test_gpu_conv_f64.py no longer calls %s" % missing
+    assert {"vqa_gemm_set_config", "vqa_gemm_shortk_set_mode", "vqa_gemm_shortk_supported"} <= calls and "conv_ref" in text
+    assert not set("vqa_" + k for k in CONV) & set(ALLOWED)
+    declared = set(_declared(repo_root))
+    assert all("vqa_" + k in declared for k in CONV)

@@ -195,8 +195,11 @@ def _attn_equal(B, Rg, H, D, seed, with_mask, expect_ds):
 
 
 # generic kernels: B 3, R 5, H 8, D 12; the loads-in-flight kernels of the models' shape: B 4, R 36, H 1024, D 2048; the
-# forward's other instantiations (H 256, two 2048-wide column groups) over a short memory
-ATTN_SHAPES = [("generic", 3, 5, 8, 12, False), ("fast", 4, 36, 1024, 2048, True), ("fast-fwd-h256-d4096", 2, 7, 256, 4096, False)]
+# forward's other instantiations (H 256 .. 1024 in one to four 256-wide groups, one or two 2048-wide column groups) over a
+# short memory
+ATTN_SHAPES = [("generic", 3, 5, 8, 12, False), ("fast", 4, 36, 1024, 2048, True), ("fast-fwd-h256-d4096", 2, 7, 256, 4096, False)] + \
+              [("fast-fwd-h%d-d%d" % (H, D), 2, 7, H, D, False)
+               for H, D in ((256, 2048), (512, 2048), (768, 2048), (512, 4096), (768, 4096), (1024, 4096))]
 
 
 @pytest.mark.parametrize("with_mask", [False, True], ids=["nomask", "mask"])

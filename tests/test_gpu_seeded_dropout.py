@@ -58,9 +58,12 @@ def test_dropout_mask_equals_the_numpy_restatement(n, seed, offset, keep):
 
 # ------------------------------------------------------------------------------------------------------ attention
 # (name, B, R, H, D, vqa_attn_set_fast or None): the generic kernels, the loads-in-flight pair of the models' shape, another
-# instantiation of the loads-in-flight forward, and the generic kernels at the models' shape
+# instantiation of the loads-in-flight forward, the generic kernels at the models' shape, and the forward's six other
+# <H / 256, D / 2048> instantiations over a short memory (the backward of those shapes is the generic kernel)
 ATT_CASES = [("generic", 3, 5, 8, 12, None), ("fast", 4, 36, 1024, 2048, None), ("fast-fwd-h256-d4096", 2, 7, 256, 4096, None),
-             ("generic-at-the-models-shape", 2, 36, 1024, 2048, 0)]
+             ("generic-at-the-models-shape", 2, 36, 1024, 2048, 0)] + \
+            [("fast-fwd-h%d-d%d" % (H, D), 2, 7, H, D, None)
+             for H, D in ((256, 2048), (512, 2048), (768, 2048), (512, 4096), (768, 4096), (1024, 4096))]
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32-memory", "bf16-memory"])
@@ -171,6 +174,14 @@ def test_refusals():
         ops.attn_pool_fwd(v, qv, V, nb, w, bias, keep_seed=(SEED, 2), keep_prob=0.8)
     with pytest.raises(L.VqaHotError, match="aligned"):
         ops.ln_relu_fwd(v.view(B * Rg, H), w, w, keep_seed=(SEED, 6), keep_prob=0.5)
+    # gamma 4 bytes off a 16-byte boundary sends the LayerNorm to its route of single columns, which has no seeded form
+    x, gam = v.view(B * Rg, H), torch.ones(H + 4).cuda()[1:1 + H]
+    assert gam.data_ptr() % 16 == 4
+    y, mean, rstd = ops.ln_relu_fwd(x, gam, w)
+    with pytest.raises(L.VqaHotError, match="aligned"):
+        ops.ln_relu_fwd(x, gam, w, keep_seed=(SEED, 0), keep_prob=0.5)
+    with pytest.raises(L.VqaHotError, match="aligned"):
+        ops.ln_relu_bwd(x, x, mean, rstd, gam, w, keep_seed=(SEED, 0), keep_prob=0.5)
     mask = ops.dropout_mask(B * Rg * H, SEED, 0, 0.8, "cuda")
     with pytest.raises(ValueError, match="mutually exclusive"):
         ops.attn_pool_fwd(v, qv, V, nb, w, bias, keepmask=mask, keep_seed=(SEED, 0), keep_prob=0.8)

@@ -15,7 +15,7 @@
 // (295 KB) are each read exactly once with 16-byte-per-lane coalesced loads and
 // the scores never leave the CU.  Row dot products use wavefront (64-lane)
 // shuffles; the softmax over R runs in one wave.
-#include "vqa_common.h"
+#include "keep_launch.h"
 
 namespace {
 
@@ -831,14 +831,136 @@ inline bool v_aligned(const VT* V) { return (reinterpret_cast<uintptr_t>(V) & (4
 template <typename VT>
 constexpr bool v_is_f32() { return sizeof(VT) == sizeof(float); }
 
+// Forward for one memory type.  The route is chosen from rep, the shape and alignments; the keep source picks the
+// instantiation on it.  (Pointers, then the keep source, then the integers: the order in which the *_seeded entry points
+// always checked.)
 template <typename VT>
-int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
-                 const uint8_t* keepmask, float keep_prob, float* att, float* pooled, int B, int rep, int R, int H, int D,
-                 void* stream, const KeepSeed* sd = nullptr);
+int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
+                   const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
+    VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
+    VQA_REQUIRE(keep.err == VQA_OK, keep.err);
+    VQA_REQUIRE(!keep.is_seeded() || rep == 1, VQA_ERR_UNSUPPORTED);      // the kernels for several queries per memory have
+    VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);                       // no seeded form ...
+    VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
+    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);         // ... and read an f32 memory only
+    VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
+    VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(pooled) && keep.words_ok(), VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    const uint8_t* keepmask = keep.mask;
+    const float ik = keep.inv_keep();
+    hipStream_t st = (hipStream_t)stream;
+    const bool fast = g_attn_fast && (rep == 1 || rep == 5 || g_attn_fast > 1) && R <= 40 && H % 256 == 0 && H <= 1024 && D % 2048 == 0 && D <= 4096 &&
+                      vqa_aligned16(qv) && vqa_aligned16(w);
+    // the 1024-wide memory (v_adapt of the pre-training model): per-memory kernel for rep 5 only; one query per memory at
+    // D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
+    const bool fast1024 = g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
+                          vqa_aligned16(qv) && vqa_aligned16(w);
+    if constexpr (v_is_f32<VT>()) {
+        // one workgroup per memory for the pre-training model's 5 queries per image (these kernels take "a mask is read"
+        // as a template bool)
+        if (fast1024 || (fast && rep == 5 && g_attn_fast != 3)) {
+            const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
+            int_dispatch<0, 1>(keepmask != nullptr, [&](auto mk) {
+                constexpr bool MASK = decltype(mk)::value != 0;
+                if (fast1024)
+                    hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, MASK, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
+                                       nb, w, bias, keepmask, ik, att, pooled, R);
+                else
+                    int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
+                        int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
+                            hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<decltype(h4l)::value, decltype(d4t)::value, MASK, 5>),
+                                               dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att,
+                                               pooled, R);
+                        });
+                    });
+            });
+            VQA_CHECK_LAUNCH();
+            return VQA_OK;
+        }
+    }
+    const size_t lds = (size_t)(H + R) * sizeof(float);
+    if (fast)
+        int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
+            int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
+                keep_dispatch(keep, [&](auto kp, auto... ks) {
+                    hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<decltype(h4l)::value, decltype(d4t)::value, decltype(kp)::value,
+                                                                  VT, decltype(ks)...>),
+                                       dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled,
+                                       R, rep, ks...);
+                });
+            });
+        });
+    else
+        keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
+            hipLaunchKernelGGL((attn_pool_fwd_kernel<VT, decltype(kp)::value, decltype(ks)...>), dim3(B * rep), dim3(FWD_THREADS),
+                               lds, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, H, D, rep, ks...);
+        });
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
+
 template <typename VT>
-int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
-                 const uint8_t* keepmask, float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
-                 int R, int H, int D, void* stream, const KeepSeed* sd = nullptr);
+int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
+                   const KeepSrc& keep, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H,
+                   int D, void* stream) {
+    VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
+    VQA_REQUIRE(keep.err == VQA_OK, keep.err);
+    VQA_REQUIRE(!keep.is_seeded() || rep == 1, VQA_ERR_UNSUPPORTED);      // as in the forward
+    VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
+    VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
+    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);
+    VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
+    VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(dv) && vqa_aligned16(dqv) &&
+                    vqa_aligned16(part_dw) && vqa_aligned16(qv) && vqa_aligned16(w) && keep.words_ok(),
+                VQA_ERR_ALIGN);
+    if (B == 0) return VQA_OK;
+    const uint8_t* keepmask = keep.mask;
+    const float ik = keep.inv_keep();
+    hipStream_t st = (hipStream_t)stream;
+    auto lds_for = [&](int REPt) { return (size_t)(D + ((REPt * R + 3) / 4) * 4 + REPt * H) * sizeof(float); };
+    VQA_REQUIRE(lds_for(rep == 1 ? 1 : rep <= 5 ? 5 : 8) <= 64 * 1024, VQA_ERR_UNSUPPORTED);
+    // one workgroup per memory: one query at D 2048; the pre-training model's 5 queries at D 2048 and at D 1024 (the
+    // 1024-wide memory; one query per memory at D 1024 stays on the generic kernel)
+    const bool fast_shape = g_attn_fast && H == 1024 && R <= 40 && vqa_aligned16(dpooled);
+    const size_t l = (size_t)(rep * D + rep * 40 + rep * H) * sizeof(float);
+    if (fast_shape && rep == 1 && D == 2048) {
+        keep_dispatch(keep, [&](auto kp, auto... ks) {
+            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<1, decltype(kp)::value, 2048, VT, decltype(ks)...>), dim3(B),
+                               dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H,
+                               ks...);
+        });
+        VQA_CHECK_LAUNCH();
+        return VQA_OK;
+    }
+    if constexpr (v_is_f32<VT>()) {      // several queries per memory
+        if (fast_shape && rep == 5 && (D == 2048 || D == 1024)) {
+            int_dispatch<2048, 1024>(D, [&](auto dd) {
+                int_dispatch<KEEP_BYTES, KEEP_NONE>(keep.policy, [&](auto kp) {
+                    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, decltype(dd)::value>), dim3(B),
+                                       dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db,
+                                       R, H);
+                });
+            });
+            VQA_CHECK_LAUNCH();
+            return VQA_OK;
+        }
+        if (rep > 1) {
+            int_dispatch<5, 8>(rep <= 5 ? 5 : 8, [&](auto rt) {
+                hipLaunchKernelGGL((attn_pool_bwd_kernel<decltype(rt)::value>), dim3(B), dim3(BWD_THREADS),
+                                   lds_for(decltype(rt)::value), st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw,
+                                   part_db, R, H, D, rep);
+            });
+            VQA_CHECK_LAUNCH();
+            return VQA_OK;
+        }
+    }
+    keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
+        hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT, decltype(kp)::value, decltype(ks)...>), dim3(B), dim3(BWD_THREADS),
+                           lds_for(1), st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep, ks...);
+    });
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
+}
 
 }  // namespace
 
@@ -847,6 +969,24 @@ extern "C" int vqa_attn_set_fast(int on) {
     // kernel for the other reps as well; 3 per-query fast kernel for every rep (A/B of the per-memory kernel)
     g_attn_fast = on;
     return VQA_OK;
+}
+
+int vqa_attn_fwd_run(const float* v, const float* qv, const void* V, bool v_bf16, const int32_t* nb, const float* w,
+                     const float* bias, const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D,
+                     void* stream) {
+    if (v_bf16)
+        return attn_fwd_typed(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, keep, att, pooled, B, rep, R, H, D, stream);
+    return attn_fwd_typed(v, qv, static_cast<const float*>(V), nb, w, bias, keep, att, pooled, B, rep, R, H, D, stream);
+}
+
+int vqa_attn_bwd_run(const float* dpooled, const float* v, const float* qv, const void* V, bool v_bf16, const float* att,
+                     const float* w, const KeepSrc& keep, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
+                     int R, int H, int D, void* stream) {
+    if (v_bf16)
+        return attn_bwd_typed(dpooled, v, qv, static_cast<const uint16_t*>(V), att, w, keep, dv, dqv, part_dw, part_db, B, rep, R,
+                              H, D, stream);
+    return attn_bwd_typed(dpooled, v, qv, static_cast<const float*>(V), att, w, keep, dv, dqv, part_dw, part_db, B, rep, R, H, D,
+                          stream);
 }
 
 extern "C" int vqa_attn_pool_fwd(const float* v, const float* qv, const float* V, const int32_t* nb, const float* w,
@@ -858,109 +998,24 @@ extern "C" int vqa_attn_pool_fwd(const float* v, const float* qv, const float* V
 extern "C" int vqa_attn_pool_fwd_rep(const float* v, const float* qv, const float* V, const int32_t* nb,
                                      const float* w, const float* bias, const uint8_t* keepmask, float keep_prob,
                                      float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
-    return attn_fwd_run<float>(v, qv, V, nb, w, bias, keepmask, keep_prob, att, pooled, B, rep, R, H, D, stream);
+    return vqa_attn_fwd_run(v, qv, V, false, nb, w, bias, KeepSrc::bytes(keepmask, keep_prob), att, pooled, B, rep, R, H, D, stream);
 }
 
 // bf16 memory (raw patterns), one query per memory: the kernels vqa_attn_pool_fwd selects for the shape, V loads 8 bytes wide
 extern "C" int vqa_attn_pool_fwd_v16(const float* v, const float* qv, const uint16_t* V, const int32_t* nb, const float* w,
                                      const float* bias, const uint8_t* keepmask, float keep_prob, float* att,
                                      float* pooled, int B, int R, int H, int D, void* stream) {
-    return attn_fwd_run<uint16_t>(v, qv, V, nb, w, bias, keepmask, keep_prob, att, pooled, B, 1, R, H, D, stream);
+    return vqa_attn_fwd_run(v, qv, V, true, nb, w, bias, KeepSrc::bytes(keepmask, keep_prob), att, pooled, B, 1, R, H, D, stream);
 }
 
-namespace {
-template <typename VT>
-int attn_fwd_run(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
-                 const uint8_t* keepmask, float keep_prob, float* att, float* pooled, int B, int rep, int R, int H, int D,
-                 void* stream, const KeepSeed* sd) {      // sd: the keep bits come from the stream (rep == 1, keepmask NULL)
-    VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
-    VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
-    VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
-    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);      // several queries per memory: f32 memory only
-    VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
-    VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(pooled), VQA_ERR_ALIGN);
-    VQA_REQUIRE(keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0, VQA_ERR_ALIGN);
-    if (B == 0) return VQA_OK;
-    const size_t lds = (size_t)(H + R) * sizeof(float);
-    const float ik = (keepmask || sd) ? 1.f / keep_prob : 1.f;
-    hipStream_t st = (hipStream_t)stream;
-    const bool fast = g_attn_fast && (rep == 1 || rep == 5 || g_attn_fast > 1) && R <= 40 && H % 256 == 0 && H <= 1024 && D % 2048 == 0 && D <= 4096 &&
-                      vqa_aligned16(qv) && vqa_aligned16(w);
-    // the 1024-wide memory (v_adapt of the pre-training model): per-memory kernel for rep 5 only; one query per memory at
-    // D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
-    const bool fast1024 = g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
-                          vqa_aligned16(qv) && vqa_aligned16(w);
-    if constexpr (v_is_f32<VT>()) {      // the kernels with several queries per memory (rep == 1 for a bf16 memory, above)
-        if (fast1024) {
-            const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
-            if (keepmask != nullptr)
-                hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, true, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
-                                   nb, w, bias, keepmask, ik, att, pooled, R);
-            else
-                hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, false, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
-                                   nb, w, bias, keepmask, ik, att, pooled, R);
-            VQA_CHECK_LAUNCH();
-            return VQA_OK;
-        }
-        if (fast && rep == 5 && g_attn_fast != 3) {
-            // one workgroup per memory for the pre-training model's 5 queries per image
-            const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
-#define VQA_ATTN_REP5(h4l, d4t)                                                                                        \
-    do {                                                                                                                \
-        if (keepmask != nullptr)                                                                                        \
-            hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<h4l, d4t, true, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v,  \
-                               qv, V, nb, w, bias, keepmask, ik, att, pooled, R);                                       \
-        else                                                                                                            \
-            hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<h4l, d4t, false, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, \
-                               qv, V, nb, w, bias, keepmask, ik, att, pooled, R);                                       \
-    } while (0)
-            const int h4l = H / 256, d4t = D / 2048;
-            if (d4t == 1) {
-                if (h4l == 1) VQA_ATTN_REP5(1, 1); else if (h4l == 2) VQA_ATTN_REP5(2, 1);
-                else if (h4l == 3) VQA_ATTN_REP5(3, 1); else VQA_ATTN_REP5(4, 1);
-            } else {
-                if (h4l == 1) VQA_ATTN_REP5(1, 2); else if (h4l == 2) VQA_ATTN_REP5(2, 2);
-                else if (h4l == 3) VQA_ATTN_REP5(3, 2); else VQA_ATTN_REP5(4, 2);
-            }
-#undef VQA_ATTN_REP5
-            VQA_CHECK_LAUNCH();
-            return VQA_OK;
-        }
-    }
-    if (fast) {
-#define VQA_ATTN_FAST(h4l, d4t)                                                                                         \
-    do {                                                                                                                \
-        if (sd != nullptr)                                                                                              \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, KEEP_SEEDED, VT, KeepSeed>), dim3(B * rep),         \
-                               dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep, *sd); \
-        else if (keepmask != nullptr)                                                                                   \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, KEEP_BYTES, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
-                               qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep);                                  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<h4l, d4t, KEEP_NONE, VT>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, \
-                               qv, V, nb, w, bias, keepmask, ik, att, pooled, R, rep);                                  \
-    } while (0)
-        const int h4l = H / 256, d4t = D / 2048;
-        if (d4t == 1) {
-            if (h4l == 1) VQA_ATTN_FAST(1, 1); else if (h4l == 2) VQA_ATTN_FAST(2, 1);
-            else if (h4l == 3) VQA_ATTN_FAST(3, 1); else VQA_ATTN_FAST(4, 1);
-        } else {
-            if (h4l == 1) VQA_ATTN_FAST(1, 2); else if (h4l == 2) VQA_ATTN_FAST(2, 2);
-            else if (h4l == 3) VQA_ATTN_FAST(3, 2); else VQA_ATTN_FAST(4, 2);
-        }
-#undef VQA_ATTN_FAST
-    } else if (sd != nullptr) {
-        hipLaunchKernelGGL((attn_pool_fwd_kernel<VT, KEEP_SEEDED, KeepSeed>), dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V,
-                           nb, w, bias, keepmask, ik, att, pooled, R, H, D, rep, *sd);
-    } else {
-        hipLaunchKernelGGL(attn_pool_fwd_kernel<VT>, dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias,
-                           keepmask, ik, att, pooled, R, H, D, rep);
-    }
-    VQA_CHECK_LAUNCH();
-    return VQA_OK;
+// The keep bits of the score's dropout computed in the kernel instead of loaded: the kernels the explicit entry points
+// select for the shape (same route selection), instantiated with KEEP_SEEDED.  One query per memory.
+extern "C" int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int v_bf16, const int32_t* nb,
+                                        const float* w, const float* bias, uint64_t seed, uint64_t offset, float keep_prob,
+                                        float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
+    return vqa_attn_fwd_run(v, qv, V, v_bf16 != 0, nb, w, bias, KeepSrc::seeded(seed, offset, H, keep_prob), att, pooled, B, rep,
+                            R, H, D, stream);
 }
-}  // namespace
 
 extern "C" int vqa_attn_pool_bwd(const float* dpooled, const float* v, const float* qv, const float* V,
                                  const float* att, const float* w, const uint8_t* keepmask, float keep_prob, float* dv,
@@ -973,113 +1028,23 @@ extern "C" int vqa_attn_pool_bwd_rep(const float* dpooled, const float* v, const
                                      const float* att, const float* w, const uint8_t* keepmask, float keep_prob,
                                      float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R,
                                      int H, int D, void* stream) {
-    return attn_bwd_run<float>(dpooled, v, qv, V, att, w, keepmask, keep_prob, dv, dqv, part_dw, part_db, B, rep, R, H, D,
-                               stream);
+    return vqa_attn_bwd_run(dpooled, v, qv, V, false, att, w, KeepSrc::bytes(keepmask, keep_prob), dv, dqv, part_dw, part_db, B,
+                            rep, R, H, D, stream);
 }
 
 extern "C" int vqa_attn_pool_bwd_v16(const float* dpooled, const float* v, const float* qv, const uint16_t* V,
                                      const float* att, const float* w, const uint8_t* keepmask, float keep_prob, float* dv,
                                      float* dqv, float* part_dw, float* part_db, int B, int R, int H, int D, void* stream) {
-    return attn_bwd_run<uint16_t>(dpooled, v, qv, V, att, w, keepmask, keep_prob, dv, dqv, part_dw, part_db, B, 1, R, H, D,
-                                  stream);
-}
-
-namespace {
-template <typename VT>
-int attn_bwd_run(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
-                 const uint8_t* keepmask, float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
-                 int R, int H, int D, void* stream, const KeepSeed* sd) {
-    VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
-    VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
-    VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
-    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);      // several queries per memory: f32 memory only
-    VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
-    VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(dv) && vqa_aligned16(dqv) &&
-                    vqa_aligned16(part_dw) && vqa_aligned16(qv) && vqa_aligned16(w),
-                VQA_ERR_ALIGN);
-    VQA_REQUIRE(keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0, VQA_ERR_ALIGN);
-    if (B == 0) return VQA_OK;
-    const float ik = (keepmask || sd) ? 1.f / keep_prob : 1.f;
-    hipStream_t st = (hipStream_t)stream;
-    auto lds_for = [&](int REPt) { return (size_t)(D + ((REPt * R + 3) / 4) * 4 + REPt * H) * sizeof(float); };
-    VQA_REQUIRE(lds_for(rep == 1 ? 1 : rep <= 5 ? 5 : 8) <= 64 * 1024, VQA_ERR_UNSUPPORTED);
-    if (g_attn_fast && (rep == 1 || rep == 5) && D == 2048 && H == 1024 && R <= 40 && vqa_aligned16(dpooled)) {
-        const size_t l = (size_t)(rep * D + rep * 40 + rep * H) * sizeof(float);
-#define VQA_ATTN_BWD_FAST(r, mk)                                                                                       \
-    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<r, mk, 2048, VT>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, \
-                       keepmask, ik, dv, dqv, part_dw, part_db, R, H)
-        if (rep == 1 && sd != nullptr)
-            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<1, KEEP_SEEDED, 2048, VT, KeepSeed>), dim3(B), dim3(BWD_THREADS), l, st,
-                               dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H, *sd);
-        else if (rep == 1) { if (keepmask) VQA_ATTN_BWD_FAST(1, KEEP_BYTES); else VQA_ATTN_BWD_FAST(1, KEEP_NONE); }
-        else if constexpr (v_is_f32<VT>()) { if (keepmask) VQA_ATTN_BWD_FAST(5, KEEP_BYTES); else VQA_ATTN_BWD_FAST(5, KEEP_NONE); }
-#undef VQA_ATTN_BWD_FAST
-        VQA_CHECK_LAUNCH();
-        return VQA_OK;
-    }
-    if constexpr (v_is_f32<VT>()) {
-        if (g_attn_fast && rep == 5 && D == 1024 && H == 1024 && R <= 40 && vqa_aligned16(dpooled)) {
-            // the 1024-wide memory at 5 queries per memory; rep 1 at D 1024 stays on the generic kernel below
-            const size_t l = (size_t)(5 * D + 5 * 40 + 5 * H) * sizeof(float);
-            if (keepmask)
-                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, KEEP_BYTES, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
-                                   V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
-            else
-                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, KEEP_NONE, 1024>), dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv,
-                                   V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H);
-            VQA_CHECK_LAUNCH();
-            return VQA_OK;
-        }
-    }
-    if (rep == 1 && sd != nullptr)
-        hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT, KEEP_SEEDED, KeepSeed>), dim3(B), dim3(BWD_THREADS), lds_for(1), st, dpooled, v,
-                           qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep, *sd);
-    else if (rep == 1)
-        hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT>), dim3(B), dim3(BWD_THREADS), lds_for(1), st, dpooled, v, qv, V, att, w,
-                           keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
-    else if constexpr (!v_is_f32<VT>())
-        return VQA_ERR_UNSUPPORTED;
-    else if (rep <= 5)
-        hipLaunchKernelGGL(attn_pool_bwd_kernel<5>, dim3(B), dim3(BWD_THREADS), lds_for(5), st, dpooled, v, qv, V, att, w,
-                           keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
-    else
-        hipLaunchKernelGGL(attn_pool_bwd_kernel<8>, dim3(B), dim3(BWD_THREADS), lds_for(8), st, dpooled, v, qv, V, att, w,
-                           keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep);
-    VQA_CHECK_LAUNCH();
-    return VQA_OK;
-}
-}  // namespace
-
-// The keep bits of the score's dropout computed in the kernel instead of loaded: the kernels the explicit entry points
-// select for the shape (same route selection), instantiated with KEEP_SEEDED.  One query per memory.
-extern "C" int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int v_bf16, const int32_t* nb,
-                                        const float* w, const float* bias, uint64_t seed, uint64_t offset, float keep_prob,
-                                        float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
-    VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
-    VQA_REQUIRE_KEEP_SEED(offset, H, keep_prob);
-    VQA_REQUIRE(rep == 1, VQA_ERR_UNSUPPORTED);
-    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
-    if (v_bf16)
-        return attn_fwd_run<uint16_t>(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, nullptr, keep_prob, att, pooled, B, 1,
-                                      R, H, D, stream, &sd);
-    return attn_fwd_run<float>(v, qv, static_cast<const float*>(V), nb, w, bias, nullptr, keep_prob, att, pooled, B, 1, R, H, D,
-                               stream, &sd);
+    return vqa_attn_bwd_run(dpooled, v, qv, V, true, att, w, KeepSrc::bytes(keepmask, keep_prob), dv, dqv, part_dw, part_db, B, 1,
+                            R, H, D, stream);
 }
 
 extern "C" int vqa_attn_pool_bwd_seeded(const float* dpooled, const float* v, const float* qv, const void* V, int v_bf16,
                                         const float* att, const float* w, uint64_t seed, uint64_t offset, float keep_prob,
                                         float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H,
                                         int D, void* stream) {
-    VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
-    VQA_REQUIRE_KEEP_SEED(offset, H, keep_prob);
-    VQA_REQUIRE(rep == 1, VQA_ERR_UNSUPPORTED);
-    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
-    if (v_bf16)
-        return attn_bwd_run<uint16_t>(dpooled, v, qv, static_cast<const uint16_t*>(V), att, w, nullptr, keep_prob, dv, dqv,
-                                      part_dw, part_db, B, 1, R, H, D, stream, &sd);
-    return attn_bwd_run<float>(dpooled, v, qv, static_cast<const float*>(V), att, w, nullptr, keep_prob, dv, dqv, part_dw,
-                               part_db, B, 1, R, H, D, stream, &sd);
+    return vqa_attn_bwd_run(dpooled, v, qv, V, v_bf16 != 0, att, w, KeepSrc::seeded(seed, offset, H, keep_prob), dv, dqv, part_dw,
+                            part_db, B, rep, R, H, D, stream);
 }
 
 // The chain v_linear_v's LayerNorm -> attention score and its gradient at the one shape of the register-resident

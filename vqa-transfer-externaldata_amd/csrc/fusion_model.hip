@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "vqa_common.h"
+#include "keep_launch.h"
 
 namespace {
 
@@ -447,53 +447,15 @@ inline int64_t pooled_dim(const vqa_dims_t& d) { return d.model_type == VQA_MODE
 
 // One dropout site of the step (VQA_KEEP_SITE_*): the explicit mask of the batch (or NULL: no dropout), or, where the
 // site's bit of vqa_batch_t.keep_seeded is set, the stream position its bits are drawn from inside the consuming kernels.
-// Every mask site of the forward and the backward resolves through keep_site() and calls the op through the members below,
-// which pick the explicit or the seeded entry point; the batch struct carries everything, nothing is remembered here.
+// Every mask site of the forward and the backward resolves through keep_site() and hands src() to the op's launch function
+// (keep_launch.h), which picks the kernel; the batch struct carries everything, nothing is remembered here.
 struct KeepSite {
     const uint8_t* mask;
     bool seeded;
     uint64_t seed, off;
-
-    int ln_relu_fwd(const float* pre, const float* gamma, const float* beta, float keep_prob, float* y, float* mean, float* rstd,
-                    int G, int rows, int N, void* st) const {
-        if (seeded) return vqa_ln_act_fwd_seeded(pre, gamma, beta, seed, off, keep_prob, y, mean, rstd, G, rows, N, 0, st);
-        return vqa_ln_relu_fwd(pre, gamma, beta, mask, keep_prob, y, mean, rstd, G, rows, N, st);
-    }
-    int ln_relu_bwd(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma, const float* beta,
-                    float keep_prob, float* dpre, float* pdg, float* pdb, float* pdbias, int G, int rows, int N, void* st) const {
-        if (seeded)
-            return vqa_ln_act_bwd_seeded(dy, pre, mean, rstd, gamma, beta, seed, off, keep_prob, dpre, pdg, pdb, pdbias, G, rows, N,
-                                         0, st);
-        return vqa_ln_relu_bwd(dy, pre, mean, rstd, gamma, beta, mask, keep_prob, dpre, pdg, pdb, pdbias, G, rows, N, st);
-    }
-    // V: float, or raw bf16 patterns (v16)
-    int attn_pool_fwd(const float* v, const float* qv, const void* V, bool v16, const int32_t* nb, const float* w, const float* bias,
-                      float keep_prob, float* att, float* pooled, int B, int R, int H, int D, void* st) const {
-        if (seeded) return vqa_attn_pool_fwd_seeded(v, qv, V, v16 ? 1 : 0, nb, w, bias, seed, off, keep_prob, att, pooled, B, 1, R, H, D, st);
-        if (v16)
-            return vqa_attn_pool_fwd_v16(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, mask, keep_prob, att, pooled, B, R, H, D, st);
-        return vqa_attn_pool_fwd(v, qv, static_cast<const float*>(V), nb, w, bias, mask, keep_prob, att, pooled, B, R, H, D, st);
-    }
-    int attn_pool_bwd(const float* dpooled, const float* v, const float* qv, const void* V, bool v16, const float* att, const float* w,
-                      float keep_prob, float* dv, float* dqv, float* part_dw, float* part_db, int B, int R, int H, int D,
-                      void* st) const {
-        if (seeded)
-            return vqa_attn_pool_bwd_seeded(dpooled, v, qv, V, v16 ? 1 : 0, att, w, seed, off, keep_prob, dv, dqv, part_dw, part_db, B, 1,
-                                            R, H, D, st);
-        if (v16)
-            return vqa_attn_pool_bwd_v16(dpooled, v, qv, static_cast<const uint16_t*>(V), att, w, mask, keep_prob, dv, dqv, part_dw,
-                                         part_db, B, R, H, D, st);
-        return vqa_attn_pool_bwd(dpooled, v, qv, static_cast<const float*>(V), att, w, mask, keep_prob, dv, dqv, part_dw, part_db, B, R,
-                                 H, D, st);
-    }
-    int ln_relu_att_bwd(const float* ds, const float* qv, const float* w, float keep_prob, const float* pre, const float* mean,
-                        const float* rstd, const float* gamma, const float* beta, float* dpre, float* pdg, float* pdb, float* pdbias,
-                        float* dqv, float* part_dw, int B, int R, int H, int D, void* st) const {
-        if (seeded)
-            return vqa_ln_relu_att_bwd_seeded(ds, qv, w, seed, off, keep_prob, pre, mean, rstd, gamma, beta, dpre, pdg, pdb, pdbias, dqv,
-                                              part_dw, B, 1, R, H, D, st);
-        return vqa_ln_relu_att_bwd(ds, qv, w, mask, keep_prob, pre, mean, rstd, gamma, beta, dpre, pdg, pdb, pdbias, dqv, part_dw, B, 1, R,
-                                   H, D, st);
+    // the keep source of an op on this site whose rows are row_len long
+    KeepSrc src(float keep_prob, int64_t row_len) const {
+        return seeded ? KeepSrc::seeded(seed, off, row_len, keep_prob) : KeepSrc::bytes(mask, keep_prob);
     }
 };
 const KeepSite NO_KEEP = {nullptr, false, 0, 0};      // a layer without dropout
@@ -527,8 +489,8 @@ int fc_ln_relu_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N
         TRY(gemm_x(c, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
     }
     ProbeScope ps(rows > 1 ? "v_linear_v.ln_fwd" : "fc.ln_fwd", c.st);
-    return keep.ln_relu_fwd(c.f(pre), p.gamma, p.beta, keep_prob, c.f(y), c.f(mean), c.f(rstd), (int)(M / rows), rows, (int)N,
-                            c.st);
+    return vqa_ln_act_fwd_run(c.f(pre), p.gamma, p.beta, keep.src(keep_prob, N), c.f(y), c.f(mean), c.f(rstd), (int)(M / rows), rows,
+                              (int)N, 0, c.st);
 }
 
 // the FC half of the backward once d_pre is known: parameter gradients from the per-group partials (g.w == NULL => frozen
@@ -561,9 +523,9 @@ int fc_ln_relu_bwd(const Ctx& c, const float* dy, const float* x, int64_t M, int
     const int64_t G = M / rows;
     {
         ProbeScope ps(rows > 1 ? "v_linear_v.ln_bwd" : "fc.ln_bwd", c.st);
-        TRY(keep.ln_relu_bwd(dy, c.f(pre), c.f(mean), c.f(rstd), p.gamma, p.beta, keep_prob, c.f(d_pre),
-                             train ? c.part(0) : nullptr, train ? c.part(1) : nullptr,
-                             train ? c.part(2) : nullptr, (int)G, rows, (int)N, c.st));
+        TRY(vqa_ln_act_bwd_run(dy, c.f(pre), c.f(mean), c.f(rstd), p.gamma, p.beta, keep.src(keep_prob, N), c.f(d_pre),
+                               train ? c.part(0) : nullptr, train ? c.part(1) : nullptr,
+                               train ? c.part(2) : nullptr, (int)G, rows, (int)N, 0, c.st));
     }
     return fc_bwd_tail(c, x, M, K, N, p, g, rows, c.f(d_pre), c.part(0), c.part(1), c.part(2), dx, dx_accumulate);
 }
@@ -622,9 +584,9 @@ int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt) 
                        NO_KEEP, 1.f));
     TRY(fc_ln_relu_fwd(c, c.f("e2"), B * T, W, H, P->v_word_fc, (int)T, "pre_vw", "q_v_ft", "mean_vw", "rstd_vw", NO_KEEP, 1.f));
     ProbeScope ps("attn_pool.fwd", c.st);
-    return keep_site(bt, VQA_KEEP_SITE_WORD)
-        .attn_pool_fwd(c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), false, bt->q_intseq_len, P->word_score.w, P->word_score.b,
-                       d.keep_att, c.f("w_att_score"), c.f("pooled_q_v"), (int)B, (int)T, (int)H, (int)H, c.st);
+    return vqa_attn_fwd_run(c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), false, bt->q_intseq_len, P->word_score.w,
+                            P->word_score.b, keep_site(bt, VQA_KEEP_SITE_WORD).src(d.keep_att, H), c.f("w_att_score"),
+                            c.f("pooled_q_v"), (int)B, 1, (int)T, (int)H, (int)H, c.st);
 }
 
 // everything between d(pooled_q_v) / d(q_L_ft) and the two recurrences' inputs: word attention, v_word_fc (+ the second
@@ -634,10 +596,9 @@ int bi_question_bwd_head(const Ctx& c, const vqa_params_t* P, const vqa_params_t
     const int64_t B = d.B, H = d.H, T = d.T, W = d.W;
     {
         ProbeScope ps("attn_pool.bwd", c.st);
-        TRY(keep_site(bt, VQA_KEEP_SITE_WORD)
-                .attn_pool_bwd(c.f("d_pooled_qv"), c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), false, c.f("w_att_score"),
-                               P->word_score.w, d.keep_att, c.f("d_key"), c.f("d_query"), c.f("part_wdw"), c.f("part_wdb"), (int)B,
-                               (int)T, (int)H, (int)H, c.st));
+        TRY(vqa_attn_bwd_run(c.f("d_pooled_qv"), c.f("q_att_key"), c.f("q_att_query"), c.f("q_v_ft"), false, c.f("w_att_score"),
+                             P->word_score.w, keep_site(bt, VQA_KEEP_SITE_WORD).src(d.keep_att, H), c.f("d_key"), c.f("d_query"),
+                             c.f("part_wdw"), c.f("part_wdb"), (int)B, 1, (int)T, (int)H, (int)H, c.st));
         if (G->word_score.w != nullptr) {
             TRY(colsum(c, c.f("part_wdw"), B, H, (int)H, G->word_score.w));
             TRY(colsum(c, c.f("part_wdb"), B, 1, 1, G->word_score.b));
@@ -1002,9 +963,9 @@ int fwd_attention(const Step& s) {
     ProbeScope ps("attn_pool.fwd", c.st);
     const bool v16 = feat16(s.d);
     const void* V = v16 ? (const void*)c.u16("V_ft") : (const void*)c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft");
-    return keep_site(s.bt, VQA_KEEP_SITE_ATT)
-        .attn_pool_fwd(c.f("v_linear_v"), c.f("q_linear_v"), V, v16, c.i32("num_V_ft"), s.P->score.w, s.P->score.b, s.d.keep_att,
-                       c.f("att_score"), c.f("pooled_V_ft"), (int)s.B, (int)s.R, (int)s.H, (int)s.Dp, c.st);
+    return vqa_attn_fwd_run(c.f("v_linear_v"), c.f("q_linear_v"), V, v16, c.i32("num_V_ft"), s.P->score.w, s.P->score.b,
+                            keep_site(s.bt, VQA_KEEP_SITE_ATT).src(s.d.keep_att, s.H), c.f("att_score"), c.f("pooled_V_ft"),
+                            (int)s.B, 1, (int)s.R, (int)s.H, (int)s.Dp, c.st);
 }
 
 // a8: pooled_linear_l and q_linear_l; the paired form also leaves their product in joint_in
@@ -1115,9 +1076,9 @@ int fwd_loss(const Step& s, int want_dz) {
         TRY(vqa_tile_mul_fwd(c.f("pooled_linear_l"), c.f("l_linear_l"), c.f("tile_in"), (int)B, (int)M, (int)H, c.st));
         TRY(gemm(c, 0, 0, B * M, 2 * H, H, c.f("tile_in"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("pre_tj"), (int)(2 * H),
                  P->joint_fc.b));
-        TRY(keep_site(bt, VQA_KEEP_SITE_TILE)
-                .ln_relu_fwd(c.f("pre_tj"), P->joint_fc.gamma, P->joint_fc.beta, s.d.keep_joint, c.f("tile_joint"), c.f("mean_tj"),
-                             c.f("rstd_tj"), (int)B, (int)M, (int)(2 * H), c.st));
+        TRY(vqa_ln_act_fwd_run(c.f("pre_tj"), P->joint_fc.gamma, P->joint_fc.beta,
+                               keep_site(bt, VQA_KEEP_SITE_TILE).src(s.d.keep_joint, 2 * H), c.f("tile_joint"), c.f("mean_tj"),
+                               c.f("rstd_tj"), (int)B, (int)M, (int)(2 * H), 0, c.st));
         TRY(gemm(c, 0, 0, B * M, C, 2 * H, c.f("tile_joint"), (int)(2 * H), P->head.w, (int)A, c.f("tile_z"), (int)C, P->head.b));
         TRY(vqa_marginal_entropy(c.f("tile_z"), bt->train_mask, bt->exist_mask, s.d.extra_weight * s.d.inv_global_batch,
                                  c.f("marginal_prob"), c.f("extra_row"), (int)B, (int)M, (int)C, (int)C, want_dz, c.st));
@@ -1242,9 +1203,9 @@ int bwd_entropy(const Step& s) {
     ProbeScope ps("ent.bwd", c.st);
     const int64_t M = s.d.num_marginal, C = s.d.ent_cols;
     TRY(gemm(c, 0, 1, B * M, 2 * H, C, c.f("tile_z"), (int)C, P->head.w, (int)A, c.f("d_tile_joint"), (int)(2 * H)));
-    TRY(keep_site(s.bt, VQA_KEEP_SITE_TILE)
-            .ln_relu_bwd(c.f("d_tile_joint"), c.f("pre_tj"), c.f("mean_tj"), c.f("rstd_tj"), P->joint_fc.gamma, P->joint_fc.beta,
-                         s.d.keep_joint, c.f("d_pre_tj"), nullptr, nullptr, nullptr, (int)B, (int)M, (int)(2 * H), c.st));
+    TRY(vqa_ln_act_bwd_run(c.f("d_tile_joint"), c.f("pre_tj"), c.f("mean_tj"), c.f("rstd_tj"), P->joint_fc.gamma, P->joint_fc.beta,
+                           keep_site(s.bt, VQA_KEEP_SITE_TILE).src(s.d.keep_joint, 2 * H), c.f("d_pre_tj"), nullptr, nullptr, nullptr,
+                           (int)B, (int)M, (int)(2 * H), 0, c.st));
     TRY(gemm(c, 0, 1, B * M, H, 2 * H, c.f("d_pre_tj"), (int)(2 * H), P->joint_fc.w, (int)(2 * H), c.f("d_tile_in"), (int)H));
     // (paired LayerNorm backward: d_ll holds only this extra gradient and is added inside that kernel)
     return vqa_tile_mul_bwd(c.f("d_tile_in"), c.f("pooled_linear_l"), c.f("d_ll"), (int)B, (int)M, (int)H, s.pair ? 0 : 1, c.st);
@@ -1372,10 +1333,10 @@ int bwd_attention(Step& s) {
         }
         {
             ProbeScope ps("v_linear_v.ln_bwd", c.st);
-            TRY(keep_site(bt, VQA_KEEP_SITE_ATT)
-                    .ln_relu_att_bwd(c.f("ds"), c.f("q_linear_v"), P->score.w, s.d.keep_att, c.f("pre_v"), c.f("mean_v"),
-                                     c.f("rstd_v"), P->v_linear_v.gamma, P->v_linear_v.beta, c.f("d_pre_v"), c.part(0), c.part(1),
-                                     c.part(2), c.f("d_qv"), c.f("part_dw"), (int)B, (int)R, (int)H, (int)D, c.st));
+            TRY(vqa_ln_relu_att_bwd_run(c.f("ds"), c.f("q_linear_v"), P->score.w, keep_site(bt, VQA_KEEP_SITE_ATT).src(s.d.keep_att, H),
+                                        c.f("pre_v"), c.f("mean_v"), c.f("rstd_v"), P->v_linear_v.gamma, P->v_linear_v.beta,
+                                        c.f("d_pre_v"), c.part(0), c.part(1), c.part(2), c.f("d_qv"), c.f("part_dw"), (int)B, 1, (int)R,
+                                        (int)H, (int)D, c.st));
             TRY(vqa_colsum_vtail(c.part(0), c.part(1), c.part(2), c.f("part_dw"), c.f("part_db"), (int)B, (int)H,
                                  G->v_linear_v.gamma, G->v_linear_v.beta, G->v_linear_v.b, G->score.w, G->score.b, c.colsum_ws(),
                                  c.colsum_ws_floats(), c.st));
@@ -1387,10 +1348,9 @@ int bwd_attention(Step& s) {
         ProbeScope ps("attn_pool.bwd", c.st);
         const bool v16 = feat16(s.d);
         const void* V = v16 ? (const void*)c.u16("V_ft") : (const void*)c.f(s.mt == VQA_MODEL_ADAPT ? "v_adapt" : "V_ft");
-        TRY(keep_site(bt, VQA_KEEP_SITE_ATT)
-                .attn_pool_bwd(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), V, v16, c.f("att_score"), P->score.w,
-                               s.d.keep_att, c.f("d_v"), c.f("d_qv"), c.f("part_dw"), c.f("part_db"), (int)B, (int)R, (int)H,
-                               (int)Dp, c.st));
+        TRY(vqa_attn_bwd_run(c.f("d_pooled"), c.f("v_linear_v"), c.f("q_linear_v"), V, v16, c.f("att_score"), P->score.w,
+                             keep_site(bt, VQA_KEEP_SITE_ATT).src(s.d.keep_att, H), c.f("d_v"), c.f("d_qv"), c.f("part_dw"),
+                             c.f("part_db"), (int)B, 1, (int)R, (int)H, (int)Dp, c.st));
     }
     if (s.mt == VQA_MODEL_ADAPT) {
         // the pooled memory is trainable here: d v_adapt = att (x) d pooled, then LN[R,H] + ReLU + FC backward (V_ft is an

@@ -1,0 +1,26 @@
+// Launch functions of the kernels that have a dropout site (layernorm.hip, attention.hip), with the site's keep source
+// as a KeepSrc: what the explicit-mask and the *_seeded entry points of the C ABI wrap, and what the fusion step calls
+// directly (fusion_model.hip).  Same checks and return codes as the entry points; a combination of keep source, queries
+// per memory and memory type that has no kernel is refused here.  Internal: nothing here is part of the C ABI.
+#pragma once
+#include "vqa_common.h"
+
+// layernorm.hip.  act: 0 ReLU, 1 tanh.  Seeded: the 16-byte route only (VQA_ERR_ALIGN on the route of single columns)
+int vqa_ln_act_fwd_run(const float* pre, const float* gamma, const float* beta, const KeepSrc& keep, float* y, float* mean,
+                       float* rstd, int G, int rows, int N, int act, void* stream);
+int vqa_ln_act_bwd_run(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma,
+                       const float* beta, const KeepSrc& keep, float* dpre, float* part_dgamma, float* part_dbeta,
+                       float* part_dbias, int G, int rows, int N, int act, void* stream);
+int vqa_ln_relu_att_bwd_run(const float* ds, const float* qv, const float* w, const KeepSrc& keep, const float* pre,
+                            const float* mean, const float* rstd, const float* gamma, const float* beta, float* dpre,
+                            float* part_dgamma, float* part_dbeta, float* part_dbias, float* dqv, float* part_dw, int B, int rep,
+                            int R, int H, int D, void* stream);
+
+// attention.hip.  V: float, or raw bf16 patterns (v_bf16).  Seeded, and a bf16 memory: one query per memory (rep == 1)
+// only, VQA_ERR_UNSUPPORTED otherwise
+int vqa_attn_fwd_run(const float* v, const float* qv, const void* V, bool v_bf16, const int32_t* nb, const float* w,
+                     const float* bias, const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D,
+                     void* stream);
+int vqa_attn_bwd_run(const float* dpooled, const float* v, const float* qv, const void* V, bool v_bf16, const float* att,
+                     const float* w, const KeepSrc& keep, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
+                     int R, int H, int D, void* stream);

@@ -10,7 +10,7 @@
 // statistics passes and the normalise pass, so HBM sees one read + one write.
 // Thread layout: (column unit cx, row lane ry); a column unit is 4 consecutive
 // columns (float4) when N % 4 == 0.
-#include "vqa_common.h"
+#include "keep_launch.h"
 
 namespace {
 
@@ -232,6 +232,7 @@ __global__ void ln_relu_bwd_kernel(const float* __restrict__ dy, const float* __
 // attention.hip on what hipcc does with guarded float4 loads.)
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int REG_CUT = 256, REG_RY = 4;
+constexpr size_t REG_BWD_LDS = (size_t)2 * REG_RY * REG_CUT * 4 * sizeof(float);      // the backward forms' two column-reduce buffers
 
 // RPT rows and CPT float4 column units (cx, cx + 256) per thread; EXACT: rows == REG_RY * RPT, no clamp and no guard
 // (the 36-row kernel must not grow: 117 VGPRs in the backward); otherwise rows <= REG_RY * RPT, row indices are
@@ -537,11 +538,17 @@ inline int reg_mode(int U, int rows, int N) {
     return 0;
 }
 
+// template arguments of the register-resident kernels per reg_mode()
+template <int RM>
+struct RegForm {
+    static constexpr int RPT = RM == 1 ? 9 : 2, CPT = RM == 3 ? 2 : 1;
+    static constexpr bool EXACT = RM == 1;
+};
+
 struct Shape { int U, CUt, RY, threads; };
-Shape pick(const void* a, const void* b, const void* c, int rows, int N, bool mask) {
+Shape pick(const void* a, const void* b, const void* c, int rows, int N) {
     Shape s;
     const bool vec = (N % 4 == 0) && vqa_aligned16(a) && vqa_aligned16(b) && (c == nullptr || vqa_aligned16(c));
-    (void)mask;
     s.U = vec ? 4 : 1;
     const int CU = N / s.U;
     s.CUt = std::min(CU, 256);
@@ -550,6 +557,11 @@ Shape pick(const void* a, const void* b, const void* c, int rows, int N, bool ma
     s.RY = rows >= 4 ? 4 : 1;
     s.threads = s.CUt * s.RY;
     return s;
+}
+// the route of single columns, for a 16-byte shape whose other operands turn out not to be aligned
+Shape scalar_shape(const Shape& s, int N) {
+    const int CUt = std::min(256, ((std::min(N, 256) + 63) / 64) * 64);
+    return Shape{1, CUt, s.RY, CUt * s.RY};
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -764,51 +776,35 @@ extern "C" int vqa_ln_set_fast(int on) {
     return VQA_OK;
 }
 
-extern "C" int vqa_ln_relu_fwd(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
-                               float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N,
-                               void* stream) {
-    return vqa_ln_act_fwd(pre, gamma, beta, keepmask, keep_prob, y, mean, rstd, G, rows, N, 0, stream);
-}
-
-// sd: the keep bits come from the stream (keepmask NULL); the route is the explicit form's, and the route of single
-// columns, which has no 4-byte mask words, is refused
-static int ln_act_fwd_run(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
-                          float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
-                          void* stream, const KeepSeed* sd) {
-    VQA_REQUIRE(act == 0 || act == 1, VQA_ERR_ARG);
-    VQA_REQUIRE(pre && gamma && beta && y && mean && rstd && G >= 0 && rows > 0 && N > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
-    Shape s = pick(pre, y, nullptr, rows, N, keepmask != nullptr);
-    if (s.U == 4 && !(vqa_aligned16(gamma) && vqa_aligned16(beta) &&
-                      (keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0)))
-        s = Shape{1, std::min(256, ((std::min(N, 256) + 63) / 64) * 64), s.RY, 0};
-    VQA_REQUIRE(sd == nullptr || s.U == 4, VQA_ERR_ALIGN);
+// The route is chosen from shapes and alignments alone; the keep source picks the instantiation on it.  The route of
+// single columns has no 4-byte mask words: a mask that is not 4-byte aligned takes it, seeded keep bits are refused there.
+// (Pointers, then the keep source, then the integers: the order in which the *_seeded entry points always checked.)
+int vqa_ln_act_fwd_run(const float* pre, const float* gamma, const float* beta, const KeepSrc& keep, float* y, float* mean,
+                       float* rstd, int G, int rows, int N, int act, void* stream) {
+    VQA_REQUIRE(pre && gamma && beta && y && mean && rstd, VQA_ERR_ARG);
+    VQA_REQUIRE(keep.err == VQA_OK, keep.err);
+    VQA_REQUIRE((act == 0 || act == 1) && G >= 0 && rows > 0 && N > 0, VQA_ERR_ARG);
+    Shape s = pick(pre, y, nullptr, rows, N);
+    if (s.U == 4 && !(vqa_aligned16(gamma) && vqa_aligned16(beta) && keep.words_ok())) s = scalar_shape(s, N);
+    VQA_REQUIRE(!keep.is_seeded() || s.U == 4, VQA_ERR_ALIGN);
     if (G == 0) return VQA_OK;
-    s.threads = s.CUt * s.RY;
-    const float inv_keep = (keepmask || sd) ? 1.f / keep_prob : 1.f;
+    const uint8_t* keepmask = keep.mask;
+    const float inv_keep = keep.inv_keep();
     hipStream_t st = (hipStream_t)stream;
     const int rm = act == 0 ? reg_mode(s.U, rows, N) : 0;
-    if (rm != 0) {
-#define VQA_LN_FWD_REG(rpt, cpt, exact)                                                                                    \
-    do {                                                                                                                 \
-        if (sd != nullptr)                                                                                               \
-            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, KEEP_SEEDED, exact, KeepSeed>), dim3(G), dim3(REG_CUT * REG_RY), \
-                               0, st, pre, gamma, beta, keepmask, inv_keep, y, mean, rstd, rows, *sd);                   \
-        else if (keepmask != nullptr)                                                                                    \
-            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, KEEP_BYTES, exact>), dim3(G), dim3(REG_CUT * REG_RY), 0, st, pre, \
-                               gamma, beta, keepmask, inv_keep, y, mean, rstd, rows);                                    \
-        else                                                                                                             \
-            hipLaunchKernelGGL((ln_fwd_reg_kernel<rpt, cpt, KEEP_NONE, exact>), dim3(G), dim3(REG_CUT * REG_RY), 0, st, pre, \
-                               gamma, beta, keepmask, inv_keep, y, mean, rstd, rows);                                    \
-    } while (0)
-        if (rm == 1) VQA_LN_FWD_REG(9, 1, true); else if (rm == 2) VQA_LN_FWD_REG(2, 1, false); else VQA_LN_FWD_REG(2, 2, false);
-#undef VQA_LN_FWD_REG
-    } else if (sd != nullptr)
-        hipLaunchKernelGGL((ln_relu_fwd_kernel<4, KEEP_SEEDED, KeepSeed>), dim3(G), dim3(s.threads), 0, st, pre, gamma, beta,
-                           keepmask, inv_keep, y, mean, rstd, rows, N, s.CUt, s.RY, act, *sd);
+    if (rm != 0)
+        int_dispatch<1, 2, 3>(rm, [&](auto m) {
+            using F = RegForm<decltype(m)::value>;
+            keep_dispatch(keep, [&](auto kp, auto... ks) {
+                hipLaunchKernelGGL((ln_fwd_reg_kernel<F::RPT, F::CPT, decltype(kp)::value, F::EXACT, decltype(ks)...>), dim3(G),
+                                   dim3(REG_CUT * REG_RY), 0, st, pre, gamma, beta, keepmask, inv_keep, y, mean, rstd, rows, ks...);
+            });
+        });
     else if (s.U == 4)
-        hipLaunchKernelGGL(ln_relu_fwd_kernel<4>, dim3(G), dim3(s.threads), 0, st, pre, gamma, beta, keepmask, inv_keep,
-                           y, mean, rstd, rows, N, s.CUt, s.RY, act);
+        keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
+            hipLaunchKernelGGL((ln_relu_fwd_kernel<4, decltype(kp)::value, decltype(ks)...>), dim3(G), dim3(s.threads), 0, st, pre,
+                               gamma, beta, keepmask, inv_keep, y, mean, rstd, rows, N, s.CUt, s.RY, act, ks...);
+        });
     else
         hipLaunchKernelGGL(ln_relu_fwd_kernel<1>, dim3(G), dim3(s.threads), 0, st, pre, gamma, beta, keepmask, inv_keep,
                            y, mean, rstd, rows, N, s.CUt, s.RY, act);
@@ -816,19 +812,64 @@ static int ln_act_fwd_run(const float* pre, const float* gamma, const float* bet
     return VQA_OK;
 }
 
+extern "C" int vqa_ln_relu_fwd(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
+                               float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N,
+                               void* stream) {
+    return vqa_ln_act_fwd(pre, gamma, beta, keepmask, keep_prob, y, mean, rstd, G, rows, N, 0, stream);
+}
+
 extern "C" int vqa_ln_act_fwd(const float* pre, const float* gamma, const float* beta, const uint8_t* keepmask,
                               float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
                               void* stream) {
-    return ln_act_fwd_run(pre, gamma, beta, keepmask, keep_prob, y, mean, rstd, G, rows, N, act, stream, nullptr);
+    return vqa_ln_act_fwd_run(pre, gamma, beta, KeepSrc::bytes(keepmask, keep_prob), y, mean, rstd, G, rows, N, act, stream);
 }
 
 extern "C" int vqa_ln_act_fwd_seeded(const float* pre, const float* gamma, const float* beta, uint64_t seed, uint64_t offset,
                                      float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act,
                                      void* stream) {
-    VQA_REQUIRE(pre && gamma && beta && y && mean && rstd, VQA_ERR_ARG);
-    VQA_REQUIRE_KEEP_SEED(offset, N, keep_prob);
-    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
-    return ln_act_fwd_run(pre, gamma, beta, nullptr, keep_prob, y, mean, rstd, G, rows, N, act, stream, &sd);
+    return vqa_ln_act_fwd_run(pre, gamma, beta, KeepSrc::seeded(seed, offset, N, keep_prob), y, mean, rstd, G, rows, N, act,
+                              stream);
+}
+
+int vqa_ln_act_bwd_run(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma,
+                       const float* beta, const KeepSrc& keep, float* dpre, float* part_dgamma, float* part_dbeta,
+                       float* part_dbias, int G, int rows, int N, int act, void* stream) {
+    VQA_REQUIRE(dy && pre && mean && rstd && gamma && beta && dpre, VQA_ERR_ARG);
+    VQA_REQUIRE(keep.err == VQA_OK, keep.err);
+    VQA_REQUIRE((act == 0 || act == 1) && G >= 0 && rows > 0 && N > 0, VQA_ERR_ARG);
+    VQA_REQUIRE((part_dgamma == nullptr) == (part_dbeta == nullptr), VQA_ERR_ARG);
+    Shape s = pick(pre, dy, dpre, rows, N);
+    if (s.U == 4 && !(vqa_aligned16(gamma) && vqa_aligned16(beta) && keep.words_ok() &&
+                      (part_dgamma == nullptr || (vqa_aligned16(part_dgamma) && vqa_aligned16(part_dbeta))) &&
+                      (part_dbias == nullptr || vqa_aligned16(part_dbias))))
+        s = scalar_shape(s, N);
+    VQA_REQUIRE(!keep.is_seeded() || s.U == 4, VQA_ERR_ALIGN);
+    if (G == 0) return VQA_OK;
+    const uint8_t* keepmask = keep.mask;
+    const float inv_keep = keep.inv_keep();
+    const size_t dyn = s.RY > 1 ? (size_t)2 * s.RY * s.CUt * s.U * sizeof(float) : 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int rm = act == 0 ? reg_mode(s.U, rows, N) : 0;
+    if (rm != 0)
+        int_dispatch<1, 2, 3>(rm, [&](auto m) {
+            using F = RegForm<decltype(m)::value>;
+            keep_dispatch(keep, [&](auto kp, auto... ks) {
+                hipLaunchKernelGGL((ln_bwd_reg_kernel<F::RPT, F::CPT, decltype(kp)::value, F::EXACT, decltype(ks)...>), dim3(G),
+                                   dim3(REG_CUT * REG_RY), REG_BWD_LDS, st, dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep,
+                                   dpre, part_dgamma, part_dbeta, part_dbias, rows, ks...);
+            });
+        });
+    else if (s.U == 4)
+        keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
+            hipLaunchKernelGGL((ln_relu_bwd_kernel<4, decltype(kp)::value, decltype(ks)...>), dim3(G), dim3(s.threads), dyn, st, dy,
+                               pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N,
+                               s.CUt, s.RY, act, ks...);
+        });
+    else
+        hipLaunchKernelGGL(ln_relu_bwd_kernel<1>, dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd, gamma, beta,
+                           keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act);
+    VQA_CHECK_LAUNCH();
+    return VQA_OK;
 }
 
 extern "C" int vqa_ln_relu_bwd(const float* dy, const float* pre, const float* mean, const float* rstd,
@@ -839,108 +880,45 @@ extern "C" int vqa_ln_relu_bwd(const float* dy, const float* pre, const float* m
                           part_dbias, G, rows, N, 0, stream);
 }
 
-static int ln_act_bwd_run(const float* dy, const float* pre, const float* mean, const float* rstd,
-                          const float* gamma, const float* beta, const uint8_t* keepmask, float keep_prob,
-                          float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
-                          int N, int act, void* stream, const KeepSeed* sd) {
-    VQA_REQUIRE(act == 0 || act == 1, VQA_ERR_ARG);
-    VQA_REQUIRE(dy && pre && mean && rstd && gamma && beta && dpre && G >= 0 && rows > 0 && N > 0, VQA_ERR_ARG);
-    VQA_REQUIRE((part_dgamma == nullptr) == (part_dbeta == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE(keepmask == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
-    Shape s = pick(pre, dy, dpre, rows, N, keepmask != nullptr);
-    if (s.U == 4 && !(vqa_aligned16(gamma) && vqa_aligned16(beta) &&
-                      (keepmask == nullptr || (reinterpret_cast<uintptr_t>(keepmask) & 3u) == 0) &&
-                      (part_dgamma == nullptr || (vqa_aligned16(part_dgamma) && vqa_aligned16(part_dbeta))) &&
-                      (part_dbias == nullptr || vqa_aligned16(part_dbias))))
-        s = Shape{1, std::min(256, ((std::min(N, 256) + 63) / 64) * 64), s.RY, 0};
-    VQA_REQUIRE(sd == nullptr || s.U == 4, VQA_ERR_ALIGN);
-    if (G == 0) return VQA_OK;
-    s.threads = s.CUt * s.RY;
-    const float inv_keep = (keepmask || sd) ? 1.f / keep_prob : 1.f;
-    const size_t dyn = s.RY > 1 ? (size_t)2 * s.RY * s.CUt * s.U * sizeof(float) : 0;
-    hipStream_t st = (hipStream_t)stream;
-    const int rm = act == 0 ? reg_mode(s.U, rows, N) : 0;
-    if (rm != 0) {
-        const size_t dyn_reg = (size_t)2 * REG_RY * REG_CUT * 4 * sizeof(float);
-#define VQA_LN_BWD_REG(rpt, cpt, exact)                                                                                    \
-    do {                                                                                                                 \
-        if (sd != nullptr)                                                                                               \
-            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, KEEP_SEEDED, exact, KeepSeed>), dim3(G), dim3(REG_CUT * REG_RY), \
-                               dyn_reg, st, dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma,     \
-                               part_dbeta, part_dbias, rows, *sd);                                                       \
-        else if (keepmask != nullptr)                                                                                    \
-            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, KEEP_BYTES, exact>), dim3(G), dim3(REG_CUT * REG_RY), dyn_reg, st, \
-                               dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta,      \
-                               part_dbias, rows);                                                                        \
-        else                                                                                                             \
-            hipLaunchKernelGGL((ln_bwd_reg_kernel<rpt, cpt, KEEP_NONE, exact>), dim3(G), dim3(REG_CUT * REG_RY), dyn_reg, st, \
-                               dy, pre, mean, rstd, gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta,      \
-                               part_dbias, rows);                                                                        \
-    } while (0)
-        if (rm == 1) VQA_LN_BWD_REG(9, 1, true); else if (rm == 2) VQA_LN_BWD_REG(2, 1, false); else VQA_LN_BWD_REG(2, 2, false);
-#undef VQA_LN_BWD_REG
-    } else if (sd != nullptr)
-        hipLaunchKernelGGL((ln_relu_bwd_kernel<4, KEEP_SEEDED, KeepSeed>), dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd,
-                           gamma, beta, keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act,
-                           *sd);
-    else if (s.U == 4)
-        hipLaunchKernelGGL(ln_relu_bwd_kernel<4>, dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd, gamma, beta,
-                           keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act);
-    else
-        hipLaunchKernelGGL(ln_relu_bwd_kernel<1>, dim3(G), dim3(s.threads), dyn, st, dy, pre, mean, rstd, gamma, beta,
-                           keepmask, inv_keep, dpre, part_dgamma, part_dbeta, part_dbias, rows, N, s.CUt, s.RY, act);
-    VQA_CHECK_LAUNCH();
-    return VQA_OK;
-}
-
 extern "C" int vqa_ln_act_bwd(const float* dy, const float* pre, const float* mean, const float* rstd,
                               const float* gamma, const float* beta, const uint8_t* keepmask, float keep_prob,
                               float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
                               int N, int act, void* stream) {
-    return ln_act_bwd_run(dy, pre, mean, rstd, gamma, beta, keepmask, keep_prob, dpre, part_dgamma, part_dbeta, part_dbias, G,
-                          rows, N, act, stream, nullptr);
+    return vqa_ln_act_bwd_run(dy, pre, mean, rstd, gamma, beta, KeepSrc::bytes(keepmask, keep_prob), dpre, part_dgamma,
+                              part_dbeta, part_dbias, G, rows, N, act, stream);
 }
 
 extern "C" int vqa_ln_act_bwd_seeded(const float* dy, const float* pre, const float* mean, const float* rstd,
                                      const float* gamma, const float* beta, uint64_t seed, uint64_t offset, float keep_prob,
                                      float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias, int G, int rows,
                                      int N, int act, void* stream) {
-    VQA_REQUIRE(dy && pre && mean && rstd && gamma && beta && dpre, VQA_ERR_ARG);
-    VQA_REQUIRE_KEEP_SEED(offset, N, keep_prob);
-    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
-    return ln_act_bwd_run(dy, pre, mean, rstd, gamma, beta, nullptr, keep_prob, dpre, part_dgamma, part_dbeta, part_dbias, G,
-                          rows, N, act, stream, &sd);
+    return vqa_ln_act_bwd_run(dy, pre, mean, rstd, gamma, beta, KeepSrc::seeded(seed, offset, N, keep_prob), dpre, part_dgamma,
+                              part_dbeta, part_dbias, G, rows, N, act, stream);
 }
 
-static int ln_relu_att_bwd_run(const float* ds, const float* qv, const float* w, const uint8_t* keep_att, float keep_prob,
-                               const float* pre, const float* mean, const float* rstd, const float* gamma,
-                               const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
-                               float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream,
-                               const KeepSeed* sd) {
+// (the one shape of vqa_vtail_supported has one query per memory; seeded keep bits with several are refused by name)
+int vqa_ln_relu_att_bwd_run(const float* ds, const float* qv, const float* w, const KeepSrc& keep, const float* pre,
+                            const float* mean, const float* rstd, const float* gamma, const float* beta, float* dpre,
+                            float* part_dgamma, float* part_dbeta, float* part_dbias, float* dqv, float* part_dw, int B, int rep,
+                            int R, int H, int D, void* stream) {
     VQA_REQUIRE(ds && qv && w && pre && mean && rstd && gamma && beta && dpre && part_dgamma && part_dbeta && part_dbias && dqv &&
-                    part_dw && B >= 0,
+                    part_dw,
                 VQA_ERR_ARG);
-    VQA_REQUIRE(keep_att == nullptr || keep_prob > 0.f, VQA_ERR_ARG);
+    VQA_REQUIRE(keep.err == VQA_OK, keep.err);
+    VQA_REQUIRE(!keep.is_seeded() || rep == 1, VQA_ERR_UNSUPPORTED);
+    VQA_REQUIRE(B >= 0, VQA_ERR_ARG);
     VQA_REQUIRE(vqa_vtail_supported(rep, R, H, D), VQA_ERR_UNSUPPORTED);
     VQA_REQUIRE(vqa_aligned16(qv) && vqa_aligned16(w) && vqa_aligned16(pre) && vqa_aligned16(gamma) && vqa_aligned16(beta) &&
                     vqa_aligned16(dpre) && vqa_aligned16(part_dgamma) && vqa_aligned16(part_dbeta) && vqa_aligned16(part_dbias) &&
-                    vqa_aligned16(dqv) && vqa_aligned16(part_dw) &&
-                    (keep_att == nullptr || (reinterpret_cast<uintptr_t>(keep_att) & 3u) == 0),
+                    vqa_aligned16(dqv) && vqa_aligned16(part_dw) && keep.words_ok(),
                 VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
-    const float inv_keep = (keep_att || sd) ? 1.f / keep_prob : 1.f;
-    const size_t dyn_reg = (size_t)2 * REG_RY * REG_CUT * 4 * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (sd != nullptr)
-        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<KEEP_SEEDED, KeepSeed>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w,
-                           keep_att, inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw,
-                           9, *sd);
-    else if (keep_att != nullptr)
-        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<KEEP_BYTES>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
-                           inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw, 9);
-    else
-        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<KEEP_NONE>), dim3(B), dim3(REG_CUT * REG_RY), dyn_reg, st, ds, qv, w, keep_att,
-                           inv_keep, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta, part_dbias, dqv, part_dw, 9);
+    keep_dispatch(keep, [&](auto kp, auto... ks) {
+        hipLaunchKernelGGL((ln_att_bwd_reg_kernel<decltype(kp)::value, decltype(ks)...>), dim3(B), dim3(REG_CUT * REG_RY),
+                           REG_BWD_LDS, st, ds, qv, w, keep.mask, keep.inv_keep(), pre, mean, rstd, gamma, beta, dpre, part_dgamma,
+                           part_dbeta, part_dbias, dqv, part_dw, 9, ks...);
+    });
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
@@ -949,8 +927,8 @@ extern "C" int vqa_ln_relu_att_bwd(const float* ds, const float* qv, const float
                                    const float* pre, const float* mean, const float* rstd, const float* gamma,
                                    const float* beta, float* dpre, float* part_dgamma, float* part_dbeta, float* part_dbias,
                                    float* dqv, float* part_dw, int B, int rep, int R, int H, int D, void* stream) {
-    return ln_relu_att_bwd_run(ds, qv, w, keep_att, keep_prob, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta,
-                               part_dbias, dqv, part_dw, B, rep, R, H, D, stream, nullptr);
+    return vqa_ln_relu_att_bwd_run(ds, qv, w, KeepSrc::bytes(keep_att, keep_prob), pre, mean, rstd, gamma, beta, dpre, part_dgamma,
+                                   part_dbeta, part_dbias, dqv, part_dw, B, rep, R, H, D, stream);
 }
 
 extern "C" int vqa_ln_relu_att_bwd_seeded(const float* ds, const float* qv, const float* w, uint64_t seed, uint64_t offset,
@@ -958,12 +936,6 @@ extern "C" int vqa_ln_relu_att_bwd_seeded(const float* ds, const float* qv, cons
                                           const float* gamma, const float* beta, float* dpre, float* part_dgamma,
                                           float* part_dbeta, float* part_dbias, float* dqv, float* part_dw, int B, int rep,
                                           int R, int H, int D, void* stream) {
-    VQA_REQUIRE(ds && qv && w && pre && mean && rstd && gamma && beta && dpre && part_dgamma && part_dbeta && part_dbias && dqv &&
-                    part_dw,
-                VQA_ERR_ARG);
-    VQA_REQUIRE_KEEP_SEED(offset, H, keep_prob);
-    VQA_REQUIRE(rep == 1, VQA_ERR_UNSUPPORTED);
-    const KeepSeed sd = keep_seed_make(seed, offset, keep_prob);
-    return ln_relu_att_bwd_run(ds, qv, w, nullptr, keep_prob, pre, mean, rstd, gamma, beta, dpre, part_dgamma, part_dbeta,
-                               part_dbias, dqv, part_dw, B, rep, R, H, D, stream, &sd);
+    return vqa_ln_relu_att_bwd_run(ds, qv, w, KeepSrc::seeded(seed, offset, H, keep_prob), pre, mean, rstd, gamma, beta, dpre,
+                                   part_dgamma, part_dbeta, part_dbias, dqv, part_dw, B, rep, R, H, D, stream);
 }

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/vqa_hot.h"
 
 #define VQA_WAVE 64
@@ -129,12 +131,59 @@ static inline KeepSeed keep_seed_make(uint64_t seed, uint64_t offset, float keep
 }
 __device__ __forceinline__ KeepSeed keep_seed_of() { return KeepSeed{0, 0, 0}; }
 __device__ __forceinline__ KeepSeed keep_seed_of(KeepSeed s) { return s; }
-// the argument checks every *_seeded entry point shares (after its NULL checks, before any HIP call)
-#define VQA_REQUIRE_KEEP_SEED(offset, row_len, keep_prob)                                 \
-    do {                                                                                  \
-        VQA_REQUIRE((keep_prob) > 0.f, VQA_ERR_ARG);                                      \
-        VQA_REQUIRE(((offset) & 3u) == 0 && (row_len) % 4 == 0, VQA_ERR_ALIGN);           \
-    } while (0)
+
+// The keep source of one dropout site, as the host passes it to a launch function: no dropout, a uint8 mask, or the
+// (seed, offset) stream.  The two makers are the one place the source's own arguments are checked; `err` is what the
+// entry point returns for a source that failed them (a launch function checks it after its pointer checks).
+struct KeepSrc {
+    KeepPolicy policy = KEEP_NONE;
+    const uint8_t* mask = nullptr;      // KEEP_BYTES
+    KeepSeed sd = {0, 0, 0};            // KEEP_SEEDED
+    float keep_prob = 1.f;
+    int err = VQA_OK;
+
+    // mask NULL: no dropout (keep_prob is not looked at)
+    static KeepSrc bytes(const uint8_t* mask, float keep_prob) {
+        KeepSrc k;
+        if (mask == nullptr) return k;
+        k.policy = KEEP_BYTES, k.mask = mask, k.keep_prob = keep_prob;
+        if (!(keep_prob > 0.f)) k.err = VQA_ERR_ARG;
+        return k;
+    }
+    // offset: stream position of the site's element 0; row_len: the site's row length.  Both multiples of 4, so a
+    // kernel's 4-byte mask word is one word of the stream
+    static KeepSrc seeded(uint64_t seed, uint64_t offset, int64_t row_len, float keep_prob) {
+        KeepSrc k;
+        k.policy = KEEP_SEEDED, k.sd = keep_seed_make(seed, offset, keep_prob), k.keep_prob = keep_prob;
+        if (!(keep_prob > 0.f)) k.err = VQA_ERR_ARG;
+        else if ((offset & 3u) != 0 || row_len % 4 != 0) k.err = VQA_ERR_ALIGN;
+        return k;
+    }
+    bool is_seeded() const { return policy == KEEP_SEEDED; }
+    float inv_keep() const { return policy == KEEP_NONE ? 1.f : 1.f / keep_prob; }
+    // the kernels that read a mask four bytes at a time can take it (no mask: yes)
+    bool words_ok() const { return (reinterpret_cast<uintptr_t>(mask) & 3u) == 0; }
+};
+
+// fn(std::integral_constant<int, V>) for the V of the list that equals v; false (and no call) when none does
+template <int... Vs, typename F>
+inline bool int_dispatch(int v, F&& fn) {
+    return ((v == Vs ? (fn(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// fn(policy tag, trailing by-value kernel arguments...): the KeepPolicy template argument of a kernel and its `KS... ks`
+// pack from a KeepSrc.  Three policies for the kernels that are instantiated once per policy ...
+template <typename F>
+inline void keep_dispatch(const KeepSrc& k, F&& fn) {
+    if (k.policy == KEEP_SEEDED) fn(std::integral_constant<int, KEEP_SEEDED>{}, k.sd);
+    else if (k.policy == KEEP_BYTES) fn(std::integral_constant<int, KEEP_BYTES>{});
+    else fn(std::integral_constant<int, KEEP_NONE>{});
+}
+// ... two for the generic kernels, whose KEEP_BYTES instantiation decides "no mask" at run time by the mask pointer
+template <typename F>
+inline void keep_dispatch_generic(const KeepSrc& k, F&& fn) {
+    if (k.policy == KEEP_SEEDED) fn(std::integral_constant<int, KEEP_SEEDED>{}, k.sd);
+    else fn(std::integral_constant<int, KEEP_BYTES>{});
+}
 
 __device__ __forceinline__ float mul_rounded(float a, float b) {      // a product that no later add absorbs into an fma
 #pragma clang fp contract(off)

@@ -18,6 +18,7 @@ Memory layout in HBM (all fp32):
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -62,6 +63,19 @@ LSTM_SCOPE = "encode_L/rnn/basic_lstm_cell"
 NUM_MARGINAL = 200            # vqa/model_vlmap_answer_ent.py:16
 W_ENTROPY = 0.1               # vqa/model_vlmap_answer_ent.py:14
 LATENT_LOSS_WEIGHT = 0.1      # vqa/model_vlmap_answer_full.py:33
+
+# The step's dropout sites, in the order of their bits (_lib.KEEP_SITE).  name: the mask's member of vqa_batch_t, and with a
+# leading "_" the engine's cached buffer; per_sample(dims): mask elements per batch row; keep: the dims member holding the
+# keep probability; region: the site's region of the (seed, step) stream, starting at region << 40 (sites of one region
+# follow each other in table order); models: the model types that have the site (None: every type with dropout).
+KeepSiteRow = collections.namedtuple("KeepSiteRow", "name per_sample keep region models")
+KEEP_SITES = (
+    KeepSiteRow("keep_att", lambda d: d.R * d.H, "keep_att", 0, None),
+    KeepSiteRow("keep_joint", lambda d: 2 * d.H, "keep_joint", 0, None),
+    KeepSiteRow("keep_joint2", lambda d: 2 * d.H, "keep_joint", 1, NOC_FAMILY),
+    KeepSiteRow("keep_tile", lambda d: d.num_marginal * 2 * d.H, "keep_joint", 2, ("vlmap_answer_ent",)),
+    KeepSiteRow("keep_word", lambda d: d.T * d.H, "keep_att", 3, BI_FAMILY),
+)
 
 
 PRECISIONS = ("f32", "bf16")
@@ -469,7 +483,7 @@ class FusionEngine:
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self._tensor_cache = {}
         self._reset_recurrence_word()
-        for a in ("_keep_att", "_keep_joint", "_keep_joint2", "_keep_tile", "_noise", "_keep_word"):
+        for a in ["_" + k.name for k in KEEP_SITES] + ["_noise", "_keep_lay"]:
             if hasattr(self, a):
                 delattr(self, a)
 
@@ -532,34 +546,27 @@ class FusionEngine:
         d = self.dims
         seeded = {}
         if dropout is not None:
-            if any(k is not None for k in (keep_att, keep_joint, keep_joint2, keep_tile, keep_word)):
+            if any(m is not None for m in (keep_att, keep_joint, keep_joint2, keep_tile, keep_word)):
                 raise ValueError("dropout=(seed, step) draws every keep bit inside the kernels: pass no keep_* mask with it")
             seed, step = dropout
             off = self.keep_offsets(int(step), row_offset, global_rows)
             seeded = dict(keep_seed=int(seed), keep_seeded=sum(_lib.KEEP_SITE[k] for k in self.keep_sites()),
                           **{k + "_off": off[k] for k in self.keep_sites()})
-        if keep_word is not None:
-            assert keep_word.dtype == torch.uint8 and keep_word.numel() == d.B * d.T * d.H
+        masks = dict(keep_att=keep_att, keep_joint=keep_joint, keep_joint2=keep_joint2, keep_tile=keep_tile, keep_word=keep_word)
+        for name, m in masks.items():
+            assert m is None or (m.dtype == torch.uint8 and m.numel() == d.B * self._keep_layout()[name][3]), name
         if self.model_type == "vlmap_answer_full":
             if noise is None:
                 raise ValueError("vlmap_answer_full needs the reparameterisation noise [B, H] (make_noise)")
             assert noise.dtype == torch.float32 and noise.numel() == d.B * d.H and noise.is_contiguous()
-        if keep_tile is not None:
-            assert keep_tile.dtype == torch.uint8 and keep_tile.numel() == d.B * d.num_marginal * 2 * d.H
         assert batch["image_idx"].dtype == torch.int64 and batch["image_idx"].numel() == d.B
         assert batch["q_intseq"].dtype == torch.int32 and tuple(batch["q_intseq"].shape) == (d.B, d.T)
         assert batch["q_intseq_len"].dtype == torch.int32
         assert tuple(batch["answer_target"].shape) == (d.B, d.A)
-        if keep_att is not None:
-            assert keep_att.dtype == torch.uint8 and keep_att.numel() == d.B * d.R * d.H
-        if keep_joint is not None:
-            assert keep_joint.dtype == torch.uint8 and keep_joint.numel() == d.B * 2 * d.H
         live = batch.get("live_rows")
         if live is not None:      # host int32[T]: rows sorted by length, longest first (input_ops_vqa.sort_by_length)
             live = np.ascontiguousarray(live, dtype=np.int32)
             assert live.shape == (d.T,) and (np.diff(live) <= 0).all() and 0 <= live[-1] and live[0] <= d.B
-        if keep_joint2 is not None:
-            assert keep_joint2.dtype == torch.uint8 and keep_joint2.numel() == d.B * 2 * d.H
         self._batch_keepalive = (batch, keep_att, keep_joint, keep_joint2, live, noise, keep_tile, keep_word)
         am = self._amask
         return _lib.Batch(
@@ -568,13 +575,9 @@ class FusionEngine:
             q_intseq_len=batch["q_intseq_len"].data_ptr(), answer_target=batch["answer_target"].data_ptr(),
             train_mask=am["train"].data_ptr(), obj_mask=am["obj"].data_ptr(), attr_mask=am["attr"].data_ptr(),
             exist_mask=am["exist"].data_ptr(),
-            keep_att=keep_att.data_ptr() if keep_att is not None else None,
-            keep_joint=keep_joint.data_ptr() if keep_joint is not None else None,
-            keep_joint2=keep_joint2.data_ptr() if keep_joint2 is not None else None,
+            **{name: m.data_ptr() if m is not None else None for name, m in masks.items()},
             live_rows=live.ctypes.data if live is not None else None,
             noise=noise.data_ptr() if noise is not None else None,
-            keep_tile=keep_tile.data_ptr() if keep_tile is not None else None,
-            keep_word=keep_word.data_ptr() if keep_word is not None else None,
             answer_intseq=self._answers[0].data_ptr() if self._answers is not None else None,
             answer_intseq_len=self._answers[1].data_ptr() if self._answers is not None else None, **seeded)
 
@@ -836,25 +839,43 @@ class FusionEngine:
         """the dropout sites of this model type, by the name of their mask in vqa_batch_t"""
         if self.model_type == "vqa":
             return ()
-        return ("keep_att", "keep_joint") + (("keep_joint2",) if self.model_type in NOC_FAMILY else ()) + \
-            (("keep_tile",) if self.model_type == "vlmap_answer_ent" else ()) + \
-            (("keep_word",) if self.model_type in BI_FAMILY else ())
+        return tuple(k.name for k in KEEP_SITES if k.models is None or self.model_type in k.models)
 
     def keep_offsets(self, step, row_offset=0, global_rows=None):
         """Stream position of element 0 of every dropout site's mask at `step`: the one place that lays the (seed, step)
         stream out, for the explicit masks (make_keep_mask*) and for seeded dropout (forward(dropout=...)).  The stream
         is indexed by the GLOBAL batch row (row_offset, global_rows: see make_keep_masks).  keep_att and keep_joint share
         the region at 0; l_joint of vlmap_answer_noc, the pairings of vlmap_answer_ent and the word attention of
-        vlmap_finetune have regions of their own at 1, 2 and 3 << 40."""
+        vlmap_finetune have regions of their own at 1, 2 and 3 << 40 (KEEP_SITES)."""
+        Bg = int(global_rows) if global_rows is not None else self.dims.B
+        return {name: (region << 40) + Bg * (step * width + before) + row_offset * n
+                for name, (region, width, before, n, _) in self._keep_layout().items()}
+
+    def _keep_layout(self):
+        """per site of KEEP_SITES: (its region, the elements per batch row of the region's sites together, of the region's
+        earlier sites, of the site itself; the dims member of its keep probability).  Held until resize() (the per-step path reads it: make_keep_masks)."""
+        lay = getattr(self, "_keep_lay", None)
+        if lay is None:
+            d = self.dims
+            lay = self._keep_lay = {}
+            for i, k in enumerate(KEEP_SITES):
+                width = sum(r.per_sample(d) for r in KEEP_SITES if r.region == k.region)
+                before = sum(r.per_sample(d) for r in KEEP_SITES[:i] if r.region == k.region)
+                lay[k.name] = (k.region, width, before, k.per_sample(d), k.keep)
+        return lay
+
+    def _make_keep_mask(self, name, seed, off):
+        """the site's mask for its stream position off[name] (keep_offsets), in the cached buffer _<name>"""
         d = self.dims
-        Bg = int(global_rows) if global_rows is not None else d.B
-        base = step * (Bg * d.R * d.H + Bg * 2 * d.H)
-        tile_row, word_row = d.num_marginal * 2 * d.H, d.T * d.H
-        return {"keep_att": base + row_offset * d.R * d.H,
-                "keep_joint": base + Bg * d.R * d.H + row_offset * 2 * d.H,
-                "keep_joint2": (1 << 40) + step * (Bg * 2 * d.H) + row_offset * 2 * d.H,
-                "keep_tile": (2 << 40) + step * (Bg * tile_row) + row_offset * tile_row,
-                "keep_word": (3 << 40) + step * (Bg * word_row) + row_offset * word_row}
+        _, _, _, per_sample, keep = self._keep_layout()[name]
+        n = d.B * per_sample
+        buf = getattr(self, "_" + name, None)
+        if buf is None:
+            buf = torch.empty(n, dtype=torch.uint8, device=self.device)
+            setattr(self, "_" + name, buf)
+        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(buf.data_ptr()), n, seed, off[name], getattr(d, keep), self._stream()),
+                   "vqa_dropout_mask")
+        return buf
 
     def make_keep_masks(self, seed, step, row_offset=0, global_rows=None):
         """Reproducible dropout keep-masks for (seed, step) -- the explicit stand-in for
@@ -862,41 +883,18 @@ class FusionEngine:
         The mask stream is indexed by the GLOBAL batch row: a data-parallel shard passes its first global row
         (row_offset) and the global batch size, and draws exactly the bits one process running the whole batch
         would draw for those rows -- ranks never reuse each other's bits."""
-        d = self.dims
-        n_att, n_j = d.B * d.R * d.H, d.B * 2 * d.H
-        if not hasattr(self, "_keep_att"):
-            self._keep_att = torch.empty(n_att, dtype=torch.uint8, device=self.device)
-            self._keep_joint = torch.empty(n_j, dtype=torch.uint8, device=self.device)
         off = self.keep_offsets(step, row_offset, global_rows)
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_att.data_ptr()), n_att, seed, off["keep_att"], d.keep_att,
-                                             self._stream()), "vqa_dropout_mask")
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_joint.data_ptr()), n_j, seed, off["keep_joint"],
-                                             d.keep_joint, self._stream()), "vqa_dropout_mask")
-        return self._keep_att, self._keep_joint
+        return self._make_keep_mask("keep_att", seed, off), self._make_keep_mask("keep_joint", seed, off)
 
     def make_keep_mask_word(self, seed, step, row_offset=0, global_rows=None):
         """vlmap_finetune / vlmap_only: keep-mask [B, T, H] of the question self-attention's tf.nn.dropout(., 0.8)
         (modules.hadamard_attention under scope word_attention), its own region of the (seed, step) stream"""
-        d = self.dims
-        n = d.B * d.T * d.H
-        if not hasattr(self, "_keep_word"):
-            self._keep_word = torch.empty(n, dtype=torch.uint8, device=self.device)
-        off = self.keep_offsets(step, row_offset, global_rows)["keep_word"]
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_word.data_ptr()), n, seed, off, d.keep_att,
-                                             self._stream()), "vqa_dropout_mask")
-        return self._keep_word
+        return self._make_keep_mask("keep_word", seed, self.keep_offsets(step, row_offset, global_rows))
 
     def make_keep_mask_tile(self, seed, step, row_offset=0, global_rows=None):
         """vlmap_answer_ent: keep-mask [B, num_marginal, 2H] of tf.nn.dropout(tile_joint, 0.5)
         (vqa/model_vlmap_answer_ent.py:205), its own region of the (seed, step) stream, indexed by the global batch row"""
-        d = self.dims
-        n = d.B * d.num_marginal * 2 * d.H
-        if not hasattr(self, "_keep_tile"):
-            self._keep_tile = torch.empty(n, dtype=torch.uint8, device=self.device)
-        off = self.keep_offsets(step, row_offset, global_rows)["keep_tile"]
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_tile.data_ptr()), n, seed, off, d.keep_joint,
-                                             self._stream()), "vqa_dropout_mask")
-        return self._keep_tile
+        return self._make_keep_mask("keep_tile", seed, self.keep_offsets(step, row_offset, global_rows))
 
     def make_noise(self, seed, step, row_offset=0, global_rows=None):
         """vlmap_answer_full: the standard-normal draws [B, H] that tf.random_normal(seed=123) produces inside the
@@ -914,11 +912,4 @@ class FusionEngine:
 
     def make_keep_mask_joint2(self, seed, step, row_offset=0, global_rows=None):
         """vlmap_answer_noc: the second dropout site's keep-mask (l_joint), from its own region of the same stream"""
-        d = self.dims
-        n_j = d.B * 2 * d.H
-        if not hasattr(self, "_keep_joint2"):
-            self._keep_joint2 = torch.empty(n_j, dtype=torch.uint8, device=self.device)
-        off = self.keep_offsets(step, row_offset, global_rows)["keep_joint2"]      # far beyond the two masks of make_keep_masks
-        _lib.check(self.lib.vqa_dropout_mask(C.c_void_p(self._keep_joint2.data_ptr()), n_j, seed, off, d.keep_joint,
-                                             self._stream()), "vqa_dropout_mask")
-        return self._keep_joint2
+        return self._make_keep_mask("keep_joint2", seed, self.keep_offsets(step, row_offset, global_rows))

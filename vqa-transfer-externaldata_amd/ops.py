@@ -96,17 +96,79 @@ def _seeded(keepmask, keep_seed):
     return C.c_uint64(int(seed)), C.c_uint64(int(offset))
 
 
-def ln_relu_fwd(pre, gamma, beta, rows=1, keepmask=None, keep_prob=1.0, keep_seed=None):
-    if _seeded(keepmask, keep_seed):
-        return ln_act_fwd(pre, gamma, beta, rows, "relu", None, keep_prob, keep_seed)
-    lib = _lib.load()
+def _call(entry, *args):
+    _lib.check(getattr(_lib.load(), entry)(*args), entry)
+
+
+# One body per op for the entry points that have a dropout site.  `entry` is the explicit-mask entry point of the public
+# wrapper; with keep_seed the op's *_seeded entry point is called instead, with (seed, offset) in the mask's place.  An
+# argument the entry point does not take is None: `act` for vqa_ln_relu_*, `rep` for the one-query attention entry points.
+def _opt(x):
+    return () if x is None else (x,)
+
+
+def _ln_fwd(entry, pre, gamma, beta, rows, act, keepmask, keep_prob, keep_seed):
     M, N = pre.shape
     G = M // rows
     y = torch.empty_like(pre)
     mean, rstd = _f32(G, like=pre), _f32(G, like=pre)
-    _lib.check(lib.vqa_ln_relu_fwd(_p(pre), _p(gamma), _p(beta), _p(keepmask), keep_prob, _p(y), _p(mean), _p(rstd),
-                                   G, rows, N, _st(pre)), "vqa_ln_relu_fwd")
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        entry, act = "vqa_ln_act_fwd_seeded", act or 0
+    _call(entry, _p(pre), _p(gamma), _p(beta), *(sd or (_p(keepmask),)), keep_prob, _p(y), _p(mean), _p(rstd), G, rows, N,
+          *_opt(act), _st(pre))
     return y, mean, rstd
+
+
+def _ln_bwd(entry, dy, pre, mean, rstd, gamma, beta, rows, act, keepmask, keep_prob, keep_seed, want_params=True):
+    M, N = pre.shape
+    G = M // rows
+    dpre = torch.empty_like(pre)
+    pg, pb, pbias = (_f32(G, N, like=pre) if want_params else None for _ in range(3))
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        entry, act = "vqa_ln_act_bwd_seeded", act or 0
+    _call(entry, _p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), *(sd or (_p(keepmask),)), keep_prob, _p(dpre),
+          _p(pg), _p(pb), _p(pbias), G, rows, N, *_opt(act), _st(pre))
+    if not want_params:
+        return dpre, None, None, None
+    dgamma, dbeta, dbias = colsum3(pg, pb, pbias)        # one pair of launches instead of three
+    return dpre, dgamma, dbeta, dbias
+
+
+def _attn_fwd(entry, v, qv, V, nb, w, bias, rep, keepmask, keep_prob, keep_seed=None):
+    B, R, H = v.shape
+    D = V.shape[2]
+    n = B * (rep or 1)
+    att, pooled = _f32(n, R, like=v), _f32(n, D, like=v)
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        _call("vqa_attn_pool_fwd_seeded", _p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(nb), _p(w), _p(bias), *sd,
+              keep_prob, _p(att), _p(pooled), B, 1, R, H, D, _st(v))
+    else:
+        _call(entry, _p(v), _p(qv), _p(V), _p(nb), _p(w), _p(bias), _p(keepmask), keep_prob, _p(att), _p(pooled), B, *_opt(rep),
+              R, H, D, _st(v))
+    return att, pooled
+
+
+def _attn_bwd(entry, dpooled, v, qv, V, att, w, rep, keepmask, keep_prob, keep_seed=None):
+    B, R, H = v.shape
+    D = V.shape[2]
+    n = B * (rep or 1)
+    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
+    pdw, pdb = _f32(n, H, like=v), _f32(n, 1, like=v)
+    sd = _seeded(keepmask, keep_seed)
+    if sd:
+        _call("vqa_attn_pool_bwd_seeded", _p(dpooled), _p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(att), _p(w), *sd,
+              keep_prob, _p(dv), _p(dqv), _p(pdw), _p(pdb), B, 1, R, H, D, _st(v))
+    else:
+        _call(entry, _p(dpooled), _p(v), _p(qv), _p(V), _p(att), _p(w), _p(keepmask), keep_prob, _p(dv), _p(dqv), _p(pdw),
+              _p(pdb), B, *_opt(rep), R, H, D, _st(v))
+    return dv, dqv, colsum(pdw), colsum(pdb)
+
+
+def ln_relu_fwd(pre, gamma, beta, rows=1, keepmask=None, keep_prob=1.0, keep_seed=None):
+    return _ln_fwd("vqa_ln_relu_fwd", pre, gamma, beta, rows, None, keepmask, keep_prob, keep_seed)
 
 
 def colsum(X):
@@ -131,107 +193,28 @@ def colsum3(X0, X1, X2):
 
 
 def ln_relu_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, keepmask=None, keep_prob=1.0, want_params=True, keep_seed=None):
-    lib = _lib.load()
-    M, N = pre.shape
-    G = M // rows
-    dpre = torch.empty_like(pre)
-    pg = _f32(G, N, like=pre) if want_params else None
-    pb = _f32(G, N, like=pre) if want_params else None
-    pbias = _f32(G, N, like=pre) if want_params else None
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        _lib.check(lib.vqa_ln_act_bwd_seeded(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), sd[0], sd[1], keep_prob,
-                                             _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, 0, _st(pre)),
-                   "vqa_ln_act_bwd_seeded")
-    else:
-        _lib.check(lib.vqa_ln_relu_bwd(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(keepmask), keep_prob,
-                                       _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, _st(pre)), "vqa_ln_relu_bwd")
-    if not want_params:
-        return dpre, None, None, None
-    dgamma, dbeta, dbias = colsum3(pg, pb, pbias)
-    return dpre, dgamma, dbeta, dbias
-
-
-def _attn_fwd_seeded(v, qv, V, nb, w, bias, sd, keep_prob):
-    lib = _lib.load()
-    B, R, H = v.shape
-    D = V.shape[2]
-    att, pooled = _f32(B, R, like=v), _f32(B, D, like=v)
-    _lib.check(lib.vqa_attn_pool_fwd_seeded(_p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(nb), _p(w), _p(bias), sd[0],
-                                            sd[1], keep_prob, _p(att), _p(pooled), B, 1, R, H, D, _st(v)),
-               "vqa_attn_pool_fwd_seeded")
-    return att, pooled
-
-
-def _attn_bwd_seeded(dpooled, v, qv, V, att, w, sd, keep_prob):
-    lib = _lib.load()
-    B, R, H = v.shape
-    D = V.shape[2]
-    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
-    pdw, pdb = _f32(B, H, like=v), _f32(B, 1, like=v)
-    _lib.check(lib.vqa_attn_pool_bwd_seeded(_p(dpooled), _p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(att), _p(w),
-                                            sd[0], sd[1], keep_prob, _p(dv), _p(dqv), _p(pdw), _p(pdb), B, 1, R, H, D, _st(v)),
-               "vqa_attn_pool_bwd_seeded")
-    return dv, dqv, colsum(pdw), colsum(pdb)
+    return _ln_bwd("vqa_ln_relu_bwd", dy, pre, mean, rstd, gamma, beta, rows, None, keepmask, keep_prob, keep_seed, want_params)
 
 
 def attn_pool_fwd(v, qv, V, nb, w, bias, keepmask=None, keep_prob=1.0, keep_seed=None):
     """modules.hadamard_attention + modules.attention_pooling."""
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        return _attn_fwd_seeded(v, qv, V, nb, w, bias, sd, keep_prob)
-    lib = _lib.load()
-    B, R, H = v.shape
-    D = V.shape[2]
-    att, pooled = _f32(B, R, like=v), _f32(B, D, like=v)
-    _lib.check(lib.vqa_attn_pool_fwd(_p(v), _p(qv), _p(V), _p(nb), _p(w), _p(bias), _p(keepmask), keep_prob, _p(att),
-                                     _p(pooled), B, R, H, D, _st(v)), "vqa_attn_pool_fwd")
-    return att, pooled
+    return _attn_fwd("vqa_attn_pool_fwd", v, qv, V, nb, w, bias, None, keepmask, keep_prob, keep_seed)
 
 
 def attn_pool_bwd(dpooled, v, qv, V, att, w, keepmask=None, keep_prob=1.0, keep_seed=None):
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        return _attn_bwd_seeded(dpooled, v, qv, V, att, w, sd, keep_prob)
-    lib = _lib.load()
-    B, R, H = v.shape
-    D = V.shape[2]
-    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
-    pdw, pdb = _f32(B, H, like=v), _f32(B, 1, like=v)
-    _lib.check(lib.vqa_attn_pool_bwd(_p(dpooled), _p(v), _p(qv), _p(V), _p(att), _p(w), _p(keepmask), keep_prob,
-                                     _p(dv), _p(dqv), _p(pdw), _p(pdb), B, R, H, D, _st(v)), "vqa_attn_pool_bwd")
-    return dv, dqv, colsum(pdw), colsum(pdb)
+    return _attn_bwd("vqa_attn_pool_bwd", dpooled, v, qv, V, att, w, None, keepmask, keep_prob, keep_seed)
 
 
 def attn_pool_fwd_v16(v, qv, V16, nb, w, bias, keepmask=None, keep_prob=1.0, keep_seed=None):
     """attn_pool_fwd over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_fwd on V16.float()."""
-    lib = _lib.load()
     assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        return _attn_fwd_seeded(v, qv, V16, nb, w, bias, sd, keep_prob)
-    B, R, H = v.shape
-    D = V16.shape[2]
-    att, pooled = _f32(B, R, like=v), _f32(B, D, like=v)
-    _lib.check(lib.vqa_attn_pool_fwd_v16(_p(v), _p(qv), _p(V16), _p(nb), _p(w), _p(bias), _p(keepmask), keep_prob, _p(att),
-                                         _p(pooled), B, R, H, D, _st(v)), "vqa_attn_pool_fwd_v16")
-    return att, pooled
+    return _attn_fwd("vqa_attn_pool_fwd_v16", v, qv, V16, nb, w, bias, None, keepmask, keep_prob, keep_seed)
 
 
 def attn_pool_bwd_v16(dpooled, v, qv, V16, att, w, keepmask=None, keep_prob=1.0, keep_seed=None):
     """attn_pool_bwd over a bf16 memory V16 [B,R,D] (torch.bfloat16): the bits of attn_pool_bwd on V16.float()."""
-    lib = _lib.load()
     assert V16.dtype == torch.bfloat16 and V16.is_contiguous()
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        return _attn_bwd_seeded(dpooled, v, qv, V16, att, w, sd, keep_prob)
-    B, R, H = v.shape
-    D = V16.shape[2]
-    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
-    pdw, pdb = _f32(B, H, like=v), _f32(B, 1, like=v)
-    _lib.check(lib.vqa_attn_pool_bwd_v16(_p(dpooled), _p(v), _p(qv), _p(V16), _p(att), _p(w), _p(keepmask), keep_prob,
-                                         _p(dv), _p(dqv), _p(pdw), _p(pdb), B, R, H, D, _st(v)), "vqa_attn_pool_bwd_v16")
-    return dv, dqv, colsum(pdw), colsum(pdb)
+    return _attn_bwd("vqa_attn_pool_bwd_v16", dpooled, v, qv, V16, att, w, None, keepmask, keep_prob, keep_seed)
 
 
 def attn_pool_bwd_ds_v16(dpooled, V16, att):
@@ -260,19 +243,13 @@ def ln_relu_att_bwd(ds, qv, w, pre, mean, rstd, gamma, beta, keepmask=None, keep
     """v_linear_v's LayerNorm + ReLU backward with dy = ds x (keep / keep_prob * qv * w) formed in registers; also the
     attention backward's dqv and score-weight partial.  pre [B,R,H] -> dpre, (part_dgamma, part_dbeta, part_dbias) [B,H],
     dqv [B,H], part_dw [B,H]."""
-    lib = _lib.load()
     B, R, H = pre.shape
     dpre = torch.empty_like(pre)
     pg, pb, pbias, dqv, pdw = (_f32(B, H, like=pre) for _ in range(5))
     sd = _seeded(keepmask, keep_seed)
-    if sd:
-        _lib.check(lib.vqa_ln_relu_att_bwd_seeded(_p(ds), _p(qv), _p(w), sd[0], sd[1], keep_prob, _p(pre), _p(mean), _p(rstd),
-                                                  _p(gamma), _p(beta), _p(dpre), _p(pg), _p(pb), _p(pbias), _p(dqv), _p(pdw), B,
-                                                  1, R, H, 2048, _st(pre)), "vqa_ln_relu_att_bwd_seeded")
-        return dpre, (pg, pb, pbias), dqv, pdw
-    _lib.check(lib.vqa_ln_relu_att_bwd(_p(ds), _p(qv), _p(w), _p(keepmask), keep_prob, _p(pre), _p(mean), _p(rstd),
-                                       _p(gamma), _p(beta), _p(dpre), _p(pg), _p(pb), _p(pbias), _p(dqv), _p(pdw), B, 1, R,
-                                       H, 2048, _st(pre)), "vqa_ln_relu_att_bwd")
+    _call("vqa_ln_relu_att_bwd_seeded" if sd else "vqa_ln_relu_att_bwd", _p(ds), _p(qv), _p(w), *(sd or (_p(keepmask),)), keep_prob,
+          _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dpre), _p(pg), _p(pb), _p(pbias), _p(dqv), _p(pdw), B, 1, R, H, 2048,
+          _st(pre))
     return dpre, (pg, pb, pbias), dqv, pdw
 
 
@@ -403,62 +380,21 @@ def sumsq(g, extra=None):
 # ---------------------------------------------------------------- ops used by the pre-training model
 def ln_act_fwd(pre, gamma, beta, rows=1, act="relu", keepmask=None, keep_prob=1.0, keep_seed=None):
     """modules.fc_layer's layer_norm + activation ('relu' | 'tanh') (+ dropout)."""
-    lib = _lib.load()
-    M, N = pre.shape
-    G = M // rows
-    y = torch.empty_like(pre)
-    mean, rstd = _f32(G, like=pre), _f32(G, like=pre)
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        _lib.check(lib.vqa_ln_act_fwd_seeded(_p(pre), _p(gamma), _p(beta), sd[0], sd[1], keep_prob, _p(y), _p(mean), _p(rstd), G,
-                                             rows, N, 0 if act == "relu" else 1, _st(pre)), "vqa_ln_act_fwd_seeded")
-        return y, mean, rstd
-    _lib.check(lib.vqa_ln_act_fwd(_p(pre), _p(gamma), _p(beta), _p(keepmask), keep_prob, _p(y), _p(mean), _p(rstd), G,
-                                  rows, N, 0 if act == "relu" else 1, _st(pre)), "vqa_ln_act_fwd")
-    return y, mean, rstd
+    return _ln_fwd("vqa_ln_act_fwd", pre, gamma, beta, rows, 0 if act == "relu" else 1, keepmask, keep_prob, keep_seed)
 
 
 def ln_act_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, act="relu", keepmask=None, keep_prob=1.0, keep_seed=None):
-    lib = _lib.load()
-    M, N = pre.shape
-    G = M // rows
-    dpre = torch.empty_like(pre)
-    pg, pb, pbias = _f32(G, N, like=pre), _f32(G, N, like=pre), _f32(G, N, like=pre)
-    sd = _seeded(keepmask, keep_seed)
-    if sd:
-        _lib.check(lib.vqa_ln_act_bwd_seeded(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), sd[0], sd[1], keep_prob,
-                                             _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, 0 if act == "relu" else 1,
-                                             _st(pre)), "vqa_ln_act_bwd_seeded")
-        dgamma, dbeta, dbias = colsum3(pg, pb, pbias)
-        return dpre, dgamma, dbeta, dbias
-    _lib.check(lib.vqa_ln_act_bwd(_p(dy), _p(pre), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(keepmask), keep_prob,
-                                  _p(dpre), _p(pg), _p(pb), _p(pbias), G, rows, N, 0 if act == "relu" else 1,
-                                  _st(pre)), "vqa_ln_act_bwd")
-    dgamma, dbeta, dbias = colsum3(pg, pb, pbias)        # one pair of launches instead of three
-    return dpre, dgamma, dbeta, dbias
+    return _ln_bwd("vqa_ln_act_bwd", dy, pre, mean, rstd, gamma, beta, rows, 0 if act == "relu" else 1, keepmask, keep_prob,
+                   keep_seed)
 
 
 def attn_pool_fwd_rep(v, qv, V, nb, w, bias, rep, keepmask=None, keep_prob=1.0):
     """`rep` queries per memory: v [B,R,H], V [B,R,D], nb [B]; qv [B*rep,H] -> att [B*rep,R], pooled [B*rep,D]."""
-    lib = _lib.load()
-    B, R, H = v.shape
-    D = V.shape[2]
-    att, pooled = _f32(B * rep, R, like=v), _f32(B * rep, D, like=v)
-    _lib.check(lib.vqa_attn_pool_fwd_rep(_p(v), _p(qv), _p(V), _p(nb), _p(w), _p(bias), _p(keepmask), keep_prob,
-                                         _p(att), _p(pooled), B, rep, R, H, D, _st(v)), "vqa_attn_pool_fwd_rep")
-    return att, pooled
+    return _attn_fwd("vqa_attn_pool_fwd_rep", v, qv, V, nb, w, bias, rep, keepmask, keep_prob)
 
 
 def attn_pool_bwd_rep(dpooled, v, qv, V, att, w, rep, keepmask=None, keep_prob=1.0):
-    lib = _lib.load()
-    B, R, H = v.shape
-    D = V.shape[2]
-    dv, dqv = torch.empty_like(v), torch.empty_like(qv)
-    pdw, pdb = _f32(B * rep, H, like=v), _f32(B * rep, 1, like=v)
-    _lib.check(lib.vqa_attn_pool_bwd_rep(_p(dpooled), _p(v), _p(qv), _p(V), _p(att), _p(w), _p(keepmask), keep_prob,
-                                         _p(dv), _p(dqv), _p(pdw), _p(pdb), B, rep, R, H, D, _st(v)),
-               "vqa_attn_pool_bwd_rep")
-    return dv, dqv, colsum(pdw), colsum(pdb)
+    return _attn_bwd("vqa_attn_pool_bwd_rep", dpooled, v, qv, V, att, w, rep, keepmask, keep_prob)
 
 
 def tanh_fwd(x):

@@ -477,7 +477,8 @@ int vqa_dropout_mask(uint8_t* out, int64_t n, uint64_t seed, uint64_t offset, fl
  * word in every consuming kernel; saves the mask buffer, its launch, one write and two reads of it per step.
  * Checked before any HIP call: a NULL required pointer or keep_prob <= 0 -> VQA_ERR_ARG; offset % 4 != 0, a row length
  * (H, N) that is no multiple of 4, or pointers whose alignment would send the explicit form to its one-column kernels
- * -> VQA_ERR_ALIGN; rep != 1 -> VQA_ERR_UNSUPPORTED (one query per memory; the kernels with several stay explicit).
+ * -> VQA_ERR_ALIGN; rep != 1 -> VQA_ERR_UNSUPPORTED (one query per memory: the contract these entry points were published
+ * with; several queries per memory have vqa_attn_pool_fwd_rep_seeded / vqa_attn_pool_bwd_rep_seeded below).
  * V: the pooled memory, const float* (v_bf16 == 0) or const uint16_t* raw bf16 patterns (v_bf16 != 0, the _v16 kernels). */
 int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int v_bf16, const int32_t* nb, const float* w,
                              const float* bias, uint64_t seed, uint64_t offset, float keep_prob, float* att, float* pooled,
@@ -485,6 +486,16 @@ int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int
 int vqa_attn_pool_bwd_seeded(const float* dpooled, const float* v, const float* qv, const void* V, int v_bf16,
                              const float* att, const float* w, uint64_t seed, uint64_t offset, float keep_prob, float* dv,
                              float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H, int D, void* stream);
+/* vqa_attn_pool_fwd_rep / vqa_attn_pool_bwd_rep with the keep bits computed: `rep` queries per f32 memory, 1..8.  The mask is
+ * the [B * rep, R, H] mask of those entry points, query q = m * rep + j at stream position offset + q * R * H; the kernels that
+ * serve several queries per memory (one workgroup per memory: rep 5 at the models' shapes, the generic backward) compute the
+ * word of every query where their explicit forms load it.  Checks and codes as above, without the rep refusal. */
+int vqa_attn_pool_fwd_rep_seeded(const float* v, const float* qv, const float* V, const int32_t* nb, const float* w,
+                                 const float* bias, uint64_t seed, uint64_t offset, float keep_prob, float* att, float* pooled,
+                                 int B, int rep, int R, int H, int D, void* stream);
+int vqa_attn_pool_bwd_rep_seeded(const float* dpooled, const float* v, const float* qv, const float* V, const float* att,
+                                 const float* w, uint64_t seed, uint64_t offset, float keep_prob, float* dv, float* dqv,
+                                 float* part_dw, float* part_db, int B, int rep, int R, int H, int D, void* stream);
 int vqa_ln_act_fwd_seeded(const float* pre, const float* gamma, const float* beta, uint64_t seed, uint64_t offset,
                           float keep_prob, float* y, float* mean, float* rstd, int G, int rows, int N, int act, void* stream);
 int vqa_ln_act_bwd_seeded(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma,
@@ -770,6 +781,31 @@ typedef struct {
     const int32_t *perm, *inv, *live_rows;
 } vqa_pretrain_batch_t;
 
+/* Seeded dropout of the pre-training steps (the *_ex entry points of all four families below): which dropout sites draw
+ * their keep bits inside the consuming kernels (the attention and LayerNorm *_seeded forms) instead of reading the mask
+ * pointer of the batch structs, and where each site's element 0 sits in the stream of vqa_dropout_mask(seed = keep_seed).
+ * Index [k]: category (0 object, 1 attribute); l_joint_off[k][t]: head type t (0 bf, 1 ws, 2 ew) of the noc models' l
+ * branch.  A bit of `seeded` covers the site of both categories (VQA_PT_KEEP_SITE_L_JOINT: of every head type as well).
+ * Zero-filled, or a NULL pointer to it: every site reads its mask pointer, as the entry points without _ex do.
+ * A seeded site whose mask pointer is non-NULL, or an unknown bit -> VQA_ERR_ARG; an offset that is no multiple of 4 ->
+ * VQA_ERR_ALIGN (H % 4 == 0 holds for every accepted dims).  The library keeps no state: the backward is handed the same
+ * struct as the forward and regenerates the bits. */
+typedef struct {
+    uint64_t keep_seed;
+    uint64_t att_off[2];                    /* keep_att [B*n,R,H] */
+    uint64_t bf_joint_off[2];               /* keep_bf_joint [B*n,2H] */
+    uint64_t ws_joint_off[2];               /* keep_ws_joint [B*n,2H] */
+    uint64_t ew_joint_off[2];               /* keep_ew_joint [B*n,2H] (vqa_pretrain_ctx_kind_t) */
+    uint64_t l_joint_off[2][3];             /* keep_{bf,ws,ew}_l_joint [B*n,2H] (vqa_pretrain_noc_kind_t) */
+    int32_t seeded;                         /* VQA_PT_KEEP_SITE_* bits */
+} vqa_pretrain_keep_t;
+#define VQA_PT_KEEP_SITE_ATT 1
+#define VQA_PT_KEEP_SITE_BF_JOINT 2
+#define VQA_PT_KEEP_SITE_WS_JOINT 4
+#define VQA_PT_KEEP_SITE_EW_JOINT 8
+#define VQA_PT_KEEP_SITE_L_JOINT 16
+#define VQA_PT_KEEP_SITE_ALL 31
+
 int64_t vqa_pretrain_workspace_bytes(const vqa_pretrain_dims_t* dims);
 /* Named intermediates inside the workspace: "<obj|attr>/{att,pooled,valid,bf_state,...}",
  * "<obj|attr>/<bf|ws>/{z,dz,stats,j,...}", "report" (13 floats in the order of vqa_pretrain_report_key). */
@@ -794,6 +830,14 @@ int vqa_pretrain_backward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_pa
 int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* params,
                                  const vqa_pretrain_params_t* grads, const vqa_pretrain_batch_t* batch, void* workspace,
                                  int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+/* vqa_pretrain_forward / vqa_pretrain_backward_phases with seeded dropout sites (keep NULL: exactly those calls) */
+int vqa_pretrain_forward_ex(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* params,
+                            const vqa_pretrain_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                            void* stream, const vqa_pretrain_keep_t* keep);
+int vqa_pretrain_backward_phases_ex(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* params,
+                                    const vqa_pretrain_params_t* grads, const vqa_pretrain_batch_t* batch, void* workspace,
+                                    int64_t workspace_bytes, float* slice_sq, int phases, void* stream,
+                                    const vqa_pretrain_keep_t* keep);
 
 /* ------------------------------------------------------------------------
  * Pre-training with a variable head set (csrc/pretrain_model.hip): the cfg-5 model above plus, per category, the
@@ -878,6 +922,14 @@ int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pre
 int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
                                      const vqa_pretrain_ext_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
                                      void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+/* with seeded dropout sites (vqa_pretrain_keep_t; keep NULL: exactly the calls above) */
+int vqa_pretrain_ext_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
+                                const vqa_pretrain_ext_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                                void* stream, const vqa_pretrain_keep_t* keep);
+int vqa_pretrain_ext_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* params,
+                                        const vqa_pretrain_ext_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
+                                        void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream,
+                                        const vqa_pretrain_keep_t* keep);
 
 /* ------------------------------------------------------------------------
  * "No composition" pre-training (csrc/pretrain_model.hip): vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py (=
@@ -943,6 +995,14 @@ int vqa_pretrain_noc_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pre
 int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* params,
                                      const vqa_pretrain_noc_params_t* grads, const vqa_pretrain_noc_batch_t* batch,
                                      void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+/* with seeded dropout sites (vqa_pretrain_keep_t, the l branch: VQA_PT_KEEP_SITE_L_JOINT; keep NULL: exactly the calls above) */
+int vqa_pretrain_noc_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* params,
+                                const vqa_pretrain_noc_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                                void* stream, const vqa_pretrain_keep_t* keep);
+int vqa_pretrain_noc_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* params,
+                                        const vqa_pretrain_noc_params_t* grads, const vqa_pretrain_noc_batch_t* batch,
+                                        void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream,
+                                        const vqa_pretrain_keep_t* keep);
 
 /* ------------------------------------------------------------------------
  * Pre-training with an adapted memory (csrc/pretrain_model.hip): vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py,
@@ -981,6 +1041,15 @@ int vqa_pretrain_adapt_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_p
 int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* params,
                                        const vqa_pretrain_adapt_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
                                        void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream);
+/* with seeded dropout sites (vqa_pretrain_keep_t; keep NULL: exactly the calls above).  The attention pools the 1024-wide
+ * memory: its seeded forms are those of the per-memory D 1024 kernels */
+int vqa_pretrain_adapt_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* params,
+                                  const vqa_pretrain_ext_batch_t* batch, void* workspace, int64_t workspace_bytes, int want_dz,
+                                  void* stream, const vqa_pretrain_keep_t* keep);
+int vqa_pretrain_adapt_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* params,
+                                          const vqa_pretrain_adapt_params_t* grads, const vqa_pretrain_ext_batch_t* batch,
+                                          void* workspace, int64_t workspace_bytes, float* slice_sq, int phases, void* stream,
+                                          const vqa_pretrain_keep_t* keep);
 
 /* ------------------------------------------------------------------------
  * Region-feature extractor, NHWC fp32.

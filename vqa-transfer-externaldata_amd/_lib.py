@@ -141,6 +141,17 @@ class PtAdaptParams(C.Structure):
     _fields_ = [("ext", PtExtParams), ("v_adapt", PtFc6)]
 
 
+class PtKeep(C.Structure):
+    """vqa_pretrain_keep_t: the seeded dropout sites of the vqa_pretrain_*_ex entry points"""
+    _fields_ = [("keep_seed", C.c_uint64), ("att_off", C.c_uint64 * 2), ("bf_joint_off", C.c_uint64 * 2),
+                ("ws_joint_off", C.c_uint64 * 2), ("ew_joint_off", C.c_uint64 * 2), ("l_joint_off", (C.c_uint64 * 3) * 2),
+                ("seeded", C.c_int32)]
+
+
+# VQA_PT_KEEP_SITE_*: bits of PtKeep.seeded
+PT_KEEP_SITE = {"att": 1, "bf_joint": 2, "ws_joint": 4, "ew_joint": 8, "l_joint": 16}
+
+
 SOFTMAX_PAIR_MAX = 8     # VQA_SOFTMAX_PAIR_MAX
 
 
@@ -240,6 +251,8 @@ SIGNATURES = {
     "vqa_ln_relu_att_bwd": (_I, [_P, _P, _P, _P, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_fwd_seeded": (_I, [_P, _P, _P, _I, _P, _P, _P, _U, _U, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_attn_pool_bwd_seeded": (_I, [_P, _P, _P, _P, _I, _P, _P, _U, _U, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_fwd_rep_seeded": (_I, [_P, _P, _P, _P, _P, _P, _U, _U, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vqa_attn_pool_bwd_rep_seeded": (_I, [_P, _P, _P, _P, _P, _P, _U, _U, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "vqa_ln_act_fwd_seeded": (_I, [_P, _P, _P, _U, _U, _F, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_ln_act_bwd_seeded": (_I, [_P, _P, _P, _P, _P, _P, _U, _U, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vqa_ln_relu_att_bwd_seeded": (_I, [_P, _P, _P, _U, _U, _F] + [_P] * 11 + [_I, _I, _I, _I, _I, _P]),
@@ -362,6 +375,11 @@ SIGNATURES = {
     "vqa_pretrain_adapt_backward_phases": (_I, [C.POINTER(PtExtDims), C.POINTER(PtAdaptParams), C.POINTER(PtAdaptParams),
                                                 C.POINTER(PtExtBatch), _P, _L, _P, _I, _P]),
 }
+# the pre-training entry points with seeded dropout sites: the plain signature + const vqa_pretrain_keep_t*
+for _fam in ("vqa_pretrain_", "vqa_pretrain_ext_", "vqa_pretrain_noc_", "vqa_pretrain_adapt_"):
+    for _fn in ("forward", "backward_phases"):
+        _res, _args = SIGNATURES[_fam + _fn]
+        SIGNATURES[_fam + _fn + "_ex"] = (_res, _args + [C.POINTER(PtKeep)])
 
 ABI_VERSION = 5      # VQA_HOT_ABI_VERSION of include/vqa_hot.h
 

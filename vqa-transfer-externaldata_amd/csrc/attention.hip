@@ -291,11 +291,13 @@ __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
 // for 0.32 GB of distinct bytes at 512 images), only the keep masks are per query.  Same three phases as above; a
 // wave scores its rows for all REP queries from one load of the row, waves 0..REP-1 run the REP softmaxes, and the
 // pooling loop keeps REP accumulators per thread over one stream of V.
+// Keep policy as in the one-query forms: KEEP_BYTES loads the mask word of query q0 + j from mb4 (the base of query q0),
+// KEEP_SEEDED computes it (sq.word0 = the word index of query q0's mask).
 constexpr int REP_PF = 4, REP_POOL_BATCH = 6;
-template <int H4L, int CNT, bool MASK, int REP>
+template <int H4L, int CNT, int KP, int REP, typename... KS>
 __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ vb4, const unsigned* __restrict__ mb4,
                                                     const f32x4v* qw4, float* s, int R, int row0, float inv_keep,
-                                                    float bias0, int lane, bool sync_first) {
+                                                    float bias0, int lane, bool sync_first, KS... sq) {
     constexpr int H4 = H4L * 64;
     f32x4v x[CNT][H4L];
     int rr[CNT];
@@ -309,11 +311,19 @@ __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ v
 #pragma unroll
     for (int j = 0; j < REP; ++j) {
         unsigned m[CNT][H4L];
-        if (MASK) {
+        if (KP == KEEP_BYTES) {
 #pragma unroll
             for (int i = 0; i < CNT; ++i)
 #pragma unroll
                 for (int k = 0; k < H4L; ++k) m[i][k] = mb4[((int64_t)j * R + rr[i]) * H4 + lane + 64 * k];
+        }
+        if constexpr (KP == KEEP_SEEDED) {
+            const KeepSeed sd = keep_seed_of(sq...);
+#pragma unroll
+            for (int i = 0; i < CNT; ++i)
+#pragma unroll
+                for (int k = 0; k < H4L; ++k)
+                    m[i][k] = keep_word4(sd.key, sd.word0 + ((uint64_t)j * R + rr[i]) * H4 + lane + 64 * k, sd.thr);
         }
 #pragma unroll
         for (int i = 0; i < CNT; ++i) {
@@ -321,7 +331,7 @@ __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ v
 #pragma unroll
             for (int k = 0; k < H4L; ++k) {
                 const f32x4v q = qw4[j * H4 + lane + 64 * k];
-                if (MASK) {
+                if (KP != KEEP_NONE) {
                     const unsigned mm = m[i][k];
                     acc += (x[i][k].x * q.x * (float)(mm & 0xFFu) + x[i][k].y * q.y * (float)((mm >> 8) & 0xFFu) +
                             x[i][k].z * q.z * (float)((mm >> 16) & 0xFFu) + x[i][k].w * q.w * (float)(mm >> 24)) * inv_keep;
@@ -335,11 +345,12 @@ __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ v
     }
 }
 
-template <int H4L, int D4T, bool MASK, int REP>
+template <int H4L, int D4T, int KP, int REP, typename... KS>
 __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
     const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
-    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R) {
+    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
+    KS... ks) {
     static_assert(REP <= FWD_THREADS / 64, "one softmax wave per query");
     constexpr int H = H4L * 256, D = D4T * 2048, D4 = D / 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[REP][H] | s[REP][40]
@@ -348,7 +359,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
     const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t q0 = (int64_t)mem * REP;                         // first query of this memory
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
-    const unsigned* mb4 = MASK ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
+    const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
     const f32x4v* Vb4 = reinterpret_cast<const f32x4v*>(V + (int64_t)mem * R * D);
 
     f32x4v xv[REP_PF][D4T];
@@ -361,9 +372,17 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
     const float bias0 = bias[0];
 
     const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
-    attn_score_rows_rep<H4L, 2, MASK, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
-    attn_score_rows_rep<H4L, 2, MASK, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
-    attn_score_rows_rep<H4L, 1, MASK, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
+    if constexpr (KP == KEEP_SEEDED) {
+        KeepSeed sq = keep_seed_of(ks...);
+        sq.word0 += (uint64_t)q0 * R * (H / 4);
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false, sq);
+        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false, sq);
+    } else {
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
+        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
+    }
     __syncthreads();
 
     if (wave < REP) {
@@ -424,11 +443,12 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
 // no thread idle and no partial sums to combine.  Scores and softmax as above.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 constexpr int REP_N_PF = 6, REP_N_POOL_BATCH = 6;
-template <int H4L, bool MASK, int REP>
+template <int H4L, int KP, int REP, typename... KS>
 __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel(
     const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
-    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R) {
+    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
+    KS... ks) {
     static_assert(REP <= FWD_THREADS / 64, "one softmax wave per query");
     constexpr int H = H4L * 256, D = 1024, D2 = D / 2;
     static_assert(D2 == FWD_THREADS, "one float2 column per thread");
@@ -438,7 +458,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel
     const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t q0 = (int64_t)mem * REP;
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
-    const unsigned* mb4 = MASK ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
+    const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
     const f32x2v* Vb2 = reinterpret_cast<const f32x2v*>(V + (int64_t)mem * R * D);
 
     f32x2v xv[REP_N_PF];
@@ -449,9 +469,17 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel
     const float bias0 = bias[0];
 
     const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
-    attn_score_rows_rep<H4L, 2, MASK, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
-    attn_score_rows_rep<H4L, 2, MASK, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
-    attn_score_rows_rep<H4L, 1, MASK, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
+    if constexpr (KP == KEEP_SEEDED) {
+        KeepSeed sq = keep_seed_of(ks...);
+        sq.word0 += (uint64_t)q0 * R * (H / 4);
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false, sq);
+        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false, sq);
+    } else {
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
+        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
+        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
+    }
     __syncthreads();
 
     if (wave < REP) {
@@ -502,7 +530,6 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
     const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
     float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, int D, int rep, KS... ks) {
-    static_assert(KP != KEEP_SEEDED || REP == 1, "seeded keep bits: one query per memory");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[D] | ds[REP][R] | comb[REP][H]
     float* dp = lds;
     float* ds = lds + D;
@@ -631,7 +658,6 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, KS... ks) {
     constexpr int D = DD, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64, RB = 4;
     static_assert(REP <= NW, "one softmax wave per query");
-    static_assert(KP != KEEP_SEEDED || REP == 1, "seeded keep bits: one query per memory");
     static_assert(D4 <= BWD_THREADS && D4 % 64 == 0, "dpooled is staged with one float4 per thread");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[REP][D] | ds[REP][40] | comb[REP][H]
     float* ds = lds + REP * D;
@@ -716,9 +742,11 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
 #pragma unroll
                     for (int j = 0; j < REP; ++j) m[i][j] = mk4[((int64_t)j * R + r) * H4 + hu];
                 }
-                if constexpr (KP == KEEP_SEEDED) {      // (REP == 1: the mask of query q0)
+                if constexpr (KP == KEEP_SEEDED) {
                     const KeepSeed sd = keep_seed_of(ks...);
-                    m[i][0] = keep_word4(sd.key, sd.word0 + ((uint64_t)q0 * R + r) * H4 + hu, sd.thr);
+#pragma unroll
+                    for (int j = 0; j < REP; ++j)
+                        m[i][j] = keep_word4(sd.key, sd.word0 + ((uint64_t)(q0 + j) * R + r) * H4 + hu, sd.thr);
                 }
             }
 #pragma unroll
@@ -836,13 +864,14 @@ constexpr bool v_is_f32() { return sizeof(VT) == sizeof(float); }
 // always checked.)
 template <typename VT>
 int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* nb, const float* w, const float* bias,
-                   const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
+                   const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream,
+                   bool seeded_one_query) {
     VQA_REQUIRE(v && qv && V && nb && w && bias && att && pooled, VQA_ERR_ARG);
     VQA_REQUIRE(keep.err == VQA_OK, keep.err);
-    VQA_REQUIRE(!keep.is_seeded() || rep == 1, VQA_ERR_UNSUPPORTED);      // the kernels for several queries per memory have
-    VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);                       // no seeded form ...
+    VQA_REQUIRE(!(seeded_one_query && keep.is_seeded()) || rep == 1, VQA_ERR_UNSUPPORTED);      // vqa_attn_pool_fwd_seeded
+    VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);         // ... and read an f32 memory only
+    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);         // several queries per memory: an f32 memory only
     VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
     VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(pooled) && keep.words_ok(), VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
@@ -856,24 +885,25 @@ int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* 
     const bool fast1024 = g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
                           vqa_aligned16(qv) && vqa_aligned16(w);
     if constexpr (v_is_f32<VT>()) {
-        // one workgroup per memory for the pre-training model's 5 queries per image (these kernels take "a mask is read"
-        // as a template bool)
+        // one workgroup per memory for the pre-training model's 5 queries per image
         if (fast1024 || (fast && rep == 5 && g_attn_fast != 3)) {
             const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
-            int_dispatch<0, 1>(keepmask != nullptr, [&](auto mk) {
-                constexpr bool MASK = decltype(mk)::value != 0;
-                if (fast1024)
-                    hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, MASK, 5>), dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V,
-                                       nb, w, bias, keepmask, ik, att, pooled, R);
-                else
-                    int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
-                        int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
-                            hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<decltype(h4l)::value, decltype(d4t)::value, MASK, 5>),
+            if (fast1024)
+                keep_dispatch(keep, [&](auto kp, auto... ks) {
+                    hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, decltype(kp)::value, 5, decltype(ks)...>), dim3(B),
+                                       dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, ks...);
+                });
+            else
+                int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
+                    int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
+                        keep_dispatch(keep, [&](auto kp, auto... ks) {
+                            hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<decltype(h4l)::value, decltype(d4t)::value,
+                                                                         decltype(kp)::value, 5, decltype(ks)...>),
                                                dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att,
-                                               pooled, R);
+                                               pooled, R, ks...);
                         });
                     });
-            });
+                });
             VQA_CHECK_LAUNCH();
             return VQA_OK;
         }
@@ -902,10 +932,10 @@ int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* 
 template <typename VT>
 int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const VT* V, const float* att, const float* w,
                    const KeepSrc& keep, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H,
-                   int D, void* stream) {
+                   int D, void* stream, bool seeded_one_query) {
     VQA_REQUIRE(dpooled && v && qv && V && att && w && dv && dqv && part_dw && part_db, VQA_ERR_ARG);
     VQA_REQUIRE(keep.err == VQA_OK, keep.err);
-    VQA_REQUIRE(!keep.is_seeded() || rep == 1, VQA_ERR_UNSUPPORTED);      // as in the forward
+    VQA_REQUIRE(!(seeded_one_query && keep.is_seeded()) || rep == 1, VQA_ERR_UNSUPPORTED);      // vqa_attn_pool_bwd_seeded
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
     VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);
@@ -935,10 +965,11 @@ int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const 
     if constexpr (v_is_f32<VT>()) {      // several queries per memory
         if (fast_shape && rep == 5 && (D == 2048 || D == 1024)) {
             int_dispatch<2048, 1024>(D, [&](auto dd) {
-                int_dispatch<KEEP_BYTES, KEEP_NONE>(keep.policy, [&](auto kp) {
-                    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, decltype(dd)::value>), dim3(B),
-                                       dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db,
-                                       R, H);
+                keep_dispatch(keep, [&](auto kp, auto... ks) {
+                    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, decltype(dd)::value, float,
+                                                                  decltype(ks)...>),
+                                       dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw,
+                                       part_db, R, H, ks...);
                 });
             });
             VQA_CHECK_LAUNCH();
@@ -946,9 +977,11 @@ int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const 
         }
         if (rep > 1) {
             int_dispatch<5, 8>(rep <= 5 ? 5 : 8, [&](auto rt) {
-                hipLaunchKernelGGL((attn_pool_bwd_kernel<decltype(rt)::value>), dim3(B), dim3(BWD_THREADS),
-                                   lds_for(decltype(rt)::value), st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw,
-                                   part_db, R, H, D, rep);
+                keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
+                    hipLaunchKernelGGL((attn_pool_bwd_kernel<decltype(rt)::value, float, decltype(kp)::value, decltype(ks)...>),
+                                       dim3(B), dim3(BWD_THREADS), lds_for(decltype(rt)::value), st, dpooled, v, qv, V, att, w,
+                                       keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep, ks...);
+                });
             });
             VQA_CHECK_LAUNCH();
             return VQA_OK;
@@ -973,20 +1006,22 @@ extern "C" int vqa_attn_set_fast(int on) {
 
 int vqa_attn_fwd_run(const float* v, const float* qv, const void* V, bool v_bf16, const int32_t* nb, const float* w,
                      const float* bias, const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D,
-                     void* stream) {
+                     void* stream, bool seeded_one_query) {
     if (v_bf16)
-        return attn_fwd_typed(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, keep, att, pooled, B, rep, R, H, D, stream);
-    return attn_fwd_typed(v, qv, static_cast<const float*>(V), nb, w, bias, keep, att, pooled, B, rep, R, H, D, stream);
+        return attn_fwd_typed(v, qv, static_cast<const uint16_t*>(V), nb, w, bias, keep, att, pooled, B, rep, R, H, D, stream,
+                              seeded_one_query);
+    return attn_fwd_typed(v, qv, static_cast<const float*>(V), nb, w, bias, keep, att, pooled, B, rep, R, H, D, stream,
+                          seeded_one_query);
 }
 
 int vqa_attn_bwd_run(const float* dpooled, const float* v, const float* qv, const void* V, bool v_bf16, const float* att,
                      const float* w, const KeepSrc& keep, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
-                     int R, int H, int D, void* stream) {
+                     int R, int H, int D, void* stream, bool seeded_one_query) {
     if (v_bf16)
         return attn_bwd_typed(dpooled, v, qv, static_cast<const uint16_t*>(V), att, w, keep, dv, dqv, part_dw, part_db, B, rep, R,
-                              H, D, stream);
+                              H, D, stream, seeded_one_query);
     return attn_bwd_typed(dpooled, v, qv, static_cast<const float*>(V), att, w, keep, dv, dqv, part_dw, part_db, B, rep, R, H, D,
-                          stream);
+                          stream, seeded_one_query);
 }
 
 extern "C" int vqa_attn_pool_fwd(const float* v, const float* qv, const float* V, const int32_t* nb, const float* w,
@@ -1009,12 +1044,23 @@ extern "C" int vqa_attn_pool_fwd_v16(const float* v, const float* qv, const uint
 }
 
 // The keep bits of the score's dropout computed in the kernel instead of loaded: the kernels the explicit entry points
-// select for the shape (same route selection), instantiated with KEEP_SEEDED.  One query per memory.
+// select for the shape (same route selection), instantiated with KEEP_SEEDED.  These two entry points keep the contract
+// they were published with: one query per memory, rep != 1 -> VQA_ERR_UNSUPPORTED.  Several queries per memory:
+// vqa_attn_pool_fwd_rep_seeded / vqa_attn_pool_bwd_rep_seeded below.
 extern "C" int vqa_attn_pool_fwd_seeded(const float* v, const float* qv, const void* V, int v_bf16, const int32_t* nb,
                                         const float* w, const float* bias, uint64_t seed, uint64_t offset, float keep_prob,
                                         float* att, float* pooled, int B, int rep, int R, int H, int D, void* stream) {
     return vqa_attn_fwd_run(v, qv, V, v_bf16 != 0, nb, w, bias, KeepSrc::seeded(seed, offset, H, keep_prob), att, pooled, B, rep,
-                            R, H, D, stream);
+                            R, H, D, stream, true);
+}
+
+// vqa_attn_pool_fwd_rep with the keep bits computed: rep queries per memory, the mask of query q = m * rep + j at stream
+// position offset + q * R * H, as in the explicit [B * rep, R, H] mask
+extern "C" int vqa_attn_pool_fwd_rep_seeded(const float* v, const float* qv, const float* V, const int32_t* nb, const float* w,
+                                            const float* bias, uint64_t seed, uint64_t offset, float keep_prob, float* att,
+                                            float* pooled, int B, int rep, int R, int H, int D, void* stream) {
+    return vqa_attn_fwd_run(v, qv, V, false, nb, w, bias, KeepSrc::seeded(seed, offset, H, keep_prob), att, pooled, B, rep, R, H,
+                            D, stream);
 }
 
 extern "C" int vqa_attn_pool_bwd(const float* dpooled, const float* v, const float* qv, const float* V,
@@ -1044,6 +1090,14 @@ extern "C" int vqa_attn_pool_bwd_seeded(const float* dpooled, const float* v, co
                                         float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H,
                                         int D, void* stream) {
     return vqa_attn_bwd_run(dpooled, v, qv, V, v_bf16 != 0, att, w, KeepSrc::seeded(seed, offset, H, keep_prob), dv, dqv, part_dw,
+                            part_db, B, rep, R, H, D, stream, true);
+}
+
+extern "C" int vqa_attn_pool_bwd_rep_seeded(const float* dpooled, const float* v, const float* qv, const float* V,
+                                            const float* att, const float* w, uint64_t seed, uint64_t offset, float keep_prob,
+                                            float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep, int R, int H,
+                                            int D, void* stream) {
+    return vqa_attn_bwd_run(dpooled, v, qv, V, false, att, w, KeepSrc::seeded(seed, offset, H, keep_prob), dv, dqv, part_dw,
                             part_db, B, rep, R, H, D, stream);
 }
 

@@ -1,6 +1,6 @@
 // Launch functions of the kernels that have a dropout site (layernorm.hip, attention.hip), with the site's keep source
-// as a KeepSrc: what the explicit-mask and the *_seeded entry points of the C ABI wrap, and what the fusion step calls
-// directly (fusion_model.hip).  Same checks and return codes as the entry points; a combination of keep source, queries
+// as a KeepSrc: what the explicit-mask and the *_seeded entry points of the C ABI wrap, and what the fusion step and the
+// pre-training steps call directly (fusion_model.hip, pretrain_model.hip).  Same checks and return codes as the entry points; a combination of keep source, queries
 // per memory and memory type that has no kernel is refused here.  Internal: nothing here is part of the C ABI.
 #pragma once
 #include "vqa_common.h"
@@ -16,11 +16,13 @@ int vqa_ln_relu_att_bwd_run(const float* ds, const float* qv, const float* w, co
                             float* part_dgamma, float* part_dbeta, float* part_dbias, float* dqv, float* part_dw, int B, int rep,
                             int R, int H, int D, void* stream);
 
-// attention.hip.  V: float, or raw bf16 patterns (v_bf16).  Seeded, and a bf16 memory: one query per memory (rep == 1)
-// only, VQA_ERR_UNSUPPORTED otherwise
+// attention.hip.  V: float, or raw bf16 patterns (v_bf16).  rep queries per memory, 1..8, with any keep source (the mask
+// of query q = m * rep + j: rows q * R .. of the [B * rep, R, H] mask or stream); a bf16 memory: rep == 1 only,
+// VQA_ERR_UNSUPPORTED otherwise.  seeded_one_query: the contract of vqa_attn_pool_fwd_seeded / _bwd_seeded, which refuse a
+// seeded source with rep != 1 (VQA_ERR_UNSUPPORTED, where they always checked it)
 int vqa_attn_fwd_run(const float* v, const float* qv, const void* V, bool v_bf16, const int32_t* nb, const float* w,
                      const float* bias, const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D,
-                     void* stream);
+                     void* stream, bool seeded_one_query = false);
 int vqa_attn_bwd_run(const float* dpooled, const float* v, const float* qv, const void* V, bool v_bf16, const float* att,
                      const float* w, const KeepSrc& keep, float* dv, float* dqv, float* part_dw, float* part_db, int B, int rep,
-                     int R, int H, int D, void* stream);
+                     int R, int H, int D, void* stream, bool seeded_one_query = false);

@@ -35,7 +35,7 @@
 #include <string>
 #include <vector>
 
-#include "vqa_common.h"
+#include "keep_launch.h"
 
 namespace {
 
@@ -123,6 +123,14 @@ struct Ctx {
     const Layout& L;
     char* ws;
     hipStream_t st;
+    const vqa_pretrain_keep_t* keep = nullptr;      // the *_ex entry points' seeded sites; NULL: every site reads its mask
+    // The keep source of one dropout site: `bit` = its VQA_PT_KEEP_SITE_* bit, `mask` = its mask pointer of the batch, `off`
+    // = its stream offset of the keep struct, row_len = the row length of the op that consumes it.  Every mask site of
+    // the forward and the backward resolves through here and hands the result to the op's launch function (keep_launch.h).
+    KeepSrc site(int bit, const uint8_t* mask, uint64_t off, float keep_prob, int64_t row_len) const {
+        if (keep != nullptr && (keep->seeded & bit)) return KeepSrc::seeded(keep->keep_seed, off, row_len, keep_prob);
+        return KeepSrc::bytes(mask, keep_prob);
+    }
     float* f(const std::string& name) const { return reinterpret_cast<float*>(ws + L.find(name)->off); }
     int32_t* i32(const std::string& name) const { return reinterpret_cast<int32_t*>(ws + L.find(name)->off); }
     int64_t count(const std::string& name) const { return L.find(name)->n; }
@@ -152,11 +160,12 @@ enum Prec { PREC_F32, PREC_ROUTED };      // which of the two a helper shared by
 // Its users are the unrouted layers (K = 6 box layers, wordset_ft): the product is f32 in every mode.
 int fc_ln_fwd(const Ctx& c, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc6_t& p, int ln, int rows,
               int act, const std::string& pre, const std::string& y, const std::string& mean, const std::string& rstd,
-              const uint8_t* keep, float keep_prob) {
+              const KeepSrc& keep) {
     TRY(c.gemm_f32(0, 0, M, N, K, x, (int)K, p.w, (int)N, c.f(pre), (int)N, p.b));
-    return vqa_ln_act_fwd(c.f(pre), p.gamma[ln], p.beta[ln], keep, keep_prob, c.f(y), c.f(mean), c.f(rstd),
-                          (int)(M / rows), rows, (int)N, act, c.st);
+    return vqa_ln_act_fwd_run(c.f(pre), p.gamma[ln], p.beta[ln], keep, c.f(y), c.f(mean), c.f(rstd), (int)(M / rows), rows,
+                              (int)N, act, c.st);
 }
+const KeepSrc NO_KEEP;      // a layer without dropout
 
 // Gradient accumulation over the call sites that share a variable: the first contribution overwrites (gradient
 // buffers are not cleared between steps), later ones add.
@@ -196,11 +205,10 @@ struct Acc {
 // backward of the LayerNorm / activation half of fc_ln_fwd on pointers (the stacked heads hand in their slices):
 // dy -> d_pre; gamma, beta and bias gradients accumulated
 int ln_bwd(const Ctx& c, Acc& acc, const float* dy, int64_t M, int64_t N, const vqa_pt_fc6_t& p, const vqa_pt_fc6_t& g, int ln,
-           int rows, int act, const float* pre, const float* mean, const float* rstd, const uint8_t* keep, float keep_prob,
-           float* d_pre) {
+           int rows, int act, const float* pre, const float* mean, const float* rstd, const KeepSrc& keep, float* d_pre) {
     const int64_t G = M / rows;
-    TRY(vqa_ln_act_bwd(dy, pre, mean, rstd, p.gamma[ln], p.beta[ln], keep, keep_prob, d_pre, c.f("part_a"), c.f("part_b"),
-                       c.f("part_c"), (int)G, rows, (int)N, act, c.st));
+    TRY(vqa_ln_act_bwd_run(dy, pre, mean, rstd, p.gamma[ln], p.beta[ln], keep, d_pre, c.f("part_a"), c.f("part_b"),
+                           c.f("part_c"), (int)G, rows, (int)N, act, c.st));
     return acc.colsum3(c.f("part_a"), c.f("part_b"), c.f("part_c"), G, N, g.gamma[ln], g.beta[ln], g.b);
 }
 
@@ -216,8 +224,8 @@ int fc_bwd(const Ctx& c, Acc& acc, Prec prec, const std::string& d_pre, const fl
 // backward of fc_ln_fwd (the unrouted layers: f32 products)
 int fc_ln_bwd(const Ctx& c, Acc& acc, const float* dy, const float* x, int64_t M, int64_t K, int64_t N, const vqa_pt_fc6_t& p,
               const vqa_pt_fc6_t& g, int ln, int rows, int act, const std::string& pre, const std::string& mean,
-              const std::string& rstd, const uint8_t* keep, float keep_prob, const std::string& d_pre, float* dx) {
-    TRY(ln_bwd(c, acc, dy, M, N, p, g, ln, rows, act, c.f(pre), c.f(mean), c.f(rstd), keep, keep_prob, c.f(d_pre)));
+              const std::string& rstd, const KeepSrc& keep, const std::string& d_pre, float* dx) {
+    TRY(ln_bwd(c, acc, dy, M, N, p, g, ln, rows, act, c.f(pre), c.f(mean), c.f(rstd), keep, c.f(d_pre)));
     return fc_bwd(c, acc, PREC_F32, d_pre, x, M, K, N, p, g, dx);
 }
 
@@ -450,9 +458,40 @@ std::string ext_report_key(int heads, int i) {
 // the memory the spatial attention pools when it is not the batch's image_ft [B,R,D]: one [B,R,width] block per category
 struct PoolMem { const float* mem[2]; int64_t width; };
 
-// joint_fc dropout mask of the head of type t, category k
-const uint8_t* joint_keep(const vqa_pretrain_ext_batch_t& x, int k, int t) {
-    return t == 0 ? x.base.kind[k].keep_bf_joint : t == 1 ? x.base.kind[k].keep_ws_joint : x.ctx[k].keep_ew_joint;
+// the keep struct's offsets, or zeros without one
+const vqa_pretrain_keep_t NO_SEEDED_SITES = {};
+const vqa_pretrain_keep_t& keep_of(const Ctx& c) { return c.keep ? *c.keep : NO_SEEDED_SITES; }
+
+// dropout of the attention score, category k: [B*n, R, H]
+KeepSrc att_keep(const Ctx& c, const vqa_pretrain_ext_batch_t& x, int k) {
+    return c.site(VQA_PT_KEEP_SITE_ATT, x.base.kind[k].keep_att, keep_of(c).att_off[k], c.d.keep_att, c.d.H);
+}
+
+// joint_fc dropout of the head of type t, category k: [B*n, 2H]
+KeepSrc joint_keep(const Ctx& c, const vqa_pretrain_ext_batch_t& x, int k, int t) {
+    const vqa_pretrain_keep_t& o = keep_of(c);
+    const int64_t N = 2 * (int64_t)c.d.H;
+    if (t == 0) return c.site(VQA_PT_KEEP_SITE_BF_JOINT, x.base.kind[k].keep_bf_joint, o.bf_joint_off[k], c.d.keep_joint, N);
+    if (t == 1) return c.site(VQA_PT_KEEP_SITE_WS_JOINT, x.base.kind[k].keep_ws_joint, o.ws_joint_off[k], c.d.keep_joint, N);
+    return c.site(VQA_PT_KEEP_SITE_EW_JOINT, x.ctx[k].keep_ew_joint, o.ew_joint_off[k], c.d.keep_joint, N);
+}
+
+// a seeded site must not also carry a mask; unknown site bits are refused (checked with the entry point's other arguments,
+// before the workspace).  noc_l: the l branch's masks of a noc batch
+int keep_sites_ok(const vqa_pretrain_keep_t* ks, const vqa_pretrain_ext_batch_t& x, const vqa_pretrain_noc_kind_t* noc_l) {
+    if (ks == nullptr) return VQA_OK;
+    VQA_REQUIRE((ks->seeded & ~VQA_PT_KEEP_SITE_ALL) == 0, VQA_ERR_ARG);
+    for (int k = 0; k < 2; ++k) {
+        const vqa_pretrain_kind_t& kb = x.base.kind[k];
+        VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_ATT) || kb.keep_att == nullptr, VQA_ERR_ARG);
+        VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_BF_JOINT) || kb.keep_bf_joint == nullptr, VQA_ERR_ARG);
+        VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_WS_JOINT) || kb.keep_ws_joint == nullptr, VQA_ERR_ARG);
+        VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_EW_JOINT) || x.ctx[k].keep_ew_joint == nullptr, VQA_ERR_ARG);
+        if (noc_l != nullptr)
+            VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_L_JOINT) ||
+                        (!noc_l[k].keep_bf_l_joint && !noc_l[k].keep_ws_l_joint && !noc_l[k].keep_ew_l_joint), VQA_ERR_ARG);
+    }
+    return VQA_OK;
 }
 
 // what the trunk dereferences, checked before the first launch
@@ -617,12 +656,12 @@ int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_p
                            c.f(p + "key6"), (int)Bn);
         VQA_CHECK_LAUNCH();
         TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, c.li(k), (int)R, 0, p + "v_pre", p + "v",
-                      p + "v_mean", p + "v_rstd", nullptr, 1.f));
+                      p + "v_mean", p + "v_rstd", NO_KEEP));
         TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, c.li(k), (int)n, 0, p + "qv_pre", p + "qv",
-                      p + "qv_mean", p + "qv_rstd", nullptr, 1.f));
-        TRY(vqa_attn_pool_fwd_rep(c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, bt->num_boxes,
-                                  P->spat_att_score.w, P->spat_att_score.b, kb.keep_att, d->keep_att, c.f(p + "att"),
-                                  c.f(p + "pooled"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
+                      p + "qv_mean", p + "qv_rstd", NO_KEEP));
+        TRY(vqa_attn_fwd_run(c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, false, bt->num_boxes,
+                             P->spat_att_score.w, P->spat_att_score.b, att_keep(c, *bx, k), c.f(p + "att"), c.f(p + "pooled"),
+                             (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
                            (int)B, (int)n, d->global_valid[k]);
         VQA_CHECK_LAUNCH();
@@ -630,7 +669,7 @@ int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_p
             TRY(vqa_embed_fwd(P->wordset_map, kb.wordsets, c.f(p + "wse"), (int)Bn, 1, (int)W, d->n_ws, c.st));
             TRY(vqa_tanh_fwd(c.f(p + "wse"), c.f(p + "ws"), Bn * W, c.st));
             TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, P->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
-                          p + "wf_rstd", nullptr, 1.f));
+                          p + "wf_rstd", NO_KEEP));
         }
     }
     // ---- build_*_blank_fill -> heads 0 / 1 of "S/lft", build_*_enwiki -> heads 2 r_ew + k
@@ -661,7 +700,7 @@ int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, c
         const std::string p = std::string(KIND[k]) + "/";
         if (hs.rank[1] >= 0) {      // ---- word set -> wordset_ft -> tanh -> wordset_map
             TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 * hs.rank[1] + k) * Bn * H, c.f(p + "ws"), Bn, W, H, P->wordset_ft,
-                          G->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", nullptr, 1.f, "d_wfpre",
+                          G->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", NO_KEEP, "d_wfpre",
                           c.f("d_ws")));
             TRY(vqa_tanh_bwd(c.f("d_ws"), c.f(p + "ws"), c.f("d_wse"), Bn * W, c.st));
             TRY(vqa_embed_bwd_len_det(c.f("d_wse"), kb.wordsets, nullptr, G->wordset_map, (int)Bn, 1, (int)W, d->n_ws, det,
@@ -669,15 +708,15 @@ int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, c
             TRY(sq.add(c.f("d_wse"), Bn * W));
         }
         // ---- spatial attention
-        TRY(vqa_attn_pool_bwd_rep(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft,
-                                  c.f(p + "att"), P->spat_att_score.w, kb.keep_att, d->keep_att, c.f("d_v"), c.f("d_qv"),
-                                  c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
+        TRY(vqa_attn_bwd_run(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, false,
+                             c.f(p + "att"), P->spat_att_score.w, att_keep(c, *bx, k), c.f("d_v"), c.f("d_qv"),
+                             c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G->spat_att_score.w));
         TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G->spat_att_score.b));
         TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, G->spat_v_linear_v, c.li(k), (int)R,
-                      0, p + "v_pre", p + "v_mean", p + "v_rstd", nullptr, 1.f, "d_vpre", nullptr));
+                      0, p + "v_pre", p + "v_mean", p + "v_rstd", NO_KEEP, "d_vpre", nullptr));
         TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, G->spat_q_linear_v, c.li(k), (int)n,
-                      0, p + "qv_pre", p + "qv_mean", p + "qv_rstd", nullptr, 1.f, "d_qvpre", nullptr));
+                      0, p + "qv_pre", p + "qv_mean", p + "qv_rstd", NO_KEEP, "d_qvpre", nullptr));
     }
     if ((phases & 8) && slice_sq != nullptr && sq.prev != nullptr)
         if (hipMemcpyAsync(slice_sq, sq.prev, sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
@@ -696,10 +735,10 @@ int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, co
     TRY(c.gemm_routed(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, qlin.w, (int)H, c.f("S/ll_pre"), (int)H, qlin.b));
     for (int h = 0; h < NH; ++h) {
         const std::string q = hs.name(h);
-        TRY(vqa_ln_act_fwd(c.f("S/vl_pre") + (h & 1) * SH, pooled.gamma[c.li(h)], pooled.beta[c.li(h)], nullptr, 1.f,
-                           c.f("S/vl") + h * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n, (int)H, 0, c.st));
-        TRY(vqa_ln_act_fwd(c.f("S/ll_pre") + h * SH, qlin.gamma[c.li(h)], qlin.beta[c.li(h)], nullptr, 1.f, c.f("S/ll") + h * SH,
-                           c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
+        TRY(vqa_ln_act_fwd_run(c.f("S/vl_pre") + (h & 1) * SH, pooled.gamma[c.li(h)], pooled.beta[c.li(h)], NO_KEEP,
+                               c.f("S/vl") + h * SH, c.f(q + "vl_mean"), c.f(q + "vl_rstd"), (int)B, (int)n, (int)H, 0, c.st));
+        TRY(vqa_ln_act_fwd_run(c.f("S/ll_pre") + h * SH, qlin.gamma[c.li(h)], qlin.beta[c.li(h)], NO_KEEP, c.f("S/ll") + h * SH,
+                               c.f(q + "ll_mean"), c.f(q + "ll_rstd"), (int)B, (int)n, (int)H, 0, c.st));
     }
     return VQA_OK;
 }
@@ -712,9 +751,9 @@ int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& 
     for (int h = 0; h < NH; ++h) {
         const std::string q = hs.name(h);
         TRY(ln_bwd(c, acc, c.f("d_vl") + h * SH, Bn, H, pooled, g_pooled, c.li(h), (int)n, 0, c.f("S/vl_pre") + (h & 1) * SH,
-                   c.f(q + "vl_mean"), c.f(q + "vl_rstd"), nullptr, 1.f, c.f("d_vlpre") + h * SH));
+                   c.f(q + "vl_mean"), c.f(q + "vl_rstd"), NO_KEEP, c.f("d_vlpre") + h * SH));
         TRY(ln_bwd(c, acc, c.f("d_ll") + h * SH, Bn, H, qlin, g_qlin, c.li(h), (int)n, 0, c.f("S/ll_pre") + h * SH,
-                   c.f(q + "ll_mean"), c.f(q + "ll_rstd"), nullptr, 1.f, c.f("d_llpre") + h * SH));
+                   c.f(q + "ll_mean"), c.f(q + "ll_rstd"), NO_KEEP, c.f("d_llpre") + h * SH));
     }
     // every head of a category applies pooled_linear_l to the same pooled rows: their d_pre meet before one dW / dx
     for (int r = 1; r < hs.nt; ++r) TRY(vqa_add_inplace(c.f("d_vlpre"), c.f("d_vlpre") + 2 * r * SH, 2 * SH, c.st));
@@ -760,8 +799,8 @@ int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t
     TRY(c.gemm_routed(0, 0, B * R, H, D, bt->image_ft, (int)D, va.w, (int)H, c.f("va_pre"), (int)H, va.b));
     for (int k = 0; k < (ln_shared ? 1 : 2); ++k) {
         const std::string p = std::string(KIND[k]) + "/";
-        TRY(vqa_ln_act_fwd(c.f("va_pre"), va.gamma[k], va.beta[k], nullptr, 1.f, c.f(p + "va"), c.f(p + "va_mean"),
-                           c.f(p + "va_rstd"), (int)B, (int)R, (int)H, 0, c.st));
+        TRY(vqa_ln_act_fwd_run(c.f("va_pre"), va.gamma[k], va.beta[k], NO_KEEP, c.f(p + "va"), c.f(p + "va_mean"),
+                               c.f(p + "va_rstd"), (int)B, (int)R, (int)H, 0, c.st));
     }
     pm->mem[0] = c.f("obj/va"); pm->mem[1] = c.f("attr/va"); pm->width = H;
     return VQA_OK;
@@ -779,13 +818,13 @@ int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vq
     if (ln_shared) {
         TRY(vqa_outer_rows_rep(c.f("obj/att"), dp[0], c.f("attr/att"), dp[1], c.f("d_va"), (int)B, (int)n, (int)R, (int)H, c.st));
         TRY(ln_bwd(c, acc, c.f("d_va"), B * R, H, va, g_va, 0, (int)R, 0, c.f("va_pre"), c.f("va_mean"), c.f("va_rstd"),
-                   nullptr, 1.f, c.f("d_vapre")));
+                   NO_KEEP, c.f("d_vapre")));
     } else {
         for (int k = 0; k < 2; ++k) {
             const std::string p = std::string(KIND[k]) + "/";
             TRY(vqa_outer_rows_rep(c.f(p + "att"), dp[k], nullptr, nullptr, c.f("d_va"), (int)B, (int)n, (int)R, (int)H, c.st));
             TRY(ln_bwd(c, acc, c.f("d_va"), B * R, H, va, g_va, k, (int)R, 0, c.f("va_pre"), c.f(p + "va_mean"),
-                       c.f(p + "va_rstd"), nullptr, 1.f, c.f(k == 0 ? "d_vapre" : "d_vapre1")));
+                       c.f(p + "va_rstd"), NO_KEEP, c.f(k == 0 ? "d_vapre" : "d_vapre1")));
         }
         TRY(vqa_add_inplace(c.f("d_vapre"), c.f("d_vapre1"), B * R * H, c.st));
     }
@@ -795,11 +834,11 @@ int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vq
 // forward of the variable-head-set model on the layout L; va != NULL: with the v_adapt layer (vqa_pretrain_adapt_*)
 int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                      const vqa_pretrain_ext_batch_t* bx, void* workspace, int want_dz, void* stream,
-                     const vqa_pt_fc6_t* va) {
+                     const vqa_pt_fc6_t* va, const vqa_pretrain_keep_t* ks) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
     const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), ks};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
     TRY(trunk_inputs_ok(hs, P, bx));
     ReportExtArgs ra{};
@@ -818,9 +857,9 @@ int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const
                           (int)(2 * H), P->joint_fc.b));
         for (int h = 0; h < NH; ++h) {
             const std::string q = hs.name(h);
-            TRY(vqa_ln_act_fwd(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[c.li(h)], P->joint_fc.beta[c.li(h)],
-                               joint_keep(*bx, h & 1, hs.type[h >> 1]), d->keep_joint, c.f("S/j") + h * SJ,
-                               c.f(q + "j_mean"), c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0, c.st));
+            TRY(vqa_ln_act_fwd_run(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[c.li(h)], P->joint_fc.beta[c.li(h)],
+                                   joint_keep(c, *bx, h & 1, hs.type[h >> 1]), c.f("S/j") + h * SJ, c.f(q + "j_mean"),
+                                   c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0, c.st));
         }
         TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
                           P->classifier.b));
@@ -841,14 +880,21 @@ int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const
 
 }  // namespace
 
-extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
-                                        int want_dz, void* stream) {
+extern "C" int vqa_pretrain_ext_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                           const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                           int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
     VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, *bx, nullptr));
     const Layout L = make_layout_ext(*dims);
     VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
     VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    return ext_forward_impl(L, dims, P, bx, workspace, want_dz, stream, nullptr);
+    return ext_forward_impl(L, dims, P, bx, workspace, want_dz, stream, nullptr, keep);
+}
+
+extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                        int want_dz, void* stream) {
+    return vqa_pretrain_ext_forward_ex(dims, P, bx, workspace, workspace_bytes, want_dz, stream, nullptr);
 }
 
 // Backward phases of the variable head set; the buckets of vqa_pretrain_backward_phases, with
@@ -861,11 +907,12 @@ namespace {
 // va / g_va != NULL: with the v_adapt layer, whose gradients complete phase 8
 int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                       const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, void* workspace,
-                      float* slice_sq, int phases, void* stream, const vqa_pt_fc6_t* va, const vqa_pt_fc6_t* g_va) {
+                      float* slice_sq, int phases, void* stream, const vqa_pt_fc6_t* va, const vqa_pt_fc6_t* g_va,
+                      const vqa_pretrain_keep_t* ks) {
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bx->base;
     const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), ks};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
     ProbeScope ps_all("pretrain_ext.backward", c.st);
     Acc acc{c, {}};
@@ -878,8 +925,8 @@ int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, cons
         for (int h = 0; h < NH; ++h) {
             const std::string q = hs.name(h);
             TRY(ln_bwd(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, P->joint_fc, G->joint_fc, c.li(h), (int)n, 0,
-                       c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), joint_keep(*bx, h & 1, hs.type[h >> 1]),
-                       d->keep_joint, c.f("d_jpre") + h * SJ));
+                       c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), joint_keep(c, *bx, h & 1, hs.type[h >> 1]),
+                       c.f("d_jpre") + h * SJ));
         }
         TRY(fc_bwd(c, acc, PREC_ROUTED, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, P->joint_fc, G->joint_fc, c.f("d_jin")));
         TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
@@ -893,15 +940,23 @@ int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, cons
 
 }  // namespace
 
+extern "C" int vqa_pretrain_ext_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                                   const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                   void* stream, const vqa_pretrain_keep_t* keep) {
+    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, *bx, nullptr));
+    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    const Layout L = make_layout_ext(*dims);
+    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
+    return ext_backward_impl(L, dims, P, G, bx, workspace, slice_sq, phases, stream, nullptr, nullptr, keep);
+}
+
 extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
                                                 const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
                                                 void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                                 void* stream) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    return ext_backward_impl(L, dims, P, G, bx, workspace, slice_sq, phases, stream, nullptr, nullptr);
+    return vqa_pretrain_ext_backward_phases_ex(dims, P, G, bx, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
 }
 
 extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
@@ -963,25 +1018,38 @@ extern "C" int vqa_pretrain_tensor(const vqa_pretrain_dims_t* dims, const char* 
     return layout_tensor(make_layout_ext(x), name, offset_bytes, n_elems);
 }
 
-extern "C" int vqa_pretrain_forward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
-                                    const vqa_pretrain_batch_t* bt, void* workspace, int64_t workspace_bytes,
-                                    int want_dz, void* stream) {
+extern "C" int vqa_pretrain_forward_ex(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
+                                       const vqa_pretrain_batch_t* bt, void* workspace, int64_t workspace_bytes,
+                                       int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
     vqa_pretrain_ext_dims_t x;
     VQA_REQUIRE(cfg5_dims(dims, &x) && P && bt && workspace, VQA_ERR_ARG);
     const vqa_pretrain_ext_params_t EP = cfg5_params(*P);
     const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
-    return vqa_pretrain_ext_forward(&x, &EP, &bx, workspace, workspace_bytes, want_dz, stream);
+    return vqa_pretrain_ext_forward_ex(&x, &EP, &bx, workspace, workspace_bytes, want_dz, stream, keep);
+}
+
+extern "C" int vqa_pretrain_forward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
+                                    const vqa_pretrain_batch_t* bt, void* workspace, int64_t workspace_bytes,
+                                    int want_dz, void* stream) {
+    return vqa_pretrain_forward_ex(dims, P, bt, workspace, workspace_bytes, want_dz, stream, nullptr);
+}
+
+extern "C" int vqa_pretrain_backward_phases_ex(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
+                                               const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt,
+                                               void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                               void* stream, const vqa_pretrain_keep_t* keep) {
+    vqa_pretrain_ext_dims_t x;
+    VQA_REQUIRE(cfg5_dims(dims, &x) && P && G && bt && workspace, VQA_ERR_ARG);
+    const vqa_pretrain_ext_params_t EP = cfg5_params(*P), EG = cfg5_params(*G);
+    const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
+    return vqa_pretrain_ext_backward_phases_ex(&x, &EP, &EG, &bx, workspace, workspace_bytes, slice_sq, phases, stream, keep);
 }
 
 extern "C" int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
                                             const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt,
                                             void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                             void* stream) {
-    vqa_pretrain_ext_dims_t x;
-    VQA_REQUIRE(cfg5_dims(dims, &x) && P && G && bt && workspace, VQA_ERR_ARG);
-    const vqa_pretrain_ext_params_t EP = cfg5_params(*P), EG = cfg5_params(*G);
-    const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
-    return vqa_pretrain_ext_backward_phases(&x, &EP, &EG, &bx, workspace, workspace_bytes, slice_sq, phases, stream);
+    return vqa_pretrain_backward_phases_ex(dims, P, G, bt, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
 }
 
 extern "C" int vqa_pretrain_backward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
@@ -1018,10 +1086,11 @@ vqa_pretrain_ext_params_t noc_trunk(const vqa_pretrain_noc_params_t& p) {
     return e;
 }
 
-// keep-mask of the l joint branch of the head of type t, category k (the v branch has joint_keep of the ext batch)
-const uint8_t* noc_lmask(const vqa_pretrain_noc_batch_t* b, int k, int t) {
+// dropout of the l joint branch of the head of type t, category k (the v branch has joint_keep of the ext batch)
+KeepSrc noc_lmask(const Ctx& c, const vqa_pretrain_noc_batch_t* b, int k, int t) {
     const vqa_pretrain_noc_kind_t& l = b->l[k];
-    return t == 0 ? l.keep_bf_l_joint : t == 1 ? l.keep_ws_l_joint : l.keep_ew_l_joint;
+    return c.site(VQA_PT_KEEP_SITE_L_JOINT, t == 0 ? l.keep_bf_l_joint : t == 1 ? l.keep_ws_l_joint : l.keep_ew_l_joint,
+                  keep_of(c).l_joint_off[k][t], c.d.keep_joint, 2 * (int64_t)c.d.H);
 }
 
 std::string noc_report_key(int heads, int i) {
@@ -1073,7 +1142,14 @@ extern "C" int vqa_pretrain_noc_tensor(const vqa_pretrain_ext_dims_t* dims, cons
 extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
                                         const vqa_pretrain_noc_batch_t* bn, void* workspace, int64_t workspace_bytes,
                                         int want_dz, void* stream) {
+    return vqa_pretrain_noc_forward_ex(dims, P, bn, workspace, workspace_bytes, want_dz, stream, nullptr);
+}
+
+extern "C" int vqa_pretrain_noc_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                           const vqa_pretrain_noc_batch_t* bn, void* workspace, int64_t workspace_bytes,
+                                           int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
     VQA_REQUIRE(noc_dims_ok(dims) && P && bn && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, bn->base, bn->l));
     const Layout L = make_layout_ext(*dims, true);
     VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
     VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
@@ -1081,7 +1157,7 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
     const vqa_pretrain_dims_t* d = &dims->base;
     const vqa_pretrain_batch_t* bt = &bn->base.base;
     const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
     ProbeScope ps_all("pretrain_noc.forward", c.st);
     const vqa_pretrain_ext_params_t E = noc_trunk(*P);
@@ -1099,12 +1175,12 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
         for (int h = 0; h < NH; ++h) {
             const int k = h & 1, t = hs.type[h >> 1];
             const std::string q = hs.name(h);
-            TRY(vqa_ln_act_fwd(c.f("S/jv_pre") + h * SJ, P->joint_v.gamma[c.li(h)], P->joint_v.beta[c.li(h)], joint_keep(bn->base, k, t),
-                               d->keep_joint, c.f("S/jv") + h * SJ, c.f(q + "jv_mean"), c.f(q + "jv_rstd"), (int)B, (int)n,
-                               (int)(2 * H), 0, c.st));
-            TRY(vqa_ln_act_fwd(c.f("S/jl_pre") + h * SJ, P->joint_l.gamma[c.li(h)], P->joint_l.beta[c.li(h)], noc_lmask(bn, k, t),
-                               d->keep_joint, c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"), (int)B, (int)n,
-                               (int)(2 * H), 0, c.st));
+            TRY(vqa_ln_act_fwd_run(c.f("S/jv_pre") + h * SJ, P->joint_v.gamma[c.li(h)], P->joint_v.beta[c.li(h)],
+                                   joint_keep(c, bn->base, k, t), c.f("S/jv") + h * SJ, c.f(q + "jv_mean"), c.f(q + "jv_rstd"),
+                                   (int)B, (int)n, (int)(2 * H), 0, c.st));
+            TRY(vqa_ln_act_fwd_run(c.f("S/jl_pre") + h * SJ, P->joint_l.gamma[c.li(h)], P->joint_l.beta[c.li(h)],
+                                   noc_lmask(c, bn, k, t), c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"),
+                                   (int)B, (int)n, (int)(2 * H), 0, c.st));
         }
         TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jv"), (int)(2 * H), P->classifier_v.w, (int)A, c.f("S/zv"),
                           (int)A, P->classifier_v.b));
@@ -1145,13 +1221,21 @@ extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* d
                                                 const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
                                                 void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                                 void* stream) {
+    return vqa_pretrain_noc_backward_phases_ex(dims, P, G, bn, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
+}
+
+extern "C" int vqa_pretrain_noc_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                                   const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
+                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                   void* stream, const vqa_pretrain_keep_t* keep) {
     VQA_REQUIRE(noc_dims_ok(dims) && P && G && bn && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, bn->base, bn->l));
     VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
     const Layout L = make_layout_ext(*dims, true);
     VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
     const vqa_pretrain_dims_t* d = &dims->base;
     const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream)};
+    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
     const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
     ProbeScope ps_all("pretrain_noc.backward", c.st);
     Acc acc{c, {}};
@@ -1175,7 +1259,7 @@ extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* d
                 const std::string q = hs.name(h) + b.tag;
                 TRY(ln_bwd(c, acc, c.f(b.dj) + h * SJ, Bn, 2 * H, *b.jP, *b.jG, c.li(h), (int)n, 0,
                              c.f(b.jpre) + h * SJ, c.f(q + "_mean"), c.f(q + "_rstd"),
-                             v == 0 ? joint_keep(bn->base, k, t) : noc_lmask(bn, k, t), d->keep_joint, c.f(b.djpre) + h * SJ));
+                             v == 0 ? joint_keep(c, bn->base, k, t) : noc_lmask(c, bn, k, t), c.f(b.djpre) + h * SJ));
             }
             TRY(fc_bwd(c, acc, PREC_ROUTED, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, *b.jP, *b.jG, c.f(b.din)));
         }
@@ -1219,28 +1303,44 @@ extern "C" int vqa_pretrain_adapt_tensor(const vqa_pretrain_ext_dims_t* dims, co
 extern "C" int vqa_pretrain_adapt_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
                                           const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
                                           int want_dz, void* stream) {
+    return vqa_pretrain_adapt_forward_ex(dims, P, bx, workspace, workspace_bytes, want_dz, stream, nullptr);
+}
+
+extern "C" int vqa_pretrain_adapt_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                             const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                             int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
     VQA_REQUIRE(adapt_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, *bx, nullptr));
     const bool ln_shared = (dims->base.flags & VQA_FLAG_SHARED_LN) != 0;
     VQA_REQUIRE(P->v_adapt.w && P->v_adapt.b && P->v_adapt.gamma[0] && P->v_adapt.beta[0] &&
                 (ln_shared || (P->v_adapt.gamma[1] && P->v_adapt.beta[1])), VQA_ERR_ARG);
     const Layout L = make_layout_ext(*dims, false, true);
     VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
     VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    return ext_forward_impl(L, dims, &P->ext, bx, workspace, want_dz, stream, &P->v_adapt);
+    return ext_forward_impl(L, dims, &P->ext, bx, workspace, want_dz, stream, &P->v_adapt, keep);
 }
 
 extern "C" int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
                                                   const vqa_pretrain_adapt_params_t* G, const vqa_pretrain_ext_batch_t* bx,
                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                                   void* stream) {
+    return vqa_pretrain_adapt_backward_phases_ex(dims, P, G, bx, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
+}
+
+extern "C" int vqa_pretrain_adapt_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                                     const vqa_pretrain_adapt_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                     void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                     void* stream, const vqa_pretrain_keep_t* keep) {
     VQA_REQUIRE(adapt_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, *bx, nullptr));
     VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
     const bool ln_shared = (dims->base.flags & VQA_FLAG_SHARED_LN) != 0;
     VQA_REQUIRE(G->v_adapt.w && G->v_adapt.b && G->v_adapt.gamma[0] && G->v_adapt.beta[0] &&
                 (ln_shared || (G->v_adapt.gamma[1] && G->v_adapt.beta[1])), VQA_ERR_ARG);
     const Layout L = make_layout_ext(*dims, false, true);
     VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    return ext_backward_impl(L, dims, &P->ext, &G->ext, bx, workspace, slice_sq, phases, stream, &P->v_adapt, &G->v_adapt);
+    return ext_backward_impl(L, dims, &P->ext, &G->ext, bx, workspace, slice_sq, phases, stream, &P->v_adapt, &G->v_adapt,
+                             keep);
 }
 
 extern "C" int vqa_pretrain_adapt_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,

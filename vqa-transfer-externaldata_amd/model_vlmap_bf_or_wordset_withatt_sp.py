@@ -173,12 +173,19 @@ class Model(object):
         if tables is not None and getattr(eng, "_tables", None) is None:
             eng.bind_tables(*tables)           # (image_features, spatial_features, num_boxes): gathered on the device
         dpi = db.get("_dp") or {}
-        masks = None if getattr(self.config, "dropout_off", False) else eng.make_keep_masks(
-            B, int(getattr(self.config, "seed", 123)), self._step, row_offset=dpi.get("row_offset", 0),
-            global_rows=dpi.get("global_rows"))
+        # dropout: off, or the (seed, step, global row) stream -- as explicit keep-mask tensors (the default), or under
+        # config.inline_dropout computed inside the consuming kernels (the same bits, no mask tensor)
+        seed, masks, dropout = int(getattr(self.config, "seed", 123)), None, None
+        if getattr(self.config, "dropout_off", False):
+            pass
+        elif getattr(self.config, "inline_dropout", False):
+            dropout = (seed, self._step, dpi.get("row_offset", 0), dpi.get("global_rows"))
+        else:
+            masks = eng.make_keep_masks(B, seed, self._step, row_offset=dpi.get("row_offset", 0),
+                                        global_rows=dpi.get("global_rows"))
         self._step += 1
         self._reduce_report = bool(dpi)
-        eng.forward(db, masks, global_valid=dpi.get("global_valid"))
+        eng.forward(db, masks, global_valid=dpi.get("global_valid"), dropout=dropout)
         for k in PT.KINDS:
             kt = eng._tape["kinds"][k]
             name = "object" if k == "obj" else "attribute"

@@ -142,7 +142,10 @@ def _attn_fwd(entry, v, qv, V, nb, w, bias, rep, keepmask, keep_prob, keep_seed=
     n = B * (rep or 1)
     att, pooled = _f32(n, R, like=v), _f32(n, D, like=v)
     sd = _seeded(keepmask, keep_seed)
-    if sd:
+    if sd and rep is not None:       # several queries per memory (f32)
+        _call("vqa_attn_pool_fwd_rep_seeded", _p(v), _p(qv), _p(V), _p(nb), _p(w), _p(bias), *sd, keep_prob, _p(att), _p(pooled), B,
+              rep, R, H, D, _st(v))
+    elif sd:
         _call("vqa_attn_pool_fwd_seeded", _p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(nb), _p(w), _p(bias), *sd,
               keep_prob, _p(att), _p(pooled), B, 1, R, H, D, _st(v))
     else:
@@ -151,19 +154,24 @@ def _attn_fwd(entry, v, qv, V, nb, w, bias, rep, keepmask, keep_prob, keep_seed=
     return att, pooled
 
 
-def _attn_bwd(entry, dpooled, v, qv, V, att, w, rep, keepmask, keep_prob, keep_seed=None):
+def _attn_bwd(entry, dpooled, v, qv, V, att, w, rep, keepmask, keep_prob, keep_seed=None, parts=False):
     B, R, H = v.shape
     D = V.shape[2]
     n = B * (rep or 1)
     dv, dqv = torch.empty_like(v), torch.empty_like(qv)
     pdw, pdb = _f32(n, H, like=v), _f32(n, 1, like=v)
     sd = _seeded(keepmask, keep_seed)
-    if sd:
+    if sd and rep is not None:
+        _call("vqa_attn_pool_bwd_rep_seeded", _p(dpooled), _p(v), _p(qv), _p(V), _p(att), _p(w), *sd, keep_prob, _p(dv), _p(dqv),
+              _p(pdw), _p(pdb), B, rep, R, H, D, _st(v))
+    elif sd:
         _call("vqa_attn_pool_bwd_seeded", _p(dpooled), _p(v), _p(qv), _p(V), int(V.dtype == torch.bfloat16), _p(att), _p(w), *sd,
               keep_prob, _p(dv), _p(dqv), _p(pdw), _p(pdb), B, 1, R, H, D, _st(v))
     else:
         _call(entry, _p(dpooled), _p(v), _p(qv), _p(V), _p(att), _p(w), _p(keepmask), keep_prob, _p(dv), _p(dqv), _p(pdw),
               _p(pdb), B, *_opt(rep), R, H, D, _st(v))
+    if parts:       # the per-query partials of d w [n,H] and d bias [n,1] as the kernel wrote them
+        return dv, dqv, pdw, pdb
     return dv, dqv, colsum(pdw), colsum(pdb)
 
 
@@ -388,13 +396,15 @@ def ln_act_bwd(dy, pre, mean, rstd, gamma, beta, rows=1, act="relu", keepmask=No
                    keep_seed)
 
 
-def attn_pool_fwd_rep(v, qv, V, nb, w, bias, rep, keepmask=None, keep_prob=1.0):
-    """`rep` queries per memory: v [B,R,H], V [B,R,D], nb [B]; qv [B*rep,H] -> att [B*rep,R], pooled [B*rep,D]."""
-    return _attn_fwd("vqa_attn_pool_fwd_rep", v, qv, V, nb, w, bias, rep, keepmask, keep_prob)
+def attn_pool_fwd_rep(v, qv, V, nb, w, bias, rep, keepmask=None, keep_prob=1.0, keep_seed=None):
+    """`rep` queries per memory: v [B,R,H], V [B,R,D], nb [B]; qv [B*rep,H] -> att [B*rep,R], pooled [B*rep,D].
+    keepmask [B*rep,R,H], or keep_seed=(seed, offset): that mask's stream (vqa_attn_pool_fwd_rep_seeded)."""
+    return _attn_fwd("vqa_attn_pool_fwd_rep", v, qv, V, nb, w, bias, rep, keepmask, keep_prob, keep_seed)
 
 
-def attn_pool_bwd_rep(dpooled, v, qv, V, att, w, rep, keepmask=None, keep_prob=1.0):
-    return _attn_bwd("vqa_attn_pool_bwd_rep", dpooled, v, qv, V, att, w, rep, keepmask, keep_prob)
+def attn_pool_bwd_rep(dpooled, v, qv, V, att, w, rep, keepmask=None, keep_prob=1.0, keep_seed=None, parts=False):
+    """parts: return the per-query partials part_dw [B*rep,H], part_db [B*rep,1] instead of their column sums"""
+    return _attn_bwd("vqa_attn_pool_bwd_rep", dpooled, v, qv, V, att, w, rep, keepmask, keep_prob, keep_seed, parts)
 
 
 def tanh_fwd(x):

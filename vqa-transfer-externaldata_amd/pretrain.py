@@ -33,6 +33,10 @@ with `adapt=True`: v_adapt = fc_layer(V_ft, 1024, LayerNorm over the [36, 1024] 
 the attention pools (:365-367, :461-463), so pooled_linear_l is [H, H] -- the only pre-training checkpoint
 vlmap_answer_adapt can transfer its heads from.  It runs on vqa_pretrain_adapt_forward / _backward_phases; the FC is
 computed once per image and once for both categories, and its gradients complete in backward phase 8.
+
+Dropout: explicit uint8 keep-masks from make_keep_masks(B, seed, step) (the default), or `dropout=(seed, step)`: the same
+bits computed inside the attention and LayerNorm kernels that consume them (vqa_pretrain_*_ex with a vqa_pretrain_keep_t;
+DESIGN.md section 7), no mask tensor, bit for bit the same step.  keep_offsets() is the one copy of the stream layout.
 """
 from __future__ import annotations
 
@@ -297,36 +301,59 @@ class PretrainEngine:
             (_lib.FLAG_BF16_GEMM if self.precision == "bf16" else 0)
 
     # ------------------------------------------------------------------ C-ABI plumbing
-    def make_keep_masks(self, B, seed, step, row_offset=0, global_rows=None):
-        """reproducible dropout keep-masks for (seed, step): {kind/att, kind/bf_joint, kind/ws_joint}.  The stream is
-        indexed by the GLOBAL image row: a data-parallel shard of B images passes its first global row (row_offset) and
-        the global batch size and draws exactly the bits one process on the whole batch would draw for its rows."""
+    def keep_offsets(self, B, step, row_offset=0, global_rows=None):
+        """The layout of the dropout stream at `step`, the ONE copy of its arithmetic: {site: (offset, elements per image,
+        keep_prob)} for the sites {kind/att, kind/bf_joint, kind/ws_joint} (the cfg-5 region), {kind}/ew_joint (with the
+        enwiki head: their own counter range from EW_MASK_COUNTER) and {kind}/{head}_joint_l (noc: the l branch, a third
+        range from NOC_L_MASK_COUNTER; the v branch uses the joint sites).  `offset` is the stream position of the site's
+        element 0 for THESE B images.  The stream is indexed by the GLOBAL image row: a data-parallel shard of B images
+        passes its first global row (row_offset) and the global batch size, and its sites then start at the bits one
+        process on the whole batch draws for those rows.  make_keep_masks writes these streams into tensors; with
+        dropout=(seed, step) the kernels compute them in place."""
         n, R, H = self.n, self.R, self.H
         Bg = int(global_rows) if global_rows is not None else B
         out, off = {}, step * (2 * (Bg * n * R * H + 2 * Bg * n * 2 * H))
         for k in KINDS:
             for name, per_image, keep in ((k + "/att", n * R * H, KEEP_ATT), (k + "/bf_joint", n * 2 * H, KEEP_JOINT),
                                           (k + "/ws_joint", n * 2 * H, KEEP_JOINT)):
-                out[name] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image, keep, self.device)
+                out[name] = (off + row_offset * per_image, per_image, keep)
                 off += Bg * per_image
+        per_image = n * 2 * H
         if "ew" in self.heads:
-            # {kind}/ew_joint from their own counter range: the cfg-5 masks above keep their bits for (seed, step, row)
-            per_image = n * 2 * H
+            # their own counter range: the cfg-5 sites above keep their bits for (seed, step, row)
             off = EW_MASK_COUNTER + step * (2 * Bg * per_image)
             for k in KINDS:
-                out[k + "/ew_joint"] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image, KEEP_JOINT,
-                                                        self.device)
+                out[k + "/ew_joint"] = (off + row_offset * per_image, per_image, KEEP_JOINT)
                 off += Bg * per_image
         if self.noc:
-            # the l branch of every noc head ({kind}/{head}_joint_l) from a third range; the v branch uses the masks above
-            per_image = n * 2 * H
             off = NOC_L_MASK_COUNTER + step * (2 * len(self.heads) * Bg * per_image)
             for h in self.heads:
                 for k in KINDS:
-                    out["%s/%s_joint_l" % (k, h)] = ops.dropout_mask(B * per_image, seed, off + row_offset * per_image,
-                                                                     KEEP_JOINT, self.device)
+                    out["%s/%s_joint_l" % (k, h)] = (off + row_offset * per_image, per_image, KEEP_JOINT)
                     off += Bg * per_image
         return out
+
+    def make_keep_masks(self, B, seed, step, row_offset=0, global_rows=None):
+        """reproducible dropout keep-masks for (seed, step): uint8 tensors of the sites of keep_offsets, by site name"""
+        return {name: ops.dropout_mask(B * per_image, seed, off, keep, self.device)
+                for name, (off, per_image, keep) in self.keep_offsets(B, step, row_offset, global_rows).items()}
+
+    def _keep_struct(self, B, dropout):
+        """vqa_pretrain_keep_t of dropout = (seed, step[, row_offset, global_rows]): every site the model has is seeded"""
+        seed, step = int(dropout[0]), int(dropout[1])
+        row_offset, global_rows = (dropout[2], dropout[3]) if len(dropout) == 4 else (0, None)
+        offs = self.keep_offsets(B, step, int(row_offset or 0), global_rows)
+        ks = _lib.PtKeep(keep_seed=seed)
+        for ki, k in enumerate(KINDS):
+            for site in ("att", "bf_joint", "ws_joint", "ew_joint"):
+                if k + "/" + site in offs:
+                    getattr(ks, site + "_off")[ki] = offs[k + "/" + site][0]
+                    ks.seeded |= _lib.PT_KEEP_SITE[site]
+            for ti, h in enumerate(("bf", "ws", "ew")):
+                if "%s/%s_joint_l" % (k, h) in offs:
+                    ks.l_joint_off[ki][ti] = offs["%s/%s_joint_l" % (k, h)][0]
+                    ks.seeded |= _lib.PT_KEEP_SITE["l_joint"]
+        return ks
 
     def _param_struct(self, table):
         if self.noc:
@@ -522,11 +549,23 @@ class PretrainEngine:
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=group)
         return tuple(float(v) for v in cnt.cpu())
 
-    def forward(self, batch, masks, want_dz=True, global_valid=None):
+    def forward(self, batch, masks, want_dz=True, global_valid=None, dropout=None, row_offset=0, global_rows=None):
         """batch: dict of arrays / tensors (keys of dataset_vlmap's batches; optional 'blank_fill/sort' from
         add_length_sort); masks: uint8 keep-masks keyed '<kind>/att|bf_joint|ws_joint' or None (no dropout);
-        global_valid: data parallel only -- (object, attribute) valid-entry counts of the global batch."""
+        global_valid: data parallel only -- (object, attribute) valid-entry counts of the global batch.
+        dropout=(seed, step) or (seed, step, row_offset, global_rows): seeded dropout -- the bits of
+        make_keep_masks(B, seed, step, row_offset, global_rows), computed inside the attention and LayerNorm kernels that
+        consume them (vqa_pretrain_*_ex); no mask tensor exists, and the step is bit for bit the step on those masks.
+        Exclusive with masks.  row_offset / global_rows may also be given by keyword."""
+        if dropout is not None:
+            if masks is not None:
+                raise ValueError("masks and dropout=(seed, step) are mutually exclusive")
+            if len(dropout) == 2:
+                dropout = (dropout[0], dropout[1], row_offset, global_rows)
+            elif len(dropout) != 4:
+                raise ValueError("dropout is (seed, step) or (seed, step, row_offset, global_rows)")
         bs, B, L, keep = self._batch_struct(batch, masks)
+        self._ks = self._keep_struct(B, dropout) if dropout is not None else None
         d = _lib.PtDims(B=B, n=self.n, R=self.R, D=self.D, H=self.H, W=self.W, A=self.A, Vq=self.Vq, n_ws=self.n_ws, L=L,
                         flags=self._flags(), keep_att=KEEP_ATT,
                         keep_joint=KEEP_JOINT)
@@ -540,9 +579,10 @@ class PretrainEngine:
         if self.workspace is None or need > self.workspace.numel():
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self.dims, self._bs, self._keepalive = d, bs, keep
-        fwd = getattr(self.lib, self._abi + "forward")
+        fwd = getattr(self.lib, self._abi + "forward_ex")
         _lib.check(fwd(C.byref(d), C.byref(self._p_struct), C.byref(bs), C.c_void_p(self.workspace.data_ptr()),
-                       self.workspace.numel(), 1 if want_dz else 0, self._stream()), "vqa_pretrain_forward")
+                       self.workspace.numel(), 1 if want_dz else 0, self._stream(),
+                       C.byref(self._ks) if self._ks is not None else None), "vqa_pretrain_forward")
         Bn = B * self.n
         zs = ("zv", "zl") if self.noc else ("z",)       # noc: the two branches' logits of every head
         self._tape = {"B": B, "kinds": {
@@ -578,11 +618,11 @@ class PretrainEngine:
 
     def _backward_phases(self, phases):
         tail = self.grad_flat[self.n_train:]
-        fn = getattr(self.lib, self._abi + "backward_phases")
+        fn = getattr(self.lib, self._abi + "backward_phases_ex")      # the forward's keep struct: the bits are regenerated
         _lib.check(fn(
             C.byref(self.dims), C.byref(self._p_struct), C.byref(self._g_struct), C.byref(self._bs),
             C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), C.c_void_p(tail.data_ptr()), phases,
-            self._stream()), "vqa_pretrain_backward_phases")
+            self._stream(), C.byref(self._ks) if self._ks is not None else None), "vqa_pretrain_backward_phases")
 
     def backward(self, reducer=None):
         """All gradients into grad_flat (vlmap_memft/trainer.py:129-137: optimize_loss over every variable).  With a
@@ -622,12 +662,12 @@ class PretrainEngine:
                                           self.n_train, P(self.norm_sq), CLIP_NORM, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS,
                                           st), "vqa_clip_adam")
 
-    def train_step(self, batch, masks, lr, allreduce=None, global_valid=None):
+    def train_step(self, batch, masks, lr, allreduce=None, global_valid=None, dropout=None, row_offset=0, global_rows=None):
         """forward -> backward -> (gradient all-reduce) -> clip + Adam.  Data parallel: `allreduce` is a
         dp.BucketedAllReduce (overlapped with the backward phases) or any callable on grad_flat; pass the global
         valid counts so that every shard divides by the global denominators and a SUM reduce gives the gradient of
-        the global-batch losses; all ranks then apply the identical update."""
-        self.forward(batch, masks, global_valid=global_valid)
+        the global-batch losses; all ranks then apply the identical update.  dropout: as for forward."""
+        self.forward(batch, masks, global_valid=global_valid, dropout=dropout, row_offset=row_offset, global_rows=global_rows)
         if allreduce is not None and hasattr(allreduce, "start"):
             self.backward(reducer=allreduce)
         else:

@@ -253,6 +253,9 @@ def build_parser():
                         help="bf16: the shared head layers' products (pooled_linear_l, q_linear_l, joint, classifier, "
                              "v_adapt) with bf16 operands in the matrix unit, f32 master weights and accumulation; the "
                              "encoders stay f32 (not in the reference; checkpoints are those of f32)")
+    parser.add_argument("--inline_dropout", action="store_true", default=False,
+                        help="draw the dropout keep bits inside the kernels that consume them instead of writing mask "
+                             "buffers first: the same bits, so the same results (not in the reference)")
     parser.add_argument("--input_workers", type=int, default=4, help="forked batch producers (0: in-process)")
     parser.add_argument("--input_prefetch", type=int, default=2, help="batches assembled ahead of the step")
     return parser

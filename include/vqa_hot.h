@@ -723,8 +723,9 @@ int vqa_fusion_backward(const vqa_dims_t* dims, const vqa_params_t* params, cons
 /* ------------------------------------------------------------------------
  * Whole cfg-5 pre-training model (vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py:54-94,
  * 323-609, 675-706) and its backward, one host call each -- the same shape as vqa_fusion_forward / _backward.
- * These entry points are the VQA_PT_HEAD_BF | VQA_PT_HEAD_WS case of the variable-head-set path below (vqa_pretrain_ext_*):
- * they widen their arguments to its structs and run it, so layout, kernels and results are those of that head set.
+ * These entry points are the VQA_PT_HEAD_BF | VQA_PT_HEAD_WS case of the variable-head-set model below (vqa_pretrain_ext_*):
+ * both families adapt their arguments to one internal model description and run the same forward and backward, so layout,
+ * kernels and results are those of that head set.
  * ------------------------------------------------------------------------ */
 typedef struct {
     int32_t B, n, R, D, H, W, A, Vq, n_ws;  /* images, entries per category (5), regions, feature / hidden / word dims,

@@ -346,3 +346,78 @@ def test_two_prepared_batches_in_flight_without_a_device_sync():
     del p1, p2
     torch.cuda.synchronize()
     assert got == want
+
+
+def _ext_params(PT, L, table, ln_shared):
+    """vqa_pretrain_ext_params_t over the tensors of a cfg-5 engine (heads bf | ws: four LayerNorm slots, no enwiki
+    members), built here from the variable names so that it does not depend on the engine's own struct builder"""
+    def fc(scope, n_ln):
+        f = L.PtFc6(w=table[scope + "/fc/weights"].data_ptr(), b=table[scope + "/fc/biases"].data_ptr())
+        for i in range(min(n_ln, 1) if ln_shared else n_ln):
+            f.beta[i] = table[PT.ln_name(scope, i) + "/beta"].data_ptr()
+            f.gamma[i] = table[PT.ln_name(scope, i) + "/gamma"].data_ptr()
+        return f
+    g = "encode_L_blank/rnn/gru_cell/"
+    return L.PtExtParams(
+        wordset_map=table["wordset_map/learn"].data_ptr(), l_glove=table["L_GloVe/embed_map"].data_ptr(),
+        spat_v_linear_v=fc("spat_v_linear_v", 2), spat_q_linear_v=fc("spat_q_linear_v", 2),
+        spat_att_score=fc("spat_att/compute/score", 0), gru_wg=table[g + "gates/kernel"].data_ptr(),
+        gru_bg=table[g + "gates/bias"].data_ptr(), gru_wc=table[g + "candidate/kernel"].data_ptr(),
+        gru_bc=table[g + "candidate/bias"].data_ptr(), pooled_linear_l=fc("pooled_linear_l", 4),
+        q_linear_l=fc("q_linear_l", 4), joint_fc=fc("joint_fc", 4), wordset_ft=fc("wordset_ft", 2),
+        classifier=fc("classifier", 0))
+
+
+@pytest.mark.parametrize("seeded", [False, True], ids=["masks", "seeded"])
+@pytest.mark.parametrize("cfg", [dict(B=3, n=5, R=6, D=16, H=8, L=4, W=12, Vq=20, n_ws=7, A=12),
+                                 dict(B=2, n=5, R=36, D=2048, H=1024, L=4, W=300, Vq=60, n_ws=15, A=40)],
+                         ids=["generic", "h1024"])
+def test_cfg5_entry_points_are_the_bf_ws_case_of_the_ext_entry_points(cfg, seeded):
+    """include/vqa_hot.h: vqa_pretrain_* is "the VQA_PT_HEAD_BF | VQA_PT_HEAD_WS case" of vqa_pretrain_ext_*.  Forward and
+    backward (phases 15) of a deterministic cfg-5 engine through vqa_pretrain_*_ex, then the same tensors, batch, keep
+    struct and workspace through vqa_pretrain_ext_*_ex with heads 3: the same workspace size and offsets, and report,
+    S/z, S/dz and grad_flat (tail slot included) bit for bit."""
+    import ctypes as C
+    from vqa_transfer_externaldata_amd import _lib as L, pretrain as PT
+    rng = np.random.default_rng(21)
+    p = PO.init_params(rng, cfg["Vq"], cfg["n_ws"], cfg["A"], W=cfg["W"], D=cfg["D"], H=cfg["H"])
+    batch = PO.make_batch(rng, *(cfg[k] for k in ("B", "n", "R", "D", "L", "Vq", "n_ws", "A")))
+    eng = PT.PretrainEngine(n=cfg["n"], R=cfg["R"], D=cfg["D"], H=cfg["H"], W=cfg["W"], A=cfg["A"], Vq=cfg["Vq"],
+                            n_ws=cfg["n_ws"], params=p, deterministic=True)
+    assert eng._abi == "vqa_pretrain_"
+    db = {k: dev(v) for k, v in batch.items()}
+    if seeded:
+        eng.forward(db, None, dropout=(77, 2))
+    else:
+        eng.forward(db, eng.make_keep_masks(cfg["B"], 77, 2))
+    eng.backward()
+    torch.cuda.synchronize()
+    names = ("report", "S/z", "S/dz")
+    want = {k: eng.tensor(k).clone() for k in names}
+    want_grad = eng.grad_flat.clone()
+    assert all(torch.isfinite(v).all() for v in want.values()) and torch.isfinite(want_grad).all()
+    assert float(want["S/dz"].abs().max()) > 0 and float(want_grad[:eng.n_train].abs().max()) > 0
+
+    lib = eng.lib
+    xd = L.PtExtDims(base=eng.dims, heads=L.PT_HEAD_BF | L.PT_HEAD_WS, Lc=0, n_ctx=0)
+    assert int(lib.vqa_pretrain_ext_workspace_bytes(C.byref(xd))) == int(lib.vqa_pretrain_workspace_bytes(C.byref(eng.dims)))
+    xp, xg = _ext_params(PT, L, eng.params, eng.ln_shared), _ext_params(PT, L, eng.grads, eng.ln_shared)
+    xb = L.PtExtBatch(base=eng._bs)
+    ks = C.byref(eng._ks) if seeded else None
+    assert (eng._ks is not None) == seeded
+    ws, st = C.c_void_p(eng.workspace.data_ptr()), eng._stream()
+    eng.workspace.zero_()
+    eng.grad_flat.zero_()
+    L.check(lib.vqa_pretrain_ext_forward_ex(C.byref(xd), C.byref(xp), C.byref(xb), ws, eng.workspace.numel(), 1, st, ks),
+            "vqa_pretrain_ext_forward_ex")
+    L.check(lib.vqa_pretrain_ext_backward_phases_ex(C.byref(xd), C.byref(xp), C.byref(xg), C.byref(xb), ws,
+                                                    eng.workspace.numel(), C.c_void_p(eng.grad_flat[eng.n_train:].data_ptr()),
+                                                    15, st, ks), "vqa_pretrain_ext_backward_phases_ex")
+    torch.cuda.synchronize()
+    for k in names:
+        off, cnt = C.c_int64(), C.c_int64()
+        L.check(lib.vqa_pretrain_ext_tensor(C.byref(xd), k.encode(), C.byref(off), C.byref(cnt)), "vqa_pretrain_ext_tensor")
+        got = eng.workspace[off.value:off.value + 4 * cnt.value].view(torch.float32)
+        assert got.numel() == want[k].numel() and got.data_ptr() == eng.tensor(k).data_ptr(), k      # the same layout
+        assert torch.equal(got, want[k]), k
+    assert torch.equal(eng.grad_flat, want_grad)

@@ -1,11 +1,13 @@
 // Host-side composition of the pre-training models: one call enqueues the whole forward (or backward)
 // pass on the caller's stream -- the counterpart of vqa_fusion_forward / vqa_fusion_backward for the fusion model.
-// ONE code path serves every model; a model is a head set plus, for two of them, another head block or pooled memory:
-//   vqa_pretrain_*        cfg 5, vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py: heads bf | ws.  Thin adapters onto
+// ONE model description, ONE prologue, ONE forward and ONE backward serve every model: a model is a head set on one of
+// three architectures (Model), and each public family only adapts its structs to the internal views (Params, Batch):
+//   vqa_pretrain_*        cfg 5, vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py: heads bf | ws, standard
 //   vqa_pretrain_ext_*    model_vlmap_bf_or_wordset_enwiki_withatt_sp.py (bf | ws | ew), model_vlmap_bf_enwiki_withatt_sp.py
-//                         (bf | ew)
-//   vqa_pretrain_noc_*    the "no composition" heads on the same trunk (see that section)
-//   vqa_pretrain_adapt_*  the v_adapt layer between the features and the attention pooling (see that section)
+//                         (bf | ew), and bf | ws = cfg 5 bit for bit; standard
+//   vqa_pretrain_noc_*    the "no composition" heads on the same trunk (noc_heads_fwd / noc_heads_bwd)
+//   vqa_pretrain_adapt_*  the v_adapt layer between the features and the attention pooling (v_adapt_fwd / v_adapt_bwd)
+// No family calls another family's entry points.
 //
 // Per category k in {object, attribute} (reference lines relative to the cfg-5 file):
 //   build_*_V_ft      :323-364, :414-455   6-d box -> FC 1024 + LN + ReLU for the 36 regions (once per image) and the
@@ -261,11 +263,19 @@ struct HeadSet {
     std::string name(int h) const { return std::string(KIND[h & 1]) + "/" + HEAD[type[h >> 1]] + "/"; }
 };
 
-bool ext_dims_ok(const vqa_pretrain_ext_dims_t* d) {
-    if (d == nullptr || !dims_ok(&d->base)) return false;
-    if (!(d->heads & VQA_PT_HEAD_BF) || (d->heads & ~(VQA_PT_HEAD_BF | VQA_PT_HEAD_WS | VQA_PT_HEAD_EW))) return false;
-    return !(d->heads & VQA_PT_HEAD_EW) || (d->Lc > 0 && d->n_ctx > 0);
+// The architecture of a model: what sits between the features and the attention pooling, and which head block follows
+// the shared head inputs.  noc: the "no composition" heads (two joint branches and two logit blocks per head instead of
+// jin / joint_fc / classifier); adapt: the attention pools the adapted memory v_adapt [B,R,H], so the pooled width is H
+enum Arch { ARCH_STANDARD, ARCH_NOC, ARCH_ADAPT };
+
+// the head sets an architecture has a model for
+bool heads_ok(Arch arch, int heads) {
+    if (!(heads & VQA_PT_HEAD_BF) || (heads & ~(VQA_PT_HEAD_BF | VQA_PT_HEAD_WS | VQA_PT_HEAD_EW))) return false;
+    if (arch == ARCH_NOC) return heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS) || heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_EW);
+    return arch == ARCH_STANDARD || heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS);
 }
+
+bool noc_split(int type) { return type != 0; }      // noc: blank fill SUM, word set / enwiki SPLIT
 
 // report[3 i + j] (i = k * nt + r: the key order of vqa_pretrain_ext_report_key), report[3 nh] = sum of the losses
 struct ReportExtArgs { const float* stats[6]; const float* inv[6]; int rows, nh; };
@@ -292,10 +302,7 @@ __global__ __launch_bounds__(256) void pretrain_ext_report_kernel(ReportExtArgs 
     }
 }
 
-// noc: the "no composition" heads (vqa_pretrain_noc_*): two joint branches and two logit blocks per head instead of
-// jin / joint_fc / classifier
-// adapt: the attention pools the adapted memory v_adapt [B,R,H] (vqa_pretrain_adapt_*), so the pooled width is H, not D
-Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool adapt = false) {
+Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc, bool adapt) {
     const vqa_pretrain_dims_t& d = dx.base;
     const HeadSet hs(dx.heads);
     Layout L;
@@ -437,8 +444,72 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc = false, bool
     return L;
 }
 
-// vqa_pretrain_*_tensor of every model: a name of the layout -> byte offset and element count
-int layout_tensor(const Layout& L, const char* name, int64_t* offset_bytes, int64_t* n_elems) {
+// ---------------------------------------------------------------- the normalised view of a call
+// Every public family (vqa_pretrain_*, _ext_*, _noc_*, _adapt_*) hands its structs to an adapter (Model::cfg5 / Model::of,
+// view()) and runs the ONE prologue, forward and backward below on the result.  The views hold pointers only.
+
+// report keys of a head set in report order: per category, per enabled type <kind>_<task>_{loss,acc,top_5_acc} (a SPLIT
+// head of a noc model: <kind>_<task>_v_{...} then <kind>_<task>_l_{...}); then total_loss
+std::vector<std::string> report_keys(Arch arch, int heads) {
+    const HeadSet hs(heads);
+    std::vector<std::string> keys;
+    for (int k = 0; k < 2; ++k)
+        for (int r = 0; r < hs.nt; ++r) {
+            const std::string base = std::string(KIND[k]) + "_" + TASK[hs.type[r]];
+            const bool split = arch == ARCH_NOC && noc_split(hs.type[r]);
+            for (const char* br : split ? std::vector<const char*>{"_v", "_l"} : std::vector<const char*>{""})
+                for (const char* suf : {"_loss", "_acc", "_top_5_acc"}) keys.push_back(base + br + suf);
+        }
+    keys.push_back("total_loss");
+    return keys;
+}
+
+// vqa_pretrain_*_report_key of every family; NULL past the last key or for a head set the architecture has no model for
+const char* report_key(Arch arch, int heads, int i) {
+    static std::vector<std::string> keys[3][8];        // built once; the pointers stay valid
+    static const int init = [] {
+        for (const Arch a : {ARCH_STANDARD, ARCH_NOC, ARCH_ADAPT})
+            for (int m = 0; m < 8; ++m)
+                if (heads_ok(a, m)) keys[a][m] = report_keys(a, m);
+        return 0;
+    }();
+    (void)init;
+    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[arch][heads].size()) return nullptr;
+    return keys[arch][heads][i].c_str();
+}
+
+// The model of a call: the dims of the variable head set plus the architecture.  The one place that maps a family to its
+// dims check, its layout and its probe labels.
+struct Model {
+    vqa_pretrain_ext_dims_t dims{};
+    Arch arch = ARCH_STANDARD;
+    bool ok = false;      // the family's dims check
+    // vqa_pretrain_*: heads bf | ws, no context batch
+    static Model cfg5(const vqa_pretrain_dims_t* d) {
+        Model m;
+        if ((m.ok = dims_ok(d))) m.dims = vqa_pretrain_ext_dims_t{*d, VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, 0, 0};
+        return m;
+    }
+    static Model of(const vqa_pretrain_ext_dims_t* d, Arch arch) {
+        Model m;
+        m.arch = arch;
+        m.ok = d != nullptr && dims_ok(&d->base) && heads_ok(arch, d->heads) &&
+               (!(d->heads & VQA_PT_HEAD_EW) || (d->Lc > 0 && d->n_ctx > 0));
+        if (m.ok) m.dims = *d;
+        return m;
+    }
+    Layout layout() const { return make_layout_ext(dims, arch == ARCH_NOC, arch == ARCH_ADAPT); }
+    bool ln_shared() const { return (dims.base.flags & VQA_FLAG_SHARED_LN) != 0; }
+    const char* fwd_label() const { return arch == ARCH_NOC ? "pretrain_noc.forward" : "pretrain_ext.forward"; }
+    const char* bwd_label() const { return arch == ARCH_NOC ? "pretrain_noc.backward" : "pretrain_ext.backward"; }
+};
+
+int64_t layout_bytes(const Model& m) { return m.ok ? m.layout().total : VQA_ERR_ARG; }
+
+// vqa_pretrain_*_tensor of every family: a name of the layout -> byte offset and element count
+int layout_tensor(const Model& m, const char* name, int64_t* offset_bytes, int64_t* n_elems) {
+    if (!m.ok || name == nullptr) return VQA_ERR_ARG;
+    const Layout L = m.layout();
     const Entry* e = L.find(name);
     if (e == nullptr) return VQA_ERR_ARG;
     if (offset_bytes) *offset_bytes = e->off;
@@ -446,16 +517,94 @@ int layout_tensor(const Layout& L, const char* name, int64_t* offset_bytes, int6
     return VQA_OK;
 }
 
-std::string ext_report_key(int heads, int i) {
-    const HeadSet hs(heads);
-    if (i == 3 * hs.nh()) return "total_loss";
-    if (i < 0 || i > 3 * hs.nh()) return "";
-    const int h = i / 3, j = i % 3, k = h / hs.nt, r = h % hs.nt;
-    static const char* const SUFFIX[3] = {"_loss", "_acc", "_top_5_acc"};
-    return std::string(KIND[k]) + "_" + TASK[hs.type[r]] + SUFFIX[j];
+struct GruVars { float *wg, *bg, *wc, *bc; };      // gates / candidate kernel [W + H, 2H] / [W + H, H] and bias
+
+// The variables (or their gradients) of a call, whichever public struct they came in: the trunk, up to two joint /
+// classifier blocks (standard, adapt: [0] = joint_fc / classifier; noc: [0] = joint_v / classifier_v, [1] = joint_l /
+// classifier_l) and v_adapt.  Members the model does not have stay NULL.
+struct Params {
+    bool present;      // the caller's pointer was non-NULL
+    float *wordset_map, *l_glove, *enwiki_map;
+    vqa_pt_fc6_t spat_v_linear_v, spat_q_linear_v, spat_att_score;
+    GruVars gru, egru;
+    vqa_pt_fc6_t pooled_linear_l, q_linear_l, wordset_ft, joint[2], classifier[2], v_adapt;
+};
+
+// the widening of a cfg-5 fc_layer scope from 4 to 6 LayerNorm slots (4 and 5 NULL: four heads never index them)
+vqa_pt_fc6_t fc6(const vqa_pt_fc_t& f) {
+    vqa_pt_fc6_t o{};
+    o.w = f.w; o.b = f.b;
+    for (int i = 0; i < 4; ++i) { o.beta[i] = f.beta[i]; o.gamma[i] = f.gamma[i]; }
+    return o;
+}
+const vqa_pt_fc6_t& fc6(const vqa_pt_fc6_t& f) { return f; }
+
+// the members every public params struct has under the same names
+template <class T>
+void view_trunk(const T& p, Params* v) {
+    v->present = true;
+    v->wordset_map = p.wordset_map; v->l_glove = p.l_glove;
+    v->spat_v_linear_v = fc6(p.spat_v_linear_v); v->spat_q_linear_v = fc6(p.spat_q_linear_v);
+    v->spat_att_score = fc6(p.spat_att_score);
+    v->gru = {p.gru_wg, p.gru_bg, p.gru_wc, p.gru_bc};
+    v->pooled_linear_l = fc6(p.pooled_linear_l); v->q_linear_l = fc6(p.q_linear_l); v->wordset_ft = fc6(p.wordset_ft);
+}
+template <class T>
+void view_enwiki(const T& p, Params* v) {
+    v->enwiki_map = p.enwiki_map;
+    v->egru = {p.egru_wg, p.egru_bg, p.egru_wc, p.egru_bc};
 }
 
-// the memory the spatial attention pools when it is not the batch's image_ft [B,R,D]: one [B,R,width] block per category
+Params view(const vqa_pretrain_params_t* p) {
+    Params v{};
+    if (p == nullptr) return v;
+    view_trunk(*p, &v);
+    v.joint[0] = fc6(p->joint_fc); v.classifier[0] = fc6(p->classifier);
+    return v;
+}
+Params view(const vqa_pretrain_ext_params_t* p) {
+    Params v{};
+    if (p == nullptr) return v;
+    view_trunk(*p, &v); view_enwiki(*p, &v);
+    v.joint[0] = p->joint_fc; v.classifier[0] = p->classifier;
+    return v;
+}
+Params view(const vqa_pretrain_noc_params_t* p) {
+    Params v{};
+    if (p == nullptr) return v;
+    view_trunk(*p, &v); view_enwiki(*p, &v);
+    v.joint[0] = p->joint_v; v.joint[1] = p->joint_l; v.classifier[0] = p->classifier_v; v.classifier[1] = p->classifier_l;
+    return v;
+}
+Params view(const vqa_pretrain_adapt_params_t* p) {
+    Params v = view(p ? &p->ext : nullptr);
+    if (p != nullptr) v.v_adapt = p->v_adapt;
+    return v;
+}
+
+// The batch of a call: the ext batch (cfg-5: no contexts) plus the l branch's masks of a noc batch (else NULL)
+struct Batch {
+    bool present;
+    vqa_pretrain_ext_batch_t x;
+    const vqa_pretrain_noc_kind_t* l;
+};
+Batch view(const vqa_pretrain_ext_batch_t* b) {
+    Batch v{};
+    if ((v.present = b != nullptr)) v.x = *b;
+    return v;
+}
+Batch view(const vqa_pretrain_batch_t* b) {
+    Batch v{};
+    if ((v.present = b != nullptr)) v.x.base = *b;
+    return v;
+}
+Batch view(const vqa_pretrain_noc_batch_t* b) {
+    Batch v = view(b ? &b->base : nullptr);
+    if (b != nullptr) v.l = b->l;
+    return v;
+}
+
+// the memory the spatial attention pools: one [B,R,width] block per category
 struct PoolMem { const float* mem[2]; int64_t width; };
 
 // the keep struct's offsets, or zeros without one
@@ -463,52 +612,92 @@ const vqa_pretrain_keep_t NO_SEEDED_SITES = {};
 const vqa_pretrain_keep_t& keep_of(const Ctx& c) { return c.keep ? *c.keep : NO_SEEDED_SITES; }
 
 // dropout of the attention score, category k: [B*n, R, H]
-KeepSrc att_keep(const Ctx& c, const vqa_pretrain_ext_batch_t& x, int k) {
-    return c.site(VQA_PT_KEEP_SITE_ATT, x.base.kind[k].keep_att, keep_of(c).att_off[k], c.d.keep_att, c.d.H);
+KeepSrc att_keep(const Ctx& c, const Batch& b, int k) {
+    return c.site(VQA_PT_KEEP_SITE_ATT, b.x.base.kind[k].keep_att, keep_of(c).att_off[k], c.d.keep_att, c.d.H);
 }
 
-// joint_fc dropout of the head of type t, category k: [B*n, 2H]
-KeepSrc joint_keep(const Ctx& c, const vqa_pretrain_ext_batch_t& x, int k, int t) {
+// joint_fc dropout (noc: the v branch's) of the head of type t, category k: [B*n, 2H]
+KeepSrc joint_keep(const Ctx& c, const Batch& b, int k, int t) {
     const vqa_pretrain_keep_t& o = keep_of(c);
+    const vqa_pretrain_kind_t& kb = b.x.base.kind[k];
     const int64_t N = 2 * (int64_t)c.d.H;
-    if (t == 0) return c.site(VQA_PT_KEEP_SITE_BF_JOINT, x.base.kind[k].keep_bf_joint, o.bf_joint_off[k], c.d.keep_joint, N);
-    if (t == 1) return c.site(VQA_PT_KEEP_SITE_WS_JOINT, x.base.kind[k].keep_ws_joint, o.ws_joint_off[k], c.d.keep_joint, N);
-    return c.site(VQA_PT_KEEP_SITE_EW_JOINT, x.ctx[k].keep_ew_joint, o.ew_joint_off[k], c.d.keep_joint, N);
+    if (t == 0) return c.site(VQA_PT_KEEP_SITE_BF_JOINT, kb.keep_bf_joint, o.bf_joint_off[k], c.d.keep_joint, N);
+    if (t == 1) return c.site(VQA_PT_KEEP_SITE_WS_JOINT, kb.keep_ws_joint, o.ws_joint_off[k], c.d.keep_joint, N);
+    return c.site(VQA_PT_KEEP_SITE_EW_JOINT, b.x.ctx[k].keep_ew_joint, o.ew_joint_off[k], c.d.keep_joint, N);
 }
 
-// a seeded site must not also carry a mask; unknown site bits are refused (checked with the entry point's other arguments,
-// before the workspace).  noc_l: the l branch's masks of a noc batch
-int keep_sites_ok(const vqa_pretrain_keep_t* ks, const vqa_pretrain_ext_batch_t& x, const vqa_pretrain_noc_kind_t* noc_l) {
+// dropout of the l joint branch of a noc head of type t, category k
+KeepSrc noc_lmask(const Ctx& c, const Batch& b, int k, int t) {
+    const vqa_pretrain_noc_kind_t& l = b.l[k];
+    return c.site(VQA_PT_KEEP_SITE_L_JOINT, t == 0 ? l.keep_bf_l_joint : t == 1 ? l.keep_ws_l_joint : l.keep_ew_l_joint,
+                  keep_of(c).l_joint_off[k][t], c.d.keep_joint, 2 * (int64_t)c.d.H);
+}
+
+// a seeded site must not also carry a mask; unknown site bits are refused
+int keep_sites_ok(const vqa_pretrain_keep_t* ks, const Batch& b) {
     if (ks == nullptr) return VQA_OK;
     VQA_REQUIRE((ks->seeded & ~VQA_PT_KEEP_SITE_ALL) == 0, VQA_ERR_ARG);
     for (int k = 0; k < 2; ++k) {
-        const vqa_pretrain_kind_t& kb = x.base.kind[k];
+        const vqa_pretrain_kind_t& kb = b.x.base.kind[k];
         VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_ATT) || kb.keep_att == nullptr, VQA_ERR_ARG);
         VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_BF_JOINT) || kb.keep_bf_joint == nullptr, VQA_ERR_ARG);
         VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_WS_JOINT) || kb.keep_ws_joint == nullptr, VQA_ERR_ARG);
-        VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_EW_JOINT) || x.ctx[k].keep_ew_joint == nullptr, VQA_ERR_ARG);
-        if (noc_l != nullptr)
+        VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_EW_JOINT) || b.x.ctx[k].keep_ew_joint == nullptr, VQA_ERR_ARG);
+        if (b.l != nullptr)
             VQA_REQUIRE(!(ks->seeded & VQA_PT_KEEP_SITE_L_JOINT) ||
-                        (!noc_l[k].keep_bf_l_joint && !noc_l[k].keep_ws_l_joint && !noc_l[k].keep_ew_l_joint), VQA_ERR_ARG);
+                        (!b.l[k].keep_bf_l_joint && !b.l[k].keep_ws_l_joint && !b.l[k].keep_ew_l_joint), VQA_ERR_ARG);
     }
     return VQA_OK;
 }
 
-// what the trunk dereferences, checked before the first launch
-int trunk_inputs_ok(const HeadSet& hs, const vqa_pretrain_ext_params_t* P, const vqa_pretrain_ext_batch_t* bx) {
-    const vqa_pretrain_batch_t* bt = &bx->base;
+// what the trunk dereferences
+int trunk_inputs_ok(const HeadSet& hs, const Params& P, const Batch& b) {
+    const vqa_pretrain_batch_t* bt = &b.x.base;
     VQA_REQUIRE(bt->image_ft && bt->spatial_ft && bt->num_boxes, VQA_ERR_ARG);
     VQA_REQUIRE((bt->perm == nullptr) == (bt->inv == nullptr) && (bt->perm == nullptr) == (bt->live_rows == nullptr), VQA_ERR_ARG);
-    VQA_REQUIRE((bx->ctx_perm == nullptr) == (bx->ctx_inv == nullptr) &&
-                (bx->ctx_perm == nullptr) == (bx->ctx_live_rows == nullptr), VQA_ERR_ARG);
+    VQA_REQUIRE((b.x.ctx_perm == nullptr) == (b.x.ctx_inv == nullptr) &&
+                (b.x.ctx_perm == nullptr) == (b.x.ctx_live_rows == nullptr), VQA_ERR_ARG);
     for (const vqa_pretrain_kind_t& kb : bt->kind)
         VQA_REQUIRE(kb.normal_boxes && kb.fills && kb.blanks && kb.blanks_len && kb.num && (hs.rank[1] < 0 || kb.wordsets),
                     VQA_ERR_ARG);
-    VQA_REQUIRE(P->wordset_map && P->l_glove && P->gru_wg && P->gru_bg && P->gru_wc && P->gru_bc, VQA_ERR_ARG);
-    if (hs.rank[1] >= 0) VQA_REQUIRE(P->wordset_ft.w && P->wordset_ft.b, VQA_ERR_ARG);
+    VQA_REQUIRE(P.wordset_map && P.l_glove && P.gru.wg && P.gru.bg && P.gru.wc && P.gru.bc, VQA_ERR_ARG);
+    if (hs.rank[1] >= 0) VQA_REQUIRE(P.wordset_ft.w && P.wordset_ft.b, VQA_ERR_ARG);
     if (hs.rank[2] >= 0)
-        VQA_REQUIRE(P->enwiki_map && P->egru_wg && P->egru_bg && P->egru_wc && P->egru_bc && bx->ctx[0].context &&
-                    bx->ctx[0].context_len && bx->ctx[1].context && bx->ctx[1].context_len, VQA_ERR_ARG);
+        VQA_REQUIRE(P.enwiki_map && P.egru.wg && P.egru.bg && P.egru.wc && P.egru.bc && b.x.ctx[0].context &&
+                    b.x.ctx[0].context_len && b.x.ctx[1].context && b.x.ctx[1].context_len, VQA_ERR_ARG);
+    return VQA_OK;
+}
+
+// The ONE prologue of every forward (G == NULL) and backward of every family.  The order of the checks is part of the
+// ABI -- a call that fails several of them returns the first one's code -- and it is not the same for every call.  The
+// differences found in the per-family prologues this one replaced, each kept as it was:
+//   - forwards only: the workspace's 16-byte alignment (VQA_ERR_ALIGN), after the workspace size; the backwards run on
+//     the workspace a forward accepted and do not look again
+//   - forwards only: the trunk's inputs (trunk_inputs_ok), after the workspace checks; the backwards never had the check
+//   - backwards only: the phase range, after the keep sites and before everything below
+//   - noc forward only: the six head weights, after the trunk's inputs (no other architecture checks its head weights)
+//   - adapt only: v_adapt's pointers (with the LayerNorm slots in use), BEFORE the layout and the workspace size.  The
+//     forward checks the parameters' v_adapt, the backward the GRADIENTS' and not the parameters'
+//   - cfg 5 is judged by dims_ok alone (Model::cfg5); its head set cannot be wrong
+const int ALL_PHASES = 15;
+int prologue(const Model& m, const Params& P, const Params* G, const Batch& b, const void* workspace,
+             int64_t workspace_bytes, int phases, const vqa_pretrain_keep_t* keep, Layout* L) {
+    const bool fwd = G == nullptr;
+    VQA_REQUIRE(m.ok && P.present && (fwd || G->present) && b.present && workspace, VQA_ERR_ARG);
+    TRY(keep_sites_ok(keep, b));
+    if (!fwd) VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
+    if (m.arch == ARCH_ADAPT) {
+        const vqa_pt_fc6_t& va = fwd ? P.v_adapt : G->v_adapt;
+        VQA_REQUIRE(va.w && va.b && va.gamma[0] && va.beta[0] && (m.ln_shared() || (va.gamma[1] && va.beta[1])), VQA_ERR_ARG);
+    }
+    *L = m.layout();
+    VQA_REQUIRE(workspace_bytes >= L->total, VQA_ERR_WORKSPACE);
+    if (!fwd) return VQA_OK;
+    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
+    TRY(trunk_inputs_ok(HeadSet(m.dims.heads), P, b));
+    if (m.arch == ARCH_NOC)
+        VQA_REQUIRE(P.pooled_linear_l.w && P.q_linear_l.w && P.joint[0].w && P.joint[1].w && P.classifier[0].w &&
+                    P.classifier[1].w, VQA_ERR_ARG);
     return VQA_OK;
 }
 
@@ -518,7 +707,6 @@ int trunk_inputs_ok(const HeadSet& hs, const vqa_pretrain_ext_params_t* P, const
 // recurrence over 5120 rows replaces two over 2560 (half the step launches, tiles that fill the chip).  Rows in length
 // order when the host sorted them (perm / inv / live_rows: the recurrence runs on the live prefix).  Two users: the
 // blank-fill captions (L_GloVe, encode_L_blank, "J/...") and the enwiki contexts (enwiki_map, encode_L_enwiki, "E/...").
-struct GruVars { float *wg, *bg, *wc, *bc; };      // gates / candidate kernel [W + H, 2H] / [W + H, H] and bias
 struct Seq {
     // workspace names: in + {tok, "lens_s", "x_tm", "xp", "hs", "gru_r", "gru_u", "gru_c", "gru_rh"} hold the sorted
     // batch and the forward tape, scr + {"wx_cat", "bx_cat", "dwx_cat", "d_state_s", "dxp", "dx"} the packed x rows
@@ -536,8 +724,8 @@ struct SeqSet { Seq s[2]; int n; };
 
 // the token batches of the head set: the captions, then the contexts when the enwiki head is on (G NULL in the forward:
 // the gradient members stay NULL)
-SeqSet make_seqs(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P, const vqa_pretrain_ext_params_t* G,
-                 const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs) {
+SeqSet make_seqs(const vqa_pretrain_ext_dims_t& dims, const Params& P, const Params* G, const Batch& b, const HeadSet& hs) {
+    const vqa_pretrain_ext_batch_t* bx = &b.x;
     const vqa_pretrain_batch_t& bt = bx->base;
     SeqSet q{};
     Seq& j = q.s[0];
@@ -545,9 +733,9 @@ SeqSet make_seqs(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_par
     j.fwd_label = "pt.caption_gru.fwd"; j.bptt_label = "pt.caption_gru.bwd"; j.embed_label = "pt.caption_embed.bwd";
     for (int k = 0; k < 2; ++k) { j.tokens[k] = bt.kind[k].blanks; j.len[k] = bt.kind[k].blanks_len; }
     j.perm = bt.perm; j.inv = bt.inv; j.live_rows = bt.live_rows;
-    j.table = P->l_glove; j.vocab = dims->base.Vq; j.T = dims->base.L; j.head = 0;
-    j.P = {P->gru_wg, P->gru_bg, P->gru_wc, P->gru_bc};
-    if (G != nullptr) { j.g_table = G->l_glove; j.G = {G->gru_wg, G->gru_bg, G->gru_wc, G->gru_bc}; }
+    j.table = P.l_glove; j.vocab = dims.base.Vq; j.T = dims.base.L; j.head = 0;
+    j.P = P.gru;
+    if (G != nullptr) { j.g_table = G->l_glove; j.G = G->gru; }
     q.n = 1;
     if (hs.rank[2] < 0) return q;
     Seq& e = q.s[1];
@@ -555,9 +743,9 @@ SeqSet make_seqs(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_par
     e.fwd_label = "pt.enwiki_gru.fwd"; e.bptt_label = "pt.enwiki_gru.bwd"; e.embed_label = "pt.enwiki_embed.bwd";
     for (int k = 0; k < 2; ++k) { e.tokens[k] = bx->ctx[k].context; e.len[k] = bx->ctx[k].context_len; }
     e.perm = bx->ctx_perm; e.inv = bx->ctx_inv; e.live_rows = bx->ctx_live_rows;
-    e.table = P->enwiki_map; e.vocab = dims->n_ctx; e.T = dims->Lc; e.head = 2 * hs.rank[2];
-    e.P = {P->egru_wg, P->egru_bg, P->egru_wc, P->egru_bc};
-    if (G != nullptr) { e.g_table = G->enwiki_map; e.G = {G->egru_wg, G->egru_bg, G->egru_wc, G->egru_bc}; }
+    e.table = P.enwiki_map; e.vocab = dims.n_ctx; e.T = dims.Lc; e.head = 2 * hs.rank[2];
+    e.P = P.egru;
+    if (G != nullptr) { e.g_table = G->enwiki_map; e.G = G->egru; }
     q.n = 2;
     return q;
 }
@@ -638,14 +826,13 @@ int seq_embed_bwd(const Ctx& c, const Seq& s, SliceSq& sq) {
     return sq.add(dx, T * B2 * W);
 }
 
-// The trunk of every model of this file: spatial attention and pooling, word sets, the caption batch and the context
-// batch, up to the stacked "S/pooled" and "S/lft" blocks the heads read
-int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                  const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs, const PoolMem* pm = nullptr) {
-    const vqa_pretrain_dims_t* d = &dims->base;
-    const vqa_pretrain_batch_t* bt = &bx->base;
-    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, Bn = B * n;
-    const SeqSet q = make_seqs(dims, P, nullptr, bx, hs);
+// The trunk of every model of this file: spatial attention and pooling over the memory pm, word sets, the caption batch
+// and the context batch, up to the stacked "S/pooled" and "S/lft" blocks the heads read
+int trunk_fwd(const Ctx& c, const Model& m, const Params& P, const Batch& b, const HeadSet& hs, const PoolMem& pm) {
+    const vqa_pretrain_dims_t* d = &m.dims.base;
+    const vqa_pretrain_batch_t* bt = &b.x.base;
+    const int64_t B = d->B, n = d->n, R = d->R, D = pm.width, H = d->H, W = d->W, Bn = B * n;
+    const SeqSet q = make_seqs(m.dims, P, nullptr, b, hs);
     TRY(seq_pack_wx(c, q.s[0]));
     for (int k = 0; k < 2; ++k) {
         const vqa_pretrain_kind_t& kb = bt->kind[k];
@@ -655,20 +842,20 @@ int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_p
         hipLaunchKernelGGL(box6_kernel, dim3((unsigned)((Bn + 255) / 256)), dim3(256), 0, c.st, kb.normal_boxes,
                            c.f(p + "key6"), (int)Bn);
         VQA_CHECK_LAUNCH();
-        TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, c.li(k), (int)R, 0, p + "v_pre", p + "v",
+        TRY(fc_ln_fwd(c, bt->spatial_ft, B * R, 6, H, P.spat_v_linear_v, c.li(k), (int)R, 0, p + "v_pre", p + "v",
                       p + "v_mean", p + "v_rstd", NO_KEEP));
-        TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, c.li(k), (int)n, 0, p + "qv_pre", p + "qv",
+        TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, P.spat_q_linear_v, c.li(k), (int)n, 0, p + "qv_pre", p + "qv",
                       p + "qv_mean", p + "qv_rstd", NO_KEEP));
-        TRY(vqa_attn_fwd_run(c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, false, bt->num_boxes,
-                             P->spat_att_score.w, P->spat_att_score.b, att_keep(c, *bx, k), c.f(p + "att"), c.f(p + "pooled"),
+        TRY(vqa_attn_fwd_run(c.f(p + "v"), c.f(p + "qv"), pm.mem[k], false, bt->num_boxes,
+                             P.spat_att_score.w, P.spat_att_score.b, att_keep(c, b, k), c.f(p + "att"), c.f(p + "pooled"),
                              (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
                            (int)B, (int)n, d->global_valid[k]);
         VQA_CHECK_LAUNCH();
         if (hs.rank[1] >= 0) {      // ---- build_*_wordset
-            TRY(vqa_embed_fwd(P->wordset_map, kb.wordsets, c.f(p + "wse"), (int)Bn, 1, (int)W, d->n_ws, c.st));
+            TRY(vqa_embed_fwd(P.wordset_map, kb.wordsets, c.f(p + "wse"), (int)Bn, 1, (int)W, d->n_ws, c.st));
             TRY(vqa_tanh_fwd(c.f(p + "wse"), c.f(p + "ws"), Bn * W, c.st));
-            TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, P->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
+            TRY(fc_ln_fwd(c, c.f(p + "ws"), Bn, W, H, P.wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf", p + "wf_mean",
                           p + "wf_rstd", NO_KEEP));
         }
     }
@@ -678,20 +865,19 @@ int ext_trunk_fwd(const Ctx& c, const vqa_pretrain_ext_dims_t* dims, const vqa_p
 }
 
 // Phases 2, 4 and 8 of the backward (everything below the heads)
-int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                  const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, const HeadSet& hs,
-                  float* slice_sq, int phases, const PoolMem* pm = nullptr) {
-    const vqa_pretrain_dims_t* d = &dims->base;
-    const vqa_pretrain_batch_t* bt = &bx->base;
-    const int64_t B = d->B, n = d->n, R = d->R, D = pm ? pm->width : d->D, H = d->H, W = d->W, Bn = B * n;
+int trunk_bwd(const Ctx& c, Acc& acc, const Model& m, const Params& P, const Params& G, const Batch& b, const HeadSet& hs,
+              float* slice_sq, int phases, const PoolMem& pm) {
+    const vqa_pretrain_dims_t* d = &m.dims.base;
+    const vqa_pretrain_batch_t* bt = &b.x.base;
+    const int64_t B = d->B, n = d->n, R = d->R, D = pm.width, H = d->H, W = d->W, Bn = B * n;
     const int det = (d->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0;
     // the embedding tables are scatter-added: cleared in their phase; every other gradient is overwritten on first touch
     SliceSq sq{c, nullptr};
-    const SeqSet q = make_seqs(dims, P, G, bx, hs);
+    const SeqSet q = make_seqs(m.dims, P, &G, b, hs);
     for (int i = 0; i < q.n && (phases & 2); ++i) TRY(seq_bptt(c, acc, q.s[i]));
     for (int i = 0; i < q.n && (phases & 4); ++i) TRY(seq_embed_bwd(c, q.s[i], sq));
     if (phases & 8) {
-        if (hipMemsetAsync(G->wordset_map, 0, (size_t)d->n_ws * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+        if (hipMemsetAsync(G.wordset_map, 0, (size_t)d->n_ws * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
         if (!(phases & 4)) sq.prev = c.f("sq");      // phase 4 of this step left the sequences' slice sum of squares there
     }
     for (int k = 0; k < 2 && (phases & 8); ++k) {
@@ -699,23 +885,23 @@ int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, c
         const vqa_pretrain_kind_t& kb = bt->kind[k];
         const std::string p = std::string(KIND[k]) + "/";
         if (hs.rank[1] >= 0) {      // ---- word set -> wordset_ft -> tanh -> wordset_map
-            TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 * hs.rank[1] + k) * Bn * H, c.f(p + "ws"), Bn, W, H, P->wordset_ft,
-                          G->wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", NO_KEEP, "d_wfpre",
+            TRY(fc_ln_bwd(c, acc, c.f("d_lft") + (2 * hs.rank[1] + k) * Bn * H, c.f(p + "ws"), Bn, W, H, P.wordset_ft,
+                          G.wordset_ft, c.li(k), (int)n, 1, p + "wf_pre", p + "wf_mean", p + "wf_rstd", NO_KEEP, "d_wfpre",
                           c.f("d_ws")));
             TRY(vqa_tanh_bwd(c.f("d_ws"), c.f(p + "ws"), c.f("d_wse"), Bn * W, c.st));
-            TRY(vqa_embed_bwd_len_det(c.f("d_wse"), kb.wordsets, nullptr, G->wordset_map, (int)Bn, 1, (int)W, d->n_ws, det,
+            TRY(vqa_embed_bwd_len_det(c.f("d_wse"), kb.wordsets, nullptr, G.wordset_map, (int)Bn, 1, (int)W, d->n_ws, det,
                                       c.st));
             TRY(sq.add(c.f("d_wse"), Bn * W));
         }
         // ---- spatial attention
-        TRY(vqa_attn_bwd_run(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm ? pm->mem[k] : bt->image_ft, false,
-                             c.f(p + "att"), P->spat_att_score.w, att_keep(c, *bx, k), c.f("d_v"), c.f("d_qv"),
+        TRY(vqa_attn_bwd_run(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm.mem[k], false,
+                             c.f(p + "att"), P.spat_att_score.w, att_keep(c, b, k), c.f("d_v"), c.f("d_qv"),
                              c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
-        TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G->spat_att_score.w));
-        TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G->spat_att_score.b));
-        TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, P->spat_v_linear_v, G->spat_v_linear_v, c.li(k), (int)R,
+        TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G.spat_att_score.w));
+        TRY(acc.colsum(c.f("part_db"), Bn, 1, 1, G.spat_att_score.b));
+        TRY(fc_ln_bwd(c, acc, c.f("d_v"), bt->spatial_ft, B * R, 6, H, P.spat_v_linear_v, G.spat_v_linear_v, c.li(k), (int)R,
                       0, p + "v_pre", p + "v_mean", p + "v_rstd", NO_KEEP, "d_vpre", nullptr));
-        TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, P->spat_q_linear_v, G->spat_q_linear_v, c.li(k), (int)n,
+        TRY(fc_ln_bwd(c, acc, c.f("d_qv"), c.f(p + "key6"), Bn, 6, H, P.spat_q_linear_v, G.spat_q_linear_v, c.li(k), (int)n,
                       0, p + "qv_pre", p + "qv_mean", p + "qv_rstd", NO_KEEP, "d_qvpre", nullptr));
     }
     if ((phases & 8) && slice_sq != nullptr && sq.prev != nullptr)
@@ -726,11 +912,10 @@ int ext_trunk_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_ext_dims_t* dims, c
 
 // pooled_linear_l over the 2 Bn pooled rows and q_linear_l over the NH Bn stacked language rows ("S/lft"), then each
 // head's LayerNorm + ReLU of both into its slices of "S/vl" / "S/ll" (v_linear_l / l_linear_l of the reference)
-// (pooled_width: K of pooled_linear_l when the attention pooled another memory than image_ft; 0 = D)
-int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin,
-                 int64_t pooled_width = 0) {
+// (D: the width of the pooled memory = K of pooled_linear_l)
+int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin, int64_t D) {
     const vqa_pretrain_dims_t& d = c.d;
-    const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
+    const int64_t B = d.B, n = d.n, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
     TRY(c.gemm_routed(0, 0, 2 * Bn, H, D, c.f("S/pooled"), (int)D, pooled.w, (int)H, c.f("S/vl_pre"), (int)H, pooled.b));
     TRY(c.gemm_routed(0, 0, NH * Bn, H, H, c.f("S/lft"), (int)H, qlin.w, (int)H, c.f("S/ll_pre"), (int)H, qlin.b));
     for (int h = 0; h < NH; ++h) {
@@ -745,9 +930,9 @@ int heads_in_fwd(const Ctx& c, const HeadSet& hs, const vqa_pt_fc6_t& pooled, co
 
 // its backward from "d_vl" / "d_ll": LayerNorms, pooled_linear_l (dW, d_pooled) and q_linear_l (dW, d_lft)
 int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& pooled, const vqa_pt_fc6_t& qlin,
-                 const vqa_pt_fc6_t& g_pooled, const vqa_pt_fc6_t& g_qlin, int64_t pooled_width = 0) {
+                 const vqa_pt_fc6_t& g_pooled, const vqa_pt_fc6_t& g_qlin, int64_t D) {
     const vqa_pretrain_dims_t& d = c.d;
-    const int64_t B = d.B, n = d.n, D = pooled_width > 0 ? pooled_width : d.D, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
+    const int64_t B = d.B, n = d.n, H = d.H, Bn = B * n, NH = hs.nh(), SH = Bn * H;
     for (int h = 0; h < NH; ++h) {
         const std::string q = hs.name(h);
         TRY(ln_bwd(c, acc, c.f("d_vl") + h * SH, Bn, H, pooled, g_pooled, c.li(h), (int)n, 0, c.f("S/vl_pre") + (h & 1) * SH,
@@ -762,36 +947,9 @@ int heads_in_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const vqa_pt_fc6_t& 
     return fc_bwd(c, acc, PREC_ROUTED, "d_llpre", c.f("S/lft"), NH * Bn, H, H, qlin, g_qlin, c.f("d_lft"));
 }
 
-}  // namespace
-
-extern "C" const char* vqa_pretrain_ext_report_key(int heads, int i) {
-    static std::vector<std::string> keys[8];        // built once per head set; the pointers stay valid
-    static const int init = [] {
-        for (int m = 0; m < 8; ++m)
-            if (m & VQA_PT_HEAD_BF)
-                for (int i = 0; i <= 3 * HeadSet(m).nh(); ++i) keys[m].push_back(ext_report_key(m, i));
-        return 0;
-    }();
-    (void)init;
-    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[heads].size()) return nullptr;
-    return keys[heads][i].c_str();
-}
-
-extern "C" int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    return ext_dims_ok(dims) ? make_layout_ext(*dims).total : VQA_ERR_ARG;
-}
-
-extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
-                                       int64_t* n_elems) {
-    if (!ext_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    return layout_tensor(make_layout_ext(*dims), name, offset_bytes, n_elems);
-}
-
-namespace {
-
-// the v_adapt layer of vqa_pretrain_adapt_*: image_ft [B R, D] -> FC -> LayerNorm over each image's [R,H] block + ReLU,
-// one pre-activation, one output per LayerNorm slot in use (pm.mem[1] == pm.mem[0] when the slot is shared)
-int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t& va, PoolMem* pm) {
+// the v_adapt layer of the adapt architecture: image_ft [B R, D] -> FC -> LayerNorm over each image's [R,H] block + ReLU,
+// one pre-activation, one output per LayerNorm slot in use ("attr/va" names "obj/va" when the slot is shared)
+int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t& va) {
     const vqa_pretrain_dims_t& d = c.d;
     const int64_t B = d.B, R = d.R, D = d.D, H = d.H;
     const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
@@ -802,7 +960,6 @@ int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t
         TRY(vqa_ln_act_fwd_run(c.f("va_pre"), va.gamma[k], va.beta[k], NO_KEEP, c.f(p + "va"), c.f(p + "va_mean"),
                                c.f(p + "va_rstd"), (int)B, (int)R, (int)H, 0, c.st));
     }
-    pm->mem[0] = c.f("obj/va"); pm->mem[1] = c.f("attr/va"); pm->width = H;
     return VQA_OK;
 }
 
@@ -831,201 +988,205 @@ int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vq
     return acc.weight(PREC_ROUTED, g_va.w, bt->image_ft, (int)D, c.f("d_vapre"), (int)H, D, H, B * R);
 }
 
-// forward of the variable-head-set model on the layout L; va != NULL: with the v_adapt layer (vqa_pretrain_adapt_*)
-int ext_forward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                     const vqa_pretrain_ext_batch_t* bx, void* workspace, int want_dz, void* stream,
-                     const vqa_pt_fc6_t* va, const vqa_pretrain_keep_t* ks) {
-    const vqa_pretrain_dims_t* d = &dims->base;
-    const vqa_pretrain_batch_t* bt = &bx->base;
-    const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), ks};
-    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    TRY(trunk_inputs_ok(hs, P, bx));
+// the memory the model's attention pools: the features, or v_adapt per LayerNorm slot
+PoolMem pool_mem(const Ctx& c, const Model& m, const Batch& b) {
+    if (m.arch == ARCH_ADAPT) return {{c.f("obj/va"), c.f("attr/va")}, c.d.H};
+    return {{b.x.base.image_ft, b.x.base.image_ft}, c.d.D};
+}
+
+// ---------------------------------------------------------------- the head blocks
+// What follows "S/vl" / "S/ll" (heads_in_fwd), per architecture: the logits and losses of the NH stacked heads, and the
+// stats blocks the report reads, in key order.  The backward counterparts run from the dz blocks to "d_vl" / "d_ll".
+
+// standard and adapt: joint_fc(v_linear_l * l_linear_l) -> classifier -> masked softmax-CE per head
+int std_heads_fwd(const Ctx& c, const HeadSet& hs, const Params& P, const Batch& b, int want_dz, ReportExtArgs* ra) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, n = d.n, H = d.H, A = d.A, Bn = B * n, NH = hs.nh(), SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
+    const vqa_pt_fc6_t &joint = P.joint[0], &cls = P.classifier[0];
+    TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
+    TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, joint.w, (int)(2 * H), c.f("S/j_pre"), (int)(2 * H),
+                      joint.b));
+    for (int h = 0; h < NH; ++h) {
+        const std::string q = hs.name(h);
+        TRY(vqa_ln_act_fwd_run(c.f("S/j_pre") + h * SJ, joint.gamma[c.li(h)], joint.beta[c.li(h)],
+                               joint_keep(c, b, h & 1, hs.type[h >> 1]), c.f("S/j") + h * SJ, c.f(q + "j_mean"),
+                               c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0, c.st));
+    }
+    TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), cls.w, (int)A, c.f("S/z"), (int)A, cls.b));
+    for (int h = 0; h < NH; ++h) {
+        const int k = h & 1, r = h >> 1;
+        const std::string p = std::string(KIND[k]) + "/";
+        TRY(vqa_softmax_ce_fwd(c.f("S/z") + h * SA, b.x.base.kind[k].fills, c.f(p + "valid"), 5, c.f(p + "inv_valid"),
+                               c.f("S/stats") + h * Bn * 4, want_dz ? c.f("S/dz") + h * SA : nullptr, (int)Bn, (int)A, c.st));
+        ra->stats[k * hs.nt + r] = c.f("S/stats") + h * Bn * 4;
+        ra->inv[k * hs.nt + r] = c.f(p + "inv_valid");
+    }
+    ra->nh = (int)NH;
+    return VQA_OK;
+}
+
+int std_heads_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const Params& P, const Params& G, const Batch& b) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, n = d.n, H = d.H, A = d.A, Bn = B * n, NH = hs.nh(), SH = Bn * H, SJ = Bn * 2 * H;
+    const vqa_pt_fc6_t &joint = P.joint[0], &g_joint = G.joint[0];
+    TRY(acc.weight(PREC_ROUTED, G.classifier[0].w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
+    TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G.classifier[0].b));
+    TRY(c.gemm_routed(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P.classifier[0].w, (int)A, c.f("d_j"), (int)(2 * H)));
+    for (int h = 0; h < NH; ++h) {
+        const std::string q = hs.name(h);
+        TRY(ln_bwd(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, joint, g_joint, c.li(h), (int)n, 0, c.f("S/j_pre") + h * SJ,
+                   c.f(q + "j_mean"), c.f(q + "j_rstd"), joint_keep(c, b, h & 1, hs.type[h >> 1]), c.f("d_jpre") + h * SJ));
+    }
+    TRY(fc_bwd(c, acc, PREC_ROUTED, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, joint, g_joint, c.f("d_jin")));
+    return vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st);
+}
+
+// noc (vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py = model_vlmap_nocarch_bf_or_wordset_withatt_sp.py, bf | ws;
+// model_vlmap_noc_bf_or_enwiki_withatt_sp.py, bf | ew): per head two branches instead of the product,
+//   v_joint = dropout(relu(LN(v_linear_l joint_v)), 0.5) -> classifier_v,  l_joint = the same on l_linear_l -> classifier_l
+// Blank fill is a SUM head (one CE of v_logit + l_logit), word set and enwiki are SPLIT heads (a CE per branch).  Both
+// branches' joint and classifier GEMMs run over the whole stacked NH Bn block, forward and backward, whatever the
+// head's loss; vqa_softmax_ce_pair_fwd writes every head's stats and dz in one launch.
+int noc_heads_fwd(const Ctx& c, const HeadSet& hs, const Params& P, const Batch& b, int want_dz, ReportExtArgs* ra) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t B = d.B, n = d.n, H = d.H, A = d.A, Bn = B * n, NH = hs.nh(), SJ = Bn * 2 * H, SA = Bn * A;
+    TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/vl"), (int)H, P.joint[0].w, (int)(2 * H), c.f("S/jv_pre"), (int)(2 * H),
+                      P.joint[0].b));
+    TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/ll"), (int)H, P.joint[1].w, (int)(2 * H), c.f("S/jl_pre"), (int)(2 * H),
+                      P.joint[1].b));
+    for (int h = 0; h < NH; ++h) {
+        const int k = h & 1, t = hs.type[h >> 1];
+        const std::string q = hs.name(h);
+        TRY(vqa_ln_act_fwd_run(c.f("S/jv_pre") + h * SJ, P.joint[0].gamma[c.li(h)], P.joint[0].beta[c.li(h)],
+                               joint_keep(c, b, k, t), c.f("S/jv") + h * SJ, c.f(q + "jv_mean"), c.f(q + "jv_rstd"), (int)B,
+                               (int)n, (int)(2 * H), 0, c.st));
+        TRY(vqa_ln_act_fwd_run(c.f("S/jl_pre") + h * SJ, P.joint[1].gamma[c.li(h)], P.joint[1].beta[c.li(h)],
+                               noc_lmask(c, b, k, t), c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"), (int)B,
+                               (int)n, (int)(2 * H), 0, c.st));
+    }
+    TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jv"), (int)(2 * H), P.classifier[0].w, (int)A, c.f("S/zv"), (int)A,
+                      P.classifier[0].b));
+    TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jl"), (int)(2 * H), P.classifier[1].w, (int)A, c.f("S/zl"), (int)A,
+                      P.classifier[1].b));
+    // every head's loss in one launch; the report reads the stats blocks in key order
+    vqa_softmax_pair_t pr[VQA_SOFTMAX_PAIR_MAX] = {};
+    const float* st_by_key[2][3][2] = {};
+    for (int h = 0; h < NH; ++h) {
+        const int k = h & 1, r = h >> 1;
+        const std::string p = std::string(KIND[k]) + "/";
+        vqa_softmax_pair_t& e = pr[h];
+        e.zv = c.f("S/zv") + h * SA; e.zl = c.f("S/zl") + h * SA;
+        e.label = b.x.base.kind[k].fills; e.valid = c.f(p + "valid"); e.inv_valid_sum = c.f(p + "inv_valid");
+        e.split = noc_split(hs.type[r]) ? 1 : 0;
+        e.stats_v = c.f("S/stats") + h * Bn * 4; e.stats_l = c.f("S/stats_l") + h * Bn * 4;
+        e.dzv = want_dz ? c.f("S/dzv") + h * SA : nullptr; e.dzl = want_dz ? c.f("S/dzl") + h * SA : nullptr;
+        st_by_key[k][r][0] = e.stats_v;
+        st_by_key[k][r][1] = e.split ? e.stats_l : nullptr;
+    }
+    TRY(vqa_softmax_ce_pair_fwd(pr, (int)NH, 5, (int)Bn, (int)A, c.st));
+    for (int k = 0; k < 2; ++k)
+        for (int r = 0; r < hs.nt; ++r)
+            for (int br = 0; br < 2; ++br)
+                if (st_by_key[k][r][br] != nullptr) {
+                    ra->stats[ra->nh] = st_by_key[k][r][br];
+                    ra->inv[ra->nh++] = c.f(std::string(KIND[k]) + "/inv_valid");
+                }
+    return VQA_OK;
+}
+
+// per branch: classifier dW / db / dx, each head's joint LayerNorm, the joint dW / db and dx into d_vl / d_ll
+int noc_heads_bwd(const Ctx& c, Acc& acc, const HeadSet& hs, const Params& P, const Params& G, const Batch& b) {
+    const vqa_pretrain_dims_t& d = c.d;
+    const int64_t n = d.n, H = d.H, A = d.A, Bn = (int64_t)d.B * n, NH = hs.nh(), SJ = Bn * 2 * H;
+    struct Branch { const char *j, *dz, *dj, *jpre, *djpre, *in, *din, *tag; };
+    const Branch br[2] = {{"S/jv", "S/dzv", "d_jv", "S/jv_pre", "d_jvpre", "S/vl", "d_vl", "jv"},
+                          {"S/jl", "S/dzl", "d_jl", "S/jl_pre", "d_jlpre", "S/ll", "d_ll", "jl"}};
+    for (int v = 0; v < 2; ++v) {
+        const Branch& x = br[v];
+        TRY(acc.weight(PREC_ROUTED, G.classifier[v].w, c.f(x.j), (int)(2 * H), c.f(x.dz), (int)A, 2 * H, A, NH * Bn));
+        TRY(acc.colsum(c.f(x.dz), NH * Bn, A, (int)A, G.classifier[v].b));
+        TRY(c.gemm_routed(0, 1, NH * Bn, 2 * H, A, c.f(x.dz), (int)A, P.classifier[v].w, (int)A, c.f(x.dj), (int)(2 * H)));
+        for (int h = 0; h < NH; ++h) {
+            const int k = h & 1, t = hs.type[h >> 1];
+            const std::string q = hs.name(h) + x.tag;
+            TRY(ln_bwd(c, acc, c.f(x.dj) + h * SJ, Bn, 2 * H, P.joint[v], G.joint[v], c.li(h), (int)n, 0, c.f(x.jpre) + h * SJ,
+                       c.f(q + "_mean"), c.f(q + "_rstd"), v == 0 ? joint_keep(c, b, k, t) : noc_lmask(c, b, k, t),
+                       c.f(x.djpre) + h * SJ));
+        }
+        TRY(fc_bwd(c, acc, PREC_ROUTED, x.djpre, c.f(x.in), NH * Bn, H, 2 * H, P.joint[v], G.joint[v], c.f(x.din)));
+    }
+    return VQA_OK;
+}
+
+// ---------------------------------------------------------------- the forward and the backward of every model
+int forward(const Model& m, const Params& P, const Batch& b, void* workspace, int64_t workspace_bytes, int want_dz,
+            void* stream, const vqa_pretrain_keep_t* keep) {
+    Layout L;
+    TRY(prologue(m, P, nullptr, b, workspace, workspace_bytes, ALL_PHASES, keep, &L));      // a forward has no phases
+    const HeadSet hs(m.dims.heads);
+    const Ctx c{m.dims.base, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
     ReportExtArgs ra{};
-    ra.rows = (int)Bn;
-    ra.nh = (int)NH;
-    ProbeScope ps_all("pretrain_ext.forward", c.st);
-    PoolMem pm{};
-    if (va != nullptr) TRY(v_adapt_fwd(c, bt, *va, &pm));
-    TRY(ext_trunk_fwd(c, dims, P, bx, hs, va ? &pm : nullptr));
+    ra.rows = c.d.B * c.d.n;
+    ProbeScope ps_all(m.fwd_label(), c.st);
+    if (m.arch == ARCH_ADAPT) TRY(v_adapt_fwd(c, &b.x.base, P.v_adapt));
+    const PoolMem pm = pool_mem(c, m, b);
+    TRY(trunk_fwd(c, m, P, b, hs, pm));
     {   // the NH heads, stacked
-        const int64_t SH = Bn * H, SJ = Bn * 2 * H, SA = Bn * A;
         ProbeScope ps_h("pt.heads.fwd", c.st);
-        TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l, pm.width));
-        TRY(vqa_mul(c.f("S/vl"), c.f("S/ll"), c.f("S/jin"), NH * SH, c.st));
-        TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/jin"), (int)H, P->joint_fc.w, (int)(2 * H), c.f("S/j_pre"),
-                          (int)(2 * H), P->joint_fc.b));
-        for (int h = 0; h < NH; ++h) {
-            const std::string q = hs.name(h);
-            TRY(vqa_ln_act_fwd_run(c.f("S/j_pre") + h * SJ, P->joint_fc.gamma[c.li(h)], P->joint_fc.beta[c.li(h)],
-                                   joint_keep(c, *bx, h & 1, hs.type[h >> 1]), c.f("S/j") + h * SJ, c.f(q + "j_mean"),
-                                   c.f(q + "j_rstd"), (int)B, (int)n, (int)(2 * H), 0, c.st));
-        }
-        TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/j"), (int)(2 * H), P->classifier.w, (int)A, c.f("S/z"), (int)A,
-                          P->classifier.b));
-        for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, r = h >> 1;
-            const std::string p = std::string(KIND[k]) + "/";
-            TRY(vqa_softmax_ce_fwd(c.f("S/z") + h * SA, bt->kind[k].fills, c.f(p + "valid"), 5, c.f(p + "inv_valid"),
-                                   c.f("S/stats") + h * Bn * 4, want_dz ? c.f("S/dz") + h * SA : nullptr, (int)Bn, (int)A,
-                                   c.st));
-            ra.stats[k * hs.nt + r] = c.f("S/stats") + h * Bn * 4;
-            ra.inv[k * hs.nt + r] = c.f(p + "inv_valid");
-        }
+        TRY(heads_in_fwd(c, hs, P.pooled_linear_l, P.q_linear_l, pm.width));
+        TRY((m.arch == ARCH_NOC ? noc_heads_fwd : std_heads_fwd)(c, hs, P, b, want_dz, &ra));
     }
     hipLaunchKernelGGL(pretrain_ext_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
 
-}  // namespace
-
-extern "C" int vqa_pretrain_ext_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                           const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
-                                           int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
-    TRY(keep_sites_ok(keep, *bx, nullptr));
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    return ext_forward_impl(L, dims, P, bx, workspace, want_dz, stream, nullptr, keep);
-}
-
-extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
-                                        int want_dz, void* stream) {
-    return vqa_pretrain_ext_forward_ex(dims, P, bx, workspace, workspace_bytes, want_dz, stream, nullptr);
-}
-
-// Backward phases of the variable head set; the buckets of vqa_pretrain_backward_phases, with
-//   1  the NH stacked heads
+// The backward in dependency-ordered phases (bit mask, ascending within a step):
+//   1  the NH stacked heads: the architecture's head block, then pooled_linear_l and q_linear_l
 //   2  BPTT of the caption batch, then of the enwiki context batch (encode_L_blank and encode_L_enwiki gradients)
 //   4  L_GloVe scatter-add, then enwiki_map scatter-add (both slice sums of squares)
-//   8  per category: wordset_ft / wordset_map (cleared even without the word-set head), spatial attention (writes slice_sq)
-namespace {
-
-// va / g_va != NULL: with the v_adapt layer, whose gradients complete phase 8
-int ext_backward_impl(const Layout& L, const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                      const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx, void* workspace,
-                      float* slice_sq, int phases, void* stream, const vqa_pt_fc6_t* va, const vqa_pt_fc6_t* g_va,
-                      const vqa_pretrain_keep_t* ks) {
-    const vqa_pretrain_dims_t* d = &dims->base;
-    const vqa_pretrain_batch_t* bt = &bx->base;
-    const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), ks};
-    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    ProbeScope ps_all("pretrain_ext.backward", c.st);
+//   8  per category: wordset_ft / wordset_map (cleared even without the word-set head), spatial attention (writes
+//      slice_sq); adapt: then the v_adapt gradients, which need the attention backward of both categories
+int backward(const Model& m, const Params& P, const Params& G, const Batch& b, void* workspace, int64_t workspace_bytes,
+             float* slice_sq, int phases, void* stream, const vqa_pretrain_keep_t* keep) {
+    Layout L;
+    TRY(prologue(m, P, &G, b, workspace, workspace_bytes, phases, keep, &L));
+    const HeadSet hs(m.dims.heads);
+    const Ctx c{m.dims.base, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
+    ProbeScope ps_all(m.bwd_label(), c.st);
     Acc acc{c, {}};
+    const PoolMem pm = pool_mem(c, m, b);
     if (phases & 1) {
         ProbeScope ps_h("pt.heads.bwd", c.st);
-        const int64_t SH = Bn * H, SJ = Bn * 2 * H;
-        TRY(acc.weight(PREC_ROUTED, G->classifier.w, c.f("S/j"), (int)(2 * H), c.f("S/dz"), (int)A, 2 * H, A, NH * Bn));
-        TRY(acc.colsum(c.f("S/dz"), NH * Bn, A, (int)A, G->classifier.b));
-        TRY(c.gemm_routed(0, 1, NH * Bn, 2 * H, A, c.f("S/dz"), (int)A, P->classifier.w, (int)A, c.f("d_j"), (int)(2 * H)));
-        for (int h = 0; h < NH; ++h) {
-            const std::string q = hs.name(h);
-            TRY(ln_bwd(c, acc, c.f("d_j") + h * SJ, Bn, 2 * H, P->joint_fc, G->joint_fc, c.li(h), (int)n, 0,
-                       c.f("S/j_pre") + h * SJ, c.f(q + "j_mean"), c.f(q + "j_rstd"), joint_keep(c, *bx, h & 1, hs.type[h >> 1]),
-                       c.f("d_jpre") + h * SJ));
-        }
-        TRY(fc_bwd(c, acc, PREC_ROUTED, "d_jpre", c.f("S/jin"), NH * Bn, H, 2 * H, P->joint_fc, G->joint_fc, c.f("d_jin")));
-        TRY(vqa_mul_bwd(c.f("d_jin"), c.f("S/vl"), c.f("S/ll"), c.f("d_vl"), c.f("d_ll"), NH * SH, c.st));
-        TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l, va ? d->H : 0));
+        TRY((m.arch == ARCH_NOC ? noc_heads_bwd : std_heads_bwd)(c, acc, hs, P, G, b));
+        TRY(heads_in_bwd(c, acc, hs, P.pooled_linear_l, P.q_linear_l, G.pooled_linear_l, G.q_linear_l, pm.width));
     }
-    if (va == nullptr) return ext_trunk_bwd(c, acc, dims, P, G, bx, hs, slice_sq, phases);
-    const PoolMem pm{{c.f("obj/va"), c.f("attr/va")}, d->H};
-    TRY(ext_trunk_bwd(c, acc, dims, P, G, bx, hs, slice_sq, phases, &pm));
-    return (phases & 8) ? v_adapt_bwd(c, acc, bt, *va, *g_va) : VQA_OK;
+    TRY(trunk_bwd(c, acc, m, P, G, b, hs, slice_sq, phases, pm));
+    return (m.arch == ARCH_ADAPT && (phases & 8)) ? v_adapt_bwd(c, acc, &b.x.base, P.v_adapt, G.v_adapt) : VQA_OK;
 }
 
 }  // namespace
 
-extern "C" int vqa_pretrain_ext_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                                   const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
-                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                                   void* stream, const vqa_pretrain_keep_t* keep) {
-    VQA_REQUIRE(ext_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
-    TRY(keep_sites_ok(keep, *bx, nullptr));
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    return ext_backward_impl(L, dims, P, G, bx, workspace, slice_sq, phases, stream, nullptr, nullptr, keep);
-}
+// ================================================================ the entry points
+// Every family: an adapter from its public structs to (Model, Params, Batch), then the one function above.  The calls
+// without _ex are the _ex calls with keep = NULL, *_backward is *_backward_phases with phases = 15.
 
-extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
-                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                                void* stream) {
-    return vqa_pretrain_ext_backward_phases_ex(dims, P, G, bx, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
-}
-
-extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
-                                         const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
-                                         void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
-    return vqa_pretrain_ext_backward_phases(dims, P, G, bx, workspace, workspace_bytes, slice_sq, 15, stream);
-}
-
-// ================================================================ the cfg-5 entry points
-// vqa_pretrain_* = vqa_pretrain_ext_* with heads bf | ws, no context batch, and every fc_layer scope widened from 4 to 6
-// LayerNorm slots (4 and 5 NULL: four heads never index them)
-namespace {
-
-bool cfg5_dims(const vqa_pretrain_dims_t* d, vqa_pretrain_ext_dims_t* x) {
-    if (!dims_ok(d)) return false;
-    *x = vqa_pretrain_ext_dims_t{*d, VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, 0, 0};
-    return true;
-}
-
-vqa_pt_fc6_t fc6(const vqa_pt_fc_t& f) {
-    vqa_pt_fc6_t o{};
-    o.w = f.w; o.b = f.b;
-    for (int i = 0; i < 4; ++i) { o.beta[i] = f.beta[i]; o.gamma[i] = f.gamma[i]; }
-    return o;
-}
-
-vqa_pretrain_ext_params_t cfg5_params(const vqa_pretrain_params_t& p) {
-    vqa_pretrain_ext_params_t e{};      // the enwiki members stay NULL
-    e.wordset_map = p.wordset_map; e.l_glove = p.l_glove;
-    e.spat_v_linear_v = fc6(p.spat_v_linear_v); e.spat_q_linear_v = fc6(p.spat_q_linear_v);
-    e.spat_att_score = fc6(p.spat_att_score);
-    e.gru_wg = p.gru_wg; e.gru_bg = p.gru_bg; e.gru_wc = p.gru_wc; e.gru_bc = p.gru_bc;
-    e.pooled_linear_l = fc6(p.pooled_linear_l); e.q_linear_l = fc6(p.q_linear_l); e.joint_fc = fc6(p.joint_fc);
-    e.wordset_ft = fc6(p.wordset_ft); e.classifier = fc6(p.classifier);
-    return e;
-}
-
-vqa_pretrain_ext_batch_t cfg5_batch(const vqa_pretrain_batch_t& b) {
-    vqa_pretrain_ext_batch_t e{};
-    e.base = b;
-    return e;
-}
-
-}  // namespace
-
+// ---- vqa_pretrain_*: cfg 5 = heads bf | ws on the standard architecture, structs with 4 LayerNorm slots and no contexts
 extern "C" const char* vqa_pretrain_report_key(int i) {
-    return vqa_pretrain_ext_report_key(VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, i);
+    return report_key(ARCH_STANDARD, VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, i);
 }
 
-extern "C" int64_t vqa_pretrain_workspace_bytes(const vqa_pretrain_dims_t* dims) {
-    vqa_pretrain_ext_dims_t x;
-    return cfg5_dims(dims, &x) ? make_layout_ext(x).total : VQA_ERR_ARG;
-}
+extern "C" int64_t vqa_pretrain_workspace_bytes(const vqa_pretrain_dims_t* dims) { return layout_bytes(Model::cfg5(dims)); }
 
 extern "C" int vqa_pretrain_tensor(const vqa_pretrain_dims_t* dims, const char* name, int64_t* offset_bytes,
                                    int64_t* n_elems) {
-    vqa_pretrain_ext_dims_t x;
-    if (!cfg5_dims(dims, &x) || name == nullptr) return VQA_ERR_ARG;
-    return layout_tensor(make_layout_ext(x), name, offset_bytes, n_elems);
+    return layout_tensor(Model::cfg5(dims), name, offset_bytes, n_elems);
 }
 
 extern "C" int vqa_pretrain_forward_ex(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
                                        const vqa_pretrain_batch_t* bt, void* workspace, int64_t workspace_bytes,
                                        int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
-    vqa_pretrain_ext_dims_t x;
-    VQA_REQUIRE(cfg5_dims(dims, &x) && P && bt && workspace, VQA_ERR_ARG);
-    const vqa_pretrain_ext_params_t EP = cfg5_params(*P);
-    const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
-    return vqa_pretrain_ext_forward_ex(&x, &EP, &bx, workspace, workspace_bytes, want_dz, stream, keep);
+    return forward(Model::cfg5(dims), view(P), view(bt), workspace, workspace_bytes, want_dz, stream, keep);
 }
 
 extern "C" int vqa_pretrain_forward(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
@@ -1038,11 +1199,7 @@ extern "C" int vqa_pretrain_backward_phases_ex(const vqa_pretrain_dims_t* dims, 
                                                const vqa_pretrain_params_t* G, const vqa_pretrain_batch_t* bt,
                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                                void* stream, const vqa_pretrain_keep_t* keep) {
-    vqa_pretrain_ext_dims_t x;
-    VQA_REQUIRE(cfg5_dims(dims, &x) && P && G && bt && workspace, VQA_ERR_ARG);
-    const vqa_pretrain_ext_params_t EP = cfg5_params(*P), EG = cfg5_params(*G);
-    const vqa_pretrain_ext_batch_t bx = cfg5_batch(*bt);
-    return vqa_pretrain_ext_backward_phases_ex(&x, &EP, &EG, &bx, workspace, workspace_bytes, slice_sq, phases, stream, keep);
+    return backward(Model::cfg5(dims), view(P), view(G), view(bt), workspace, workspace_bytes, slice_sq, phases, stream, keep);
 }
 
 extern "C" int vqa_pretrain_backward_phases(const vqa_pretrain_dims_t* dims, const vqa_pretrain_params_t* P,
@@ -1058,85 +1215,67 @@ extern "C" int vqa_pretrain_backward(const vqa_pretrain_dims_t* dims, const vqa_
     return vqa_pretrain_backward_phases(dims, P, G, bt, workspace, workspace_bytes, slice_sq, 15, stream);
 }
 
-// ================================================================ "no composition" pre-training
-// vlmap_memft/model_vlmap_noc_bf_or_wordset_withatt_sp.py (= model_vlmap_nocarch_bf_or_wordset_withatt_sp.py, bf | ws) and
-// model_vlmap_noc_bf_or_enwiki_withatt_sp.py (bf | ew): the trunk and head inputs of the variable-head-set model, then
-// per head two branches instead of joint_fc(v_linear_l * l_linear_l) -> classifier:
-//   v_joint = dropout(relu(LN(v_linear_l joint_v)), 0.5) -> classifier_v,  l_joint = the same on l_linear_l -> classifier_l
-// Blank fill is a SUM head (one CE of v_logit + l_logit), word set and enwiki are SPLIT heads (a CE per branch).  Both
-// branches' joint and classifier GEMMs run over the whole stacked NH Bn block, forward and backward, whatever the
-// head's loss; vqa_softmax_ce_pair_fwd writes every head's stats and dz in one launch.
-namespace {
+// ---- vqa_pretrain_ext_*: the variable head set on the standard architecture
+extern "C" const char* vqa_pretrain_ext_report_key(int heads, int i) { return report_key(ARCH_STANDARD, heads, i); }
 
-bool noc_dims_ok(const vqa_pretrain_ext_dims_t* d) {
-    return ext_dims_ok(d) && (d->heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS) || d->heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_EW));
+extern "C" int64_t vqa_pretrain_ext_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
+    return layout_bytes(Model::of(dims, ARCH_STANDARD));
 }
 
-bool noc_split(int type) { return type != 0; }      // blank fill SUM, word set / enwiki SPLIT
-
-// the trunk members of the noc params as an ext params struct (joint_fc / classifier stay NULL: the noc path never
-// reads them)
-vqa_pretrain_ext_params_t noc_trunk(const vqa_pretrain_noc_params_t& p) {
-    vqa_pretrain_ext_params_t e{};
-    e.wordset_map = p.wordset_map; e.l_glove = p.l_glove; e.enwiki_map = p.enwiki_map;
-    e.spat_v_linear_v = p.spat_v_linear_v; e.spat_q_linear_v = p.spat_q_linear_v; e.spat_att_score = p.spat_att_score;
-    e.gru_wg = p.gru_wg; e.gru_bg = p.gru_bg; e.gru_wc = p.gru_wc; e.gru_bc = p.gru_bc;
-    e.egru_wg = p.egru_wg; e.egru_bg = p.egru_bg; e.egru_wc = p.egru_wc; e.egru_bc = p.egru_bc;
-    e.pooled_linear_l = p.pooled_linear_l; e.q_linear_l = p.q_linear_l; e.wordset_ft = p.wordset_ft;
-    return e;
+extern "C" int vqa_pretrain_ext_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
+                                       int64_t* n_elems) {
+    return layout_tensor(Model::of(dims, ARCH_STANDARD), name, offset_bytes, n_elems);
 }
 
-// dropout of the l joint branch of the head of type t, category k (the v branch has joint_keep of the ext batch)
-KeepSrc noc_lmask(const Ctx& c, const vqa_pretrain_noc_batch_t* b, int k, int t) {
-    const vqa_pretrain_noc_kind_t& l = b->l[k];
-    return c.site(VQA_PT_KEEP_SITE_L_JOINT, t == 0 ? l.keep_bf_l_joint : t == 1 ? l.keep_ws_l_joint : l.keep_ew_l_joint,
-                  keep_of(c).l_joint_off[k][t], c.d.keep_joint, 2 * (int64_t)c.d.H);
+extern "C" int vqa_pretrain_ext_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                           const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                           int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
+    return forward(Model::of(dims, ARCH_STANDARD), view(P), view(bx), workspace, workspace_bytes, want_dz, stream, keep);
 }
 
-std::string noc_report_key(int heads, int i) {
-    const HeadSet hs(heads);
-    std::vector<std::string> keys;
-    static const char* const SUFFIX[3] = {"_loss", "_acc", "_top_5_acc"};
-    for (int k = 0; k < 2; ++k)
-        for (int r = 0; r < hs.nt; ++r) {
-            const std::string base = std::string(KIND[k]) + "_" + TASK[hs.type[r]];
-            for (const char* br : noc_split(hs.type[r]) ? std::vector<const char*>{"_v", "_l"} : std::vector<const char*>{""})
-                for (const char* suf : SUFFIX) keys.push_back(base + br + suf);
-        }
-    keys.push_back("total_loss");
-    return (i >= 0 && i < (int)keys.size()) ? keys[i] : "";
+extern "C" int vqa_pretrain_ext_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                        const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                        int want_dz, void* stream) {
+    return vqa_pretrain_ext_forward_ex(dims, P, bx, workspace, workspace_bytes, want_dz, stream, nullptr);
 }
 
-int noc_inputs_ok(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P, const vqa_pretrain_noc_batch_t* b) {
-    const vqa_pretrain_ext_params_t E = noc_trunk(*P);
-    TRY(trunk_inputs_ok(HeadSet(dims->heads), &E, &b->base));
-    VQA_REQUIRE(P->pooled_linear_l.w && P->q_linear_l.w && P->joint_v.w && P->joint_l.w && P->classifier_v.w &&
-                P->classifier_l.w, VQA_ERR_ARG);
-    return VQA_OK;
+extern "C" int vqa_pretrain_ext_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                                   const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                   void* stream, const vqa_pretrain_keep_t* keep) {
+    return backward(Model::of(dims, ARCH_STANDARD), view(P), view(G), view(bx), workspace, workspace_bytes, slice_sq, phases,
+                    stream, keep);
 }
 
-}  // namespace
-
-extern "C" const char* vqa_pretrain_noc_report_key(int heads, int i) {
-    static std::vector<std::string> keys[8];        // built once per head set; the pointers stay valid
-    static const int init = [] {
-        for (const int m : {VQA_PT_HEAD_BF | VQA_PT_HEAD_WS, VQA_PT_HEAD_BF | VQA_PT_HEAD_EW})
-            for (int i = 0; !noc_report_key(m, i).empty(); ++i) keys[m].push_back(noc_report_key(m, i));
-        return 0;
-    }();
-    (void)init;
-    if (heads < 0 || heads >= 8 || i < 0 || i >= (int)keys[heads].size()) return nullptr;
-    return keys[heads][i].c_str();
+extern "C" int vqa_pretrain_ext_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                                const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                void* stream) {
+    return vqa_pretrain_ext_backward_phases_ex(dims, P, G, bx, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
 }
+
+extern "C" int vqa_pretrain_ext_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_ext_params_t* P,
+                                         const vqa_pretrain_ext_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                         void* workspace, int64_t workspace_bytes, float* slice_sq, void* stream) {
+    return vqa_pretrain_ext_backward_phases(dims, P, G, bx, workspace, workspace_bytes, slice_sq, 15, stream);
+}
+
+// ---- vqa_pretrain_noc_*: the "no composition" architecture, heads bf | ws or bf | ew
+extern "C" const char* vqa_pretrain_noc_report_key(int heads, int i) { return report_key(ARCH_NOC, heads, i); }
 
 extern "C" int64_t vqa_pretrain_noc_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    return noc_dims_ok(dims) ? make_layout_ext(*dims, true).total : VQA_ERR_ARG;
+    return layout_bytes(Model::of(dims, ARCH_NOC));
 }
 
 extern "C" int vqa_pretrain_noc_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
                                        int64_t* n_elems) {
-    if (!noc_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    return layout_tensor(make_layout_ext(*dims, true), name, offset_bytes, n_elems);
+    return layout_tensor(Model::of(dims, ARCH_NOC), name, offset_bytes, n_elems);
+}
+
+extern "C" int vqa_pretrain_noc_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                           const vqa_pretrain_noc_batch_t* bn, void* workspace, int64_t workspace_bytes,
+                                           int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
+    return forward(Model::of(dims, ARCH_NOC), view(P), view(bn), workspace, workspace_bytes, want_dz, stream, keep);
 }
 
 extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
@@ -1145,128 +1284,19 @@ extern "C" int vqa_pretrain_noc_forward(const vqa_pretrain_ext_dims_t* dims, con
     return vqa_pretrain_noc_forward_ex(dims, P, bn, workspace, workspace_bytes, want_dz, stream, nullptr);
 }
 
-extern "C" int vqa_pretrain_noc_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
-                                           const vqa_pretrain_noc_batch_t* bn, void* workspace, int64_t workspace_bytes,
-                                           int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
-    VQA_REQUIRE(noc_dims_ok(dims) && P && bn && workspace, VQA_ERR_ARG);
-    TRY(keep_sites_ok(keep, bn->base, bn->l));
-    const Layout L = make_layout_ext(*dims, true);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    TRY(noc_inputs_ok(dims, P, bn));
-    const vqa_pretrain_dims_t* d = &dims->base;
-    const vqa_pretrain_batch_t* bt = &bn->base.base;
-    const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
-    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    ProbeScope ps_all("pretrain_noc.forward", c.st);
-    const vqa_pretrain_ext_params_t E = noc_trunk(*P);
-    TRY(ext_trunk_fwd(c, dims, &E, &bn->base, hs));
-    ReportExtArgs ra{};
-    ra.rows = (int)Bn;
-    {   // the NH heads, stacked; every branch GEMM covers all of them
-        const int64_t SJ = Bn * 2 * H, SA = Bn * A;
-        ProbeScope ps_h("pt.heads.fwd", c.st);
-        TRY(heads_in_fwd(c, hs, P->pooled_linear_l, P->q_linear_l));
-        TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/vl"), (int)H, P->joint_v.w, (int)(2 * H), c.f("S/jv_pre"),
-                          (int)(2 * H), P->joint_v.b));
-        TRY(c.gemm_routed(0, 0, NH * Bn, 2 * H, H, c.f("S/ll"), (int)H, P->joint_l.w, (int)(2 * H), c.f("S/jl_pre"),
-                          (int)(2 * H), P->joint_l.b));
-        for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, t = hs.type[h >> 1];
-            const std::string q = hs.name(h);
-            TRY(vqa_ln_act_fwd_run(c.f("S/jv_pre") + h * SJ, P->joint_v.gamma[c.li(h)], P->joint_v.beta[c.li(h)],
-                                   joint_keep(c, bn->base, k, t), c.f("S/jv") + h * SJ, c.f(q + "jv_mean"), c.f(q + "jv_rstd"),
-                                   (int)B, (int)n, (int)(2 * H), 0, c.st));
-            TRY(vqa_ln_act_fwd_run(c.f("S/jl_pre") + h * SJ, P->joint_l.gamma[c.li(h)], P->joint_l.beta[c.li(h)],
-                                   noc_lmask(c, bn, k, t), c.f("S/jl") + h * SJ, c.f(q + "jl_mean"), c.f(q + "jl_rstd"),
-                                   (int)B, (int)n, (int)(2 * H), 0, c.st));
-        }
-        TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jv"), (int)(2 * H), P->classifier_v.w, (int)A, c.f("S/zv"),
-                          (int)A, P->classifier_v.b));
-        TRY(c.gemm_routed(0, 0, NH * Bn, A, 2 * H, c.f("S/jl"), (int)(2 * H), P->classifier_l.w, (int)A, c.f("S/zl"),
-                          (int)A, P->classifier_l.b));
-        // every head's loss in one launch; the report reads the stats blocks in key order
-        vqa_softmax_pair_t pr[VQA_SOFTMAX_PAIR_MAX] = {};
-        const float* st_by_key[2][3][2] = {};
-        for (int h = 0; h < NH; ++h) {
-            const int k = h & 1, r = h >> 1;
-            const std::string p = std::string(KIND[k]) + "/";
-            vqa_softmax_pair_t& e = pr[h];
-            e.zv = c.f("S/zv") + h * SA; e.zl = c.f("S/zl") + h * SA;
-            e.label = bt->kind[k].fills; e.valid = c.f(p + "valid"); e.inv_valid_sum = c.f(p + "inv_valid");
-            e.split = noc_split(hs.type[r]) ? 1 : 0;
-            e.stats_v = c.f("S/stats") + h * Bn * 4; e.stats_l = c.f("S/stats_l") + h * Bn * 4;
-            e.dzv = want_dz ? c.f("S/dzv") + h * SA : nullptr; e.dzl = want_dz ? c.f("S/dzl") + h * SA : nullptr;
-            st_by_key[k][r][0] = e.stats_v;
-            st_by_key[k][r][1] = e.split ? e.stats_l : nullptr;
-        }
-        TRY(vqa_softmax_ce_pair_fwd(pr, (int)NH, 5, (int)Bn, (int)A, c.st));
-        for (int k = 0; k < 2; ++k)
-            for (int r = 0; r < hs.nt; ++r)
-                for (int br = 0; br < 2; ++br)
-                    if (st_by_key[k][r][br] != nullptr) {
-                        ra.stats[ra.nh] = st_by_key[k][r][br];
-                        ra.inv[ra.nh++] = c.f(std::string(KIND[k]) + "/inv_valid");
-                    }
-    }
-    hipLaunchKernelGGL(pretrain_ext_report_kernel, dim3(1), dim3(256), 0, c.st, ra, c.f("report"));
-    VQA_CHECK_LAUNCH();
-    return VQA_OK;
+extern "C" int vqa_pretrain_noc_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
+                                                   const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
+                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                   void* stream, const vqa_pretrain_keep_t* keep) {
+    return backward(Model::of(dims, ARCH_NOC), view(P), view(G), view(bn), workspace, workspace_bytes, slice_sq, phases,
+                    stream, keep);
 }
 
-// Backward phases of the noc models: phase 1 the stacked heads (both classifiers, both joint branches, pooled_linear_l,
-// q_linear_l); 2, 4, 8 the trunk as vqa_pretrain_ext_backward_phases
 extern "C" int vqa_pretrain_noc_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
                                                 const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
                                                 void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                                 void* stream) {
     return vqa_pretrain_noc_backward_phases_ex(dims, P, G, bn, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
-}
-
-extern "C" int vqa_pretrain_noc_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
-                                                   const vqa_pretrain_noc_params_t* G, const vqa_pretrain_noc_batch_t* bn,
-                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                                   void* stream, const vqa_pretrain_keep_t* keep) {
-    VQA_REQUIRE(noc_dims_ok(dims) && P && G && bn && workspace, VQA_ERR_ARG);
-    TRY(keep_sites_ok(keep, bn->base, bn->l));
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims, true);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    const vqa_pretrain_dims_t* d = &dims->base;
-    const HeadSet hs(dims->heads);
-    const Ctx c{*d, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
-    const int64_t B = d->B, n = d->n, H = d->H, A = d->A, Bn = B * n, NH = hs.nh();
-    ProbeScope ps_all("pretrain_noc.backward", c.st);
-    Acc acc{c, {}};
-    if (phases & 1) {
-        ProbeScope ps_h("pt.heads.bwd", c.st);
-        const int64_t SJ = Bn * 2 * H;
-        // per branch: classifier dW / db / dx, each head's joint LayerNorm, the joint dW / db and dx into d_vl / d_ll
-        struct Branch { const char *j, *dz, *dj, *jpre, *djpre, *in, *din, *tag; const vqa_pt_fc6_t *cP, *cG, *jP, *jG; };
-        const Branch br[2] = {
-            {"S/jv", "S/dzv", "d_jv", "S/jv_pre", "d_jvpre", "S/vl", "d_vl", "jv", &P->classifier_v, &G->classifier_v,
-             &P->joint_v, &G->joint_v},
-            {"S/jl", "S/dzl", "d_jl", "S/jl_pre", "d_jlpre", "S/ll", "d_ll", "jl", &P->classifier_l, &G->classifier_l,
-             &P->joint_l, &G->joint_l}};
-        for (int v = 0; v < 2; ++v) {
-            const Branch& b = br[v];
-            TRY(acc.weight(PREC_ROUTED, b.cG->w, c.f(b.j), (int)(2 * H), c.f(b.dz), (int)A, 2 * H, A, NH * Bn));
-            TRY(acc.colsum(c.f(b.dz), NH * Bn, A, (int)A, b.cG->b));
-            TRY(c.gemm_routed(0, 1, NH * Bn, 2 * H, A, c.f(b.dz), (int)A, b.cP->w, (int)A, c.f(b.dj), (int)(2 * H)));
-            for (int h = 0; h < NH; ++h) {
-                const int k = h & 1, t = hs.type[h >> 1];
-                const std::string q = hs.name(h) + b.tag;
-                TRY(ln_bwd(c, acc, c.f(b.dj) + h * SJ, Bn, 2 * H, *b.jP, *b.jG, c.li(h), (int)n, 0,
-                             c.f(b.jpre) + h * SJ, c.f(q + "_mean"), c.f(q + "_rstd"),
-                             v == 0 ? joint_keep(c, bn->base, k, t) : noc_lmask(c, bn, k, t), c.f(b.djpre) + h * SJ));
-            }
-            TRY(fc_bwd(c, acc, PREC_ROUTED, b.djpre, c.f(b.in), NH * Bn, H, 2 * H, *b.jP, *b.jG, c.f(b.din)));
-        }
-        TRY(heads_in_bwd(c, acc, hs, P->pooled_linear_l, P->q_linear_l, G->pooled_linear_l, G->q_linear_l));
-    }
-    const vqa_pretrain_ext_params_t EP = noc_trunk(*P), EG = noc_trunk(*G);
-    return ext_trunk_bwd(c, acc, dims, &EP, &EG, &bn->base, hs, slice_sq, phases);
 }
 
 extern "C" int vqa_pretrain_noc_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_noc_params_t* P,
@@ -1275,29 +1305,23 @@ extern "C" int vqa_pretrain_noc_backward(const vqa_pretrain_ext_dims_t* dims, co
     return vqa_pretrain_noc_backward_phases(dims, P, G, bn, workspace, workspace_bytes, slice_sq, 15, stream);
 }
 
-// ================================================================ pre-training with the adapted memory
-// vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py (bf | ws): the variable-head-set model with the v_adapt layer
-// (:346-350, :442-446) between the features and the attention pooling (:365-367, :461-463); see v_adapt_fwd / v_adapt_bwd.
-namespace {
-
-bool adapt_dims_ok(const vqa_pretrain_ext_dims_t* d) {
-    return ext_dims_ok(d) && d->heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS);
-}
-
-}  // namespace
-
-extern "C" const char* vqa_pretrain_adapt_report_key(int heads, int i) {
-    return heads == (VQA_PT_HEAD_BF | VQA_PT_HEAD_WS) ? vqa_pretrain_ext_report_key(heads, i) : nullptr;
-}
+// ---- vqa_pretrain_adapt_*: vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp_adapt.py (bf | ws), the v_adapt layer (:346-350,
+// :442-446) between the features and the attention pooling (:365-367, :461-463)
+extern "C" const char* vqa_pretrain_adapt_report_key(int heads, int i) { return report_key(ARCH_ADAPT, heads, i); }
 
 extern "C" int64_t vqa_pretrain_adapt_workspace_bytes(const vqa_pretrain_ext_dims_t* dims) {
-    return adapt_dims_ok(dims) ? make_layout_ext(*dims, false, true).total : VQA_ERR_ARG;
+    return layout_bytes(Model::of(dims, ARCH_ADAPT));
 }
 
 extern "C" int vqa_pretrain_adapt_tensor(const vqa_pretrain_ext_dims_t* dims, const char* name, int64_t* offset_bytes,
                                          int64_t* n_elems) {
-    if (!adapt_dims_ok(dims) || name == nullptr) return VQA_ERR_ARG;
-    return layout_tensor(make_layout_ext(*dims, false, true), name, offset_bytes, n_elems);
+    return layout_tensor(Model::of(dims, ARCH_ADAPT), name, offset_bytes, n_elems);
+}
+
+extern "C" int vqa_pretrain_adapt_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                             const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
+                                             int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
+    return forward(Model::of(dims, ARCH_ADAPT), view(P), view(bx), workspace, workspace_bytes, want_dz, stream, keep);
 }
 
 extern "C" int vqa_pretrain_adapt_forward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
@@ -1306,18 +1330,12 @@ extern "C" int vqa_pretrain_adapt_forward(const vqa_pretrain_ext_dims_t* dims, c
     return vqa_pretrain_adapt_forward_ex(dims, P, bx, workspace, workspace_bytes, want_dz, stream, nullptr);
 }
 
-extern "C" int vqa_pretrain_adapt_forward_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
-                                             const vqa_pretrain_ext_batch_t* bx, void* workspace, int64_t workspace_bytes,
-                                             int want_dz, void* stream, const vqa_pretrain_keep_t* keep) {
-    VQA_REQUIRE(adapt_dims_ok(dims) && P && bx && workspace, VQA_ERR_ARG);
-    TRY(keep_sites_ok(keep, *bx, nullptr));
-    const bool ln_shared = (dims->base.flags & VQA_FLAG_SHARED_LN) != 0;
-    VQA_REQUIRE(P->v_adapt.w && P->v_adapt.b && P->v_adapt.gamma[0] && P->v_adapt.beta[0] &&
-                (ln_shared || (P->v_adapt.gamma[1] && P->v_adapt.beta[1])), VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims, false, true);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    VQA_REQUIRE(vqa_aligned16(workspace), VQA_ERR_ALIGN);
-    return ext_forward_impl(L, dims, &P->ext, bx, workspace, want_dz, stream, &P->v_adapt, keep);
+extern "C" int vqa_pretrain_adapt_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
+                                                     const vqa_pretrain_adapt_params_t* G, const vqa_pretrain_ext_batch_t* bx,
+                                                     void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
+                                                     void* stream, const vqa_pretrain_keep_t* keep) {
+    return backward(Model::of(dims, ARCH_ADAPT), view(P), view(G), view(bx), workspace, workspace_bytes, slice_sq, phases,
+                    stream, keep);
 }
 
 extern "C" int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
@@ -1325,22 +1343,6 @@ extern "C" int vqa_pretrain_adapt_backward_phases(const vqa_pretrain_ext_dims_t*
                                                   void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
                                                   void* stream) {
     return vqa_pretrain_adapt_backward_phases_ex(dims, P, G, bx, workspace, workspace_bytes, slice_sq, phases, stream, nullptr);
-}
-
-extern "C" int vqa_pretrain_adapt_backward_phases_ex(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,
-                                                     const vqa_pretrain_adapt_params_t* G, const vqa_pretrain_ext_batch_t* bx,
-                                                     void* workspace, int64_t workspace_bytes, float* slice_sq, int phases,
-                                                     void* stream, const vqa_pretrain_keep_t* keep) {
-    VQA_REQUIRE(adapt_dims_ok(dims) && P && G && bx && workspace, VQA_ERR_ARG);
-    TRY(keep_sites_ok(keep, *bx, nullptr));
-    VQA_REQUIRE(phases > 0 && phases < 16, VQA_ERR_ARG);
-    const bool ln_shared = (dims->base.flags & VQA_FLAG_SHARED_LN) != 0;
-    VQA_REQUIRE(G->v_adapt.w && G->v_adapt.b && G->v_adapt.gamma[0] && G->v_adapt.beta[0] &&
-                (ln_shared || (G->v_adapt.gamma[1] && G->v_adapt.beta[1])), VQA_ERR_ARG);
-    const Layout L = make_layout_ext(*dims, false, true);
-    VQA_REQUIRE(workspace_bytes >= L.total, VQA_ERR_WORKSPACE);
-    return ext_backward_impl(L, dims, &P->ext, &G->ext, bx, workspace, slice_sq, phases, stream, &P->v_adapt, &G->v_adapt,
-                             keep);
 }
 
 extern "C" int vqa_pretrain_adapt_backward(const vqa_pretrain_ext_dims_t* dims, const vqa_pretrain_adapt_params_t* P,

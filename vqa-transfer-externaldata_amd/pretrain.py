@@ -168,40 +168,64 @@ def init_random_params(rng, Vq, n_ws, A, W=300, D=2048, H=1024, ln_shared=True, 
     return p
 
 
+def _length_sort(batch, len_key, tok_key):
+    """{'perm', 'inv', 'live_rows'} over the 2*B*n rows of both categories (object rows first), ordered by the lengths
+    '<kind>_blank_fill/<len_key>' (longest first); live_rows[t] = #rows longer than t, t below the padded length of
+    '<kind>_blank_fill/<tok_key>'.  None when the batch does not carry the lengths as host arrays."""
+    keys = [k + "_blank_fill/" + len_key for k in KINDS]
+    if any(k not in batch or torch.is_tensor(batch[k]) for k in keys):
+        return None
+    lens = np.concatenate([np.asarray(batch[k]).reshape(-1) for k in keys]).astype(np.int64)
+    L = int(np.asarray(batch[KINDS[0] + "_blank_fill/" + tok_key]).shape[-1])
+    perm = np.argsort(-lens, kind="stable")
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    sl = np.clip(lens[perm], 0, L)
+    return {"perm": perm, "inv": inv, "live_rows": (sl[None, :] > np.arange(L)[:, None]).sum(1).astype(np.int32)}
+
+
 def add_length_sort(batch):
     """Host-side: the blank-fill captions of both categories are encoded as ONE batch of 2*B*n rows (object rows first).
     This adds 'blank_fill/sort' = the permutation that orders those rows by length (longest first), its inverse and
     live_rows[t] = #captions longer than t.  The engine then embeds / encodes the captions in that order, runs every GRU
     step on the live prefix only, and un-permutes the final states."""
-    keys = [k + "_blank_fill/blanks_len" for k in KINDS]
-    if any(k not in batch or torch.is_tensor(batch[k]) for k in keys):
+    srt = _length_sort(batch, "blanks_len", "blanks")
+    if srt is None:
         return batch
-    lens = np.concatenate([np.asarray(batch[k]).reshape(-1) for k in keys]).astype(np.int64)
-    L = int(np.asarray(batch[KINDS[0] + "_blank_fill/blanks"]).shape[-1])
-    perm = np.argsort(-lens, kind="stable")
-    inv = np.empty_like(perm)
-    inv[perm] = np.arange(len(perm))
-    sl = np.clip(lens[perm], 0, L)
-    batch["blank_fill/sort"] = {"perm": perm, "inv": inv,
-                                "live_rows": (sl[None, :] > np.arange(L)[:, None]).sum(1).astype(np.int32)}
+    batch["blank_fill/sort"] = srt
     return add_context_sort(batch)
 
 
 def add_context_sort(batch):
     """The enwiki contexts of both categories the same way: 'enwiki_context/sort' = permutation (longest first), inverse
     and live_rows over the 2*B*n context rows, so that encode_L_enwiki also runs on the live prefix only."""
-    keys = [k + "_blank_fill/enwiki_context_len" for k in KINDS]
-    if any(k not in batch or torch.is_tensor(batch[k]) for k in keys):
-        return batch
-    lens = np.concatenate([np.asarray(batch[k]).reshape(-1) for k in keys]).astype(np.int64)
-    Lc = int(np.asarray(batch[KINDS[0] + "_blank_fill/enwiki_context"]).shape[-1])
-    perm = np.argsort(-lens, kind="stable")
-    inv = np.empty_like(perm)
-    inv[perm] = np.arange(len(perm))
-    sl = np.clip(lens[perm], 0, Lc)
-    batch["enwiki_context/sort"] = {"perm": perm, "inv": inv,
-                                    "live_rows": (sl[None, :] > np.arange(Lc)[:, None]).sum(1).astype(np.int32)}
+    srt = _length_sort(batch, "enwiki_context_len", "enwiki_context")
+    if srt is not None:
+        batch["enwiki_context/sort"] = srt
     return batch
+
+
+# The C parameter structs: per struct type its members as (member, source).  A source is a variable name (a plain
+# pointer), (scope, LayerNorm slots) for an fc_layer scope ("nh": one slot per head), or a nested struct type.  A table
+# that lacks a variable is a KeyError, except for the members only some head sets have (_OPTIONAL: NULL then).
+_GRU, _EGRU = "encode_L_blank/rnn/gru_cell/", "encode_L_enwiki/rnn/gru_cell/"
+_TRUNK = (("wordset_map", "wordset_map/learn"), ("l_glove", "L_GloVe/embed_map"),
+          ("spat_v_linear_v", ("spat_v_linear_v", 2)), ("spat_q_linear_v", ("spat_q_linear_v", 2)),
+          ("spat_att_score", ("spat_att/compute/score", 0)),
+          ("gru_wg", _GRU + "gates/kernel"), ("gru_bg", _GRU + "gates/bias"),
+          ("gru_wc", _GRU + "candidate/kernel"), ("gru_bc", _GRU + "candidate/bias"),
+          ("pooled_linear_l", ("pooled_linear_l", "nh")), ("q_linear_l", ("q_linear_l", "nh")),
+          ("wordset_ft", ("wordset_ft", 2)))
+_ENWIKI = (("enwiki_map", "enwiki_map/learn"), ("egru_wg", _EGRU + "gates/kernel"), ("egru_bg", _EGRU + "gates/bias"),
+           ("egru_wc", _EGRU + "candidate/kernel"), ("egru_bc", _EGRU + "candidate/bias"))
+_HEADS = (("joint_fc", ("joint_fc", "nh")), ("classifier", ("classifier", 0)))
+_NOC_HEADS = (("joint_v", ("joint_v", "nh")), ("joint_l", ("joint_l", "nh")),
+              ("classifier_v", ("classifier_v", 0)), ("classifier_l", ("classifier_l", 0)))
+_OPTIONAL = ("wordset_ft",) + tuple(m for m, _ in _ENWIKI)      # without the word-set head / without the enwiki head
+PARAM_FIELDS = {_lib.PtParams: _TRUNK + _HEADS,
+                _lib.PtExtParams: _TRUNK + _ENWIKI + _HEADS,
+                _lib.PtNocParams: _TRUNK + _ENWIKI + _NOC_HEADS,
+                _lib.PtAdaptParams: (("ext", _lib.PtExtParams), ("v_adapt", ("v_adapt", 2)))}
 
 
 PRECISIONS = ("f32", "bf16")      # PretrainEngine(precision=...): "bf16" sets VQA_FLAG_BF16_GEMM
@@ -355,67 +379,31 @@ class PretrainEngine:
                     ks.seeded |= _lib.PT_KEEP_SITE["l_joint"]
         return ks
 
-    def _param_struct(self, table):
-        if self.noc:
-            return self._param_struct_noc(table)
-        if self.adapt:
-            return _lib.PtAdaptParams(ext=self._param_struct_ext(table), v_adapt=self._fc6(table)("v_adapt", 2))
-        if self.ext:
-            return self._param_struct_ext(table)
+    def _param_struct(self, table, struct=None):
+        """The C struct `struct` (default: the one this engine's entry points take) filled from the name -> tensor
+        `table` by PARAM_FIELDS; an _OPTIONAL member the table lacks stays NULL, any other missing variable raises."""
+        struct = struct or {"vqa_pretrain_": _lib.PtParams, "vqa_pretrain_ext_": _lib.PtExtParams,
+                            "vqa_pretrain_noc_": _lib.PtNocParams, "vqa_pretrain_adapt_": _lib.PtAdaptParams}[self._abi]
+        types = dict(struct._fields_)
 
-        def fc(scope, n_ln):
-            f = _lib.PtFc(w=table[scope + "/fc/weights"].data_ptr(), b=table[scope + "/fc/biases"].data_ptr())
-            for i in range(min(n_ln, 1) if self.ln_shared else n_ln):
-                f.beta[i] = table[ln_name(scope, i) + "/beta"].data_ptr()
-                f.gamma[i] = table[ln_name(scope, i) + "/gamma"].data_ptr()
-            return f
-        g = "encode_L_blank/rnn/gru_cell/"
-        return _lib.PtParams(
-            wordset_map=table["wordset_map/learn"].data_ptr(), l_glove=table["L_GloVe/embed_map"].data_ptr(),
-            spat_v_linear_v=fc("spat_v_linear_v", 2), spat_q_linear_v=fc("spat_q_linear_v", 2),
-            spat_att_score=fc("spat_att/compute/score", 0), gru_wg=table[g + "gates/kernel"].data_ptr(),
-            gru_bg=table[g + "gates/bias"].data_ptr(), gru_wc=table[g + "candidate/kernel"].data_ptr(),
-            gru_bc=table[g + "candidate/bias"].data_ptr(), pooled_linear_l=fc("pooled_linear_l", 4),
-            q_linear_l=fc("q_linear_l", 4), joint_fc=fc("joint_fc", 4), wordset_ft=fc("wordset_ft", 2),
-            classifier=fc("classifier", 0))
-
-    def _fc6(self, table):
-        def fc(scope, n_ln):
-            f = _lib.PtFc6()
-            if scope + "/fc/weights" not in table:       # e.g. wordset_ft of a model without the word-set head
-                return f
+        def fc(f, scope, n_ln):
             f.w, f.b = table[scope + "/fc/weights"].data_ptr(), table[scope + "/fc/biases"].data_ptr()
+            n_ln = 2 * len(self.heads) if n_ln == "nh" else n_ln
             for i in range(min(n_ln, 1) if self.ln_shared else n_ln):
                 f.beta[i] = table[ln_name(scope, i) + "/beta"].data_ptr()
                 f.gamma[i] = table[ln_name(scope, i) + "/gamma"].data_ptr()
             return f
-        return fc
-
-    def _param_struct_ext(self, table):
-        nh = 2 * len(self.heads)
-        fc = self._fc6(table)
-        ptr = lambda k: table[k].data_ptr() if k in table else None      # the enwiki variables exist with 'ew' only
-        g, e = "encode_L_blank/rnn/gru_cell/", "encode_L_enwiki/rnn/gru_cell/"
-        return _lib.PtExtParams(
-            wordset_map=table["wordset_map/learn"].data_ptr(), l_glove=table["L_GloVe/embed_map"].data_ptr(),
-            enwiki_map=ptr("enwiki_map/learn"),
-            spat_v_linear_v=fc("spat_v_linear_v", 2), spat_q_linear_v=fc("spat_q_linear_v", 2),
-            spat_att_score=fc("spat_att/compute/score", 0), gru_wg=table[g + "gates/kernel"].data_ptr(),
-            gru_bg=table[g + "gates/bias"].data_ptr(), gru_wc=table[g + "candidate/kernel"].data_ptr(),
-            gru_bc=table[g + "candidate/bias"].data_ptr(), egru_wg=ptr(e + "gates/kernel"),
-            egru_bg=ptr(e + "gates/bias"), egru_wc=ptr(e + "candidate/kernel"),
-            egru_bc=ptr(e + "candidate/bias"), pooled_linear_l=fc("pooled_linear_l", nh),
-            q_linear_l=fc("q_linear_l", nh), joint_fc=fc("joint_fc", nh), wordset_ft=fc("wordset_ft", 2),
-            classifier=fc("classifier", 0))
-
-    def _param_struct_noc(self, table):
-        """the ext struct's trunk members (joint_fc / classifier dropped) plus the two branches' scopes"""
-        ext = self._param_struct_ext(table)
-        nh = 2 * len(self.heads)
-        f = {name: getattr(ext, name) for name, _ in _lib.PtExtParams._fields_ if name not in ("joint_fc", "classifier")}
-        fc = self._fc6(table)
-        return _lib.PtNocParams(joint_v=fc("joint_v", nh), joint_l=fc("joint_l", nh), classifier_v=fc("classifier_v", 0),
-                                classifier_l=fc("classifier_l", 0), **f)
+        out = struct()
+        for member, src in PARAM_FIELDS[struct]:
+            if member in _OPTIONAL and (src[0] + "/fc/weights" if isinstance(src, tuple) else src) not in table:
+                continue
+            if isinstance(src, tuple):
+                setattr(out, member, fc(types[member](), *src))
+            elif isinstance(src, str):
+                setattr(out, member, table[src].data_ptr())
+            else:
+                setattr(out, member, self._param_struct(table, src))
+        return out
 
     def _dev(self, v, dtype):
         t = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
@@ -453,6 +441,22 @@ class PretrainEngine:
                 cache[key] = self._dev(batch[key], dtype)
             return cache[key]
         keep = [cache, masks]
+
+        def sort_ptrs(key, length):
+            """(perm, inv, live_rows) pointers of the rows' length order batch[key] (add_length_sort), or three NULLs;
+            uploaded once and cached on the sort dict"""
+            srt = batch.get(key)
+            if srt is None:
+                return None, None, None
+            if "_dev" not in srt:
+                live = np.ascontiguousarray(srt["live_rows"], dtype=np.int32)
+                assert live.shape == (length,) and \
+                    len(srt["perm"]) == 2 * int(cache[KINDS[0] + "_blank_fill/blanks_len"].numel())
+                srt["_dev"] = (self._dev(np.asarray(srt["perm"]), torch.int32),
+                               self._dev(np.asarray(srt["inv"]), torch.int32), live)
+            perm, inv, live = srt["_dev"]
+            keep.append(srt["_dev"])
+            return perm.data_ptr(), inv.data_ptr(), live.ctypes.data
         if "image_idx" in batch and "image_ft" not in batch:
             if getattr(self, "_tables", None) is None:
                 raise ValueError("batch carries image_idx but no feature tables are bound (PretrainEngine.bind_tables)")
@@ -479,16 +483,8 @@ class PretrainEngine:
                 kb.keep_att = masks[k + "/att"].data_ptr()
                 kb.keep_bf_joint = masks[k + "/bf_joint"].data_ptr()
                 kb.keep_ws_joint = masks[k + "/ws_joint"].data_ptr()
-        srt = batch.get("blank_fill/sort")
-        if srt is not None:       # captions in length order: the recurrence skips finished ones (add_length_sort)
-            if "_dev" not in srt:
-                live = np.ascontiguousarray(srt["live_rows"], dtype=np.int32)
-                assert live.shape == (L,) and len(srt["perm"]) == 2 * int(cache[KINDS[0] + "_blank_fill/blanks_len"].numel())
-                srt["_dev"] = (self._dev(np.asarray(srt["perm"]), torch.int32),
-                               self._dev(np.asarray(srt["inv"]), torch.int32), live)
-            perm, inv, live = srt["_dev"]
-            bs.perm, bs.inv, bs.live_rows = perm.data_ptr(), inv.data_ptr(), live.ctypes.data
-            keep.append(srt["_dev"])
+        # captions in length order: the recurrence skips finished ones
+        bs.perm, bs.inv, bs.live_rows = sort_ptrs("blank_fill/sort", L)
         if not self.ext:
             return bs, B, L, keep
         bx = _lib.PtExtBatch(base=bs)
@@ -503,16 +499,7 @@ class PretrainEngine:
             Lc = Lk
             if masks is not None:
                 ck.keep_ew_joint = masks[k + "/ew_joint"].data_ptr()
-        srt = batch.get("enwiki_context/sort")
-        if srt is not None:       # contexts in length order (add_context_sort)
-            if "_dev" not in srt:
-                live = np.ascontiguousarray(srt["live_rows"], dtype=np.int32)
-                assert live.shape == (Lc,) and len(srt["perm"]) == 2 * int(cache[KINDS[0] + "_blank_fill/blanks_len"].numel())
-                srt["_dev"] = (self._dev(np.asarray(srt["perm"]), torch.int32),
-                               self._dev(np.asarray(srt["inv"]), torch.int32), live)
-            perm, inv, live = srt["_dev"]
-            bx.ctx_perm, bx.ctx_inv, bx.ctx_live_rows = perm.data_ptr(), inv.data_ptr(), live.ctypes.data
-            keep.append(srt["_dev"])
+        bx.ctx_perm, bx.ctx_inv, bx.ctx_live_rows = sort_ptrs("enwiki_context/sort", Lc)      # add_context_sort
         self._Lc = Lc
         if not self.noc:
             return bx, B, L, keep
@@ -608,13 +595,8 @@ class PretrainEngine:
 
     def report_key(self, i):
         """name of report scalar i (vqa_pretrain_report_key / vqa_pretrain_ext_report_key)"""
-        if self.noc:
-            return self.lib.vqa_pretrain_noc_report_key(head_mask(self.heads), i).decode()
-        if self.adapt:
-            return self.lib.vqa_pretrain_adapt_report_key(head_mask(self.heads), i).decode()
-        if self.ext:
-            return self.lib.vqa_pretrain_ext_report_key(head_mask(self.heads), i).decode()
-        return self.lib.vqa_pretrain_report_key(i).decode()
+        fn = getattr(self.lib, self._abi + "report_key")
+        return (fn(head_mask(self.heads), i) if self.ext else fn(i)).decode()      # cfg-5's takes no head set
 
     def _backward_phases(self, phases):
         tail = self.grad_flat[self.n_train:]

@@ -383,8 +383,10 @@ int vqa_colsum_vtail(const float* X0, const float* X1, const float* X2, const fl
 /* --------------------------------------------------------------- a11 / K11
  * sigmoid-CE loss, argmax, VQA scores (vqa/model_vlmap_answer.py:192-288).
  * Per sample stats[b, VQA_STAT_*]; dz = (sigmoid(z)-t)*(loss_mask?)/B_norm when
- * dz != NULL.  masks are float [A]; loss_mask = train mask for vlmap_answer,
- * NULL for model_standard (vqa/model_standard.py:285). */
+ * dz != NULL.  masks are float [A] of 0 / 1; loss_mask = train mask for vlmap_answer,
+ * NULL for model_standard (vqa/model_standard.py:285).  pred = the FIRST maximum of the row (tf.argmax); the score
+ * statistics are target[pred] times the masks at pred, the *_MAX statistics max_a target * masks (0, not -inf, under
+ * an all-zero mask); stats[b, 15] = 0. */
 enum {
     VQA_STAT_LOSS_TRAIN = 0, VQA_STAT_LOSS_REPORT, VQA_STAT_ALL_SCORE, VQA_STAT_EXIST_SCORE,
     VQA_STAT_TEST_SCORE, VQA_STAT_TEST_OBJ_SCORE, VQA_STAT_TEST_ATTR_SCORE, VQA_STAT_TRAIN_EXIST_SCORE,
@@ -413,7 +415,10 @@ int vqa_rowmin_mask_bwd(float* dz, const float* z, const float* rowmin, const fl
 /* n-way softmax cross-entropy with a validity mask + top-1 / top-k hits (n_way_classification_loss,
  * vlmap_memft/model_vlmap_bf_or_wordset_withatt_sp.py:675-706).  z [rows,A], label i32[rows], valid f32[rows];
  * stats [rows,4] = {ce*valid, top1*valid, topk*valid, valid}; dz = (softmax-onehot)*valid*inv_valid_sum[0]
- * (inv_valid_sum is a DEVICE scalar = 1/sum(valid); dz may be NULL). */
+ * (inv_valid_sum is a DEVICE scalar = 1/sum(valid); dz may be NULL).  top1 = the FIRST maximum is the label; topk =
+ * fewer than topk entries are larger than the label's logit or equal to it at a lower index (tf.nn.top_k's order), so
+ * topk >= A is always a hit.  softmax = exp((z - max) - log sum exp(z - max)): a row shifted by a constant keeps its dz.
+ * label must lie in [0, A): the kernels clamp the read of its logit and define nothing else for a label outside. */
 int vqa_softmax_ce_fwd(const float* z, const int32_t* label, const float* valid, int topk,
                        const float* inv_valid_sum, float* stats, float* dz, int rows, int A, void* stream);
 /* tuning / A-B switch: 1 (default) = rows of A <= 4096 (A % 4 == 0, 16-byte aligned) are held in registers and read

@@ -40,9 +40,6 @@ ALLOWED = {
     "vqa_gemm_shortk_nn": "ops.gemm_shortk, test_gpu_ops.py::test_shortk_gemm_matches_float64",
     "vqa_gru_fill_finished": "vqa_gru_seq_fwd_live's finished rows, test_gpu_gru_f64.py (form live)",
     "vqa_gru_zero_finished": "vqa_gru_seq_bwd_live's finished rows, test_gpu_gru_f64.py (form live: dxp exactly 0)",
-    "vqa_loss2_fwd": "two-headed loss, test_gpu_fusion.py::test_vqa_all2_two_heads_and_dead_branch",
-    "vqa_rowmin_mask_fwd": "test_gpu_fusion.py::test_vqa_all_row_minimum_substitution_on_the_gpu",
-    "vqa_rowmin_mask_bwd": "test_gpu_fusion.py::test_vqa_all_row_minimum_substitution_on_the_gpu",
 }
 
 # the kernels tests/test_gpu_rowops_f64.py pins to a float64 reference: they must stay named THERE
@@ -65,6 +62,10 @@ GEMM = ["gemm_f32", "gemm_f32_ex", "gemm_f32_gather", "gemm_set_config", "gemm_s
 # the f32 extractor entry points and knobs tests/test_gpu_conv_f64.py pins to the float64 reference of tests/conv_ref.py, route by route
 CONV = ["conv2d_nhwc", "conv2d_nhwc_bwd", "conv2d_bwd_workspace_floats", "conv_set_config", "pad_c3c4_nhwc",
         "maxpool3x3s2_same_nhwc", "subsample_nhwc", "crop_and_resize_nhwc"]
+
+# the loss heads and the paired LayerNorm tests/test_gpu_loss_f64.py pins to the float64 references of tests/loss_ref.py, route by route
+LOSS = ["loss_fwd", "loss2_fwd", "rowmin_mask_fwd", "rowmin_mask_bwd", "softmax_ce_fwd", "softmax_ce_pair_fwd",
+        "softmax_set_fast", "ln_pair_mul_fwd", "ln_pair_mul_bwd", "ln_pair_mul_supported"]
 
 
 def _declared(repo_root):
@@ -127,3 +128,14 @@ def test_the_f32_extractor_kernels_stay_pinned_by_their_float64_test(repo_root):
     assert not set("vqa_" + k for k in CONV) & set(ALLOWED)
     declared = set(_declared(repo_root))
     assert all("vqa_" + k in declared for k in CONV)
+
+
+def test_the_loss_heads_and_the_paired_layernorm_stay_pinned_by_their_float64_test(repo_root):
+    text = open(os.path.join(repo_root, "tests", "test_gpu_loss_f64.py")).read()
+    calls = set(re.findall(r"\"(vqa_[a-z0-9_]+)\"", text)) | set(re.findall(r"\blib\.(vqa_[a-z0-9_]+)\(", text))
+    missing = ["vqa_" + k for k in LOSS if "vqa_" + k not in calls]
+    assert not missing, "tests/test_gpu_loss_f64.py no longer calls %s" % missing
+    assert "vqa_report_reduce" in calls and "loss_ref" in text
+    assert not set("vqa_" + k for k in LOSS) & set(ALLOWED)
+    declared = set(_declared(repo_root))
+    assert all("vqa_" + k in declared for k in LOSS)

@@ -230,11 +230,13 @@ __device__ __forceinline__ void softmax_ce_row(const Row zr, int lab, float vm, 
     float se = 0.f;
     for (int a = threadIdx.x; a < A; a += 256) se += expf(zr.at(a) - mx);
     se = block_sum(se, red);
-    const float lse = mx + logf(se);
+    const float lg = logf(se), lse = mx + lg;
     if (dz != nullptr) {
+        // softmax = exp((z - mx) - log(se)), not exp(z - lse): rounding lse = mx + log(se) costs |lse| 2^-24 in the exponent,
+        // which a row far from 0 (all logits near 1000) or a wide one turns into a relative error of that size
         const float sc = vm * inv_valid_sum[0];
         for (int a = threadIdx.x; a < A; a += 256) {
-            const float g = (expf(zr.at(a) - lse) - (a == lab ? 1.f : 0.f)) * sc;
+            const float g = (expf((zr.at(a) - mx) - lg) - (a == lab ? 1.f : 0.f)) * sc;
             dz[a] = g;
             if (dz2 != nullptr) dz2[a] = g;
         }
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
 // The same with the row held in registers (A <= 4096, A % 4 == 0, 16-byte aligned rows): thread t owns the float4s
 // t, t+256, ... (NV of them), so the logits are read ONCE with 16-byte loads, all of a thread's loads in flight
 // together, instead of three dependent scalar passes over the row, and dz leaves as 16-byte stores.  Same arithmetic per
-// element as softmax_ce_row (exp(z - lse) for dz); only the order of the sum of exponentials differs.
+// element as softmax_ce_row (exp((z - mx) - log(se)) for dz); only the order of the sum of exponentials differs.
 template <int NV, class Row>
 __device__ __forceinline__ void softmax_ce_row_reg(const Row zr, int lab, float vm, int topk,
                                                    const float* __restrict__ inv_valid_sum, float* __restrict__ s,
@@ -307,7 +309,7 @@ __device__ __forceinline__ void softmax_ce_row_reg(const Row zr, int lab, float 
 #pragma unroll
         for (int j = 0; j < 4; ++j) se += expf(x[k][j] - mx);     // exp(-inf) = 0 for the padding
     se = block_sum(se, red);
-    const float lse = mx + logf(se);
+    const float lg = logf(se), lse = mx + lg;
     if (dz != nullptr) {
         const float sc = vm * inv_valid_sum[0];
 #pragma unroll
@@ -316,7 +318,7 @@ __device__ __forceinline__ void softmax_ce_row_reg(const Row zr, int lab, float 
             if (i < A4) {
                 float o[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (expf(x[k][j] - lse) - (4 * i + j == lab ? 1.f : 0.f)) * sc;
+                for (int j = 0; j < 4; ++j) o[j] = (expf((x[k][j] - mx) - lg) - (4 * i + j == lab ? 1.f : 0.f)) * sc;
                 reinterpret_cast<float4*>(dz)[i] = make_float4(o[0], o[1], o[2], o[3]);
                 if (dz2 != nullptr) reinterpret_cast<float4*>(dz2)[i] = make_float4(o[0], o[1], o[2], o[3]);
             }

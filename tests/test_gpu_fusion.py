@@ -432,6 +432,36 @@ def test_phased_backward_equals_monolithic_and_bucket_layout():
             assert emb <= off < eng.gru_end
 
 
+def test_train_step_with_a_bucketed_reducer_equals_the_plain_step_and_starts_the_documented_buckets():
+    """one deterministic train_step with a reducer that records its buckets and reduces nothing == one without, bit for
+    bit (parameters, Adam slots, gradients); the buckets: after phase 1 rest, after 2 emb then tail, after 4 the GRU
+    gates, after 8 the GRU candidate"""
+    dims, B, R, T, N = SMALL, 8, 6, 7, 9
+    p, table, nbox, batch, am, masks = make_case(51, "vlmap_answer", B, R, T, N, dims)
+    ka, kj = dev(masks["att"].astype(np.uint8)), dev(masks["joint"].astype(np.uint8))
+    db = dev_batch(batch)
+    eng, twin = (make_engine("vlmap_answer", p, table, nbox, am, B, R, T, dims, deterministic=True) for _ in range(2))
+    seen = []
+
+    class Rec:
+        def start(self, bucket):
+            lo = (bucket.data_ptr() - eng.grad_flat.data_ptr()) // 4
+            seen.append((lo, lo + bucket.numel()))
+
+        def finish(self):
+            seen.append("finish")
+    before = eng.train_flat.clone()
+    eng.train_step(db, ka, kj, lr=1e-3, allreduce=Rec())
+    twin.train_step(db, ka, kj, lr=1e-3)
+    torch.cuda.synchronize()
+    for name in ("train_flat", "m_flat", "v_flat", "grad_flat"):
+        assert torch.equal(getattr(eng, name), getattr(twin, name)), name
+    assert not torch.equal(eng.train_flat, before) and eng.step_count == twin.step_count == 1
+    e, m, g, n = eng.embed_floats, eng.gru_mid, eng.gru_end, eng.n_train
+    assert 0 < e < m < g < n
+    assert seen == [(g, n), (0, e), (n, n + 4), (m, g), (e, m), "finish"]
+
+
 def test_standard_word2vec_train_steps_and_model_class(tmp_path):
     """vqa/model_standard_word2vec.py: three clip+Adam steps against the oracle; the constant answer-GloVe matrix never
     moves and is not a variable; the Model mirror builds it from GloVe with the mean-of-words rule for phrases."""

@@ -221,6 +221,40 @@ def test_checkpoint_resume_continues_the_adam_trajectory():
         np.testing.assert_allclose(v.cpu().numpy(), want[k], rtol=0, atol=2e-6, err_msg=k)
 
 
+def test_train_step_with_a_bucketed_reducer_equals_the_plain_step_and_starts_the_documented_buckets():
+    """one deterministic train_step with a reducer that records its buckets and reduces nothing == one without, bit for
+    bit (parameters, Adam slots, gradients); the buckets: after phase 1 [b2:b3], after 2 [b1:b2], after 4 [b0:b1],
+    after 8 [:b0] then [b3:] (with the tail)"""
+    from vqa_transfer_externaldata_amd import pretrain as PT
+    cfg = dict(B=3, n=5, R=6, D=16, H=8, L=4, W=12, Vq=20, n_ws=7, A=12)
+    rng = np.random.default_rng(13)
+    p = PO.init_params(rng, cfg["Vq"], cfg["n_ws"], cfg["A"], W=cfg["W"], D=cfg["D"], H=cfg["H"])
+    batch = PO.make_batch(rng, cfg["B"], cfg["n"], cfg["R"], cfg["D"], cfg["L"], cfg["Vq"], cfg["n_ws"], cfg["A"])
+    masks = {k: dev(v.astype(np.uint8)) for k, v in PO.make_masks(rng, cfg["B"], cfg["n"], cfg["R"], cfg["H"]).items()}
+    eng, twin = (PT.PretrainEngine(n=cfg["n"], R=cfg["R"], D=cfg["D"], H=cfg["H"], W=cfg["W"], A=cfg["A"], Vq=cfg["Vq"],
+                                   n_ws=cfg["n_ws"], params=p, deterministic=True) for _ in range(2))
+    seen = []
+
+    class Rec:
+        def start(self, bucket):
+            lo = (bucket.data_ptr() - eng.grad_flat.data_ptr()) // 4
+            seen.append((lo, lo + bucket.numel()))
+
+        def finish(self):
+            seen.append("finish")
+    before = eng.train_flat.clone()
+    eng.train_step({k: dev(v) for k, v in batch.items()}, masks, 2e-3, allreduce=Rec())
+    twin.train_step({k: dev(v) for k, v in batch.items()}, masks, 2e-3)
+    torch.cuda.synchronize()
+    for name in ("train_flat", "m_flat", "v_flat", "grad_flat"):
+        assert torch.equal(getattr(eng, name), getattr(twin, name)), name
+    assert not torch.equal(eng.train_flat, before) and eng.step_count == twin.step_count == 1
+    b0, b1, b2, b3 = eng._bounds[:4]
+    n = eng.n_train
+    assert 0 < b0 < b1 < b2 < b3 < n
+    assert seen == [(b2, b3), (b1, b2), (b0, b1), (0, b0), (b3, n + 4), "finish"]
+
+
 def test_resident_feature_tables_give_the_dense_batch_results():
     """PretrainEngine.bind_tables + batches that carry image_idx: the rows gathered on the device are the dense
     batch's, so report, logits and gradients are bit for bit those of the dense path"""

@@ -2,7 +2,8 @@
 composition must leave every digest as it was (same-box A/B; the environment's VQA_HOT_* switches apply as usual).
 Per case: forward, a full backward, (pre-training: another forward,) then the phased backward (1, 2, 4, 8).  A fusion
 digest covers logit, pred, report and grad_flat after either backward; a pre-training digest report, every head's logits
-(z; noc: zv and zl), <kind>/att, <kind>/pooled and grad_flat after either backward.
+(z; noc: zv and zl), <kind>/att, <kind>/pooled and grad_flat after either backward.  Then one eager train_step (lr 1e-3):
+every digest also covers train_flat, m_flat, v_flat and state_dict()'s sorted keys and values after it.
 usage: step_digest.py [--root CHECKOUT] /path/to/libvqahot.so CASE [CASE ...]
     --root: import the package and the oracles from another checkout of the repository (the parent's Python files)
     CASE = S.<model_type>                      B 8, R 5, D 64, H 32, T 6, W 12, A 20, Vq 50 (the fallback routes)
@@ -40,9 +41,21 @@ from vqa_transfer_externaldata_amd import fusion as F, pretrain as PT  # noqa: E
 
 SMALL = dict(R=5, D=64, H=32, T=6, W=12, A=20, Vq=50)
 FULL = dict(R=36, D=2048, H=1024, T=4, W=300, A=64, Vq=200)
-N_IMG, SEED = 16, 20
+N_IMG, SEED, LR = 16, 20, 1e-3
 PT_SMALL = dict(B=3, n=5, R=6, D=16, H=8, L=4, W=12, Vq=20, n_ws=7, A=12, n_ctx=15, Lc=7)
 PT_FULL = dict(B=32, n=5, R=36, D=2048, H=1024, L=4, W=300, Vq=200, n_ws=50, A=64, n_ctx=90, Lc=7)
+
+
+def take_train_step(eng, sha, take, step):
+    """one eager train_step (`step`), then the flat state and the checkpoint: train_flat, m_flat, v_flat and
+    state_dict()'s sorted keys and values"""
+    step()
+    for t in (eng.train_flat, eng.m_flat, eng.v_flat):
+        take(t)
+    sd = eng.state_dict()
+    for k in sorted(sd):
+        sha.update(k.encode())
+        take(sd[k])
 
 
 def pretrain_digest(case):
@@ -96,6 +109,7 @@ def pretrain_digest(case):
         eng._backward_phases(phase)
     take_forward()
     take(eng.grad_flat)
+    take_train_step(eng, sha, take, lambda: eng.train_step(db, masks, LR, **kw))
     return sha.hexdigest()
 
 
@@ -161,6 +175,7 @@ def digest(case):
     for phase in (1, 2, 4, 8):
         eng._backward_phases(phase)
     take(eng.grad_flat)
+    take_train_step(eng, sha, take, lambda: eng.train_step(db, ka, kj, lr=LR, **ex))
     return sha.hexdigest()
 
 

@@ -15,19 +15,19 @@ Memory layout in HBM (all fp32):
   m_flat, v_flat = Adam moments, same layout as train_flat
   frozen_flat = variables excluded by filter_train_vars (vlmap_answer only)
   workspace   = activations + backward scratch, carved by the library
+The flat buffers, their checkpoint half, the optimiser step and the phased backward are engine_core.EngineCore's.
 """
 from __future__ import annotations
 
 import collections
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from .engine_core import ADAM_B1, ADAM_B2, ADAM_EPS, EngineCore, carve, phase_schedule
 
-ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8     # tf.train.AdamOptimizer defaults
 CLIP_NORM = 20.0                                   # vqa/trainer.py:111
 
 FROZEN_TOP_SCOPES_VLMAP = ("q_linear_l", "pooled_linear_l", "joint_fc", "WordWeightAnswer")
@@ -217,8 +217,10 @@ def filter_transfer_vars(names, model_type):
     return [n for n in names if n.split("/")[0] in keep]
 
 
-def _pad4(n):
-    return (n + 3) // 4 * 4
+# FusionEngine.backward(reducer=...): (phase bit, how many of flat_layout's buckets start their reduction after it) --
+# after 1 `rest`; after 2 `emb`, `tail`; after 4 the GRU gates (10.8 MB, reduced under the candidate GEMMs); after 8 the
+# GRU candidate (5.4 MB: the only exposed reduction)
+BUCKET_PHASES = ((1, 1), (2, 2), (4, 1), (8, 1))
 
 
 def flat_layout(model_type, shapes, ft_vlmap=False):
@@ -238,32 +240,24 @@ def flat_layout(model_type, shapes, ft_vlmap=False):
     train_names = embeds + gru_first + [n for n in train if n not in embeds and not is_gru(n)]
     frozen_names = [n for n in names if n not in train]
 
-    def carve(name_list):
-        off, table = 0, {}
-        for n in name_list:
-            cnt = int(np.prod(shapes[n]))
-            table[n] = (off, cnt)
-            off += _pad4(cnt)
-        return table, off
-
-    train_tab, n_train = carve(train_names)
-    frozen_tab, n_frozen = carve(frozen_names)
-    embed_floats = sum(_pad4(int(np.prod(shapes[n]))) for n in embeds)
+    train_tab, n_train = carve(train_names, shapes)
+    frozen_tab, n_frozen = carve(frozen_names, shapes)
+    embed_floats = carve(embeds, shapes)[1]
     # the GRU tensors must sit right after the tables, and inside them [candidate/* | gates/*]: the gate half is reduced
     # while the candidate half is computed
     gru = [n for n in train_names if is_gru(n)]
     assert train_names[len(embeds):len(embeds) + len(gru)] == gru, "flat layout: the GRU kernels must follow the embeddings"
-    gru_end = embed_floats + sum(_pad4(int(np.prod(shapes[n]))) for n in gru)
+    gru_end = embed_floats + carve(gru, shapes)[1]
     cand = [n for n in gru if "/candidate/" in n]
     assert gru[:len(cand)] == cand, "flat layout: candidate/* precede gates/*"
-    gru_mid = embed_floats + sum(_pad4(int(np.prod(shapes[n]))) for n in cand)
+    gru_mid = embed_floats + carve(cand, shapes)[1]
     e, m, g, n = embed_floats, gru_mid, gru_end, n_train
     return dict(train_names=train_names, frozen_names=frozen_names, train_tab=train_tab, n_train=n_train,
                 frozen_tab=frozen_tab, n_frozen=n_frozen, embed_floats=e, gru_mid=m, gru_end=g,
                 buckets=[(g, n), (0, e), (n, n + 4), (m, g), (e, m)])
 
 
-class FusionEngine:
+class FusionEngine(EngineCore):
     MODEL_TYPE_ID = {"vlmap_answer": 0, "standard": 1, "standard_word2vec": 2, "standard_testmask": 3,
                      "vlmap_answer_vqa_all2": 4, "vlmap_answer_noc": 5, "vlmap_answer_nocarch": 5, "vlmap_answer_vqa_all": 6,
                      "vlmap_answer2": 7, "vlmap_answer_no_noise": 8, "vlmap_answer_adapt": 9, "vlmap_answer_full": 10,
@@ -341,24 +335,13 @@ class FusionEngine:
         self.shapes = variable_shapes(model_type, Vq, W, D, H, A, map_dim=map_dim)
         lay = flat_layout(model_type, self.shapes, ft_vlmap=ft_vlmap)
         self.train_names, self.frozen_names = lay["train_names"], lay["frozen_names"]
-        self._train_tab, self.n_train = lay["train_tab"], lay["n_train"]
-        self._frozen_tab, self.n_frozen = lay["frozen_tab"], lay["n_frozen"]
+        self._train_tab, self._frozen_tab, self.n_frozen = lay["train_tab"], lay["frozen_tab"], lay["n_frozen"]
         self.embed_floats, self.gru_mid, self.gru_end = lay["embed_floats"], lay["gru_mid"], lay["gru_end"]
         self._buckets = lay["buckets"]
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.train_flat = torch.zeros(self.n_train, **f32)
-        self.frozen_flat = torch.zeros(max(self.n_frozen, 4), **f32)
-        self.grad_flat = torch.zeros(self.n_train + 4, **f32)
-        self.m_flat = torch.zeros(self.n_train, **f32)
-        self.v_flat = torch.zeros(self.n_train, **f32)
-        self.norm_sq = torch.zeros(4, **f32)
-        self.sumsq_ws = torch.zeros(int(self.lib.vqa_sumsq_workspace_floats(self.n_train)) + 4, **f32)
+        self._alloc_flat(self._train_tab, lay["n_train"], self.shapes, self.embed_floats, self.device)
+        self._set_schedule(phase_schedule(BUCKET_PHASES, self._buckets))
+        self.frozen_flat = torch.zeros(max(self.n_frozen, 4), dtype=torch.float32, device=self.device)
         self.step_count = 0
-
-        self.params, self.grads = {}, {}
-        for n, (off, cnt) in self._train_tab.items():
-            self.params[n] = self.train_flat[off:off + cnt].view(self.shapes[n])
-            self.grads[n] = self.grad_flat[off:off + cnt].view(self.shapes[n])
         for n, (off, cnt) in self._frozen_tab.items():
             self.params[n] = self.frozen_flat[off:off + cnt].view(self.shapes[n])
         # standard_word2vec: the constant [W, A] GloVe matrix of the answers -- a tf.constant in the reference, so it
@@ -373,14 +356,10 @@ class FusionEngine:
             self.answer_glove = g.to(device=self.device, dtype=torch.float32).contiguous()
         self.load_params(params)
 
-        ws_bytes = int(self.lib.vqa_fusion_workspace_bytes(C.byref(self.dims)))
-        if ws_bytes <= 0:
-            raise _lib.VqaHotError("vqa_fusion_workspace_bytes rejected the dims")
-        self.workspace = torch.zeros(ws_bytes, dtype=torch.uint8, device=self.device)
+        self.workspace = None
+        self._grow_workspace()
         self._p_struct = self._make_struct(self.params, all_required=True)
         self._g_struct = self._make_struct(self.grads, all_required=False)
-        self._tensor_cache = {}
-        self._reset_recurrence_word()
         self._batch_keepalive = None
 
     # ------------------------------------------------------------------ parameters
@@ -396,26 +375,11 @@ class FusionEngine:
                 raise ValueError("variable %s has shape %s, expected %s" % (n, tuple(t.shape), self.shapes[n]))
             self.params[n].copy_(t.to(torch.float32))
 
-    def state_dict(self):
-        """Flat name -> CPU tensor archive with the reference's variable names
-        (+ Adam slots and global_step), the analogue of tf.train.Saver's checkpoint."""
-        out = {n: p.detach().cpu().clone() for n, p in self.params.items()}
-        for n, (off, cnt) in self._train_tab.items():
-            out[n + "/Adam"] = self.m_flat[off:off + cnt].view(self.shapes[n]).cpu().clone()
-            out[n + "/Adam_1"] = self.v_flat[off:off + cnt].view(self.shapes[n]).cpu().clone()
-        out["global_step"] = torch.tensor(self.step_count, dtype=torch.int64)
-        return out
-
     def load_state_dict(self, sd, var_names=None):
         names = var_names if var_names is not None else list(self.shapes)
         self.load_params({n: sd[n] for n in names}, strict=False)
         if var_names is None:
-            for n, (off, cnt) in self._train_tab.items():
-                if n + "/Adam" in sd:
-                    self.m_flat[off:off + cnt].copy_(sd[n + "/Adam"].reshape(-1))
-                    self.v_flat[off:off + cnt].copy_(sd[n + "/Adam_1"].reshape(-1))
-            if "global_step" in sd:
-                self.step_count = int(sd["global_step"])
+            self._load_optimizer_state(sd)
 
     def _make_struct(self, table, all_required):
         sc = self.sc
@@ -475,25 +439,14 @@ class FusionEngine:
         self.drop_graphs()            # captured step graphs hold this shape's buffers
         d.B, d.T = B, T
         d.inv_global_batch = 1.0 / float(global_batch or B)
-        need = int(self.lib.vqa_fusion_workspace_bytes(C.byref(d)))
-        if need <= 0:
-            raise _lib.VqaHotError("vqa_fusion_workspace_bytes rejected the dims")
-        if need > self.workspace.numel():
-            self.drop_graphs()
-            self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
-        self._tensor_cache = {}
-        self._reset_recurrence_word()
+        self._grow_workspace()
         for a in ["_" + k.name for k in KEEP_SITES] + ["_noise", "_keep_lay"]:
             if hasattr(self, a):
                 delattr(self, a)
 
     def _grow_workspace(self):
-        need = int(self.lib.vqa_fusion_workspace_bytes(C.byref(self.dims)))
-        if need <= 0:
-            raise _lib.VqaHotError("vqa_fusion_workspace_bytes rejected the dims")
-        if need > self.workspace.numel():
-            self.drop_graphs()
-            self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        self._ensure_workspace(self.lib.vqa_fusion_workspace_bytes, self.dims, "vqa_fusion_workspace_bytes rejected the dims",
+                               before_grow=self.drop_graphs)
         self._tensor_cache = {}
         self._reset_recurrence_word()
 
@@ -515,9 +468,6 @@ class FusionEngine:
         return t
 
     # ------------------------------------------------------------------ step pieces
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def bind_inputs(self, *, table, nbox_table, answer_masks):
         """Device-resident feature table [N,R,D] f32 (torch.bfloat16 with features="bf16": never converted here),
         num_boxes i32 [N], float [A] masks."""
@@ -611,39 +561,7 @@ class FusionEngine:
         only the GRU candidate bucket's reduction (5.4 MB) is exposed."""
         # only the embedding gradient is scatter-added; everything else is overwritten
         self.grad_flat[:self.embed_floats].zero_()
-        if reducer is None:
-            self._backward_phases(15)
-            return
-        gf = self.grad_flat
-        rest, emb, tail, gates, cand = (gf[lo:hi] for lo, hi in self._buckets)       # flat_layout: disjoint, cover grad_flat
-        self._backward_phases(1)
-        reducer.start(rest)
-        self._backward_phases(2)
-        reducer.start(emb)
-        reducer.start(tail)
-        self._backward_phases(4)
-        reducer.start(gates)                      # GRU gates (10.8 MB) reduce under the candidate GEMMs
-        self._backward_phases(8)
-        reducer.start(cand)                       # GRU candidate (5.4 MB): the only exposed reduction
-        reducer.finish()
-
-    def optimizer_step(self, lr):
-        """clip_by_global_norm(20) + Adam on the flat buffers.  The norm uses the
-        dense gradients of every non-embedding train var plus the un-aggregated
-        embedding slices (tail slot), as tf.clip_by_global_norm does for IndexedSlices."""
-        e = self.embed_floats
-        dense = self.grad_flat[e:self.n_train]
-        tail = self.grad_flat[self.n_train:]
-        _lib.check(self.lib.vqa_sumsq(C.c_void_p(dense.data_ptr()), dense.numel(), C.c_void_p(tail.data_ptr()),
-                                      C.c_void_p(self.norm_sq.data_ptr()), C.c_void_p(self.sumsq_ws.data_ptr()),
-                                      self.sumsq_ws.numel(), self._stream()), "vqa_sumsq")
-        self.step_count += 1
-        t = self.step_count
-        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
-        _lib.check(self.lib.vqa_clip_adam(C.c_void_p(self.train_flat.data_ptr()), C.c_void_p(self.grad_flat.data_ptr()),
-                                          C.c_void_p(self.m_flat.data_ptr()), C.c_void_p(self.v_flat.data_ptr()),
-                                          self.n_train, C.c_void_p(self.norm_sq.data_ptr()), float(self.clip_norm), lr_t,
-                                          ADAM_B1, ADAM_B2, ADAM_EPS, self._stream()), "vqa_clip_adam")
+        super().backward(reducer)
 
     def train_step(self, batch, keep_att=None, keep_joint=None, lr=None, allreduce=None, keep_joint2=None, noise=None,
                    keep_tile=None, keep_word=None, dropout=None, row_offset=0, global_rows=None):
@@ -652,13 +570,7 @@ class FusionEngine:
             raise TypeError("train_step needs the learning rate lr")
         self.forward(batch, keep_att, keep_joint, want_dz=True, keep_joint2=keep_joint2, noise=noise, keep_tile=keep_tile,
                      keep_word=keep_word, dropout=dropout, row_offset=row_offset, global_rows=global_rows)
-        if allreduce is not None and hasattr(allreduce, "start"):
-            self.backward(reducer=allreduce)          # bucketed, overlapped with the backward phases
-        else:
-            self.backward()
-            if allreduce is not None:
-                allreduce(self.grad_flat)
-        self.optimizer_step(lr)
+        self._backward_and_step(lr, allreduce)
 
     # ------------------------------------------------------------------ whole step as one hipGraph replay
     def train_step_graph(self, batch, lr, seed, step, dropout=None):
@@ -721,19 +633,13 @@ class FusionEngine:
                 try:
                     self.forward(st, ka, kj, want_dz=True, **extra)
                     self.backward()
-                    e = self.embed_floats
-                    dense, tail = self.grad_flat[e:self.n_train], self.grad_flat[self.n_train:]
-                    _lib.check(self.lib.vqa_sumsq(C.c_void_p(dense.data_ptr()), dense.numel(), C.c_void_p(tail.data_ptr()),
-                                                  C.c_void_p(self.norm_sq.data_ptr()), C.c_void_p(self.sumsq_ws.data_ptr()),
-                                                  self.sumsq_ws.numel(), sp), "vqa_sumsq")
+                    _lib.check(self.lib.vqa_sumsq(*self._sumsq_args(sp)), "vqa_sumsq")
                     _lib.check(self.lib.vqa_adam_lr_step(C.c_void_p(self._g_step.data_ptr()), C.c_void_p(self._g_lr.data_ptr()),
                                                          ADAM_B1, ADAM_B2, C.c_void_p(self._g_lr_t.data_ptr()), sp),
                                "vqa_adam_lr_step")
-                    _lib.check(self.lib.vqa_clip_adam_dev(
-                        C.c_void_p(self.train_flat.data_ptr()), C.c_void_p(self.grad_flat.data_ptr()),
-                        C.c_void_p(self.m_flat.data_ptr()), C.c_void_p(self.v_flat.data_ptr()), self.n_train,
-                        C.c_void_p(self.norm_sq.data_ptr()), float(self.clip_norm), C.c_void_p(self._g_lr_t.data_ptr()), ADAM_B1, ADAM_B2,
-                        ADAM_EPS, sp), "vqa_clip_adam_dev")
+                    _lib.check(self.lib.vqa_clip_adam_dev(*self._adam_ptrs, float(self.clip_norm),
+                                                          C.c_void_p(self._g_lr_t.data_ptr()), ADAM_B1, ADAM_B2, ADAM_EPS, sp),
+                               "vqa_clip_adam_dev")
                 except Exception:
                     self.lib.vqa_graph_capture_abort(sp)
                     raise

@@ -41,17 +41,17 @@ DESIGN.md section 7), no mask tensor, bit for bit the same step.  keep_offsets()
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
 from . import _lib, ops
+from .engine_core import EngineCore, carve, phase_schedule
 
 TOP_K = 5
 KINDS = ("obj", "attr")
 KEEP_ATT, KEEP_JOINT = 0.8, 0.5
-ADAM_B1, ADAM_B2, ADAM_EPS, CLIP_NORM = 0.9, 0.999, 1e-8, 20.0
+CLIP_NORM = 20.0
 NO_GRAD_VARS = ("V_GloVe/embed_map", "LearnAnswerGloVe/embed_map")      # created for export only
 SPARSE_VARS = ("wordset_map/learn", "L_GloVe/embed_map", "enwiki_map/learn")   # IndexedSlices gradients (if present)
 # Order of the dense variables in the flat buffers = the order in which the phases of vqa_pretrain_backward_phases
@@ -63,6 +63,13 @@ PHASE_SCOPES = (("encode_L_blank/", "encode_L_enwiki/"),
                 ("classifier/", "joint_fc/", "pooled_linear_l/", "q_linear_l/", "classifier_v/", "classifier_l/", "joint_v/",
                  "joint_l/"),
                 ("spat_att/", "spat_q_linear_v/", "spat_v_linear_v/", "wordset_ft/", "v_adapt/"))
+# PretrainEngine.backward(reducer=...) (engine_core; vlmap_memft/trainer.py:129-137: optimize_loss over every variable):
+# (phase bit, how many of flat_layout's buckets start their reduction after it) -- after 1 the stacked heads [b2:b3]
+# (50+ MB, reduced under the back-propagation through time); after 2 the GRUs [b1:b2] (under the dx GEMM + embedding
+# scatter-add); after 4 L_GloVe (+ enwiki_map) [b0:b1] (under the spatial-attention backward); after 8 wordset_map [:b0],
+# then the spatial attention / wordset_ft / v_adapt gradients with the tail [b3:]: only these small ones are exposed.
+# Nothing is zeroed before the phases: the C side clears the scatter-added tables.
+BUCKET_PHASES = ((1, 1), (2, 1), (4, 1), (8, 2))
 # head set per model type: blank fill, word set, enwiki context (in TF build order; head 2 r + k of the type of rank r
 # and category k owns LayerNorm slot 2 r + k of the shared fusion scopes when they are not shared)
 MODEL_HEADS = {"vlmap_bf_or_wordset_withatt_sp": ("bf", "ws"),
@@ -231,11 +238,29 @@ PARAM_FIELDS = {_lib.PtParams: _TRUNK + _HEADS,
 PRECISIONS = ("f32", "bf16")      # PretrainEngine(precision=...): "bf16" sets VQA_FLAG_BF16_GEMM
 
 
-def _pad4(n):
-    return (n + 3) // 4 * 4
+def flat_layout(shapes):
+    """Where every variable sits in the flat buffers (pure host arithmetic, no GPU), the twin of fusion.flat_layout:
+    train_flat / grad_flat order = [sparse tables | PHASE_SCOPES' groups, by name] (+ 4 tail floats in grad_flat), every
+    variable padded to a multiple of 4 floats.  `bounds` (floats): wordset_map [0, b0), L_GloVe (+ enwiki_map) [b0, b1),
+    GRUs [b1, b2), heads [b2, b3), rest [b3, n_train).  `buckets` are the slices of grad_flat
+    PretrainEngine.backward hands to a bucketed reducer, in the order it starts them."""
+    sparse = [k for k in SPARSE_VARS if k in shapes]
+    dense = sorted(k for k in shapes if k not in NO_GRAD_VARS and k not in SPARSE_VARS)
+    groups = [[k for k in dense if k.startswith(sc)] for sc in PHASE_SCOPES]
+    assert sorted(sum(groups, [])) == dense, "a variable outside the phase scopes"
+    train_names = sparse + sum(groups, [])
+    tab, n_train = carve(train_names, shapes)
+    ends, o = [], 0
+    for names in ([sparse[0]], sparse[1:], groups[0], groups[1], groups[2]):
+        o += carve(names, shapes)[1]
+        ends.append(o)
+    assert ends[-1] == n_train
+    b0, b1, b2, b3 = ends[:4]
+    return dict(train_names=train_names, tab=tab, n_train=n_train, bounds=tuple(ends), sparse_floats=b1,
+                buckets=[(b2, b3), (b1, b2), (b0, b1), (0, b0), (b3, n_train + 4)])
 
 
-class PretrainEngine:
+class PretrainEngine(EngineCore):
     def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
                  heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False, precision="f32"):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
@@ -273,7 +298,7 @@ class PretrainEngine:
         self.device = torch.device(device)
         self.n, self.R, self.D, self.H, self.W, self.A = n, R, D, H, W, A
         self.Vq, self.n_ws, self.deterministic = Vq, n_ws, bool(deterministic)
-        self.step_count = 0
+        self.step_count, self.clip_norm = 0, CLIP_NORM
         self.report = {}
         self.workspace, self.dims = None, None
         self._layout(ln_shared_in(params) if ln_shared is None else bool(ln_shared))
@@ -285,38 +310,13 @@ class PretrainEngine:
         self.ln_shared = bool(ln_shared)
         self.shapes = variable_shapes(self.Vq, self.n_ws, self.A, self.W, self.D, self.H, self.ln_shared, self.heads,
                                       self.n_ctx, self.noc, self.adapt)
-        sparse = [k for k in SPARSE_VARS if k in self.shapes]
-        dense = sorted(k for k in self.shapes if k not in NO_GRAD_VARS and k not in SPARSE_VARS)
-        groups = [[k for k in dense if k.startswith(sc)] for sc in PHASE_SCOPES]
-        assert sorted(sum(groups, [])) == dense, "a variable outside the phase scopes"
-        self.train_names = sparse + sum(groups, [])
-        off, self._tab = 0, {}
-        for k in self.train_names:
-            cnt = int(np.prod(self.shapes[k]))
-            self._tab[k] = (off, cnt)
-            off += _pad4(cnt)
-        self.n_train = off
-        # bucket bounds (floats): wordset_map [0, b0), L_GloVe (+ enwiki_map) [b0, b1), GRUs [b1, b2), heads [b2, b3),
-        # rest [b3, n_train)
-        ends, o = [], 0
-        for names in ([sparse[0]], sparse[1:], groups[0], groups[1], groups[2]):
-            o += sum(_pad4(int(np.prod(self.shapes[k]))) for k in names)
-            ends.append(o)
-        self._bounds = tuple(ends)
-        assert ends[-1] == self.n_train
-        self.sparse_floats = sum(_pad4(int(np.prod(self.shapes[k]))) for k in sparse)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.train_flat = torch.zeros(self.n_train, **f32)
-        self.grad_flat = torch.zeros(self.n_train + 4, **f32)      # tail slot 0: un-aggregated slice sum of squares
-        self.m_flat, self.v_flat = torch.zeros(self.n_train, **f32), torch.zeros(self.n_train, **f32)
-        self.norm_sq = torch.zeros(4, **f32)
-        self.sumsq_ws = torch.zeros(int(self.lib.vqa_sumsq_workspace_floats(self.n_train)) + 4, **f32)
-        self.params, self.grads = {}, {}
-        for k, (o, cnt) in self._tab.items():
-            self.params[k] = self.train_flat[o:o + cnt].view(self.shapes[k])
-            self.grads[k] = self.grad_flat[o:o + cnt].view(self.shapes[k])
+        lay = flat_layout(self.shapes)
+        self.train_names, self._tab, self._bounds = lay["train_names"], lay["tab"], lay["bounds"]
+        self.sparse_floats = lay["sparse_floats"]
+        self._alloc_flat(self._tab, lay["n_train"], self.shapes, self.sparse_floats, self.device)
+        self._set_schedule(phase_schedule(BUCKET_PHASES, lay["buckets"]))
         for k in NO_GRAD_VARS:
-            self.params[k] = torch.zeros(self.shapes[k], **f32)
+            self.params[k] = torch.zeros(self.shapes[k], dtype=torch.float32, device=self.device)
         self._p_struct = self._param_struct(self.params)
         self._g_struct = self._param_struct(self.grads)
 
@@ -517,9 +517,6 @@ class PretrainEngine:
         _lib.check(fn(C.byref(self.dims), name.encode(), C.byref(off), C.byref(n)), "vqa_pretrain_tensor(%s)" % name)
         return self.workspace[off.value:off.value + 4 * n.value].view(dtype)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ------------------------------------------------------------------ forward / backward
     def global_valid_counts(self, batch, group=None):
         """(#valid object entries, #valid attribute entries) of the GLOBAL batch = the denominators of the masked mean
@@ -560,11 +557,8 @@ class PretrainEngine:
             d.global_valid[0], d.global_valid[1] = float(global_valid[0]), float(global_valid[1])
         if self.ext:
             d = _lib.PtExtDims(base=d, heads=head_mask(self.heads), Lc=self._Lc or 0, n_ctx=self.n_ctx or 0)
-        need = int(getattr(self.lib, self._abi + "workspace_bytes")(C.byref(d)))
-        if need <= 0:
-            raise _lib.VqaHotError("vqa_pretrain_workspace_bytes rejected the dims")
-        if self.workspace is None or need > self.workspace.numel():
-            self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        self._ensure_workspace(getattr(self.lib, self._abi + "workspace_bytes"), d,
+                               "vqa_pretrain_workspace_bytes rejected the dims")
         self.dims, self._bs, self._keepalive = d, bs, keep
         fwd = getattr(self.lib, self._abi + "forward_ex")
         _lib.check(fwd(C.byref(d), C.byref(self._p_struct), C.byref(bs), C.c_void_p(self.workspace.data_ptr()),
@@ -606,68 +600,13 @@ class PretrainEngine:
             C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), C.c_void_p(tail.data_ptr()), phases,
             self._stream(), C.byref(self._ks) if self._ks is not None else None), "vqa_pretrain_backward_phases")
 
-    def backward(self, reducer=None):
-        """All gradients into grad_flat (vlmap_memft/trainer.py:129-137: optimize_loss over every variable).  With a
-        bucketed `reducer` (dp.BucketedAllReduce) the dependency-ordered phases are enqueued one by one and each
-        finished bucket's all-reduce starts right away: the stacked heads' 50+ MB reduce under the back-propagation
-        through time, the GRU kernels under the dx GEMM + embedding scatter-add, L_GloVe under the spatial-attention
-        backward; only the last, small bucket (word sets, spatial FCs, slice sum of squares) is exposed."""
-        if reducer is None:
-            self._backward_phases(15)
-            return
-        b0, b1, b2, b3 = self._bounds[:4]
-        n = self.n_train
-        self._backward_phases(1)
-        reducer.start(self.grad_flat[b2:b3])
-        self._backward_phases(2)
-        reducer.start(self.grad_flat[b1:b2])
-        self._backward_phases(4)
-        reducer.start(self.grad_flat[b0:b1])
-        self._backward_phases(8)
-        reducer.start(self.grad_flat[:b0])
-        reducer.start(self.grad_flat[b3:])          # spatial attention / wordset_ft gradients + the tail (slice sum of squares)
-        reducer.finish()
-
-    def optimizer_step(self, lr):
-        """clip_by_global_norm(20) + Adam; the two embedding tables contribute their UN-AGGREGATED slice
-        gradients to the norm (tf.clip_by_global_norm on IndexedSlices), see fusion.FusionEngine."""
-        dense = self.grad_flat[self.sparse_floats:self.n_train]
-        tail = self.grad_flat[self.n_train:]
-        P = lambda x: C.c_void_p(x.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.lib.vqa_sumsq(P(dense), dense.numel(), P(tail), P(self.norm_sq), P(self.sumsq_ws),
-                                      self.sumsq_ws.numel(), st), "vqa_sumsq")
-        self.step_count += 1
-        s = self.step_count
-        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** s) / (1.0 - ADAM_B1 ** s)
-        _lib.check(self.lib.vqa_clip_adam(P(self.train_flat), P(self.grad_flat), P(self.m_flat), P(self.v_flat),
-                                          self.n_train, P(self.norm_sq), CLIP_NORM, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS,
-                                          st), "vqa_clip_adam")
-
     def train_step(self, batch, masks, lr, allreduce=None, global_valid=None, dropout=None, row_offset=0, global_rows=None):
         """forward -> backward -> (gradient all-reduce) -> clip + Adam.  Data parallel: `allreduce` is a
         dp.BucketedAllReduce (overlapped with the backward phases) or any callable on grad_flat; pass the global
         valid counts so that every shard divides by the global denominators and a SUM reduce gives the gradient of
         the global-batch losses; all ranks then apply the identical update.  dropout: as for forward."""
         self.forward(batch, masks, global_valid=global_valid, dropout=dropout, row_offset=row_offset, global_rows=global_rows)
-        if allreduce is not None and hasattr(allreduce, "start"):
-            self.backward(reducer=allreduce)
-        else:
-            self.backward()
-            if allreduce is not None:
-                allreduce(self.grad_flat)
-        self.optimizer_step(lr)
-
-    def state_dict(self):
-        """name -> CPU tensor with the reference's variable names, the Adam slots of every trained variable
-        (`<var>/Adam`, `<var>/Adam_1`) and global_step -- what tf.train.Saver keeps (vlmap_memft/trainer.py);
-        same layout as fusion.FusionEngine.state_dict."""
-        out = {k: v.detach().cpu().clone() for k, v in self.params.items()}
-        for k, (o, cnt) in self._tab.items():
-            out[k + "/Adam"] = self.m_flat[o:o + cnt].view(self.shapes[k]).cpu().clone()
-            out[k + "/Adam_1"] = self.v_flat[o:o + cnt].view(self.shapes[k]).cpu().clone()
-        out["global_step"] = torch.tensor(self.step_count, dtype=torch.int64)
-        return out
+        self._backward_and_step(lr, allreduce)
 
     def load_state_dict(self, sd, strict=True):
         """Restores parameters, Adam moments and the step count (beta powers), so a resumed run continues the
@@ -686,12 +625,7 @@ class PretrainEngine:
         for k in self.shapes:
             if k in sd:
                 self.params[k].copy_(torch.as_tensor(sd[k]).to(torch.float32))
-        for k, (o, cnt) in self._tab.items():
-            if k + "/Adam" in sd:
-                self.m_flat[o:o + cnt].copy_(torch.as_tensor(sd[k + "/Adam"]).reshape(-1))
-                self.v_flat[o:o + cnt].copy_(torch.as_tensor(sd[k + "/Adam_1"]).reshape(-1))
-        if "global_step" in sd:
-            self.step_count = int(sd["global_step"])
+        self._load_optimizer_state(sd)
         return missing
 
 

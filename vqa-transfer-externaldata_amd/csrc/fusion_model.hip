@@ -17,27 +17,10 @@
 #include <string>
 #include <vector>
 
+#include "gru_encoder.h"
 #include "keep_launch.h"
 
 namespace {
-
-struct Entry { const char* name; int64_t off; int64_t n; int esz; };
-
-struct Layout {
-    std::vector<Entry> e;
-    int64_t total = 0;
-    int64_t add(const char* name, int64_t n, int esz = 4) {
-        const int64_t off = total;
-        e.push_back({name, off, n, esz});
-        total += ((n * esz + 255) / 256) * 256;  // 256-B aligned carve
-        return off;
-    }
-    const Entry* find(const char* name) const {
-        for (const auto& x : e)
-            if (strcmp(x.name, name) == 0) return &x;
-        return nullptr;
-    }
-};
 
 // properties that several model types share (include/vqa_hot.h: VQA_MODEL_*)
 inline bool has_tuned_head(int mt) { return mt == VQA_MODEL_VQA_ALL2 || mt == VQA_MODEL_VQA_ALL; }      // a second, trainable head on `joint`
@@ -191,15 +174,10 @@ Layout make_layout(const vqa_dims_t& d) {
     return L;
 }
 
-struct Ctx {
+struct Ctx : Workspace {
     const vqa_dims_t& d;
-    const Layout& L;
-    char* ws;
     hipStream_t st;
     int lane;   // 0 = caller's stream, 1 = side stream (own scratch so the two never share a buffer)
-    float* f(const char* name) const { return reinterpret_cast<float*>(ws + L.find(name)->off); }
-    int32_t* i32(const char* name) const { return reinterpret_cast<int32_t*>(ws + L.find(name)->off); }
-    uint16_t* u16(const char* name) const { return reinterpret_cast<uint16_t*>(ws + L.find(name)->off); }
     float* gemm_ws() const { return f(lane ? "gemm_ws1" : "gemm_ws"); }
     float* colsum_ws() const { return f(lane ? "colsum_ws1" : "colsum_ws"); }
     float* part(int i) const {
@@ -207,8 +185,8 @@ struct Ctx {
         static const char* const n1[3] = {"part_a1", "part_b1", "part_c1"};
         return f(lane ? n1[i] : n0[i]);
     }
-    int64_t gemm_ws_floats() const { return L.find("gemm_ws")->n; }
-    int64_t colsum_ws_floats() const { return L.find("colsum_ws")->n; }
+    int64_t gemm_ws_floats() const { return count("gemm_ws"); }
+    int64_t colsum_ws_floats() const { return count("colsum_ws"); }
 };
 
 // ---- The VQA_HOT_* switches of this file.  Each is read from the environment once per process, at its first use (never
@@ -425,6 +403,9 @@ int gemm_x(const Ctx& c, int tA, int64_t M, int64_t N, int64_t K, const float* x
 int colsum(const Ctx& c, const float* X, int64_t M, int64_t N, int ldx, float* out) {
     return vqa_colsum(X, (int)M, (int)N, ldx, out, c.colsum_ws(), c.colsum_ws_floats(), c.st);
 }
+auto f32(const Ctx& c) { return [&c](auto... a) { return gemm_f32(c, a...); }; }      // gemm_f32 on c as a callable (gru_encoder.h)
+GruCell fw_cell(const vqa_params_t* p) { return {p->gru_wg, p->gru_bg, p->gru_wc, p->gru_bc}; }
+GruCell bw_cell(const vqa_params_t* p) { return {p->gru_bw_wg, p->gru_bw_bg, p->gru_bw_wc, p->gru_bw_bc}; }      // model_type 12
 
 bool dims_ok(const vqa_dims_t* d) {
     if (!(d && d->B > 0 && d->R > 0 && d->D > 0 && d->H > 0 && d->T > 0 && d->W > 0 && d->A > 0 && d->Vq > 0 &&
@@ -540,12 +521,10 @@ bool ln_pair_ok(const vqa_dims_t& d, const vqa_params_t* P) {
 #include "legacy_vqa.inc"
 
 // ---- model_type 12: bi-directional question encoder + question self-attention (vqa/model_vlmap_finetune.py:119-150) ----
-struct BiGru { const float *wg, *bg, *wc, *bc; };
-
-int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt) {
+// bi[0] / bi[1]: the forward / backward cell's encoder (Step::enc)
+int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt, const GruTape* bi) {
     const vqa_dims_t& d = c.d;
     const int64_t B = d.B, H = d.H, T = d.T, W = d.W, h = H / 2;
-    const int64_t Wp = x_stride(W);
     VQA_REQUIRE(P->embed2 && P->gru_bw_wg && P->gru_bw_bg && P->gru_bw_wc && P->gru_bw_bc && P->q_att_key.w &&
                     P->q_att_key.gamma && P->q_att_query.w && P->q_att_query.gamma && P->word_score.w && P->word_score.b &&
                     P->v_word_fc.w && P->v_word_fc.gamma,
@@ -554,29 +533,24 @@ int bi_question_fwd(const Ctx& c, const vqa_params_t* P, const vqa_batch_t* bt) 
     {
         ProbeScope ps("embed.fwd", c.st);
         TRY(vqa_reverse_tokens(bt->q_intseq, bt->q_intseq_len, q_rev, (int)B, (int)T, c.st));
-        TRY(vqa_embed_fwd_ld(P->embed, bt->q_intseq, c.f("x_tm"), (int)B, (int)T, (int)W, d.Vq, (int)Wp, c.st));
-        TRY(vqa_embed_fwd_ld(P->embed, q_rev, c.f("x_tm_bw"), (int)B, (int)T, (int)W, d.Vq, (int)Wp, c.st));
+        TRY(vqa_embed_fwd_ld(P->embed, bt->q_intseq, bi[0].x_tm, (int)B, (int)T, (int)W, d.Vq, bi[0].ldx(), c.st));
+        TRY(vqa_embed_fwd_ld(P->embed, q_rev, bi[1].x_tm, (int)B, (int)T, (int)W, d.Vq, bi[1].ldx(), c.st));
         // the second embedding, batch-major rows (b, t): one "sequence" per token
         TRY(vqa_embed_fwd_ld(P->embed2, bt->q_intseq, c.f("e2"), (int)(B * T), 1, (int)W, d.Vq, (int)W, c.st));
     }
-    const BiGru cell[2] = {{P->gru_wg, P->gru_bg, P->gru_wc, P->gru_bc}, {P->gru_bw_wg, P->gru_bw_bg, P->gru_bw_wc, P->gru_bw_bc}};
-    static const char* const nm[2][9] = {{"x_tm", "xp", "wx_cat", "bx_cat", "hs", "gru_r", "gru_u", "gru_c", "gru_rh"},
-                                         {"x_tm_bw", "xp_bw", "wx_cat_bw", "bx_cat_bw", "hs_bw", "gru_r_bw", "gru_u_bw",
-                                          "gru_c_bw", "gru_rh_bw"}};
     for (int k = 0; k < 2; ++k) {
+        const GruTape& t = bi[k];
         {
             ProbeScope ps("gru.xp_gemm", c.st);
-            TRY(vqa_gru_pack_wx(cell[k].wg, cell[k].wc, cell[k].bg, cell[k].bc, c.f(nm[k][2]), c.f(nm[k][3]), (int)W, (int)h, c.st));
-            TRY(gemm_f32(c, 0, 0, T * B, 3 * h, W, c.f(nm[k][0]), (int)Wp, c.f(nm[k][2]), (int)(3 * h), c.f(nm[k][1]), (int)(3 * h),
-                     c.f(nm[k][3])));
+            TRY(t.pack_wx());
+            TRY(t.project(f32(c)));
         }
-        float* hs = c.f(nm[k][4]);
-        if (hipMemsetAsync(hs, 0, (size_t)B * h * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
+        TRY(t.clear_h0());
         ProbeScope ps("gru.fwd", c.st);
-        TRY(vqa_gru_seq_fwd_rows(c.f(nm[k][1]), cell[k].wg + W * 2 * h, cell[k].wc + W * h, bt->q_intseq_len, hs, c.f(nm[k][5]),
-                                 c.f(nm[k][6]), c.f(nm[k][7]), c.f(nm[k][8]), (int)T, (int)B, (int)h, 0, (int)B, c.st));
+        TRY(vqa_gru_seq_fwd_rows(t.xp, t.Wg_h(), t.Wc_h(), bt->q_intseq_len, t.hs, t.gru_r, t.gru_u, t.gru_c, t.gru_rh, (int)T,
+                                 (int)B, (int)h, 0, (int)B, c.st));
     }
-    TRY(vqa_bi_outputs_fwd(c.f("hs"), c.f("hs_bw"), bt->q_intseq_len, c.f("q_L_map"), c.f("q_L_ft"), (int)B, (int)T, (int)h, c.st));
+    TRY(vqa_bi_outputs_fwd(bi[0].hs, bi[1].hs, bt->q_intseq_len, c.f("q_L_map"), c.f("q_L_ft"), (int)B, (int)T, (int)h, c.st));
     // keys: fc_layer on [B,T,H] -- LayerNorm over the whole [T,H] block of a question, padded positions included
     TRY(fc_ln_relu_fwd(c, c.f("q_L_map"), B * T, H, H, P->q_att_key, (int)T, "pre_key", "q_att_key", "mean_key", "rstd_key",
                        NO_KEEP, 1.f));
@@ -614,7 +588,7 @@ int bi_question_bwd_head(const Ctx& c, const vqa_params_t* P, const vqa_params_t
         ProbeScope ps("embed.bwd", c.st);
         TRY(vqa_embed_bwd_len_det(c.f("d_e2"), bt->q_intseq, nullptr, G->embed2, (int)(B * T), 1, (int)W, d.Vq,
                                   (d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
-        TRY(vqa_sumsq(c.f("d_e2"), B * T * W, nullptr, c.f("sq_e2"), c.f("sumsq_ws2"), c.L.find("sumsq_ws2")->n, c.st));
+        TRY(vqa_sumsq(c.f("d_e2"), B * T * W, nullptr, c.f("sq_e2"), c.f("sumsq_ws2"), c.count("sumsq_ws2"), c.st));
     }
     TRY(fc_ln_relu_bwd(c, c.f("d_query"), c.f("q_L_ft"), B, H, H, P->q_att_query, &G->q_att_query, 1, "pre_query", "mean_query",
                        "rstd_query", NO_KEEP, 1.f, "d_pre_query", dh, true));
@@ -623,27 +597,27 @@ int bi_question_bwd_head(const Ctx& c, const vqa_params_t* P, const vqa_params_t
 }
 
 // phase 2: both BPTTs, the gradient wrt the looked-up embeddings, LearnGloVe's scatter-add and the slice norm
-int bi_question_bwd_bptt(const Ctx& c, const vqa_params_t* P, const vqa_params_t* G, const vqa_batch_t* bt, const float* dh,
+int bi_question_bwd_bptt(const Ctx& c, const vqa_params_t* G, const vqa_batch_t* bt, const GruTape* bi, const float* dh,
                          float* embed_slice_sq) {
     const vqa_dims_t& d = c.d;
     const int64_t B = d.B, H = d.H, T = d.T, W = d.W, h = H / 2;
+    const std::string dir[2] = {"_fw", "_bw"};      // the bi-directional model's own per-cell buffers
     TRY(vqa_bi_outputs_bwd(c.f("d_qmap"), dh, bt->q_intseq_len, c.f("dout_fw"), c.f("dout_bw"), c.f("dhT_fw"), c.f("dhT_bw"),
                            (int)B, (int)T, (int)h, c.st));
     {
         ProbeScope ps("gru.bwd", c.st);
-        TRY(vqa_gru_seq_bwd_outs(c.f("dhT_fw"), P->gru_wg + W * 2 * h, P->gru_wc + W * h, bt->q_intseq_len, c.f("hs"), c.f("gru_r"),
-                                 c.f("gru_u"), c.f("gru_c"), c.f("dout_fw"), c.f("dxp"), c.f("dhS_fw"), (int)T, (int)B, (int)h, c.st));
-        TRY(vqa_gru_seq_bwd_outs(c.f("dhT_bw"), P->gru_bw_wg + W * 2 * h, P->gru_bw_wc + W * h, bt->q_intseq_len, c.f("hs_bw"),
-                                 c.f("gru_r_bw"), c.f("gru_u_bw"), c.f("gru_c_bw"), c.f("dout_bw"), c.f("dxp_bw"), c.f("dhS_bw"),
-                                 (int)T, (int)B, (int)h, c.st));
+        for (int k = 0; k < 2; ++k) {
+            const GruTape& t = bi[k];
+            TRY(vqa_gru_seq_bwd_outs(c.f("dhT" + dir[k]), t.Wg_h(), t.Wc_h(), bt->q_intseq_len, t.hs, t.gru_r,
+                                     t.gru_u, t.gru_c, c.f("dout" + dir[k]), t.dxp, c.f("dhS" + dir[k]), (int)T, (int)B, (int)h, c.st));
+        }
     }
     {
         ProbeScope ps("gru.dx_gemm", c.st);
-        TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)h, c.st));
-        TRY(gemm_f32(c, 0, 1, T * B, W, 3 * h, c.f("dxp"), (int)(3 * h), c.f("wx_cat"), (int)(3 * h), c.f("dx_fw"), (int)W));
-        TRY(vqa_gru_pack_wx(P->gru_bw_wg, P->gru_bw_wc, P->gru_bw_bg, P->gru_bw_bc, c.f("wx_cat_bw"), c.f("bx_cat_bw"), (int)W,
-                            (int)h, c.st));
-        TRY(gemm_f32(c, 0, 1, T * B, W, 3 * h, c.f("dxp_bw"), (int)(3 * h), c.f("wx_cat_bw"), (int)(3 * h), c.f("dx_bw"), (int)W));
+        for (int k = 0; k < 2; ++k) {
+            TRY(bi[k].pack_wx());
+            TRY(bi[k].dx(f32(c), c.f("dx" + dir[k])));
+        }
         TRY(vqa_bi_dx_combine(c.f("dx_fw"), c.f("dx_bw"), bt->q_intseq_len, c.f("dx_embed"), (int)B, (int)T, (int)W, c.st));
     }
     ProbeScope ps("embed.bwd", c.st);
@@ -652,34 +626,7 @@ int bi_question_bwd_bptt(const Ctx& c, const vqa_params_t* P, const vqa_params_t
                                   (d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
     if (embed_slice_sq != nullptr)
         TRY(vqa_sumsq(c.f("dx_embed"), T * B * W, G->embed2 != nullptr ? c.f("sq_e2") : nullptr, embed_slice_sq, c.f("sumsq_ws"),
-                      c.L.find("sumsq_ws")->n, c.st));
-    return VQA_OK;
-}
-
-// phases 4 / 8: the two cells' gate (incl. every x row and bias) / candidate recurrent weight gradients
-int bi_question_bwd_weights(const Ctx& c, const vqa_params_t* G, int phases) {
-    const vqa_dims_t& d = c.d;
-    const int64_t B = d.B, H = d.H, T = d.T, W = d.W, h = H / 2;
-    const int64_t Wp = x_stride(W);
-    float* const gw[2][4] = {{G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc}, {G->gru_bw_wg, G->gru_bw_wc, G->gru_bw_bg, G->gru_bw_bc}};
-    static const char* const nm[2][5] = {{"x_tm", "dxp", "dwx_cat", "hs", "gru_rh"}, {"x_tm_bw", "dxp_bw", "dwx_cat_bw", "hs_bw", "gru_rh_bw"}};
-    for (int k = 0; k < 2; ++k) {
-        if (gw[k][0] == nullptr) continue;
-        float* dxp = c.f(nm[k][1]);
-        if (phases & 4) {
-            {
-                ProbeScope ps("gru.dwx_gemm", c.st);
-                TRY(gemm_f32(c, 1, 0, Wp, 3 * h, T * B, c.f(nm[k][0]), (int)Wp, dxp, (int)(3 * h), c.f(nm[k][2]), (int)(3 * h)));
-                TRY(vqa_gru_unpack_dwx_bias(c.f(nm[k][2]), gw[k][0], gw[k][1], gw[k][2], gw[k][3], (int)W, (int)h, c.st));
-            }
-            ProbeScope ps("gru.dwh_gemm", c.st);
-            TRY(gemm_f32(c, 1, 0, h, 2 * h, T * B, c.f(nm[k][3]), (int)h, dxp, (int)(3 * h), gw[k][0] + W * 2 * h, (int)(2 * h)));
-        }
-        if (phases & 8) {
-            ProbeScope ps("gru.dwh_gemm", c.st);
-            TRY(gemm_f32(c, 1, 0, h, h, T * B, c.f(nm[k][4]), (int)h, dxp + 2 * h, (int)(3 * h), gw[k][1] + W * h, (int)h));
-        }
-    }
+                      c.count("sumsq_ws"), c.st));
     return VQA_OK;
 }
 
@@ -699,19 +646,19 @@ extern "C" int vqa_fusion_tensor(const vqa_dims_t* dims, const char* name, int64
     else if (dims->model_type == VQA_MODEL_LEGACY_VQA && (strcmp(name, "q_L_ft") == 0 || strcmp(name, "answer_ft") == 0)) {
         // final LSTM states: the last [N,H] block of the time-major state tapes
         const bool q = name[0] == 'q';
-        const Entry* hsn = L.find(q ? "lv_hsq" : "lv_hsa");
+        const auto* hsn = L.find(q ? "lv_hsq" : "lv_hsa");
         const int64_t N = q ? dims->B : dims->A, Tn = q ? dims->T : dims->La;
         if (offset_bytes) *offset_bytes = hsn->off + Tn * N * dims->H * 4;
         if (n_elems) *n_elems = N * dims->H;
         return VQA_OK;
     }
     else if (strcmp(name, "condition") == 0) {  // heavy_output['condition'] = final GRU state = hs[T]
-        const Entry* h = L.find("hs");
+        const auto* h = L.find("hs");
         if (offset_bytes) *offset_bytes = h->off + (int64_t)dims->T * dims->B * dims->H * 4;
         if (n_elems) *n_elems = (int64_t)dims->B * dims->H;
         return VQA_OK;
     }
-    const Entry* e = L.find(key);
+    const auto* e = L.find(key);
     if (e == nullptr) return VQA_ERR_ARG;
     if (offset_bytes) *offset_bytes = e->off;
     if (n_elems) *n_elems = e->n;
@@ -744,8 +691,8 @@ struct Step {
     const Ctx c;                       // the caller's stream
     const int mt;
     const int64_t B, R, D, H, T, W, A;
-    const int64_t Wp;                  // row stride of x_tm
     const int64_t Dp;                  // width of what the attention pools
+    GruTape enc[2];                    // [0] the question encoder; model_type 12: the forward and [1] the backward cell, H / 2 units each
     // side stream (VQA_HOT_OVERLAP=1): set where the visual branch (forward) or v_linear_v's backward forks
     Side* sd = nullptr;
     bool forked = false;
@@ -760,28 +707,21 @@ struct Step {
     Step(const vqa_dims_t* dims, const vqa_params_t* P_, const vqa_params_t* G_, const vqa_batch_t* bt_, void* workspace,
          void* stream)
         : d(*dims), P(P_), G(G_), bt(bt_), L(make_layout(*dims)),
-          c{*dims, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), 0}, mt(dims->model_type),
-          B(dims->B), R(dims->R), D(dims->D), H(dims->H), T(dims->T), W(dims->W), A(dims->A), Wp(x_stride(dims->W)),
-          Dp(pooled_dim(*dims)) {}
+          c{{L, static_cast<char*>(workspace)}, *dims, static_cast<hipStream_t>(stream), 0}, mt(dims->model_type),
+          B(dims->B), R(dims->R), D(dims->D), H(dims->H), T(dims->T), W(dims->W), A(dims->A),
+          Dp(pooled_dim(*dims)) {
+        if (mt == VQA_MODEL_LEGACY_VQA) return;      // LSTM encoders (legacy_vqa.inc)
+        const int64_t Hc = mt == VQA_MODEL_BI ? H / 2 : H;
+        enc[0] = GruTape(c, "", "", "", T, B, Hc, W, fw_cell(P), c.st);
+        if (mt == VQA_MODEL_BI) enc[1] = GruTape(c, "", "", "_bw", T, B, Hc, W, bw_cell(P), c.st);
+    }
     Step(const Step&) = delete;
     Step& operator=(const Step&) = delete;
 
     // the context of what may run beside the caller's stream (the visual branch; v_linear_v's backward): the side stream
     // and its own scratch when forked, else the caller's
-    Ctx side_ctx() const { return Ctx{d, L, c.ws, forked ? sd->s : c.st, forked ? 1 : 0}; }
-    // backward: resolved once per call (bind_bwd), behind the workspace checks
-    const float* hs = nullptr;         // the GRU's state tape
-    const float* h = nullptr;          // the final GRU state hs[T]
-    float* dh = nullptr;               // gradient wrt the question code
-    float* dxp = nullptr;
-    void bind_bwd() {
-        hs = c.f("hs");
-        h = hs + T * B * H;
-        dh = c.f("d_h0");
-        dxp = c.f("dxp");
-    }
-    const float* Wg_h() const { return P->gru_wg + W * 2 * H; }      // the recurrent rows of the two GRU kernels
-    const float* Wc_h() const { return P->gru_wc + W * H; }
+    Ctx side_ctx() const { return Ctx{{L, c.ws}, d, forked ? sd->s : c.st, forked ? 1 : 0}; }
+    float* const dh = c.f("d_h0");     // backward: gradient wrt the question code
 };
 
 // the two halves of the side stream's join: its work is recorded, the caller's stream waits for the record
@@ -864,59 +804,55 @@ int fwd_question(Step& s) {
     const Ctx& c = s.c;
     const vqa_params_t* P = s.P;
     const vqa_batch_t* bt = s.bt;
-    const int64_t B = s.B, H = s.H, T = s.T, W = s.W, Wp = s.Wp;
+    const int64_t B = s.B, H = s.H, T = s.T, W = s.W;
     if (s.mt == VQA_MODEL_BI) {
-        TRY(bi_question_fwd(c, P, bt));
+        TRY(bi_question_fwd(c, P, bt, s.enc));
         s.q_ft = c.f("q_L_ft");
         s.qv_in = c.f("pooled_q_v");
         return VQA_OK;
     }
+    const GruTape& e = s.enc[0];
     // a3: embedding lookup, time-major
     // x_tm rows carry the constant 1 after the W inputs (vqa_embed_fwd_ld): the x-part weight-gradient GEMM then also
     // delivers the bias gradients, and the two passes over dxp that summed its columns are gone
     {
         ProbeScope ps("embed.fwd", c.st);
-        TRY(vqa_embed_fwd_ld(P->embed, bt->q_intseq, c.f("x_tm"), (int)B, (int)T, (int)W, s.d.Vq, (int)Wp, c.st));
+        TRY(vqa_embed_fwd_ld(P->embed, bt->q_intseq, e.x_tm, (int)B, (int)T, (int)W, s.d.Vq, e.ldx(), c.st));
     }
     // a4: GRU.  Input projections of all steps as one packed GEMM (or the two-GEMM form) ...
-    float* xp = c.f("xp");
     {
         ProbeScope ps("gru.xp_gemm", c.st);
         if (xcat_enabled()) {
-            TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-            TRY(gemm_f32(c, 0, 0, T * B, 3 * H, W, c.f("x_tm"), (int)Wp, c.f("wx_cat"), (int)(3 * H), xp, (int)(3 * H), c.f("bx_cat")));
+            TRY(e.pack_wx());
+            TRY(e.project(f32(c)));
         } else {
-            TRY(gemm_f32(c, 0, 0, T * B, 2 * H, W, c.f("x_tm"), (int)Wp, P->gru_wg, (int)(2 * H), xp, (int)(3 * H), P->gru_bg));
-            TRY(gemm_f32(c, 0, 0, T * B, H, W, c.f("x_tm"), (int)Wp, P->gru_wc, (int)H, xp + 2 * H, (int)(3 * H), P->gru_bc));
+            TRY(gemm_f32(c, 0, 0, T * B, 2 * H, W, e.x_tm, e.ldx(), P->gru_wg, (int)(2 * H), e.xp, (int)(3 * H), P->gru_bg));
+            TRY(gemm_f32(c, 0, 0, T * B, H, W, e.x_tm, e.ldx(), P->gru_wc, (int)H, e.xp + 2 * H, (int)(3 * H), P->gru_bc));
         }
     }
     // ... then the recurrence
-    float* hs = c.f("hs");
-    if (hipMemsetAsync(hs, 0, (size_t)B * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-    const float* Wg_h = s.Wg_h();
-    const float* Wc_h = s.Wc_h();
+    TRY(e.clear_h0());
+    const float *Wg_h = e.Wg_h(), *Wc_h = e.Wc_h();
     {
         ProbeScope ps("gru.fwd", c.st);
         switch (gru_form(GRU_FWD, T, B, H, bt->live_rows)) {
             case GRU_WS:
-                TRY(vqa_gru_seq_fwd_ws_ex(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), c.f("gru_rh"),
-                                          (int)T, (int)B, (int)H, h0skip_mode() & 1, c.f("gru_ws"), c.st));      // hs[0]: cleared above
+                TRY(vqa_gru_seq_fwd_ws_ex(e.xp, Wg_h, Wc_h, bt->q_intseq_len, e.hs, e.gru_r, e.gru_u, e.gru_c, e.gru_rh, (int)T, (int)B,
+                                          (int)H, h0skip_mode() & 1, c.find_f("gru_ws"), c.st));      // hs[0]: cleared above
                 break;
             case GRU_LIVE:
-                TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
-                                         c.f("gru_c"), c.f("gru_rh"), (int)T, (int)B, (int)H, c.st));
+                TRY(vqa_gru_seq_fwd_live(e.xp, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, e.hs, e.gru_r, e.gru_u, e.gru_c, e.gru_rh,
+                                         (int)T, (int)B, (int)H, c.st));
                 break;
-            case GRU_CHAINS: {
-                float* gr = c.f("gru_r"); float* gu = c.f("gru_u"); float* gc = c.f("gru_c"); float* grh = c.f("gru_rh");
+            case GRU_CHAINS:
                 TRY(run_chains(c, B, [&](int, int64_t row0, int64_t rows, hipStream_t st) {
-                    return vqa_gru_seq_fwd_rows(xp, Wg_h, Wc_h, bt->q_intseq_len, hs, gr, gu, gc, grh, (int)T, (int)B, (int)H,
-                                                (int)row0, (int)rows, st);
+                    return vqa_gru_seq_fwd_rows(e.xp, Wg_h, Wc_h, bt->q_intseq_len, e.hs, e.gru_r, e.gru_u, e.gru_c, e.gru_rh, (int)T,
+                                                (int)B, (int)H, (int)row0, (int)rows, st);
                 }));
                 break;
-            }
         }
     }
-    s.q_ft = hs + T * B * H;
+    s.q_ft = e.h_final();
     s.qv_in = s.q_ft;
     return VQA_OK;
 }
@@ -1250,7 +1186,7 @@ int bwd_question_code(const Step& s) {
     const vqa_params_t* P = s.P;
     const vqa_params_t* G = s.G;
     const int64_t B = s.B, H = s.H;
-    const float* h = s.h;
+    const float* h = s.enc[0].h_final();      // the final GRU state hs[T]
     float* dh = s.dh;
     if (s.mt == VQA_MODEL_ANSWER2) {
         // q_linear_l read q_L_ft2: back through it, then through tanh + LN + FC (trainable) into dh
@@ -1384,8 +1320,8 @@ int bwd_q_linear_v(const Step& s) {
         return bi_question_bwd_head(c, s.P, s.G, s.bt, s.dh);
     }
     // q_linear_v: dh += ...
-    return fc_ln_relu_bwd(c, c.f("d_qv"), s.h, B, H, H, s.P->q_linear_v, &s.G->q_linear_v, 1, "pre_qv", "mean_qv", "rstd_qv",
-                          NO_KEEP, 1.f, "d_pre_qv", s.dh, true);
+    return fc_ln_relu_bwd(c, c.f("d_qv"), s.enc[0].h_final(), B, H, H, s.P->q_linear_v, &s.G->q_linear_v, 1, "pre_qv", "mean_qv",
+                          "rstd_qv", NO_KEEP, 1.f, "d_pre_qv", s.dh, true);
 }
 
 // phase 2: GRU back-propagation through time (gate math fused into the GEMM epilogues), dx, embedding scatter-add, slice
@@ -1395,29 +1331,26 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
     const vqa_params_t* P = s.P;
     const vqa_batch_t* bt = s.bt;
     const int64_t B = s.B, H = s.H, T = s.T, W = s.W;
-    const float* hs = s.hs;
+    const GruTape& e = s.enc[0];
     float* dh = s.dh;
-    float* dxp = s.dxp;
-    const float* Wg_h = s.Wg_h();
-    const float* Wc_h = s.Wc_h();
+    const float *Wg_h = e.Wg_h(), *Wc_h = e.Wc_h();
     {
         ProbeScope ps("gru.bwd", c.st);
         switch (gru_form(GRU_BWD, T, B, H, bt->live_rows)) {
             case GRU_WS:
                 // (hs[0] of this tape: fwd_question's zeros)
-                TRY(vqa_gru_seq_bwd_ws_ex(dh, nullptr, Wg_h, Wc_h, bt->q_intseq_len, hs, c.f("gru_r"), c.f("gru_u"), c.f("gru_c"), dxp,
-                                          (int)T, (int)B, (int)H, h0skip_mode() & 1, c.f("gru_ws"), c.st));
+                TRY(vqa_gru_seq_bwd_ws_ex(dh, nullptr, Wg_h, Wc_h, bt->q_intseq_len, e.hs, e.gru_r, e.gru_u, e.gru_c, e.dxp, (int)T, (int)B,
+                                          (int)H, h0skip_mode() & 1, c.find_f("gru_ws"), c.st));
                 break;
             case GRU_LIVE:
-                TRY(vqa_gru_seq_bwd_live(dh, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, hs, c.f("gru_r"), c.f("gru_u"),
-                                         c.f("gru_c"), dxp, c.f("d_h1"), (int)T, (int)B, (int)H, c.st));
+                TRY(vqa_gru_seq_bwd_live(dh, Wg_h, Wc_h, bt->q_intseq_len, bt->live_rows, e.hs, e.gru_r, e.gru_u, e.gru_c, e.dxp,
+                                         c.f("d_h1"), (int)T, (int)B, (int)H, c.st));
                 break;
             case GRU_CHAINS: {
-                const float* gr = c.f("gru_r"); const float* gu = c.f("gru_u"); const float* gc = c.f("gru_c");
                 float* dh1 = c.f("d_h1");
                 TRY(run_chains(c, B, [&](int, int64_t row0, int64_t rows, hipStream_t st) {
-                    return vqa_gru_seq_bwd_rows(dh, Wg_h, Wc_h, bt->q_intseq_len, hs, gr, gu, gc, dxp, dh1, (int)T, (int)B, (int)H,
-                                                (int)row0, (int)rows, st);
+                    return vqa_gru_seq_bwd_rows(dh, Wg_h, Wc_h, bt->q_intseq_len, e.hs, e.gru_r, e.gru_u, e.gru_c, e.dxp, dh1, (int)T,
+                                                (int)B, (int)H, (int)row0, (int)rows, st);
                 }));
                 break;
             }
@@ -1430,12 +1363,11 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
         if (xcat_enabled()) {
             // wx_cat: the forward's packed copy of the x rows still sits in the workspace (backward follows the forward of the
             // same step on the same weights: every gradient here is meaningless otherwise); VQA_HOT_REPACK=1 packs it again
-            if (repack_enabled())
-                TRY(vqa_gru_pack_wx(P->gru_wg, P->gru_wc, P->gru_bg, P->gru_bc, c.f("wx_cat"), c.f("bx_cat"), (int)W, (int)H, c.st));
-            TRY(gemm_f32(c, 0, 1, T * B, W, 3 * H, dxp, (int)(3 * H), c.f("wx_cat"), (int)(3 * H), dx, (int)W));
+            if (repack_enabled()) TRY(e.pack_wx());
+            TRY(e.dx(f32(c), dx));
         } else {
-            TRY(gemm_f32(c, 0, 1, T * B, W, 2 * H, dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
-            TRY(gemm_f32(c, 0, 1, T * B, W, H, dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
+            TRY(gemm_f32(c, 0, 1, T * B, W, 2 * H, e.dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
+            TRY(gemm_f32(c, 0, 1, T * B, W, H, e.dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
         }
     }
     ProbeScope ps_embed("embed.bwd", c.st);
@@ -1443,59 +1375,45 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
         TRY(vqa_embed_bwd_len_det(dx, bt->q_intseq, bt->q_intseq_len, s.G->embed, (int)B, (int)T, (int)W, s.d.Vq,
                                   (s.d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
     if (embed_slice_sq != nullptr)
-        TRY(vqa_sumsq(dx, T * B * W, nullptr, embed_slice_sq, c.f("sumsq_ws"), c.L.find("sumsq_ws")->n, c.st));
+        TRY(vqa_sumsq(dx, T * B * W, nullptr, embed_slice_sq, c.f("sumsq_ws"), c.count("sumsq_ws"), c.st));
     return VQA_OK;
 }
 
-// A recurrent weight gradient dW [H,N] = tape[0..T-1]^T dxp_part (gru.dwh_gemm).  The tape's rows of t = 0 are h_0 (gate
-// kernel) or r * h_0 (candidate kernel): zeros, since fwd_question cleared hs[0].  With bit 1 of h0skip_mode() the product
-// starts at row B of both operands, K = (T-1) B; at T = 1 nothing is left and the block, which the GEMM overwrites, is
-// cleared (rows W.. of a [W+H,N] gradient: contiguous).
-int dwh_gemm(const Step& s, const float* tape, const float* dxp_part, int64_t N, float* dW) {
-    const Ctx& c = s.c;
-    const int64_t B = s.B, H = s.H, T = s.T;
-    if (!(h0skip_mode() & 2))
-        return gemm_f32(c, 1, 0, H, N, T * B, tape, (int)H, dxp_part, (int)(3 * H), dW, (int)N);
-    if (T == 1)
-        return hipMemsetAsync(dW, 0, (size_t)(H * N) * sizeof(float), c.st) == hipSuccess ? VQA_OK : VQA_ERR_LAUNCH;
-    return gemm_f32(c, 1, 0, H, N, (T - 1) * B, tape + B * H, (int)H, dxp_part + B * 3 * H, (int)(3 * H), dW, (int)N);
-}
-
-// phase 4: the gate kernel's weight and bias gradients; in the packed form the x rows and biases of BOTH kernels (the
-// candidate's bucket is reduced after phase 4)
-int bwd_gate_weights(const Step& s) {
-    const Ctx& c = s.c;
-    const vqa_params_t* G = s.G;
-    const int64_t B = s.B, H = s.H, T = s.T, W = s.W, Wp = s.Wp;
-    float* dxp = s.dxp;
-    {
-        ProbeScope ps("gru.dwx_gemm", c.st);
-        if (xcat_enabled()) {
-            // rows 0..W-1: x rows of both kernels' gradients; row W (the constant input): both bias gradients
-            TRY(gemm_f32(c, 1, 0, Wp, 3 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), c.f("dwx_cat"), (int)(3 * H)));
-            TRY(vqa_gru_unpack_dwx_bias(c.f("dwx_cat"), G->gru_wg, G->gru_wc, G->gru_bg, G->gru_bc, (int)W, (int)H, c.st));
-        } else {
-            TRY(gemm_f32(c, 1, 0, W, 2 * H, T * B, c.f("x_tm"), (int)Wp, dxp, (int)(3 * H), G->gru_wg, (int)(2 * H)));
-            TRY(colsum(c, dxp, T * B, 2 * H, (int)(3 * H), G->gru_bg));
+// Phases 4 and 8 of one cell e with gradients g (frozen: nothing).  packed: the x rows and biases of both kernels come out of
+// one GEMM into dwx_cat; else fusion's two-GEMM form (VQA_HOT_XCAT=0).  The recurrent weight gradients (gru.dwh_gemm) start
+// at the tape's rows of step t0: those of t = 0 are h_0 (gate kernel) or r * h_0 (candidate kernel), zeros since the forward
+// cleared hs[0], and bit 1 of h0skip_mode() leaves them out for the question encoder.
+int bwd_gru_weights(const Ctx& c, const GruTape& e, const GruCell& g, int phases, bool packed, int t0) {
+    const int64_t TB = e.T * e.B, H = e.H, W = e.W;
+    const int ld3 = (int)(3 * H);
+    if (g.wg == nullptr) return VQA_OK;
+    // phase 4: the gate kernel's weight and bias gradients; in the packed form the x rows and biases of BOTH kernels (the
+    // candidate's bucket is reduced after phase 4)
+    if (phases & 4) {
+        {
+            ProbeScope ps("gru.dwx_gemm", c.st);
+            if (packed) {
+                TRY(e.dwx(f32(c)));
+                TRY(e.unpack_dwx(g));
+            } else {
+                TRY(gemm_f32(c, 1, 0, W, 2 * H, TB, e.x_tm, e.ldx(), e.dxp, ld3, g.wg, (int)(2 * H)));
+                TRY(colsum(c, e.dxp, TB, 2 * H, ld3, g.bg));
+            }
         }
+        ProbeScope ps("gru.dwh_gemm", c.st);
+        TRY(e.dwh(f32(c), g, false, t0));
     }
-    ProbeScope ps("gru.dwh_gemm", c.st);
-    return dwh_gemm(s, s.hs, dxp, 2 * H, G->gru_wg + W * 2 * H);
-}
-
-// phase 8: the candidate kernel's weight and bias gradients (its x rows and bias only in the two-GEMM form)
-int bwd_cand_weights(const Step& s) {
-    const Ctx& c = s.c;
-    const vqa_params_t* G = s.G;
-    const int64_t B = s.B, H = s.H, T = s.T, W = s.W, Wp = s.Wp;
-    float* dxp = s.dxp;
-    if (!xcat_enabled()) {
-        ProbeScope ps("gru.dwx_gemm", c.st);
-        TRY(gemm_f32(c, 1, 0, W, H, T * B, c.f("x_tm"), (int)Wp, dxp + 2 * H, (int)(3 * H), G->gru_wc, (int)H));
-        TRY(colsum(c, dxp + 2 * H, T * B, H, (int)(3 * H), G->gru_bc));
+    // phase 8: the candidate kernel's weight and bias gradients (its x rows and bias only in the two-GEMM form)
+    if (phases & 8) {
+        if (!packed) {
+            ProbeScope ps("gru.dwx_gemm", c.st);
+            TRY(gemm_f32(c, 1, 0, W, H, TB, e.x_tm, e.ldx(), e.dxp + 2 * H, ld3, g.wc, (int)H));
+            TRY(colsum(c, e.dxp + 2 * H, TB, H, ld3, g.bc));
+        }
+        ProbeScope ps("gru.dwh_gemm", c.st);
+        TRY(e.dwh(f32(c), g, true, t0));
     }
-    ProbeScope ps("gru.dwh_gemm", c.st);
-    return dwh_gemm(s, c.f("gru_rh"), dxp + 2 * H, H, G->gru_wc + W * H);
+    return VQA_OK;
 }
 
 }  // namespace
@@ -1515,7 +1433,6 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
     VQA_REQUIRE(workspace_bytes >= s.L.total, VQA_ERR_WORKSPACE);
     ProbeScope ps_all("backward", s.c.st);
     if (s.mt == VQA_MODEL_LEGACY_VQA) return (phases & 1) ? legacy_vqa_backward(s.c, P, G, bt, embed_slice_sq) : VQA_OK;
-    s.bind_bwd();
     s.pair = ln_pair_ok(s.d, P);
 
     if (phases & 1) {
@@ -1529,14 +1446,12 @@ extern "C" int vqa_fusion_backward_phases(const vqa_dims_t* dims, const vqa_para
         TRY(side_wait(s));
     }
     if (s.mt == VQA_MODEL_BI) {
-        if (phases & 2) TRY(bi_question_bwd_bptt(s.c, P, G, bt, s.dh, embed_slice_sq));
-        if (phases & 12) TRY(bi_question_bwd_weights(s.c, G, phases));
-        return VQA_OK;
+        if (phases & 2) TRY(bi_question_bwd_bptt(s.c, G, bt, s.enc, s.dh, embed_slice_sq));
+        TRY(bwd_gru_weights(s.c, s.enc[0], fw_cell(G), phases, true, 0));
+        return bwd_gru_weights(s.c, s.enc[1], bw_cell(G), phases, true, 0);
     }
     if (phases & 2) TRY(bwd_bptt(s, embed_slice_sq));
-    if ((phases & 4) && G->gru_wg != nullptr) TRY(bwd_gate_weights(s));
-    if ((phases & 8) && G->gru_wg != nullptr) TRY(bwd_cand_weights(s));
-    return VQA_OK;
+    return (phases & 12) ? bwd_gru_weights(s.c, s.enc[0], fw_cell(G), phases, xcat_enabled(), (h0skip_mode() >> 1) & 1) : VQA_OK;
 }
 
 extern "C" int vqa_hot_version(void) { return VQA_HOT_ABI_VERSION; }

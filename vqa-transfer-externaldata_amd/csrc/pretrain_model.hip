@@ -37,6 +37,7 @@
 #include <string>
 #include <vector>
 
+#include "gru_encoder.h"
 #include "keep_launch.h"
 
 namespace {
@@ -90,27 +91,7 @@ __global__ __launch_bounds__(256) void gather_rows2_kernel(const uint32_t* __res
     }
 }
 
-// ---------------------------------------------------------------- workspace layout
-struct Entry { std::string name; int64_t off, n; };
-struct Layout {
-    std::vector<Entry> e;
-    int64_t total = 0;
-    void add(const std::string& name, int64_t n) {
-        e.push_back({name, total, n});
-        total += ((n * 4 + 255) / 256) * 256;
-    }
-    // a named view of `cnt` floats inside an existing entry (the four heads' tensors are slices of stacked blocks)
-    void alias(const std::string& name, const std::string& base, int64_t off_floats, int64_t cnt) {
-        const Entry* b = find(base);
-        e.push_back({name, b->off + off_floats * 4, cnt});
-    }
-    const Entry* find(const std::string& name) const {
-        for (const auto& x : e)
-            if (x.name == name) return &x;
-        return nullptr;
-    }
-};
-
+// ---------------------------------------------------------------- workspace layout (step_workspace.h)
 const char* const KIND[2] = {"obj", "attr"};
 const char* const HEAD[3] = {"bf", "ws", "ew"};      // blank fill, word set, enwiki context
 const char* const TASK[3] = {"blank_fill", "wordset", "enwiki"};
@@ -120,10 +101,8 @@ bool dims_ok(const vqa_pretrain_dims_t* d) {
            d->Vq > 0 && d->n_ws > 0 && d->L > 0 && d->H % 4 == 0 && d->D % 4 == 0;
 }
 
-struct Ctx {
+struct Ctx : Workspace {
     const vqa_pretrain_dims_t& d;
-    const Layout& L;
-    char* ws;
     hipStream_t st;
     const vqa_pretrain_keep_t* keep = nullptr;      // the *_ex entry points' seeded sites; NULL: every site reads its mask
     // The keep source of one dropout site: `bit` = its VQA_PT_KEEP_SITE_* bit, `mask` = its mask pointer of the batch, `off`
@@ -133,9 +112,6 @@ struct Ctx {
         if (keep != nullptr && (keep->seeded & bit)) return KeepSrc::seeded(keep->keep_seed, off, row_len, keep_prob);
         return KeepSrc::bytes(mask, keep_prob);
     }
-    float* f(const std::string& name) const { return reinterpret_cast<float*>(ws + L.find(name)->off); }
-    int32_t* i32(const std::string& name) const { return reinterpret_cast<int32_t*>(ws + L.find(name)->off); }
-    int64_t count(const std::string& name) const { return L.find(name)->n; }
     // LayerNorm slot of call site `site` of an fc_layer scope: slot 0 for every site under VQA_FLAG_SHARED_LN
     int li(int site) const { return (d.flags & VQA_FLAG_SHARED_LN) ? 0 : site; }
     // The f32 MFMA product, whatever the flags say: both encoders (x-projection, dx, dwx, dwh), wordset_ft and the K = 6
@@ -145,6 +121,7 @@ struct Ctx {
         return vqa_gemm_f32(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, f("gemm_ws"),
                             count("gemm_ws"), st);
     }
+    auto f32() const { return [this](auto... a) { return gemm_f32(a...); }; }      // as a callable (gru_encoder.h)
     // The routed layers' products (forward, dW, dx): bf16 operands in the matrix unit under VQA_FLAG_BF16_GEMM, else f32.
     // A shape the bf16 kernel refuses is its error return, never a silent f32 product.  Every call site names one of the
     // two wrappers: there is no default a new site could pick up by accident.
@@ -188,6 +165,10 @@ struct Acc {
         const float* add = first ? nullptr : gw;
         if (prec == PREC_ROUTED) return c.gemm_routed(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
         return c.gemm_f32(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
+    }
+    auto f32() {      // weight(PREC_F32, ...) in the argument order of a GEMM call with tA = 1, tB = 0 (gru_encoder.h)
+        return [this](int, int, int64_t K, int64_t N, int64_t M, const float* x, int ldx, const float* dy, int ldy, float* gw, int,
+                      const float*) { return weight(PREC_F32, gw, x, ldx, dy, ldy, K, N, M); };
     }
     // three column sums (d_gamma, d_beta, d_bias partials [G, N]) into their gradients: first touch overwrites, later
     // ones add inside the reduction's last pass (no temporaries, no add kernels)
@@ -510,14 +491,12 @@ int64_t layout_bytes(const Model& m) { return m.ok ? m.layout().total : VQA_ERR_
 int layout_tensor(const Model& m, const char* name, int64_t* offset_bytes, int64_t* n_elems) {
     if (!m.ok || name == nullptr) return VQA_ERR_ARG;
     const Layout L = m.layout();
-    const Entry* e = L.find(name);
+    const auto* e = L.find(name);
     if (e == nullptr) return VQA_ERR_ARG;
     if (offset_bytes) *offset_bytes = e->off;
     if (n_elems) *n_elems = e->n;
     return VQA_OK;
 }
-
-struct GruVars { float *wg, *bg, *wc, *bc; };      // gates / candidate kernel [W + H, 2H] / [W + H, H] and bias
 
 // The variables (or their gradients) of a call, whichever public struct they came in: the trunk, up to two joint /
 // classifier blocks (standard, adapt: [0] = joint_fc / classifier; noc: [0] = joint_v / classifier_v, [1] = joint_l /
@@ -526,7 +505,7 @@ struct Params {
     bool present;      // the caller's pointer was non-NULL
     float *wordset_map, *l_glove, *enwiki_map;
     vqa_pt_fc6_t spat_v_linear_v, spat_q_linear_v, spat_att_score;
-    GruVars gru, egru;
+    GruCell gru, egru;
     vqa_pt_fc6_t pooled_linear_l, q_linear_l, wordset_ft, joint[2], classifier[2], v_adapt;
 };
 
@@ -717,14 +696,15 @@ struct Seq {
     const int32_t *perm, *inv, *live_rows;
     float *table, *g_table;                                // embedding table [vocab,W] and its gradient
     int vocab;
-    GruVars P, G;                                          // the recurrence's variables and their gradients
+    GruCell G;                                             // the gradients of the recurrence's variables
     int64_t T, head;                                       // padded length; "S/lft" / "d_lft" slices head, head + 1
+    GruTape t;                                             // the encoder's buffers (gru_encoder.h) with the variables P
 };
 struct SeqSet { Seq s[2]; int n; };
 
 // the token batches of the head set: the captions, then the contexts when the enwiki head is on (G NULL in the forward:
 // the gradient members stay NULL)
-SeqSet make_seqs(const vqa_pretrain_ext_dims_t& dims, const Params& P, const Params* G, const Batch& b, const HeadSet& hs) {
+SeqSet make_seqs(const Ctx& c, const vqa_pretrain_ext_dims_t& dims, const Params& P, const Params* G, const Batch& b, const HeadSet& hs) {
     const vqa_pretrain_ext_batch_t* bx = &b.x;
     const vqa_pretrain_batch_t& bt = bx->base;
     SeqSet q{};
@@ -734,7 +714,7 @@ SeqSet make_seqs(const vqa_pretrain_ext_dims_t& dims, const Params& P, const Par
     for (int k = 0; k < 2; ++k) { j.tokens[k] = bt.kind[k].blanks; j.len[k] = bt.kind[k].blanks_len; }
     j.perm = bt.perm; j.inv = bt.inv; j.live_rows = bt.live_rows;
     j.table = P.l_glove; j.vocab = dims.base.Vq; j.T = dims.base.L; j.head = 0;
-    j.P = P.gru;
+    j.t = GruTape(c, j.in, j.scr, "", j.T, 2 * (int64_t)c.d.B * c.d.n, c.d.H, c.d.W, P.gru, c.st);
     if (G != nullptr) { j.g_table = G->l_glove; j.G = G->gru; }
     q.n = 1;
     if (hs.rank[2] < 0) return q;
@@ -744,61 +724,52 @@ SeqSet make_seqs(const vqa_pretrain_ext_dims_t& dims, const Params& P, const Par
     for (int k = 0; k < 2; ++k) { e.tokens[k] = bx->ctx[k].context; e.len[k] = bx->ctx[k].context_len; }
     e.perm = bx->ctx_perm; e.inv = bx->ctx_inv; e.live_rows = bx->ctx_live_rows;
     e.table = P.enwiki_map; e.vocab = dims.n_ctx; e.T = dims.Lc; e.head = 2 * hs.rank[2];
-    e.P = P.egru;
+    e.t = GruTape(c, e.in, e.scr, "", e.T, 2 * (int64_t)c.d.B * c.d.n, c.d.H, c.d.W, P.egru, c.st);
     if (G != nullptr) { e.g_table = G->enwiki_map; e.G = G->egru; }
     q.n = 2;
     return q;
-}
-
-// the x rows of the two GRU kernels side by side: one projection GEMM for all steps
-int seq_pack_wx(const Ctx& c, const Seq& s) {
-    return vqa_gru_pack_wx(s.P.wg, s.P.wc, s.P.bg, s.P.bc, c.f(s.scr + "wx_cat"), c.f(s.scr + "bx_cat"), (int)c.d.W, (int)c.d.H,
-                           c.st);
 }
 
 // pack_wx false: the caller has packed the x rows already (the caption batch: the step's first launch)
 int seq_fwd(const Ctx& c, const Seq& s, bool pack_wx) {
     const int64_t H = c.d.H, W = c.d.W, Bn = (int64_t)c.d.B * c.d.n, B2 = 2 * Bn, T = s.T;
     ProbeScope ps(s.fwd_label, c.st);
-    if (pack_wx) TRY(seq_pack_wx(c, s));
+    const GruTape& t = s.t;
+    if (pack_wx) TRY(t.pack_wx());
     int32_t *tok = c.i32(s.in + s.tok), *lens = c.i32(s.in + "lens_s");
-    float *x_tm = c.f(s.in + "x_tm"), *xp = c.f(s.in + "xp"), *hs = c.f(s.in + "hs");
-    float *r = c.f(s.in + "gru_r"), *u = c.f(s.in + "gru_u"), *cc = c.f(s.in + "gru_c"), *rh = c.f(s.in + "gru_rh");
     TRY(gather_rows2(s.tokens[0], s.tokens[1], s.perm, tok, B2, T, Bn, c.st));
     TRY(gather_rows2(s.len[0], s.len[1], s.perm, lens, B2, 1, Bn, c.st));
-    TRY(vqa_embed_fwd_ld(s.table, tok, x_tm, (int)B2, (int)T, (int)W, s.vocab, (int)x_stride(W), c.st));
-    TRY(c.gemm_f32(0, 0, T * B2, 3 * H, W, x_tm, (int)x_stride(W), c.f(s.scr + "wx_cat"), (int)(3 * H), xp, (int)(3 * H),
-                   c.f(s.scr + "bx_cat")));
-    if (hipMemsetAsync(hs, 0, (size_t)B2 * H * sizeof(float), c.st) != hipSuccess) return VQA_ERR_LAUNCH;
-    const float *Wg_h = s.P.wg + W * 2 * H, *Wc_h = s.P.wc + W * H;
+    TRY(vqa_embed_fwd_ld(s.table, tok, t.x_tm, (int)B2, (int)T, (int)W, s.vocab, t.ldx(), c.st));
+    TRY(t.project(c.f32()));
+    TRY(t.clear_h0());
     if (s.live_rows != nullptr)
-        TRY(vqa_gru_seq_fwd_live(xp, Wg_h, Wc_h, lens, s.live_rows, hs, r, u, cc, rh, (int)T, (int)B2, (int)H, c.st));
-    else
-        TRY(vqa_gru_seq_fwd(xp, Wg_h, Wc_h, lens, hs, r, u, cc, rh, (int)T, (int)B2, (int)H, c.st));
-    return gather_rows(hs + T * B2 * H, s.inv, c.f("S/lft") + s.head * Bn * H, B2, H, c.st);      // back to the given order
-}
-
-// phase 2: back-propagation through time from the two "d_lft" slices, the GRU kernels' and biases' gradients
-int seq_bptt(const Ctx& c, Acc& acc, const Seq& s) {
-    const int64_t H = c.d.H, W = c.d.W, Bn = (int64_t)c.d.B * c.d.n, B2 = 2 * Bn, T = s.T, Wp = x_stride(W);
-    const int ld3 = (int)(3 * H);
-    ProbeScope ps(s.bptt_label, c.st);
-    const int32_t* lens = c.i32(s.in + "lens_s");
-    const float *hs = c.f(s.in + "hs"), *r = c.f(s.in + "gru_r"), *u = c.f(s.in + "gru_u"), *cc = c.f(s.in + "gru_c");
-    float *d_state = c.f(s.scr + "d_state_s"), *dxp = c.f(s.scr + "dxp"), *dwx = c.f(s.scr + "dwx_cat");
-    TRY(gather_rows(c.f("d_lft") + s.head * Bn * H, s.perm, d_state, B2, H, c.st));      // into the sorted order
-    const float *Wg_h = s.P.wg + W * 2 * H, *Wc_h = s.P.wc + W * H;
-    if (s.live_rows != nullptr)
-        TRY(vqa_gru_seq_bwd_live(d_state, Wg_h, Wc_h, lens, s.live_rows, hs, r, u, cc, dxp, c.f("d_hscratch"), (int)T,
+        TRY(vqa_gru_seq_fwd_live(t.xp, t.Wg_h(), t.Wc_h(), lens, s.live_rows, t.hs, t.gru_r, t.gru_u, t.gru_c, t.gru_rh, (int)T,
                                  (int)B2, (int)H, c.st));
     else
-        TRY(vqa_gru_seq_bwd(d_state, Wg_h, Wc_h, lens, hs, r, u, cc, dxp, c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
-    // x rows of both kernels' gradients as one GEMM into the packed [Wp, 3H] block; x_tm carries the constant 1 in
-    // column W, so row W of the block is the two bias gradients and dxp is not read again for them
-    TRY(acc.weight(PREC_F32, dwx, c.f(s.in + "x_tm"), (int)Wp, dxp, ld3, Wp, 3 * H, T * B2));
-    TRY(acc.weight(PREC_F32, s.G.wg + W * 2 * H, hs, (int)H, dxp, ld3, H, 2 * H, T * B2));
-    TRY(acc.weight(PREC_F32, s.G.wc + W * H, c.f(s.in + "gru_rh"), (int)H, dxp + 2 * H, ld3, H, H, T * B2));
-    return vqa_gru_unpack_dwx_bias(dwx, s.G.wg, s.G.wc, s.G.bg, s.G.bc, (int)W, (int)H, c.st);
+        TRY(vqa_gru_seq_fwd(t.xp, t.Wg_h(), t.Wc_h(), lens, t.hs, t.gru_r, t.gru_u, t.gru_c, t.gru_rh, (int)T, (int)B2, (int)H,
+                            c.st));
+    return gather_rows(t.h_final(), s.inv, c.f("S/lft") + s.head * Bn * H, B2, H, c.st);      // back to the given order
+}
+
+// phase 2: back-propagation through time from the two "d_lft" slices, the GRU kernels' and biases' gradients (the x rows
+// and biases unpacked after the two recurrent blocks)
+int seq_bptt(const Ctx& c, Acc& acc, const Seq& s) {
+    const int64_t H = c.d.H, Bn = (int64_t)c.d.B * c.d.n, B2 = 2 * Bn, T = s.T;
+    ProbeScope ps(s.bptt_label, c.st);
+    const GruTape& t = s.t;
+    const int32_t* lens = c.i32(s.in + "lens_s");
+    float* d_state = c.f(s.scr + "d_state_s");
+    TRY(gather_rows(c.f("d_lft") + s.head * Bn * H, s.perm, d_state, B2, H, c.st));      // into the sorted order
+    if (s.live_rows != nullptr)
+        TRY(vqa_gru_seq_bwd_live(d_state, t.Wg_h(), t.Wc_h(), lens, s.live_rows, t.hs, t.gru_r, t.gru_u, t.gru_c, t.dxp,
+                                 c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
+    else
+        TRY(vqa_gru_seq_bwd(d_state, t.Wg_h(), t.Wc_h(), lens, t.hs, t.gru_r, t.gru_u, t.gru_c, t.dxp, c.f("d_hscratch"), (int)T,
+                            (int)B2, (int)H, c.st));
+    TRY(t.dwx(acc.f32()));
+    TRY(t.dwh(acc.f32(), s.G, false, 0));
+    TRY(t.dwh(acc.f32(), s.G, true, 0));
+    return t.unpack_dwx(s.G);
 }
 
 // running sum of squares of the un-aggregated embedding slices
@@ -814,13 +785,14 @@ struct SliceSq {
 
 // phase 4: dx of the packed x-projection -> scatter-add into the (cleared) embedding gradient, slice sum of squares
 int seq_embed_bwd(const Ctx& c, const Seq& s, SliceSq& sq) {
-    const int64_t H = c.d.H, W = c.d.W, B2 = 2 * (int64_t)c.d.B * c.d.n, T = s.T;
+    const int64_t W = c.d.W, B2 = 2 * (int64_t)c.d.B * c.d.n, T = s.T;
     ProbeScope ps(s.embed_label, c.st);
     if (hipMemsetAsync(s.g_table, 0, (size_t)s.vocab * W * 4, c.st) != hipSuccess) return VQA_ERR_LAUNCH;
     float* dx = c.f(s.scr + "dx");
+    const GruTape& t = s.t;
     // packed again here (one small kernel): no hidden dependence on the forward's copy of the weights
-    TRY(seq_pack_wx(c, s));
-    TRY(c.gemm_f32(0, 1, T * B2, W, 3 * H, c.f(s.scr + "dxp"), (int)(3 * H), c.f(s.scr + "wx_cat"), (int)(3 * H), dx, (int)W));
+    TRY(t.pack_wx());
+    TRY(t.dx(c.f32(), dx));
     TRY(vqa_embed_bwd_len_det(dx, c.i32(s.in + s.tok), c.i32(s.in + "lens_s"), s.g_table, (int)B2, (int)T, (int)W, s.vocab,
                               (c.d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
     return sq.add(dx, T * B2 * W);
@@ -832,8 +804,8 @@ int trunk_fwd(const Ctx& c, const Model& m, const Params& P, const Batch& b, con
     const vqa_pretrain_dims_t* d = &m.dims.base;
     const vqa_pretrain_batch_t* bt = &b.x.base;
     const int64_t B = d->B, n = d->n, R = d->R, D = pm.width, H = d->H, W = d->W, Bn = B * n;
-    const SeqSet q = make_seqs(m.dims, P, nullptr, b, hs);
-    TRY(seq_pack_wx(c, q.s[0]));
+    const SeqSet q = make_seqs(c, m.dims, P, nullptr, b, hs);
+    TRY(q.s[0].t.pack_wx());
     for (int k = 0; k < 2; ++k) {
         const vqa_pretrain_kind_t& kb = bt->kind[k];
         const std::string p = std::string(KIND[k]) + "/";
@@ -873,7 +845,7 @@ int trunk_bwd(const Ctx& c, Acc& acc, const Model& m, const Params& P, const Par
     const int det = (d->flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0;
     // the embedding tables are scatter-added: cleared in their phase; every other gradient is overwritten on first touch
     SliceSq sq{c, nullptr};
-    const SeqSet q = make_seqs(m.dims, P, &G, b, hs);
+    const SeqSet q = make_seqs(c, m.dims, P, &G, b, hs);
     for (int i = 0; i < q.n && (phases & 2); ++i) TRY(seq_bptt(c, acc, q.s[i]));
     for (int i = 0; i < q.n && (phases & 4); ++i) TRY(seq_embed_bwd(c, q.s[i], sq));
     if (phases & 8) {
@@ -1124,7 +1096,7 @@ int forward(const Model& m, const Params& P, const Batch& b, void* workspace, in
     Layout L;
     TRY(prologue(m, P, nullptr, b, workspace, workspace_bytes, ALL_PHASES, keep, &L));      // a forward has no phases
     const HeadSet hs(m.dims.heads);
-    const Ctx c{m.dims.base, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
+    const Ctx c{{L, static_cast<char*>(workspace)}, m.dims.base, static_cast<hipStream_t>(stream), keep};
     ReportExtArgs ra{};
     ra.rows = c.d.B * c.d.n;
     ProbeScope ps_all(m.fwd_label(), c.st);
@@ -1152,7 +1124,7 @@ int backward(const Model& m, const Params& P, const Params& G, const Batch& b, v
     Layout L;
     TRY(prologue(m, P, &G, b, workspace, workspace_bytes, phases, keep, &L));
     const HeadSet hs(m.dims.heads);
-    const Ctx c{m.dims.base, L, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), keep};
+    const Ctx c{{L, static_cast<char*>(workspace)}, m.dims.base, static_cast<hipStream_t>(stream), keep};
     ProbeScope ps_all(m.bwd_label(), c.st);
     Acc acc{c, {}};
     const PoolMem pm = pool_mem(c, m, b);

@@ -111,7 +111,8 @@ int vqa_gemm_f32_ex(int transA, int transB, int M, int N, int K, const float* A,
  * (vqa/model_vlmap_answer.py:110-117 + 126-129).  gathered_out (may be NULL; ld = ldg) receives the gathered rows
  * [M, K] as a by-product for the consumers that re-read V_ft (attention pooling, its backward, dW of v_linear_v).
  * Out-of-range indices are clamped like vqa_gather_features.  Needs K % 32 == 0, N % 4 == 0 and 16-byte aligned
- * operands; the table itself may be larger than 4 GiB. */
+ * operands.  A table below 4 GiB is read through 32-bit per-lane offsets like a dense left operand; a larger one
+ * through per-lane 64-bit pointers.  Same tile and k order as vqa_gemm_f32 under the same tall configuration. */
 int vqa_gemm_f32_gather(int M, int N, int K, const float* table, int lda, const int64_t* idx, int R,
                         int64_t n_samples_in_table, const float* B, int ldb, float* C, int ldc, const float* bias,
                         float* gathered_out, int ldg, void* stream);
@@ -125,6 +126,9 @@ int vqa_gemm_set_config(int cfg);
 int vqa_gemm_set_gru_config(int cfg);
 /* tile shape of the tall-activation GEMMs (M >= 2048, N >= 512, K >= 2048): 20 = 128x64 (default), 21 = 64x128 */
 int vqa_gemm_set_tall_config(int cfg);
+/* tuning / tests: 1 = vqa_gemm_f32_gather reads every table through 64-bit pointers (the form of tables >= 4 GiB),
+ * 0 = by the table's size (default) */
+int vqa_gemm_set_gather_ptr(int on);
 
 /* ------------------------------------------- a2,a5,a8,a9 : LN + ReLU (+dropout)
  * y = relu(layer_norm(pre)) [* keepmask / keep]  with statistics over groups of
@@ -586,8 +590,10 @@ typedef struct {
 #define VQA_MODEL_LEGACY_VQA 13
 #define VQA_FLAG_DETERMINISTIC 1   /* embedding-gradient scatter-add without atomics: bitwise reproducible steps */
 #define VQA_FLAG_FUSED_GATHER 2     /* no gather pass: v_linear_v's GEMM reads the table rows through image_idx
-                                     * (vqa_gemm_f32_gather) and leaves V_ft behind as a by-product; default: a gather
-                                     * pass in front of the GEMM (same step time, see csrc/fusion_model.hip) */
+                                     * (vqa_gemm_f32_gather) and leaves V_ft behind as a by-product, whatever the shape.
+                                     * Without the flag the step fuses by itself where the fused kernel is the plain
+                                     * GEMM's own tile (gather_mode() in csrc/fusion_model.hip) and runs a gather pass
+                                     * in front of the GEMM everywhere else */
 #define VQA_FLAG_SHARED_LN 4        /* cfg-5 model only: one LayerNorm per shared fc_layer scope (see vqa_pt_fc_t) */
 #define VQA_FLAG_BF16_GEMM 8        /* opt-in mixed precision of the fusion model's train / eval step: f32 master weights, f32
                                      * activations and gradients in HBM, f32 accumulation, bf16 operands in the matrix unit

@@ -183,6 +183,7 @@ SIGNATURES = {
     "vqa_gemm_f32_ex": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _L, _I, _P]),
     "vqa_gemm_f32_gather": (_I, [_I, _I, _I, _P, _I, _P, _I, _L, _P, _I, _P, _I, _P, _P, _I, _P]),
     "vqa_gemm_set_tall_config": (_I, [_I]),
+    "vqa_gemm_set_gather_ptr": (_I, [_I]),
     "vqa_gemm_set_max_blocks": (_I, [_I]),
     "vqa_gemm_set_order": (_I, [_I]),
     "vqa_gemm_set_config": (_I, [_I]),

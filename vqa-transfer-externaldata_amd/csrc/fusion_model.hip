@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "gemm_args.h"
 #include "gru_encoder.h"
 #include "keep_launch.h"
 
@@ -247,12 +248,20 @@ int side_max_blocks() {
     }
     return v;
 }
-// how V_ft = features[image_idx] is produced: 0 = a gather pass in front of v_linear_v's GEMM (default), 1 = fused
-// into that GEMM's operand load (VQA_FLAG_FUSED_GATHER or VQA_HOT_GATHER=fused).  Measured at bs 512
-// (profiles/r2_gather_mode_ab.txt, r2_gather_gemm_bench.txt): 3.73 ms per step either way -- the 46 us gather pass
-// doubles as a prefetch of V_ft into the Infinity Cache, from where the GEMM streams its left operand 37 us faster than
-// the fused form streams it from HBM.  A third form, the gather on a helper stream beside the question branch's
-// projection GEMMs, lost 0.13 ms to the cross-stream fork / join.
+// how V_ft = features[image_idx] is produced: 0 = a gather pass in front of v_linear_v's GEMM, 1 = fused into that GEMM's
+// operand load whatever the shape (VQA_FLAG_FUSED_GATHER or VQA_HOT_GATHER=fused), 2 = automatic (the variable unset, the
+// flag clear): fused exactly where vqa_gemm_gather_matches_plain() holds, i.e. where the plain product would run the
+// tall tile the fused kernel is built on (M >= 2048, N >= 512, K >= 2048, at least 1024 tiles: the same tile and k order,
+// so pre_v and everything behind it keep their bits) and the table fits the 32-bit offsets of a buffer descriptor; a pass
+// everywhere else.  Any other value of VQA_HOT_GATHER forces the pass.
+// Measured at the bench shape (profiles/r22_gather_gemm.txt): plain GEMM 536 us, pass + GEMM 583, fused through offsets
+// with the by-product 552 -- the gathered load itself is free (539 without the by-product code), on a cache-resident table
+// as on the 2.4 GB one, so lookahead for a cold operand was not built.  What the earlier fused kernel lost against the
+// plain one was not Infinity-Cache residency of V_ft: it ran without the SIMD-partner stagger and with a workgroup-
+// uniform test around the by-product stores inside its loop.
+// A table of 4 GiB or more needs per-lane 64-bit pointers; that form measures 584 us, no better than pass + GEMM, so
+// the automatic mode never selects it.  A third form, the gather on a helper stream beside the question branch's
+// projection GEMMs, lost 0.13 ms to the cross-stream fork / join (profiles/r2_gather_mode_ab.txt).
 int gather_mode(const vqa_dims_t* dims) {
     static int env = -2;
     if (env == -2) {
@@ -260,7 +269,7 @@ int gather_mode(const vqa_dims_t* dims) {
         env = e == nullptr ? -1 : (strcmp(e, "fused") == 0 ? 1 : 0);
     }
     if (env >= 0) return env;
-    return (dims->flags & VQA_FLAG_FUSED_GATHER) ? 1 : 0;
+    return (dims->flags & VQA_FLAG_FUSED_GATHER) ? 1 : 2;
 }
 
 // ---- side stream: the v_linear_v branch (one big GEMM) runs beside the latency-bound GRU
@@ -755,7 +764,10 @@ void fwd_visual_plan(Step& s) {
     s.sd = &side_stream();
     s.forked = fork_side(s.c, *s.sd);
     // (dims_ok refuses the FLAG pair; VQA_HOT_GATHER=fused in the environment must not bring the f32 gather GEMM into a bf16 step either)
-    s.fuse_gather = !(s.d.flags & VQA_FLAG_BF16_GEMM) && gather_mode(&s.d) == 1 && (s.D % 32 == 0) && (s.H % 4 == 0) &&
+    const int gm = gather_mode(&s.d);
+    const bool same_kernel = gm == 2 && side_max_blocks() == 0 &&
+                             vqa_gemm_gather_matches_plain((int)(s.B * s.R), (int)s.H, (int)s.D, (int)s.D, (int)s.R, s.d.N_img);
+    s.fuse_gather = !(s.d.flags & VQA_FLAG_BF16_GEMM) && (gm == 1 || same_kernel) && (s.D % 32 == 0) && (s.H % 4 == 0) &&
                     vqa_aligned16(s.bt->table);
     s.visual_late = !s.forked && visual_late_enabled();
 }

@@ -51,6 +51,9 @@ struct EpiArgs {
 // gemm_f32.hip: the argument block of C = A B (+ bias) (+ D); operand extents and tile grid are filled by the launch
 GemmArgs vqa_gemm_make_args(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                             const float* bias, const float* D, int ldd);
+// gemm_f32.hip: vqa_gemm_f32_gather on this problem is vqa_gemm_f32's own kernel configuration (tile, k order, no split)
+// with another row behind every lane, and the table fits the 32-bit offsets of a buffer descriptor
+bool vqa_gemm_gather_matches_plain(int M, int N, int K, int lda, int R, int64_t n_samples_in_table);
 // gemm_f32.hip: one fused GRU-step GEMM, epilogue `epi` (EPI_GATES .. EPI_BWD_DH), tile config `cfg` (4, 7..13, 16..18,
 // 20, 21; 30 = vqa_gru_rs_launch, falling back to 16 for the shapes it does not take)
 int vqa_gru_step_launch(int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);

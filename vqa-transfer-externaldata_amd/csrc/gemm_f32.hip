@@ -148,8 +148,10 @@ struct Stager {
             }
         }
     }
-    // row-gathered operand: every lane carries the 64-bit address of its row piece (rows of one tile come from
-    // anywhere in a table that may exceed a buffer descriptor's 4 GiB), the k advance is a uniform element offset
+    // row-gathered operand of a table beyond a buffer descriptor's 4 GiB: every lane carries the 64-bit address of its
+    // row piece, the k advance is a uniform element offset (a signed int on a float pointer: one 64-bit add per load and
+    // pair of k tiles in the unrolled loop, the second tile's 128 bytes ride in the load's immediate offset; an
+    // unsigned byte offset costs that add on every tile)
     // (The load goes through a native vector type: assigning HIP's float4 struct from a dereferenced pointer keeps
     // the whole stager object in scratch memory -- hipcc does not scalarise that copy.)
     __device__ __forceinline__ void load_ptr(const float* const (&src)[NV], int koff) {
@@ -252,13 +254,17 @@ __device__ __forceinline__ float4 frag4(const float* s, int r0, int c, int lane)
 }
 
 template <int BM, int BN, int WM, int WN, int WGK, int BK, int DEEP, bool A_KC, bool B_KC, int EPI, bool CONV = false,
-          bool EDGE = false, int NT = 256, bool GATHER = false>
+          bool EDGE = false, int NT = 256, int GATHER = 0>
 // (the 4-wave implicit-GEMM form lands on 113 + 16 registers, one allocation granule above four waves per SIMD: ask for
 // four, i.e. four co-resident workgroups per CU instead of three -- the compiler gets there without spilling, and the
 // extractor gains 1.5 %.  The same request for the 64x64 two-tile-prefetch form (121 + 16) measured 0.5 % SLOWER
 // on the pre-training step, same box, two builds: left alone.)
 __global__ __launch_bounds__(NT, (CONV && NT == 256) ? 4 : 1) void gemm_f32_kernel(GemmArgs p, EpiArgs ep) {
+    // GATHER: 0 = A is a dense matrix; row-gathered A (vqa_gemm_f32_gather): 2 = the table fits one buffer descriptor and
+    // a lane's row piece is a 32-bit byte offset, i.e. the plain kernel's loop with another row behind every lane;
+    // 1 = larger tables, per-lane 64-bit addresses
     static_assert(!GATHER || (A_KC && DEEP == 0 && !CONV && !EDGE && EPI == EPI_PLAIN), "row-gathered A: plain NN/NT tiles");
+    static_assert(!GATHER || Stager<BM, BK, A_KC, NT>::EXACT, "row-gathered A: every thread owns whole float4s of the tile");
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int WAVES_M = BM / WM, WAVES_N = BN / WN;
     static_assert(WAVES_M * WAVES_N * WGK * 64 == NT, "one 32x32-tiled wave per (m, n, k-group) slot");
@@ -414,7 +420,7 @@ __global__ __launch_bounds__(NT, (CONV && NT == 256) ? 4 : 1) void gemm_f32_kern
         unsigned gdst[NVA];
         const bool g_store = GATHER && p.g_out != nullptr && n0 == 0;      // workgroup-uniform
         const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(
-            p.g_out, 0, GATHER && p.g_out != nullptr ? (int)(((int64_t)(p.M - 1) * p.g_ldo + p.K) * 4) : 0, 0x00020000);
+            p.g_out, 0, g_store ? (int)(((int64_t)(p.M - 1) * p.g_ldo + p.K) * 4) : 0, 0x00020000);
         if (GATHER) {      // host guarantees K % BK == 0 and no split-k: every tile is full
 #pragma unroll
             for (int i = 0; i < NVA; ++i) {
@@ -424,12 +430,15 @@ __global__ __launch_bounds__(NT, (CONV && NT == 256) ? 4 : 1) void gemm_f32_kern
                 const int smp = mc / p.g_R, reg_row = mc - smp * p.g_R;
                 int64_t src = p.g_idx[smp];
                 src = src < 0 ? 0 : (src >= p.g_N ? p.g_N - 1 : src);        // np.take would raise; clamp like vqa_gather_features
-                gsrc[i] = p.A + (src * p.g_R + reg_row) * (int64_t)p.lda + kq;
+                const int64_t el = (src * p.g_R + reg_row) * (int64_t)p.lda + kq;
+                gsrc[i] = p.A + el;
+                if (GATHER == 2) sa.voff[i] = (unsigned)(el * 4);             // the host keeps the table below 4 GiB
                 gdst[i] = (m < p.M) ? (unsigned)(((int64_t)m * p.g_ldo + kq) * 4) : Stager<BM, BK, A_KC, NT>::OOB;
             }
         }
         auto load_a = [&](int k0) {
-            if (GATHER) sa.load_ptr(gsrc, k0 - kbeg);
+            if (GATHER == 2) sa.load_full(rsA, (unsigned)(k0 - kbeg) * 4u);
+            else if (GATHER) sa.load_ptr(gsrc, k0 - kbeg);
             else if (CONV) sa.load_conv(rsA, iy0, ix0, pix, k0, p.Hi, p.Wi, p.Ci, p.kw);
             else if (EDGE) sa.load(p.A, p.lda, m0, k0, p.M, kend, va);
             else sa.load_fast(rsA, p.lda, m0, k0, p.M, kend);
@@ -496,125 +505,17 @@ __global__ __launch_bounds__(NT, (CONV && NT == 256) ? 4 : 1) void gemm_f32_kern
                 __syncthreads();
             }
         }
-        if (!CONV && !EDGE) {
-            // full tiles, two per trip so both LDS buffers are compile-time addresses
-            sa.init_full(p.lda, m0, kbeg, p.M);
-            sb.init_full(p.ldb, n0, kbeg, p.N);
-            const unsigned stepA = (unsigned)(A_KC ? BK : BK * p.lda) * 4u;
-            const unsigned stepB = (unsigned)(B_KC ? BK : BK * p.ldb) * 4u;
-            const int nfull = (kend - kbeg) / BK;
-            unsigned oa = stepA, ob = stepB;   // scalar byte offsets of tile t + 1
-            // Stagger (8-wave workgroups: waves w and w + 4 share a SIMD and, running the same program with one
-            // barrier per k tile, reach their MFMA burst, their LDS traffic and the barrier together).  Inside one
-            // barrier interval "compute tile t from one LDS buffer" and "store tile t+1 into the other" commute, so
-            // waves 4..7 run the interval as store(t+1) -> fetch(t+2) -> compute(t) while waves 0..3 keep
-            // fetch(t+1) -> compute(t) -> store(t+1): a SIMD's two waves of this workgroup alternate between the
-            // MFMA burst and the LDS/global phase instead of colliding in both.  Same barrier count on both paths;
-            // one entry fetch and one transition interval bring waves 4..7 in and out of the half-interval lead.
-            // Compiled in only where it pays and costs no occupancy: the 128x64 / 64x128 tiles of 32x32 waves with BK 32
-            // (95 -> 99 registers, still two workgroups per CU) and the 128x128 BK-16 weight-gradient tile; in the
-            // 128x128 BK-32 kernel the second loop body costs 6 registers and with them its second workgroup per CU
-            // (124 -> 130: the extractor's 1x1 layers lost 1.3 % until this was fenced off).
-            constexpr bool STAG = (NT == 512) && !GATHER && EPI == EPI_PLAIN && (VQA_GEMM_STAGGER != 0) &&
-                                  ((WM == 32 && WN == 32 && BK == 32 && BM + BN == 192) || (BM == 128 && BN == 128 && BK == 16));
-            // Long k loops only: on the roofline GEMM (64 tiles) the k loop gets 2 % shorter (552 -> 541 us, same
-            // box, two builds); on the extractor's short-k 1x1 layers (4..8 tiles) the entry fetch and the transition
-            // interval cost more than the stagger returns (2064 -> 2043 imgs/s).  profiles/r2_stagger_ab.txt
-            const bool stag_wg = STAG && nfull >= 16;                 // workgroup-uniform
-            if (stag_wg && wave >= 4) {
-                // (a static s_setprio 1 for this second-dispatched half, the guide's companion rule, made the roofline
-                // GEMM 2 % SLOWER here: 563 -> 574 us, same box, two builds)
-                sa.load_full(rsA, oa); sb.load_full(rsB, ob);         // tile 1 into the staging registers
-                oa += stepA; ob += stepB;
-                for (; t + 3 < nfull; t += 2) {
-                    sa.store(L1); sb.store(L1 + A_FL);                // tile t + 1
-                    sa.load_full(rsA, oa); sb.load_full(rsB, ob);     // tile t + 2
-                    oa += stepA; ob += stepB;
-                    __builtin_amdgcn_sched_barrier(0);
-                    compute_tile(L0, L0 + A_FL);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __syncthreads();
-                    sa.store(L0); sb.store(L0 + A_FL);                // tile t + 2
-                    sa.load_full(rsA, oa); sb.load_full(rsB, ob);     // tile t + 3
-                    oa += stepA; ob += stepB;
-                    __builtin_amdgcn_sched_barrier(0);
-                    compute_tile(L1, L1 + A_FL);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __syncthreads();
-                }
-                sa.store(L1); sb.store(L1 + A_FL);                    // transition: tile t + 1 (< nfull) is in the registers
-                __builtin_amdgcn_sched_barrier(0);
-                compute_tile(L0, L0 + A_FL);
-                __builtin_amdgcn_sched_barrier(0);
-                __syncthreads();
-                ++t;
-            } else if (stag_wg) {
-                for (; t + 3 < nfull; t += 2) {                       // the same trip count as the waves above
-                    sa.load_full(rsA, oa); sb.load_full(rsB, ob);
-                    oa += stepA; ob += stepB;
-                    __builtin_amdgcn_sched_barrier(0);
-                    compute_tile(L0, L0 + A_FL);
-                    __builtin_amdgcn_sched_barrier(0);
-                    sa.store(L1); sb.store(L1 + A_FL);
-                    __syncthreads();
-                    sa.load_full(rsA, oa); sb.load_full(rsB, ob);
-                    oa += stepA; ob += stepB;
-                    __builtin_amdgcn_sched_barrier(0);
-                    compute_tile(L1, L1 + A_FL);
-                    __builtin_amdgcn_sched_barrier(0);
-                    sa.store(L0); sb.store(L0 + A_FL);
-                    __syncthreads();
-                }
-                sa.load_full(rsA, oa); sb.load_full(rsB, ob);         // transition interval
-                __builtin_amdgcn_sched_barrier(0);
-                compute_tile(L0, L0 + A_FL);
-                __builtin_amdgcn_sched_barrier(0);
-                sa.store(L1); sb.store(L1 + A_FL);
-                __syncthreads();
-                ++t;
-            }
-            for (; !stag_wg && t + 2 < nfull; t += 2) {
-                if (GATHER) sa.load_ptr(gsrc, (t + 1) * BK); else sa.load_full(rsA, oa);
-                sb.load_full(rsB, ob);
-                oa += stepA; ob += stepB;
-                __builtin_amdgcn_sched_barrier(0);
-                compute_tile(L0, L0 + A_FL);
-                __builtin_amdgcn_sched_barrier(0);
-                sa.store(L1);
-                sb.store(L1 + A_FL);
-                if (g_store) sa.store_buf(rsG, gdst, (unsigned)((t + 1) * BK) * 4u);
-                __syncthreads();
-                if (GATHER) sa.load_ptr(gsrc, (t + 2) * BK); else sa.load_full(rsA, oa);
-                sb.load_full(rsB, ob);
-                oa += stepA; ob += stepB;
-                __builtin_amdgcn_sched_barrier(0);
-                compute_tile(L1, L1 + A_FL);
-                __builtin_amdgcn_sched_barrier(0);
-                sa.store(L0);
-                sb.store(L0 + A_FL);
-                if (g_store) sa.store_buf(rsG, gdst, (unsigned)((t + 2) * BK) * 4u);
-                __syncthreads();
-            }
-        }
-        // remaining tiles (all of them for the conv / edge loaders) without conditionals, the last
-        // one peeled: loads of tile t+1 are issued before tile t's MFMA loop and consumed after it
-        for (; t + 1 < nt; ++t) {
-            float* cur = (t & 1) ? L1 : L0;
-            float* nxt = (t & 1) ? L0 : L1;
-            load_a(kbeg + (t + 1) * BK);
-            load_b(kbeg + (t + 1) * BK);
-            __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ABOVE the MFMA loop (hipcc sinks it otherwise)
-            compute_tile(cur, cur + A_FL);
-            __builtin_amdgcn_sched_barrier(0);
-            sa.store(nxt);
-            sb.store(nxt + A_FL);
-            if (g_store) sa.store_buf(rsG, gdst, (unsigned)((t + 1) * BK) * 4u);
-            __syncthreads();
-        }
-        if (nt > 0) {
-            float* cur = ((nt - 1) & 1) ? L1 : L0;
-            compute_tile(cur, cur + A_FL);
-            __syncthreads();
+        // the other k loops (gemm_f32_kloops.inc).  The offset form of the row-gathered kernel gets two copies, with and without
+        // the by-product stores; the pointer form keeps one copy with the workgroup-uniform test inside (two copies
+        // measured no faster there)
+        if (GATHER == 2 && g_store) {
+#define VQA_KLOOPS_GS true
+#include "gemm_f32_kloops.inc"
+#undef VQA_KLOOPS_GS
+        } else {
+#define VQA_KLOOPS_GS (GATHER == 1 && g_store)
+#include "gemm_f32_kloops.inc"
+#undef VQA_KLOOPS_GS
         }
     } else {
         // two tiles of register prefetch (two stager sets, loop unrolled by 2 so every register
@@ -962,7 +863,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 template <int BM, int BN, int WM, int WN, int WGK, int BK, int DEEP, bool A_KC, bool B_KC, int EPI, bool CONV = false,
-          bool EDGE = false, int NT = 256, bool GATHER = false>
+          bool EDGE = false, int NT = 256, int GATHER = 0>
 int launch_one(GemmArgs a, const EpiArgs& ep, int split, hipStream_t st, int max_blocks = 0) {
     constexpr size_t tiles = 2 * (tile_floats<BM, BK, A_KC>() + tile_floats<BN, BK, B_KC>()) * sizeof(float);
     constexpr size_t red = (EPI == EPI_PLAIN) ? (size_t)(WGK - 1) * (BM / WM) * (BN / WN) * (WM / 32) * (WN / 32) * 16 * 64 * sizeof(float) : 0;
@@ -1113,6 +1014,7 @@ int g_force_cfg = -1;   // tuning override (vqa_gemm_set_config)
 // as 64x128 (cfg 21: 551 vs 553 us) and halve the B panel every tile streams (512 KB instead of 1 MB), i.e. the
 // L2<->fabric traffic of the weight matrix, which no XCD's 4 MiB L2 can hold (8 MB).
 int g_tall_cfg = 20;
+bool g_gather_ptr = false;   // vqa_gemm_set_gather_ptr: the row-gathered GEMM addresses every table through 64-bit pointers
 int g_max_blocks = 0;   // tuning override for vqa_gemm_f32 (vqa_gemm_set_max_blocks)
 int g_conv_cfg = -1;    // tile config of the implicit-GEMM convolutions (vqa_conv_set_config); -1 = by shape
 int g_conv_cfg_plain = -1;
@@ -1345,7 +1247,11 @@ extern "C" int vqa_gemm_f32_gather(int M, int N, int K, const float* table, int 
     GemmArgs a = vqa_gemm_make_args(M, N, K, table, lda, B, ldb, C, ldc, bias, nullptr, 0);
     const int64_t bb = ((int64_t)(K - 1) * ldb + N) * 4;
     VQA_REQUIRE(bb < 0xFFFFFF00ll, VQA_ERR_UNSUPPORTED);
-    a.a_bytes = 0;                     // A is addressed through per-lane 64-bit pointers (the table may exceed 4 GiB)
+    // a table that fits one buffer descriptor is read like a dense A, through 32-bit per-lane offsets; a larger one
+    // (or any, under vqa_gemm_set_gather_ptr) through per-lane 64-bit pointers
+    const int64_t ab = ((n_samples_in_table * R - 1) * (int64_t)lda + K) * 4;
+    const bool by_offset = !g_gather_ptr && ab < 0xFFFFFF00ll;
+    a.a_bytes = by_offset ? (unsigned)ab : 0;
     a.b_bytes = (unsigned)bb;
     VQA_REQUIRE(gathered_out == nullptr || ((int64_t)(M - 1) * ldg + K) * 4 < 0xFFFFFF00ll, VQA_ERR_UNSUPPORTED);
     a.g_idx = idx; a.g_R = R; a.g_N = n_samples_in_table; a.g_out = gathered_out; a.g_ldo = ldg;
@@ -1353,8 +1259,25 @@ extern "C" int vqa_gemm_f32_gather(int M, int N, int K, const float* table, int 
     const EpiArgs ep{};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (g_tall_cfg == 21)
-        return launch_one<64, 128, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, true>(a, ep, 1, st, 0);
-    return launch_one<128, 64, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, true>(a, ep, 1, st, 0);
+        return by_offset ? launch_one<64, 128, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 2>(a, ep, 1, st, 0)
+                         : launch_one<64, 128, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 1>(a, ep, 1, st, 0);
+    return by_offset ? launch_one<128, 64, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 2>(a, ep, 1, st, 0)
+                     : launch_one<128, 64, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 1>(a, ep, 1, st, 0);
+}
+
+extern "C" int vqa_gemm_set_gather_ptr(int on) {
+    g_gather_ptr = on != 0;
+    return VQA_OK;
+}
+
+// Whether vqa_gemm_f32_gather computes C = table[idx] B with the very kernel configuration vqa_gemm_f32 would take for the
+// dense product (same tile, same k order, no split: the same bits), and reads the table the cheap way (32-bit offsets).
+bool vqa_gemm_gather_matches_plain(int M, int N, int K, int lda, int R, int64_t n_samples_in_table) {
+    if (bf16x3_mode() || g_gather_ptr || K % 32 != 0 || N % 4 != 0) return false;
+    if (((n_samples_in_table * R - 1) * (int64_t)lda + K) * 4 >= 0xFFFFFF00ll) return false;
+    int cfg, split = 0;
+    choose(0, 0, M, N, K, cfg, split);
+    return cfg == g_tall_cfg && split == 1 && M >= 2048 && N >= 512 && K >= 2048;
 }
 
 extern "C" int vqa_gemm_set_tall_config(int cfg) {

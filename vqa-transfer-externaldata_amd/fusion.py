@@ -282,8 +282,9 @@ class FusionEngine(EngineCore):
         deterministic=True: run-to-run bitwise reproducible steps (the embedding-gradient scatter-add switches
         from float atomics to an atomic-free kernel, ~30 us slower at bs 512).  Per engine: the choice travels in
         vqa_dims_t.flags with every call, no process-wide library state is touched.
-        fused_gather=True: no feature-gather pass; v_linear_v's GEMM reads the table rows through image_idx
-        (vqa_gemm_f32_gather).  Same step time as the default at bs 512, 151 MB less HBM traffic.
+        fused_gather=True: no feature-gather pass at any shape; v_linear_v's GEMM reads the table rows through image_idx
+        (vqa_gemm_f32_gather).  With False the step still fuses by itself where that is the plain GEMM's own tile and the
+        table is below 4 GiB (the bench shape), and runs the pass everywhere else.
         num_marginal / ent_cols (vlmap_answer_ent): pairings per question, and how many leading head columns the
         regulariser computes (None: from the answer masks at bind_inputs -- 1 + the last known training answer).
         map_dim / ft_vlmap / glove_fixed / answers (model_type 'vqa', vqa/model_vqa.py): MAP_DIM of L2V / V2L; whether those

@@ -278,7 +278,8 @@ int vqa_gru_seq_fwd_ws_ex(const float* xp, const float* Wg_h, const float* Wc_h,
 /* The back-propagation through time in the same frame (one launch, W_g^T / W_c^T slabs resident): dxp [T,B,3H] =
  * (dr_pre | du_pre | dc_pre) from dh_T [B,H] -- read only here, unlike vqa_gru_seq_bwd -- and the forward tape; d_outs
  * [T,B,H] or NULL as in vqa_gru_seq_bwd_outs.  256 < B <= 512, H = 1024 (vqa_gru_ws_bwd_supported); `ws` as above (one
- * buffer may serve both directions). */
+ * buffer may serve both directions).  r, u, c of a row at t >= len are loaded but selected away, whatever they hold: the
+ * tape vqa_gru_seq_fwd_live leaves, with those values unwritten, is a valid input. */
 int vqa_gru_seq_bwd_ws(const float* dh_T, const float* d_outs, const float* Wg_h, const float* Wc_h, const int32_t* len,
                        const float* hs, const float* r, const float* u, const float* c, float* dxp, int T, int B, int H,
                        void* ws, void* stream);
@@ -721,6 +722,12 @@ int64_t vqa_fusion_workspace_bytes(const vqa_dims_t* dims);
  * l_linear_l, joint, logit, pred, stats, report, dx_embed, ...).  Elements are 4 bytes wide, except "V_ft" under
  * VQA_FLAG_BF16_FEATURES: n_elems = B * R * D elements of 2 bytes (raw bf16 patterns). */
 int vqa_fusion_tensor(const vqa_dims_t* dims, const char* name, int64_t* offset_bytes, int64_t* n_elems);
+/* Which form of the question GRU's recurrence a step of these dims runs for a batch with this live_rows (host int32[T] as in
+ * vqa_batch_t, or NULL), forward (backward = 0) or back-propagation (1): 0 = the weight-stationary launch, 1 = the
+ * per-step kernels on the live prefix, 2 = the per-step kernels on row chains.  The step's own decision (it depends on
+ * vqa_gru_ws_set_mode, VQA_HOT_GRU_WS and the device), asked without running anything: host only, no launch, no stream.
+ * VQA_ERR_ARG for bad dims or another `backward`, VQA_ERR_UNSUPPORTED for the model types with another encoder (12, 13). */
+int vqa_fusion_gru_form(const vqa_dims_t* dims, const int32_t* live_rows_host, int backward);
 int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* params, const vqa_batch_t* batch,
                        void* workspace, int64_t workspace_bytes, int want_dz, void* stream);
 /* grads: same layout as params; a NULL member skips that gradient (frozen

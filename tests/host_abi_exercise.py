@@ -187,5 +187,14 @@ ok(lib.vqa_gru_seq_bwd_ws(None, None, p4, p4, p4, p4, p4, p4, p4, p4, 14, 512, 1
 ok(lib.vqa_gru_seq_bwd_ws(p4, None, p4, p4, p4, p4, p4, p4, p4, p4, 14, 512, 1024, p4, None) == -4, "ws backward without a device")
 ok(lib.vqa_gru_ws_set_mode(1) == 0 and lib.vqa_gru_ws_set_mode(0) == 0 and lib.vqa_gru_ws_set_mode(-1) == 0, "ws mode")
 ok(lib.vqa_gru_ws_set_form(3) == 0 and lib.vqa_gru_ws_set_form(0) == 0 and lib.vqa_gru_ws_set_stamps(None) == 0, "ws tuning switches")
+# the step's recurrence form, asked without a step (no device: never weight-stationary)
+d = _lib.Dims(B=512, R=4, D=8, H=1024, T=4, W=12, A=8, Vq=16, N_img=4, model_type=0, keep_att=0.8, keep_joint=0.5, inv_global_batch=1 / 512)
+live = (C.c_int32 * 4)(512, 300, 7, 0)
+for bw in (0, 1):
+    ok(lib.vqa_fusion_gru_form(C.byref(d), None, bw) == 2, "gru form without live_rows: chains")
+    ok(lib.vqa_fusion_gru_form(C.byref(d), C.cast(live, C.c_void_p), bw) == 1, "gru form with live_rows: live")
+ok(lib.vqa_fusion_gru_form(None, None, 0) == -1 and lib.vqa_fusion_gru_form(C.byref(d), None, 2) == -1, "gru form bad arguments")
+d.model_type = 12
+ok(lib.vqa_fusion_gru_form(C.byref(d), None, 0) == -4, "gru form of the bi-directional encoder")
 
 print("host ABI exercise: %d checks passed on %s" % (checks, _lib.lib_path()))

@@ -14,6 +14,7 @@ Worst errors measured on an MI355X over every case here (forward: max over hs, r
 steps of err_t / max|ref_t|), next to a float32 evaluation of the contract on the CPU at H = 1024
 (tests/test_gru_reference.py: ~7e-7 forward, ~3.5e-7 backward):
     weight-stationary            forward 5.9e-07   backward 3.9e-07
+      on the live form's tape                      backward 2.1e-07   (r, u, c of finished rows NaN; the fully written tape's bits)
     per-step (with d_outs too)   forward 1.2e-06   backward 3.9e-07
     register-streamed (cfg 30)   forward 1.9e-06   backward 6.3e-07
     row windows                  forward 1.2e-06   backward 3.9e-07
@@ -167,9 +168,9 @@ def run_forward(form, c, ws=None):
     return dict(o, hs=hs)
 
 
-def run_backward(form, c, outs, ws=None):
-    """one form's BPTT on the reference tape (float32; the live form's with r, u, c past the length NaN); dxp
-    NaN-poisoned"""
+def run_backward(form, c, outs, ws=None, live_tape=False):
+    """one form's BPTT on the reference tape (float32; the live form's, and any form's under live_tape, with r, u, c past
+    the length NaN); dxp NaN-poisoned"""
     L, lib = _lib()
     T, B, H3 = c["xp"].shape
     H = H3 // 3
@@ -178,7 +179,7 @@ def run_backward(form, c, outs, ws=None):
     dh = c["dh_T"].clone()
     scratch = torch.full((B, H), NAN, device="cuda")
     d_outs = c["d_outs"] if outs else None
-    if form == "live":        # what vqa_gru_seq_fwd_live leaves past a row's length: r, u, c unwritten (here NaN)
+    if form == "live" or live_tape:   # what vqa_gru_seq_fwd_live leaves past a row's length: r, u, c unwritten (here NaN)
         past = G.past_mask(c["lens"], T)
         tp = dict(tp, **{k: tp[k].masked_fill(past[:, :, None], NAN) for k in ("r", "u", "c")})
     mid = (P(c["Wg"]), P(c["Wc"]), P(c["lens"]))
@@ -266,6 +267,23 @@ def test_ws_backward_matches_f64(T, B, outs):
     c = _case(T, B, 1024)
     dxp = run_backward("ws", c, outs, _ws_buffer(T))
     _print("ws", (T, B, outs), bwd=G.check_backward(dxp, _ref_dxp(c, outs), c["lens"]))
+
+
+@pytest.mark.parametrize("T,B,outs", [(2, 257, False), (14, 449, False), (14, 512, True)])
+def test_ws_backward_on_a_live_tape(T, B, outs):
+    """vqa_gru_seq_bwd_ws on the tape vqa_gru_seq_fwd_live leaves -- r, u, c of a finished row unwritten, here NaN: the
+    step hands it that tape under vqa_gru_ws_set_mode(2) on a length-sorted batch.  Everything of a finished row is
+    selected away, never multiplied by a zero: dxp meets the float64 reference and has the bits of the run on the fully
+    written tape."""
+    _, lib = _lib()
+    _require(lib.vqa_gru_ws_bwd_supported(T, B, 1024), "vqa_gru_seq_bwd_ws")
+    c = _case(T, B, 1024)
+    assert bool(G.past_mask(c["lens"], T).any())
+    ws = _ws_buffer(T)
+    dxp = run_backward("ws", c, outs, ws, live_tape=True)
+    _print("ws/live", (T, B, outs), bwd=G.check_backward(dxp, _ref_dxp(c, outs), c["lens"]))
+    full = run_backward("ws", c, outs, ws)
+    assert torch.equal(dxp, full), "dxp on the live tape differs from dxp on the fully written one"
 
 
 def test_ws_consecutive_calls_on_one_workspace():

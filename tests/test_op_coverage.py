@@ -14,6 +14,7 @@ ALLOWED = {
     "vqa_pretrain_report_key": "host-only table, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
     "vqa_fusion_workspace_bytes": "host-only layout query, tests/test_abi.py",
     "vqa_fusion_tensor": "host-only layout query, tests/test_abi.py",
+    "vqa_fusion_gru_form": "host-only query of the step's recurrence form, tests/test_encoder_routes_host.py",
     "vqa_pretrain_workspace_bytes": "host-only layout query, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
     "vqa_pretrain_tensor": "host-only layout query, tests/host_abi_exercise.py (run by tests/test_sanitizers.py)",
     "vqa_gemm_bf16x3_workspace_floats": "host-only size query behind ops.gemm_bf16x3_ex (test_gpu_ops.py)",

@@ -1064,6 +1064,14 @@ extern "C" int vqa_fusion_forward(const vqa_dims_t* dims, const vqa_params_t* P,
     return fwd_loss(s, want_dz);
 }
 
+// Which recurrence a step of these dims and this batch's live_rows runs: gru_form's answer (0 GRU_WS, 1 GRU_LIVE,
+// 2 GRU_CHAINS), for tests that pin the routing.  Host only.  The bi-directional and the legacy model do not ask gru_form.
+extern "C" int vqa_fusion_gru_form(const vqa_dims_t* dims, const int32_t* live_rows_host, int backward) {
+    VQA_REQUIRE(dims_ok(dims) && (backward == 0 || backward == 1), VQA_ERR_ARG);
+    VQA_REQUIRE(dims->model_type != VQA_MODEL_BI && dims->model_type != VQA_MODEL_LEGACY_VQA, VQA_ERR_UNSUPPORTED);
+    return (int)gru_form(backward ? GRU_BWD : GRU_FWD, dims->T, dims->B, dims->H, live_rows_host);
+}
+
 extern "C" int vqa_fusion_backward(const vqa_dims_t* dims, const vqa_params_t* P, const vqa_params_t* G,
                                    const vqa_batch_t* bt, void* workspace, int64_t workspace_bytes,
                                    float* embed_slice_sq, void* stream) {

@@ -1035,8 +1035,12 @@ __global__ __launch_bounds__(WS_NT, 1) void gru_ws_bwd2_kernel(WsBwdArgs a) {
         spill_fetch(k, P);
         if (k == 15) va = p0[0] + p0[1] + p0[2] + p0[3];                       // drh
         if (k == 17) {
-            acc_own[hf] += va * tr[hf];
-            vb = va * hp_own[hf] * tr[hf] * ((f32x4n)(1.f) - tr[hf]);           // dr_pre
+            // past a row's length r is selected away like u and c in half_step, not multiplied by drh = 0: the live forward
+            // (vqa_gru_seq_fwd_live) leaves r, u, c of a finished row unwritten, and 0 * NaN is not 0.  (+0 for an r in
+            // (0, 1): the same bits where the tape was written.)
+            const f32x4n rv = t < len_own[hf] ? tr[hf] : (f32x4n)(0.f);
+            acc_own[hf] += va * rv;
+            vb = va * hp_own[hf] * rv * ((f32x4n)(1.f) - rv);                   // dr_pre
         }
         if (k == 33) ws_store2(rs_dxp, o_xp[hf], ws_uni((unsigned)t * xp_step), vb, false);
         if (k == 39) ws_store2(rs_drF, frag_v, ws_uni(frag_st(t, hf)), vb, false);

@@ -63,6 +63,17 @@ CFG = {
     20: (128, 64, 1, 32, 0, 512), 21: (64, 128, 1, 32, 0, 512), 22: (128, 64, 1, 16, 0, 512), 23: (64, 32, 4, 32, 1, 512),
 }
 NUM_CFG = 24
+# the other id namespaces of csrc/gemm_tiles.h, mirrored by hand like CFG and held to the source by the same test.
+# GRU-step id (vqa_gemm_set_gru_config) -> (tile of the 2H-wide gate GEMM, tile of the H-wide GEMMs), tiles in CFG's form
+_GRU_32 = (32, 32, 4, 32, 1, 256)
+GRU_CFG = {4: (CFG[4], CFG[4]), 7: (CFG[7], CFG[7]), 8: (CFG[8], CFG[8]), 9: (CFG[9], CFG[9]), 10: (CFG[10], CFG[10]),
+           11: (CFG[11], CFG[11]), 12: (CFG[12], CFG[12]), 13: (CFG[13], CFG[13]), 16: (_GRU_32, _GRU_32),
+           17: (CFG[23], CFG[23]), 18: ((64, 64, 4, 64, 1, 1024), (64, 32, 8, 64, 1, 1024)), 20: (CFG[20], CFG[20]),
+           21: (CFG[21], CFG[21])}
+GRU_STREAMED, GRU_STREAMED_FALLBACK = 30, 16      # the register-streamed step kernels and the id their refusals run under
+CONV_CFG = {0: 3, 1: 20, 2: 21, 3: 16}            # conv id (vqa_conv_set_config) -> plain id of its tile
+TALL_CFGS = (20, 21)                              # vqa_gemm_set_tall_config; the row-gathered product takes the same tile
+EDGE_CFG = 2                                      # plain id of the tile behind the guarded loaders
 # one configuration per class of kernel (the scalar-epilogue and the persistent-walk cases run these)
 CLASS_CFGS = (2, 7, 8, 12, 16, 20, 23)
 WGK1_CLASS_CFGS = (2, 12, 16, 20)

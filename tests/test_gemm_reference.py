@@ -214,14 +214,110 @@ def test_matrix_reaches_every_gather_form_and_refusal():
         assert [c.expect for c in r] == [R.ERR_UNSUPPORTED, R.ERR_UNSUPPORTED, R.ERR_ALIGN, R.ERR_ALIGN]
 
 
+def _csrc(repo_root, name):
+    with open(os.path.join(repo_root, "vqa-transfer-externaldata_amd", "csrc", name)) as f:
+        return f.read()
+
+
+_TILE = r"(\d+), (\d+), \d+, \d+, (\d+), (\d+), (true|false), (\d+)\)"      # BM, BN, WM, WN, WGK, BK, DEEP, NT
+
+
+def _tile(BM, BN, wgk, BK, deep, nt):
+    return (int(BM), int(BN), int(wgk), int(BK), int(deep == "true"), int(nt))
+
+
+def _macro(hdr, name):
+    """the rows X(...) of `#define name(X) ...` (continuation lines included)"""
+    body = re.search(r"#define %s\(X\)((?:[^\n]*\\\n)*[^\n]*)" % name, hdr).group(1)
+    return re.findall(r"X\(([^()]*)\)", body)
+
+
 def test_tables_mirror_the_dispatcher(repo_root):
-    src = open(os.path.join(repo_root, "vqa-transfer-externaldata_amd", "csrc", "gemm_f32.hip")).read()
-    rows = re.findall(r"case (\d+): return launch_cfg<(\d+), (\d+), \d+, \d+, (\d+), (\d+), (\w+)(?:, (\d+))?>\(tA, tB", src)
-    assert len(rows) == R.NUM_CFG
-    for cfg, BM, BN, wgk, BK, deep, nt in rows:
-        want = (int(BM), int(BN), int(wgk), int(BK), int(deep in ("true", "1")), int(nt or 256))
-        assert R.CFG[int(cfg)] == want, cfg
-    assert "constexpr int NUM_CFG = %d;" % R.NUM_CFG in src
+    hdr, src = _csrc(repo_root, "gemm_tiles.h"), _csrc(repo_root, "gemm_f32.hip")
+    # the plain ids: every id once, in order, each tile equal to the hand-written mirror, the count NUM_CFG
+    rows = re.findall(r"PLAIN\((\d+), " + _TILE, hdr)
+    assert [int(r[0]) for r in rows] == list(range(R.NUM_CFG))
+    plain = {int(r[0]): _tile(*r[1:]) for r in rows}
+    assert plain == R.CFG
+    assert "constexpr int NUM_CFG = sizeof(kPlainDims) / sizeof(kPlainDims[0]);" in hdr
+    assert "VQA_GEMM_TILES(VQA_TILE_DIMS, VQA_TILE_NONE)" in hdr and "VQA_GEMM_TILES(VQA_TILE_CASE, VQA_TILE_NONE)" in hdr
+    # the GRU-step ids: 4, 7..13 and 20, 21 are the plain ids of the same number, 16 its own 32 x 32 tile, 17 plain 23, 18 the
+    # two 1024-thread tiles, 30 the register-streamed kernels falling back to 16
+    named = {r[0]: _tile(*r[1:]) for r in re.findall(r"GRU_ONLY\((\w+), " + _TILE, hdr)}
+    assert len(named) == 3 and not set(named.values()) & set(plain.values())
+    tile_of = lambda t: plain[int(t[6:-1])] if t.startswith("Plain<") else named[t]
+    gru = [[x.strip() for x in row.split(",")] for row in _macro(hdr, "VQA_GRU_CFGS")]
+    assert [int(g[0]) for g in gru] == sorted(R.GRU_CFG)
+    assert {int(g[0]): (tile_of(g[1]), tile_of(g[2])) for g in gru} == R.GRU_CFG
+    for gid in (4, 7, 8, 9, 10, 11, 12, 13, 20, 21):
+        assert R.GRU_CFG[gid] == (R.CFG[gid], R.CFG[gid])
+    assert R.GRU_CFG[16] == ((32, 32, 4, 32, 1, 256),) * 2 and R.GRU_CFG[17] == (R.CFG[23],) * 2
+    assert R.GRU_CFG[18] == ((64, 64, 4, 64, 1, 1024), (64, 32, 8, 64, 1, 1024))
+    assert "constexpr int GRU_CFG_STREAMED = %d;" % R.GRU_STREAMED in hdr
+    assert "constexpr int GRU_CFG_STREAMED_FALLBACK = %d;" % R.GRU_STREAMED_FALLBACK in hdr
+    assert R.GRU_STREAMED_FALLBACK in R.GRU_CFG and R.GRU_STREAMED not in R.GRU_CFG
+    # conv ids 0..3 = plain 3, 20, 21, 16; the tall ids, whose tiles the row-gathered product takes; the edge tile
+    conv = [tuple(int(v) for v in row.split(",")) for row in _macro(hdr, "VQA_CONV_CFGS")]
+    assert conv == sorted(R.CONV_CFG.items()) == [(0, 3), (1, 20), (2, 21), (3, 16)]
+    assert tuple(int(row) for row in _macro(hdr, "VQA_TALL_CFGS")) == R.TALL_CFGS == (20, 21)
+    assert "using EdgeTile = Plain<%d>;" % R.EDGE_CFG in hdr and R.CFG[R.EDGE_CFG] == (64, 64, 1, 16, 0, 256)
+    # ... and the dispatchers name these entries: no tile is typed out again, the kernel's argument list stands once
+    assert not re.search(r"launch_(one|layout)<\s*\d", src)
+    assert len(re.findall(r"gemm_f32_kernel<", src)) == 1
+    assert "launch_one<Plain<ID>, true, false, EPI_PLAIN, false, false, 2>" in src      # the gather: Plain<g_tall_cfg>
+    assert "launch_one<Plain<PLAIN_ID>, true, false, EPI_PLAIN, true>" in src           # the implicit-GEMM convolution
+    assert "launch_layout<EdgeTile, true>" in src
+
+
+# ---------------------------------------------------------------------------------- the setters and the environment's ids
+@pytest.fixture(scope="module")
+def built(repo_root):
+    import __graft_entry__ as g
+    g.build()
+    from vqa_transfer_externaldata_amd import _lib
+    return _lib
+
+
+def test_setters_admit_the_ids_of_the_tables_and_no_other(built):
+    lib = built.load()
+    try:
+        for cfg in range(-8, 48):
+            assert lib.vqa_gemm_set_config(cfg) == (R.OK if -1 <= cfg < R.NUM_CFG else R.ERR_ARG), cfg
+            known = cfg == -1 or cfg in R.GRU_CFG or cfg == R.GRU_STREAMED
+            assert lib.vqa_gemm_set_gru_config(cfg) == (R.OK if known else R.ERR_ARG), cfg
+            assert lib.vqa_conv_set_config(cfg) == (R.OK if cfg == -1 or cfg in R.CONV_CFG else R.ERR_ARG), cfg
+            assert lib.vqa_gemm_set_tall_config(cfg) == (R.OK if cfg in R.TALL_CFGS else R.ERR_ARG), cfg
+    finally:
+        lib.vqa_gemm_set_config(-1), lib.vqa_gemm_set_gru_config(-1), lib.vqa_conv_set_config(-1)
+        lib.vqa_gemm_set_tall_config(20)
+
+
+# vqa_gemm_workspace_floats(1, 0, 1024, 1024, K, 0), recorded from the build before the tile table (where an id outside
+# 0..23 indexed the dispatcher's table unchecked, so only the unset and the valid cases were defined there): K 4096
+# reaches VQA_HOT_TN_SHORT_CFG, K 8192 (at most 128 tiles of 128 x 128) VQA_HOT_TN_MID_CFG.  Default id 20: 128 tiles of
+# 128 x 64, four slabs for 512 workgroups; id 19: 64 tiles of 128 x 128, eight slabs.
+_WS_DEFAULT, _WS_CFG19 = 4 << 20, 8 << 20
+_WS_CHILD = ("import ctypes, sys\n"
+             "lib = ctypes.CDLL(sys.argv[1])\n"
+             "lib.vqa_gemm_workspace_floats.restype = ctypes.c_int64\n"
+             "print(lib.vqa_gemm_workspace_floats(1, 0, 1024, 1024, int(sys.argv[2]), 0))\n")
+
+
+@pytest.mark.parametrize("var,K", [("VQA_HOT_TN_SHORT_CFG", 4096), ("VQA_HOT_TN_MID_CFG", 8192)])
+@pytest.mark.parametrize("value,want", [(None, _WS_DEFAULT), ("19", _WS_CFG19), ("24", _WS_DEFAULT), ("99", _WS_DEFAULT),
+                                        ("-7", _WS_DEFAULT)])
+def test_a_tile_id_from_the_environment_is_checked_against_the_table(built, var, K, value, want):
+    """the environment is read once per process, so every case is a fresh child; the call is host arithmetic"""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith("VQA_HOT_")}
+    if value is not None:
+        env[var] = value
+    r = subprocess.run([sys.executable, "-c", _WS_CHILD, built._LIB_PATH, str(K)], capture_output=True, text=True, env=env,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert int(r.stdout) == want
+    assert R.choose(1, 0, 1024, 1024, K)[1] * 1024 * 1024 == _WS_DEFAULT
 
 
 # ---------------------------------------------------------------------------------------------- the comparators reject

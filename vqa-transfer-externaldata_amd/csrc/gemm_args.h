@@ -54,8 +54,10 @@ GemmArgs vqa_gemm_make_args(int M, int N, int K, const float* A, int lda, const 
 // gemm_f32.hip: vqa_gemm_f32_gather on this problem is vqa_gemm_f32's own kernel configuration (tile, k order, no split)
 // with another row behind every lane, and the table fits the 32-bit offsets of a buffer descriptor
 bool vqa_gemm_gather_matches_plain(int M, int N, int K, int lda, int R, int64_t n_samples_in_table);
-// gemm_f32.hip: one fused GRU-step GEMM, epilogue `epi` (EPI_GATES .. EPI_BWD_DH), tile config `cfg` (4, 7..13, 16..18,
-// 20, 21; 30 = vqa_gru_rs_launch, falling back to 16 for the shapes it does not take)
+// gemm_f32.hip: one fused GRU-step GEMM, epilogue `epi` (EPI_GATES .. EPI_BWD_DH), tile config `cfg`: a GRU-step id of
+// gemm_tiles.h (VQA_GRU_CFGS and the register-streamed id beside it); VQA_ERR_ARG for any other value
 int vqa_gru_step_launch(int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);
+// gemm_f32.hip: whether `cfg` is such an id
+bool vqa_gru_cfg_known(int cfg);
 // gru_stream.hip: the register-streamed form of the same step; VQA_ERR_UNSUPPORTED for shapes it does not take
 int vqa_gru_rs_launch(int epi, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);

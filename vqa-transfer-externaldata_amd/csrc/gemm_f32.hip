@@ -20,6 +20,7 @@
 
 #include "vqa_common.h"
 #include "gemm_args.h"
+#include "gemm_tiles.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -862,15 +863,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
-template <int BM, int BN, int WM, int WN, int WGK, int BK, int DEEP, bool A_KC, bool B_KC, int EPI, bool CONV = false,
-          bool EDGE = false, int NT = 256, int GATHER = 0>
+// One launch of tile T (an entry of gemm_tiles.h) in the form a use asks for; the only place that spells out the
+// kernel's template arguments.
+template <class T, bool A_KC, bool B_KC, int EPI, bool CONV = false, bool EDGE = false, int GATHER = 0>
 int launch_one(GemmArgs a, const EpiArgs& ep, int split, hipStream_t st, int max_blocks = 0) {
+    constexpr int BM = T::BM, BN = T::BN, WM = T::WM, WN = T::WN, WGK = T::WGK, BK = T::BK, NT = T::NT;
     constexpr size_t tiles = 2 * (tile_floats<BM, BK, A_KC>() + tile_floats<BN, BK, B_KC>()) * sizeof(float);
     constexpr size_t red = (EPI == EPI_PLAIN) ? (size_t)(WGK - 1) * (BM / WM) * (BN / WN) * (WM / 32) * (WN / 32) * 16 * 64 * sizeof(float) : 0;
     // epilogue transpose patches: one per (m, n) wave slot, and per k group as well for the fused epilogues
     constexpr size_t stage = (size_t)(EPI == EPI_PLAIN ? 1 : WGK) * (BM / WM) * (BN / WN) * 32 * 36 * sizeof(float);
     constexpr size_t lds = tiles > red + stage ? tiles : red + stage;
-    auto kern = gemm_f32_kernel<BM, BN, WM, WN, WGK, BK, DEEP, A_KC, B_KC, EPI, CONV, EDGE, NT, GATHER>;
+    auto kern = gemm_f32_kernel<BM, BN, WM, WN, WGK, BK, T::DEEP, A_KC, B_KC, EPI, CONV, EDGE, NT, GATHER>;
     static bool attr_done = false;
     if (lds > 64 * 1024 && !attr_done) {   // MI355X has 160 KiB of LDS per CU; > 64 KiB needs the opt-in
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -906,21 +909,14 @@ int launch_one(GemmArgs a, const EpiArgs& ep, int split, hipStream_t st, int max
     return VQA_OK;
 }
 
-template <int BM, int BN, int WM, int WN, int WGK, int BK, int DEEP, int NT = 256>
-int launch_cfg(int tA, int tB, const GemmArgs& a, int split, hipStream_t st, int mb) {
+// the plain product on tile T in its NN, NT or TN operand layout (EDGE: through the guarded loaders)
+template <class T, bool EDGE>
+int launch_layout(int tA, int tB, const GemmArgs& a, int split, hipStream_t st, int mb) {
     const EpiArgs ep{};
-    if (tA == 0 && tB == 0)
-        return launch_one<BM, BN, WM, WN, WGK, BK, DEEP, true, false, EPI_PLAIN, false, false, NT>(a, ep, split, st, mb);
-    if (tA == 0 && tB == 1)
-        return launch_one<BM, BN, WM, WN, WGK, BK, DEEP, true, true, EPI_PLAIN, false, false, NT>(a, ep, split, st, mb);
-    return launch_one<BM, BN, WM, WN, WGK, BK, DEEP, false, false, EPI_PLAIN, false, false, NT>(a, ep, split, st, mb);
+    if (tA == 0 && tB == 0) return launch_one<T, true, false, EPI_PLAIN, false, EDGE>(a, ep, split, st, mb);
+    if (tA == 0 && tB == 1) return launch_one<T, true, true, EPI_PLAIN, false, EDGE>(a, ep, split, st, mb);
+    return launch_one<T, false, false, EPI_PLAIN, false, EDGE>(a, ep, split, st, mb);
 }
-
-struct TileCfg { int BM, BN; };
-constexpr int NUM_CFG = 24;
-const TileCfg kCfg[NUM_CFG] = {{128, 128}, {128, 128}, {64, 64}, {64, 64}, {64, 64}, {128, 64}, {64, 128},
-                               {64, 32}, {32, 32}, {32, 64}, {64, 64}, {64, 32}, {64, 64}, {64, 32}, {128, 32},
-                               {128, 64}, {128, 128}, {128, 128}, {256, 64}, {128, 128}, {128, 64}, {64, 128}, {128, 64}, {64, 32}};
 
 // operands that allow the buffer-load fast path (see Stager::load_fast); fills the descriptor extents
 bool fast_ok(int tA, int tB, GemmArgs& a) {
@@ -935,74 +931,30 @@ bool fast_ok(int tA, int tB, GemmArgs& a) {
     return true;
 }
 
-int launch_edge(int tA, int tB, const GemmArgs& a, int split, hipStream_t st) {
-    const EpiArgs ep{};
-    if (tA == 0 && tB == 0)
-        return launch_one<64, 64, 32, 32, 1, 16, false, true, false, EPI_PLAIN, false, true>(a, ep, split, st, 0);
-    if (tA == 0 && tB == 1)
-        return launch_one<64, 64, 32, 32, 1, 16, false, true, true, EPI_PLAIN, false, true>(a, ep, split, st, 0);
-    return launch_one<64, 64, 32, 32, 1, 16, false, false, false, EPI_PLAIN, false, true>(a, ep, split, st, 0);
-}
-
 int launch_by_id(int cfg, int tA, int tB, const GemmArgs& a_in, int split, hipStream_t st, int mb = 0) {
     GemmArgs a = a_in;
-    if (!fast_ok(tA, tB, a)) return launch_edge(tA, tB, a, split, st);   // ragged / unaligned shapes
-    switch (cfg) {
-        case 0: return launch_cfg<128, 128, 64, 64, 1, 16, false>(tA, tB, a, split, st, mb);
-        case 1: return launch_cfg<128, 128, 64, 64, 1, 32, false>(tA, tB, a, split, st, mb);
-        case 2: return launch_cfg<64, 64, 32, 32, 1, 16, false>(tA, tB, a, split, st, mb);
-        case 3: return launch_cfg<64, 64, 32, 32, 1, 32, false>(tA, tB, a, split, st, mb);
-        case 4: return launch_cfg<64, 64, 32, 32, 1, 64, false>(tA, tB, a, split, st, mb);
-        case 5: return launch_cfg<128, 64, 64, 32, 1, 32, false>(tA, tB, a, split, st, mb);
-        case 6: return launch_cfg<64, 128, 32, 64, 1, 32, false>(tA, tB, a, split, st, mb);
-        case 7: return launch_cfg<64, 32, 32, 32, 2, 64, false>(tA, tB, a, split, st, mb);
-        case 8: return launch_cfg<32, 32, 32, 32, 4, 64, false>(tA, tB, a, split, st, mb);
-        case 9: return launch_cfg<32, 64, 32, 32, 2, 64, false>(tA, tB, a, split, st, mb);
-        case 10: return launch_cfg<64, 64, 32, 32, 1, 64, true>(tA, tB, a, split, st, mb);
-        case 11: return launch_cfg<64, 32, 32, 32, 2, 64, true>(tA, tB, a, split, st, mb);
-        case 12: return launch_cfg<64, 64, 32, 32, 1, 32, true>(tA, tB, a, split, st, mb);
-        case 13: return launch_cfg<64, 32, 32, 32, 2, 32, true>(tA, tB, a, split, st, mb);
-        case 14: return launch_cfg<128, 32, 32, 32, 1, 64, true>(tA, tB, a, split, st, mb);
-        case 15: return launch_cfg<128, 64, 32, 64, 1, 32, true>(tA, tB, a, split, st, mb);
-        case 16: return launch_cfg<128, 128, 64, 32, 1, 32, 0, 512>(tA, tB, a, split, st, mb);
-        case 17: return launch_cfg<128, 128, 32, 64, 1, 32, 0, 512>(tA, tB, a, split, st, mb);
-        case 18: return launch_cfg<256, 64, 64, 32, 1, 32, 0, 512>(tA, tB, a, split, st, mb);
-        case 19: return launch_cfg<128, 128, 64, 32, 1, 16, 0, 512>(tA, tB, a, split, st, mb);
-        case 20: return launch_cfg<128, 64, 32, 32, 1, 32, 0, 512>(tA, tB, a, split, st, mb);
-        case 21: return launch_cfg<64, 128, 32, 32, 1, 32, 0, 512>(tA, tB, a, split, st, mb);
-        case 22: return launch_cfg<128, 64, 32, 32, 1, 16, 0, 512>(tA, tB, a, split, st, mb);
-        case 23: return launch_cfg<64, 32, 32, 32, 4, 32, 1, 512>(tA, tB, a, split, st, mb);
-        default: return VQA_ERR_ARG;
-    }
+    if (!fast_ok(tA, tB, a)) return launch_layout<EdgeTile, true>(tA, tB, a, split, st, 0);   // ragged / unaligned shapes
+    return with_plain_tile(cfg, [&](auto tile) { return launch_layout<decltype(tile), false>(tA, tB, a, split, st, mb); });
 }
 
-// fused GRU-step GEMMs: layout fixed by the epilogue (forward NN, backward NT)
+// fused GRU-step GEMMs: layout fixed by the epilogue (forward NN, backward NT), tile by the GRU id table
 template <int EPI>
 int launch_gru(int cfg, const GemmArgs& a_in, const EpiArgs& ep, hipStream_t st) {
     constexpr bool BKC = (EPI == EPI_BWD_RH || EPI == EPI_BWD_DH);
     GemmArgs a = a_in;
     if (!fast_ok(0, BKC ? 1 : 0, a)) return VQA_ERR_ALIGN;
-    if (cfg == 30) {   // register-streamed step kernels (gru_stream.hip); shapes they do not take fall back to the LDS-tiled form
+    if (cfg == GRU_CFG_STREAMED) {   // shapes the register-streamed kernels do not take fall back to the LDS-tiled form
         const int rc = vqa_gru_rs_launch(EPI, a_in, ep, st);
         if (rc != VQA_ERR_UNSUPPORTED) return rc;
-        cfg = 16;
+        cfg = GRU_CFG_STREAMED_FALLBACK;
     }
     switch (cfg) {
-        case 4: return launch_one<64, 64, 32, 32, 1, 64, false, true, BKC, EPI>(a, ep, 1, st);
-        case 7: return launch_one<64, 32, 32, 32, 2, 64, false, true, BKC, EPI>(a, ep, 1, st);
-        case 8: return launch_one<32, 32, 32, 32, 4, 64, false, true, BKC, EPI>(a, ep, 1, st);
-        case 9: return launch_one<32, 64, 32, 32, 2, 64, false, true, BKC, EPI>(a, ep, 1, st);
-        case 10: return launch_one<64, 64, 32, 32, 1, 64, true, true, BKC, EPI>(a, ep, 1, st);
-        case 11: return launch_one<64, 32, 32, 32, 2, 64, true, true, BKC, EPI>(a, ep, 1, st);
-        case 12: return launch_one<64, 64, 32, 32, 1, 32, true, true, BKC, EPI>(a, ep, 1, st);
-        case 13: return launch_one<64, 32, 32, 32, 2, 32, true, true, BKC, EPI>(a, ep, 1, st);
-        case 16: return launch_one<32, 32, 32, 32, 4, 32, true, true, BKC, EPI>(a, ep, 1, st);
-        case 20: return launch_one<128, 64, 32, 32, 1, 32, 0, true, BKC, EPI, false, false, 512>(a, ep, 1, st);
-        case 21: return launch_one<64, 128, 32, 32, 1, 32, 0, true, BKC, EPI, false, false, 512>(a, ep, 1, st);
-        case 17: return launch_one<64, 32, 32, 32, 4, 32, 1, true, BKC, EPI, false, false, 512>(a, ep, 1, st);
-        case 18:   // one 16-wave workgroup per CU: 64x64 tiles for the 2H-wide gate GEMM, 64x32 for the H-wide ones
-            if (EPI == EPI_GATES) return launch_one<64, 64, 32, 32, 4, 64, 1, true, BKC, EPI, false, false, 1024>(a, ep, 1, st);
-            return launch_one<64, 32, 32, 32, 8, 64, 1, true, BKC, EPI, false, false, 1024>(a, ep, 1, st);
+#define VQA_GRU_CASE(ID, GATES, OTHERS)                                                     \
+        case ID:                                                                            \
+            if (EPI == EPI_GATES) return launch_one<GATES, true, BKC, EPI>(a, ep, 1, st);   \
+            return launch_one<OTHERS, true, BKC, EPI>(a, ep, 1, st);
+        VQA_GRU_CFGS(VQA_GRU_CASE)
+#undef VQA_GRU_CASE
         default: return VQA_ERR_ARG;
     }
 }
@@ -1028,16 +980,23 @@ int g_conv_cfg_plain = -1;
 //  * batch-sized M (512) or narrow N: 64x32 tiles, in-block split-k and two tiles of register prefetch
 //    (one workgroup per CU cannot hide a global load behind a single tile's MFMAs) -- 8 waves / 4 k groups
 //    (512x1024x1024: 14.4 us against 16.0 with 4 waves / 2 k groups), 4 waves for the wide answer head.
+// A plain tile id from the environment (callers keep it in a function-local static: read once).  A value that is no
+// plain id means the default, silently; negative_ok lets a negative one through as the caller's "off".
+inline int env_plain_cfg(const char* name, int dflt, bool negative_ok = false) {
+    const int v = vqa_env_int(name, dflt);
+    return (is_plain_cfg(v) || (negative_ok && v < 0)) ? v : dflt;
+}
+
 inline int tall_small_cfg() {      // VQA_HOT_TALL_SMALL_CFG: tuning override (-1 = keep the 128x64 tile)
-    static const int v = vqa_env_int("VQA_HOT_TALL_SMALL_CFG", 12);
-    return v < NUM_CFG ? v : 12;
+    static const int v = env_plain_cfg("VQA_HOT_TALL_SMALL_CFG", 12, true);
+    return v;
 }
 
 inline int tune_pair(const char* env, int cfg, int split) {     // "cfg:split" from the environment, packed cfg << 8 | split
     const char* e = getenv(env);
     if (e != nullptr) {
         int c = 0, s = 0;
-        if (sscanf(e, "%d:%d", &c, &s) == 2 && c >= 0 && c < NUM_CFG && s >= 0 && s <= 16) { cfg = c; split = s; }
+        if (sscanf(e, "%d:%d", &c, &s) == 2 && is_plain_cfg(c) && s >= 0 && s <= 16) { cfg = c; split = s; }
     }
     return (cfg << 8) | split;
 }
@@ -1047,8 +1006,8 @@ void choose(int tA, int tB, int M, int N, int K, int& cfg, int& split) {
     if (tA) {
         // weight gradients: 128x128 tiles of 16-deep k tiles for the long ones; up to k = 4096 the 128x64 tile of 32-deep k
         // tiles is 5 % (1024 x 2048 x 2560) to 23 % (the answer head's 2048 x 3000 x 512) faster (profiles/r3_tn_tune.txt)
-        static const int tn_short = vqa_env_int("VQA_HOT_TN_SHORT_CFG", 20);
-        static const int tn_mid = vqa_env_int("VQA_HOT_TN_MID_CFG", 20);   // (k < 20000, at most 128 tiles of 128x128: v_linear_v and recurrent dW, -5 and -9 us)
+        static const int tn_short = env_plain_cfg("VQA_HOT_TN_SHORT_CFG", 20);
+        static const int tn_mid = env_plain_cfg("VQA_HOT_TN_MID_CFG", 20);   // (k < 20000, at most 128 tiles of 128x128: v_linear_v and recurrent dW, -5 and -9 us)
         const bool mid = K < 20000 && cdiv(M, 128) * cdiv(N, 128) <= 128;
         cfg = ((int64_t)M * N >= (1 << 20)) ? (K <= 4096 ? tn_short : (mid ? tn_mid : 19)) : 3;
         target = 512;
@@ -1073,8 +1032,8 @@ void choose(int tA, int tB, int M, int N, int K, int& cfg, int& split) {
         static const int t = tune_pair("VQA_HOT_DWX_TUNE", 21, 4);
         if (t >> 8) { cfg = t >> 8; want_split = t & 255; }
     }
-    if (g_force_cfg >= 0 && g_force_cfg < NUM_CFG) { cfg = g_force_cfg; want_split = 0; }
-    const int64_t blocks = cdiv(M, kCfg[cfg].BM) * cdiv(N, kCfg[cfg].BN);
+    if (is_plain_cfg(g_force_cfg)) { cfg = g_force_cfg; want_split = 0; }
+    const int64_t blocks = cdiv(M, kPlainDims[cfg].BM) * cdiv(N, kPlainDims[cfg].BN);
     if (split <= 0) {
         split = 1;
         if ((N % 4) == 0) {
@@ -1115,6 +1074,16 @@ int vqa_gru_step_launch(int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, 
     }
 }
 
+bool vqa_gru_cfg_known(int cfg) {
+    switch (cfg) {
+#define VQA_GRU_CASE(ID, GATES, OTHERS) case ID:
+        VQA_GRU_CFGS(VQA_GRU_CASE)
+#undef VQA_GRU_CASE
+        case GRU_CFG_STREAMED: return true;
+        default: return false;
+    }
+}
+
 extern "C" int64_t vqa_gemm_workspace_floats(int transA, int transB, int M, int N, int K, int split_k) {
     int cfg, split = split_k;
     choose(transA, transB, M, N, K, cfg, split);
@@ -1122,7 +1091,7 @@ extern "C" int64_t vqa_gemm_workspace_floats(int transA, int transB, int M, int 
 }
 
 extern "C" int vqa_gemm_set_config(int cfg) {
-    VQA_REQUIRE(cfg >= -1 && cfg < NUM_CFG, VQA_ERR_ARG);
+    VQA_REQUIRE(cfg == -1 || is_plain_cfg(cfg), VQA_ERR_ARG);
     g_force_cfg = cfg;
     return VQA_OK;
 }
@@ -1258,11 +1227,15 @@ extern "C" int vqa_gemm_f32_gather(int M, int N, int K, const float* table, int 
     a.k_per_split = (int)cdiv(K, 64) * 64;
     const EpiArgs ep{};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (g_tall_cfg == 21)
-        return by_offset ? launch_one<64, 128, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 2>(a, ep, 1, st, 0)
-                         : launch_one<64, 128, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 1>(a, ep, 1, st, 0);
-    return by_offset ? launch_one<128, 64, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 2>(a, ep, 1, st, 0)
-                     : launch_one<128, 64, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, false, false, 512, 1>(a, ep, 1, st, 0);
+    switch (g_tall_cfg) {      // the tile of the plain product that choose() gives this shape class
+#define VQA_TALL_CASE(ID)                                                                                        \
+        case ID:                                                                                                 \
+            return by_offset ? launch_one<Plain<ID>, true, false, EPI_PLAIN, false, false, 2>(a, ep, 1, st, 0)   \
+                             : launch_one<Plain<ID>, true, false, EPI_PLAIN, false, false, 1>(a, ep, 1, st, 0);
+        VQA_TALL_CFGS(VQA_TALL_CASE)
+#undef VQA_TALL_CASE
+        default: return VQA_ERR_ARG;      // (vqa_gemm_set_tall_config admits the tall ids only)
+    }
 }
 
 extern "C" int vqa_gemm_set_gather_ptr(int on) {
@@ -1272,6 +1245,7 @@ extern "C" int vqa_gemm_set_gather_ptr(int on) {
 
 // Whether vqa_gemm_f32_gather computes C = table[idx] B with the very kernel configuration vqa_gemm_f32 would take for the
 // dense product (same tile, same k order, no split: the same bits), and reads the table the cheap way (32-bit offsets).
+// The gather launches Plain<g_tall_cfg>, so "same tile" is: choose() answers g_tall_cfg for the dense product.
 bool vqa_gemm_gather_matches_plain(int M, int N, int K, int lda, int R, int64_t n_samples_in_table) {
     if (bf16x3_mode() || g_gather_ptr || K % 32 != 0 || N % 4 != 0) return false;
     if (((n_samples_in_table * R - 1) * (int64_t)lda + K) * 4 >= 0xFFFFFF00ll) return false;
@@ -1281,7 +1255,13 @@ bool vqa_gemm_gather_matches_plain(int M, int N, int K, int lda, int R, int64_t 
 }
 
 extern "C" int vqa_gemm_set_tall_config(int cfg) {
-    VQA_REQUIRE(cfg == 20 || cfg == 21, VQA_ERR_ARG);
+    switch (cfg) {
+#define VQA_TALL_CASE(ID) case ID:
+        VQA_TALL_CFGS(VQA_TALL_CASE)
+#undef VQA_TALL_CASE
+            break;
+        default: return VQA_ERR_ARG;
+    }
     g_tall_cfg = cfg;
     return VQA_OK;
 }
@@ -1321,7 +1301,7 @@ extern "C" int vqa_conv2d_nhwc(const float* x, int B, int Hi, int Wi, int Ci, co
         if (Ci <= 128 && Co >= 256 && Co >= 2 * Ci && (int64_t)M * Co >= (1ll << 25)) cfg = 16;
         else if (Co <= 64 && Ci >= 256) cfg = 20;
         if (g_conv_cfg_plain >= 0) cfg = g_conv_cfg_plain;
-        if (g_force_cfg >= 0 && g_force_cfg < NUM_CFG) cfg = g_force_cfg;
+        if (is_plain_cfg(g_force_cfg)) cfg = g_force_cfg;
         return launch_by_id(cfg, 0, 0, a, 1, st, 0);
     }
     // 64x64 / 4-wave tiles for every implicit-GEMM layer: at four workgroups per CU (see the kernel's launch bounds)
@@ -1339,15 +1319,15 @@ extern "C" int vqa_conv2d_nhwc(const float* x, int B, int Hi, int Wi, int Ci, co
     a.b_bytes = (unsigned)wb;
     const EpiArgs ep{};
     switch (ccfg) {
-        case 1: return launch_one<128, 64, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, true, false, 512>(a, ep, 1, st, 0);
-        case 2: return launch_one<64, 128, 32, 32, 1, 32, 0, true, false, EPI_PLAIN, true, false, 512>(a, ep, 1, st, 0);
-        case 3: return launch_one<128, 128, 64, 32, 1, 32, 0, true, false, EPI_PLAIN, true, false, 512>(a, ep, 1, st, 0);
-        default: return launch_one<64, 64, 32, 32, 1, 32, false, true, false, EPI_PLAIN, true>(a, ep, 1, st, 0);
+#define VQA_CONV_CASE(ID, PLAIN_ID) case ID: return launch_one<Plain<PLAIN_ID>, true, false, EPI_PLAIN, true>(a, ep, 1, st, 0);
+        VQA_CONV_CFGS(VQA_CONV_CASE)
+#undef VQA_CONV_CASE
+        default: return VQA_ERR_ARG;      // (vqa_conv_set_config admits the conv ids only)
     }
 }
 
 extern "C" int vqa_conv_set_config(int cfg) {
-    VQA_REQUIRE(cfg >= -1 && cfg <= 3, VQA_ERR_ARG);
+    VQA_REQUIRE(cfg >= -1 && cfg < NUM_CONV_CFG, VQA_ERR_ARG);
     g_conv_cfg = cfg;
     g_conv_cfg_plain = cfg < 0 ? -1 : 3;     // a forced config also pins the 1x1 path to its 64x64 tile
     return VQA_OK;

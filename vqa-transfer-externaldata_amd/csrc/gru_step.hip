@@ -118,8 +118,7 @@ int bwd_window(const BwdTape& p, float* dh_T, float* dh_scratch, int T, int row0
 }  // namespace
 
 extern "C" int vqa_gemm_set_gru_config(int cfg) {
-    VQA_REQUIRE(cfg == -1 || cfg == 4 || (cfg >= 7 && cfg <= 13) || (cfg >= 16 && cfg <= 18) || cfg == 20 || cfg == 21 || cfg == 30,
-                VQA_ERR_ARG);
+    VQA_REQUIRE(cfg == -1 || vqa_gru_cfg_known(cfg), VQA_ERR_ARG);
     g_gru_cfg = cfg;   // -1 restores the defaults
     return VQA_OK;
 }

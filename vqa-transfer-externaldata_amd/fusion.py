@@ -258,10 +258,13 @@ def flat_layout(model_type, shapes, ft_vlmap=False):
 
 
 class FusionEngine(EngineCore):
-    MODEL_TYPE_ID = {"vlmap_answer": 0, "standard": 1, "standard_word2vec": 2, "standard_testmask": 3,
-                     "vlmap_answer_vqa_all2": 4, "vlmap_answer_noc": 5, "vlmap_answer_nocarch": 5, "vlmap_answer_vqa_all": 6,
-                     "vlmap_answer2": 7, "vlmap_answer_no_noise": 8, "vlmap_answer_adapt": 9, "vlmap_answer_full": 10,
-                     "vlmap_answer_ent": 11, "vlmap_finetune": 12, "vlmap_only": 12, "vqa": 13}
+    # registry name -> the header's VQA_MODEL_* name; the ids are the header's
+    MODEL_TYPE_ID = {k: _lib.DEFINES["VQA_MODEL_" + v] for k, v in {
+        "vlmap_answer": "VLMAP_ANSWER", "standard": "STANDARD", "standard_word2vec": "WORD2VEC",
+        "standard_testmask": "TESTMASK", "vlmap_answer_vqa_all2": "VQA_ALL2", "vlmap_answer_noc": "NOC",
+        "vlmap_answer_nocarch": "NOC", "vlmap_answer_vqa_all": "VQA_ALL", "vlmap_answer2": "ANSWER2",
+        "vlmap_answer_no_noise": "NO_NOISE", "vlmap_answer_adapt": "ADAPT", "vlmap_answer_full": "FULL",
+        "vlmap_answer_ent": "ENT", "vlmap_finetune": "BI", "vlmap_only": "BI", "vqa": "LEGACY_VQA"}.items()}
 
     def __init__(self, *, model_type, B, R, D, H, T, W, A, Vq, N_img, params, device="cuda:0",
                  keep_att=0.8, keep_joint=0.5, global_batch=None, deterministic=None, answer_glove=None,

@@ -634,7 +634,16 @@ typedef struct {
                                      * pooled_V_ft and everything downstream stay f32, as does the question encoder.
                                      * Valid only with VQA_FLAG_BF16_GEMM, without VQA_FLAG_FUSED_GATHER, for model types 0
                                      * and 1: any other combination makes vqa_fusion_workspace_bytes / _tensor / _forward /
-                                     * _backward / _backward_phases return VQA_ERR_ARG, and nothing is launched. */
+                                     * _backward / _backward_phases return VQA_ERR_ARG, and nothing is launched.
+                                     * Also honoured in vqa_pretrain_dims_t.flags (all four pre-training families):
+                                     * vqa_pretrain_batch_t.image_ft then points at [B,R,D] raw bf16 patterns.  The attention
+                                     * kernels of the step -- several queries per memory included -- pool the patterns as they
+                                     * are; the adapt model's v_adapt product and its dW = image_ft^T d_pre run
+                                     * vqa_gemm_bf16_a16, and its pooled memory (v_adapt's output) stays f32.  The step is bit
+                                     * for bit the VQA_FLAG_BF16_GEMM step on the features widened to f32; no workspace layout
+                                     * changes (image_ft is an input).  Valid only with VQA_FLAG_BF16_GEMM: without it the
+                                     * workspace query, the tensor query, forward, backward and backward_phases (the _ex forms
+                                     * included) of every family return VQA_ERR_ARG, and nothing is launched. */
 
 /* One FC(+LN) layer: weights [in,out], biases [out], LayerNorm beta/gamma [out] (NULL if no LN). */
 typedef struct { float *w, *b, *beta, *gamma; } vqa_fc_t;
@@ -750,7 +759,8 @@ typedef struct {
                                              * answers, caption vocabulary, word-set vocabulary */
     int32_t L;                               /* padded caption length of THIS batch (blanks [B,n,L]) */
     int32_t flags;                           /* VQA_FLAG_DETERMINISTIC, VQA_FLAG_SHARED_LN, VQA_FLAG_BF16_GEMM (honoured:
-                                              * the routed layers listed at the flag) */
+                                              * the routed layers listed at the flag), VQA_FLAG_BF16_FEATURES (on top of
+                                              * VQA_FLAG_BF16_GEMM: image_ft is bf16 at rest) */
     float keep_att, keep_joint;              /* 0.8 / 0.5 */
     float global_valid[2];                   /* data parallel: number of valid entries of the GLOBAL batch per category
                                               * (object, attribute) = the denominator of the masked mean losses
@@ -789,7 +799,8 @@ typedef struct {                            /* one blank-fill category (vlmap_me
 } vqa_pretrain_kind_t;
 
 typedef struct {
-    const float* image_ft;                  /* [B,R,D] */
+    const float* image_ft;                  /* [B,R,D]; with VQA_FLAG_BF16_FEATURES the same pointer is read as
+                                             * const uint16_t* [B,R,D]: raw bf16 patterns (no member moves) */
     const float* spatial_ft;                /* [B,R,6] */
     const int32_t* num_boxes;               /* [B] */
     vqa_pretrain_kind_t kind[2];            /* 0 = object, 1 = attribute */

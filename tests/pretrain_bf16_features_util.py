@@ -1,0 +1,157 @@
+"""Helpers of tests/test_gpu_pretrain_bf16_features.py: a pair of pre-training engines built from the same parameters,
+
+    Y  PretrainEngine(precision="bf16", features="bf16") on t16 = the features rounded to bf16,
+    X  PretrainEngine(precision="bf16")                  on t16.float(),
+
+run side by side on one batch.  Rounding is idempotent and no kernel changes a summation order with the memory's type, so
+everything the two compute must be equal bit for bit; X itself is pinned to the float64 reference by
+tests/test_gpu_pretrain_bf16.py.  Variables, batches and masks come from the generators the other pre-training tests use
+(oracle/pretrain_oracle.py, tests/pretrain_*_ref.py), here at shapes chosen per attention route."""
+import numpy as np
+import torch
+
+from oracle import pretrain_oracle as PO
+from tests import pretrain_adapt_ref as AR
+from tests import pretrain_enwiki_ref as ER
+from tests import pretrain_noc_ref as NR
+
+SEED = 33
+N_CTX, LC = 60, 7
+ENWIKI_HEADS = ("bf", "ws", "ew")
+MODELS = ("cfg5", "enwiki", "noc", "adapt")
+KEEPS = ("none", "masks", "seeded")          # KEEP_NONE, KEEP_BYTES, KEEP_SEEDED of csrc/keep_launch.h
+
+# (B, n, R, D, H, W, A, L, Vq, n_ws).  Which attention kernels a shape reaches (csrc/attention.hip, attn_fwd_typed /
+# attn_bwd_typed with vqa_attn_set_fast(1)):
+#   full*   per-memory forward (attn_pool_fwd_rep_kernel<4, 1>) + fast backward <5>; R 3 is below REP_PF = 4 (every
+#           prefetched row clamps), R 7 leaves one partial pooling batch (4 + 3 of 6), R 40 is the kernels' bound
+#   h256    per-memory forward <H4L 1, D4T 2> + the generic backward <5> (H != 1024)
+#   toy, medium   generic per-query forward + generic backward <5> (n 2 and n 5)
+#   n7      generic backward <8>
+SHAPES = {"full": (4, 5, 36, 2048, 1024, 300, 4000, 10, 500, 100),
+          "full_r3": (2, 5, 3, 2048, 1024, 300, 300, 6, 200, 50),
+          "full_r7": (2, 5, 7, 2048, 1024, 300, 300, 6, 200, 50),
+          "full_r40": (2, 5, 40, 2048, 1024, 300, 300, 6, 200, 50),
+          "h256": (2, 5, 7, 4096, 256, 300, 300, 6, 200, 50),
+          "toy": (3, 2, 5, 24, 16, 12, 21, 4, 20, 7),
+          "medium": (8, 5, 36, 256, 128, 300, 300, 10, 200, 50),
+          "n7": (3, 7, 5, 24, 16, 12, 21, 4, 20, 7)}
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+_CASES = {}
+
+
+def make_case(model, shape, ln_shared=True):
+    """(engine keywords, params, batch, masks, dims) of a model at a named shape, as float32 host arrays; built once and
+    shared (nothing here is ever written to).  num_boxes lies in [max(R // 2, 1), R]: never 0 (an all-masked softmax is NaN
+    by contract)."""
+    key = (model, shape, ln_shared)
+    if key in _CASES:
+        return _CASES[key]
+    B, n, R, D, H, W, A, L, Vq, n_ws = SHAPES[shape]
+    rng = np.random.default_rng(SEED)
+    dims = dict(W=W, D=D, H=H, ln_shared=ln_shared)
+    batch = PO.make_batch(rng, B, n, R, D, L, Vq, n_ws, A)
+    masks = PO.make_masks(rng, B, n, R, H)
+    assert batch["num_boxes"].min() >= 1
+    if model == "cfg5":
+        p, ekw = PO.init_params(rng, Vq, n_ws, A, **dims), {}
+    elif model == "enwiki":
+        p = ER.init_params(rng, Vq, n_ws, A, heads=ENWIKI_HEADS, n_ctx=N_CTX, **dims)
+        batch = ER.add_enwiki_fields(rng, batch, N_CTX, LC)
+        masks = ER.add_enwiki_masks(rng, masks, B, n, H)
+        ekw = dict(heads=ENWIKI_HEADS, n_ctx=N_CTX)
+    elif model == "noc":
+        p = NR.init_params(rng, Vq, n_ws, A, heads=("bf", "ws"), **dims)
+        masks = NR.add_noc_masks(rng, masks, B, n, H, ("bf", "ws"))
+        ekw = dict(heads=("bf", "ws"), noc=True)
+    else:
+        p = AR.init_params(rng, Vq, n_ws, A, **dims)
+        ekw = dict(heads=AR.HEADS, adapt=True)
+    d = dict(B=B, n=n, R=R, D=D, H=H, W=W, A=A, L=L, Vq=Vq, n_ws=n_ws)
+    _CASES[key] = (ekw, p, batch, masks, d)
+    return _CASES[key]
+
+
+def make_tables(d, extra=3):
+    """feature tables of B + extra images and B image indices that are not all distinct and not in order"""
+    rng = np.random.default_rng(SEED + 1)
+    N, R, D = d["B"] + extra, d["R"], d["D"]
+    table = np.maximum(rng.standard_normal((N, R, D)), 0).astype(np.float32)
+    spat = rng.random((N, R, 6)).astype(np.float32)
+    nbox = rng.integers(max(R // 2, 1), R + 1, size=N).astype(np.int32)
+    idx = rng.integers(0, N, size=d["B"]).astype(np.int64)
+    idx[-1] = idx[0]                      # one image twice
+    idx[1 % d["B"]] = N - 1               # and the table's last row
+    return table, spat, nbox, idx
+
+
+def engine(model, shape, ln_shared=True, **kw):
+    from vqa_transfer_externaldata_amd import pretrain as PT
+    ekw, p, batch, masks, d = make_case(model, shape, ln_shared)
+    eng = PT.PretrainEngine(n=d["n"], R=d["R"], D=d["D"], H=d["H"], W=d["W"], A=d["A"], Vq=d["Vq"], n_ws=d["n_ws"], params=p,
+                            deterministic=True, **ekw, **kw)
+    assert eng.ln_shared == ln_shared
+    return PT, eng
+
+
+def device_batch(PT, model, shape, ln_shared, bf16, tables, eng):
+    """the device batch of one side: `bf16` selects the bf16 features (Y) or the same values widened to f32 (X); tables:
+    bind [N,R,D] tables and hand the batch image_idx instead of image_ft / spatial_ft / num_boxes"""
+    ekw, p, batch, masks, d = make_case(model, shape, ln_shared)
+    db = {k: dev(v) for k, v in batch.items()}
+    db.update({k: v for k, v in PT.add_length_sort(dict(batch)).items() if k.endswith("/sort")})
+    cast = (lambda t16: t16) if bf16 else (lambda t16: t16.float())
+    if tables:
+        table, spat, nbox, idx = make_tables(d)
+        for k in ("image_ft", "spatial_ft", "num_boxes"):
+            del db[k]
+        db["image_idx"] = dev(idx)
+        eng.bind_tables(cast(dev(table).to(torch.bfloat16)).contiguous(), spat, nbox)
+    else:
+        db["image_ft"] = cast(db["image_ft"].to(torch.bfloat16)).contiguous()
+    dm = {k: dev(v.astype(np.uint8)) for k, v in masks.items()}
+    return db, dm
+
+
+INTERMEDIATES = ("obj/att", "attr/att", "obj/pooled", "attr/pooled", "d_v", "d_qv", "part_dw", "part_db")
+
+
+def run(model, shape, keep, tables=False, ln_shared=True, bf16=True, steps=2, engine_kw=None):
+    """Two train steps of one side; returns everything the two sides are compared on, as clones"""
+    kw = dict(precision="bf16", features="bf16") if bf16 else dict(precision="bf16")
+    if engine_kw is not None:
+        kw = engine_kw
+    PT, eng = engine(model, shape, ln_shared, **kw)
+    db, dm = device_batch(PT, model, shape, ln_shared, bf16, tables, eng)
+    for it in range(steps):
+        if keep == "seeded":
+            eng.train_step(db, None, 1e-3, dropout=(SEED, it))
+        else:
+            eng.train_step(db, dm if keep == "masks" else None, 1e-3)
+    torch.cuda.synchronize()
+    out = {"grad/" + k: v.clone() for k, v in eng.grads.items()}
+    out.update({"grad_flat": eng.grad_flat.clone(), "train_flat": eng.train_flat.clone(), "adam_m": eng.m_flat.clone(),
+                "adam_v": eng.v_flat.clone()})
+    for nm in INTERMEDIATES + (("va_pre",) if model == "adapt" else ()):
+        out["ws/" + nm] = eng.tensor(nm).clone()
+    rep = eng.fetch_report()
+    out["report"] = torch.tensor([rep[k] for k in sorted(rep)], dtype=torch.float64)
+    return eng, out
+
+
+def assert_pair_equal(x, y, what):
+    """every entry bit for bit, finite where it is a result, and not trivially so (the attention did something)"""
+    assert sorted(x) == sorted(y)
+    bad = [k for k in sorted(x) if not torch.equal(x[k], y[k])]
+    for k in bad:
+        dlt = (x[k].double() - y[k].double()).abs()
+        print("%s: %s differs in %d of %d elements, max |difference| %.3e" % (what, k, int((dlt > 0).sum()), dlt.numel(), float(dlt.max())))
+    assert not bad, (what, bad)
+    for k in ("report", "grad_flat", "train_flat", "ws/obj/att", "ws/attr/pooled", "ws/d_v", "ws/d_qv", "ws/part_dw"):
+        assert torch.isfinite(y[k]).all(), (what, k)
+    assert float(y["ws/obj/pooled"].abs().max()) > 0 and float(y["ws/d_v"].abs().max()) > 0, what

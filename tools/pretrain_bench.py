@@ -7,7 +7,10 @@ also prints the analytic MFMA FLOPs per step (flops_per_step) and the rate they 
 chosen model in one process and times their steps alternately (each warmed up first), so that both rates come from the
 same box and clocks.  `--precision bf16` builds the timed engine(s) with PretrainEngine(precision="bf16");
 `--ab_precision` builds the chosen model twice, f32 and bf16 (same parameters, same batch), and alternates their steps
-the same way: both medians and their ratio.  Without options the output is the cfg-5 line as before."""
+the same way: both medians and their ratio.  `--ab_features` builds it twice with precision="bf16": X on the batch's
+features rounded to bf16 and widened to f32, Y with features="bf16" on the rounded features themselves (same parameters,
+bit-identical steps), alternated; medians of `steps`, `--repeats` times over, and Y counts as slower only when it is behind
+X by more than the spread of X's own medians.  Without options the output is the cfg-5 line as before."""
 import argparse
 import os
 import sys
@@ -31,6 +34,8 @@ _ap.add_argument("--model_type", default="vlmap_bf_or_wordset_withatt_sp",
 _ap.add_argument("--alternate", action="store_true")
 _ap.add_argument("--precision", default="f32", choices=list(PT.PRECISIONS))
 _ap.add_argument("--ab_precision", action="store_true")
+_ap.add_argument("--ab_features", action="store_true")
+_ap.add_argument("--repeats", type=int, default=5, help="--ab_features: how many medians of `steps` per engine")
 ARGS = _ap.parse_args()
 
 
@@ -66,8 +71,11 @@ sort_info = {} if os.environ.get("SORT", "1") == "0" else {k: v for k, v in PT.a
 steps = ARGS.steps
 
 
-def other_model(model_type, precisions):
-    """the engines (one per precision, same parameters), device batch and FLOPs per step of a model other than cfg-5"""
+def model_engines(model_type, engine_kws):
+    """the engines (one per keyword set, same parameters), host batch and FLOPs per step of a model"""
+    if model_type == "vlmap_bf_or_wordset_withatt_sp":
+        return ([PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p, **kw) for kw in engine_kws], batch,
+                flops_per_step(PT.CFG5_HEADS, batch))
     noc, adapt = model_type in PT.NOC_MODEL_HEADS, model_type in PT.ADAPT_MODEL_HEADS
     heads = (PT.NOC_MODEL_HEADS if noc else PT.ADAPT_MODEL_HEADS if adapt else PT.MODEL_HEADS)[model_type]
     if "ew" in heads:
@@ -80,14 +88,65 @@ def other_model(model_type, precisions):
     n_ctx = N_CTX if "ew" in heads else None
     pe = PT.init_random_params(rng, Vq, n_ws, A, W=W, D=D, H=H, heads=heads, n_ctx=n_ctx, noc=noc, adapt=adapt)
     engines = [PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=pe, heads=heads, n_ctx=n_ctx,
-                                 noc=noc, adapt=adapt, precision=pr) for pr in precisions]
+                                 noc=noc, adapt=adapt, **kw) for kw in engine_kws]
+    return engines, be, flops_per_step(heads, be, noc, adapt)
+
+
+def other_model(model_type, precisions):
+    """the engines (one per precision, same parameters), device batch and FLOPs per step of a model other than cfg-5"""
+    engines, be, fl = model_engines(model_type, [dict(precision=pr) for pr in precisions])
     dbe = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
     if os.environ.get("SORT", "1") != "0":
         dbe.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
     for ee in engines:
         for i in range(3):
             ee.train_step(dbe, ee.make_keep_masks(B, 1, i), 1e-3)
-    return engines, dbe, flops_per_step(heads, be, noc, adapt)
+    return engines, dbe, fl
+
+
+if ARGS.ab_features:
+    (ex, ey), be, fl = model_engines(ARGS.model_type, [dict(precision="bf16"), dict(precision="bf16", features="bf16")])
+    dbx = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
+    if os.environ.get("SORT", "1") != "0":
+        dbx.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
+    t16 = dbx["image_ft"].to(torch.bfloat16).contiguous()
+    dbx["image_ft"] = t16.float()
+    runs = (("X f32 features", ex, dbx), ("Y bf16 features", ey, dict(dbx, image_ft=t16)))
+    # (the timed engines run without deterministic=True, so only their forwards are compared here; the step-level
+    # comparison is tests/test_gpu_pretrain_bf16_features.py)
+    fwd = []
+    for _, e, d in runs:
+        e.forward(d, e.make_keep_masks(B, 1, 0))
+        fwd.append([e.tensor(k + "/" + t).clone() for k in PT.KINDS for t in ("att", "pooled")] + [e.tensor("report").clone()])
+    print("forward of X and Y at these dims (att, pooled, report of both categories): %s"
+          % ("bit for bit equal" if all(torch.equal(a, b) for a, b in zip(*fwd)) else "DIFFERENT"))
+    for _, e, d in runs:
+        for i in range(3):
+            e.train_step(d, e.make_keep_masks(B, 1, i), 1e-3)
+    meds = {k: [] for k, _, _ in runs}
+    for r in range(ARGS.repeats):
+        times = {k: [] for k, _, _ in runs}
+        for i in range(steps):
+            for k, e, d in runs:
+                masks = e.make_keep_masks(B, 1, 3 + r * steps + i)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.train_step(d, masks, 1e-3)
+                torch.cuda.synchronize()
+                times[k].append(time.perf_counter() - t0)
+        for k in times:
+            meds[k].append(1e3 * float(np.median(times[k])))
+        print("%s repeat %d: " % (ARGS.model_type, r) + "  ".join("%s %.3f ms" % (k, meds[k][-1]) for k in meds)
+              + "  (medians of %d alternated steps)" % steps)
+    mx, my = float(np.median(meds["X f32 features"])), float(np.median(meds["Y bf16 features"]))
+    spread = max(meds["X f32 features"]) - min(meds["X f32 features"])
+    print("%s: X %.3f ms, Y %.3f ms (medians of the %d medians), Y - X = %+.3f ms, spread of X's medians %.3f ms -> Y is %s; "
+          "flops_per_step %.3f TFLOP; total_loss %.3f / %.3f"
+          % (ARGS.model_type, mx, my, ARGS.repeats, my - mx, spread, "SLOWER" if my - mx > spread else "not slower", fl / 1e12,
+             ex.fetch_report()["total_loss"], ey.fetch_report()["total_loss"]))
+    print("resident features: N * %d * %d * 2 bytes (bf16) against N * %d * %d * 4 (f32): %.1f against %.1f GB per 100 k images"
+          % (R, D, R, D, 1e5 * R * D * 2 / 1e9, 1e5 * R * D * 4 / 1e9))
+    sys.exit(0)
 
 
 if ARGS.ab_precision:

@@ -293,6 +293,8 @@ __global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
 // pooling loop keeps REP accumulators per thread over one stream of V.
 // Keep policy as in the one-query forms: KEEP_BYTES loads the mask word of query q0 + j from mb4 (the base of query q0),
 // KEEP_SEEDED computes it (sq.word0 = the word index of query q0's mask).
+// VT as in the one-query kernels: the prefetched rows and the pooling batches stay raw in registers (half the registers
+// for a bf16 memory) and are widened where they are used; lane -> element mapping and summation orders do not depend on VT.
 constexpr int REP_PF = 4, REP_POOL_BATCH = 6;
 template <int H4L, int CNT, int KP, int REP, typename... KS>
 __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ vb4, const unsigned* __restrict__ mb4,
@@ -345,9 +347,9 @@ __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ v
     }
 }
 
-template <int H4L, int D4T, int KP, int REP, typename... KS>
+template <int H4L, int D4T, int KP, int REP, typename VT, typename... KS>
 __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
-    const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
+    const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
     KS... ks) {
@@ -360,13 +362,13 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
     const int64_t q0 = (int64_t)mem * REP;                         // first query of this memory
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
     const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
-    const f32x4v* Vb4 = reinterpret_cast<const f32x4v*>(V + (int64_t)mem * R * D);
+    const VT* Vb = V + (int64_t)mem * R * D;
 
-    f32x4v xv[REP_PF][D4T];
+    typename VMem<VT>::Raw xv[REP_PF][D4T];
 #pragma unroll
     for (int j = 0; j < REP_PF; ++j)
 #pragma unroll
-        for (int c = 0; c < D4T; ++c) xv[j][c] = Vb4[(int64_t)min(j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS];
+        for (int c = 0; c < D4T; ++c) xv[j][c] = VMem<VT>::load(Vb, (int64_t)min(j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
 
     for (int i = threadIdx.x; i < REP * H; i += FWD_THREADS) qw[i] = qv[q0 * H + i] * w[i % H];
     const float bias0 = bias[0];
@@ -411,22 +413,23 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
         for (int j = 0; j < REP; ++j) {
             const float a = (r < R) ? s[j * 40 + min(r, R - 1)] : 0.f;
 #pragma unroll
-            for (int c = 0; c < D4T; ++c) acc[j][c] += a * xv[r][c];
+            for (int c = 0; c < D4T; ++c) acc[j][c] += a * VMem<VT>::widen(xv[r][c]);
         }
     }
     for (int r0 = REP_PF; r0 < R; r0 += REP_POOL_BATCH) {
-        f32x4v y[REP_POOL_BATCH][D4T];
+        typename VMem<VT>::Raw y[REP_POOL_BATCH][D4T];
 #pragma unroll
         for (int i = 0; i < REP_POOL_BATCH; ++i)
 #pragma unroll
-            for (int c = 0; c < D4T; ++c) y[i][c] = Vb4[(int64_t)min(r0 + i, R - 1) * D4 + threadIdx.x + c * FWD_THREADS];
+            for (int c = 0; c < D4T; ++c)
+                y[i][c] = VMem<VT>::load(Vb, (int64_t)min(r0 + i, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
 #pragma unroll
         for (int i = 0; i < REP_POOL_BATCH; ++i) {
 #pragma unroll
             for (int j = 0; j < REP; ++j) {
                 const float a = (r0 + i < R) ? s[j * 40 + min(r0 + i, R - 1)] : 0.f;
 #pragma unroll
-                for (int c = 0; c < D4T; ++c) acc[j][c] += a * y[i][c];
+                for (int c = 0; c < D4T; ++c) acc[j][c] += a * VMem<VT>::widen(y[i][c]);
             }
         }
     }
@@ -871,7 +874,6 @@ int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* 
     VQA_REQUIRE(!(seeded_one_query && keep.is_seeded()) || rep == 1, VQA_ERR_UNSUPPORTED);      // vqa_attn_pool_fwd_seeded
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);         // several queries per memory: an f32 memory only
     VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
     VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(pooled) && keep.words_ok(), VQA_ERR_ALIGN);
     if (B == 0) return VQA_OK;
@@ -880,33 +882,35 @@ int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* 
     hipStream_t st = (hipStream_t)stream;
     const bool fast = g_attn_fast && (rep == 1 || rep == 5 || g_attn_fast > 1) && R <= 40 && H % 256 == 0 && H <= 1024 && D % 2048 == 0 && D <= 4096 &&
                       vqa_aligned16(qv) && vqa_aligned16(w);
-    // the 1024-wide memory (v_adapt of the pre-training model): per-memory kernel for rep 5 only; one query per memory at
-    // D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
-    const bool fast1024 = g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
+    // the 1024-wide memory (v_adapt of the pre-training model, an f32 activation -- never the table): per-memory kernel
+    // for rep 5 only; one query per memory at D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
+    const bool fast1024 = v_is_f32<VT>() && g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
                           vqa_aligned16(qv) && vqa_aligned16(w);
+    // one workgroup per memory for the pre-training model's 5 queries per image
+    const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
     if constexpr (v_is_f32<VT>()) {
-        // one workgroup per memory for the pre-training model's 5 queries per image
-        if (fast1024 || (fast && rep == 5 && g_attn_fast != 3)) {
-            const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
-            if (fast1024)
-                keep_dispatch(keep, [&](auto kp, auto... ks) {
-                    hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, decltype(kp)::value, 5, decltype(ks)...>), dim3(B),
-                                       dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, ks...);
-                });
-            else
-                int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
-                    int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
-                        keep_dispatch(keep, [&](auto kp, auto... ks) {
-                            hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<decltype(h4l)::value, decltype(d4t)::value,
-                                                                         decltype(kp)::value, 5, decltype(ks)...>),
-                                               dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att,
-                                               pooled, R, ks...);
-                        });
-                    });
-                });
+        if (fast1024) {
+            keep_dispatch(keep, [&](auto kp, auto... ks) {
+                hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, decltype(kp)::value, 5, decltype(ks)...>), dim3(B),
+                                   dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, ks...);
+            });
             VQA_CHECK_LAUNCH();
             return VQA_OK;
         }
+    }
+    if (fast && rep == 5 && g_attn_fast != 3) {
+        int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
+            int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
+                keep_dispatch(keep, [&](auto kp, auto... ks) {
+                    hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<decltype(h4l)::value, decltype(d4t)::value, decltype(kp)::value,
+                                                                 5, VT, decltype(ks)...>),
+                                       dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R,
+                                       ks...);
+                });
+            });
+        });
+        VQA_CHECK_LAUNCH();
+        return VQA_OK;
     }
     const size_t lds = (size_t)(H + R) * sizeof(float);
     if (fast)
@@ -938,7 +942,6 @@ int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const 
     VQA_REQUIRE(!(seeded_one_query && keep.is_seeded()) || rep == 1, VQA_ERR_UNSUPPORTED);      // vqa_attn_pool_bwd_seeded
     VQA_REQUIRE(rep >= 1 && rep <= 8, VQA_ERR_ARG);
     VQA_REQUIRE(B >= 0 && R > 0 && R <= MAX_R && H > 0 && D > 0, VQA_ERR_ARG);
-    VQA_REQUIRE(v_is_f32<VT>() || rep == 1, VQA_ERR_UNSUPPORTED);
     VQA_REQUIRE(H % 4 == 0 && D % 4 == 0, VQA_ERR_ALIGN);
     VQA_REQUIRE(vqa_aligned16(v) && v_aligned(V) && vqa_aligned16(dv) && vqa_aligned16(dqv) &&
                     vqa_aligned16(part_dw) && vqa_aligned16(qv) && vqa_aligned16(w) && keep.words_ok(),
@@ -962,30 +965,38 @@ int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const 
         VQA_CHECK_LAUNCH();
         return VQA_OK;
     }
-    if constexpr (v_is_f32<VT>()) {      // several queries per memory
-        if (fast_shape && rep == 5 && (D == 2048 || D == 1024)) {
-            int_dispatch<2048, 1024>(D, [&](auto dd) {
-                keep_dispatch(keep, [&](auto kp, auto... ks) {
-                    hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, decltype(dd)::value, float,
-                                                                  decltype(ks)...>),
-                                       dim3(B), dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw,
-                                       part_db, R, H, ks...);
-                });
+    // several queries per memory.  (D 1024 is the adapted memory, an f32 activation: a bf16 memory of that width takes the
+    // generic kernel, as its forward does)
+    if (fast_shape && rep == 5 && D == 2048) {
+        keep_dispatch(keep, [&](auto kp, auto... ks) {
+            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, 2048, VT, decltype(ks)...>), dim3(B),
+                               dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H,
+                               ks...);
+        });
+        VQA_CHECK_LAUNCH();
+        return VQA_OK;
+    }
+    if constexpr (v_is_f32<VT>()) {
+        if (fast_shape && rep == 5 && D == 1024) {
+            keep_dispatch(keep, [&](auto kp, auto... ks) {
+                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, 1024, float, decltype(ks)...>), dim3(B),
+                                   dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R,
+                                   H, ks...);
             });
             VQA_CHECK_LAUNCH();
             return VQA_OK;
         }
-        if (rep > 1) {
-            int_dispatch<5, 8>(rep <= 5 ? 5 : 8, [&](auto rt) {
-                keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
-                    hipLaunchKernelGGL((attn_pool_bwd_kernel<decltype(rt)::value, float, decltype(kp)::value, decltype(ks)...>),
-                                       dim3(B), dim3(BWD_THREADS), lds_for(decltype(rt)::value), st, dpooled, v, qv, V, att, w,
-                                       keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep, ks...);
-                });
+    }
+    if (rep > 1) {
+        int_dispatch<5, 8>(rep <= 5 ? 5 : 8, [&](auto rt) {
+            keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
+                hipLaunchKernelGGL((attn_pool_bwd_kernel<decltype(rt)::value, VT, decltype(kp)::value, decltype(ks)...>),
+                                   dim3(B), dim3(BWD_THREADS), lds_for(decltype(rt)::value), st, dpooled, v, qv, V, att, w,
+                                   keepmask, ik, dv, dqv, part_dw, part_db, R, H, D, rep, ks...);
             });
-            VQA_CHECK_LAUNCH();
-            return VQA_OK;
-        }
+        });
+        VQA_CHECK_LAUNCH();
+        return VQA_OK;
     }
     keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
         hipLaunchKernelGGL((attn_pool_bwd_kernel<1, VT, decltype(kp)::value, decltype(ks)...>), dim3(B), dim3(BWD_THREADS),

@@ -96,9 +96,14 @@ const char* const KIND[2] = {"obj", "attr"};
 const char* const HEAD[3] = {"bf", "ws", "ew"};      // blank fill, word set, enwiki context
 const char* const TASK[3] = {"blank_fill", "wordset", "enwiki"};
 
+inline bool feat16(const vqa_pretrain_dims_t& d) { return (d.flags & VQA_FLAG_BF16_FEATURES) != 0; }      // image_ft is bf16 patterns
+
+// (bf16 features only on top of the bf16 GEMMs: every query and every pass of every family goes through here, so the
+// flag alone is VQA_ERR_ARG before anything is launched)
 bool dims_ok(const vqa_pretrain_dims_t* d) {
     return d && d->B > 0 && d->n > 0 && d->n <= 8 && d->R > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->A > 0 &&
-           d->Vq > 0 && d->n_ws > 0 && d->L > 0 && d->H % 4 == 0 && d->D % 4 == 0;
+           d->Vq > 0 && d->n_ws > 0 && d->L > 0 && d->H % 4 == 0 && d->D % 4 == 0 &&
+           (!feat16(*d) || (d->flags & VQA_FLAG_BF16_GEMM));
 }
 
 struct Ctx : Workspace {
@@ -125,8 +130,14 @@ struct Ctx : Workspace {
     // The routed layers' products (forward, dW, dx): bf16 operands in the matrix unit under VQA_FLAG_BF16_GEMM, else f32.
     // A shape the bf16 kernel refuses is its error return, never a silent f32 product.  Every call site names one of the
     // two wrappers: there is no default a new site could pick up by accident.
+    // a16: the left operand is the features under VQA_FLAG_BF16_FEATURES -- raw bf16 patterns behind the float pointer, lda
+    // in elements; the flag implies VQA_FLAG_BF16_GEMM (dims_ok), so there is no f32 form of it.
     int gemm_routed(int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B, int ldb,
-                    float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) const {
+                    float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0,
+                    bool a16 = false) const {
+        if (a16)
+            return vqa_gemm_bf16_a16(tA, tB, (int)M, (int)N, (int)K, reinterpret_cast<const uint16_t*>(A), lda, B, ldb, C, ldc,
+                                     bias, D, ldd, 0, f("gemm_ws"), count("gemm_ws"), 0, st);
         if (d.flags & VQA_FLAG_BF16_GEMM)
             return vqa_gemm_bf16(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, f("gemm_ws"),
                                  count("gemm_ws"), 0, st);
@@ -160,10 +171,12 @@ struct Acc {
     // the same kernel's D == C form.  No model touches a ROUTED weight twice today (every routed layer is one stacked
     // product; the second touches are wordset_ft and the box layers, f32), so no step-level test runs the bf16 kernel's
     // D == C form: it is covered by the op tests of vqa_gemm_bf16 only (tests/test_gpu_bf16.py, in-place addend).
-    int weight(Prec prec, float* gw, const float* x, int ldx, const float* dpre, int ldp, int64_t K, int64_t N, int64_t M) {
+    // x16: x is the features under VQA_FLAG_BF16_FEATURES (Ctx::gemm_routed's a16; a routed layer's only)
+    int weight(Prec prec, float* gw, const float* x, int ldx, const float* dpre, int ldp, int64_t K, int64_t N, int64_t M,
+               bool x16 = false) {
         const bool first = touched.insert(gw).second;
         const float* add = first ? nullptr : gw;
-        if (prec == PREC_ROUTED) return c.gemm_routed(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
+        if (prec == PREC_ROUTED) return c.gemm_routed(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N, x16);
         return c.gemm_f32(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
     }
     auto f32() {      // weight(PREC_F32, ...) in the argument order of a GEMM call with tA = 1, tB = 0 (gru_encoder.h)
@@ -583,8 +596,9 @@ Batch view(const vqa_pretrain_noc_batch_t* b) {
     return v;
 }
 
-// the memory the spatial attention pools: one [B,R,width] block per category
-struct PoolMem { const float* mem[2]; int64_t width; };
+// the memory the spatial attention pools: one [B,R,width] block per category; bf16: raw bf16 patterns behind the pointers
+// (the features under VQA_FLAG_BF16_FEATURES; the adapted memory is an f32 activation in every mode)
+struct PoolMem { const float* mem[2]; int64_t width; bool bf16; };
 
 // the keep struct's offsets, or zeros without one
 const vqa_pretrain_keep_t NO_SEEDED_SITES = {};
@@ -818,7 +832,7 @@ int trunk_fwd(const Ctx& c, const Model& m, const Params& P, const Batch& b, con
                       p + "v_mean", p + "v_rstd", NO_KEEP));
         TRY(fc_ln_fwd(c, c.f(p + "key6"), Bn, 6, H, P.spat_q_linear_v, c.li(k), (int)n, 0, p + "qv_pre", p + "qv",
                       p + "qv_mean", p + "qv_rstd", NO_KEEP));
-        TRY(vqa_attn_fwd_run(c.f(p + "v"), c.f(p + "qv"), pm.mem[k], false, bt->num_boxes,
+        TRY(vqa_attn_fwd_run(c.f(p + "v"), c.f(p + "qv"), pm.mem[k], pm.bf16, bt->num_boxes,
                              P.spat_att_score.w, P.spat_att_score.b, att_keep(c, b, k), c.f(p + "att"), c.f(p + "pooled"),
                              (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         hipLaunchKernelGGL(valid_kernel, dim3(1), dim3(256), 0, c.st, kb.num, c.f(p + "valid"), c.f(p + "inv_valid"),
@@ -866,7 +880,7 @@ int trunk_bwd(const Ctx& c, Acc& acc, const Model& m, const Params& P, const Par
             TRY(sq.add(c.f("d_wse"), Bn * W));
         }
         // ---- spatial attention
-        TRY(vqa_attn_bwd_run(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm.mem[k], false,
+        TRY(vqa_attn_bwd_run(c.f("d_pooled") + k * Bn * D, c.f(p + "v"), c.f(p + "qv"), pm.mem[k], pm.bf16,
                              c.f(p + "att"), P.spat_att_score.w, att_keep(c, b, k), c.f("d_v"), c.f("d_qv"),
                              c.f("part_dw"), c.f("part_db"), (int)B, (int)n, (int)R, (int)H, (int)D, c.st));
         TRY(acc.colsum(c.f("part_dw"), Bn, H, (int)H, G.spat_att_score.w));
@@ -926,7 +940,8 @@ int v_adapt_fwd(const Ctx& c, const vqa_pretrain_batch_t* bt, const vqa_pt_fc6_t
     const int64_t B = d.B, R = d.R, D = d.D, H = d.H;
     const bool ln_shared = (d.flags & VQA_FLAG_SHARED_LN) != 0;
     ProbeScope ps("pt.v_adapt.fwd", c.st);
-    TRY(c.gemm_routed(0, 0, B * R, H, D, bt->image_ft, (int)D, va.w, (int)H, c.f("va_pre"), (int)H, va.b));
+    TRY(c.gemm_routed(0, 0, B * R, H, D, bt->image_ft, (int)D, va.w, (int)H, c.f("va_pre"), (int)H, va.b, nullptr, 0,
+                      feat16(d)));
     for (int k = 0; k < (ln_shared ? 1 : 2); ++k) {
         const std::string p = std::string(KIND[k]) + "/";
         TRY(vqa_ln_act_fwd_run(c.f("va_pre"), va.gamma[k], va.beta[k], NO_KEEP, c.f(p + "va"), c.f(p + "va_mean"),
@@ -957,13 +972,13 @@ int v_adapt_bwd(const Ctx& c, Acc& acc, const vqa_pretrain_batch_t* bt, const vq
         }
         TRY(vqa_add_inplace(c.f("d_vapre"), c.f("d_vapre1"), B * R * H, c.st));
     }
-    return acc.weight(PREC_ROUTED, g_va.w, bt->image_ft, (int)D, c.f("d_vapre"), (int)H, D, H, B * R);
+    return acc.weight(PREC_ROUTED, g_va.w, bt->image_ft, (int)D, c.f("d_vapre"), (int)H, D, H, B * R, feat16(d));
 }
 
 // the memory the model's attention pools: the features, or v_adapt per LayerNorm slot
 PoolMem pool_mem(const Ctx& c, const Model& m, const Batch& b) {
-    if (m.arch == ARCH_ADAPT) return {{c.f("obj/va"), c.f("attr/va")}, c.d.H};
-    return {{b.x.base.image_ft, b.x.base.image_ft}, c.d.D};
+    if (m.arch == ARCH_ADAPT) return {{c.f("obj/va"), c.f("attr/va")}, c.d.H, false};
+    return {{b.x.base.image_ft, b.x.base.image_ft}, c.d.D, feat16(c.d)};
 }
 
 // ---------------------------------------------------------------- the head blocks

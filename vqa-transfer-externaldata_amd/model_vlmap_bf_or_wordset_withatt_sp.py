@@ -16,6 +16,7 @@ import torch
 
 from . import pretrain as PT
 from .dataset_vlmap import _load_pickle
+from .model_vlmap_answer import features_to_bf16      # (that module imports fusion, never this one: no cycle)
 
 TOP_K = 5
 W_DIM = 300   # Word dimension
@@ -108,6 +109,8 @@ class Model(object):
         for k in ("image_ft", "spatial_ft"):
             if k in out:
                 out[k] = out[k].float()
+        if "image_ft" in out and getattr(self.config, "features", "f32") == "bf16":
+            out["image_ft"] = features_to_bf16(out["image_ft"]).contiguous()      # rounded once, where it lives
         if getattr(self.config, "sort_by_length", 1):
             host = PT.add_length_sort({k: v for k, v in self.batch.items()
                                        if k.endswith(("/blanks", "/blanks_len", "/enwiki_context", "/enwiki_context_len"))})
@@ -166,11 +169,14 @@ class Model(object):
                                              params=self._initial_params(shapes), device=self.device,
                                              deterministic=bool(getattr(self.config, "deterministic", 0)),
                                              heads=self.heads, n_ctx=self.num_context_vocab, noc=self.NOC,
-                                             adapt=self.ADAPT, precision=getattr(self.config, "precision", "f32"))
+                                             adapt=self.ADAPT, precision=getattr(self.config, "precision", "f32"),
+                                             features=getattr(self.config, "features", "f32"))
         eng = self._engine
         B = int((db["image_ft"] if "image_ft" in db else db["image_idx"]).shape[0])
         tables = getattr(self.config, "feature_tables", None)
         if tables is not None and getattr(eng, "_tables", None) is None:
+            if eng.features == "bf16":         # the table is rounded once, slice by slice, on its way to the device
+                tables = (features_to_bf16(tables[0], self.device),) + tuple(tables[1:])
             eng.bind_tables(*tables)           # (image_features, spatial_features, num_boxes): gathered on the device
         dpi = db.get("_dp") or {}
         # dropout: off, or the (seed, step, global row) stream -- as explicit keep-mask tensors (the default), or under

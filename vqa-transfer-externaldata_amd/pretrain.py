@@ -37,6 +37,9 @@ computed once per image and once for both categories, and its gradients complete
 Dropout: explicit uint8 keep-masks from make_keep_masks(B, seed, step) (the default), or `dropout=(seed, step)`: the same
 bits computed inside the attention and LayerNorm kernels that consume them (vqa_pretrain_*_ex with a vqa_pretrain_keep_t;
 DESIGN.md section 7), no mask tensor, bit for bit the same step.  keep_offsets() is the one copy of the stream layout.
+
+Precision: f32, or opt-in `precision="bf16"` (the routed head layers on the bf16 matrix unit) and on top of it
+`features="bf16"` (the region features at rest as bf16: table, gathered rows and what the attention kernels read).
 """
 from __future__ import annotations
 
@@ -236,6 +239,7 @@ PARAM_FIELDS = {_lib.PtParams: _TRUNK + _HEADS,
 
 
 PRECISIONS = ("f32", "bf16")      # PretrainEngine(precision=...): "bf16" sets VQA_FLAG_BF16_GEMM
+FEATURE_FORMATS = ("f32", "bf16")  # PretrainEngine(features=...): "bf16" sets VQA_FLAG_BF16_FEATURES
 
 
 def flat_layout(shapes):
@@ -262,7 +266,7 @@ def flat_layout(shapes):
 
 class PretrainEngine(EngineCore):
     def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
-                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False, precision="f32"):
+                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False, precision="f32", features="f32"):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
         variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint.
         heads: the head set (MODEL_HEADS); with 'ew', n_ctx = the enwiki context vocabulary and every batch carries
@@ -274,10 +278,21 @@ class PretrainEngine(EngineCore):
         classifier (noc: joint_v / joint_l / classifier_v / classifier_l; adapt: also v_adapt) multiply bf16-rounded
         operands with f32 accumulation (ops.gemm_bf16); both encoders, wordset_ft, the box layers and everything that is
         not a GEMM stay f32 (include/vqa_hot.h, VQA_FLAG_BF16_GEMM).  Every head set, noc and adapt.  Parameters,
-        gradients, Adam slots, state_dict() and the DP buckets are those of "f32": checkpoints are interchangeable."""
+        gradients, Adam slots, state_dict() and the DP buckets are those of "f32": checkpoints are interchangeable.
+        features="bf16" (opt-in, only with precision="bf16"): the region features are bf16 at rest -- bind_tables takes a
+        torch.bfloat16 table [N,R,D] (model_vlmap_answer.features_to_bf16 makes one), the gathered image_ft is bf16, a
+        batch that carries image_ft itself carries it as torch.bfloat16, and the attention kernels (adapt: v_adapt's
+        forward and dW GEMMs) read the 16-bit patterns as they are (VQA_FLAG_BF16_FEATURES).  Half the resident table; the
+        step equals, bit for bit, the precision="bf16" step on the same features widened to f32.  Every head set, noc
+        and adapt; parameters, checkpoints and DP buckets unchanged."""
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
+        if features not in FEATURE_FORMATS:
+            raise ValueError("features must be one of %s, not %r" % (FEATURE_FORMATS, features))
+        if features == "bf16" and precision != "bf16":
+            raise ValueError("features='bf16' needs precision='bf16' (the f32 products read f32 features)")
         self.precision = precision
+        self.features = features
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("PretrainEngine needs a GPU (no CPU fallback)")
@@ -322,7 +337,8 @@ class PretrainEngine(EngineCore):
 
     def _flags(self):
         return (_lib.FLAG_DETERMINISTIC if self.deterministic else 0) | (_lib.FLAG_SHARED_LN if self.ln_shared else 0) | \
-            (_lib.FLAG_BF16_GEMM if self.precision == "bf16" else 0)
+            (_lib.FLAG_BF16_GEMM if self.precision == "bf16" else 0) | \
+            (_lib.FLAG_BF16_FEATURES if self.features == "bf16" else 0)
 
     # ------------------------------------------------------------------ C-ABI plumbing
     def keep_offsets(self, B, step, row_offset=0, global_rows=None):
@@ -413,8 +429,17 @@ class PretrainEngine(EngineCore):
         """Keep the feature tables of the dataset ([N,R,D] f32, [N,R,6] f32, [N] i32) in HBM; batches may then carry
         `image_idx` (i64 [B]) instead of image_ft / spatial_ft / num_boxes and the rows are gathered on the device
         (`vqa_gather_features`), the cfg-5 counterpart of SURVEY row a1: no per-step np.take of 151 MB on the host and
-        no H2D copy of it.  The reference holds the whole '<split>_vfeat.hdf5' in host RAM (dataset_vlmap.py:67-72)."""
-        f = self._dev(image_features, torch.float32)
+        no H2D copy of it.  The reference holds the whole '<split>_vfeat.hdf5' in host RAM (dataset_vlmap.py:67-72).
+        features="bf16": image_features is a contiguous torch.bfloat16 device table [N,R,D], never converted here."""
+        if self.features == "bf16":
+            f = image_features
+            if not (torch.is_tensor(f) and f.dtype == torch.bfloat16 and f.is_cuda and f.is_contiguous()
+                    and f.dim() == 3 and tuple(f.shape[1:]) == (self.R, self.D)):
+                raise ValueError("features='bf16' needs a contiguous torch.bfloat16 device table [N, %d, %d] (got %s %s); "
+                                 "model_vlmap_answer.features_to_bf16 converts an f32 array"
+                                 % (self.R, self.D, getattr(f, "dtype", type(f)), tuple(getattr(f, "shape", ()))))
+        else:
+            f = self._dev(image_features, torch.float32)
         assert f.dim() == 3 and f.shape[1] == self.R and f.shape[2] == self.D, f.shape
         self._tables = (f, self._dev(spatial_features, torch.float32), self._dev(np.asarray(num_boxes), torch.int32))
         self._gathered = {}
@@ -427,7 +452,7 @@ class PretrainEngine(EngineCore):
         buf = self._gathered.get(B)
         if buf is None:
             buf = self._gathered[B] = {"spatial_ft": torch.empty(B, self.R, spat.shape[2], device=self.device)}
-        V, n = ops.gather_features(table, nb, idx)
+        V, n = (ops.gather_features_bf16 if self.features == "bf16" else ops.gather_features)(table, nb, idx)
         torch.index_select(spat, 0, idx, out=buf["spatial_ft"])
         return V, buf["spatial_ft"], n
 
@@ -465,6 +490,14 @@ class PretrainEngine(EngineCore):
             bs = _lib.PtBatch(image_ft=V.data_ptr(), spatial_ft=sp.data_ptr(), num_boxes=nb.data_ptr())
             B = V.shape[0]
         else:
+            if self.features == "bf16":      # as the table: bf16 already, never converted here
+                ft = batch["image_ft"]
+                if not (torch.is_tensor(ft) and ft.dtype == torch.bfloat16 and ft.is_cuda and ft.is_contiguous()
+                        and ft.dim() == 3 and tuple(ft.shape[1:]) == (self.R, self.D)):
+                    raise ValueError("features='bf16' needs image_ft as a contiguous torch.bfloat16 device tensor "
+                                     "[B, %d, %d] (got %s %s); model_vlmap_answer.features_to_bf16 converts an f32 array"
+                                     % (self.R, self.D, getattr(ft, "dtype", type(ft)), tuple(getattr(ft, "shape", ()))))
+                cache["image_ft"] = ft
             bs = _lib.PtBatch(image_ft=get("image_ft", torch.float32).data_ptr(),
                               spatial_ft=get("spatial_ft", torch.float32).data_ptr(),
                               num_boxes=get("num_boxes", torch.int32).data_ptr())

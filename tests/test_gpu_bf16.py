@@ -74,8 +74,8 @@ def test_gemm_bf16_strided_output_unaligned_operands_and_in_place_addend(lay):
         _check(out, A, B, tA, tB, bias, None, "%s strided out split %d" % (lay, split))
         assert torch.isnan(wide[:, :5]).all() and torch.isnan(wide[:, 5 + N:]).all()
     # operands that are windows of wider buffers at odd offsets: leading dimensions / bases off the 16-byte grid
-    Aw = torch.zeros(A.shape[0], A.shape[1] + 3, device="cuda")
-    Bw = torch.zeros(B.shape[0], B.shape[1] + 5, device="cuda")
+    Aw = torch.full((A.shape[0], A.shape[1] + 3), float("nan"), device="cuda")
+    Bw = torch.full((B.shape[0], B.shape[1] + 5), float("nan"), device="cuda")
     Aw[:, 1:1 + A.shape[1]] = A
     Bw[:, 3:3 + B.shape[1]] = B
     Av, Bv = Aw[:, 1:1 + A.shape[1]], Bw[:, 3:3 + B.shape[1]]

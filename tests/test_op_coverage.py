@@ -60,6 +60,9 @@ ATTN = ["attn_pool_fwd", "attn_pool_bwd", "attn_pool_fwd_rep", "attn_pool_bwd_re
 GEMM = ["gemm_f32", "gemm_f32_ex", "gemm_f32_gather", "gemm_set_config", "gemm_set_order", "gemm_set_max_blocks",
         "gemm_set_tall_config", "gemm_workspace_floats"]
 
+# the mixed-precision GEMM entry points tests/test_gpu_gemm_bf16_f64.py pins to the float64 reference of tests/gemm_bf16_ref.py, route by route
+GEMM_BF16 = ["gemm_bf16", "gemm_bf16_a16", "gemm_bf16_workspace_floats"]
+
 # the f32 extractor entry points and knobs tests/test_gpu_conv_f64.py pins to the float64 reference of tests/conv_ref.py, route by route
 CONV = ["conv2d_nhwc", "conv2d_nhwc_bwd", "conv2d_bwd_workspace_floats", "conv_set_config", "pad_c3c4_nhwc",
         "maxpool3x3s2_same_nhwc", "subsample_nhwc", "crop_and_resize_nhwc"]
@@ -118,6 +121,17 @@ def test_the_f32_gemm_stays_pinned_by_its_float64_test(repo_root):
     assert not set("vqa_" + k for k in GEMM) & set(ALLOWED)
     declared = set(_declared(repo_root))
     assert all("vqa_" + k in declared for k in GEMM)
+
+
+def test_the_bf16_gemm_stays_pinned_by_its_float64_test(repo_root):
+    text = open(os.path.join(repo_root, "tests", "test_gpu_gemm_bf16_f64.py")).read()
+    calls = set(re.findall(r"\blib\.(vqa_[a-z0-9_]+)\(", text))
+    missing = ["vqa_" + k for k in GEMM_BF16 if "vqa_" + k not in calls]
+    assert not missing, "tests/test_gpu_gemm_bf16_f64.py no longer calls %s" % missing
+    assert "gemm_bf16_ref" in text
+    assert not set("vqa_" + k for k in GEMM_BF16) & set(ALLOWED)
+    declared = set(_declared(repo_root))
+    assert all("vqa_" + k in declared for k in GEMM_BF16)
 
 
 def test_the_f32_extractor_kernels_stay_pinned_by_their_float64_test(repo_root):

@@ -23,7 +23,7 @@ KEEPS = ("none", "masks", "seeded")          # KEEP_NONE, KEEP_BYTES, KEEP_SEEDE
 
 # (B, n, R, D, H, W, A, L, Vq, n_ws).  Which attention kernels a shape reaches (csrc/attention.hip, attn_fwd_typed /
 # attn_bwd_typed with vqa_attn_set_fast(1)):
-#   full*   per-memory forward (attn_pool_fwd_rep_kernel<4, 1>) + fast backward <5>; R 3 is below REP_PF = 4 (every
+#   full*   per-memory forward (attn_pool_fwd_form_kernel<FwdRep, 4, 2048>) + fast backward <5>; R 3 is below FwdRep::PF = 4 (every
 #           prefetched row clamps), R 7 leaves one partial pooling batch (4 + 3 of 6), R 40 is the kernels' bound
 #   h256    per-memory forward <H4L 1, D4T 2> + the generic backward <5> (H != 1024)
 #   toy, medium   generic per-query forward + generic backward <5> (n 2 and n 5)

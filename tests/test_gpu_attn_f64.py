@@ -20,17 +20,18 @@ and output as a fraction of its bound.
 
 Worst errors measured on an MI355X over every case here, as a fraction of the bound (the float32 evaluation of the
 reference is at most 0.125 by construction):
-    kernel                             att     pooled    dv      dqv     part_dw  part_db  part_db given att
-    attn_pool_fwd_kernel               0.091   0.623
-    attn_pool_fwd_fast_kernel          0.091   0.623
-    attn_pool_fwd_rep_kernel           0.091   0.623
-    attn_pool_fwd_rep_d1024_kernel     0.044   0.482
-    attn_pool_bwd_kernel<1>                              0.089   0.046   0.045    0.075    0.126
-    attn_pool_bwd_kernel<5>                              0.076   0.053   0.052    0.095    0.218
-    attn_pool_bwd_kernel<8>                              0.030   0.033   0.033    0.050    0.160
-    attn_pool_bwd_fast_kernel<1>                         0.061   0.033   0.034    0.034    0.126
-    attn_pool_bwd_fast_kernel<5>                         0.078   0.063   0.062    0.083    0.204
-    attn_pool_bwd_fast_kernel<5,1024>                    0.058   0.043   0.044    0.049    0.229
+    kernel                                   att     pooled    dv      dqv     part_dw  part_db  part_db given att
+    attn_pool_fwd_kernel                     0.091   0.623
+    attn_pool_fwd_form_kernel<FwdFast>       0.091   0.623
+    attn_pool_fwd_form_kernel<FwdRep>        0.091   0.623
+    attn_pool_fwd_form_kernel<FwdRepD1024>   0.054   0.482
+    attn_pool_bwd_kernel<1>                                    0.089   0.067   0.066    0.075    0.126
+    attn_pool_bwd_kernel<5>                                    0.097   0.089   0.090    0.098    0.218
+    attn_pool_bwd_kernel<8>                                    0.030   0.033   0.033    0.050    0.160
+    attn_pool_bwd_fast_kernel<1>                               0.061   0.038   0.037    0.034    0.126
+    attn_pool_bwd_fast_kernel<5>                               0.078   0.063   0.062    0.086    0.204
+    attn_pool_bwd_fast_kernel<5,1024>                          0.058   0.043   0.044    0.049    0.229
+(the forward forms are the dispatch routes fwd_fast, fwd_rep and fwd_rep_d1024 of fwd_kernel() below.)
 pooled's 0.62 is where (R + 2) 2^-24 caps its coefficient (R <= 32).  The mask of ones at keep_prob 1 holds the bits
 of the unmasked call on the generic kernels, a misaligned operand holds the bits of the generic kernels, and the
 neighbours of an nb == 0 memory hold the bits of a run without it.
@@ -224,8 +225,8 @@ def run_case(c):
 @pytest.mark.parametrize("D", [2048, 4096])
 @pytest.mark.parametrize("H", [256, 512, 768, 1024])
 def test_fast_forward_forms(H, D, rep):
-    # rep 1: attn_pool_fwd_fast_kernel<H/256, D/2048, MASK> under 1; rep 2: the same kernel under 3 (m = q // 2);
-    # rep 5: attn_pool_fwd_rep_kernel<H/256, D/2048, MASK, 5> under 1 and the per-query kernel under 3;
+    # rep 1: attn_pool_fwd_form_kernel<FwdFast, H/256, D, MASK> under 1; rep 2: the same form under 3 (m = q // 2);
+    # rep 5: attn_pool_fwd_form_kernel<FwdRep, H/256, D, MASK> under 1 and the per-query form under 3;
     # every one beside attn_pool_fwd_kernel under 0; R on both sides of every row batch.  H 1024, D 2048 also runs
     # 1 and 2 at rep 2 (generic under 1, fast under 2) and 2 at rep 5 (the per-memory kernel, like 1)
     for c in A.fast_fwd_cases(H, D):
@@ -235,7 +236,7 @@ def test_fast_forward_forms(H, D, rep):
 
 @pytest.mark.parametrize("rep", [1, 5])
 def test_1024_wide_memory_forms(rep):
-    # rep 5: attn_pool_fwd_rep_d1024_kernel<4, MASK, 5> and attn_pool_bwd_fast_kernel<5, MASK, 1024> under 1 and 2, the generic
+    # rep 5: attn_pool_fwd_form_kernel<FwdRepD1024, 4, 1024, MASK> and attn_pool_bwd_fast_kernel<5, MASK, 1024> under 1 and 2, the generic
     # forward with the fast backward under 3; rep 1: the generic kernels under every setting
     for c in A.d1024_cases():
         if c.rep == rep:
@@ -292,7 +293,7 @@ def test_misaligned_operands_take_the_generic_kernels(rep, which):
 # ------------------------------------------------------------------------------------------------------------ data edges
 @pytest.mark.parametrize("c", A.edge_cases(), ids=A.Case.id)
 def test_data_edges(c):
-    # two fast shapes (fwd_fast<4,1> + bwd_fast<1>; fwd_rep<4,1,.,5> / fwd_fast<4,1> + bwd_fast<5>) and one generic shape
+    # two fast shapes (fwd_fast<4,2048> + bwd_fast<1>; fwd_rep<4,2048> / fwd_fast<4,2048> + bwd_fast<5>) and one generic shape
     # (attn_pool_fwd_kernel + attn_pool_bwd_kernel<5>), see attn_ref.EDGE_SHAPES
     d, ref, outs = run_case(c)
     if c.kind == "dp_zero":
@@ -325,7 +326,7 @@ def _without_middle(case):
 
 @pytest.mark.parametrize("c", A.nb0_cases(), ids=A.Case.id)
 def test_nb_zero_in_the_middle_memory(c):
-    # fwd_fast + bwd_fast<1>; fwd_rep<4,1,.,5> + bwd_fast<5> (five queries share one workgroup's LDS); fwd_rep_d1024 +
+    # fwd_fast + bwd_fast<1>; fwd_rep<4,2048> + bwd_fast<5> (five queries share one workgroup's LDS); fwd_rep_d1024 +
     # bwd_fast<5,1024>; the generic kernels
     case = A.make_case(c)
     d, d2 = to_dev(case), to_dev(_without_middle(case))

@@ -49,14 +49,14 @@ def _same(x, y, what):
 
 # ------------------------------------------------------------------------------------------------------ the ops
 # (name, B, rep, R, H, D, vqa_attn_set_fast or None).  Forward route / backward route of each:
-#   rep-fwd-*     the per-memory forward attn_pool_fwd_rep_kernel<H / 256, D / 2048, ., 5>; R 3: fewer rows than its prefetch
+#   rep-fwd-*     the per-memory forward attn_pool_fwd_form_kernel<FwdRep, H / 256, D, .>; R 3: fewer rows than its prefetch
 #                 depth of 4, R 9 and R 40: the edges of the 8-row wave stride and the 6-row pooling batch.  Backward: generic
 #                 attn_pool_bwd_kernel<5> (H 256; D 4096)
-#   d1024         attn_pool_fwd_rep_d1024_kernel<4, ., 5> / attn_pool_bwd_fast_kernel<5, ., 1024>
-#   fast-bwd      attn_pool_bwd_fast_kernel<5, ., 2048> (forward: attn_pool_fwd_rep_kernel<4, 1, ., 5>)
+#   d1024         attn_pool_fwd_form_kernel<FwdRepD1024, 4, 1024, .> / attn_pool_bwd_fast_kernel<5, ., 1024>
+#   fast-bwd      attn_pool_bwd_fast_kernel<5, ., 2048> (forward: attn_pool_fwd_form_kernel<FwdRep, 4, 2048, .>)
 #   generic       attn_pool_fwd_kernel with rep / attn_pool_bwd_kernel<5> (rep 2, 5) and <8> (rep 8)
 #   generic-big   the generic pair at a models' shape under vqa_attn_set_fast(0)
-#   per-query     attn_pool_fwd_fast_kernel with rep > 1 under vqa_attn_set_fast(2) (rep 3) and (3) (rep 5)
+#   per-query     attn_pool_fwd_form_kernel<FwdFast, ...> with rep > 1 under vqa_attn_set_fast(2) (rep 3) and (3) (rep 5)
 ATT_CASES = [("rep-fwd-h256-d2048-R%d" % R, 3, 5, R, 256, 2048, None) for R in (36, 3, 9, 40)] + \
             [("rep-fwd-h1024-d4096-R%d" % R, 2, 5, R, 1024, 4096, None) for R in (36, 3, 9, 40)] + \
             [("d1024", 2, 5, 36, 1024, 1024, None), ("fast-bwd-R36", 2, 5, 36, 1024, 2048, None),
@@ -129,7 +129,7 @@ def test_refusals_of_the_seeded_rep_calls():
 # ------------------------------------------------------------------------------------------------------ the engines
 TOY = dict(B=3, n=5, R=6, D=16, H=8, L=4, W=12, Vq=20, n_ws=7, A=12)
 MID = dict(B=16, n=5, R=36, D=256, H=128, L=10, W=300, Vq=200, n_ws=50, A=400)
-# H 1024, R 36: the per-memory rep kernels inside a step -- D 2048 (cfg-5: attn_pool_fwd_rep_kernel<4, 1, ., 5> and
+# H 1024, R 36: the per-memory rep kernels inside a step -- D 2048 (cfg-5: attn_pool_fwd_form_kernel<FwdRep, 4, 2048, .> and
 # attn_pool_bwd_fast_kernel<5, ., 2048>) and the 1024-wide adapted memory (the d1024 pair)
 WIDE = dict(B=2, n=5, R=36, D=2048, H=1024, L=4, W=12, Vq=20, n_ws=7, A=12)
 WIDE_ADAPT = dict(WIDE, D=64)

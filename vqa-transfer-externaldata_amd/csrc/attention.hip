@@ -134,13 +134,13 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
     }
 }
 
-// The same for the shapes of the models (H a multiple of 256 up to 1024, D a multiple of 2048 up to 4096, R <= 40),
+// The same for the shapes of the models (H a multiple of 256 up to 1024, D a multiple of 2048 up to 4096 or 1024, R <= 40),
 // restructured around loads in flight.  The generic kernel above streams 480 KB per sample in three dependent phases
 // whose workgroups run in lockstep (all 512 are resident at once), so the memory system idles at every phase
 // boundary: 251.9 MB in 64.5 us = 3.9 TB/s at bs 512.  Here (a) each thread fetches its first PF rows of V before
 // anything else -- they do not depend on the scores and land during the score phase, (b) a wave issues the loads of
-// all rows of a score batch (3 + 2 of its <= 5 rows) before the first use, so the batch costs one memory latency
-// instead of one per row, (c) the pooling loop keeps 7 rows per thread in flight.
+// all rows of a score batch (3 + 2 of its <= 5 rows, one query per workgroup) before the first use, so the batch costs
+// one memory latency instead of one per row, (c) the pooling loop keeps 7 rows per thread in flight.
 // (hipcc note: the loads are written on a native 4-float vector type and are UNCONDITIONAL -- row indices are clamped
 // and rows past R get weight zero.  With HIP's float4 struct a guarded `in ? load : zero` becomes four scalar loads
 // in four branches, each waited for before the next is issued.)
@@ -150,182 +150,90 @@ __global__ __launch_bounds__(FWD_THREADS) void attn_pool_fwd_kernel(
 #ifndef VQA_ATTN_POOL_BATCH
 #define VQA_ATTN_POOL_BATCH 7
 #endif
-constexpr int FAST_PF = VQA_ATTN_PF, FAST_POOL_BATCH = VQA_ATTN_POOL_BATCH;
 
-// scores of CNT rows (row0, row0 + 8, ...) of one wave: every load of the batch is issued before the first use
-// (KEEP_SEEDED: sq.word0 = the word index of this query's mask)
-template <int H4L, int CNT, int KP, typename... KS>
+// The forms of the fast forward: one kernel (attn_pool_fwd_form_kernel), one row of constants per dispatch route.
+//   REP     queries per workgroup.  1: one workgroup per QUERY (any rep: m = q / rep).  5: one workgroup per MEMORY (the
+//           pre-training model: 5 key boxes per image), so v and V are read once per image instead of once per query (the
+//           per-query form re-reads them REP times through L2: 1.2 GB of requests for 0.32 GB of distinct bytes at 512
+//           images) and only the keep masks are per query
+//   PF      rows of V a thread fetches before anything else; BATCH: rows per thread in flight in the pooling loop
+//   S0..S2  rows per score batch of a wave (its <= 5 rows wave + 8 i, R <= 40)
+//   BLOCKS  workgroups per CU the registers are allotted for (__launch_bounds__)
+struct FwdFast     { static constexpr int REP = 1, PF = VQA_ATTN_PF, BATCH = VQA_ATTN_POOL_BATCH, S0 = 3, S1 = 2, S2 = 0, BLOCKS = 4; };
+struct FwdRep      { static constexpr int REP = 5, PF = 4, BATCH = 6, S0 = 2, S1 = 2, S2 = 1, BLOCKS = 2; };
+struct FwdRepD1024 { static constexpr int REP = 5, PF = 6, BATCH = 6, S0 = 2, S1 = 2, S2 = 1, BLOCKS = 2; };
+
+// What a thread holds of one row of V and of pooled: N pieces, raw between the load and the use (half the registers for a
+// bf16 memory), widened where they are used; lane -> element mapping and summation orders do not depend on VT.
+// D a multiple of 2048: D / 2048 pieces of four elements at threadIdx.x + c * 512 ...
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+template <typename VT, int D> struct VCols {
+    static_assert(D % 2048 == 0, "a 1024-wide memory is f32");
+    static constexpr int N = D / 2048;
+    typedef typename VMem<VT>::Raw Raw;
+    typedef f32x4v Acc;
+    static __device__ __forceinline__ Raw load(const VT* __restrict__ Vb, int r, int c) {
+        return VMem<VT>::load(Vb, (int64_t)r * (D / 4) + threadIdx.x + c * FWD_THREADS);
+    }
+    static __device__ __forceinline__ Acc widen(Raw x) { return VMem<VT>::widen(x); }
+    static __device__ __forceinline__ void store(float* __restrict__ row, int c, Acc a) {
+        reinterpret_cast<f32x4v*>(row)[threadIdx.x + c * FWD_THREADS] = a;
+    }
+};
+// ... D == 1024 (v_adapt of the pre-training model, an f32 activation): a row is 512 float2 columns, one per thread, so
+// every thread streams V with 8-byte loads (a wave still covers 512 contiguous bytes per row) and sums its rows in order
+// -- the generic kernel's summation order, no thread idle and no partial sums to combine
+template <> struct VCols<float, 1024> {
+    static constexpr int N = 1;
+    typedef f32x2v Raw;
+    typedef f32x2v Acc;
+    static __device__ __forceinline__ Raw load(const float* __restrict__ Vb, int r, int) {
+        return reinterpret_cast<const f32x2v*>(Vb)[(int64_t)r * FWD_THREADS + threadIdx.x];
+    }
+    static __device__ __forceinline__ Acc widen(Raw x) { return x; }
+    static __device__ __forceinline__ void store(float* __restrict__ row, int, Acc a) {
+        reinterpret_cast<f32x2v*>(row)[threadIdx.x] = a;
+    }
+};
+
+// scores of CNT rows (row0, row0 + 8, ...) of one wave against the REP queries of its workgroup, from one load of each
+// row: every load of the batch is issued before the first use.  The mask word of query q0 + j is loaded from mb4 (the base
+// of query q0; KEEP_BYTES) or computed (KEEP_SEEDED: sq.word0 = the word index of query q0's mask) -- at REP == 1
+// together with the rows, before qw is awaited, so the batch costs one memory latency; at REP > 1 query by query.
+template <int H4L, int CNT, int KP, int REP>
 __device__ __forceinline__ void attn_score_rows(const f32x4v* __restrict__ vb4, const unsigned* __restrict__ mb4,
                                                 const f32x4v* qw4, float* s, int R, int row0, float inv_keep, float bias0,
-                                                int lane, bool sync_first, KS... sq) {
+                                                int lane, bool sync_first, KeepSeed sq) {
     constexpr int H4 = H4L * 64;
     f32x4v x[CNT][H4L];
     unsigned m[CNT][H4L];
+    int rr[CNT];
+    auto mask_word = [&](int64_t at) -> unsigned {      // word `at` of the mask of query q0
+        if constexpr (KP == KEEP_SEEDED) {
+            return keep_word4(sq.key, sq.word0 + (uint64_t)at, sq.thr);
+        } else {
+            return mb4[at];
+        }
+    };
 #pragma unroll
     for (int i = 0; i < CNT; ++i) {
         const int r = min(row0 + 8 * i, R - 1);
+        rr[i] = r;
 #pragma unroll
         for (int k = 0; k < H4L; ++k) {
-            x[i][k] = vb4[(int64_t)r * H4 + lane + 64 * k];
-            if (KP == KEEP_BYTES) m[i][k] = mb4[(int64_t)r * H4 + lane + 64 * k];
-            if constexpr (KP == KEEP_SEEDED) {
-                const KeepSeed sd = keep_seed_of(sq...);
-                m[i][k] = keep_word4(sd.key, sd.word0 + (uint64_t)r * H4 + lane + 64 * k, sd.thr);
-            }
+            const int64_t at = (int64_t)r * H4 + lane + 64 * k;
+            x[i][k] = vb4[at];
+            if constexpr (REP == 1 && KP != KEEP_NONE) m[i][k] = mask_word(at);
         }
-    }
-    if (sync_first) __syncthreads();                 // qw is complete
-#pragma unroll
-    for (int i = 0; i < CNT; ++i) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < H4L; ++k) {
-            const f32x4v q = qw4[lane + 64 * k];
-            if (KP != KEEP_NONE) {
-                const unsigned mm = m[i][k];
-                acc += (x[i][k].x * q.x * (float)(mm & 0xFFu) + x[i][k].y * q.y * (float)((mm >> 8) & 0xFFu) +
-                        x[i][k].z * q.z * (float)((mm >> 16) & 0xFFu) + x[i][k].w * q.w * (float)(mm >> 24)) * inv_keep;
-            } else {
-                acc += x[i][k].x * q.x + x[i][k].y * q.y + x[i][k].z * q.z + x[i][k].w * q.w;
-            }
-        }
-        acc = wave_sum(acc);
-        if (lane == 0 && row0 + 8 * i < R) s[row0 + 8 * i] = acc + bias0;
-    }
-}
-
-template <int H4L, int D4T, int KP, typename VT = float, typename... KS>
-__global__ __launch_bounds__(FWD_THREADS, 4) void attn_pool_fwd_fast_kernel(
-    const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
-    const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
-    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
-    int rep, KS... ks) {
-    constexpr int H = H4L * 256, D = D4T * 2048, D4 = D / 4;
-    extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[H] | s[R]
-    float* qw = lds;
-    float* s = lds + H;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // b = query index
-    const int mem = b / rep;
-    const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
-    const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + (int64_t)b * R * H) : nullptr;
-    const VT* Vb = V + (int64_t)mem * R * D;
-
-    // (a) first rows of this thread's V columns
-    typename VMem<VT>::Raw xv[FAST_PF][D4T];
-#pragma unroll
-    for (int j = 0; j < FAST_PF; ++j)
-#pragma unroll
-        for (int c = 0; c < D4T; ++c) xv[j][c] = VMem<VT>::load(Vb, (int64_t)min(j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
-
-    for (int h = threadIdx.x; h < H; h += FWD_THREADS) qw[h] = qv[(int64_t)b * H + h] * w[h];
-    const float bias0 = bias[0];
-
-    // (b) scores: wave `wave` owns rows wave + 8 i, i < 5 (R <= 40)
-    const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
-    if constexpr (KP == KEEP_SEEDED) {
-        KeepSeed sq = keep_seed_of(ks...);
-        sq.word0 += (uint64_t)b * R * (H / 4);
-        attn_score_rows<H4L, 3, KP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
-        attn_score_rows<H4L, 2, KP>(vb4, mb4, qw4, s, R, wave + 24, inv_keep, bias0, lane, false, sq);
-    } else {
-        attn_score_rows<H4L, 3, KP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
-        attn_score_rows<H4L, 2, KP>(vb4, mb4, qw4, s, R, wave + 24, inv_keep, bias0, lane, false);
-    }
-    __syncthreads();
-
-    if (wave == 0) {
-        const int n_valid = nb[mem];
-        float mx = -INFINITY;
-        for (int r = lane; r < R; r += 64) {
-            const float x = (r < n_valid) ? s[r] : -INFINITY;
-            s[r] = x;
-            mx = fmaxf(mx, x);
-        }
-        mx = wave_max(mx);
-        float sum = 0.f;
-        for (int r = lane; r < R; r += 64) {
-            const float e = expf(s[r] - mx);  // all -inf (nb == 0) -> NaN, like TF
-            s[r] = e;
-            sum += e;
-        }
-        sum = wave_sum(sum);
-        for (int r = lane; r < R; r += 64) {
-            const float a = s[r] / sum;
-            s[r] = a;
-            att_out[(int64_t)b * R + r] = a;
-        }
-    }
-    __syncthreads();
-
-    // (c) pooling, rows in order
-    f32x4v acc[D4T];
-#pragma unroll
-    for (int c = 0; c < D4T; ++c) acc[c] = (f32x4v)(0.f);
-#pragma unroll
-    for (int j = 0; j < FAST_PF; ++j) {
-        const float a = (j < R) ? s[min(j, R - 1)] : 0.f;
-#pragma unroll
-        for (int c = 0; c < D4T; ++c) acc[c] += a * VMem<VT>::widen(xv[j][c]);
-    }
-    for (int r0 = FAST_PF; r0 < R; r0 += FAST_POOL_BATCH) {
-        typename VMem<VT>::Raw y[FAST_POOL_BATCH][D4T];
-#pragma unroll
-        for (int j = 0; j < FAST_POOL_BATCH; ++j)
-#pragma unroll
-            for (int c = 0; c < D4T; ++c)
-                y[j][c] = VMem<VT>::load(Vb, (int64_t)min(r0 + j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
-#pragma unroll
-        for (int j = 0; j < FAST_POOL_BATCH; ++j) {
-            const float a = (r0 + j < R) ? s[min(r0 + j, R - 1)] : 0.f;
-#pragma unroll
-            for (int c = 0; c < D4T; ++c) acc[c] += a * VMem<VT>::widen(y[j][c]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < D4T; ++c)
-        reinterpret_cast<f32x4v*>(pooled + (int64_t)b * D)[threadIdx.x + c * FWD_THREADS] = acc[c];
-}
-
-// `REP` queries per memory (the pre-training model: 5 key boxes per image), one workgroup per MEMORY: v and V are read
-// once per image instead of once per query (the per-query form re-reads them REP times through L2: 1.2 GB of requests
-// for 0.32 GB of distinct bytes at 512 images), only the keep masks are per query.  Same three phases as above; a
-// wave scores its rows for all REP queries from one load of the row, waves 0..REP-1 run the REP softmaxes, and the
-// pooling loop keeps REP accumulators per thread over one stream of V.
-// Keep policy as in the one-query forms: KEEP_BYTES loads the mask word of query q0 + j from mb4 (the base of query q0),
-// KEEP_SEEDED computes it (sq.word0 = the word index of query q0's mask).
-// VT as in the one-query kernels: the prefetched rows and the pooling batches stay raw in registers (half the registers
-// for a bf16 memory) and are widened where they are used; lane -> element mapping and summation orders do not depend on VT.
-constexpr int REP_PF = 4, REP_POOL_BATCH = 6;
-template <int H4L, int CNT, int KP, int REP, typename... KS>
-__device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ vb4, const unsigned* __restrict__ mb4,
-                                                    const f32x4v* qw4, float* s, int R, int row0, float inv_keep,
-                                                    float bias0, int lane, bool sync_first, KS... sq) {
-    constexpr int H4 = H4L * 64;
-    f32x4v x[CNT][H4L];
-    int rr[CNT];
-#pragma unroll
-    for (int i = 0; i < CNT; ++i) {
-        rr[i] = min(row0 + 8 * i, R - 1);
-#pragma unroll
-        for (int k = 0; k < H4L; ++k) x[i][k] = vb4[(int64_t)rr[i] * H4 + lane + 64 * k];
     }
     if (sync_first) __syncthreads();                 // qw is complete
 #pragma unroll
     for (int j = 0; j < REP; ++j) {
-        unsigned m[CNT][H4L];
-        if (KP == KEEP_BYTES) {
+        if constexpr (REP > 1 && KP != KEEP_NONE) {
 #pragma unroll
             for (int i = 0; i < CNT; ++i)
 #pragma unroll
-                for (int k = 0; k < H4L; ++k) m[i][k] = mb4[((int64_t)j * R + rr[i]) * H4 + lane + 64 * k];
-        }
-        if constexpr (KP == KEEP_SEEDED) {
-            const KeepSeed sd = keep_seed_of(sq...);
-#pragma unroll
-            for (int i = 0; i < CNT; ++i)
-#pragma unroll
-                for (int k = 0; k < H4L; ++k)
-                    m[i][k] = keep_word4(sd.key, sd.word0 + ((uint64_t)j * R + rr[i]) * H4 + lane + 64 * k, sd.thr);
+                for (int k = 0; k < H4L; ++k) m[i][k] = mask_word(((int64_t)j * R + rr[i]) * H4 + lane + 64 * k);
         }
 #pragma unroll
         for (int i = 0; i < CNT; ++i) {
@@ -347,44 +255,47 @@ __device__ __forceinline__ void attn_score_rows_rep(const f32x4v* __restrict__ v
     }
 }
 
-template <int H4L, int D4T, int KP, int REP, typename VT, typename... KS>
-__global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
+// Workgroup blockIdx.x takes the queries q0 .. q0 + REP - 1, q0 = blockIdx.x * REP, of the memory q0 / rep (REP == 1 with
+// any rep, or REP == rep).  A wave scores its rows for all REP queries, waves 0..REP-1 run the REP softmaxes, and the
+// pooling loop keeps REP accumulators per thread over one stream of V.
+template <typename F, int H4L, int D, int KP, typename VT, typename... KS>
+__global__ __launch_bounds__(FWD_THREADS, F::BLOCKS) void attn_pool_fwd_form_kernel(
     const float* __restrict__ v, const float* __restrict__ qv, const VT* __restrict__ V,
     const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
     const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
-    KS... ks) {
+    int rep, KS... ks) {
+    typedef VCols<VT, D> COL;
+    constexpr int REP = F::REP, PF = F::PF, BATCH = F::BATCH, H = H4L * 256, N = COL::N;
     static_assert(REP <= FWD_THREADS / 64, "one softmax wave per query");
-    constexpr int H = H4L * 256, D = D4T * 2048, D4 = D / 4;
+    static_assert(F::S0 + F::S1 + F::S2 == 5, "a wave owns rows wave + 8 i, i < 5 (R <= 40)");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[REP][H] | s[REP][40]
     float* qw = lds;
     float* s = lds + REP * H;
-    const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t q0 = (int64_t)mem * REP;                         // first query of this memory
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * REP, mem = b / rep;
+    const int64_t q0 = b;                                          // first query of this workgroup
     const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
     const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
     const VT* Vb = V + (int64_t)mem * R * D;
 
-    typename VMem<VT>::Raw xv[REP_PF][D4T];
+    // (a) first rows of this thread's V columns
+    typename COL::Raw xv[PF][N];
 #pragma unroll
-    for (int j = 0; j < REP_PF; ++j)
+    for (int r = 0; r < PF; ++r)
 #pragma unroll
-        for (int c = 0; c < D4T; ++c) xv[j][c] = VMem<VT>::load(Vb, (int64_t)min(j, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
+        for (int c = 0; c < N; ++c) xv[r][c] = COL::load(Vb, min(r, R - 1), c);
 
     for (int i = threadIdx.x; i < REP * H; i += FWD_THREADS) qw[i] = qv[q0 * H + i] * w[i % H];
     const float bias0 = bias[0];
 
+    // (b) scores
     const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
-    if constexpr (KP == KEEP_SEEDED) {
-        KeepSeed sq = keep_seed_of(ks...);
-        sq.word0 += (uint64_t)q0 * R * (H / 4);
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false, sq);
-        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false, sq);
-    } else {
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
-        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
-    }
+    KeepSeed sq = keep_seed_of(ks...);                              // zeros unless KEEP_SEEDED
+    sq.word0 += (uint64_t)q0 * R * (H / 4);
+    attn_score_rows<H4L, F::S0, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
+    attn_score_rows<H4L, F::S1, KP, REP>(vb4, mb4, qw4, s, R, wave + 8 * F::S0, inv_keep, bias0, lane, false, sq);
+    if constexpr (F::S2 > 0)
+        attn_score_rows<H4L, F::S2, KP, REP>(vb4, mb4, qw4, s, R, wave + 8 * (F::S0 + F::S1), inv_keep, bias0, lane, false, sq);
     __syncthreads();
 
     if (wave < REP) {
@@ -402,124 +313,41 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_kernel(
     }
     __syncthreads();
 
-    f32x4v acc[REP][D4T];
+    // (c) pooling, rows in order
+    typename COL::Acc acc[REP][N];
 #pragma unroll
     for (int j = 0; j < REP; ++j)
 #pragma unroll
-        for (int c = 0; c < D4T; ++c) acc[j][c] = (f32x4v)(0.f);
+        for (int c = 0; c < N; ++c) acc[j][c] = (typename COL::Acc)(0.f);
 #pragma unroll
-    for (int r = 0; r < REP_PF; ++r) {
+    for (int r = 0; r < PF; ++r) {
 #pragma unroll
         for (int j = 0; j < REP; ++j) {
             const float a = (r < R) ? s[j * 40 + min(r, R - 1)] : 0.f;
 #pragma unroll
-            for (int c = 0; c < D4T; ++c) acc[j][c] += a * VMem<VT>::widen(xv[r][c]);
+            for (int c = 0; c < N; ++c) acc[j][c] += a * COL::widen(xv[r][c]);
         }
     }
-    for (int r0 = REP_PF; r0 < R; r0 += REP_POOL_BATCH) {
-        typename VMem<VT>::Raw y[REP_POOL_BATCH][D4T];
+    for (int r0 = PF; r0 < R; r0 += BATCH) {
+        typename COL::Raw y[BATCH][N];
 #pragma unroll
-        for (int i = 0; i < REP_POOL_BATCH; ++i)
+        for (int i = 0; i < BATCH; ++i)
 #pragma unroll
-            for (int c = 0; c < D4T; ++c)
-                y[i][c] = VMem<VT>::load(Vb, (int64_t)min(r0 + i, R - 1) * D4 + threadIdx.x + c * FWD_THREADS);
+            for (int c = 0; c < N; ++c) y[i][c] = COL::load(Vb, min(r0 + i, R - 1), c);
 #pragma unroll
-        for (int i = 0; i < REP_POOL_BATCH; ++i) {
+        for (int i = 0; i < BATCH; ++i) {
 #pragma unroll
             for (int j = 0; j < REP; ++j) {
                 const float a = (r0 + i < R) ? s[j * 40 + min(r0 + i, R - 1)] : 0.f;
 #pragma unroll
-                for (int c = 0; c < D4T; ++c) acc[j][c] += a * VMem<VT>::widen(y[i][c]);
+                for (int c = 0; c < N; ++c) acc[j][c] += a * COL::widen(y[i][c]);
             }
         }
     }
 #pragma unroll
     for (int j = 0; j < REP; ++j)
 #pragma unroll
-        for (int c = 0; c < D4T; ++c)
-            reinterpret_cast<f32x4v*>(pooled + (q0 + j) * D)[threadIdx.x + c * FWD_THREADS] = acc[j][c];
-}
-
-// The per-memory kernel for a 1024-wide memory (the pre-training model with the adapted memory pools v_adapt [R,1024], not
-// the 2048-wide features): a row is 512 float2 columns, one per thread, so every thread streams V with 8-byte loads (a
-// wave still covers 512 contiguous bytes per row) and sums its rows in order -- the generic kernel's summation order,
-// no thread idle and no partial sums to combine.  Scores and softmax as above.
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-constexpr int REP_N_PF = 6, REP_N_POOL_BATCH = 6;
-template <int H4L, int KP, int REP, typename... KS>
-__global__ __launch_bounds__(FWD_THREADS, 2) void attn_pool_fwd_rep_d1024_kernel(
-    const float* __restrict__ v, const float* __restrict__ qv, const float* __restrict__ V,
-    const int32_t* __restrict__ nb, const float* __restrict__ w, const float* __restrict__ bias,
-    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ att_out, float* __restrict__ pooled, int R,
-    KS... ks) {
-    static_assert(REP <= FWD_THREADS / 64, "one softmax wave per query");
-    constexpr int H = H4L * 256, D = 1024, D2 = D / 2;
-    static_assert(D2 == FWD_THREADS, "one float2 column per thread");
-    extern __shared__ __attribute__((aligned(16))) float lds[];  // qw[REP][H] | s[REP][40]
-    float* qw = lds;
-    float* s = lds + REP * H;
-    const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t q0 = (int64_t)mem * REP;
-    const f32x4v* vb4 = reinterpret_cast<const f32x4v*>(v + (int64_t)mem * R * H);
-    const unsigned* mb4 = KP == KEEP_BYTES ? reinterpret_cast<const unsigned*>(keepmask + q0 * R * H) : nullptr;
-    const f32x2v* Vb2 = reinterpret_cast<const f32x2v*>(V + (int64_t)mem * R * D);
-
-    f32x2v xv[REP_N_PF];
-#pragma unroll
-    for (int j = 0; j < REP_N_PF; ++j) xv[j] = Vb2[(int64_t)min(j, R - 1) * D2 + threadIdx.x];
-
-    for (int i = threadIdx.x; i < REP * H; i += FWD_THREADS) qw[i] = qv[q0 * H + i] * w[i % H];
-    const float bias0 = bias[0];
-
-    const f32x4v* qw4 = reinterpret_cast<const f32x4v*>(qw);
-    if constexpr (KP == KEEP_SEEDED) {
-        KeepSeed sq = keep_seed_of(ks...);
-        sq.word0 += (uint64_t)q0 * R * (H / 4);
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true, sq);
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false, sq);
-        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false, sq);
-    } else {
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave, inv_keep, bias0, lane, true);
-        attn_score_rows_rep<H4L, 2, KP, REP>(vb4, mb4, qw4, s, R, wave + 16, inv_keep, bias0, lane, false);
-        attn_score_rows_rep<H4L, 1, KP, REP>(vb4, mb4, qw4, s, R, wave + 32, inv_keep, bias0, lane, false);
-    }
-    __syncthreads();
-
-    if (wave < REP) {
-        float* sj = s + wave * 40;
-        const int n_valid = nb[mem];
-        const float x = (lane < R && lane < n_valid) ? sj[min(lane, R - 1)] : -INFINITY;      // R <= 40 < 64: one lane per row
-        const float mx = wave_max(x);
-        const float e = (lane < R) ? expf(x - mx) : 0.f;  // all -inf (nb == 0) -> NaN, like TF
-        const float sum = wave_sum(e);
-        if (lane < R) {
-            const float a = e / sum;
-            sj[lane] = a;
-            att_out[(q0 + wave) * R + lane] = a;
-        }
-    }
-    __syncthreads();
-
-    f32x2v acc[REP];
-#pragma unroll
-    for (int j = 0; j < REP; ++j) acc[j] = (f32x2v)(0.f);
-#pragma unroll
-    for (int r = 0; r < REP_N_PF; ++r) {
-#pragma unroll
-        for (int j = 0; j < REP; ++j) acc[j] += ((r < R) ? s[j * 40 + min(r, R - 1)] : 0.f) * xv[r];
-    }
-    for (int r0 = REP_N_PF; r0 < R; r0 += REP_N_POOL_BATCH) {
-        f32x2v y[REP_N_POOL_BATCH];
-#pragma unroll
-        for (int i = 0; i < REP_N_POOL_BATCH; ++i) y[i] = Vb2[(int64_t)min(r0 + i, R - 1) * D2 + threadIdx.x];
-#pragma unroll
-        for (int i = 0; i < REP_N_POOL_BATCH; ++i) {
-#pragma unroll
-            for (int j = 0; j < REP; ++j) acc[j] += ((r0 + i < R) ? s[j * 40 + min(r0 + i, R - 1)] : 0.f) * y[i];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < REP; ++j) reinterpret_cast<f32x2v*>(pooled + (q0 + j) * D)[threadIdx.x] = acc[j];
+        for (int c = 0; c < N; ++c) COL::store(pooled + (q0 + j) * D, c, acc[j][c]);
 }
 
 // Backward.  One workgroup per MEMORY walks its `rep` queries, so dv (the gradient of the shared
@@ -653,18 +481,18 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_kernel(
 // the dv phase keeps four rows (+ their REP mask words) per thread in flight.  Same per-lane summation order.
 // DD = 1024 (REP 5 only is dispatched): the adapted memory of the pre-training model; D4 is then half a workgroup, so
 // half of the threads stage dpooled and a wave's V row is 4 float4 per lane instead of 8.
-template <int REP, int KP, int DD = 2048, typename VT = float, typename... KS>
-__global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
-    const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
-    const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
-    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
-    float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, KS... ks) {
-    constexpr int D = DD, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64, RB = 4;
+// Its phases 1-3, the score gradient of the REP queries of memory blockIdx.x: dpooled staged in LDS, datt[j][r] =
+// <dpooled[q0 + j], V[mem, r]> with two V rows per wave in flight, the softmax backward ds = att * (datt - sum(att * datt))
+// in one wave per query.  lds: dp[REP][DD] | ds[REP][40].  ds of query q0 + j goes to g_out + j * g_ld (the ds rows in
+// LDS themselves, or global memory), its sum to part_db; the caller synchronises before it reads them.
+template <int REP, int DD, typename VT>
+__device__ __forceinline__ void attn_bwd_ds_phases(const float* __restrict__ dpooled, const VT* __restrict__ V,
+                                                   const float* __restrict__ att, float* lds, float* g_out, int g_ld,
+                                                   float* __restrict__ part_db, int R) {
+    constexpr int D = DD, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64;
     static_assert(REP <= NW, "one softmax wave per query");
     static_assert(D4 <= BWD_THREADS && D4 % 64 == 0, "dpooled is staged with one float4 per thread");
-    extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[REP][D] | ds[REP][40] | comb[REP][H]
     float* ds = lds + REP * D;
-    float* comb = ds + REP * 40;
     const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t q0 = (int64_t)mem * REP;
     f32x4v* dp4 = reinterpret_cast<f32x4v*>(lds);
@@ -677,7 +505,6 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
         for (int j = 0; j < REP; ++j) dp4[j * D4 + threadIdx.x] = t[j];
     }
     __syncthreads();
-    // datt[j][r] = <dpooled[q0 + j], V[mem, r]>
     const VT* Vb = V + (int64_t)mem * R * D;
     for (int r0 = wave; r0 < R; r0 += 2 * NW) {
         const int rb = min(r0 + NW, R - 1);
@@ -707,17 +534,32 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
         }
     }
     __syncthreads();
-    // softmax backward: ds = att * (datt - sum(att*datt)); R <= 40 < 64: one lane per region
+    // R <= 40 < 64: one lane per region
     if (wave < REP) {
         const int64_t q = q0 + wave;
         const float a = lane < R ? att[q * R + lane] : 0.f;
         const float d = lane < R ? ds[wave * 40 + lane] : 0.f;
         const float dot = wave_sum(a * d);
         const float g = a * (d - dot);
-        if (lane < R) ds[wave * 40 + lane] = g;
+        if (lane < R) g_out[wave * g_ld + lane] = g;
         const float tot = wave_sum(g);
         if (lane == 0) part_db[q] = tot;
     }
+}
+
+template <int REP, int KP, int DD = 2048, typename VT = float, typename... KS>
+__global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
+    const float* __restrict__ dpooled, const float* __restrict__ v, const float* __restrict__ qv,
+    const VT* __restrict__ V, const float* __restrict__ att, const float* __restrict__ w,
+    const uint8_t* __restrict__ keepmask, float inv_keep, float* __restrict__ dv, float* __restrict__ dqv,
+    float* __restrict__ part_dw, float* __restrict__ part_db, int R, int H, KS... ks) {
+    constexpr int D = DD, RB = 4;
+    extern __shared__ __attribute__((aligned(16))) float lds[];  // dp[REP][D] | ds[REP][40] | comb[REP][H]
+    float* ds = lds + REP * D;
+    float* comb = ds + REP * 40;
+    const int mem = blockIdx.x;
+    const int64_t q0 = (int64_t)mem * REP;
+    attn_bwd_ds_phases<REP, DD, VT>(dpooled, V, att, lds, ds, 40, part_db, R);
     __syncthreads();
 
     const int H4 = H / 4;
@@ -792,9 +634,8 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_fast_kernel(
     }
 }
 
-// Phases 1-3 of attn_pool_bwd_fast_kernel<1, ., 2048> on their own (vqa_attn_pool_bwd_ds): dpooled staged in LDS, datt
-// with two V rows per wave in flight, the softmax backward in one wave -- the same expressions in the same order, so ds
-// and part_db hold the bits of that kernel.  The score gradient ds [B,R] leaves the CU instead of dv [B,R,H]: dv is
+// Phases 1-3 of attn_pool_bwd_fast_kernel<1, ., 2048> on their own (vqa_attn_pool_bwd_ds): the same attn_bwd_ds_phases, so
+// ds and part_db hold the bits of that kernel.  The score gradient ds [B,R] leaves the CU instead of dv [B,R,H]: dv is
 // ds[b,r] x (keep/keep_prob * qv * w), which the LayerNorm backward of v_linear_v forms in registers
 // (layernorm.hip: ln_att_bwd_reg_kernel), so neither v nor the keep mask is read here.
 template <typename VT>
@@ -803,55 +644,8 @@ __global__ __launch_bounds__(BWD_THREADS) void attn_pool_bwd_ds_kernel(const flo
                                                                        const float* __restrict__ att,
                                                                        float* __restrict__ ds_out,
                                                                        float* __restrict__ part_db, int R) {
-    constexpr int D = 2048, D4 = D / 4, DL = D4 / 64, NW = BWD_THREADS / 64;
-    static_assert(D4 == BWD_THREADS, "dpooled is staged with one float4 per thread");
-    __shared__ __attribute__((aligned(16))) float lds[D + 40];  // dp[D] | ds[40]
-    float* ds = lds + D;
-    const int mem = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t q0 = (int64_t)mem;
-    f32x4v* dp4 = reinterpret_cast<f32x4v*>(lds);
-    {
-        const f32x4v* g4 = reinterpret_cast<const f32x4v*>(dpooled + q0 * D);
-        const f32x4v t = g4[threadIdx.x];
-        dp4[threadIdx.x] = t;
-    }
-    __syncthreads();
-    const VT* Vb = V + (int64_t)mem * R * D;
-    for (int r0 = wave; r0 < R; r0 += 2 * NW) {
-        const int rb = min(r0 + NW, R - 1);
-        const bool okb = r0 + NW < R;
-        typename VMem<VT>::Raw ra[DL], rbw[DL];
-#pragma unroll
-        for (int k = 0; k < DL; ++k) {
-            ra[k] = VMem<VT>::load(Vb, (int64_t)r0 * D4 + lane + 64 * k);
-            rbw[k] = VMem<VT>::load(Vb, (int64_t)rb * D4 + lane + 64 * k);
-        }
-        float a = 0.f, b = 0.f;
-#pragma unroll
-        for (int k = 0; k < DL; ++k) {
-            const f32x4v g = dp4[lane + 64 * k];
-            const f32x4v xa = VMem<VT>::widen(ra[k]), xb = VMem<VT>::widen(rbw[k]);
-            a += xa.x * g.x + xa.y * g.y + xa.z * g.z + xa.w * g.w;
-            b += xb.x * g.x + xb.y * g.y + xb.z * g.z + xb.w * g.w;
-        }
-        a = wave_sum(a);
-        b = wave_sum(b);
-        if (lane == 0) {
-            ds[r0] = a;
-            if (okb) ds[rb] = b;
-        }
-    }
-    __syncthreads();
-    // softmax backward: ds = att * (datt - sum(att*datt)); R <= 40 < 64: one lane per region
-    if (wave == 0) {
-        const float a = lane < R ? att[q0 * R + lane] : 0.f;
-        const float d = lane < R ? ds[lane] : 0.f;
-        const float dot = wave_sum(a * d);
-        const float g = a * (d - dot);
-        if (lane < R) ds_out[q0 * R + lane] = g;
-        const float tot = wave_sum(g);
-        if (lane == 0) part_db[q0] = tot;
-    }
+    __shared__ __attribute__((aligned(16))) float lds[2048 + 40];  // dp[D] | ds[40]
+    attn_bwd_ds_phases<1, 2048, VT>(dpooled, V, att, lds, ds_out + (int64_t)blockIdx.x * R, R, part_db, R);
 }
 
 int g_attn_fast = 1;   // tuning / A-B switch (vqa_attn_set_fast)
@@ -886,49 +680,37 @@ int attn_fwd_typed(const float* v, const float* qv, const VT* V, const int32_t* 
     // for rep 5 only; one query per memory at D 1024 (vlmap_answer_adapt's step) stays on the generic kernel
     const bool fast1024 = v_is_f32<VT>() && g_attn_fast && g_attn_fast != 3 && rep == 5 && R <= 40 && H == 1024 && D == 1024 &&
                           vqa_aligned16(qv) && vqa_aligned16(w);
-    // one workgroup per memory for the pre-training model's 5 queries per image
-    const size_t lds5 = (size_t)(5 * H + 5 * 40) * sizeof(float);
+    // the one fast kernel with the row `form` of the form table at <H / 256, D>, one workgroup per form.REP queries
+    auto launch_form = [&](auto form, auto h4l, auto d) {
+        typedef decltype(form) F;
+        keep_dispatch(keep, [&](auto kp, auto... ks) {
+            hipLaunchKernelGGL(
+                (attn_pool_fwd_form_kernel<F, decltype(h4l)::value, decltype(d)::value, decltype(kp)::value, VT, decltype(ks)...>),
+                dim3(B * rep / F::REP), dim3(FWD_THREADS), (size_t)F::REP * (H + 40) * sizeof(float), st, v, qv, V, nb, w, bias,
+                keepmask, ik, att, pooled, R, rep, ks...);
+        });
+    };
+    auto launch_form_shapes = [&](auto form) {
+        int_dispatch<2048, 4096>(D, [&](auto d) { int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) { launch_form(form, h4l, d); }); });
+    };
     if constexpr (v_is_f32<VT>()) {
         if (fast1024) {
-            keep_dispatch(keep, [&](auto kp, auto... ks) {
-                hipLaunchKernelGGL((attn_pool_fwd_rep_d1024_kernel<4, decltype(kp)::value, 5, decltype(ks)...>), dim3(B),
-                                   dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, ks...);
-            });
+            launch_form(FwdRepD1024{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 1024>{});
             VQA_CHECK_LAUNCH();
             return VQA_OK;
         }
     }
     if (fast && rep == 5 && g_attn_fast != 3) {
-        int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
-            int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
-                keep_dispatch(keep, [&](auto kp, auto... ks) {
-                    hipLaunchKernelGGL((attn_pool_fwd_rep_kernel<decltype(h4l)::value, decltype(d4t)::value, decltype(kp)::value,
-                                                                 5, VT, decltype(ks)...>),
-                                       dim3(B), dim3(FWD_THREADS), lds5, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R,
-                                       ks...);
-                });
-            });
-        });
-        VQA_CHECK_LAUNCH();
-        return VQA_OK;
-    }
-    const size_t lds = (size_t)(H + R) * sizeof(float);
-    if (fast)
-        int_dispatch<1, 2>(D / 2048, [&](auto d4t) {
-            int_dispatch<1, 2, 3, 4>(H / 256, [&](auto h4l) {
-                keep_dispatch(keep, [&](auto kp, auto... ks) {
-                    hipLaunchKernelGGL((attn_pool_fwd_fast_kernel<decltype(h4l)::value, decltype(d4t)::value, decltype(kp)::value,
-                                                                  VT, decltype(ks)...>),
-                                       dim3(B * rep), dim3(FWD_THREADS), lds, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled,
-                                       R, rep, ks...);
-                });
-            });
-        });
-    else
+        launch_form_shapes(FwdRep{});               // one workgroup per memory for the pre-training model's 5 queries per image
+    } else if (fast) {
+        launch_form_shapes(FwdFast{});
+    } else {
         keep_dispatch_generic(keep, [&](auto kp, auto... ks) {
             hipLaunchKernelGGL((attn_pool_fwd_kernel<VT, decltype(kp)::value, decltype(ks)...>), dim3(B * rep), dim3(FWD_THREADS),
-                               lds, st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, H, D, rep, ks...);
+                               (size_t)(H + R) * sizeof(float), st, v, qv, V, nb, w, bias, keepmask, ik, att, pooled, R, H, D, rep,
+                               ks...);
         });
+    }
     VQA_CHECK_LAUNCH();
     return VQA_OK;
 }
@@ -955,37 +737,26 @@ int attn_bwd_typed(const float* dpooled, const float* v, const float* qv, const 
     // one workgroup per memory: one query at D 2048; the pre-training model's 5 queries at D 2048 and at D 1024 (the
     // 1024-wide memory; one query per memory at D 1024 stays on the generic kernel)
     const bool fast_shape = g_attn_fast && H == 1024 && R <= 40 && vqa_aligned16(dpooled);
-    const size_t l = (size_t)(rep * D + rep * 40 + rep * H) * sizeof(float);
-    if (fast_shape && rep == 1 && D == 2048) {
+    auto launch_fast = [&](auto rept, auto dd) -> int {
         keep_dispatch(keep, [&](auto kp, auto... ks) {
-            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<1, decltype(kp)::value, 2048, VT, decltype(ks)...>), dim3(B),
-                               dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H,
-                               ks...);
+            hipLaunchKernelGGL(
+                (attn_pool_bwd_fast_kernel<decltype(rept)::value, decltype(kp)::value, decltype(dd)::value, VT, decltype(ks)...>),
+                dim3(B), dim3(BWD_THREADS), (size_t)(rep * D + rep * 40 + rep * H) * sizeof(float), st, dpooled, v, qv, V, att, w,
+                keepmask, ik, dv, dqv, part_dw, part_db, R, H, ks...);
         });
         VQA_CHECK_LAUNCH();
         return VQA_OK;
-    }
+    };
+    std::integral_constant<int, 1> one;
+    std::integral_constant<int, 5> five;
+    std::integral_constant<int, 1024> d1024;
+    std::integral_constant<int, 2048> d2048;
+    if (fast_shape && rep == 1 && D == 2048) return launch_fast(one, d2048);
     // several queries per memory.  (D 1024 is the adapted memory, an f32 activation: a bf16 memory of that width takes the
     // generic kernel, as its forward does)
-    if (fast_shape && rep == 5 && D == 2048) {
-        keep_dispatch(keep, [&](auto kp, auto... ks) {
-            hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, 2048, VT, decltype(ks)...>), dim3(B),
-                               dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R, H,
-                               ks...);
-        });
-        VQA_CHECK_LAUNCH();
-        return VQA_OK;
-    }
+    if (fast_shape && rep == 5 && D == 2048) return launch_fast(five, d2048);
     if constexpr (v_is_f32<VT>()) {
-        if (fast_shape && rep == 5 && D == 1024) {
-            keep_dispatch(keep, [&](auto kp, auto... ks) {
-                hipLaunchKernelGGL((attn_pool_bwd_fast_kernel<5, decltype(kp)::value, 1024, float, decltype(ks)...>), dim3(B),
-                                   dim3(BWD_THREADS), l, st, dpooled, v, qv, V, att, w, keepmask, ik, dv, dqv, part_dw, part_db, R,
-                                   H, ks...);
-            });
-            VQA_CHECK_LAUNCH();
-            return VQA_OK;
-        }
+        if (fast_shape && rep == 5 && D == 1024) return launch_fast(five, d1024);
     }
     if (rep > 1) {
         int_dispatch<5, 8>(rep <= 5 ? 5 : 8, [&](auto rt) {

@@ -17,9 +17,10 @@ int vqa_ln_relu_att_bwd_run(const float* ds, const float* qv, const float* w, co
                             int R, int H, int D, void* stream);
 
 // attention.hip.  V: float, or raw bf16 patterns (v_bf16).  rep queries per memory, 1..8, with any keep source (the mask
-// of query q = m * rep + j: rows q * R .. of the [B * rep, R, H] mask or stream); a bf16 memory: rep == 1 only,
-// VQA_ERR_UNSUPPORTED otherwise.  seeded_one_query: the contract of vqa_attn_pool_fwd_seeded / _bwd_seeded, which refuse a
-// seeded source with rep != 1 (VQA_ERR_UNSUPPORTED, where they always checked it)
+// of query q = m * rep + j: rows q * R .. of the [B * rep, R, H] mask or stream), for either memory type (the bf16
+// pre-training steps run rep 5 over a bf16 memory; the C ABI's bf16 entry points are one query per memory).
+// seeded_one_query: the contract of vqa_attn_pool_fwd_seeded / _bwd_seeded, which refuse a seeded source with rep != 1
+// (VQA_ERR_UNSUPPORTED, where they always checked it)
 int vqa_attn_fwd_run(const float* v, const float* qv, const void* V, bool v_bf16, const int32_t* nb, const float* w,
                      const float* bias, const KeepSrc& keep, float* att, float* pooled, int B, int rep, int R, int H, int D,
                      void* stream, bool seeded_one_query = false);

@@ -614,7 +614,8 @@ typedef struct {
                                      * backward_phases) honour the bit the same way.  ROUTED (forward, dW and dx):
                                      * pooled_linear_l, q_linear_l, joint_fc and classifier; in the "no composition" models
                                      * joint_v, joint_l, classifier_v and classifier_l; in the adapt model v_adapt (forward
-                                     * and dW: it has no dx).  NOT ROUTED: everything of both encoders (encode_L_blank,
+                                     * and dW: it has no dx).  NOT ROUTED (unless VQA_PT_FLAG_BF16_ENCODER, below, is set as
+                                     * well): everything of both encoders (encode_L_blank,
                                      * encode_L_enwiki) -- the packed K = W x-projection, the recurrence, the dx product of
                                      * the embedding backward and the three weight products of the BPTT (dwx, both dwh) --
                                      * for the same reason; wordset_ft (K = W) and spat_v_linear_v / spat_q_linear_v (K = 6),
@@ -644,6 +645,28 @@ typedef struct {
                                      * changes (image_ft is an input).  Valid only with VQA_FLAG_BF16_GEMM: without it the
                                      * workspace query, the tensor query, forward, backward and backward_phases (the _ex forms
                                      * included) of every family return VQA_ERR_ARG, and nothing is launched. */
+/* A bit of vqa_pretrain_dims_t.flags that vqa_dims_t.flags REFUSES (hence its own prefix, VQA_PT_FLAG_); it shares the
+ * field's bit space with the VQA_FLAG_ bits above and takes the next free one. */
+#define VQA_PT_FLAG_BF16_ENCODER 32 /* opt-in on top of VQA_FLAG_BF16_GEMM, pre-training steps only (vqa_pretrain_dims_t.flags,
+                                     * all four families): both sequence encoders (encode_L_blank, encode_L_enwiki) join the
+                                     * routed list.  The packed x-projection, the dx product of the embedding backward and
+                                     * the three weight products of the BPTT (dwx, both dwh) run the bf16 GEMM that the heads
+                                     * run, and the per-step recurrence (plain and live-prefix) runs its four fused step
+                                     * GEMMs with bf16 operands (csrc/gru_step_bf16.hip).  Rounding points: both operands
+                                     * of each of these products, round to nearest even, on their way into LDS -- h_{t-1},
+                                     * r * h_{t-1}, dc_pre and dr_pre | du_pre on the left, the weights on the right.
+                                     * Accumulation, the xp / dh_acc addend, the gate math, the state update, the t < len
+                                     * mask and the backward formulas stay f32, every tape stays f32 in HBM and the state is
+                                     * carried in f32: a finished row's hs[t+1] is hs[len] bit for bit.  Row W of dwx (the
+                                     * constant-1 input) then yields bias gradients summed from ROUNDED dxp.  With the flag
+                                     * set "gemm_ws" also covers the bf16 kernel's split k of the encoders' shapes; with it
+                                     * clear every layout and every bit of the step is what it was.  Per call: the form of
+                                     * the recurrence is an argument of the step's drivers, not the process-wide setting of
+                                     * the GRU-step configuration setter.  Valid only with VQA_FLAG_BF16_GEMM: without it the
+                                     * workspace query, the tensor query, forward, backward and backward_phases (the _ex
+                                     * forms included) of every family return VQA_ERR_ARG, and nothing is launched.  In
+                                     * vqa_dims_t.flags (the VQA step, whose recurrence is the weight-stationary launch) the
+                                     * bit is VQA_ERR_ARG. */
 
 /* One FC(+LN) layer: weights [in,out], biases [out], LayerNorm beta/gamma [out] (NULL if no LN). */
 typedef struct { float *w, *b, *beta, *gamma; } vqa_fc_t;

@@ -1,4 +1,6 @@
-"""Tile-config sweep for the fused GRU recurrence (vqa_gru_seq_fwd / _bwd) at B 512, H 1024, T 14; min of repeats."""
+"""Tile-config sweep for the fused GRU recurrence (vqa_gru_seq_fwd / _bwd) at B 512, H 1024, T 14; min of repeats.
+`python tools/gru_tune.py -1,64` (GRU_B / GRU_T: the shape) times the f32 defaults against GRU-step id 64, the bf16 form
+of the step GEMMs (csrc/gru_step_bf16.hip); VQA_HOT_GRU_BF16_TALL_ROWS=0 / 1000000 forces its 128x128 / 64x64 tile."""
 import ctypes as C
 import os
 import sys

@@ -10,7 +10,10 @@ same box and clocks.  `--precision bf16` builds the timed engine(s) with Pretrai
 the same way: both medians and their ratio.  `--ab_features` builds it twice with precision="bf16": X on the batch's
 features rounded to bf16 and widened to f32, Y with features="bf16" on the rounded features themselves (same parameters,
 bit-identical steps), alternated; medians of `steps`, `--repeats` times over, and Y counts as slower only when it is behind
-X by more than the spread of X's own medians.  Without options the output is the cfg-5 line as before."""
+X by more than the spread of X's own medians.  `--ab_encoder` is the same protocol for the bf16 sequence encoder: X =
+precision="bf16", Y = X + encoder="bf16" on the same parameters and batch; Y counts as FASTER only when it is ahead of X
+by more than that spread.  `--encoder bf16` (with `--precision bf16`) builds the timed engine(s) with it (a kernel trace
+of Y alone).  Without options the output is the cfg-5 line as before."""
 import argparse
 import os
 import sys
@@ -35,7 +38,9 @@ _ap.add_argument("--alternate", action="store_true")
 _ap.add_argument("--precision", default="f32", choices=list(PT.PRECISIONS))
 _ap.add_argument("--ab_precision", action="store_true")
 _ap.add_argument("--ab_features", action="store_true")
-_ap.add_argument("--repeats", type=int, default=5, help="--ab_features: how many medians of `steps` per engine")
+_ap.add_argument("--encoder", default="f32", choices=list(PT.ENCODER_FORMATS))
+_ap.add_argument("--ab_encoder", action="store_true")
+_ap.add_argument("--repeats", type=int, default=5, help="--ab_features / --ab_encoder: how many medians of `steps` per engine")
 ARGS = _ap.parse_args()
 
 
@@ -94,7 +99,7 @@ def model_engines(model_type, engine_kws):
 
 def other_model(model_type, precisions):
     """the engines (one per precision, same parameters), device batch and FLOPs per step of a model other than cfg-5"""
-    engines, be, fl = model_engines(model_type, [dict(precision=pr) for pr in precisions])
+    engines, be, fl = model_engines(model_type, [dict(precision=pr, encoder=ARGS.encoder if pr == "bf16" else "f32") for pr in precisions])
     dbe = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
     if os.environ.get("SORT", "1") != "0":
         dbe.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
@@ -102,6 +107,47 @@ def other_model(model_type, precisions):
         for i in range(3):
             ee.train_step(dbe, ee.make_keep_masks(B, 1, i), 1e-3)
     return engines, dbe, fl
+
+
+def ab_medians(runs):
+    """runs: ((label, engine, device batch), ...), warmed up.  `--repeats` times: `steps` alternated steps, one median
+    per engine.  Returns {label: [medians in ms]}."""
+    meds = {k: [] for k, _, _ in runs}
+    for r in range(ARGS.repeats):
+        times = {k: [] for k, _, _ in runs}
+        for i in range(steps):
+            for k, e, d in runs:
+                masks = e.make_keep_masks(B, 1, 3 + r * steps + i)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.train_step(d, masks, 1e-3)
+                torch.cuda.synchronize()
+                times[k].append(time.perf_counter() - t0)
+        for k in times:
+            meds[k].append(1e3 * float(np.median(times[k])))
+        print("%s repeat %d: " % (ARGS.model_type, r) + "  ".join("%s %.3f ms" % (k, meds[k][-1]) for k in meds)
+              + "  (medians of %d alternated steps)" % steps)
+    return meds
+
+
+if ARGS.ab_encoder:
+    (ex, ey), be, fl = model_engines(ARGS.model_type, [dict(precision="bf16"), dict(precision="bf16", encoder="bf16")])
+    dbx = {k: torch.from_numpy(v).cuda() for k, v in be.items()}
+    if os.environ.get("SORT", "1") != "0":
+        dbx.update({k: v for k, v in PT.add_length_sort(dict(be)).items() if k.endswith("/sort")})
+    runs = (("X f32 encoder", ex, dbx), ("Y bf16 encoder", ey, dbx))
+    for _, e, d in runs:
+        for i in range(3):
+            e.train_step(d, e.make_keep_masks(B, 1, i), 1e-3)
+    meds = ab_medians(runs)
+    mx, my = float(np.median(meds["X f32 encoder"])), float(np.median(meds["Y bf16 encoder"]))
+    spread = max(meds["X f32 encoder"]) - min(meds["X f32 encoder"])
+    verdict = "FASTER" if mx - my > spread else "SLOWER" if my - mx > spread else "no measurable difference"
+    print("%s: X %.3f ms, Y %.3f ms (medians of the %d medians), X - Y = %+.3f ms, spread of X's medians %.3f ms -> Y: %s; "
+          "flops_per_step %.3f TFLOP; total_loss %.3f / %.3f"
+          % (ARGS.model_type, mx, my, ARGS.repeats, mx - my, spread, verdict, fl / 1e12, ex.fetch_report()["total_loss"],
+             ey.fetch_report()["total_loss"]))
+    sys.exit(0)
 
 
 if ARGS.ab_features:
@@ -123,21 +169,7 @@ if ARGS.ab_features:
     for _, e, d in runs:
         for i in range(3):
             e.train_step(d, e.make_keep_masks(B, 1, i), 1e-3)
-    meds = {k: [] for k, _, _ in runs}
-    for r in range(ARGS.repeats):
-        times = {k: [] for k, _, _ in runs}
-        for i in range(steps):
-            for k, e, d in runs:
-                masks = e.make_keep_masks(B, 1, 3 + r * steps + i)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                e.train_step(d, masks, 1e-3)
-                torch.cuda.synchronize()
-                times[k].append(time.perf_counter() - t0)
-        for k in times:
-            meds[k].append(1e3 * float(np.median(times[k])))
-        print("%s repeat %d: " % (ARGS.model_type, r) + "  ".join("%s %.3f ms" % (k, meds[k][-1]) for k in meds)
-              + "  (medians of %d alternated steps)" % steps)
+    meds = ab_medians(runs)
     mx, my = float(np.median(meds["X f32 features"])), float(np.median(meds["Y bf16 features"]))
     spread = max(meds["X f32 features"]) - min(meds["X f32 features"])
     print("%s: X %.3f ms, Y %.3f ms (medians of the %d medians), Y - X = %+.3f ms, spread of X's medians %.3f ms -> Y is %s; "
@@ -176,7 +208,7 @@ if ARGS.ab_precision:
     print("step time ratio f32 / bf16 = %.3f" % (med["f32"] / med["bf16"]))
     sys.exit(0)
 
-eng = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p, precision=ARGS.precision)
+eng = PT.PretrainEngine(n=n, R=R, D=D, H=H, W=W, A=A, Vq=Vq, n_ws=n_ws, params=p, precision=ARGS.precision, encoder=ARGS.encoder)
 db = {k: torch.from_numpy(v).cuda() for k, v in batch.items()}
 db.update(sort_info)
 if any(os.environ.get(k) for k in ("VQA_LN_FAST", "VQA_GRU_CFG", "VQA_ATTN_FAST", "VQA_SOFTMAX_FAST")):   # A/B switches

@@ -122,6 +122,7 @@ ABI_VERSION = DEFINES["VQA_HOT_ABI_VERSION"]
 SOFTMAX_PAIR_MAX = DEFINES["VQA_SOFTMAX_PAIR_MAX"]
 globals().update({"FLAG_" + k: v for k, v in _macros("VQA_FLAG_").items()})         # FLAG_DETERMINISTIC, FLAG_BF16_GEMM, ...
 globals().update({"PT_HEAD_" + k: v for k, v in _macros("VQA_PT_HEAD_").items()})   # PT_HEAD_BF, PT_HEAD_WS, PT_HEAD_EW
+globals().update({"PT_FLAG_" + k: v for k, v in _macros("VQA_PT_FLAG_").items()})   # PT_FLAG_BF16_ENCODER: vqa_pretrain_dims_t.flags only
 # bits of Batch.keep_seeded by the name of the site's mask pointer / offset member; bits of PtKeep.seeded by site
 KEEP_SITE = {"keep_" + k.lower(): v for k, v in _macros("VQA_KEEP_SITE_").items()}
 PT_KEEP_SITE = {k.lower(): v for k, v in _macros("VQA_PT_KEEP_SITE_", skip=("ALL",)).items()}

@@ -424,6 +424,8 @@ bool dims_ok(const vqa_dims_t* d) {
     if ((d->flags & VQA_FLAG_BF16_GEMM) && (!bf16_routed(d->model_type) || (d->flags & VQA_FLAG_FUSED_GATHER))) return false;
     // a bf16 table: only inside the bf16 mode (which brings the two conditions above with it)
     if ((d->flags & VQA_FLAG_BF16_FEATURES) && !(d->flags & VQA_FLAG_BF16_GEMM)) return false;
+    // the bf16 sequence encoder is the pre-training steps' (this step's recurrence is the weight-stationary launch)
+    if (d->flags & VQA_PT_FLAG_BF16_ENCODER) return false;
     if (d->model_type == VQA_MODEL_LEGACY_VQA)      // 16-byte rows everywhere; the scoring kernel keeps one H-row in LDS
         return d->map_dim > 0 && d->La > 0 && d->H % 4 == 0 && d->D % 4 == 0 && d->map_dim % 4 == 0 && d->W % 4 == 0 && d->H <= 1024 && d->Vq > 3;
     if (d->model_type == VQA_MODEL_BI) return d->H % 8 == 0;      // two cells of H / 2 units, 16-byte rows each

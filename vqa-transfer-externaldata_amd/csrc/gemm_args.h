@@ -57,6 +57,9 @@ bool vqa_gemm_gather_matches_plain(int M, int N, int K, int lda, int R, int64_t 
 // gemm_f32.hip: one fused GRU-step GEMM, epilogue `epi` (EPI_GATES .. EPI_BWD_DH), tile config `cfg`: a GRU-step id of
 // gemm_tiles.h (VQA_GRU_CFGS and the register-streamed id beside it); VQA_ERR_ARG for any other value
 int vqa_gru_step_launch(int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);
+// gru_step_bf16.hip: the same four problems with bf16 operands in the matrix unit (rounded on their way into LDS), f32
+// accumulation and the same f32 epilogues; any M, N, K >= 1, the tile is chosen by M
+int vqa_gru_step_launch_bf16(int epi, const GemmArgs& a, const EpiArgs& ep, hipStream_t st);
 // gemm_f32.hip: whether `cfg` is such an id
 bool vqa_gru_cfg_known(int cfg);
 // gru_stream.hip: the register-streamed form of the same step; VQA_ERR_UNSUPPORTED for shapes it does not take

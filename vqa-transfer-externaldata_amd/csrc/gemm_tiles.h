@@ -3,7 +3,8 @@
 // (vqa_gemm_set_gru_config, VQA_HOT_GRU_*), conv ids (vqa_conv_set_config) and tall ids (vqa_gemm_set_tall_config).
 // Every dispatcher of gemm_f32.hip names an entry of VQA_GEMM_TILES; none repeats a tile's numbers.  To add a tile: one
 // row here (a PLAIN row takes the next id), one row in tests/gemm_ref.py::CFG, and a row in whichever id table below
-// should reach it.  Internal: gemm_f32.hip includes it, other translation units ask through gemm_args.h.
+// should reach it.  Internal: gemm_f32.hip includes it (and gru_step.hip, for the ids that are no tile), other translation units ask through
+// gemm_args.h.
 #pragma once
 #include "vqa_common.h"
 
@@ -108,6 +109,9 @@ using EdgeTile = Plain<2>;
 // they do not take run under the fallback id
 constexpr int GRU_CFG_STREAMED = 30;
 constexpr int GRU_CFG_STREAMED_FALLBACK = 16;
+// ... and one that is no tile of gemm_f32_kernel at all: the per-step drivers (gru_step.hip) run their step GEMMs on the
+// bf16 matrix unit (gru_step_bf16.hip).  vqa_gemm_set_gru_config admits it; vqa_gru_step_launch never sees it.
+constexpr int GRU_CFG_BF16 = 64;
 
 // conv ids of the implicit-GEMM convolutions: X(conv id, plain id of its tile).  (The 1x1 path names plain ids itself.)
 #define VQA_CONV_CFGS(X) X(0, 3) X(1, 20) X(2, 21) X(3, 16)

@@ -4,9 +4,14 @@
 // weight-stationary launch (gru_ws.hip) does not take runs here.  Tapes are time-major: xp / dxp [T,B,3H] (r | u | c),
 // hs [T+1,B,H] (hs[0] = the initial state), r, u, c, rh [T,B,H].  The forward and the backward step are written once
 // (fwd_step, bwd_step) on rows [row0, row0 + rows); the entry points differ in which rows they hand to each step.
+// Every driver exists once, as a C++ function that takes the FORM of the step GEMMs (gru_step.h: f32, or the bf16 matrix
+// unit of gru_step_bf16.hip); the extern "C" entry points forward the process-wide setting (GRU-step id GRU_CFG_BF16 =
+// the bf16 form), a train step hands in its own.
 
 #include "vqa_common.h"
 #include "gemm_args.h"
+#include "gemm_tiles.h"
+#include "gru_step.h"
 
 namespace {
 
@@ -24,7 +29,8 @@ int g_gru_cfg = -1;
 // 1536 rows: 1072 -> 961 us per 10 steps) and 64x32 tiles of 8 waves backward (632 -> 559, 995 -> 869);
 // profiles/r2_gru_tune_rows.txt.
 inline int gru_cfg_by_rows(int rows, int mid, int tall) {
-    return g_gru_cfg >= 0 ? g_gru_cfg : (rows >= 2048 ? tall : rows > 512 ? mid : rows > 256 ? 18 : 16);
+    // (GRU_CFG_BF16 names a form, not a tile of the f32 kernels: an f32 recurrence under it runs the defaults)
+    return (g_gru_cfg >= 0 && g_gru_cfg != GRU_CFG_BF16) ? g_gru_cfg : (rows >= 2048 ? tall : rows > 512 ? mid : rows > 256 ? 18 : 16);
 }
 inline int gru_cfg_fwd(int rows) {
     static const int mid = vqa_env_int("VQA_HOT_GRU_MID_FWD", 9), tall = vqa_env_int("VQA_HOT_GRU_TALL_FWD", 12);
@@ -35,7 +41,7 @@ inline int gru_cfg_fwd(int rows) {
 // 2560 rows, T 10.  VQA_HOT_GRU_NARROW_CFG overrides (tuning; -1 = the same config as the gate kernel).
 inline int gru_cfg_fwd_cand(int rows) {
     static const int narrow = vqa_env_int("VQA_HOT_GRU_NARROW_CFG", 9);
-    return (g_gru_cfg < 0 && rows >= 2048 && narrow >= 0) ? narrow : gru_cfg_fwd(rows);
+    return ((g_gru_cfg < 0 || g_gru_cfg == GRU_CFG_BF16) && rows >= 2048 && narrow >= 0) ? narrow : gru_cfg_fwd(rows);
 }
 inline int gru_cfg_bwd(int rows) {
     static const int mid = vqa_env_int("VQA_HOT_GRU_MID_BWD", 17), tall = vqa_env_int("VQA_HOT_GRU_TALL_BWD", 13);
@@ -46,12 +52,19 @@ inline int gru_cfg_bwd(int rows) {
 struct FwdTape {
     float* xp; const float *Wg_h, *Wc_h; const int32_t* len; float *hs, *r, *u, *c, *rh;
     int B, H; hipStream_t st;
+    int form;              // GRU_FORM_*
 };
 struct BwdTape {
     const float *Wg_h, *Wc_h; const int32_t* len; const float *hs, *r, *u, *c;
     const float* d_outs;   // gradient wrt every step's output [T,B,H], or null
     float* dxp; int B, H; hipStream_t st;
+    int form;
 };
+
+// one fused step GEMM in the tape's form; `cfg`: the f32 form's tile (the bf16 form chooses its own by rows)
+inline int step_launch(int form, int epi, int cfg, const GemmArgs& a, const EpiArgs& ep, hipStream_t st) {
+    return form == GRU_FORM_BF16 ? vqa_gru_step_launch_bf16(epi, a, ep, st) : vqa_gru_step_launch(epi, cfg, a, ep, st);
+}
 
 // Forward step t on rows [row0, row0 + rows): gates (r, u, rh = r * h_prev), then candidate and the new state.
 int fwd_step(const FwdTape& p, int t, int row0, int rows) {
@@ -62,12 +75,12 @@ int fwd_step(const FwdTape& p, int t, int row0, int rows) {
     EpiArgs eg{};
     eg.H = H; eg.h_prev = hp; eg.o0 = p.r + s; eg.o1 = p.u + s; eg.o2 = p.rh + s;
     GemmArgs ag = vqa_gemm_make_args(rows, 2 * H, H, hp, H, p.Wg_h, 2 * H, nullptr, 0, nullptr, xpt, 3 * H);
-    int rc = vqa_gru_step_launch(EPI_GATES, gru_cfg_fwd(rows), ag, eg, p.st);
+    int rc = step_launch(p.form, EPI_GATES, gru_cfg_fwd(rows), ag, eg, p.st);
     if (rc != VQA_OK) return rc;
     EpiArgs ec{};
     ec.H = H; ec.t = t; ec.len = p.len + row0; ec.h_prev = hp; ec.i0 = p.u + s; ec.o0 = p.c + s; ec.o1 = p.hs + s + BH;
     GemmArgs ac = vqa_gemm_make_args(rows, H, H, p.rh + s, H, p.Wc_h, H, nullptr, 0, nullptr, xpt + 2 * H, 3 * H);
-    return vqa_gru_step_launch(EPI_CAND, gru_cfg_fwd_cand(rows), ac, ec, p.st);
+    return step_launch(p.form, EPI_CAND, gru_cfg_fwd_cand(rows), ac, ec, p.st);
 }
 
 // Second half of backward step t on rows [row0, row0 + rows), whose first half (vqa_gru_bwd_a: dc_pre, du_pre, dh_acc)
@@ -82,7 +95,7 @@ int bwd_step(const BwdTape& p, int t, int row0, int rows, float*& cur, float*& o
     EpiArgs e1{};
     e1.H = H; e1.ldo = ld; e1.h_prev = p.hs + s; e1.i0 = p.r + s; e1.o0 = dxpt; e1.o1 = cur;
     GemmArgs a1 = vqa_gemm_make_args(rows, H, H, dxpt + 2 * H, ld, p.Wc_h, H, nullptr, 0, nullptr, nullptr, 0);
-    int rc = vqa_gru_step_launch(EPI_BWD_RH, gru_cfg_bwd(rows), a1, e1, p.st);
+    int rc = step_launch(p.form, EPI_BWD_RH, gru_cfg_bwd(rows), a1, e1, p.st);
     if (rc != VQA_OK || t == 0) return rc;
     const int64_t sp = s - BH;   // step t-1
     if (p.d_outs) {
@@ -94,7 +107,7 @@ int bwd_step(const BwdTape& p, int t, int row0, int rows, float*& cur, float*& o
     e2.H = H; e2.t = t - 1; e2.ldo = ld; e2.len = p.len + row0; e2.h_prev = p.hs + sp;
     e2.i0 = p.u + sp; e2.i1 = p.c + sp; e2.o0 = dxpp + 2 * H; e2.o1 = dxpp + H; e2.o2 = other;
     GemmArgs a2 = vqa_gemm_make_args(rows, H, 2 * H, dxpt, ld, p.Wg_h, 2 * H, nullptr, 0, nullptr, cur, H);
-    rc = vqa_gru_step_launch(EPI_BWD_DH, gru_cfg_bwd(rows), a2, e2, p.st);
+    rc = step_launch(p.form, EPI_BWD_DH, gru_cfg_bwd(rows), a2, e2, p.st);
     float* x = cur; cur = other; other = x;
     return rc;
 }
@@ -115,28 +128,36 @@ int bwd_window(const BwdTape& p, float* dh_T, float* dh_scratch, int T, int row0
     return rc;
 }
 
+inline int global_form() { return g_gru_cfg == GRU_CFG_BF16 ? GRU_FORM_BF16 : GRU_FORM_F32; }
+inline bool form_ok(int form) { return form == GRU_FORM_F32 || form == GRU_FORM_BF16; }
+
 }  // namespace
 
 extern "C" int vqa_gemm_set_gru_config(int cfg) {
-    VQA_REQUIRE(cfg == -1 || vqa_gru_cfg_known(cfg), VQA_ERR_ARG);
+    VQA_REQUIRE(cfg == -1 || cfg == GRU_CFG_BF16 || vqa_gru_cfg_known(cfg), VQA_ERR_ARG);
     g_gru_cfg = cfg;   // -1 restores the defaults
     return VQA_OK;
 }
 
 extern "C" int vqa_gru_seq_fwd(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
                                float* r, float* u, float* c, float* rh, int T, int B, int H, void* stream) {
-    return vqa_gru_seq_fwd_rows(xp, Wg_h, Wc_h, len, hs, r, u, c, rh, T, B, H, 0, B, stream);
+    return gru_seq_fwd_rows_form(global_form(), xp, Wg_h, Wc_h, len, hs, r, u, c, rh, T, B, H, 0, B, stream);
 }
 
 // rows [row0, row0 + rows) of the batch only (independent chains: one per stream)
 extern "C" int vqa_gru_seq_fwd_rows(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs,
                                     float* r, float* u, float* c, float* rh, int T, int B, int H, int row0, int rows,
                                     void* stream) {
+    return gru_seq_fwd_rows_form(global_form(), xp, Wg_h, Wc_h, len, hs, r, u, c, rh, T, B, H, row0, rows, stream);
+}
+int gru_seq_fwd_rows_form(int form, float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len, float* hs, float* r,
+                          float* u, float* c, float* rh, int T, int B, int H, int row0, int rows, void* stream) {
+    VQA_REQUIRE(form_ok(form), VQA_ERR_ARG);
     VQA_REQUIRE(xp && Wg_h && Wc_h && len && hs && r && u && c && rh && T >= 0 && B > 0 && H > 0, VQA_ERR_ARG);
     VQA_REQUIRE(row0 >= 0 && rows >= 0 && row0 + rows <= B, VQA_ERR_ARG);
     VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
     if (rows == 0) return VQA_OK;
-    const FwdTape p{xp, Wg_h, Wc_h, len, hs, r, u, c, rh, B, H, static_cast<hipStream_t>(stream)};
+    const FwdTape p{xp, Wg_h, Wc_h, len, hs, r, u, c, rh, B, H, static_cast<hipStream_t>(stream), form};
     int rc = VQA_OK;
     for (int t = 0; t < T && rc == VQA_OK; ++t) rc = fwd_step(p, t, row0, rows);
     return rc;
@@ -149,9 +170,15 @@ extern "C" int vqa_gru_seq_fwd_rows(float* xp, const float* Wg_h, const float* W
 extern "C" int vqa_gru_seq_fwd_live(float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len,
                                     const int32_t* live_rows, float* hs, float* r, float* u, float* c, float* rh,
                                     int T, int B, int H, void* stream) {
+    return gru_seq_fwd_live_form(global_form(), xp, Wg_h, Wc_h, len, live_rows, hs, r, u, c, rh, T, B, H, stream);
+}
+int gru_seq_fwd_live_form(int form, float* xp, const float* Wg_h, const float* Wc_h, const int32_t* len,
+                          const int32_t* live_rows, float* hs, float* r, float* u, float* c, float* rh, int T, int B, int H,
+                          void* stream) {
+    VQA_REQUIRE(form_ok(form), VQA_ERR_ARG);
     VQA_REQUIRE(xp && Wg_h && Wc_h && len && live_rows && hs && r && u && c && rh && T >= 0 && B > 0 && H > 0, VQA_ERR_ARG);
     VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    const FwdTape p{xp, Wg_h, Wc_h, len, hs, r, u, c, rh, B, H, static_cast<hipStream_t>(stream)};
+    const FwdTape p{xp, Wg_h, Wc_h, len, hs, r, u, c, rh, B, H, static_cast<hipStream_t>(stream), form};
     int prev = B;
     for (int t = 0; t < T; ++t) {
         const int rows = live_rows[t];
@@ -171,17 +198,24 @@ extern "C" int vqa_gru_seq_fwd_live(float* xp, const float* Wg_h, const float* W
 extern "C" int vqa_gru_seq_bwd(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
                                const float* hs, const float* r, const float* u, const float* c, float* dxp,
                                float* dh_scratch, int T, int B, int H, void* stream) {
-    return vqa_gru_seq_bwd_rows(dh_T, Wg_h, Wc_h, len, hs, r, u, c, dxp, dh_scratch, T, B, H, 0, B, stream);
+    return gru_seq_bwd_rows_form(global_form(), dh_T, Wg_h, Wc_h, len, hs, r, u, c, dxp, dh_scratch, T, B, H, 0, B, stream);
 }
 
 extern "C" int vqa_gru_seq_bwd_rows(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
                                     const float* hs, const float* r, const float* u, const float* c, float* dxp,
                                     float* dh_scratch, int T, int B, int H, int row0, int rows, void* stream) {
+    return gru_seq_bwd_rows_form(global_form(), dh_T, Wg_h, Wc_h, len, hs, r, u, c, dxp, dh_scratch, T, B, H, row0, rows,
+                                 stream);
+}
+int gru_seq_bwd_rows_form(int form, float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len, const float* hs,
+                          const float* r, const float* u, const float* c, float* dxp, float* dh_scratch, int T, int B, int H,
+                          int row0, int rows, void* stream) {
+    VQA_REQUIRE(form_ok(form), VQA_ERR_ARG);
     VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && hs && r && u && c && dxp && dh_scratch && T >= 0 && B > 0 && H > 0,
                 VQA_ERR_ARG);
     VQA_REQUIRE(row0 >= 0 && rows >= 0 && row0 + rows <= B, VQA_ERR_ARG);
     VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    const BwdTape p{Wg_h, Wc_h, len, hs, r, u, c, nullptr, dxp, B, H, static_cast<hipStream_t>(stream)};
+    const BwdTape p{Wg_h, Wc_h, len, hs, r, u, c, nullptr, dxp, B, H, static_cast<hipStream_t>(stream), form};
     return bwd_window(p, dh_T, dh_scratch, T, row0, rows);
 }
 
@@ -195,7 +229,7 @@ extern "C" int vqa_gru_seq_bwd_outs(float* dh_T, const float* Wg_h, const float*
     VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && hs && r && u && c && d_outs && dxp && dh_scratch && T >= 0 && B > 0 && H > 0,
                 VQA_ERR_ARG);
     VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
-    const BwdTape p{Wg_h, Wc_h, len, hs, r, u, c, d_outs, dxp, B, H, static_cast<hipStream_t>(stream)};
+    const BwdTape p{Wg_h, Wc_h, len, hs, r, u, c, d_outs, dxp, B, H, static_cast<hipStream_t>(stream), global_form()};
     return bwd_window(p, dh_T, dh_scratch, T, 0, B);
 }
 
@@ -204,11 +238,18 @@ extern "C" int vqa_gru_seq_bwd_outs(float* dh_T, const float* Wg_h, const float*
 extern "C" int vqa_gru_seq_bwd_live(float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
                                     const int32_t* live_rows, const float* hs, const float* r, const float* u,
                                     const float* c, float* dxp, float* dh_scratch, int T, int B, int H, void* stream) {
+    return gru_seq_bwd_live_form(global_form(), dh_T, Wg_h, Wc_h, len, live_rows, hs, r, u, c, dxp, dh_scratch, T, B, H,
+                                 stream);
+}
+int gru_seq_bwd_live_form(int form, float* dh_T, const float* Wg_h, const float* Wc_h, const int32_t* len,
+                          const int32_t* live_rows, const float* hs, const float* r, const float* u, const float* c,
+                          float* dxp, float* dh_scratch, int T, int B, int H, void* stream) {
+    VQA_REQUIRE(form_ok(form), VQA_ERR_ARG);
     VQA_REQUIRE(dh_T && Wg_h && Wc_h && len && live_rows && hs && r && u && c && dxp && dh_scratch, VQA_ERR_ARG);
     VQA_REQUIRE(T >= 0 && B > 0 && H > 0, VQA_ERR_ARG);
     VQA_REQUIRE(H % 4 == 0, VQA_ERR_ALIGN);
     if (T == 0) return VQA_OK;
-    const BwdTape p{Wg_h, Wc_h, len, hs, r, u, c, nullptr, dxp, B, H, static_cast<hipStream_t>(stream)};
+    const BwdTape p{Wg_h, Wc_h, len, hs, r, u, c, nullptr, dxp, B, H, static_cast<hipStream_t>(stream), form};
     const int64_t BH = (int64_t)B * H;
     const int ld = 3 * H;
     // both state-gradient buffers start as dL/dh_final: a row is first touched at its own last step

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "gru_encoder.h"
+#include "gru_step.h"
 #include "keep_launch.h"
 
 namespace {
@@ -97,13 +98,14 @@ const char* const HEAD[3] = {"bf", "ws", "ew"};      // blank fill, word set, en
 const char* const TASK[3] = {"blank_fill", "wordset", "enwiki"};
 
 inline bool feat16(const vqa_pretrain_dims_t& d) { return (d.flags & VQA_FLAG_BF16_FEATURES) != 0; }      // image_ft is bf16 patterns
+inline bool enc16(const vqa_pretrain_dims_t& d) { return (d.flags & VQA_PT_FLAG_BF16_ENCODER) != 0; }       // both encoders are routed
 
-// (bf16 features only on top of the bf16 GEMMs: every query and every pass of every family goes through here, so the
-// flag alone is VQA_ERR_ARG before anything is launched)
+// (bf16 features and the bf16 encoder only on top of the bf16 GEMMs: every query and every pass of every family goes
+// through here, so either flag alone is VQA_ERR_ARG before anything is launched)
 bool dims_ok(const vqa_pretrain_dims_t* d) {
     return d && d->B > 0 && d->n > 0 && d->n <= 8 && d->R > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->A > 0 &&
            d->Vq > 0 && d->n_ws > 0 && d->L > 0 && d->H % 4 == 0 && d->D % 4 == 0 &&
-           (!feat16(*d) || (d->flags & VQA_FLAG_BF16_GEMM));
+           (!(feat16(*d) || enc16(*d)) || (d->flags & VQA_FLAG_BF16_GEMM));
 }
 
 struct Ctx : Workspace {
@@ -119,14 +121,19 @@ struct Ctx : Workspace {
     }
     // LayerNorm slot of call site `site` of an fc_layer scope: slot 0 for every site under VQA_FLAG_SHARED_LN
     int li(int site) const { return (d.flags & VQA_FLAG_SHARED_LN) ? 0 : site; }
-    // The f32 MFMA product, whatever the flags say: both encoders (x-projection, dx, dwx, dwh), wordset_ft and the K = 6
-    // box layers call this one (include/vqa_hot.h, VQA_FLAG_BF16_GEMM: the unrouted list).
+    // The f32 MFMA product, whatever the flags say: wordset_ft, the K = 6 box layers and -- without
+    // VQA_PT_FLAG_BF16_ENCODER -- both encoders (x-projection, dx, dwx, dwh) call this one (include/vqa_hot.h,
+    // VQA_FLAG_BF16_GEMM: the unrouted list).
     int gemm_f32(int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B, int ldb, float* C,
                  int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) const {
         return vqa_gemm_f32(tA, tB, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, bias, D, ldd, 0, f("gemm_ws"),
                             count("gemm_ws"), st);
     }
     auto f32() const { return [this](auto... a) { return gemm_f32(a...); }; }      // as a callable (gru_encoder.h)
+    auto routed() const { return [this](auto... a) { return gemm_routed(a...); }; }
+    // what the encoders run: the routed product and the bf16 recurrence under VQA_PT_FLAG_BF16_ENCODER (which implies
+    // VQA_FLAG_BF16_GEMM, dims_ok), else the f32 product and the recurrence's entry points as they always were
+    bool enc_routed() const { return enc16(d); }
     // The routed layers' products (forward, dW, dx): bf16 operands in the matrix unit under VQA_FLAG_BF16_GEMM, else f32.
     // A shape the bf16 kernel refuses is its error return, never a silent f32 product.  Every call site names one of the
     // two wrappers: there is no default a new site could pick up by accident.
@@ -179,9 +186,9 @@ struct Acc {
         if (prec == PREC_ROUTED) return c.gemm_routed(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N, x16);
         return c.gemm_f32(1, 0, K, N, M, x, ldx, dpre, ldp, gw, (int)N, nullptr, add, (int)N);
     }
-    auto f32() {      // weight(PREC_F32, ...) in the argument order of a GEMM call with tA = 1, tB = 0 (gru_encoder.h)
-        return [this](int, int, int64_t K, int64_t N, int64_t M, const float* x, int ldx, const float* dy, int ldy, float* gw, int,
-                      const float*) { return weight(PREC_F32, gw, x, ldx, dy, ldy, K, N, M); };
+    auto as_gemm(Prec prec) {      // weight(prec, ...) in the argument order of a GEMM call with tA = 1, tB = 0 (gru_encoder.h)
+        return [this, prec](int, int, int64_t K, int64_t N, int64_t M, const float* x, int ldx, const float* dy, int ldy, float* gw,
+                            int, const float*) { return weight(prec, gw, x, ldx, dy, ldy, K, N, M); };
     }
     // three column sums (d_gamma, d_beta, d_bias partials [G, N]) into their gradients: first touch overwrites, later
     // ones add inside the reduction's last pass (no temporaries, no add kernels)
@@ -418,8 +425,10 @@ Layout make_layout_ext(const vqa_pretrain_ext_dims_t& dx, bool noc, bool adapt) 
     g(1, 0, 6, H, B * R); g(1, 0, 6, H, Bn); g(1, 0, W, H, Bn); g(0, 1, Bn, W, H);
     for (const int64_t S : {T, Tc}) {        // the two recurrences' x-projection, its dW / dx and the h-row dW
         if (S == 0) continue;
-        g(0, 0, S * 2 * Bn, 3 * H, W); g(1, 0, x_stride(W), 3 * H, S * 2 * Bn); g(0, 1, S * 2 * Bn, W, 3 * H);
-        g(1, 0, H, 2 * H, S * 2 * Bn); g(1, 0, H, H, S * 2 * Bn);
+        // (routed under VQA_PT_FLAG_BF16_ENCODER only: without it the sizing is what it was)
+        auto ge = [&](int tA, int tB, int64_t M, int64_t N, int64_t K) { enc16(d) ? gr(tA, tB, M, N, K) : g(tA, tB, M, N, K); };
+        ge(0, 0, S * 2 * Bn, 3 * H, W); ge(1, 0, x_stride(W), 3 * H, S * 2 * Bn); ge(0, 1, S * 2 * Bn, W, 3 * H);
+        ge(1, 0, H, 2 * H, S * 2 * Bn); ge(1, 0, H, H, S * 2 * Bn);
     }
     // the routed layers: pooled_linear_l, q_linear_l, the joint layer(s) and the classifier(s), forward / dW / dx
     gr(0, 0, 2 * Bn, H, D); gr(0, 0, NH * Bn, H, H); gr(0, 0, NH * Bn, 2 * H, H); gr(0, 0, NH * Bn, A, 2 * H);
@@ -754,9 +763,16 @@ int seq_fwd(const Ctx& c, const Seq& s, bool pack_wx) {
     TRY(gather_rows2(s.tokens[0], s.tokens[1], s.perm, tok, B2, T, Bn, c.st));
     TRY(gather_rows2(s.len[0], s.len[1], s.perm, lens, B2, 1, Bn, c.st));
     TRY(vqa_embed_fwd_ld(s.table, tok, t.x_tm, (int)B2, (int)T, (int)W, s.vocab, t.ldx(), c.st));
-    TRY(t.project(c.f32()));
+    TRY(c.enc_routed() ? t.project(c.routed()) : t.project(c.f32()));
     TRY(t.clear_h0());
-    if (s.live_rows != nullptr)
+    if (c.enc_routed()) {      // the bf16 form of the same two drivers, per call (gru_step.h)
+        if (s.live_rows != nullptr)
+            TRY(gru_seq_fwd_live_form(GRU_FORM_BF16, t.xp, t.Wg_h(), t.Wc_h(), lens, s.live_rows, t.hs, t.gru_r, t.gru_u, t.gru_c,
+                                      t.gru_rh, (int)T, (int)B2, (int)H, c.st));
+        else
+            TRY(gru_seq_fwd_rows_form(GRU_FORM_BF16, t.xp, t.Wg_h(), t.Wc_h(), lens, t.hs, t.gru_r, t.gru_u, t.gru_c, t.gru_rh,
+                                      (int)T, (int)B2, (int)H, 0, (int)B2, c.st));
+    } else if (s.live_rows != nullptr)
         TRY(vqa_gru_seq_fwd_live(t.xp, t.Wg_h(), t.Wc_h(), lens, s.live_rows, t.hs, t.gru_r, t.gru_u, t.gru_c, t.gru_rh, (int)T,
                                  (int)B2, (int)H, c.st));
     else
@@ -774,15 +790,23 @@ int seq_bptt(const Ctx& c, Acc& acc, const Seq& s) {
     const int32_t* lens = c.i32(s.in + "lens_s");
     float* d_state = c.f(s.scr + "d_state_s");
     TRY(gather_rows(c.f("d_lft") + s.head * Bn * H, s.perm, d_state, B2, H, c.st));      // into the sorted order
-    if (s.live_rows != nullptr)
+    if (c.enc_routed()) {
+        if (s.live_rows != nullptr)
+            TRY(gru_seq_bwd_live_form(GRU_FORM_BF16, d_state, t.Wg_h(), t.Wc_h(), lens, s.live_rows, t.hs, t.gru_r, t.gru_u,
+                                      t.gru_c, t.dxp, c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
+        else
+            TRY(gru_seq_bwd_rows_form(GRU_FORM_BF16, d_state, t.Wg_h(), t.Wc_h(), lens, t.hs, t.gru_r, t.gru_u, t.gru_c, t.dxp,
+                                      c.f("d_hscratch"), (int)T, (int)B2, (int)H, 0, (int)B2, c.st));
+    } else if (s.live_rows != nullptr)
         TRY(vqa_gru_seq_bwd_live(d_state, t.Wg_h(), t.Wc_h(), lens, s.live_rows, t.hs, t.gru_r, t.gru_u, t.gru_c, t.dxp,
                                  c.f("d_hscratch"), (int)T, (int)B2, (int)H, c.st));
     else
         TRY(vqa_gru_seq_bwd(d_state, t.Wg_h(), t.Wc_h(), lens, t.hs, t.gru_r, t.gru_u, t.gru_c, t.dxp, c.f("d_hscratch"), (int)T,
                             (int)B2, (int)H, c.st));
-    TRY(t.dwx(acc.f32()));
-    TRY(t.dwh(acc.f32(), s.G, false, 0));
-    TRY(t.dwh(acc.f32(), s.G, true, 0));
+    const Prec prec = c.enc_routed() ? PREC_ROUTED : PREC_F32;
+    TRY(t.dwx(acc.as_gemm(prec)));
+    TRY(t.dwh(acc.as_gemm(prec), s.G, false, 0));
+    TRY(t.dwh(acc.as_gemm(prec), s.G, true, 0));
     return t.unpack_dwx(s.G);
 }
 
@@ -806,7 +830,7 @@ int seq_embed_bwd(const Ctx& c, const Seq& s, SliceSq& sq) {
     const GruTape& t = s.t;
     // packed again here (one small kernel): no hidden dependence on the forward's copy of the weights
     TRY(t.pack_wx());
-    TRY(t.dx(c.f32(), dx));
+    TRY(c.enc_routed() ? t.dx(c.routed(), dx) : t.dx(c.f32(), dx));
     TRY(vqa_embed_bwd_len_det(dx, c.i32(s.in + s.tok), c.i32(s.in + "lens_s"), s.g_table, (int)B2, (int)T, (int)W, s.vocab,
                               (c.d.flags & VQA_FLAG_DETERMINISTIC) ? 1 : 0, c.st));
     return sq.add(dx, T * B2 * W);

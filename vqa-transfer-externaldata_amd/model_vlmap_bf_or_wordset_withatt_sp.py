@@ -170,7 +170,8 @@ class Model(object):
                                              deterministic=bool(getattr(self.config, "deterministic", 0)),
                                              heads=self.heads, n_ctx=self.num_context_vocab, noc=self.NOC,
                                              adapt=self.ADAPT, precision=getattr(self.config, "precision", "f32"),
-                                             features=getattr(self.config, "features", "f32"))
+                                             features=getattr(self.config, "features", "f32"),
+                                             encoder=getattr(self.config, "encoder", "f32"))
         eng = self._engine
         B = int((db["image_ft"] if "image_ft" in db else db["image_idx"]).shape[0])
         tables = getattr(self.config, "feature_tables", None)

@@ -39,7 +39,8 @@ bits computed inside the attention and LayerNorm kernels that consume them (vqa_
 DESIGN.md section 7), no mask tensor, bit for bit the same step.  keep_offsets() is the one copy of the stream layout.
 
 Precision: f32, or opt-in `precision="bf16"` (the routed head layers on the bf16 matrix unit) and on top of it
-`features="bf16"` (the region features at rest as bf16: table, gathered rows and what the attention kernels read).
+`features="bf16"` (the region features at rest as bf16: table, gathered rows and what the attention kernels read) and
+`encoder="bf16"` (both sequence encoders on the bf16 matrix unit: their five products and the per-step recurrence).
 """
 from __future__ import annotations
 
@@ -240,6 +241,7 @@ PARAM_FIELDS = {_lib.PtParams: _TRUNK + _HEADS,
 
 PRECISIONS = ("f32", "bf16")      # PretrainEngine(precision=...): "bf16" sets VQA_FLAG_BF16_GEMM
 FEATURE_FORMATS = ("f32", "bf16")  # PretrainEngine(features=...): "bf16" sets VQA_FLAG_BF16_FEATURES
+ENCODER_FORMATS = ("f32", "bf16")  # PretrainEngine(encoder=...): "bf16" sets VQA_PT_FLAG_BF16_ENCODER
 
 
 def flat_layout(shapes):
@@ -266,7 +268,8 @@ def flat_layout(shapes):
 
 class PretrainEngine(EngineCore):
     def __init__(self, *, n, R, D, H, W, A, Vq, n_ws, params, device="cuda:0", deterministic=False, ln_shared=None,
-                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False, precision="f32", features="f32"):
+                 heads=CFG5_HEADS, n_ctx=None, noc=False, adapt=False, precision="f32", features="f32",
+                 encoder="f32"):
         """ln_shared: one LayerNorm per shared fc_layer scope (True) or one per call site (False); None = whatever the
         variable names in `params` say (`.../LayerNorm_1/...` present -> per call site), as for a checkpoint.
         heads: the head set (MODEL_HEADS); with 'ew', n_ctx = the enwiki context vocabulary and every batch carries
@@ -284,15 +287,26 @@ class PretrainEngine(EngineCore):
         batch that carries image_ft itself carries it as torch.bfloat16, and the attention kernels (adapt: v_adapt's
         forward and dW GEMMs) read the 16-bit patterns as they are (VQA_FLAG_BF16_FEATURES).  Half the resident table; the
         step equals, bit for bit, the precision="bf16" step on the same features widened to f32.  Every head set, noc
-        and adapt; parameters, checkpoints and DP buckets unchanged."""
+        and adapt; parameters, checkpoints and DP buckets unchanged.
+        encoder="bf16" (opt-in, only with precision="bf16"): both sequence encoders join the routed list -- the
+        x-projection, dx, dwx and both dwh on the bf16 GEMM, the per-step recurrence with bf16 operands in its four fused
+        step GEMMs (VQA_PT_FLAG_BF16_ENCODER; h, r*h, the backward's d_pre operands and the weights are rounded on their way
+        into the matrix unit, the state, the tapes and the gate math stay f32).  Per engine, not process-wide.  Every head
+        set, noc and adapt; composes with features="bf16" and seeded dropout; parameters, checkpoints and DP buckets
+        unchanged."""
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
         if features not in FEATURE_FORMATS:
             raise ValueError("features must be one of %s, not %r" % (FEATURE_FORMATS, features))
+        if encoder not in ENCODER_FORMATS:
+            raise ValueError("encoder must be one of %s, not %r" % (ENCODER_FORMATS, encoder))
+        if encoder == "bf16" and precision != "bf16":
+            raise ValueError("encoder='bf16' needs precision='bf16' (the flag is valid only on top of the bf16 GEMMs)")
         if features == "bf16" and precision != "bf16":
             raise ValueError("features='bf16' needs precision='bf16' (the f32 products read f32 features)")
         self.precision = precision
         self.features = features
+        self.encoder = encoder
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VqaHotError("PretrainEngine needs a GPU (no CPU fallback)")
@@ -338,7 +352,8 @@ class PretrainEngine(EngineCore):
     def _flags(self):
         return (_lib.FLAG_DETERMINISTIC if self.deterministic else 0) | (_lib.FLAG_SHARED_LN if self.ln_shared else 0) | \
             (_lib.FLAG_BF16_GEMM if self.precision == "bf16" else 0) | \
-            (_lib.FLAG_BF16_FEATURES if self.features == "bf16" else 0)
+            (_lib.FLAG_BF16_FEATURES if self.features == "bf16" else 0) | \
+            (_lib.PT_FLAG_BF16_ENCODER if self.encoder == "bf16" else 0)
 
     # ------------------------------------------------------------------ C-ABI plumbing
     def keep_offsets(self, B, step, row_offset=0, global_rows=None):

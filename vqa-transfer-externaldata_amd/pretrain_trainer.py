@@ -65,8 +65,9 @@ class Trainer(object):
         if self.rank == 0:
             os.makedirs(self.train_dir, exist_ok=True)
             log.infov("Train Dir: %s", self.train_dir)
-            log.infov("Model: %s, batch size %d, precision %s, features %s", config.model_type, config.batch_size,
-                      getattr(config, "precision", "f32"), getattr(config, "features", "f32"))
+            log.infov("Model: %s, batch size %d, precision %s, features %s, encoder %s", config.model_type,
+                      config.batch_size, getattr(config, "precision", "f32"), getattr(config, "features", "f32"),
+                      getattr(config, "encoder", "f32"))
         self.batch_size = config.batch_size
         # Input side (not in the reference, whose sequential py_func pipeline fed a 2018 GPU): the feature tables of
         # both splits stay in HBM and batches carry image indices (features_on_device), batches are assembled by
@@ -256,6 +257,10 @@ def build_parser():
     parser.add_argument("--features", type=str, default="f32", choices=["f32", "bf16"],
                         help="bf16 (only with --precision bf16): the region-feature table is rounded to bf16 once at load and "
                              "kept in HBM as bf16 -- half the feature memory and gather traffic; the feature file stays f32")
+    parser.add_argument("--encoder", type=str, default="f32", choices=["f32", "bf16"],
+                        help="bf16 (only with --precision bf16): both sequence encoders (caption, enwiki context) run their "
+                             "x-projection, BPTT weight products and the per-step recurrence with bf16 operands in the "
+                             "matrix unit; state, tapes and gate math stay f32 (checkpoints are those of f32)")
     parser.add_argument("--inline_dropout", action="store_true", default=False,
                         help="draw the dropout keep bits inside the kernels that consume them instead of writing mask "
                              "buffers first: the same bits, so the same results (not in the reference)")

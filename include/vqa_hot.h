@@ -604,7 +604,9 @@ typedef struct {
                                      * NOT ROUTED, f32 MFMA as without the flag: the question encoder -- the K = W
                                      * x-projection of the GRU, its weight-stationary / per-step recurrence, its dx product
                                      * and its weight gradients (dwx, dwh) -- because rounding would compound over the T
-                                     * steps.  Everything that is not a GEMM (LayerNorm, attention, loss, clip, Adam) is f32.
+                                     * steps -- unless VQA_FLAG_BF16_ENCODER_GEMMS, below, is set as well: that routes the
+                                     * five single products and leaves the recurrence, the only place where rounding
+                                     * would compound, in f32.  Everything that is not a GEMM (LayerNorm, attention, loss, clip, Adam) is f32.
                                      * Accepted model types: 0 (vlmap_answer) and 1 (standard); every other type, and the
                                      * flag together with VQA_FLAG_FUSED_GATHER (the gather-fused GEMM has no bf16 form),
                                      * makes vqa_fusion_workspace_bytes / _tensor / _forward / _backward* return
@@ -667,6 +669,30 @@ typedef struct {
                                      * forms included) of every family return VQA_ERR_ARG, and nothing is launched.  In
                                      * vqa_dims_t.flags (the VQA step, whose recurrence is the weight-stationary launch) the
                                      * bit is VQA_ERR_ARG. */
+#define VQA_FLAG_BF16_ENCODER_GEMMS 0x40 /* = 64, the next free bit after VQA_PT_FLAG_BF16_ENCODER.  Opt-in on top of
+                                     * VQA_FLAG_BF16_GEMM, the VQA step only (vqa_dims_t.flags): the five
+                                     * single products of the question encoder join the routed list and run vqa_gemm_bf16 --
+                                     * the x-projection xp = x_tm wx_cat + bx_cat (bias added unrounded, in f32), dx =
+                                     * dxp wx_cat^T, dwx = x_tm^T dxp and both dwh (hs^T dxp_{r|u}, gru_rh^T dxp_c; with
+                                     * bit 1 of vqa_gru_h0skip_set_mode from the rows of step 1, and the memset where no
+                                     * step is left), each in its packed and in its two-GEMM form (VQA_HOT_XCAT=0, where
+                                     * the second dx product's f32 addend stays an addend).  Rounding points are those of
+                                     * vqa_gemm_bf16: both operands, round to nearest even, on their way into LDS.
+                                     * In the packed form row W of dwx (the constant-1 input) yields bias gradients summed
+                                     * from ROUNDED dxp; in the two-GEMM form the biases are vqa_colsum of the UNROUNDED dxp.
+                                     * NOT ROUTED: the recurrence, forward and backward, in every form (weight-stationary,
+                                     * live-prefix, row chains) -- given the same xp it computes bit for bit what it computes
+                                     * without the bit.  Accumulation, the tapes hs / gru_r / gru_u / gru_c / gru_rh, xp,
+                                     * dxp and x_tm, vqa_gru_pack_wx / vqa_gru_unpack_dwx_bias, the embedding scatter-add and
+                                     * the slice sum of squares stay f32.  The workspace layout is byte for byte that of
+                                     * VQA_FLAG_BF16_GEMM (whose "gemm_ws" already covers the bf16 split k of every encoder
+                                     * shape); with the bit clear every launch is the one it was.  Composes with
+                                     * VQA_FLAG_BF16_FEATURES, VQA_FLAG_DETERMINISTIC and the seeded keep sites.  Valid only
+                                     * with VQA_FLAG_BF16_GEMM (hence model types 0 and 1, no VQA_FLAG_FUSED_GATHER): without
+                                     * it vqa_fusion_workspace_bytes / _tensor / _forward / _backward / _backward_phases and
+                                     * vqa_fusion_gru_form return VQA_ERR_ARG, and nothing is launched.  In
+                                     * vqa_pretrain_dims_t.flags the bit is VQA_ERR_ARG in all four families: their switch
+                                     * is VQA_PT_FLAG_BF16_ENCODER, which includes the recurrence. */
 
 /* One FC(+LN) layer: weights [in,out], biases [out], LayerNorm beta/gamma [out] (NULL if no LN). */
 typedef struct { float *w, *b, *beta, *gamma; } vqa_fc_t;

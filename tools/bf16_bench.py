@@ -11,8 +11,15 @@ bf16 x 3 experiment, alternated in ONE process on one box:
       median of 20 steps repeated 5 times (the spread of X's own medians is the yardstick of the difference), then the
       five kernels of the mode in both forms: the two GEMMs that read V_ft, the gather, the three attention entry points
 
+  (f) --ab_encoder (this leg alone): the question encoder's five single products -- engine X (precision "bf16") against
+      engine Y (X + encoder "bf16-gemms") alternated step by step at the bench shape, medians of --step-iters steps repeated
+      --repeats times (the min - max of X's own medians is the yardstick), then the five products at their VQA shapes
+      (T B = 7168, W 300, H 1024) in both forms through ops.  --x-only times X alone and --lib PATH loads another build of
+      the library: X of this build against X of the parent's, in fresh processes
+
 usage: bf16_bench.py [--iters 20] [--step-iters 12] [--skip-ops] [--skip-step] [--skip-errors] [--step-precisions bf16]
        bf16_bench.py --ab_features [--iters 20] [--repeats 5]
+       bf16_bench.py --ab_encoder [--step-iters 20] [--repeats 5] [--iters 20] [--x-only] [--lib PATH]
 Every time is the median of the timed iterations after 3 warm-up iterations (device events); the achieved byte rate is
 the algorithmic traffic 4 (MK + KN + MN) over that time, as a fraction of the 6.3 TB/s a copy achieves on the MI355X."""
 import argparse
@@ -247,6 +254,84 @@ def bench_ab_features(iters, repeats):
     print("(every op call allocates its outputs inside the timed region, the same on both sides)")
 
 
+def bench_ab_encoder(step_iters, repeats, iters, x_only):
+    import bench as BENCH
+    from vqa_transfer_externaldata_amd import fusion as F
+    cfg = dict(BENCH.CFG)
+    dev = torch.device("cuda", 0)
+    params = BENCH.synth_params("vlmap_answer", cfg, seed=1234)
+    table, nbox, am, batches = BENCH.synth_inputs(cfg, seed=1234, device=dev)
+    B, T, W, H = cfg["B"], cfg["T"], cfg["W"], cfg["H"]
+    names = ("X",) if x_only else ("X", "Y")
+    engs = {}
+    for name in names:
+        kw = {"encoder": "bf16-gemms"} if name == "Y" else {}
+        e = F.FusionEngine(model_type="vlmap_answer", B=B, R=cfg["R"], D=cfg["D"], H=H, T=T, W=W, A=cfg["A"], Vq=cfg["Vq"],
+                           N_img=cfg["N_img"], params=params, device=dev, precision="bf16", **kw)
+        e.bind_inputs(table=table, nbox_table=nbox, answer_masks=am)
+        engs[name] = e
+    count = {n: 0 for n in names}
+
+    def step(name):
+        e, i = engs[name], count[name]
+        ka, kj = e.make_keep_masks(seed=99, step=i)
+        e.train_step(batches[i % len(batches)], ka, kj, 1e-3)
+        count[name] += 1
+
+    print("== (f) question encoder: X = precision bf16, Y = X + encoder bf16-gemms; vlmap_answer, bs %d, library %s"
+          % (B, ops._lib.lib_path()))
+    meds = {n: [] for n in names}
+    for r in range(repeats):
+        res = alternate_us([lambda n=n: step(n) for n in names], step_iters)
+        for n, (med, best) in zip(names, res):
+            meds[n].append(med)
+        print("repeat %d: " % r + "   ".join("%s median %.3f ms (best %.3f)" % (n, med / 1e3, best / 1e3) for n, (med, best) in zip(names, res))
+              + ("" if x_only else "   X / Y %.4f" % (res[0][0] / res[1][0])), flush=True)
+    mid = {n: sorted(meds[n])[repeats // 2] for n in names}
+    print("X: median of the %d medians %.3f ms, min - max of the medians %.3f - %.3f ms (spread %.1f us)"
+          % (repeats, mid["X"] / 1e3, min(meds["X"]) / 1e3, max(meds["X"]) / 1e3, max(meds["X"]) - min(meds["X"])), flush=True)
+    if x_only:
+        return
+    spread = max(meds["X"]) - min(meds["X"])
+    print("Y: median of the %d medians %.3f ms, min - max %.3f - %.3f ms; X - Y = %.1f us"
+          % (repeats, mid["Y"] / 1e3, min(meds["Y"]) / 1e3, max(meds["Y"]) / 1e3, mid["X"] - mid["Y"]))
+    print("verdict: Y is %s" % ("faster than X by more than X's own spread" if mid["X"] - mid["Y"] > spread else
+                                "NOT faster than X by more than X's own spread"), flush=True)
+    print("loss after %d steps each: X %.5f, Y %.5f" % (count["X"], engs["X"].report()["answer_train_loss"],
+                                                        engs["Y"].report()["answer_train_loss"]), flush=True)
+    del engs
+    torch.cuda.empty_cache()
+
+    # ---- the five products at their VQA shapes, operands laid out as the step's (x_tm rows of x_stride(W), dxp columns)
+    print("== (f) products at T B = %d, W %d, H %d: f32 MFMA | bf16 operands, alternated, median us (best us)" % (T * B, W, H))
+    g = torch.Generator(device=dev).manual_seed(7)
+    TB, Wp = T * B, (W + 1 + 3) // 4 * 4
+    x_tm = torch.randn(TB, Wp, generator=g, device=dev)
+    x_tm[:, W] = 1
+    x_tm[:, W + 1:] = 0
+    wx, bx = torch.randn(W, 3 * H, generator=g, device=dev) * 0.05, torch.randn(3 * H, generator=g, device=dev) * 0.05
+    dxp = torch.randn(TB, 3 * H, generator=g, device=dev) * 1e-3
+    hs, rh = torch.tanh(torch.randn(TB, H, generator=g, device=dev)), torch.tanh(torch.randn(TB, H, generator=g, device=dev))
+    prods = [("x-projection NN %d x %d x %d" % (TB, 3 * H, W), x_tm[:, :W], wx, False, False, bx),
+             ("dx          NT %d x %d x %d" % (TB, W, 3 * H), dxp, wx, False, True, None),
+             ("dwx         TN %d x %d x %d" % (Wp, 3 * H, TB), x_tm, dxp, True, False, None),
+             ("dwh gates   TN %d x %d x %d" % (H, 2 * H, TB), hs, dxp[:, :2 * H], True, False, None),
+             ("dwh cand.   TN %d x %d x %d" % (H, H, TB), rh, dxp[:, 2 * H:], True, False, None)]
+    tot = [0.0, 0.0]
+    for name, A, Bm, tA, tB, bias in prods:
+        M = A.shape[1] if tA else A.shape[0]
+        N = Bm.shape[0] if tB else Bm.shape[1]
+        o32, o16 = torch.empty(M, N, device=dev), torch.empty(M, N, device=dev)
+        (m32, b32), (m16, b16) = alternate_us([lambda: ops.gemm(A, Bm, transA=tA, transB=tB, bias=bias, out=o32),
+                                               lambda: ops.gemm_bf16(A, Bm, transA=tA, transB=tB, bias=bias, out=o16)], iters)
+        tot[0] += m32
+        tot[1] += m16
+        print("%-38s f32 %7.1f (%7.1f) | bf16 %7.1f (%7.1f) | f32 / bf16 = %.2fx%s"
+              % (name, m32, b32, m16, b16, m32 / m16, "   <- SLOWER in bf16" if m16 > m32 else ""), flush=True)
+    print("sum of the five medians: f32 %.1f us, bf16 %.1f us (every op call allocates its split-k workspace inside the timed "
+          "region, the same on both sides)" % tuple(tot), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -257,12 +342,20 @@ def main():
     ap.add_argument("--step-precisions", nargs="+", default=["f32", "bf16"], choices=["f32", "bf16"],
                     help="the engines of part (c); one name = that step alone (for a kernel trace)")
     ap.add_argument("--ab_features", action="store_true", help="leg (e) alone: f32 against bf16 feature table")
-    ap.add_argument("--repeats", type=int, default=5, help="repeated medians of leg (e)")
+    ap.add_argument("--repeats", type=int, default=5, help="repeated medians of legs (e) and (f)")
+    ap.add_argument("--ab_encoder", action="store_true", help="leg (f) alone: encoder f32 against bf16-gemms in the bf16 step")
+    ap.add_argument("--x-only", action="store_true", help="leg (f): time X alone (with --lib: another build's X)")
+    ap.add_argument("--lib", type=str, default=None, help="load this build of the library instead of the package's")
     args = ap.parse_args()
+    if args.lib:
+        ops._lib._LIB_PATH = os.path.abspath(args.lib)
     if not torch.cuda.is_available():
         raise SystemExit("bf16_bench.py needs a GPU: a time taken elsewhere says nothing")
     if args.ab_features:
         bench_ab_features(args.iters, args.repeats)
+        return
+    if args.ab_encoder:
+        bench_ab_encoder(max(args.step_iters, 10), args.repeats, args.iters, args.x_only)
         return
     if not args.skip_errors:
         bench_errors()

@@ -69,7 +69,8 @@ def parse_header(text):
     """(structs, signatures, defines) of a header text: {typedef name: Structure class} in declaration order,
     {function: (restype, [argtypes])}, {VQA_* macro: int}.  Anything it does not understand raises VqaHotError."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VQA_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    defines = {k: int(v, 0) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VQA_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|0|[1-9]\d*))[ \t]*$",
+                                                   text, re.M)}      # decimal or hexadecimal integer macros
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
     structs, signatures, pos = {}, {}, 0
     while text[pos:].strip():

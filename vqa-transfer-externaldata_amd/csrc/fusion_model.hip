@@ -28,6 +28,7 @@ inline bool has_tuned_head(int mt) { return mt == VQA_MODEL_VQA_ALL2 || mt == VQ
 inline bool train_loss_masked(int mt) { return mt != VQA_MODEL_STANDARD; }      // train loss masked by the train-answer mask
 inline bool bf16_routed(int mt) { return mt == VQA_MODEL_VLMAP_ANSWER || mt == VQA_MODEL_STANDARD; }      // every dense product on VQA_FLAG_BF16_GEMM's routed list
 inline bool feat16(const vqa_dims_t& d) { return (d.flags & VQA_FLAG_BF16_FEATURES) != 0; }      // table and V_ft are bf16 patterns
+inline bool enc16(const vqa_dims_t& d) { return (d.flags & VQA_FLAG_BF16_ENCODER_GEMMS) != 0; }      // the encoder's five single products are routed
 
 void legacy_vqa_layout(Layout& L, const vqa_dims_t& d, int64_t& gw);      // csrc/legacy_vqa.inc (model_type 13)
 
@@ -381,8 +382,8 @@ bool fork_side(const Ctx& c, Side& sd) {
 bool join_side_record(Side& sd) { return hipEventRecord(sd.join, sd.s) == hipSuccess; }
 
 
-// The f32 MFMA product, whatever the flags say: the question encoder's sites (x-projection, dx, dwx, dwh) call this one
-// (include/vqa_hot.h, VQA_FLAG_BF16_GEMM: the unrouted list).
+// The f32 MFMA product, whatever the flags say: without VQA_FLAG_BF16_ENCODER_GEMMS the question encoder's sites
+// (x-projection, dx, dwx, dwh) call this one (include/vqa_hot.h, VQA_FLAG_BF16_GEMM: the unrouted list).
 int gemm_f32(const Ctx& c, int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B,
              int ldb, float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) {
     // side-stream GEMMs: one workgroup per CU (persistent), so the recurrence on the caller's
@@ -412,7 +413,16 @@ int gemm_x(const Ctx& c, int tA, int64_t M, int64_t N, int64_t K, const float* x
 int colsum(const Ctx& c, const float* X, int64_t M, int64_t N, int ldx, float* out) {
     return vqa_colsum(X, (int)M, (int)N, ldx, out, c.colsum_ws(), c.colsum_ws_floats(), c.st);
 }
+// The question encoder's single products (x-projection, dx, dwx, both dwh; never the recurrence): the dense layers' routed
+// product under VQA_FLAG_BF16_ENCODER_GEMMS (which implies VQA_FLAG_BF16_GEMM, dims_ok: lane scratch and the side
+// stream's max_blocks as for them), else the f32 product, launch for launch what it was.
+int gemm_enc(const Ctx& c, int tA, int tB, int64_t M, int64_t N, int64_t K, const float* A, int lda, const float* B,
+             int ldb, float* C, int ldc, const float* bias = nullptr, const float* D = nullptr, int ldd = 0) {
+    return enc16(c.d) ? gemm(c, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd)
+                      : gemm_f32(c, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, D, ldd);
+}
 auto f32(const Ctx& c) { return [&c](auto... a) { return gemm_f32(c, a...); }; }      // gemm_f32 on c as a callable (gru_encoder.h)
+auto enc(const Ctx& c) { return [&c](auto... a) { return gemm_enc(c, a...); }; }      // gemm_enc likewise: the question encoder's sites
 GruCell fw_cell(const vqa_params_t* p) { return {p->gru_wg, p->gru_bg, p->gru_wc, p->gru_bc}; }
 GruCell bw_cell(const vqa_params_t* p) { return {p->gru_bw_wg, p->gru_bw_bg, p->gru_bw_wc, p->gru_bw_bc}; }      // model_type 12
 
@@ -426,6 +436,8 @@ bool dims_ok(const vqa_dims_t* d) {
     if ((d->flags & VQA_FLAG_BF16_FEATURES) && !(d->flags & VQA_FLAG_BF16_GEMM)) return false;
     // the bf16 sequence encoder is the pre-training steps' (this step's recurrence is the weight-stationary launch)
     if (d->flags & VQA_PT_FLAG_BF16_ENCODER) return false;
+    // this step's switch for the encoder's single products: only inside the bf16 mode, like the bf16 table
+    if (enc16(*d) && !(d->flags & VQA_FLAG_BF16_GEMM)) return false;
     if (d->model_type == VQA_MODEL_LEGACY_VQA)      // 16-byte rows everywhere; the scoring kernel keeps one H-row in LDS
         return d->map_dim > 0 && d->La > 0 && d->H % 4 == 0 && d->D % 4 == 0 && d->map_dim % 4 == 0 && d->W % 4 == 0 && d->H <= 1024 && d->Vq > 3;
     if (d->model_type == VQA_MODEL_BI) return d->H % 8 == 0;      // two cells of H / 2 units, 16-byte rows each
@@ -838,10 +850,10 @@ int fwd_question(Step& s) {
         ProbeScope ps("gru.xp_gemm", c.st);
         if (xcat_enabled()) {
             TRY(e.pack_wx());
-            TRY(e.project(f32(c)));
+            TRY(e.project(enc(c)));
         } else {
-            TRY(gemm_f32(c, 0, 0, T * B, 2 * H, W, e.x_tm, e.ldx(), P->gru_wg, (int)(2 * H), e.xp, (int)(3 * H), P->gru_bg));
-            TRY(gemm_f32(c, 0, 0, T * B, H, W, e.x_tm, e.ldx(), P->gru_wc, (int)H, e.xp + 2 * H, (int)(3 * H), P->gru_bc));
+            TRY(gemm_enc(c, 0, 0, T * B, 2 * H, W, e.x_tm, e.ldx(), P->gru_wg, (int)(2 * H), e.xp, (int)(3 * H), P->gru_bg));
+            TRY(gemm_enc(c, 0, 0, T * B, H, W, e.x_tm, e.ldx(), P->gru_wc, (int)H, e.xp + 2 * H, (int)(3 * H), P->gru_bc));
         }
     }
     // ... then the recurrence
@@ -1386,10 +1398,10 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
             // wx_cat: the forward's packed copy of the x rows still sits in the workspace (backward follows the forward of the
             // same step on the same weights: every gradient here is meaningless otherwise); VQA_HOT_REPACK=1 packs it again
             if (repack_enabled()) TRY(e.pack_wx());
-            TRY(e.dx(f32(c), dx));
+            TRY(e.dx(enc(c), dx));
         } else {
-            TRY(gemm_f32(c, 0, 1, T * B, W, 2 * H, e.dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
-            TRY(gemm_f32(c, 0, 1, T * B, W, H, e.dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
+            TRY(gemm_enc(c, 0, 1, T * B, W, 2 * H, e.dxp, (int)(3 * H), P->gru_wg, (int)(2 * H), dx, (int)W));
+            TRY(gemm_enc(c, 0, 1, T * B, W, H, e.dxp + 2 * H, (int)(3 * H), P->gru_wc, (int)H, dx, (int)W, nullptr, dx, (int)W));
         }
     }
     ProbeScope ps_embed("embed.bwd", c.st);
@@ -1404,7 +1416,8 @@ int bwd_bptt(const Step& s, float* embed_slice_sq) {
 // Phases 4 and 8 of one cell e with gradients g (frozen: nothing).  packed: the x rows and biases of both kernels come out of
 // one GEMM into dwx_cat; else fusion's two-GEMM form (VQA_HOT_XCAT=0).  The recurrent weight gradients (gru.dwh_gemm) start
 // at the tape's rows of step t0: those of t = 0 are h_0 (gate kernel) or r * h_0 (candidate kernel), zeros since the forward
-// cleared hs[0], and bit 1 of h0skip_mode() leaves them out for the question encoder.
+// cleared hs[0], and bit 1 of h0skip_mode() leaves them out for the question encoder.  Every product here is the
+// encoder's (enc(c)): bf16 operands under VQA_FLAG_BF16_ENCODER_GEMMS, which the bi-directional model never carries.
 int bwd_gru_weights(const Ctx& c, const GruTape& e, const GruCell& g, int phases, bool packed, int t0) {
     const int64_t TB = e.T * e.B, H = e.H, W = e.W;
     const int ld3 = (int)(3 * H);
@@ -1415,25 +1428,25 @@ int bwd_gru_weights(const Ctx& c, const GruTape& e, const GruCell& g, int phases
         {
             ProbeScope ps("gru.dwx_gemm", c.st);
             if (packed) {
-                TRY(e.dwx(f32(c)));
+                TRY(e.dwx(enc(c)));
                 TRY(e.unpack_dwx(g));
             } else {
-                TRY(gemm_f32(c, 1, 0, W, 2 * H, TB, e.x_tm, e.ldx(), e.dxp, ld3, g.wg, (int)(2 * H)));
+                TRY(gemm_enc(c, 1, 0, W, 2 * H, TB, e.x_tm, e.ldx(), e.dxp, ld3, g.wg, (int)(2 * H)));
                 TRY(colsum(c, e.dxp, TB, 2 * H, ld3, g.bg));
             }
         }
         ProbeScope ps("gru.dwh_gemm", c.st);
-        TRY(e.dwh(f32(c), g, false, t0));
+        TRY(e.dwh(enc(c), g, false, t0));
     }
     // phase 8: the candidate kernel's weight and bias gradients (its x rows and bias only in the two-GEMM form)
     if (phases & 8) {
         if (!packed) {
             ProbeScope ps("gru.dwx_gemm", c.st);
-            TRY(gemm_f32(c, 1, 0, W, H, TB, e.x_tm, e.ldx(), e.dxp + 2 * H, ld3, g.wc, (int)H));
+            TRY(gemm_enc(c, 1, 0, W, H, TB, e.x_tm, e.ldx(), e.dxp + 2 * H, ld3, g.wc, (int)H));
             TRY(colsum(c, e.dxp + 2 * H, TB, H, ld3, g.bc));
         }
         ProbeScope ps("gru.dwh_gemm", c.st);
-        TRY(e.dwh(f32(c), g, true, t0));
+        TRY(e.dwh(enc(c), g, true, t0));
     }
     return VQA_OK;
 }

@@ -105,7 +105,8 @@ inline bool enc16(const vqa_pretrain_dims_t& d) { return (d.flags & VQA_PT_FLAG_
 bool dims_ok(const vqa_pretrain_dims_t* d) {
     return d && d->B > 0 && d->n > 0 && d->n <= 8 && d->R > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->A > 0 &&
            d->Vq > 0 && d->n_ws > 0 && d->L > 0 && d->H % 4 == 0 && d->D % 4 == 0 &&
-           (!(feat16(*d) || enc16(*d)) || (d->flags & VQA_FLAG_BF16_GEMM));
+           (!(feat16(*d) || enc16(*d)) || (d->flags & VQA_FLAG_BF16_GEMM)) &&
+           !(d->flags & VQA_FLAG_BF16_ENCODER_GEMMS);      // the VQA step's switch: these steps' is VQA_PT_FLAG_BF16_ENCODER
 }
 
 struct Ctx : Workspace {

@@ -34,6 +34,9 @@ def build_parser():
                         help="bf16: the dense layers' products with bf16 operands in the matrix unit (not in the reference)")
     parser.add_argument("--features", type=str, default="f32", choices=["f32", "bf16"],
                         help="bf16 (only with --precision bf16): the region-feature table lives in HBM as bf16")
+    parser.add_argument("--encoder", type=str, default="f32", choices=["f32", "bf16-gemms"],
+                        help="bf16-gemms (only with --precision bf16): the question encoder's x-projection with bf16 "
+                             "operands too; the recurrence stays f32")
     parser.add_argument("--inline_dropout", action="store_true", default=False,
                         help="draw the dropout keep bits inside the kernels that consume them (the same bits as the mask buffers)")
     parser.add_argument("--debug", type=int, default=0, help="0: normal, 1: debug")

@@ -201,6 +201,9 @@ _FLAGS = (("--image_dir", dict(type=str, default="data/VQA_v2/images")),
                                help="bf16: the dense layers' products with bf16 operands in the matrix unit (not in the reference)")),
           ("--features", dict(type=str, default="f32", choices=["f32", "bf16"],
                               help="bf16 (only with --precision bf16): the region-feature table lives in HBM as bf16")),
+          ("--encoder", dict(type=str, default="f32", choices=["f32", "bf16-gemms"],
+                             help="bf16-gemms (only with --precision bf16): the question encoder's x-projection with bf16 "
+                                  "operands too; the recurrence stays f32")),
           ("--inline_dropout", dict(action="store_true", default=False,
                                     help="draw the dropout keep bits inside the kernels that consume them (the same bits as the mask buffers)")),
           ("--debug", dict(type=int, default=0, help="0: normal, 1: debug")),

@@ -81,6 +81,9 @@ KEEP_SITES = (
 PRECISIONS = ("f32", "bf16")
 BF16_MODEL_TYPES = ("vlmap_answer", "standard")       # include/vqa_hot.h, VQA_FLAG_BF16_GEMM
 FEATURE_FORMATS = ("f32", "bf16")                     # FusionEngine(features=...): the feature table at rest
+# FusionEngine(encoder=...): the products of the question encoder.  Not "bf16": PretrainEngine(encoder="bf16") includes the
+# recurrence, and this mode routes the five single GEMMs only.
+ENCODER_FORMATS = ("f32", "bf16-gemms")
 
 
 def scope_names(model_type):
@@ -269,8 +272,15 @@ class FusionEngine(EngineCore):
     def __init__(self, *, model_type, B, R, D, H, T, W, A, Vq, N_img, params, device="cuda:0",
                  keep_att=0.8, keep_joint=0.5, global_batch=None, deterministic=None, answer_glove=None,
                  fused_gather=False, num_marginal=NUM_MARGINAL, ent_cols=None, map_dim=None, ft_vlmap=False,
-                 glove_fixed=None, answers=None, precision="f32", features="f32"):
-        """features="bf16" (opt-in, only with precision="bf16"): the region-feature table is bf16 at rest -- bind_inputs
+                 glove_fixed=None, answers=None, precision="f32", features="f32", encoder="f32"):
+        """encoder="bf16-gemms" (opt-in, only with precision="bf16"): the five single products of the question encoder --
+        the x-projection, dx, dwx and both dwh -- round both operands to bf16 on their way into the matrix unit like the
+        dense layers' (VQA_FLAG_BF16_ENCODER_GEMMS).  NOT routed: the recurrence, forward and backward, in every form; given
+        the same projection it computes bit for bit what it computes with encoder="f32".  The tapes, dxp, x_tm, accumulation,
+        the bias add, the embedding scatter-add and everything that is not a GEMM stay f32; the bias gradients of the packed
+        form are summed from rounded dxp.  Same workspace layout, checkpoints and data-parallel wire format as
+        precision="bf16".  Composes with features="bf16", deterministic and the seeded dropout.
+        features="bf16" (opt-in, only with precision="bf16"): the region-feature table is bf16 at rest -- bind_inputs
         takes a torch.bfloat16 table [N,R,D] (model_vlmap_answer.features_to_bf16 makes one), the gathered V_ft is bf16 in
         the workspace, and v_linear_v's forward and dW GEMMs and the attention kernels read it as it is
         (VQA_FLAG_BF16_FEATURES).  Half the resident feature memory and half the traffic of the step's largest stream; the
@@ -306,9 +316,14 @@ class FusionEngine(EngineCore):
             raise ValueError("features must be one of %s, not %r" % (FEATURE_FORMATS, features))
         if features == "bf16" and precision != "bf16":
             raise ValueError("features='bf16' needs precision='bf16' (the f32 products read an f32 table)")
-        # (features='bf16' with fused_gather or another model type: refused above, as precision='bf16' is)
+        if encoder not in ENCODER_FORMATS:
+            raise ValueError("encoder must be one of %s, not %r" % (ENCODER_FORMATS, encoder))
+        if encoder == "bf16-gemms" and precision != "bf16":
+            raise ValueError("encoder='bf16-gemms' needs precision='bf16' (it puts the encoder's products on the routed list)")
+        # (features='bf16' / encoder='bf16-gemms' with fused_gather or another model type: refused above, as precision='bf16' is)
         self.precision = precision
         self.features = features
+        self.encoder = encoder
         self.device = torch.device(device)
         self.model_type = model_type
         self.sc = scope_names(model_type)
@@ -319,7 +334,8 @@ class FusionEngine(EngineCore):
                               flags=(_lib.FLAG_DETERMINISTIC if deterministic else 0) |
                                     (_lib.FLAG_FUSED_GATHER if fused_gather else 0) |
                                     (_lib.FLAG_BF16_GEMM if precision == "bf16" else 0) |
-                                    (_lib.FLAG_BF16_FEATURES if features == "bf16" else 0),
+                                    (_lib.FLAG_BF16_FEATURES if features == "bf16" else 0) |
+                                    (_lib.FLAG_BF16_ENCODER_GEMMS if encoder == "bf16-gemms" else 0),
                               num_marginal=int(num_marginal) if model_type == "vlmap_answer_ent" else 0,
                               ent_cols=int(ent_cols or A) if model_type == "vlmap_answer_ent" else 0,
                               extra_weight={"vlmap_answer_ent": W_ENTROPY, "vlmap_answer_full": LATENT_LOSS_WEIGHT}.get(model_type, 0.0))

@@ -308,7 +308,8 @@ class Model(object):
                              params=self._initial_params(shapes), device=self.device,
                              global_batch=getattr(self.config, "global_batch", None),
                              precision=getattr(self.config, "precision", "f32"),
-                             features=getattr(self.config, "features", "f32"), **self._engine_kwargs())
+                             features=getattr(self.config, "features", "f32"),
+                             encoder=getattr(self.config, "encoder", "f32"), **self._engine_kwargs())
         eng.bind_inputs(
             # the whole table lives in HBM (a1): f32, or rounded to bf16 slice by slice on its way up (--features bf16)
             table=(features_to_bf16(self.features, self.device) if eng.features == "bf16"

@@ -111,7 +111,8 @@ class Model(_Base):
                              A=self.num_answer, Vq=Vq, N_img=len(self.features), params=p, device=self.device,
                              global_batch=getattr(cfg, "global_batch", None), map_dim=MAP_DIM, ft_vlmap=self.ft_vlmap,
                              glove_fixed=fixed, answers={"intseq": self.answer_intseq_value, "len": self.answer_intseq_len_value},
-                             precision=getattr(cfg, "precision", "f32"), features=getattr(cfg, "features", "f32"))
+                             precision=getattr(cfg, "precision", "f32"), features=getattr(cfg, "features", "f32"),
+                             encoder=getattr(cfg, "encoder", "f32"))
         eng.bind_inputs(table=self._to_dev(self.features, torch.float32), nbox_table=self._to_dev(self.num_boxes, torch.int32),
                         answer_masks={"train": self._to_dev(self.train_answer_mask, torch.float32),
                                       "obj": self._to_dev(self.obj_answer_mask, torch.float32),

@@ -330,6 +330,9 @@ def build_parser():
     parser.add_argument("--features", type=str, default="f32", choices=["f32", "bf16"],
                         help="bf16 (only with --precision bf16): the region-feature table is rounded to bf16 once at load and "
                              "kept in HBM as bf16 -- half the feature memory and gather traffic; the feature file stays f32")
+    parser.add_argument("--encoder", type=str, default="f32", choices=["f32", "bf16-gemms"],
+                        help="bf16-gemms (only with --precision bf16): the question encoder's five single products "
+                             "(x-projection, dx, dwx, both dwh) with bf16 operands too; the recurrence stays f32")
     parser.add_argument("--inline_dropout", action="store_true", default=False,
                         help="draw the dropout keep bits inside the kernels that consume them instead of writing mask "
                              "buffers first: the same bits, so the same results (not in the reference)")

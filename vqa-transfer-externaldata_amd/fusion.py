@@ -562,6 +562,9 @@ class FusionEngine(EngineCore):
         keep_word: vlmap_finetune / vlmap_only -- keep-mask [B, T, H] of the word attention's dropout (make_keep_mask_word)"""
         self._bs = self._batch_struct(batch, keep_att, keep_joint, keep_joint2, noise, keep_tile, keep_word, dropout,
                                       row_offset, global_rows)
+        self._micro_report = None     # the report functions speak of THIS batch again (train_micro_steps sets it after its last)
+        if not getattr(self, "_in_micro_step", False) or getattr(self, "_first_of_micro_step", True):
+            self._ws_err_carried = False       # (an error word carried over a resize belongs to an earlier step)
         _lib.check(self.lib.vqa_fusion_forward(C.byref(self.dims), C.byref(self._p_struct), C.byref(self._bs),
                                                C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
                                                1 if want_dz else 0, self._stream()), "vqa_fusion_forward")
@@ -592,6 +595,86 @@ class FusionEngine(EngineCore):
                      keep_word=keep_word, dropout=dropout, row_offset=row_offset, global_rows=global_rows)
         self._backward_and_step(lr, allreduce)
 
+    # ------------------------------------------------------------------ micro-batched step (EngineCore.train_micro_steps)
+    # micro[i] = {"batch": ..., keep_att=, keep_joint=, keep_joint2=, noise=, keep_tile=, keep_word= | dropout=(seed, step)}
+    def _micro_rows(self, m):
+        return int(m["batch"]["q_intseq"].shape[0])
+
+    def _micro_open(self, micro, G, dp, allreduce, global_valid=None):
+        """what the step leaves as it found it: the engine's own 1/global batch"""
+        if global_valid is not None:
+            raise ValueError("global_valid belongs to the pre-training step; this one scales by 1 / the global batch")
+        d = self.dims
+        self._in_micro_step = len(micro) > 1
+        return {"B": d.B, "T": d.T, "inv": d.inv_global_batch, "ran": 0}
+
+    def _micro_forward(self, m, row_offset, G, ctx):
+        m = dict(m)
+        batch = m.pop("batch")
+        B, T = (int(x) for x in batch["q_intseq"].shape)
+        d = self.dims
+        if (B, T) != (d.B, d.T):
+            if ctx["ran"]:
+                # resize() relocates and zeroes the recurrence's sticky error word: what the micro-batches before this one
+                # left in it is carried to check_recurrence
+                self._carry_recurrence_word()
+            self.resize(B, T, global_batch=G)
+        elif C.c_float(1.0 / G).value != d.inv_global_batch:
+            self.drop_graphs()        # (captured graphs hold the dims by value)
+            d.inv_global_batch = 1.0 / float(G)
+        self._first_of_micro_step = ctx["ran"] == 0
+        ctx["ran"] += 1
+        self.forward(batch, want_dz=True, row_offset=row_offset, global_rows=G, **m)
+
+    def _micro_stats(self):
+        """this micro-batch's rows of the per-sample statistics, summed: what a rank all-reduces in report(global_rows=...)"""
+        return self.tensor("stats").view(self.dims.B, 16).sum(0)
+
+    def _micro_close(self, ctx):
+        d = self.dims
+        self._in_micro_step = False
+        d.inv_global_batch = ctx["inv"] if (d.B, d.T) == (ctx["B"], ctx["T"]) else 1.0 / float(d.B)
+
+    def _carry_recurrence_word(self):
+        """keeps the recurrence's error word of the micro-batches that ran so far in this step beside the word a resize is
+        about to relocate.  _ws_err_carried says whether the kept word counts: any forward outside a micro-batched step,
+        and the first one inside, drop it without a launch (forward)."""
+        if getattr(self, "_ws_err_word", None) is None or self._ws_err_word is False:
+            return
+        if getattr(self, "_ws_err_carry", None) is None:
+            self._ws_err_carry = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if getattr(self, "_ws_err_carried", False):
+            self._ws_err_carry.bitwise_or_(self._ws_err_word)
+        else:
+            self._ws_err_carry.copy_(self._ws_err_word)
+            self._ws_err_carried = True
+
+    def _micro_mean_stats(self, global_rows=None, group=None):
+        """the 16 per-sample statistics of the last micro-batched step, meaned over its global batch; under data
+        parallelism the accumulator is SUM-all-reduced first (once per step, whichever report function asks first)"""
+        import torch.distributed as dist
+        mr = self._micro_report
+        if mr["mean"] is None:
+            s = mr["stats"]
+            group = group if group is not None else mr["group"]
+            if (mr["dp"] or global_rows is not None) and dist.is_initialized() and dist.get_world_size(group) > 1:
+                if dist.get_backend(group) == "gloo":
+                    h = s.cpu()
+                    dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+                    s = h.to(self.device)
+                else:
+                    s = s.clone()
+                    dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group)
+            mr["mean"] = (s / float(mr["G"])).contiguous()
+        return mr["mean"]
+
+    def _finish_report(self, mean):
+        """the 13 scalars from meaned statistics, by the kernel that finishes every report (vqa_report_reduce)"""
+        out = torch.zeros(16, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.vqa_report_reduce(C.c_void_p(mean.data_ptr()), 1, C.c_void_p(out.data_ptr()),
+                                              self._stream()), "vqa_report_reduce")
+        return out
+
     # ------------------------------------------------------------------ whole step as one hipGraph replay
     def train_step_graph(self, batch, lr, seed, step, dropout=None):
         """One train step = refresh the step's inputs in place + ONE vqa_graph_launch.
@@ -609,6 +692,10 @@ class FusionEngine(EngineCore):
         if dropout is not None:
             raise ValueError("train_step_graph keeps explicit dropout masks: seed and offsets of a seeded step are by-value "
                              "kernel arguments, which a graph replay cannot advance")
+        if not hasattr(batch, "get"):
+            raise ValueError("train_step_graph replays ONE captured forward/backward pair: a sequence of micro-batches "
+                             "takes the eager train_micro_steps")
+        self._micro_report = None
         d = self.dims
         live = batch.get("live_rows")
         live_key = None if live is None else tuple(int(x) for x in np.asarray(live))
@@ -702,7 +789,10 @@ class FusionEngine(EngineCore):
             self._reset_recurrence_word()
         if self._ws_err_word is None:
             return
-        if self._ws_err_word is not False and int(self._ws_err_word.item()) != 0:
+        # micro-batches of another shape, earlier in the step that ran last
+        carried = self._ws_err_carry if getattr(self, "_ws_err_carried", False) else None
+        if (self._ws_err_word is not False and int(self._ws_err_word.item()) != 0) or \
+                (carried is not None and int(carried.item()) != 0):
             raise _lib.VqaHotError("the persistent GRU recurrence timed out waiting for its workgroups (is another process "
                                    "computing on this GPU?): results of this step are invalid; VQA_HOT_GRU_WS=0 selects the "
                                    "per-step kernels")
@@ -714,7 +804,9 @@ class FusionEngine(EngineCore):
         the same kernel -- every rank then reports what one process on the whole batch would."""
         import torch.distributed as dist
         self.check_recurrence()
-        if global_rows is None or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        if getattr(self, "_micro_report", None) is not None:      # after train_micro_steps: the step's global batch
+            r = self._finish_report(self._micro_mean_stats(global_rows, group))[:13].cpu().numpy()
+        elif global_rows is None or not dist.is_initialized() or dist.get_world_size(group) == 1:
             r = self.tensor("report")[:13].cpu().numpy()
         else:
             d = self.dims
@@ -725,11 +817,7 @@ class FusionEngine(EngineCore):
                 s = h.to(self.device)
             else:
                 dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group)
-            mean = (s / float(global_rows)).contiguous()
-            out = torch.zeros(16, dtype=torch.float32, device=self.device)
-            _lib.check(self.lib.vqa_report_reduce(C.c_void_p(mean.data_ptr()), 1, C.c_void_p(out.data_ptr()),
-                                                  self._stream()), "vqa_report_reduce")
-            r = out[:13].cpu().numpy()
+            r = self._finish_report((s / float(global_rows)).contiguous())[:13].cpu().numpy()
         return {self.lib.vqa_report_key(i).decode(): float(r[i]) for i in range(13)}
 
     EXTRA_REPORT_KEYS = {"vlmap_answer_full": ("latent_loss", "train_latent_loss"),       # vqa/model_vlmap_answer_full.py:222-223
@@ -743,6 +831,9 @@ class FusionEngine(EngineCore):
         if keys is None:
             return {}
         import torch.distributed as dist
+        if getattr(self, "_micro_report", None) is not None:
+            a, e = (float(x) for x in self._micro_mean_stats(global_rows, group)[[0, 15]].cpu())
+            return {keys[0]: e, keys[1]: self.dims.extra_weight * e, "total_loss": a + self.dims.extra_weight * e}
         if global_rows is None or not dist.is_initialized() or dist.get_world_size(group) == 1:
             r = self.tensor("report")[13:16].cpu().numpy()
             return {keys[0]: float(r[0]), keys[1]: float(r[1]), "total_loss": float(r[2])}
@@ -758,7 +849,13 @@ class FusionEngine(EngineCore):
         return {keys[0]: e, keys[1]: d.extra_weight * e, "total_loss": a + d.extra_weight * e}
 
     def loss(self):
-        """the scalar optimize_loss minimises: sum of the model's `losses` (vqa/model_vlmap_answer.py:304-306)"""
+        """the scalar optimize_loss minimises: sum of the model's `losses` (vqa/model_vlmap_answer.py:304-306); after
+        train_micro_steps the global batch's"""
+        if getattr(self, "_micro_report", None) is not None:
+            mean = self._micro_mean_stats()
+            if self.model_type in self.EXTRA_REPORT_KEYS:
+                return mean[0] + self.dims.extra_weight * mean[15]
+            return self._finish_report(mean)[0]
         return self.tensor("report")[15 if self.model_type in self.EXTRA_REPORT_KEYS else 0]
 
     def keep_sites(self):

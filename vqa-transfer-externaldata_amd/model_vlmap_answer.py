@@ -370,6 +370,25 @@ class Model(object):
         mask is left out under config.inline_dropout, like the common ones"""
         return {}
 
+    def _step_inputs(self, eng, row_offset, gb):
+        """FusionEngine.forward's dropout and variant keywords for the batch the engine is sized for, at this model's
+        position of the (seed, step) stream and the batch's place (row_offset, gb) in the global batch"""
+        seed = int(getattr(self.config, "seed", 123))
+        kj2 = seeded = None
+        if getattr(self.config, "dropout_off", False):
+            ka = kj = None
+        elif getattr(self.config, "inline_dropout", False):
+            # the same bits, drawn inside the kernels that consume them (FusionEngine.forward(dropout=...)): no mask buffers
+            ka = kj = None
+            seeded = dict(dropout=(seed, self._step), row_offset=row_offset, global_rows=gb)
+        else:   # tf.nn.dropout is applied unconditionally in the reference (also at eval time)
+            # under data parallelism the stream is indexed by the global row (config.shard_row_offset, global_batch)
+            ka, kj = eng.make_keep_masks(seed, self._step, row_offset=row_offset, global_rows=gb)
+            if self.MODEL_TYPE in F.NOC_FAMILY:
+                kj2 = eng.make_keep_mask_joint2(seed, self._step, row_offset=row_offset, global_rows=gb)
+        extra_in = self._variant_inputs(eng, seed, row_offset, gb, bool(getattr(self.config, "dropout_off", False)))
+        return dict(keep_att=ka, keep_joint=kj, keep_joint2=kj2, **extra_in, **(seeded or {}))
+
     def build(self):
         """build network architecture and loss (here: run it on self.batch)"""
         db = self._device_batch()
@@ -380,28 +399,11 @@ class Model(object):
         else:
             self._engine.resize(B, T, gb)
         eng = self._engine
-        kj2 = seeded = None
-        if getattr(self.config, "dropout_off", False):
-            ka = kj = None
-        elif getattr(self.config, "inline_dropout", False):
-            # the same bits, drawn inside the kernels that consume them (FusionEngine.forward(dropout=...)): no mask buffers
-            ka = kj = None
-            seeded = dict(dropout=(int(getattr(self.config, "seed", 123)), self._step),
-                          row_offset=int(getattr(self.config, "shard_row_offset", 0) or 0), global_rows=gb)
-        else:   # tf.nn.dropout is applied unconditionally in the reference (also at eval time)
-            # under data parallelism the stream is indexed by the global row (config.shard_row_offset, global_batch)
-            ka, kj = eng.make_keep_masks(int(getattr(self.config, "seed", 123)), self._step,
-                                         row_offset=int(getattr(self.config, "shard_row_offset", 0) or 0),
-                                         global_rows=gb)
-            if self.MODEL_TYPE in F.NOC_FAMILY:
-                kj2 = eng.make_keep_mask_joint2(int(getattr(self.config, "seed", 123)), self._step,
-                                                row_offset=int(getattr(self.config, "shard_row_offset", 0) or 0), global_rows=gb)
-        extra_in = self._variant_inputs(eng, int(getattr(self.config, "seed", 123)),
-                                        int(getattr(self.config, "shard_row_offset", 0) or 0), gb,
-                                        bool(getattr(self.config, "dropout_off", False)))
+        inputs = self._step_inputs(eng, int(getattr(self.config, "shard_row_offset", 0) or 0), gb)
+        ka, kj = inputs.pop("keep_att"), inputs.pop("keep_joint")
         self._step += 1
         self._db, self._keep = db, (ka, kj)
-        eng.forward(db, ka, kj, want_dz=self.is_train, keep_joint2=kj2, **extra_in, **(seeded or {}))
+        eng.forward(db, ka, kj, want_dz=self.is_train, **inputs)
 
         d = eng.dims
         A, R = d.A, d.R
@@ -441,3 +443,35 @@ class Model(object):
         if allreduce is not None:
             allreduce(self._engine.grad_flat)
         self._engine.optimizer_step(learning_rate)
+
+    def train_micro_steps(self, batches, learning_rate, allreduce=None, row_offset=0, global_rows=None):
+        """ONE optimiser step on `batches` together (FusionEngine.train_micro_steps; the Trainer's --accum_steps): the
+        (seed, step) pair of the dropout stream advances once, the batches' rows follow each other in the global batch
+        from row_offset on.  Explicit masks are written while the engine is sized for their batch and kept until the
+        step has used them (the engine reuses one buffer per site); under config.inline_dropout no mask exists.
+        Only the engine is driven: `report`, `losses`, `mid_result`, `output` and `heavy_output` keep what the last build()
+        left (they describe one batch), and `loss` is None -- the step's global-batch values are engine.report() /
+        extra_report() / loss(), which the Trainer reads after it has queued the next batch's upload (under data
+        parallelism they all-reduce the statistics, so asking here would make the step wait)."""
+        from .engine_core import micro_plan
+        eng = self._engine
+        dbs = []
+        for b in batches:
+            self.batch = b
+            dbs.append(self._device_batch())
+        starts, G = micro_plan([int(db["q_intseq"].shape[0]) for db in dbs], row_offset, global_rows)
+        micro = []
+        for db, start in zip(dbs, starts):
+            B, T = (int(x) for x in db["q_intseq"].shape)
+            if (B, T) != (eng.dims.B, eng.dims.T):       # the masks' sizes follow the engine's
+                eng.resize(B, T, G)
+            inputs = {k: v for k, v in self._step_inputs(eng, start, G).items() if v is not None}
+            for k in ("row_offset", "global_rows"):      # the engine places the micro-batches itself
+                inputs.pop(k, None)
+            if len(dbs) > 1:
+                inputs = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in inputs.items()}
+            micro.append(dict(batch=db, **inputs))
+        self._step += 1
+        self._db = dbs[-1]
+        eng.train_micro_steps(micro, learning_rate, allreduce=allreduce, row_offset=row_offset, global_rows=global_rows)
+        self.loss = None

@@ -125,6 +125,10 @@ class Model(object):
                 out[k] = out[k].float()
         if "_dp" in self.batch:               # data parallel: the shard's place in the global batch (Trainer._shard)
             out["_dp"] = self.batch["_dp"]
+        nums = [self.batch.get(k + "_blank_fill/num") for k in PT.KINDS]
+        if all(isinstance(v, np.ndarray) for v in nums):
+            # this batch's valid-entry counts, from the host arrays (train_micro_steps sums them: no read-back on the step)
+            out["_valid"] = tuple(float(np.clip(v, 0, self.data_cfg.n_obj_bf).sum()) for v in nums)
         return out
 
     def prepare(self, batch):
@@ -141,22 +145,24 @@ class Model(object):
         ev.record(self._side)
         return db, ev
 
+    def _adopt(self, prepared):
+        """the device batch of a prepare() handle, once the compute stream may read it"""
+        db, ev = prepared
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        # the tensors were allocated on the side stream: tell the caching allocator that the compute stream uses them
+        # too, so that their blocks are not handed out again (to the next prepare()) while this step still reads them
+        for v in db.values():
+            for t in (v.get("_dev", ()) if isinstance(v, dict) else (v,)):
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(cur)
+        return db
+
     def build(self, prepared=None, defer_report=False):
         """build network architecture and loss (here: run it on self.batch, or on the batch handed to prepare()).
         defer_report: queue the forward only; finish_report() then fetches the 13 scalars (one host sync per step,
         after backward and the update have been queued as well)."""
-        if prepared is None:
-            db = self._device_batch()
-        else:
-            db, ev = prepared
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(ev)
-            # the tensors were allocated on the side stream: tell the caching allocator that the compute stream uses them
-            # too, so that their blocks are not handed out again (to the next prepare()) while this step still reads them
-            for v in db.values():
-                for t in (v.get("_dev", ()) if isinstance(v, dict) else (v,)):
-                    if torch.is_tensor(t) and t.is_cuda:
-                        t.record_stream(cur)
+        db = self._device_batch() if prepared is None else self._adopt(prepared)
         if self._engine is None:
             cfg = self.data_cfg
             # one LayerNorm per shared fc_layer scope (TF 1.x: pretrain.py) unless the config asks for the
@@ -238,3 +244,35 @@ class Model(object):
 
     def apply_gradients(self, learning_rate):
         self._engine.optimizer_step(learning_rate)
+
+    def train_micro_steps(self, prepared, learning_rate, allreduce=None):
+        """ONE optimiser step on the batches of the prepare() handles `prepared` together
+        (PretrainEngine.train_micro_steps; the Trainer's --accum_steps): the (seed, step) pair of the dropout stream advances
+        once and the batches' images follow each other in the global batch.  Data parallel: this rank's images of the N
+        shards follow each other from the sum of the shards' first rows on, in a global batch of the sum of the global image
+        counts, and the valid-entry counts are the sums of the batches' global ones (Trainer._shard) -- no collective.
+        finish_report() then gives the global batch's scalars."""
+        from .engine_core import micro_plan
+        eng = self._engine
+        dbs = [self._adopt(p) for p in prepared]
+        dps = [db.get("_dp") for db in dbs]
+        dp = all(dps)
+        row_offset = sum(d["row_offset"] for d in dps) if dp else 0
+        global_rows = sum(d["global_rows"] for d in dps) if dp else None
+        global_valid = tuple(sum(d["global_valid"][i] for d in dps) for i in range(2)) if dp else None
+        if not dp and len(dbs) > 1 and all("_valid" in db for db in dbs):
+            global_valid = tuple(sum(db["_valid"][i] for db in dbs) for i in range(2))
+        rows = [int((db["image_ft"] if "image_ft" in db else db["image_idx"]).shape[0]) for db in dbs]
+        starts, G = micro_plan(rows, row_offset, global_rows)
+        seed, micro = int(getattr(self.config, "seed", 123)), []
+        for db, B, start in zip(dbs, rows, starts):
+            if getattr(self.config, "dropout_off", False):
+                micro.append(dict(batch=db, masks=None))
+            elif getattr(self.config, "inline_dropout", False):
+                micro.append(dict(batch=db, dropout=(seed, self._step)))
+            else:
+                micro.append(dict(batch=db, masks=eng.make_keep_masks(B, seed, self._step, row_offset=start, global_rows=G)))
+        self._step += 1
+        self._reduce_report, self._report_event = dp, None
+        eng.train_micro_steps(micro, learning_rate, allreduce=allreduce, row_offset=row_offset, global_rows=global_rows,
+                              global_valid=global_valid)

@@ -328,7 +328,7 @@ class PretrainEngine(EngineCore):
         self.n, self.R, self.D, self.H, self.W, self.A = n, R, D, H, W, A
         self.Vq, self.n_ws, self.deterministic = Vq, n_ws, bool(deterministic)
         self.step_count, self.clip_norm = 0, CLIP_NORM
-        self.report = {}
+        self.report, self._micro_report = {}, None
         self.workspace, self.dims = None, None
         self._layout(ln_shared_in(params) if ln_shared is None else bool(ln_shared))
         for k in self.shapes:
@@ -597,6 +597,7 @@ class PretrainEngine(EngineCore):
             elif len(dropout) != 4:
                 raise ValueError("dropout is (seed, step) or (seed, step, row_offset, global_rows)")
         bs, B, L, keep = self._batch_struct(batch, masks)
+        self._micro_report = None     # fetch_report speaks of THIS batch again (train_micro_steps sets it after its last)
         self._ks = self._keep_struct(B, dropout) if dropout is not None else None
         d = _lib.PtDims(B=B, n=self.n, R=self.R, D=self.D, H=self.H, W=self.W, A=self.A, Vq=self.Vq, n_ws=self.n_ws, L=L,
                         flags=self._flags(), keep_att=KEEP_ATT,
@@ -627,7 +628,11 @@ class PretrainEngine(EngineCore):
         valid count (forward(global_valid=...)), so a SUM all-reduce gives what one process on the whole batch reports."""
         import torch.distributed as dist
         nk = len(self.report_keys)
-        r = self.tensor("report")[:nk]
+        mr = getattr(self, "_micro_report", None)
+        # after train_micro_steps: the micro-batches' scalars, summed -- each was divided by the step's global valid counts
+        r = self.tensor("report")[:nk] if mr is None else mr["stats"]
+        group = group if group is not None or mr is None else mr["group"]
+        reduce = reduce or (mr is not None and mr["dp"])
         if reduce and dist.is_initialized() and dist.get_world_size(group) > 1:
             r = r.cpu() if dist.get_backend(group) == "gloo" else r.clone()
             dist.all_reduce(r, op=dist.ReduceOp.SUM, group=group)
@@ -655,6 +660,46 @@ class PretrainEngine(EngineCore):
         the global-batch losses; all ranks then apply the identical update.  dropout: as for forward."""
         self.forward(batch, masks, global_valid=global_valid, dropout=dropout, row_offset=row_offset, global_rows=global_rows)
         self._backward_and_step(lr, allreduce)
+
+    # ------------------------------------------------------------------ micro-batched step (EngineCore.train_micro_steps)
+    # micro[i] = {"batch": ..., "masks": keep-masks of make_keep_masks(B_i, seed, step, row_offset_i, G) | None,
+    #             or "dropout": (seed, step)}; train_micro_steps(..., global_valid=(obj, attr)) as for train_step
+    def _micro_rows(self, m):
+        b = m["batch"]
+        return int(len(b["image_idx"] if "image_idx" in b and "image_ft" not in b else b["image_ft"]))
+
+    def _micro_open(self, micro, G, dp, allreduce, global_valid=None):
+        """The denominators of the masked mean losses are the GLOBAL batch's valid-entry counts: the pre-training step's
+        1/G.  One micro-batch keeps what train_step does with None (the batch's own counts, taken on the device); more
+        than one needs them summed over the micro-batches (and, data parallel, over the ranks) before the first runs.
+        Summing them HERE reads every micro-batch's `num` back (a host synchronisation per micro-batch when the batches are
+        device tensors): a caller that has the host arrays passes global_valid, as the trainer's model does."""
+        if global_valid is None and (len(micro) > 1 or dp):
+            import torch.distributed as dist
+            group = getattr(allreduce, "group", None)
+            cnt = torch.zeros(2, dtype=torch.float64)
+            for m in micro:
+                cnt += torch.stack([torch.as_tensor(m["batch"][k + "_blank_fill/num"]).to(torch.int64).clamp(0, self.n).sum()
+                                    for k in KINDS]).to(torch.float64).cpu()
+            if dp and dist.is_initialized() and dist.get_world_size(group) > 1:
+                if dist.get_backend(group) != "gloo":
+                    cnt = cnt.to(self.device)
+                dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=group)
+            global_valid = tuple(float(v) for v in cnt.cpu())
+        return {"global_valid": global_valid}
+
+    def _micro_forward(self, m, row_offset, G, ctx):
+        if "dropout" in m and m["dropout"] is not None and len(m["dropout"]) != 2:
+            raise ValueError("a micro-batch's dropout is (seed, step): train_micro_steps places its rows in the global batch")
+        self.forward(m["batch"], m.get("masks"), global_valid=ctx["global_valid"], dropout=m.get("dropout"),
+                     row_offset=row_offset, global_rows=G)
+
+    def _micro_stats(self):
+        """this micro-batch's report scalars: sums over its rows already divided by the global valid counts, so they add"""
+        return self.tensor("report")[:len(self.report_keys)].clone()
+
+    def _micro_close(self, ctx):
+        pass
 
     def load_state_dict(self, sd, strict=True):
         """Restores parameters, Adam moments and the step count (beta powers), so a resumed run continues the

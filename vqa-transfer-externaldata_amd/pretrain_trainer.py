@@ -102,6 +102,11 @@ class Trainer(object):
         self.train_average_iter, self.val_average_iter = config.train_average_iter, config.val_average_iter
         self.heavy_summary_step, self.validation_step = config.heavy_summary_step, config.validation_step
         self.checkpoint_step = config.checkpoint_step
+        # --accum_steps N: one optimiser step per N batches; global_step, the schedules of train(), the learning-rate
+        # decay and the checkpoints count optimiser steps
+        self.accum_steps = int(getattr(config, "accum_steps", 1) or 1)
+        if self.accum_steps < 1:
+            raise ValueError("--accum_steps must be at least 1, not %d" % self.accum_steps)
         self._summary_path = os.path.join(self.train_dir, "summaries.jsonl")
         if config.checkpoint is not None:
             # parameters + Adam slots + step count (tf.train.Saver restores the slots and beta powers too)
@@ -142,9 +147,13 @@ class Trainer(object):
         prepared, self._prepared = getattr(self, "_prepared", None), None
         if prepared is None:
             prepared = self.model.prepare(self._next("train"))
-        self.model.build(prepared=prepared, defer_report=True)
-        self.model.backward(reducer=self._allreduce)
-        self.model.apply_gradients(self._lr())
+        if self.accum_steps > 1:       # N batches, one clip + Adam on their summed gradients (PretrainEngine.train_micro_steps)
+            more = [self.model.prepare(self._next("train")) for _ in range(self.accum_steps - 1)]
+            self.model.train_micro_steps([prepared] + more, self._lr(), allreduce=self._allreduce)
+        else:
+            self.model.build(prepared=prepared, defer_report=True)
+            self.model.backward(reducer=self._allreduce)
+            self.model.apply_gradients(self._lr())
         # the GPU is busy with this step: draw the next batch and upload it now (tf.data prefetch of the reference)
         self._prepared = self.model.prepare(self._next("train"))
         self.model.finish_report()
@@ -209,7 +218,8 @@ class Trainer(object):
         if step_time == 0:
             step_time = 0.001
         log_str = "[{:5s} step {:4d} ".format(split, step)
-        log_str += "({:.3f} sec/batch, {:.3f} instances/sec)]\n".format(step_time, self.batch_size / step_time)
+        log_str += "({:.3f} sec/batch, {:.3f} instances/sec)]\n".format(
+            step_time, self.batch_size * (getattr(self, "accum_steps", 1) if is_train else 1) / step_time)
         for key in sorted(avg_report.keys()):
             log_str += "  * {}: {:.5f}\n".format(key, np.array(avg_report[key], dtype=np.float32).mean())
         if self.rank == 0:
@@ -264,6 +274,9 @@ def build_parser():
     parser.add_argument("--inline_dropout", action="store_true", default=False,
                         help="draw the dropout keep bits inside the kernels that consume them instead of writing mask "
                              "buffers first: the same bits, so the same results (not in the reference)")
+    parser.add_argument("--accum_steps", type=int, default=1,
+                        help="batches per optimiser step: their gradients are summed and clipped + applied once, as one "
+                             "batch of accum_steps x batch_size images (not in the reference; steps count optimiser steps)")
     parser.add_argument("--input_workers", type=int, default=4, help="forked batch producers (0: in-process)")
     parser.add_argument("--input_prefetch", type=int, default=2, help="batches assembled ahead of the step")
     return parser

@@ -96,6 +96,11 @@ class Trainer(object):
         self.transfer_vars = self.model.filter_transfer_vars(all_vars)
         log.warning("Filtered train variables: %s", ", ".join(self.train_vars))
         self._allreduce = dp.BucketedAllReduce() if self.world > 1 else None
+        # --accum_steps N: one optimiser step per N batches (FusionEngine.train_micro_steps); every step count below --
+        # global_step, the schedules of train(), the learning-rate decay, checkpoints -- counts optimiser steps
+        self.accum_steps = int(getattr(config, "accum_steps", 1) or 1)
+        if self.accum_steps < 1:
+            raise ValueError("--accum_steps must be at least 1, not %d" % self.accum_steps)
 
         self.train_average_iter = config.train_average_iter
         self.val_average_iter = config.val_average_iter
@@ -176,10 +181,21 @@ class Trainer(object):
     # ------------------------------------------------------------------ steps
     def run_train_step(self, use_heavy_summary):
         _start_time = time.time()
-        self.model.set_batch(self._next("train"))
-        self.model.build()
-        self.model.backward(reducer=self._allreduce)       # buckets reduced while backward still runs
-        self.model.apply_gradients(self._lr())
+        if self.accum_steps > 1:
+            # N batches, one clip + Adam on their summed gradients.  Under data parallelism this rank's rows of the N
+            # shards follow each other in the global batch of sum(n_global) rows, from sum(shard starts) on
+            batches, first_row, rows = [], 0, 0
+            for _ in range(self.accum_steps):
+                batches.append(self._next("train"))
+                first_row += self.config.shard_row_offset
+                rows += self.config.global_batch
+            self.model.train_micro_steps(batches, self._lr(), allreduce=self._allreduce, row_offset=first_row,
+                                         global_rows=rows if self.world > 1 else None)
+        else:
+            self.model.set_batch(self._next("train"))
+            self.model.build()
+            self.model.backward(reducer=self._allreduce)       # buckets reduced while backward still runs
+            self.model.apply_gradients(self._lr())
         # everything above is only ENQUEUED: assemble (and, first epoch, upload) the next batch while the GPU
         # works, and only then wait for this step's report
         gb = self.config.global_batch
@@ -260,7 +276,7 @@ class Trainer(object):
         mean32 = lambda xs: np.asarray(xs, dtype=np.float32).mean()
         per_batch = mean32(avg_step_time) or 0.001
         lines = ["[{:5s} step {:4d} ({:.3f} sec/batch, {:.3f} instances/sec)]".format(
-            split, step, per_batch, self.batch_size / per_batch)]
+            split, step, per_batch, self.batch_size * (getattr(self, "accum_steps", 1) if is_train else 1) / per_batch)]
         lines += ["  * {}: {:.5f}".format(k, mean32(avg_report[k])) for k in sorted(avg_report)]
         text = "\n".join(lines) + "\n"
         (log.info if is_train else log.infov)(text)
@@ -336,6 +352,9 @@ def build_parser():
     parser.add_argument("--inline_dropout", action="store_true", default=False,
                         help="draw the dropout keep bits inside the kernels that consume them instead of writing mask "
                              "buffers first: the same bits, so the same results (not in the reference)")
+    parser.add_argument("--accum_steps", type=int, default=1,
+                        help="batches per optimiser step: their gradients are summed and clipped + applied once, as one "
+                             "batch of accum_steps x batch_size rows (not in the reference; steps count optimiser steps)")
     parser.add_argument("--debug", type=int, default=0, help="0: normal, 1: debug")
     return parser
 
